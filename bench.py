@@ -10,12 +10,17 @@ exists offline).  N>1: every rank holds its own 2^30-byte shard of 
 N-GiB stream (weak scaling); the shards share one code table through an RCCL
 all-gather of the local histograms and land at their global bit offsets.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Invoked plainly with --gpus N > 1 (no WORLD_SIZE in the environment) it starts the N ranks itself -- torch.distributed.run
 as a CHILD process, before this process has imported torch or touched a GPU -- relays rank 0's line and exits with the
 children's status.  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline alone: set-up, W warm-up steps, SETTLE_STEPS more untimed ones, K timed steps, the line.
+--full adds everything else the line has carried: the as-asked region right behind the warm-up (value_cold), the instrumented
+steps behind phase_ms / kernels / roofline, at N = 1 the extra workloads and the CPU baselines, at N > 1 the concatenation,
+the one-GPU comparison step and the cold sharded decode.
 """
 import argparse
 import json
@@ -27,7 +32,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
-SETTLE_STEPS = 200       # untimed steps between the as-asked measurement (value_cold) and the steady-state one (value); see main
+SETTLE_STEPS = 200       # untimed steps between the warm-up (--full: the as-asked value_cold region) and the steady-state region (value); see main
 HBM_COPY_GBPS = 6290.0  # same guide: what a float4 copy reaches (report against both, headline against spec)
 
 
@@ -104,6 +109,35 @@ def load_pmc_traffic(kernel, bytes_per_gpu):
         return None, f"profiles/pmc_latest.json was collected at {meta.get('bytes_per_gpu', 1 << 30)} B per GPU, this run has {bytes_per_gpu}"
     v = d.get(kernel, {}).get("hbm_bytes_per_launch")
     return v, f"profiles/pmc_latest.json (tag {meta.get('tag', 'r03')}; rocprofv3 --pmc passes of this command, not this run)"
+
+
+DUMP_SAMPLE = 1 << 22   # values per dumped array: two float32 arrays of 16 MiB, under the 64 MB a dump may take
+DUMP_SEED = 0x5EED0D0D
+
+
+def dump_positions(length):
+    """Where an array of `length` values is sampled for --dump-outputs: the first 4096 (the .et header and dictionary) and
+    DUMP_SAMPLE - 4096 seeded draws, sorted -- a function of the length alone, so two builds are compared position for position."""
+    import numpy as np
+
+    if length <= DUMP_SAMPLE:
+        return np.arange(length, dtype=np.int64)
+    head = np.arange(4096, dtype=np.int64)
+    rest = np.sort(np.random.default_rng(DUMP_SEED).integers(4096, length, DUMP_SAMPLE - 4096, dtype=np.int64))
+    return np.concatenate([head, rest])
+
+
+def dump_outputs(directory, torch, image, decoded, n):
+    """What the last timed step handed its caller, as float32 .npy files: `encoded` (the .et image, or this rank's part
+    of it), `decoded` (the text decoded back), each sampled at dump_positions(); `sizes` (float64: input bytes, image
+    bytes, decoded symbols)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, t in (("encoded", image), ("decoded", decoded)):
+        pos = torch.from_numpy(dump_positions(t.numel())).to(t.device)
+        np.save(os.path.join(directory, name + ".npy"), t[pos].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(directory, "sizes.npy"), np.array([n, image.numel(), decoded.numel()], dtype=np.float64))
 
 
 def fail(msg):
@@ -292,6 +326,12 @@ def main():
     ap.add_argument("--decode", choices=("cold", "shard"), default="cold",
                     help="N = 1 only: 'shard' decodes the image the way the ranks of an N > 1 step decode their shards (the encode's code table and "
                          "start bit, no header hand-over) -- the N = 1 step an N > 1 value is comparable with; the headline is 'cold'")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: value_cold, phase / kernel / roofline figures, at N = 1 the extra "
+                         "workloads and CPU baselines (--no-extra-workloads / --no-cpu-baseline leave them out), at N > 1 the "
+                         "concatenation, the one-GPU comparison step and the cold sharded decode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's image and decoded text, sampled) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -442,6 +482,8 @@ def main():
     # steps to come back after an idle stretch such as the verification's 0.1 s (the write kernel: 0.59 ms falling to 0.49,
     # rocprofv3 trace).  Both figures are in the line; `value` is the steady state, value_cold the run as the contract
     # words it (same code, same K, only the number of untimed steps before it differs).
+    # A plain run (no --full) leaves out the value_cold region and the instrumented steps: W warm-up steps, SETTLE_STEPS untimed
+    # ones, the K timed steps of `value`.
     # (the harness's own comparison kernels are loaded before the pipeline first runs: the verification below then costs a
     # fraction of a millisecond instead of ~0.1 s of module loading with the GPU idle and its clocks falling)
     torch.equal(dec[:n], text)
@@ -454,33 +496,42 @@ def main():
         fail("round trip is not the identity")
     for _ in range(args.warmup):
         step(False, True)
-    elapsed_cold = timed_region()
-    # the untimed set-up steps: the last K of them carry every phase's events -> phase_ms and the four kernels' figures
-    for _ in range(max(SETTLE_STEPS - args.steps - 8, 0)):
-        step(False, True)
-    timing_mode(all_phases=True)
-    for _ in range(4):
-        step(False, True)
-    zero_phases()
-    for i in range(args.steps):
-        step(True, i == 0)
-    torch.cuda.synchronize()
-    add_decode_timings()
-    instrumented = dict(phases)
-    timing_mode(all_phases=False)
-    for _ in range(4):
-        step(False, True)
+    if args.full:
+        elapsed_cold = timed_region()
+        # the untimed set-up steps: the last K of them carry every phase's events -> phase_ms and the four kernels' figures
+        for _ in range(max(SETTLE_STEPS - args.steps - 8, 0)):
+            step(False, True)
+        timing_mode(all_phases=True)
+        for _ in range(4):
+            step(False, True)
+        zero_phases()
+        for i in range(args.steps):
+            step(True, i == 0)
+        torch.cuda.synchronize()
+        add_decode_timings()
+        instrumented = dict(phases)
+        timing_mode(all_phases=False)
+        for _ in range(4):
+            step(False, True)
+    else:
+        for _ in range(SETTLE_STEPS):  # (the untimed set-up steps alone: `value` is the same steady state as --full's)
+            step(False, True)
     elapsed = timed_region()
     body_ms_timed = phases["dec_body"] / args.steps  # the write kernel's own events, every step of the timed region
-    timing_mode(all_phases=True)  # (the second workload below reports its phases)
     m_bytes = state["layout"]["body_bytes"]  # packed body bytes of this rank's shard (worked out here, off the timed path)
     if verify and not (state["decoded"] == n and torch.equal(dec[:n], text)):
         fail("round trip of the last timed step is not the identity")
+    if args.dump_outputs and rank == 0:
+        r = state["layout"]
+        image = enc[: r["et_len"]] if r["single"] else enc[: (r["end_bit"] + 7) // 8]
+        dump_outputs(args.dump_outputs, torch, image, dec[: state["decoded"]], n)
+    if args.full:
+        timing_mode(all_phases=True)  # (the second workload below reports its phases)
 
     # N > 1: the bit-offset-adjusted concatenation of the shards into ONE image on rank 0 (seam merge + owned
     # words over xGMI), timed on its own after the headline region -- it is not part of `value`.
     concat_ms = seam_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         best = None
         for _ in range(3):
             r = pipe.encode_shard(text, enc, timings=False)
@@ -502,7 +553,7 @@ def main():
     # exchange), the same step -- encode, then the body decoded with the encode's code table -- all ranks at once (each GPU as
     # busy as in the N-GPU step), K steps between barriers, the max over ranks.  scaling_efficiency = value / (N x this).
     n1_same_ms = cold_sharded_ms = None
-    if world > 1 or force_group:
+    if (world > 1 or force_group) and args.full:
         solo = sharded.ShardedCodec(ctx, None, dev)
         torch.cuda.synchronize()
         ctx.enable_timing(False)
@@ -573,7 +624,7 @@ def main():
     # BASELINE.json's other configurations (5.4 MB and 10^8 B of text, 4 GiB of 255 uniform byte values through the exhaustive
     # decode, 16 GiB of 256 for the encode) -- same step, a few repetitions each, reported beside the headline, never instead of it.
     extras = None
-    if world == 1 and not force_group and not args.no_second_workload:
+    if world == 1 and not force_group and not args.no_second_workload and args.full:
         extras = {}
         del text, enc, dec
         text = None
@@ -590,26 +641,6 @@ def main():
 
     if rank == 0:
         K = args.steps
-        ms = {k: v / K for k, v in instrumented.items()}  # per step, over the K instrumented set-up steps
-        kernels = {
-            # name: (ms per launch, algorithmic bytes per launch).  Each of the four kernels carries
-            # its own pair of HIP events on the ctx stream (hipExtLaunchKernelGGL: begin and end of
-            # that dispatch, no marker packets), recorded in every step of the timed region.
-            "k_hist_tiles": (ms["hist"], n),
-            "k_encode_tiles": (ms["enc_body"], n + m_bytes),
-            state["sync_kernel"]: (ms["dec_sync_first"], m_bytes),
-            state["write_kernel"]: (ms["dec_body"], m_bytes + n),
-        }
-        dominant = max(kernels, key=lambda k: kernels[k][0])
-        d_ms, d_bytes = kernels[dominant]
-        in_timed_region = dominant == state["write_kernel"]
-        if in_timed_region:  # (the kernel that carries its events through the timed region; any other: the instrumented steps' figure)
-            d_ms = body_ms_timed
-        achieved = d_bytes / (d_ms * 1e-3) / 1e9
-        traffic, traffic_source = load_pmc_traffic(dominant.split("<")[0], n)
-        # whole encode on the GPU's clock, begin of K1 to end of K4 (enc_scan = everything between the
-        # two: histogram reduce, the host's code construction, tile scan, uploads)
-        enc_kernel_ms = ms["hist"] + ms["enc_scan"] + ms["enc_body"]
         out = {
             "metric": "GB/s encode+decode on 1 GiB text at 1/2/4/8 MI355X; % of HBM read peak",
             ("value" if verify else "value_unverified"): round(world * n / elapsed * K / 1e9, 3),
@@ -617,9 +648,7 @@ def main():
             "n_gpus": world,
             "steps": K,
             "warmup": args.warmup,
-            "value_cold": round(world * n / elapsed_cold * K / 1e9, 3),  # the same K steps right behind the W warm-up steps (no further untimed steps)
-            "ms_per_step_cold": round(elapsed_cold / K * 1e3, 4),
-            "setup_steps": SETTLE_STEPS,  # untimed steps between the value_cold region and the `value` region (host clocks and caches; see main)
+            "setup_steps": SETTLE_STEPS,  # untimed steps between the warm-up (--full: the value_cold region) and the `value` region (host clocks and caches; see main)
             "ms_per_step": round(elapsed / K * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -636,30 +665,55 @@ def main():
                 "value_definition": "text bytes taken through encode+decode per second, all GPUs",
                 "decode": pipe.DECODE_SHARD if (world > 1 or force_group or n1_as_shard) else pipe.DECODE_SINGLE,
             },
-            "encode_GBps": round(world * n / (ms["enc_total"] * 1e-3) / 1e9, 2),
-            "decode_GBps": round(world * n / (ms["dec_total"] * 1e-3) / 1e9, 2),
-            "encode_hbm_frac": round((2 * n + m_bytes) / (enc_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-            "phase_ms": {k: round(v, 4) for k, v in ms.items()},
-            "roofline": {
-                "kernel": dominant,
-                "bound": "hbm",
-                "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                "frac_of_measured_copy": round(achieved / HBM_COPY_GBPS, 4),
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "ms_per_launch": round(d_ms, 4),
-                "algorithmic_bytes_per_launch": d_bytes,
-                "measured": ("HIP events carried by the dispatch, every step of the timed region" if in_timed_region
-                             else f"HIP events carried by the dispatch, the {K} instrumented set-up steps"),
-            },
-            "phase_ms_measured": (f"the last {K} of the {SETTLE_STEPS} untimed set-up steps, every phase carrying HIP events; in the timed regions only "
-                                  f"{state['write_kernel']} does (a dispatch with events costs ~5 us of queue time on either side: ~35 us per step)"),
-            "kernels": {k: {"ms_per_launch": round(v[0], 4), "GBps": round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] else None,
-                            "frac": round(v[1] / (v[0] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if v[0] else None} for k, v in kernels.items()},
         }
+        if args.full:
+            ms = {k: v / K for k, v in instrumented.items()}  # per step, over the K instrumented set-up steps
+            kernels = {
+                # name: (ms per launch, algorithmic bytes per launch).  Each of the four kernels carries
+                # its own pair of HIP events on the ctx stream (hipExtLaunchKernelGGL: begin and end of
+                # that dispatch, no marker packets), recorded in every step of the timed region.
+                "k_hist_tiles": (ms["hist"], n),
+                "k_encode_tiles": (ms["enc_body"], n + m_bytes),
+                state["sync_kernel"]: (ms["dec_sync_first"], m_bytes),
+                state["write_kernel"]: (ms["dec_body"], m_bytes + n),
+            }
+            dominant = max(kernels, key=lambda k: kernels[k][0])
+            d_ms, d_bytes = kernels[dominant]
+            in_timed_region = dominant == state["write_kernel"]
+            if in_timed_region:  # (the kernel that carries its events through the timed region; any other: the instrumented steps' figure)
+                d_ms = body_ms_timed
+            achieved = d_bytes / (d_ms * 1e-3) / 1e9
+            traffic, traffic_source = load_pmc_traffic(dominant.split("<")[0], n)
+            # whole encode on the GPU's clock, begin of K1 to end of K4 (enc_scan = everything between the
+            # two: histogram reduce, the host's code construction, tile scan, uploads)
+            enc_kernel_ms = ms["hist"] + ms["enc_scan"] + ms["enc_body"]
+            out.update({
+                "value_cold": round(world * n / elapsed_cold * K / 1e9, 3),  # the same K steps right behind the W warm-up steps (no further untimed steps)
+                "ms_per_step_cold": round(elapsed_cold / K * 1e3, 4),
+                "encode_GBps": round(world * n / (ms["enc_total"] * 1e-3) / 1e9, 2),
+                "decode_GBps": round(world * n / (ms["dec_total"] * 1e-3) / 1e9, 2),
+                "encode_hbm_frac": round((2 * n + m_bytes) / (enc_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                "phase_ms": {k: round(v, 4) for k, v in ms.items()},
+                "roofline": {
+                    "kernel": dominant,
+                    "bound": "hbm",
+                    "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBPS,
+                    "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                    "frac_of_measured_copy": round(achieved / HBM_COPY_GBPS, 4),
+                    "traffic": traffic,
+                    "traffic_source": traffic_source,
+                    "ms_per_launch": round(d_ms, 4),
+                    "algorithmic_bytes_per_launch": d_bytes,
+                    "measured": ("HIP events carried by the dispatch, every step of the timed region" if in_timed_region
+                                 else f"HIP events carried by the dispatch, the {K} instrumented set-up steps"),
+                },
+                "phase_ms_measured": (f"the last {K} of the {SETTLE_STEPS} untimed set-up steps, every phase carrying HIP events; in the timed regions only "
+                                      f"{state['write_kernel']} does (a dispatch with events costs ~5 us of queue time on either side: ~35 us per step)"),
+                "kernels": {k: {"ms_per_launch": round(v[0], 4), "GBps": round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] else None,
+                                "frac": round(v[1] / (v[0] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if v[0] else None} for k, v in kernels.items()},
+            })
         if concat_ms is not None:
             out["concat_ms"] = round(concat_ms, 4)     # seams merged + every rank's owned words on rank 0's GPU, max over ranks, best of 3
             out["seam_ms"] = None if seam_ms is None else round(seam_ms, 4)
@@ -679,7 +733,7 @@ def main():
                 out["ref_value"] = args.ref_value
         if extras is not None:
             out["workloads"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and not args.no_cpu_baseline and args.full:
             if real_sample is not None:
                 host_text = real_sample
             else:

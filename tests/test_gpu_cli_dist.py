@@ -408,13 +408,13 @@ def test_cli_refuses_files_without_the_magic(tmp_path, res_files):
 
 
 def test_bench_line_has_the_contract_keys():
-    """bench.py as the driver runs it (smaller stream, fewer steps): one JSON line on stdout with the contract's keys,
+    """bench.py --full (smaller stream, fewer steps): one JSON line on stdout with the contract's keys,
     the roofline and CPU-baseline objects, a kernel table that names what a decode really ran, and the second workload."""
     import json
     import sys
 
     env = dict(os.environ, ET_BENCH_BYTES=str(32 << 20))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--cpu-threads", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "2", "--cpu-threads", "4",
                         "--workloads", "enwik-like,text-5M"],  # (the 4 GiB and 16 GiB streams of BASELINE config 5 are the default run's)
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -446,6 +446,42 @@ def test_bench_line_has_the_contract_keys():
     assert d["config"]["decode"].startswith("cold")
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """bench.py without --full, as every change runs it: exactly K timed steps and the headline line, none of --full's
+    figures; --dump-outputs writes the last timed step's .et image and decoded text, sampled at bench.dump_positions(), as
+    float32 under 64 MB -- the image's sample is the oracle's .et at those positions, the text's the input's."""
+    import json
+    import sys
+
+    import torch
+
+    import bench
+    from oracle import oracle as O
+
+    n = 16 << 20
+    out = tmp_path / "out"
+    env = dict(os.environ, ET_BENCH_BYTES=str(n))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["unit"] == "GB/s" and d["dtype"] == "u8" and d["higher_is_better"] is True
+    assert d["verified"] is True and abs(d["value"] - n / (d["ms_per_step"] * 1e-3) / 1e9) < 0.01 * d["value"]
+    for k in ("value_cold", "phase_ms", "kernels", "roofline", "workloads", "cpu_baseline", "cpu_baseline_parallel"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["decoded.npy", "encoded.npy", "sizes.npy"]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+    text = corpus.text_like_torch(n, 0x5EED0004, torch.device("cuda", 0)).cpu().numpy()
+    et = np.frombuffer(O.encode(text), dtype=np.uint8)
+    assert np.load(out / "sizes.npy").tolist() == [n, et.size, n]
+    for name, full in (("encoded", et), ("decoded", text)):
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == np.float32 and got.size == bench.DUMP_SAMPLE
+        assert np.array_equal(got, full[bench.dump_positions(full.size)].astype(np.float32)), name
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher on the command line and no WORLD_SIZE in the environment: bench.py starts
     the two ranks itself (torch.distributed.run as a child process), relays rank 0's one line and exits 0.  Rehearsed on the
@@ -455,7 +491,7 @@ def test_bench_starts_its_own_ranks():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ET_BENCH_BYTES=str(16 << 20), ET_BENCH_DEVICE="0", ET_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--ref-value", "100"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--ref-value", "100"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

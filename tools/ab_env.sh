@@ -1,8 +1,8 @@
 #!/bin/bash
 # A/B runs of bench.py under different environments, one line each.  Usage (through gpurun, from the repo root):
 #   bash tools/ab_env.sh "name1:VAR=1 VAR2=x" "name2:VAR=2" ...      (name "base": no variables)
-# ET_AB_ARGS: extra bench.py arguments (default: --steps 20 --warmup 3 --no-cpu-baseline --no-second-workload)
-ARGS=${ET_AB_ARGS:---steps 20 --warmup 3 --no-cpu-baseline --no-second-workload}
+# ET_AB_ARGS: extra bench.py arguments (default: --full --steps 20 --warmup 3 --no-cpu-baseline --no-second-workload)
+ARGS=${ET_AB_ARGS:---full --steps 20 --warmup 3 --no-cpu-baseline --no-second-workload}
 for spec in "$@"; do
   name=${spec%%:*}; vars=${spec#*:}; [ "$vars" = "$spec" ] && vars=""
   env $vars timeout -k 10 300 python bench.py $ARGS > gpurun_out/ab_$name.json 2> gpurun_out/ab_$name.err || { echo "$name FAILED"; tail -5 gpurun_out/ab_$name.err; exit 1; }

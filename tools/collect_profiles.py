@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""gpurun_out/ (tools/refresh_profiles.sh <tag>) -> profiles/<tag>_*: the bench line, the
+"""What tools/refresh_profiles.sh <tag> wrote -> profiles/<tag>_*: the bench line (from $OUT, default bench_out/), the
 rocprofv3 kernel-stats summary of the same command (et:: kernels first), the PMC summary."""
-import csv, glob, json, shutil, subprocess, sys
+import csv, glob, json, os, shutil, subprocess, sys
 
 tag = sys.argv[1]
-shutil.copy(f"gpurun_out/{tag}_bench.json", f"profiles/{tag}_bench.json")
+shutil.copy(os.path.join(os.environ.get("OUT", "bench_out"), f"{tag}_bench.json"), f"profiles/{tag}_bench.json")
 shutil.copy(f"gpurun_out/{tag}_bench_under_rocprof.json", f"profiles/{tag}_bench_under_rocprof.json")
 src = glob.glob(f"gpurun_out/prof_{tag}/**/*kernel_stats.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(src)))
