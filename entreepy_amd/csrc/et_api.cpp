@@ -39,6 +39,13 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// A range of a stream split over GPUs (et_decode_range_*): its words, bytes (those after it included) and subsequences (not).
+struct RangeGeometry {
+    const uint32_t *words;
+    uint64_t n_bytes, n_subs;
+    uint32_t n_blocks;
+};
+
 constexpr size_t HEADER_STAGE = 8192;  // >= 4631-byte worst-case header, padded
 constexpr size_t SUB_TABLE_ONLY = (static_cast<size_t>(et::DEC_SUB_TABLES_MAX) << et::DEC_SUB_BITS_MAX) * sizeof(uint16_t) + 64;
 constexpr size_t SUB_TABLE_BYTES = SUB_TABLE_ONLY + 256;
@@ -110,9 +117,9 @@ struct et_ctx {
     // et_decode_range_sync -> et_decode_range_write
     struct {
         bool valid = false;
-        const uint32_t *words = nullptr;
-        uint64_t n_bytes = 0, n_subs = 0, total = 0;
-        uint32_t n_blocks = 0, flags = 0;
+        RangeGeometry g = {};
+        uint64_t total = 0;
+        uint32_t flags = 0;
         et::DecodeTables tb = {}, tb_write = {};
         bool tw = false;  // synchronised by tree walk: the write goes over the chained tables (n_chain entries in ctx->chain_table)
         uint32_t n_chain = 0, max_len = 0;
@@ -792,6 +799,21 @@ extern "C" int et_device_to_fd(et_ctx *ctx, const void *d_src, size_t len, int f
 // ---------------------------------------------------------------------------------
 namespace {
 
+// The switches that overrule the decode's choices, each ET_<NAME>=1 (A/B runs, and the tests that pin the paths
+// behind them, in child processes), read once per process.  Value-initialised: the choices as they are.
+struct DecodeSwitches {
+    bool no_quick_sync, quick_sync_always, no_fixed_sync, no_fixed_write, no_row_sync, no_row_write, no_strips, dec_tables_host;
+};
+
+const DecodeSwitches &decode_switches() {
+    static const DecodeSwitches sw = [] {
+        auto on = [](const char *name) { const char *e = std::getenv(name); return e && e[0] == '1'; };
+        return DecodeSwitches{on("ET_NO_QUICK_SYNC"), on("ET_QUICK_SYNC_ALWAYS"), on("ET_NO_FIXED_SYNC"), on("ET_NO_FIXED_WRITE"),
+                              on("ET_NO_ROW_SYNC"),   on("ET_NO_ROW_WRITE"),      on("ET_NO_STRIPS"),     on("ET_DEC_TABLES_HOST")};
+    }();
+    return sw;
+}
+
 // Build the decode tables on the host and upload them (one pinned block, one device block,
 // one copy): the step tables of the register-window kernels (k_dec_sync_reg: index
 // step_bits, symbol-free; k_dec_write_reg: index lut_bits_write, two symbols) and ONE set of
@@ -820,7 +842,7 @@ int prepare_decode_tables(et_ctx *ctx, const et_codebook *cb, et::DecodeTables *
     // the host can fill this one while the stream is still busy with whatever precedes this decode.
     const int turn = ctx->lut_turn ^= 1;
     ctx->h_lut = ctx->h_lut_buf[turn];
-    static const bool on_host = [] { const char *e = std::getenv("ET_DEC_TABLES_HOST"); return e && e[0] == '1'; }();  // the host builders instead of k_build_dec_tables (they are what the device's tables are tested against)
+    const bool on_host = decode_switches().dec_tables_host;  // (the host builders are what the device's tables are tested against)
     HostDecodeTables ht, hw;
     uint32_t *h_lut_w = ctx->h_lut + (1u << et::DEC_LUT_BITS_MAX);
     uint32_t *h_long = ctx->h_lut + (2u << et::DEC_LUT_BITS_MAX), *h_long_w = h_long + 512;
@@ -999,19 +1021,306 @@ extern "C" int et_row_code(const et_codebook *cb, uint32_t *t) {
     return ET_OK;
 }
 
-// Which way a one-GPU decode of a whole stream goes for this code table, before it has seen the stream (et_decode_body_device makes
-// the same choices in the same order -- tests/test_gpu_fixedsync.py holds the two against each other; the switches ET_NO_* aside).
+namespace {
+
+// The decode families.  The first two are sweeps that may give up on a stream (it then goes to the plan's fallback); the
+// others synchronise whatever the stream, or (FIXED_WRITE) need not.
+enum class Family { TREE_WALK, WINDOWS, ROWS, FIXED_SYNC, FIXED_WRITE, EXIT_MAPS };
+
+bool is_sweep(Family f) { return f == Family::TREE_WALK || f == Family::WINDOWS; }
+
+struct DecodePlan {
+    Family first;          // what starts the decode
+    Family fallback;       // where a first sweep whose blocks give up goes: ROWS or EXIT_MAPS
+    bool full_tree;        // the code as a tree with a leaf for every codeword and none more (an encoder's)
+    et::RowCode row_code;  // for ROWS
+    bool row_write;        // ROWS written by rows (else over the chained tables)
+    bool strips;           // the chained-table write may take its strips instantiation
+};
+
+// Which way a one-GPU decode of a whole stream goes for this code table and its tree (nullptr: none), before it has seen the stream.
+DecodePlan plan_decode(const et_codebook *cb, const et::TwTree *tree, const DecodeSwitches &sw) {
+    DecodePlan p{};
+    p.full_tree = tree && tree->n_int + 1 == cb->n_coded;
+    // Fixed-length codes (2^L codewords of L bits, so L <= 8: two, four, 16, 64 symbols of about equal weight): where the codewords
+    // begin is arithmetic, and so is where symbol i lies -- the write alone (k_fixed_write), no synchronisation, no scan, no tables.
+    const bool fixed = p.full_tree && !sw.no_fixed_sync && cb->n_coded >= 2 && cb->min_length == cb->max_length;
+    // Uniform-like bytes (complete codes of 7 and 8 bits, BASELINE's worst case): one pass by rows and columns (et_rowsync.h)
+    // instead of the exit maps for every start offset.
+    const bool rows = tree && !fixed && !sw.no_row_sync && et::row_code_of(cb, &p.row_code);
+    // A (nearly) fixed-length code has little to re-synchronise on: unless its mix of L- and (L + 1)-bit codewords says otherwise
+    // (et::quick_to_synchronise), do not even try.
+    const bool near_fixed = cb->max_length <= cb->min_length + 1 && cb->n_coded > 2 && !sw.quick_sync_always && (sw.no_quick_sync || !et::quick_to_synchronise(cb));
+    p.fallback = rows ? Family::ROWS : Family::EXIT_MAPS;
+    if (fixed) p.first = sw.no_fixed_write ? Family::FIXED_SYNC : Family::FIXED_WRITE;
+    else if (near_fixed) p.first = p.fallback;
+    else p.first = tree ? Family::TREE_WALK : Family::WINDOWS;
+    p.row_write = !sw.no_row_write;
+    p.strips = !sw.no_strips;
+    return p;
+}
+
+// The workspaces every synchronisation writes: each lane's state, each block's exit and count, the scan's offsets and group
+// sums, the flags.
+int ensure_dec_ws(et_ctx *ctx, uint64_t n_subs, uint32_t n_blocks) {
+    ET_TRY(ensure(ctx, ctx->sub_state, n_subs * sizeof(uint32_t)));
+    ET_TRY(ensure(ctx, ctx->blk_exit, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
+    ET_TRY(ensure(ctx, ctx->blk_count, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
+    ET_TRY(ensure(ctx, ctx->blk_off, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint64_t)));
+    ET_TRY(ensure(ctx, ctx->group_sum, (static_cast<size_t>(n_blocks) / 1024 + 2) * sizeof(uint64_t)));
+    ET_TRY(ensure(ctx, ctx->flag, 64));
+    return ET_OK;
+}
+
+// ... as the kernels take them
+struct DecWs {
+    uint32_t *sub_state, *blk_exit, *blk_count, *flag, *worklist;
+    unsigned long long *blk_off, *group_sum;
+};
+
+DecWs dec_ws(const et_ctx *ctx) {
+    return DecWs{static_cast<uint32_t *>(ctx->sub_state.p), static_cast<uint32_t *>(ctx->blk_exit.p), static_cast<uint32_t *>(ctx->blk_count.p),
+                 static_cast<uint32_t *>(ctx->flag.p), static_cast<uint32_t *>(ctx->worklist.p), static_cast<unsigned long long *>(ctx->blk_off.p),
+                 static_cast<unsigned long long *>(ctx->group_sum.p)};
+}
+
+// The exit maps' workspaces (et_kernels_fallback.hip): a map of the L = max_length start offsets per lane, block and group of 256 blocks.
+uint32_t map_stride(uint32_t n_starts) { return n_starts <= 8 ? 8 : (n_starts <= 16 ? 16 : 32); }
+
+int ensure_maps_ws(et_ctx *ctx, uint64_t n_subs, uint32_t n_blocks, uint32_t stride) {
+    const size_t n_groups = (static_cast<size_t>(n_blocks) + 255) / 256;
+    ET_TRY(ensure(ctx, ctx->lane_maps, n_subs * stride + 64));
+    ET_TRY(ensure(ctx, ctx->blk_maps, static_cast<size_t>(n_blocks) * 32 + 64));
+    ET_TRY(ensure(ctx, ctx->grp_maps, n_groups * 32 + 64));
+    ET_TRY(ensure(ctx, ctx->blk_in, static_cast<size_t>(n_blocks) + 64));
+    ET_TRY(ensure(ctx, ctx->grp_in, n_groups + 64));
+    return ET_OK;
+}
+
+// One whole-stream decode (et_decode_body_device), as its stages share it.
+struct BodyDecode : DecWs {
+    et_ctx *ctx;
+    const et_codebook *cb;
+    uint8_t *out;  // cap bytes
+    size_t cap;
+    uint64_t n_symbols, n_bytes, n_subs;
+    const uint32_t *words;  // the stream from its 4-byte aligned base (n_bytes, n_subs: measured from there)
+    uint32_t first_bit, n_blocks;
+    uint32_t *h_flags, *blk_start;  // h_flags: the host copy of flag[0..15]
+    float host_ms;
+    et::TwUpload *h_up;  // the code as a tree (one of the pinned blocks; nullptr: none)
+    DecodePlan plan;
+    Family family;  // what runs now: plan.first, then plan.fallback if a first sweep gives up
+    et::DecodeTables tb, tb_write;
+    const uint16_t *tw_table;
+    const uint64_t *chain;  // the chained write tables (nullptr: the window tables')
+    uint32_t tw_n_int, n_chain, iters;
+    bool flags_zeroed, more_sweeps, wrote, write_ticket_zero;
+    bool strips;  // the write whose output is kept took the strips instantiation
+};
+
+// The tree (if the code is one: an encoder's always is) and the plan; the window kernels' tables up front for the families that start
+// on them (their building kernel clears the flags on its way).  The host time a decode reports is this.  Then the tree walk's table (for
+// its sweeps) and the chained write tables, both filled by ONE small launch that reads tree and plan from the pinned block itself.
+int body_setup(BodyDecode &d) {
+    et_ctx *ctx = d.ctx;
+    const double t0 = now_ms();
+    d.h_up = ctx->h_tw_tree[ctx->tw_turn ^= 1];  // two pinned blocks in turn, as prepare_decode_tables' (this call waits for its flags before it returns)
+    if (et::tw_build_tree(d.cb, &d.h_up->tree, true) != ET_OK) d.h_up = nullptr;  // (bit patterns without a symbol become leaves that decode as byte 0)
+    d.plan = plan_decode(d.cb, d.h_up ? &d.h_up->tree : nullptr, decode_switches());
+    d.family = d.plan.first;
+    if (d.family == Family::WINDOWS || d.family == Family::EXIT_MAPS) ET_TRY(prepare_decode_tables(ctx, d.cb, &d.tb, &d.tb_write, d.flag, &d.flags_zeroed));
+    d.host_ms = static_cast<float>(now_ms() - t0);
+    if (!d.h_up || d.family == Family::FIXED_WRITE) return ET_OK;
+    const bool sweeps = d.family == Family::TREE_WALK;
+    et::tw_chain_plan(&d.h_up->tree, &d.h_up->plan);
+    ET_TRY(ensure(ctx, ctx->tw_tree, sizeof(et::TwUpload)));
+    ET_TRY(ensure(ctx, ctx->chain_table, static_cast<size_t>(et::CH_MAX_ENTRIES) * sizeof(uint64_t)));
+    if (sweeps) {
+        ET_TRY(ensure(ctx, ctx->tw_table, static_cast<size_t>(et::tw_table_entries(et::TW_MAX_NODES)) * sizeof(uint16_t) + 64));
+        ET_TRY(ensure(ctx, ctx->blk_start, static_cast<size_t>(d.n_blocks) * sizeof(uint32_t)));
+        ET_TRY(ensure(ctx, ctx->blk_pub, static_cast<size_t>(d.n_blocks) * sizeof(uint32_t)));
+    }
+    d.tw_n_int = d.h_up->tree.n_int;
+    d.n_chain = d.h_up->plan.n_entries;
+    const bool zero_here = !d.flags_zeroed && d.family != Family::EXIT_MAPS;
+    et::launch_tw_build(ctx->stream, d.h_up, static_cast<uint32_t>(et::tw_upload_bytes(d.h_up)), d.tw_n_int, sweeps ? static_cast<uint16_t *>(ctx->tw_table.p) : nullptr,
+                        d.n_chain, static_cast<uint64_t *>(ctx->chain_table.p), zero_here ? d.flag : nullptr, sweeps ? static_cast<uint32_t *>(ctx->blk_pub.p) : nullptr, d.n_blocks);
+    d.flags_zeroed = d.flags_zeroed || zero_here;
+    d.chain = static_cast<const uint64_t *>(ctx->chain_table.p);
+    if (sweeps) {
+        d.tw_table = static_cast<const uint16_t *>(ctx->tw_table.p);
+        d.blk_start = static_cast<uint32_t *>(ctx->blk_start.p);
+    }
+    return ET_OK;
+}
+
+// D2, the scan of the blocks' symbol counts; its last thread stores the flags and the total into the pinned h_flags and then the
+// launch's epoch into word 14, which the host waits for (wait_report).  first: behind the first sweep, whose block starts (tree walk)
+// or lane states (windows) it verifies.
+int wait_report(BodyDecode &d) { return wait_for_word<uint32_t>(d.ctx, d.h_flags + 14, d.ctx->report_epoch, 200.0, "the decode's report never reached the host"); }
+
+int body_scan(BodyDecode &d, bool first) {
+    et_ctx *ctx = d.ctx;
+    const bool tw = first && d.tw_table;
+    et::launch_dec_scan(ctx->stream, d.blk_count, d.n_blocks, d.group_sum, scan_epoch(ctx), d.blk_off, reinterpret_cast<unsigned long long *>(d.flag + 12),
+                        tw ? d.blk_start : (first ? d.sub_state : nullptr), d.blk_exit, d.flag + 2, tw ? 0u : d.first_bit, d.flag, d.h_flags, tw, ++ctx->report_epoch);
+    ET_HIP(hipGetLastError());
+    return ET_OK;
+}
+
+// D3.  speculative: the kernel itself looks at the sweeps' flags and does nothing if the state is not final.
+int write_symbols(BodyDecode &d, uint64_t clamp, bool speculative) {
+    et_ctx *ctx = d.ctx;
+    const et::KernelEvents ev = timed_body(ctx, EV_DEC + 2, EV_DEC + 3);
+    d.strips = false;
+    if (d.family == Family::ROWS && d.plan.row_write) {  // by rows (et_rowsync.h): no table chain, no bank conflicts between the lanes' regions
+        et::launch_row_write(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.plan.row_code, d.cb, d.sub_state, d.blk_off, clamp, d.out, ev.start, ev.stop);
+    } else if (d.family == Family::FIXED_WRITE) {  // symbol i is the L bits at first_bit + i L (et_rowsync.h): no walk, no state
+        et::launch_fixed_write(ctx->stream, d.words, d.n_bytes, d.first_bit, d.cb, clamp, d.out, ev.start, ev.stop);
+    } else {
+        // More than 128 symbols per 256-bit subsequence (the header says how many symbols the body's bits hold): a quarter's output is three or more
+        // windows of the write's 4 KiB stage, i.e. it would be walked three or more times -- the instantiation that walks it once, into strips
+        // (measured: +45 % at 140 symbols per subsequence, +75 % at 200; at 90-110, two windows, the strips' scattered stores cost what they save).
+        d.strips = d.plan.strips && d.chain && d.n_symbols / 128 > d.n_subs;
+        et::launch_dec_write(ctx->stream, d.words, d.n_bytes, d.n_subs, d.tb_write, d.sub_state, d.blk_off, clamp, d.out, d.flag + 5, &ctx->side,
+                             d.write_ticket_zero, speculative ? d.flag : nullptr, ev, d.chain, d.n_chain, d.cb->max_length, d.strips);
+        d.write_ticket_zero = false;
+    }
+    ET_HIP(hipGetLastError());
+    return ET_OK;
+}
+
+// D1 and D2 for the sweep families.  Sweep 0 runs in and repairs inside each block; (the windows') sweep 1 repairs across blocks
+// (on text ~0.4 % of the block boundaries); the scan that follows also verifies that every block starts where its predecessor ends
+// (the "sweep that changes nothing").  Everything up to the write kernel is enqueued without waiting, the speculative write
+// included; the flags and the total reach the host with ONE wait, and only if they say so -- blocks that gave up: the plan's
+// fallback; verification failed: more sweeps -- is the tail redone.  Device words: flag[0] sweep-1 changed, [1] blocks that gave
+// up, [2] verification failed, [4] / [5] tickets of D1 / D3, [8] worklist count, [12..13] symbol total.
+int body_first_sweep(BodyDecode &d) {
+    if (!is_sweep(d.family)) return ET_OK;
+    et_ctx *ctx = d.ctx;
+    const et::SideLane *side = &ctx->side;  // the first/last blocks' small launches run beside the large kernels (2.3 % at 1 GiB)
+    if (!d.flags_zeroed) ET_HIP(hipMemsetAsync(d.flag, 0, 16 * sizeof(uint32_t), ctx->stream));
+    d.write_ticket_zero = true;
+    if (d.tw_table) {
+        // ONE sweep: the blocks run in, settle inside and then with the block before them (k_tw_sync's blk_pub); what
+        // that leaves open -- a block that did not re-synchronise within its 8 KiB -- the verification finds
+        et::launch_tw_sync(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.tw_table, d.tw_n_int, d.sub_state, d.blk_exit, d.blk_start, d.blk_count, d.flag,
+                           et::DEC_FIRST_SWEEP_TRIPS, nullptr, nullptr, timed(ctx, EV_DEC + 0, EV_DEC + 5), static_cast<uint32_t *>(ctx->blk_pub.p));
+    } else {
+        et::launch_dec_sync(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.tb, 0, et::DEC_FIRST_SWEEP_TRIPS, d.sub_state, d.blk_exit, d.blk_count, d.flag,
+                            d.flag + 4, et::DEC_HAVE_START, nullptr, nullptr, side, true, timed(ctx, EV_DEC + 0, EV_DEC + 5));
+        et::launch_dec_sync(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.tb, 1, et::DEC_REPAIR_SWEEP_TRIPS, d.sub_state, d.blk_exit, d.blk_count, d.flag,
+                            d.flag + 4, et::DEC_HAVE_START, d.worklist, d.flag + 8, side);
+    }
+    ET_HIP(hipGetLastError());
+    d.iters = d.tw_table ? 2 : 3;  // run-in sweep, (repair sweep,) verification
+    ET_TRY(body_scan(d, true));
+    if (d.cap >= d.n_symbols) {
+        ET_TRY(write_symbols(d, d.n_symbols, true));
+        d.wrote = true;
+    }
+    ET_TRY(wait_report(d));  // not the stream: the write kernel keeps running while the caller moves on
+    const bool gave_up = static_cast<uint64_t>(d.h_flags[1]) * 64 > d.n_blocks;
+    if (gave_up) d.family = d.plan.fallback;
+    d.more_sweeps = !gave_up && d.h_flags[2] != 0;
+    if (!et::dec_state_final(d.h_flags[1], d.h_flags[2], d.n_blocks)) d.wrote = d.strips = false;  // the speculative launch declined by the same rule
+    return ET_OK;
+}
+
+// The families that synchronise whatever the stream: the row walk, k_fixed_sync (k_fixed_write needs nothing), the exit maps.
+// Where no first sweep carried the decode's first events, two plain markers stand in front of them.
+int body_exhaustive(BodyDecode &d) {
+    if (is_sweep(d.family)) return ET_OK;
+    et_ctx *ctx = d.ctx;
+    if (d.iters == 0) {
+        record(ctx, EV_DEC + 0);
+        record(ctx, EV_DEC + 5);
+    }
+    if (d.family == Family::ROWS) {
+        ET_TRY(ensure(ctx, ctx->row_scratch, et::row_sync_scratch_bytes(d.n_blocks)));
+        et::launch_row_sync(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.plan.row_code, ctx->row_scratch.p, d.flag + 3, d.sub_state, d.blk_exit, d.blk_count);
+        d.iters += 1;
+    } else if (d.family == Family::FIXED_SYNC) {
+        et::launch_fixed_sync(ctx->stream, d.n_bytes, d.first_bit, d.n_subs, d.cb->max_length, d.sub_state, d.blk_exit, d.blk_count);
+        d.iters += 1;
+    } else if (d.family == Family::EXIT_MAPS) {
+        if (d.plan.first == Family::TREE_WALK) ET_TRY(prepare_decode_tables(ctx, d.cb, &d.tb, &d.tb_write));  // (the others built them up front)
+        // The exhaustive kernels count with the older lookup tables, for which a bit pattern without a symbol is passed
+        // over bit by bit; in the chained tables it is a leaf that decodes as byte 0.  The two agree on every stream of a
+        // FULL tree (an encoder's) -- for a completed one the write has to count like the synchronisation did.
+        if (!d.plan.full_tree) d.chain = nullptr;
+        const uint32_t n_starts = d.cb->max_length, stride = map_stride(n_starts);
+        ET_TRY(ensure_maps_ws(ctx, d.n_subs, d.n_blocks, stride));
+        et::launch_dec_exhaustive(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.tb, n_starts, stride, static_cast<uint8_t *>(ctx->lane_maps.p),
+                                  static_cast<uint8_t *>(ctx->blk_maps.p), static_cast<uint8_t *>(ctx->grp_maps.p), static_cast<uint8_t *>(ctx->blk_in.p),
+                                  static_cast<uint8_t *>(ctx->grp_in.p), d.sub_state, d.blk_exit, d.blk_count);
+        d.iters += 5;
+    }
+    ET_HIP(hipGetLastError());
+    return ET_OK;
+}
+
+// Repair sweeps over the blocks whose start their predecessor's exit contradicts, until one changes nothing.
+int body_repair(BodyDecode &d) {
+    if (!d.more_sweeps) return ET_OK;
+    et_ctx *ctx = d.ctx;
+    for (;;) {
+        ET_HIP(hipMemsetAsync(d.flag, 0, sizeof(uint32_t), ctx->stream));
+        ET_HIP(hipMemsetAsync(d.flag + 8, 0, sizeof(uint32_t), ctx->stream));
+        if (d.tw_table) {
+            et::launch_tw_check(ctx->stream, d.blk_start, d.blk_exit, d.n_blocks, d.worklist, d.flag + 8);
+            et::launch_tw_sync(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.tw_table, d.tw_n_int, d.sub_state, d.blk_exit, d.blk_start, d.blk_count, d.flag,
+                               0xffffffffu, d.worklist, d.flag + 8);
+        } else {
+            et::launch_dec_sync(ctx->stream, d.words, d.n_bytes, d.first_bit, d.n_subs, d.tb, d.iters, 0xffffffffu, d.sub_state, d.blk_exit, d.blk_count, d.flag, d.flag + 4,
+                                et::DEC_HAVE_START, d.worklist, d.flag + 8);
+        }
+        ET_HIP(hipGetLastError());
+        ++d.iters;
+        ET_HIP(hipMemcpyAsync(d.h_flags, d.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ET_HIP(hipStreamSynchronize(ctx->stream));
+        if (d.h_flags[0] == 0) return ET_OK;
+        if (d.iters > d.n_blocks + 4) return fail(ctx, ET_ERR_HIP, "decode synchronisation did not converge");
+    }
+}
+
+// The scan behind the exhaustive families and the repair sweeps (k_fixed_write has nothing to scan).
+int body_final_scan(BodyDecode &d) {
+    if ((is_sweep(d.family) && !d.more_sweeps) || d.family == Family::FIXED_WRITE) return ET_OK;
+    ET_TRY(body_scan(d, false));
+    ET_TRY(wait_report(d));
+    if (d.family == Family::ROWS && d.h_flags[3] != 0) return fail(d.ctx, ET_ERR_HIP, "the row walk's chunks never saw the chunks before them");
+    return ET_OK;
+}
+
+// What et_last_timings reports; the events' arithmetic waits for the first call that asks.
+void body_timings(const BodyDecode &d) {
+    et_ctx *ctx = d.ctx;
+    if (!ctx->timing && !ctx->timing_body) return;
+    const bool fixed = d.plan.first == Family::FIXED_SYNC || d.plan.first == Family::FIXED_WRITE;
+    ctx->tm_dec = et_timings{};
+    ctx->tm_dec.host_ms = d.host_ms;
+    ctx->tm_dec.sync_iters = d.iters;
+    ctx->tm_dec.reserved = (is_sweep(d.family) ? 0u : 1u) | (d.tw_table ? 2u : 0u) | (d.chain ? 4u : 0u) | (d.family == Family::ROWS ? 8u : 0u) |
+                           (fixed ? 16u : 0u) | (d.strips ? 32u : 0u);
+    ctx->pend_dec = true;
+    ctx->pend_dec_first = is_sweep(d.plan.first);
+    ctx->last_kind = 1;
+}
+
+}  // namespace
+
+// Which way a one-GPU decode of a whole stream goes for this code table (the ET_NO_* switches aside).
 extern "C" int et_decode_path(const et_codebook *cb, uint32_t *path) {
     if (!cb || !path) return ET_ERR_ARG;
     if (cb->n_coded == 0) return ET_ERR_ARG;
     if (cb->max_length > 32) return ET_ERR_UNSUPPORTED;
     et::TwTree tree;
     const bool have_tree = et::tw_build_tree(cb, &tree, true) == ET_OK;
-    et::RowCode rc{};
-    if (!have_tree) *path = ET_PATH_WINDOWS;
-    else if (cb->n_coded >= 2 && cb->min_length == cb->max_length && tree.n_int + 1 == cb->n_coded) *path = ET_PATH_FIXED;
-    else if (!(cb->max_length <= cb->min_length + 1 && cb->n_coded > 2) || et::quick_to_synchronise(cb)) *path = ET_PATH_TREE_WALK;
-    else *path = et::row_code_of(cb, &rc) ? ET_PATH_ROWS : ET_PATH_EXIT_MAPS;
+    static const uint32_t path_of[] = {ET_PATH_TREE_WALK, ET_PATH_WINDOWS, ET_PATH_ROWS, ET_PATH_FIXED, ET_PATH_FIXED, ET_PATH_EXIT_MAPS};  // by Family
+    *path = path_of[static_cast<int>(plan_decode(cb, have_tree ? &tree : nullptr, DecodeSwitches{}).first)];
     return ET_OK;
 }
 
@@ -1026,497 +1335,218 @@ extern "C" int et_decode_body_device(et_ctx *ctx, const et_codebook *cb, const v
     if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(ctx, ET_ERR_ARG, "d_out must be 16-byte aligned");
     DeviceGuard guard(ctx->device);
 
+    BodyDecode d{};
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_body);
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
-    const uint32_t first_bit = static_cast<uint32_t>(a & 3) * 8 + start_bit;
-    const uint64_t n_bytes = (a & 3) + body_bytes;  // stream bytes measured from the aligned base
-    const uint64_t n_subs = (n_bytes * 8 + et::SUB_BITS - 1) / et::SUB_BITS;
-    const uint64_t n_blocks64 = (n_subs + et::BLOCK - 1) / et::BLOCK;
+    d.words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
+    d.first_bit = static_cast<uint32_t>(a & 3) * 8 + start_bit;
+    d.n_bytes = (a & 3) + body_bytes;  // stream bytes measured from the aligned base
+    d.n_subs = (d.n_bytes * 8 + et::SUB_BITS - 1) / et::SUB_BITS;
+    const uint64_t n_blocks64 = (d.n_subs + et::BLOCK - 1) / et::BLOCK;
     if (n_blocks64 > 0x7fffffffull) return fail(ctx, ET_ERR_ARG, "body too large");
-    const uint32_t n_blocks = static_cast<uint32_t>(n_blocks64);
-
-    ET_TRY(ensure(ctx, ctx->sub_state, n_subs * sizeof(uint32_t)));
-    ET_TRY(ensure(ctx, ctx->blk_exit, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-    ET_TRY(ensure(ctx, ctx->blk_count, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-    ET_TRY(ensure(ctx, ctx->blk_off, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint64_t)));
-    ET_TRY(ensure(ctx, ctx->worklist, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint32_t)));
-
+    d.n_blocks = static_cast<uint32_t>(n_blocks64);
+    ET_TRY(ensure_dec_ws(ctx, d.n_subs, d.n_blocks));
+    ET_TRY(ensure(ctx, ctx->worklist, (static_cast<size_t>(d.n_blocks) + 1) * sizeof(uint32_t)));
     ctx->range.valid = false;  // shares the workspaces
-    const double t0 = now_ms();
-    // Which tables this decode needs.  A full code tree (an encoder's always is), whatever the stream's size: the
-    // tree walk's table and the chained write tables (et_treewalk.h), both filled by ONE small launch
-    // from the tree -- the lookup tables of the LDS-window / register-window kernels are then built only if the
-    // stream turns out to need them (it does not synchronise: exhaustive path).  Otherwise those, up front.
-    et::DecodeTables tb{}, tb_write{};
-    ET_TRY(ensure(ctx, ctx->flag, 64));
-    bool flags_zeroed = false, have_tables = false;
-    auto need_tables = [&](bool zero_flags) -> int {
-        if (have_tables) return ET_OK;
-        have_tables = true;
-        return prepare_decode_tables(ctx, cb, &tb, &tb_write, zero_flags ? static_cast<uint32_t *>(ctx->flag.p) : nullptr, zero_flags ? &flags_zeroed : nullptr);
-    };
-    // A (nearly) fixed-length code has little to re-synchronise on: unless its mix of L- and (L + 1)-bit codewords says otherwise
-    // (et::quick_to_synchronise; the sweep's own verdict still decides: blocks that gave up -> the exit maps), do not even try.
-    static const bool quick_off = [] { const char *e = std::getenv("ET_NO_QUICK_SYNC"); return e && e[0] == '1'; }();  // (A/B and the tests of the paths behind it)
-    static const bool quick_always = [] { const char *e = std::getenv("ET_QUICK_SYNC_ALWAYS"); return e && e[0] == '1'; }();  // (tools/probe/ab_flat_rule.sh: where does the tree walk stop settling?)
-    const bool near_fixed = cb->max_length <= cb->min_length + 1 && cb->n_coded > 2 && !quick_always && (quick_off || !et::quick_to_synchronise(cb));
-    bool exhaustive = near_fixed;
-    et::TwUpload *h_up = nullptr;
-    {
-        h_up = ctx->h_tw_tree[ctx->tw_turn ^= 1];  // two pinned blocks in turn, as prepare_decode_tables' (this call waits for its flags before it returns)
-        if (et::tw_build_tree(cb, &h_up->tree, true) != ET_OK) h_up = nullptr;  // (bit patterns without a symbol become leaves that decode as byte 0)
-    }
-    // Fixed-length codes (2^L codewords of L bits: two, four, 16, 64 symbols of about equal weight): where the codewords begin is arithmetic.
-    static const bool fixed_off = [] { const char *e = std::getenv("ET_NO_FIXED_SYNC"); return e && e[0] == '1'; }();  // (A/B and the fallback's tests)
-    const bool fixed_sync = h_up && !fixed_off && cb->n_coded >= 2 && cb->min_length == cb->max_length && h_up->tree.n_int + 1 == cb->n_coded;
-    if (fixed_sync) exhaustive = true;  // (two 1-bit codewords as well: nothing for the tree walk to find)
-    const bool tw_sweeps = h_up && !exhaustive;
-    // Uniform-like bytes (complete codes of 7 and 8 bits, BASELINE's worst case): one pass by rows and columns (et_rowsync.h)
-    // instead of the exit maps for every start offset; the write then goes over the chained tables as for any full tree.
-    et::RowCode row_code{};
-    static const bool row_off = [] { const char *e = std::getenv("ET_NO_ROW_SYNC"); return e && e[0] == '1'; }();  // (A/B and the fallback's tests)
-    const bool row_ok = h_up && !fixed_sync && !row_off && et::row_code_of(cb, &row_code);
-    bool row_sync = exhaustive && row_ok;  // (also where a row code that tried the tree walk ends up if its blocks give up, below)
-    // ... and so is where symbol i lies: no synchronisation, no scan, no tables -- the write alone (k_fixed_write).  ET_NO_FIXED_WRITE=1 keeps
-    // k_fixed_sync's start / count words and the chained-table write behind them (A/B; what a range of such a stream on another GPU would take).
-    static const bool fixed_write_off = [] { const char *e = std::getenv("ET_NO_FIXED_WRITE"); return e && e[0] == '1'; }();
-    const bool fixed_direct = fixed_sync && !fixed_write_off && cb->max_length <= 8;
-    if (!tw_sweeps && !row_sync && !fixed_sync) ET_TRY(need_tables(true));
-    const double t1 = now_ms();
+    static_cast<DecWs &>(d) = dec_ws(ctx);
+    d.ctx = ctx;
+    d.cb = cb;
+    d.out = static_cast<uint8_t *>(d_out);
+    d.cap = cap;
+    d.n_symbols = n_symbols;
+    d.h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 4);
 
-    uint32_t *sub_state = static_cast<uint32_t *>(ctx->sub_state.p);
-    uint32_t *blk_exit = static_cast<uint32_t *>(ctx->blk_exit.p);
-    uint32_t *blk_count = static_cast<uint32_t *>(ctx->blk_count.p);
-    uint32_t *flag = static_cast<uint32_t *>(ctx->flag.p);
-    unsigned long long *blk_off = static_cast<unsigned long long *>(ctx->blk_off.p);
-    uint32_t *worklist = static_cast<uint32_t *>(ctx->worklist.p);
-    const et::SideLane *side = &ctx->side;  // the first/last blocks' small launches run beside the large kernels (2.3 % at 1 GiB)
-
-    // D1..D3.  Sweep 0 runs in and repairs inside each block; sweep 1 repairs across blocks
-    // (on text ~0.4 % of the block boundaries); the scan that follows also verifies that
-    // every block now starts where its predecessor ends (the "sweep that changes nothing").
-    // Everything up to the write kernel is enqueued without waiting; the flags and the
-    // symbol total reach the host with ONE synchronisation (stored into pinned memory by the scan, no copy), and only if they say so
-    // (blocks that do not synchronise -> exhaustive path; verification failed -> more
-    // sweeps) is the tail redone.  Device words: flag[0] sweep-1 changed, [1] blocks that
-    // gave up, [2] verification failed, [4] / [5] tickets of D1 / D3, [8] worklist count,
-    // [12..13] symbol total.
-    uint32_t iters = 0;
-    ET_TRY(ensure(ctx, ctx->group_sum, (static_cast<size_t>(n_blocks) / 1024 + 2) * sizeof(uint64_t)));
-    unsigned long long *group_sum = static_cast<unsigned long long *>(ctx->group_sum.p);
-    uint32_t *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 4);  // host copy of flag[0..15]
-    const bool can_speculate = cap >= n_symbols;
-    bool wrote = false, write_ticket_zero = false;
-    uint32_t *blk_start = nullptr;        // tree-walk sweeps (below)
-    const uint16_t *tw_table = nullptr;
-    const uint64_t *chain = nullptr;      // chained write tables (below)
-    uint32_t tw_n_int = 0, n_chain = 0;
-    // the scan's last group stores flags and total into the pinned h_flags and then the launch's epoch into word 14
-    auto wait_report = [&]() -> int { return wait_for_word<uint32_t>(ctx, h_flags + 14, ctx->report_epoch, 200.0, "the decode's report never reached the host"); };
-    auto scan_and_total = [&](bool verify) -> int {
-        // (the scan's last thread stores the flags and the total straight into the pinned h_flags)
-        et::launch_dec_scan(ctx->stream, blk_count, n_blocks, group_sum, scan_epoch(ctx), blk_off, reinterpret_cast<unsigned long long *>(flag + 12),
-                            verify ? sub_state : nullptr, blk_exit, flag + 2, first_bit, flag, h_flags, false, ++ctx->report_epoch);
-        ET_HIP(hipGetLastError());
-        return ET_OK;
-    };
-    bool used_strips = false;
-    auto write_symbols = [&](uint64_t clamp, bool speculative) -> int {
-        // speculative: the kernel itself looks at the sweeps' flags and does nothing if the state is not final
-        static const bool row_write_off = [] { const char *e = std::getenv("ET_NO_ROW_WRITE"); return e && e[0] == '1'; }();  // (A/B: the chained-table write on a row code's stream)
-        if (row_sync && !row_write_off) {  // by rows (et_rowsync.h): no table chain, no bank conflicts between the lanes' regions
-            const et::KernelEvents ev = timed_body(ctx, EV_DEC + 2, EV_DEC + 3);
-            et::launch_row_write(ctx->stream, words, n_bytes, first_bit, n_subs, row_code, cb, sub_state, blk_off, clamp, static_cast<uint8_t *>(d_out), ev.start, ev.stop);
-            ET_HIP(hipGetLastError());
-            return ET_OK;
-        }
-        if (fixed_direct) {  // symbol i is the L bits at first_bit + i L (et_rowsync.h): no walk, no state
-            const et::KernelEvents ev = timed_body(ctx, EV_DEC + 2, EV_DEC + 3);
-            et::launch_fixed_write(ctx->stream, words, n_bytes, first_bit, cb, clamp, static_cast<uint8_t *>(d_out), ev.start, ev.stop);
-            ET_HIP(hipGetLastError());
-            return ET_OK;
-        }
-        // More than 128 symbols per 256-bit subsequence (the header says how many symbols the body's bits hold): a quarter's output is three or more
-        // windows of the write's 4 KiB stage, i.e. it would be walked three or more times -- the instantiation that walks it once, into strips
-        // (measured: +45 % at 140 symbols per subsequence, +75 % at 200; at 90-110, two windows, the strips' scattered stores cost what they save).
-        static const bool strips_off = [] { const char *e = std::getenv("ET_NO_STRIPS"); return e && e[0] == '1'; }();  // (A/B and the windows' tests)
-        const bool strips = !strips_off && chain && n_symbols / 128 > n_subs;
-        used_strips = used_strips || strips;
-        et::launch_dec_write(ctx->stream, words, n_bytes, n_subs, tb_write, sub_state, blk_off, clamp, static_cast<uint8_t *>(d_out), flag + 5, side,
-                             write_ticket_zero, speculative ? flag : nullptr, timed_body(ctx, EV_DEC + 2, EV_DEC + 3), chain, n_chain, cb->max_length, strips);
-        write_ticket_zero = false;
-        ET_HIP(hipGetLastError());
-        return ET_OK;
-    };
-    bool more_sweeps = false;
-    // The synchronisation sweeps by tree walk and the write walk over chained lookup tables (no escapes).
-    if (h_up && !fixed_direct) {
-        et::tw_chain_plan(&h_up->tree, &h_up->plan);
-        ET_TRY(ensure(ctx, ctx->tw_tree, sizeof(et::TwUpload)));
-        ET_TRY(ensure(ctx, ctx->chain_table, static_cast<size_t>(et::CH_MAX_ENTRIES) * sizeof(uint64_t)));
-        if (tw_sweeps) {
-            ET_TRY(ensure(ctx, ctx->tw_table, static_cast<size_t>(et::tw_table_entries(et::TW_MAX_NODES)) * sizeof(uint16_t) + 64));
-            ET_TRY(ensure(ctx, ctx->blk_start, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_pub, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-        }
-        tw_n_int = h_up->tree.n_int;
-        n_chain = h_up->plan.n_entries;
-        const bool zero_here = !flags_zeroed && (!exhaustive || row_sync || fixed_sync);
-        // (the kernel reads the tree and the plan from the pinned block itself: no upload in front of it)
-        et::launch_tw_build(ctx->stream, h_up, static_cast<uint32_t>(et::tw_upload_bytes(h_up)), tw_n_int, tw_sweeps ? static_cast<uint16_t *>(ctx->tw_table.p) : nullptr, n_chain,
-                            static_cast<uint64_t *>(ctx->chain_table.p), zero_here ? flag : nullptr, tw_sweeps ? static_cast<uint32_t *>(ctx->blk_pub.p) : nullptr, n_blocks);
-        flags_zeroed = flags_zeroed || zero_here;
-        chain = static_cast<const uint64_t *>(ctx->chain_table.p);
-        if (tw_sweeps) {
-            tw_table = static_cast<const uint16_t *>(ctx->tw_table.p);
-            blk_start = static_cast<uint32_t *>(ctx->blk_start.p);
-        }
-    }
-    auto scan_and_total_tw = [&]() -> int {
-        et::launch_dec_scan(ctx->stream, blk_count, n_blocks, group_sum, scan_epoch(ctx), blk_off, reinterpret_cast<unsigned long long *>(flag + 12), blk_start, blk_exit, flag + 2, 0u,
-                            flag, h_flags, true, ++ctx->report_epoch);
-        ET_HIP(hipGetLastError());
-        return ET_OK;
-    };
-    if (!exhaustive) {
-        if (!flags_zeroed) ET_HIP(hipMemsetAsync(flag, 0, 16 * sizeof(uint32_t), ctx->stream));
-        write_ticket_zero = true;
-        if (tw_table) {
-            // ONE sweep: the blocks run in, settle inside and then with the block before them (k_tw_sync's blk_pub); what
-            // that leaves open -- a block that did not re-synchronise within its 8 KiB -- the verification finds
-            et::launch_tw_sync(ctx->stream, words, n_bytes, first_bit, n_subs, tw_table, tw_n_int, sub_state, blk_exit, blk_start, blk_count, flag,
-                               et::DEC_FIRST_SWEEP_TRIPS, nullptr, nullptr, timed(ctx, EV_DEC + 0, EV_DEC + 5), static_cast<uint32_t *>(ctx->blk_pub.p));
-        } else {
-            et::launch_dec_sync(ctx->stream, words, n_bytes, first_bit, n_subs, tb, 0, et::DEC_FIRST_SWEEP_TRIPS, sub_state, blk_exit, blk_count, flag, flag + 4,
-                                et::DEC_HAVE_START, nullptr, nullptr, side, true, timed(ctx, EV_DEC + 0, EV_DEC + 5));
-            et::launch_dec_sync(ctx->stream, words, n_bytes, first_bit, n_subs, tb, 1, et::DEC_REPAIR_SWEEP_TRIPS, sub_state, blk_exit, blk_count, flag, flag + 4,
-                                et::DEC_HAVE_START, worklist, flag + 8, side);
-        }
-        ET_HIP(hipGetLastError());
-        iters = tw_table ? 2 : 3;  // run-in sweep, (repair sweep,) verification
-        if (tw_table) ET_TRY(scan_and_total_tw());
-        else ET_TRY(scan_and_total(true));
-        if (can_speculate) {
-            ET_TRY(write_symbols(n_symbols, true));
-            wrote = true;
-        }
-        ET_TRY(wait_report());  // not the stream: the write kernel keeps running while the caller moves on
-        exhaustive = static_cast<uint64_t>(h_flags[1]) * 64 > n_blocks;
-        row_sync = exhaustive && row_ok;
-        more_sweeps = !exhaustive && h_flags[2] != 0;
-        if (!et::dec_state_final(h_flags[1], h_flags[2], n_blocks)) wrote = false;  // the speculative launch declined by the same rule
-    }
-    if (exhaustive && row_sync) {
-        if (iters == 0) {
-            record(ctx, EV_DEC + 0);
-            record(ctx, EV_DEC + 5);
-        }
-        ET_TRY(ensure(ctx, ctx->row_scratch, et::row_sync_scratch_bytes(n_blocks)));
-        et::launch_row_sync(ctx->stream, words, n_bytes, first_bit, n_subs, row_code, ctx->row_scratch.p, flag + 3, sub_state, blk_exit, blk_count);
-        ET_HIP(hipGetLastError());
-        iters += 1;
-    } else if (exhaustive && fixed_sync) {
-        if (iters == 0) {
-            record(ctx, EV_DEC + 0);
-            record(ctx, EV_DEC + 5);
-        }
-        if (!fixed_direct) {
-            et::launch_fixed_sync(ctx->stream, n_bytes, first_bit, n_subs, cb->max_length, sub_state, blk_exit, blk_count);
-            ET_HIP(hipGetLastError());
-            iters += 1;
-        }
-    } else if (exhaustive) {
-        ET_TRY(need_tables(false));
-        // The exhaustive kernels count with the older lookup tables, for which a bit pattern without a symbol is passed
-        // over bit by bit; in the chained tables it is a leaf that decodes as byte 0.  The two agree on every stream of a
-        // FULL tree (an encoder's) -- for a completed one the write has to count like the synchronisation did.
-        if (h_up && h_up->tree.n_int + 1 != cb->n_coded) chain = nullptr;
-        if (iters == 0) {  // no first sweep carried the events: plain markers in front of the exhaustive kernels
-            record(ctx, EV_DEC + 0);
-            record(ctx, EV_DEC + 5);
-        }
-        const uint32_t n_starts = cb->max_length;
-        const uint32_t stride = n_starts <= 8 ? 8 : (n_starts <= 16 ? 16 : 32);
-        const size_t n_groups = (static_cast<size_t>(n_blocks) + 255) / 256;
-        ET_TRY(ensure(ctx, ctx->lane_maps, n_subs * stride + 64));
-        ET_TRY(ensure(ctx, ctx->blk_maps, static_cast<size_t>(n_blocks) * 32 + 64));
-        ET_TRY(ensure(ctx, ctx->grp_maps, n_groups * 32 + 64));
-        ET_TRY(ensure(ctx, ctx->blk_in, static_cast<size_t>(n_blocks) + 64));
-        ET_TRY(ensure(ctx, ctx->grp_in, n_groups + 64));
-        et::launch_dec_exhaustive(ctx->stream, words, n_bytes, first_bit, n_subs, tb, n_starts, stride, static_cast<uint8_t *>(ctx->lane_maps.p),
-                                  static_cast<uint8_t *>(ctx->blk_maps.p), static_cast<uint8_t *>(ctx->grp_maps.p),
-                                  static_cast<uint8_t *>(ctx->blk_in.p), static_cast<uint8_t *>(ctx->grp_in.p), sub_state, blk_exit, blk_count);
-        ET_HIP(hipGetLastError());
-        iters += 5;
-    }
-    while (more_sweeps) {
-        ET_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), ctx->stream));
-        ET_HIP(hipMemsetAsync(flag + 8, 0, sizeof(uint32_t), ctx->stream));
-        if (tw_table) {
-            et::launch_tw_check(ctx->stream, blk_start, blk_exit, n_blocks, worklist, flag + 8);
-            et::launch_tw_sync(ctx->stream, words, n_bytes, first_bit, n_subs, tw_table, tw_n_int, sub_state, blk_exit, blk_start, blk_count, flag, 0xffffffffu,
-                               worklist, flag + 8);
-        } else
-        et::launch_dec_sync(ctx->stream, words, n_bytes, first_bit, n_subs, tb, iters, 0xffffffffu, sub_state, blk_exit, blk_count, flag, flag + 4,
-                            et::DEC_HAVE_START, worklist, flag + 8);
-        ET_HIP(hipGetLastError());
-        ++iters;
-        ET_HIP(hipMemcpyAsync(h_flags, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        ET_HIP(hipStreamSynchronize(ctx->stream));
-        if (h_flags[0] == 0) break;
-        if (iters > n_blocks + 4) return fail(ctx, ET_ERR_HIP, "decode synchronisation did not converge");
-    }
-    if ((exhaustive || more_sweeps) && !fixed_direct) {
-        ET_TRY(scan_and_total(false));
-        ET_TRY(wait_report());
-        if (row_sync && h_flags[3] != 0) return fail(ctx, ET_ERR_HIP, "the row walk's chunks never saw the chunks before them");
-    }
-    const uint64_t decodable = fixed_direct ? (n_bytes * 8 >= first_bit ? (n_bytes * 8 - first_bit) / cb->max_length : 0)  // the whole codewords from first_bit on
-                                            : static_cast<uint64_t>(h_flags[12]) | (static_cast<uint64_t>(h_flags[13]) << 32);
+    ET_TRY(body_setup(d));
+    ET_TRY(body_first_sweep(d));
+    ET_TRY(body_exhaustive(d));
+    ET_TRY(body_repair(d));
+    ET_TRY(body_final_scan(d));
+    const uint64_t decodable = d.family == Family::FIXED_WRITE
+                                   ? (d.n_bytes * 8 >= d.first_bit ? (d.n_bytes * 8 - d.first_bit) / cb->max_length : 0)  // the whole codewords from first_bit on
+                                   : static_cast<uint64_t>(d.h_flags[12]) | (static_cast<uint64_t>(d.h_flags[13]) << 32);
     const uint64_t n_out = decodable < n_symbols ? decodable : n_symbols;
     if (n_out > cap) return fail(ctx, ET_ERR_CAP, "output buffer too small");
-    if (n_out && !wrote) ET_TRY(write_symbols(n_out, false));
+    if (n_out && !d.wrote) ET_TRY(write_symbols(d, n_out, false));
     *out_len = static_cast<size_t>(n_out);
-    if (ctx->timing || ctx->timing_body) {
-        ctx->tm_dec = et_timings{};
-        ctx->tm_dec.host_ms = static_cast<float>(t1 - t0);
-        ctx->tm_dec.sync_iters = iters;
-        ctx->tm_dec.reserved = (exhaustive ? 1u : 0u) | (tw_table ? 2u : 0u) | (chain ? 4u : 0u) | (row_sync ? 8u : 0u) | (fixed_sync ? 16u : 0u) | (used_strips ? 32u : 0u);  // (row_sync: k_row_sync, and k_row_write unless ET_NO_ROW_WRITE; fixed_sync: k_fixed_sync)
-        ctx->pend_dec = true;
-        ctx->pend_dec_first = iters > 0 && !near_fixed && !fixed_sync;
-        ctx->last_kind = 1;
-    }
+    body_timings(d);
     return ET_OK;
 }
 
-extern "C" int et_decode_range_sync(et_ctx *ctx, const et_codebook *cb, const void *d_range, size_t range_bytes, size_t tail_bytes,
-                                    int has_front, int32_t in_start_bit, et_range_info *info) {
-    if (!ctx || !cb || !d_range || !info || range_bytes == 0) return ET_ERR_ARG;
+namespace {
+
+// The argument checks et_decode_range_sync and _maps both make, and the range's geometry.
+int range_geometry(et_ctx *ctx, const et_codebook *cb, const void *d_range, size_t range_bytes, size_t tail_bytes, int32_t in_start_bit, bool unknown_start_ok, RangeGeometry *g) {
     if (reinterpret_cast<uintptr_t>(d_range) & 3) return fail(ctx, ET_ERR_ARG, "d_range must be 4-byte aligned");
     if (tail_bytes && (range_bytes % (et::DEC_BLOCK_WORDS * 4) || tail_bytes < 16)) return fail(ctx, ET_ERR_ARG, "an inner range is a multiple of 8192 bytes with >= 16 bytes after it");
     if (in_start_bit >= 32) return fail(ctx, ET_ERR_ARG, "in_start_bit must be < 32");
-    if (in_start_bit < 0 && !has_front) return fail(ctx, ET_ERR_ARG, "an unknown start needs the 16 bytes in front of the range");
+    if (in_start_bit < 0 && !unknown_start_ok) return fail(ctx, ET_ERR_ARG, "an unknown start needs the 16 bytes in front of the range");
     if (cb->max_length > 32) return fail(ctx, ET_ERR_UNSUPPORTED, "code length > 32");
     if (cb->n_coded == 0) return fail(ctx, ET_ERR_ARG, "empty code table");
-    DeviceGuard guard(ctx->device);
-    const uint32_t *words = static_cast<const uint32_t *>(d_range);
-    const uint64_t n_bytes = static_cast<uint64_t>(range_bytes) + tail_bytes;
-    const uint64_t n_subs = (static_cast<uint64_t>(range_bytes) * 8 + et::SUB_BITS - 1) / et::SUB_BITS;
-    const uint64_t n_blocks64 = (n_subs + et::BLOCK - 1) / et::BLOCK;
+    g->words = static_cast<const uint32_t *>(d_range);
+    g->n_bytes = static_cast<uint64_t>(range_bytes) + tail_bytes;
+    g->n_subs = (static_cast<uint64_t>(range_bytes) * 8 + et::SUB_BITS - 1) / et::SUB_BITS;
+    const uint64_t n_blocks64 = (g->n_subs + et::BLOCK - 1) / et::BLOCK;
     if (n_blocks64 > 0x7fffffffull) return fail(ctx, ET_ERR_ARG, "range too large");
-    const uint32_t n_blocks = static_cast<uint32_t>(n_blocks64);
+    g->n_blocks = static_cast<uint32_t>(n_blocks64);
+    return ET_OK;
+}
+
+// The tail of every range synchronisation: the scan of its blocks' counts, then its start, exit (*exit_word; nullptr: the last block's)
+// and total to the host; the range is ready for et_decode_range_write.  row_word: the row walk's "a chunk never saw the chunks before it" word.
+int finish_range(et_ctx *ctx, const uint32_t *exit_word, const uint32_t *row_word, uint32_t sweeps, uint32_t kind, et_range_info *info) {
     auto &rs = ctx->range;
-    // A full code tree (an encoder's always is): the sweeps of et_decode_body_device -- k_tw_sync with its seam step,
-    // told that the words in front of the range are stream bytes and that the first lane runs in like any other unless
-    // the caller knows its first bit -- then check + repair launches until no block disagrees with the one before it.
-    // A second call for the same range with the predecessor's exit simply sweeps again from that bit.
-    {
-        et::TwUpload *h_up = ctx->h_tw_tree[ctx->tw_turn ^= 1];
-        if (et::tw_build_tree(cb, &h_up->tree, true) == ET_OK) {
-            rs.valid = rs.row = false;
-            et::tw_chain_plan(&h_up->tree, &h_up->plan);
-            ET_TRY(ensure(ctx, ctx->sub_state, n_subs * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_exit, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_count, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_start, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_pub, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_off, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint64_t)));
-            ET_TRY(ensure(ctx, ctx->worklist, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->group_sum, (static_cast<size_t>(n_blocks) / 1024 + 2) * sizeof(uint64_t)));
-            ET_TRY(ensure(ctx, ctx->tw_table, static_cast<size_t>(et::tw_table_entries(et::TW_MAX_NODES)) * sizeof(uint16_t) + 64));
-            ET_TRY(ensure(ctx, ctx->chain_table, static_cast<size_t>(et::CH_MAX_ENTRIES) * sizeof(uint64_t)));
-            ET_TRY(ensure(ctx, ctx->flag, 64));
-            uint32_t *sub_state = static_cast<uint32_t *>(ctx->sub_state.p), *blk_exit = static_cast<uint32_t *>(ctx->blk_exit.p);
-            uint32_t *blk_count = static_cast<uint32_t *>(ctx->blk_count.p), *blk_start = static_cast<uint32_t *>(ctx->blk_start.p);
-            uint32_t *flag = static_cast<uint32_t *>(ctx->flag.p), *worklist = static_cast<uint32_t *>(ctx->worklist.p);
-            uint16_t *tw_table = static_cast<uint16_t *>(ctx->tw_table.p);
-            unsigned long long *blk_off = static_cast<unsigned long long *>(ctx->blk_off.p);
-            uint32_t *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 2);
-            const uint32_t n_int = h_up->tree.n_int, n_chain = h_up->plan.n_entries;
-            const bool known = in_start_bit >= 0;
-            const uint32_t mode = (has_front ? et::TW_FRONT_OK : 0u) | (known ? 0u : et::TW_START_UNKNOWN);
-            const uint32_t first_bit = known ? static_cast<uint32_t>(in_start_bit) : 0u;
-            et::launch_tw_build(ctx->stream, h_up, static_cast<uint32_t>(et::tw_upload_bytes(h_up)), n_int, tw_table, n_chain, static_cast<uint64_t *>(ctx->chain_table.p), flag,
-                                static_cast<uint32_t *>(ctx->blk_pub.p), n_blocks);
-            et::launch_tw_sync(ctx->stream, words, n_bytes, first_bit, n_subs, tw_table, n_int, sub_state, blk_exit, blk_start, blk_count, flag, et::DEC_FIRST_SWEEP_TRIPS,
-                               nullptr, nullptr, {}, static_cast<uint32_t *>(ctx->blk_pub.p), mode, flag + 9);
-            ET_HIP(hipGetLastError());
-            uint32_t sweeps = 1;
-            for (;;) {  // (normally one look: nothing on the list)
-                ET_HIP(hipMemsetAsync(flag + 8, 0, sizeof(uint32_t), ctx->stream));
-                et::launch_tw_check(ctx->stream, blk_start, blk_exit, n_blocks, worklist, flag + 8, known);
-                ET_HIP(hipMemcpyAsync(h_flags, flag + 8, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-                ET_HIP(hipStreamSynchronize(ctx->stream));
-                if (h_flags[0] == 0) break;
-                if (sweeps > n_blocks + 4) return fail(ctx, ET_ERR_HIP, "decode synchronisation did not converge");
-                et::launch_tw_sync(ctx->stream, words, n_bytes, first_bit, n_subs, tw_table, n_int, sub_state, blk_exit, blk_start, blk_count, flag, 0xffffffffu, worklist,
-                                   flag + 8, {}, nullptr, mode, flag + 9);
-                ET_HIP(hipGetLastError());
-                ++sweeps;
-            }
-            et::launch_dec_scan(ctx->stream, blk_count, n_blocks, static_cast<unsigned long long *>(ctx->group_sum.p), scan_epoch(ctx), blk_off);
-            ET_HIP(hipGetLastError());
-            ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, blk_off + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-            ET_HIP(hipMemcpyAsync(h_flags, sub_state, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            ET_HIP(hipMemcpyAsync(h_flags + 1, flag + 9, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            ET_HIP(hipStreamSynchronize(ctx->stream));
-            rs.words = words;
-            rs.n_bytes = n_bytes;
-            rs.n_subs = n_subs;
-            rs.n_blocks = n_blocks;
-            rs.total = ctx->h_scalar[1];
-            rs.tw = true;
-            rs.n_chain = n_chain;
-            rs.max_len = cb->max_length;
-            rs.valid = true;
-            info->start_bit = h_flags[0] & 0xffu;
-            info->exit_bit = h_flags[1];
-            info->n_symbols = rs.total;
-            info->sweeps = sweeps;
-            info->reserved = 2;  // tree walk
-            return ET_OK;
-        }
-    }
-    rs.tw = rs.row = false;
-    const bool repair = rs.valid && rs.words == words && rs.n_subs == n_subs && in_start_bit >= 0;
-    uint32_t sweeps = 0;
-    if (!repair) {
-        rs.valid = false;
-        ET_TRY(ensure(ctx, ctx->sub_state, n_subs * sizeof(uint32_t)));
-        ET_TRY(ensure(ctx, ctx->blk_exit, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-        ET_TRY(ensure(ctx, ctx->blk_count, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-        ET_TRY(ensure(ctx, ctx->blk_off, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint64_t)));
-        ET_TRY(ensure(ctx, ctx->group_sum, (static_cast<size_t>(n_blocks) / 1024 + 2) * sizeof(uint64_t)));
-        ET_TRY(prepare_decode_tables(ctx, cb, &rs.tb, &rs.tb_write));
-        rs.words = words;
-        rs.n_bytes = n_bytes;
-        rs.n_subs = n_subs;
-        rs.n_blocks = n_blocks;
-    }
-    rs.flags = (in_start_bit >= 0 ? et::DEC_HAVE_START : 0u) | (has_front ? et::DEC_FRONT_OK : 0u);
-    const uint32_t first_bit = in_start_bit >= 0 ? static_cast<uint32_t>(in_start_bit) : 0u;
-    uint32_t *sub_state = static_cast<uint32_t *>(ctx->sub_state.p);
-    uint32_t *blk_exit = static_cast<uint32_t *>(ctx->blk_exit.p);
-    uint32_t *blk_count = static_cast<uint32_t *>(ctx->blk_count.p);
-    uint32_t *flag = static_cast<uint32_t *>(ctx->flag.p);
-    unsigned long long *blk_off = static_cast<unsigned long long *>(ctx->blk_off.p);
+    const DecWs w = dec_ws(ctx);
     uint32_t *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 2);
-    if (!repair) {
-        // Sweep 0 (run-in, local repair with a trip cap); codes that do not synchronise take
-        // many capped sweeps here -- the exhaustive path is single-GPU only for now.
-        ET_HIP(hipMemsetAsync(flag, 0, 4 * sizeof(uint32_t), ctx->stream));
-        et::launch_dec_sync(ctx->stream, words, n_bytes, first_bit, n_subs, rs.tb, 0, et::DEC_FIRST_SWEEP_TRIPS, sub_state, blk_exit, blk_count, flag,
-                            flag + 4, rs.flags);
-        ET_HIP(hipGetLastError());
-        ++sweeps;
-    }
-    for (;;) {
-        ET_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), ctx->stream));
-        et::launch_dec_sync(ctx->stream, words, n_bytes, first_bit, n_subs, rs.tb, 1 + sweeps, 0xffffffffu, sub_state, blk_exit, blk_count, flag, flag + 4,
-                            rs.flags);
-        ET_HIP(hipGetLastError());
-        ++sweeps;
-        ET_HIP(hipMemcpyAsync(h_flags, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        ET_HIP(hipStreamSynchronize(ctx->stream));
-        if (h_flags[0] == 0) break;
-        if (sweeps > n_blocks + 4) return fail(ctx, ET_ERR_HIP, "decode synchronisation did not converge");
-    }
-    et::launch_dec_scan(ctx->stream, blk_count, n_blocks, static_cast<unsigned long long *>(ctx->group_sum.p), scan_epoch(ctx), blk_off);
+    et::launch_dec_scan(ctx->stream, w.blk_count, rs.g.n_blocks, w.group_sum, scan_epoch(ctx), w.blk_off);
     ET_HIP(hipGetLastError());
-    ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, blk_off + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    ET_HIP(hipMemcpyAsync(h_flags, sub_state, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    ET_HIP(hipMemcpyAsync(h_flags + 1, blk_exit + (n_blocks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, w.blk_off + rs.g.n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    ET_HIP(hipMemcpyAsync(h_flags, w.sub_state, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ET_HIP(hipMemcpyAsync(h_flags + 1, exit_word ? exit_word : w.blk_exit + (rs.g.n_blocks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (row_word) ET_HIP(hipMemcpyAsync(h_flags + 2, row_word, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     ET_HIP(hipStreamSynchronize(ctx->stream));
+    if (row_word && h_flags[2] != 0) return fail(ctx, ET_ERR_HIP, "the row walk's chunks never saw the chunks before them");
     rs.total = ctx->h_scalar[1];
     rs.valid = true;
     info->start_bit = h_flags[0] & 0xffu;
     info->exit_bit = h_flags[1];
     info->n_symbols = rs.total;
     info->sweeps = sweeps;
-    info->reserved = 0;
+    info->reserved = kind;  // 0 windows, 1 exit maps, 2 tree walk, 3 row walk
     return ET_OK;
+}
+
+}  // namespace
+
+extern "C" int et_decode_range_sync(et_ctx *ctx, const et_codebook *cb, const void *d_range, size_t range_bytes, size_t tail_bytes,
+                                    int has_front, int32_t in_start_bit, et_range_info *info) {
+    if (!ctx || !cb || !d_range || !info || range_bytes == 0) return ET_ERR_ARG;
+    RangeGeometry g;
+    ET_TRY(range_geometry(ctx, cb, d_range, range_bytes, tail_bytes, in_start_bit, has_front != 0, &g));
+    DeviceGuard guard(ctx->device);
+    auto &rs = ctx->range;
+    const bool known = in_start_bit >= 0;
+    const uint32_t first_bit = known ? static_cast<uint32_t>(in_start_bit) : 0u;
+    // A full code tree (an encoder's always is): the sweeps of et_decode_body_device -- k_tw_sync with its seam step,
+    // told that the words in front of the range are stream bytes and that the first lane runs in like any other unless
+    // the caller knows its first bit -- then check + repair launches until no block disagrees with the one before it.
+    // A second call for the same range with the predecessor's exit simply sweeps again from that bit.
+    et::TwUpload *h_up = ctx->h_tw_tree[ctx->tw_turn ^= 1];
+    if (et::tw_build_tree(cb, &h_up->tree, true) == ET_OK) {
+        rs.valid = rs.row = false;
+        et::tw_chain_plan(&h_up->tree, &h_up->plan);
+        ET_TRY(ensure_dec_ws(ctx, g.n_subs, g.n_blocks));
+        ET_TRY(ensure(ctx, ctx->blk_start, static_cast<size_t>(g.n_blocks) * sizeof(uint32_t)));
+        ET_TRY(ensure(ctx, ctx->blk_pub, static_cast<size_t>(g.n_blocks) * sizeof(uint32_t)));
+        ET_TRY(ensure(ctx, ctx->worklist, (static_cast<size_t>(g.n_blocks) + 1) * sizeof(uint32_t)));
+        ET_TRY(ensure(ctx, ctx->tw_table, static_cast<size_t>(et::tw_table_entries(et::TW_MAX_NODES)) * sizeof(uint16_t) + 64));
+        ET_TRY(ensure(ctx, ctx->chain_table, static_cast<size_t>(et::CH_MAX_ENTRIES) * sizeof(uint64_t)));
+        const DecWs w = dec_ws(ctx);
+        uint32_t *blk_start = static_cast<uint32_t *>(ctx->blk_start.p), *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 2);
+        uint16_t *tw_table = static_cast<uint16_t *>(ctx->tw_table.p);
+        const uint32_t n_int = h_up->tree.n_int, n_chain = h_up->plan.n_entries;
+        const uint32_t mode = (has_front ? et::TW_FRONT_OK : 0u) | (known ? 0u : et::TW_START_UNKNOWN);
+        et::launch_tw_build(ctx->stream, h_up, static_cast<uint32_t>(et::tw_upload_bytes(h_up)), n_int, tw_table, n_chain, static_cast<uint64_t *>(ctx->chain_table.p), w.flag,
+                            static_cast<uint32_t *>(ctx->blk_pub.p), g.n_blocks);
+        et::launch_tw_sync(ctx->stream, g.words, g.n_bytes, first_bit, g.n_subs, tw_table, n_int, w.sub_state, w.blk_exit, blk_start, w.blk_count, w.flag,
+                           et::DEC_FIRST_SWEEP_TRIPS, nullptr, nullptr, {}, static_cast<uint32_t *>(ctx->blk_pub.p), mode, w.flag + 9);
+        ET_HIP(hipGetLastError());
+        uint32_t sweeps = 1;
+        for (;;) {  // (normally one look: nothing on the list)
+            ET_HIP(hipMemsetAsync(w.flag + 8, 0, sizeof(uint32_t), ctx->stream));
+            et::launch_tw_check(ctx->stream, blk_start, w.blk_exit, g.n_blocks, w.worklist, w.flag + 8, known);
+            ET_HIP(hipMemcpyAsync(h_flags, w.flag + 8, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            ET_HIP(hipStreamSynchronize(ctx->stream));
+            if (h_flags[0] == 0) break;
+            if (sweeps > g.n_blocks + 4) return fail(ctx, ET_ERR_HIP, "decode synchronisation did not converge");
+            et::launch_tw_sync(ctx->stream, g.words, g.n_bytes, first_bit, g.n_subs, tw_table, n_int, w.sub_state, w.blk_exit, blk_start, w.blk_count, w.flag, 0xffffffffu,
+                               w.worklist, w.flag + 8, {}, nullptr, mode, w.flag + 9);
+            ET_HIP(hipGetLastError());
+            ++sweeps;
+        }
+        rs.g = g;
+        rs.tw = true;
+        rs.n_chain = n_chain;
+        rs.max_len = cb->max_length;
+        return finish_range(ctx, w.flag + 9, nullptr, sweeps, 2, info);
+    }
+    rs.tw = rs.row = false;
+    const bool repair = rs.valid && rs.g.words == g.words && rs.g.n_subs == g.n_subs && known;
+    uint32_t sweeps = 0;
+    if (!repair) {
+        rs.valid = false;
+        ET_TRY(ensure_dec_ws(ctx, g.n_subs, g.n_blocks));
+        ET_TRY(prepare_decode_tables(ctx, cb, &rs.tb, &rs.tb_write));
+        rs.g = g;
+    }
+    rs.flags = (known ? et::DEC_HAVE_START : 0u) | (has_front ? et::DEC_FRONT_OK : 0u);
+    const DecWs w = dec_ws(ctx);
+    uint32_t *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 2);
+    if (!repair) {
+        // Sweep 0 (run-in, local repair with a trip cap); codes that do not synchronise take
+        // many capped sweeps here -- the exhaustive path is single-GPU only for now.
+        ET_HIP(hipMemsetAsync(w.flag, 0, 4 * sizeof(uint32_t), ctx->stream));
+        et::launch_dec_sync(ctx->stream, g.words, g.n_bytes, first_bit, g.n_subs, rs.tb, 0, et::DEC_FIRST_SWEEP_TRIPS, w.sub_state, w.blk_exit, w.blk_count, w.flag, w.flag + 4, rs.flags);
+        ET_HIP(hipGetLastError());
+        ++sweeps;
+    }
+    for (;;) {
+        ET_HIP(hipMemsetAsync(w.flag, 0, sizeof(uint32_t), ctx->stream));
+        et::launch_dec_sync(ctx->stream, g.words, g.n_bytes, first_bit, g.n_subs, rs.tb, 1 + sweeps, 0xffffffffu, w.sub_state, w.blk_exit, w.blk_count, w.flag, w.flag + 4, rs.flags);
+        ET_HIP(hipGetLastError());
+        ++sweeps;
+        ET_HIP(hipMemcpyAsync(h_flags, w.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ET_HIP(hipStreamSynchronize(ctx->stream));
+        if (h_flags[0] == 0) break;
+        if (sweeps > g.n_blocks + 4) return fail(ctx, ET_ERR_HIP, "decode synchronisation did not converge");
+    }
+    return finish_range(ctx, nullptr, nullptr, sweeps, 0, info);
 }
 
 extern "C" int et_decode_range_maps(et_ctx *ctx, const et_codebook *cb, const void *d_range, size_t range_bytes, size_t tail_bytes,
                                     int32_t in_start_bit, uint8_t map[32], uint32_t *n_starts_out) {
     if (!ctx || !cb || !d_range || !map || !n_starts_out || range_bytes == 0) return ET_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(d_range) & 3) return fail(ctx, ET_ERR_ARG, "d_range must be 4-byte aligned");
-    if (tail_bytes && (range_bytes % (et::DEC_BLOCK_WORDS * 4) || tail_bytes < 16)) return fail(ctx, ET_ERR_ARG, "an inner range is a multiple of 8192 bytes with >= 16 bytes after it");
-    if (in_start_bit >= 32) return fail(ctx, ET_ERR_ARG, "in_start_bit must be < 32");
-    if (cb->max_length > 32) return fail(ctx, ET_ERR_UNSUPPORTED, "code length > 32");
-    if (cb->n_coded == 0) return fail(ctx, ET_ERR_ARG, "empty code table");
+    RangeGeometry g;
+    ET_TRY(range_geometry(ctx, cb, d_range, range_bytes, tail_bytes, in_start_bit, true, &g));
     DeviceGuard guard(ctx->device);
-    const uint32_t *words = static_cast<const uint32_t *>(d_range);
-    const uint64_t n_bytes = static_cast<uint64_t>(range_bytes) + tail_bytes;
-    const uint64_t n_subs = (static_cast<uint64_t>(range_bytes) * 8 + et::SUB_BITS - 1) / et::SUB_BITS;
-    const uint64_t n_blocks64 = (n_subs + et::BLOCK - 1) / et::BLOCK;
-    if (n_blocks64 > 0x7fffffffull) return fail(ctx, ET_ERR_ARG, "range too large");
-    const uint32_t n_blocks = static_cast<uint32_t>(n_blocks64);
     auto &rs = ctx->range;
     rs.valid = rs.maps_valid = rs.tw = rs.row = false;
-    {
-        // Uniform-like bytes (a complete code of 7- and 8-bit codewords): the range's map by rows and columns -- every chunk publishes
-        // its map, the last one composes them (k_row_sync, ROW_MAP_ONLY); the resolve is a second run with the start known.
-        et::RowCode row_code{};
-        static const bool row_off = [] { const char *e = std::getenv("ET_NO_ROW_SYNC"); return e && e[0] == '1'; }();
-        if (!row_off && et::row_code_of(cb, &row_code)) {
-            ET_TRY(ensure(ctx, ctx->sub_state, n_subs * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_exit, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_count, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-            ET_TRY(ensure(ctx, ctx->blk_off, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint64_t)));
-            ET_TRY(ensure(ctx, ctx->group_sum, (static_cast<size_t>(n_blocks) / 1024 + 2) * sizeof(uint64_t)));
-            ET_TRY(ensure(ctx, ctx->row_scratch, et::row_sync_scratch_bytes(n_blocks)));
-            ET_TRY(ensure(ctx, ctx->flag, 64));
-            uint32_t *flag = static_cast<uint32_t *>(ctx->flag.p);
-            ET_HIP(hipMemsetAsync(flag, 0, 16 * sizeof(uint32_t), ctx->stream));
-            const bool known = in_start_bit >= 0;
-            const unsigned long long *d_map = nullptr;
-            et::launch_row_sync(ctx->stream, words, n_bytes, known ? static_cast<uint32_t>(in_start_bit) : 0u, n_subs, row_code, ctx->row_scratch.p, flag + 3,
-                                static_cast<uint32_t *>(ctx->sub_state.p), static_cast<uint32_t *>(ctx->blk_exit.p), static_cast<uint32_t *>(ctx->blk_count.p),
-                                et::ROW_MAP_ONLY | (known ? 0u : et::ROW_START_UNKNOWN), &d_map);
-            ET_HIP(hipGetLastError());
-            ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, d_map, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-            ET_HIP(hipMemcpyAsync(ctx->h_scalar + 2, flag + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            ET_HIP(hipStreamSynchronize(ctx->stream));
-            if (*reinterpret_cast<const uint32_t *>(ctx->h_scalar + 2) != 0) return fail(ctx, ET_ERR_HIP, "the row walk's chunks never saw the chunks before them");
-            const uint64_t m = ctx->h_scalar[1];
-            for (uint32_t p = 0; p < 32; ++p) map[p] = static_cast<uint8_t>(p < 8 ? (m >> (8 * p)) & 0xffu : (known ? m & 0xffu : p));
-            *n_starts_out = 8;
-            rs.words = words;
-            rs.n_bytes = n_bytes;
-            rs.n_subs = n_subs;
-            rs.n_blocks = n_blocks;
-            rs.flags = 0;
-            rs.row = true;
-            rs.row_code = row_code;
-            rs.row_cb = *cb;
-            rs.maps_const = known;
-            rs.maps_valid = true;
-            return ET_OK;
-        }
+    const bool known = in_start_bit >= 0;
+    ET_TRY(ensure_dec_ws(ctx, g.n_subs, g.n_blocks));
+    // Uniform-like bytes (a complete code of 7- and 8-bit codewords): the range's map by rows and columns -- every chunk publishes
+    // its map, the last one composes them (k_row_sync, ROW_MAP_ONLY); the resolve is a second run with the start known.
+    et::RowCode row_code{};
+    if (!decode_switches().no_row_sync && et::row_code_of(cb, &row_code)) {
+        ET_TRY(ensure(ctx, ctx->row_scratch, et::row_sync_scratch_bytes(g.n_blocks)));
+        const DecWs w = dec_ws(ctx);
+        ET_HIP(hipMemsetAsync(w.flag, 0, 16 * sizeof(uint32_t), ctx->stream));
+        const unsigned long long *d_map = nullptr;
+        et::launch_row_sync(ctx->stream, g.words, g.n_bytes, known ? static_cast<uint32_t>(in_start_bit) : 0u, g.n_subs, row_code, ctx->row_scratch.p, w.flag + 3,
+                            w.sub_state, w.blk_exit, w.blk_count, et::ROW_MAP_ONLY | (known ? 0u : et::ROW_START_UNKNOWN), &d_map);
+        ET_HIP(hipGetLastError());
+        ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, d_map, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ET_HIP(hipMemcpyAsync(ctx->h_scalar + 2, w.flag + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ET_HIP(hipStreamSynchronize(ctx->stream));
+        if (*reinterpret_cast<const uint32_t *>(ctx->h_scalar + 2) != 0) return fail(ctx, ET_ERR_HIP, "the row walk's chunks never saw the chunks before them");
+        const uint64_t m = ctx->h_scalar[1];
+        for (uint32_t p = 0; p < 32; ++p) map[p] = static_cast<uint8_t>(p < 8 ? (m >> (8 * p)) & 0xffu : (known ? m & 0xffu : p));
+        *n_starts_out = 8;
+        rs.g = g;
+        rs.flags = 0;
+        rs.row = true;
+        rs.row_code = row_code;
+        rs.row_cb = *cb;
+        rs.maps_const = known;
+        rs.maps_valid = true;
+        return ET_OK;
     }
-    const uint32_t n_starts = cb->max_length;
-    const uint32_t stride = n_starts <= 8 ? 8 : (n_starts <= 16 ? 16 : 32);
-    const size_t n_groups = (static_cast<size_t>(n_blocks) + 255) / 256;
-    ET_TRY(ensure(ctx, ctx->sub_state, n_subs * sizeof(uint32_t)));
-    ET_TRY(ensure(ctx, ctx->blk_exit, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-    ET_TRY(ensure(ctx, ctx->blk_count, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
-    ET_TRY(ensure(ctx, ctx->blk_off, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint64_t)));
-    ET_TRY(ensure(ctx, ctx->group_sum, (static_cast<size_t>(n_blocks) / 1024 + 2) * sizeof(uint64_t)));
-    ET_TRY(ensure(ctx, ctx->lane_maps, n_subs * stride + 64));
-    ET_TRY(ensure(ctx, ctx->blk_maps, static_cast<size_t>(n_blocks) * 32 + 64));
-    ET_TRY(ensure(ctx, ctx->grp_maps, n_groups * 32 + 64));
-    ET_TRY(ensure(ctx, ctx->blk_in, static_cast<size_t>(n_blocks) + 64));
-    ET_TRY(ensure(ctx, ctx->grp_in, n_groups + 64));
+    const uint32_t n_starts = cb->max_length, stride = map_stride(n_starts);
+    const size_t n_groups = (static_cast<size_t>(g.n_blocks) + 255) / 256;
+    ET_TRY(ensure_maps_ws(ctx, g.n_subs, g.n_blocks, stride));
     ET_TRY(prepare_decode_tables(ctx, cb, &rs.tb, &rs.tb_write));
-    rs.words = words;
-    rs.n_bytes = n_bytes;
-    rs.n_subs = n_subs;
-    rs.n_blocks = n_blocks;
+    rs.g = g;
     rs.flags = 0;
     rs.map_stride = stride;
-    rs.maps_const = in_start_bit >= 0;
-    et::launch_dec_maps(ctx->stream, words, n_bytes, in_start_bit >= 0 ? static_cast<uint32_t>(in_start_bit) : 0u, rs.maps_const, n_subs, rs.tb, n_starts, stride,
+    rs.maps_const = known;
+    et::launch_dec_maps(ctx->stream, g.words, g.n_bytes, known ? static_cast<uint32_t>(in_start_bit) : 0u, rs.maps_const, g.n_subs, rs.tb, n_starts, stride,
                         static_cast<uint8_t *>(ctx->lane_maps.p), static_cast<uint8_t *>(ctx->blk_maps.p), static_cast<uint8_t *>(ctx->grp_maps.p));
     ET_HIP(hipGetLastError());
     // last level on the host: compose the group maps (32 bytes per 2 MiB of stream)
@@ -1526,7 +1556,7 @@ extern "C" int et_decode_range_maps(et_ctx *ctx, const et_codebook *cb, const vo
     for (uint32_t p = 0; p < 32; ++p) {
         uint32_t sidx = p;
         if (p < n_starts || rs.maps_const)
-            for (size_t g = 0; g < n_groups; ++g) sidx = grp[g * 32 + sidx];
+            for (size_t i = 0; i < n_groups; ++i) sidx = grp[i * 32 + sidx];
         map[p] = static_cast<uint8_t>(sidx);
     }
     *n_starts_out = n_starts;
@@ -1540,52 +1570,21 @@ extern "C" int et_decode_range_resolve(et_ctx *ctx, uint32_t in_start_bit, et_ra
     if (!rs.maps_valid) return fail(ctx, ET_ERR_ARG, "et_decode_range_resolve needs et_decode_range_maps first");
     if (in_start_bit >= 32) return fail(ctx, ET_ERR_ARG, "in_start_bit must be < 32");
     DeviceGuard guard(ctx->device);
-    uint32_t *sub_state = static_cast<uint32_t *>(ctx->sub_state.p);
-    uint32_t *blk_exit = static_cast<uint32_t *>(ctx->blk_exit.p);
-    uint32_t *blk_count = static_cast<uint32_t *>(ctx->blk_count.p);
-    unsigned long long *blk_off = static_cast<unsigned long long *>(ctx->blk_off.p);
-    uint32_t *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 2);
+    const DecWs w = dec_ws(ctx);
     if (rs.row) {  // the same walk again, the start known: every lane's start, exit and count
-        uint32_t *flag = static_cast<uint32_t *>(ctx->flag.p);
-        ET_HIP(hipMemsetAsync(flag, 0, 16 * sizeof(uint32_t), ctx->stream));
-        et::launch_row_sync(ctx->stream, rs.words, rs.n_bytes, in_start_bit, rs.n_subs, rs.row_code, ctx->row_scratch.p, flag + 3, sub_state, blk_exit, blk_count);
-        et::launch_dec_scan(ctx->stream, blk_count, rs.n_blocks, static_cast<unsigned long long *>(ctx->group_sum.p), scan_epoch(ctx), blk_off);
+        ET_HIP(hipMemsetAsync(w.flag, 0, 16 * sizeof(uint32_t), ctx->stream));
+        et::launch_row_sync(ctx->stream, rs.g.words, rs.g.n_bytes, in_start_bit, rs.g.n_subs, rs.row_code, ctx->row_scratch.p, w.flag + 3, w.sub_state, w.blk_exit, w.blk_count);
         ET_HIP(hipGetLastError());
-        ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, blk_off + rs.n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        ET_HIP(hipMemcpyAsync(h_flags, sub_state, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        ET_HIP(hipMemcpyAsync(h_flags + 1, blk_exit + (rs.n_blocks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        ET_HIP(hipMemcpyAsync(h_flags + 2, flag + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        ET_HIP(hipStreamSynchronize(ctx->stream));
-        if (h_flags[2] != 0) return fail(ctx, ET_ERR_HIP, "the row walk's chunks never saw the chunks before them");
-        rs.total = ctx->h_scalar[1];
-        rs.flags = et::DEC_HAVE_START;
+        ET_TRY(finish_range(ctx, nullptr, w.flag + 3, 0, 3, info));
         rs.first_bit = in_start_bit;
-        rs.valid = true;
-        info->start_bit = h_flags[0] & 0xffu;
-        info->exit_bit = h_flags[1];
-        info->n_symbols = rs.total;
-        info->sweeps = 0;
-        info->reserved = 3;  // row walk
-        return ET_OK;
+    } else {
+        et::launch_dec_resolve(ctx->stream, rs.g.words, rs.g.n_bytes, in_start_bit, rs.maps_const, rs.g.n_subs, rs.tb, rs.map_stride,
+                               static_cast<const uint8_t *>(ctx->lane_maps.p), static_cast<const uint8_t *>(ctx->blk_maps.p),
+                               static_cast<const uint8_t *>(ctx->grp_maps.p), static_cast<uint8_t *>(ctx->blk_in.p), static_cast<uint8_t *>(ctx->grp_in.p), w.sub_state, w.blk_exit, w.blk_count);
+        ET_HIP(hipGetLastError());
+        ET_TRY(finish_range(ctx, nullptr, nullptr, 0, 1, info));
     }
-    et::launch_dec_resolve(ctx->stream, rs.words, rs.n_bytes, in_start_bit, rs.maps_const, rs.n_subs, rs.tb, rs.map_stride,
-                           static_cast<const uint8_t *>(ctx->lane_maps.p), static_cast<const uint8_t *>(ctx->blk_maps.p),
-                           static_cast<const uint8_t *>(ctx->grp_maps.p), static_cast<uint8_t *>(ctx->blk_in.p), static_cast<uint8_t *>(ctx->grp_in.p),
-                           sub_state, blk_exit, blk_count);
-    et::launch_dec_scan(ctx->stream, blk_count, rs.n_blocks, static_cast<unsigned long long *>(ctx->group_sum.p), scan_epoch(ctx), blk_off);
-    ET_HIP(hipGetLastError());
-    ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, blk_off + rs.n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    ET_HIP(hipMemcpyAsync(h_flags, sub_state, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    ET_HIP(hipMemcpyAsync(h_flags + 1, blk_exit + (rs.n_blocks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    ET_HIP(hipStreamSynchronize(ctx->stream));
-    rs.total = ctx->h_scalar[1];
     rs.flags = et::DEC_HAVE_START;
-    rs.valid = true;
-    info->start_bit = h_flags[0] & 0xffu;
-    info->exit_bit = h_flags[1];
-    info->n_symbols = rs.total;
-    info->sweeps = 0;
-    info->reserved = 1;  // exhaustive
     return ET_OK;
 }
 
@@ -1600,13 +1599,13 @@ extern "C" int et_decode_range_write(et_ctx *ctx, uint64_t max_symbols, void *d_
     if (n_out > cap) return fail(ctx, ET_ERR_CAP, "output buffer too small");
     DeviceGuard guard(ctx->device);
     if (rs.row) {
-        et::launch_row_write(ctx->stream, rs.words, rs.n_bytes, rs.first_bit, rs.n_subs, rs.row_code, &rs.row_cb, static_cast<const uint32_t *>(ctx->sub_state.p),
+        et::launch_row_write(ctx->stream, rs.g.words, rs.g.n_bytes, rs.first_bit, rs.g.n_subs, rs.row_code, &rs.row_cb, static_cast<const uint32_t *>(ctx->sub_state.p),
                              static_cast<const unsigned long long *>(ctx->blk_off.p), n_out, static_cast<uint8_t *>(d_out));
         ET_HIP(hipGetLastError());
         *out_len = static_cast<size_t>(n_out);
         return ET_OK;
     }
-    et::launch_dec_write(ctx->stream, rs.words, rs.n_bytes, rs.n_subs, rs.tb_write, static_cast<const uint32_t *>(ctx->sub_state.p),
+    et::launch_dec_write(ctx->stream, rs.g.words, rs.g.n_bytes, rs.g.n_subs, rs.tb_write, static_cast<const uint32_t *>(ctx->sub_state.p),
                          static_cast<const unsigned long long *>(ctx->blk_off.p), n_out, static_cast<uint8_t *>(d_out),
                          static_cast<uint32_t *>(ctx->flag.p) + 4, nullptr, false, nullptr, {},
                          rs.tw ? static_cast<const uint64_t *>(ctx->chain_table.p) : nullptr, rs.n_chain, rs.max_len);

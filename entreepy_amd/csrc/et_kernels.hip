@@ -859,9 +859,9 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) { return __builtin_amdg
 #else
 #define ET_PROBE_ONE_STATE_COND
 #endif
-// STRIPS (a second instantiation, for streams with more than ~70 symbols per 256-bit subsequence -- a dominant symbol with a 1- or 2-bit
-// codeword, alphabets of a few symbols): a quarter whose output does not fit the stage is not walked once per 4 KiB window of its
-// output (3-4 times on such streams) but ONCE, every lane into a strip of its own (WS_STRIDE bytes of what is the stage otherwise),
+// STRIPS (a second instantiation, for streams with more than 128 symbols per 256-bit subsequence -- the host's rule is n_symbols / 128
+// > n_subs, unless ET_NO_STRIPS=1 -- such as a dominant symbol with a 1- or 2-bit codeword, or alphabets of a few symbols): a quarter
+// whose output does not fit the stage is not walked once per 4 KiB window of its output (3-4 times on such streams) but ONCE, every lane into a strip of its own (WS_STRIDE bytes of what is the stage otherwise),
 // and the strips leave for their places in the output every two stream words (walk_write_chain<3>): 64-byte pieces instead of
 // 16-byte chunks of a contiguous stage, but a third or a quarter of the lookups.  The text kernel is the instantiation without.
 constexpr uint32_t WS_STRIDE = 68;                 // a strip: the <= 64 codewords of two words + the two stray bytes of a fast step, a multiple of 4

@@ -64,7 +64,7 @@ typedef struct et_timings {
     float sync_ms;      /* decode: everything in front of the write kernel (sweeps, verification, scan) */
     float total_ms;     /* begin of the first large kernel to the end of the last */
     uint32_t sync_iters;/* decode: synchronisation launches */
-    uint32_t reserved;  /* decode: bit 0 = the exhaustive synchronisation path ran, bit 1 = the sweeps ran as a tree walk, bit 2 = the write pass used the chained tables, bit 3 = synchronised (and, unless switched off, written) by rows: a complete code of 7- and 8-bit codewords, et_row_code, bit 4 = a fixed-length code (2^L codewords of L bits): decoded by arithmetic, no synchronisation (csrc/et_rowsync.h, k_fixed_write), bit 5 = the write pass ran as its instantiation for streams with more than 128 symbols per 256-bit subsequence (quarters that overflow the stage walk once, into strips) */
+    uint32_t reserved;  /* decode: bit 0 = the exhaustive synchronisation path ran, bit 1 = the sweeps ran as a tree walk, bit 2 = the write pass used the chained tables, bit 3 = synchronised (and, unless switched off, written) by rows: a complete code of 7- and 8-bit codewords, et_row_code, bit 4 = a fixed-length code (2^L codewords of L bits): decoded by arithmetic, no synchronisation (csrc/et_rowsync.h, k_fixed_write), bit 5 = the write pass whose output was kept ran as its instantiation for streams with more than 128 symbols per 256-bit subsequence (quarters that overflow the stage walk once, into strips) */
     float sync_first_ms;/* decode: the first synchronisation sweep alone (k_dec_sync<first>) */
     uint32_t pad_;
 } et_timings;
@@ -189,13 +189,15 @@ int et_chain_tables(const et_codebook *cb, uint64_t *table, size_t cap_entries, 
 int et_row_code(const et_codebook *cb, uint32_t *t);
 
 /* Which synchronisation a one-GPU decode of a whole stream starts with for this code table (diagnostics; decode.zig:143-203
- * needs no such choice -- one thread walks the stream).  The stream itself can still overrule the first two: blocks that do
- * not settle under the tree walk go to the exit maps, or by rows if the code is a row code.
+ * needs no such choice -- one thread walks the stream).  The stream itself can still overrule the two sweeps, TREE_WALK and
+ * WINDOWS: blocks that do not settle under them go to the exit maps, or by rows if the code is a row code.
  *   ET_PATH_TREE_WALK  the tree walk (text, and codes of L and L + 1 bits whose mix of lengths settles quickly: csrc/et_rowsync_host.cpp)
- *   ET_PATH_EXIT_MAPS  exit maps for every start offset (near-fixed-length codes that do not settle; csrc/et_kernels_fallback.hip)
+ *   ET_PATH_EXIT_MAPS  exit maps for every start offset (codes of one or two neighbouring lengths that do not settle and are neither
+ *                      fixed-length nor row codes, with or without a tree; csrc/et_kernels_fallback.hip)
  *   ET_PATH_ROWS       by byte rows and bit columns (complete codes of 7 and 8 bits that do not settle: uniform bytes; et_row_code)
  *   ET_PATH_FIXED      2^L codewords of L bits: no synchronisation, symbol i is the L bits at first_bit + i L
- *   ET_PATH_WINDOWS    the round-1 window kernels (a dictionary whose completed tree has more than 255 internal nodes or is not prefix-free) */
+ *   ET_PATH_WINDOWS    the round-1 window kernels (a dictionary whose completed tree has more than 255 internal nodes or is not
+ *                      prefix-free, unless its lengths send it to the exit maps) */
 enum { ET_PATH_TREE_WALK = 0, ET_PATH_EXIT_MAPS = 1, ET_PATH_ROWS = 2, ET_PATH_FIXED = 3, ET_PATH_WINDOWS = 4 };
 int et_decode_path(const et_codebook *cb, uint32_t *path);
 

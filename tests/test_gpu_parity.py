@@ -1077,6 +1077,8 @@ def test_fallback_sweeps_and_write_are_what_a_sparse_dictionary_runs(ctx, n):
     torch.cuda.synchronize()
     assert not t["tree_walk_sync"] and not t["chained_write"] and not t["exhaustive_sync"]
     assert out[:n].cpu().numpy().tobytes() == text.tobytes()
+    p = ctypes.c_uint32(99)
+    assert N.lib().et_decode_path(ctypes.byref(cb.raw), ctypes.byref(p)) == N.ET_OK and p.value == N.ET_PATH_WINDOWS  # (what ran)
 
 
 def test_fallback_range_sync_is_what_a_sparse_dictionary_runs(ctx):
