@@ -135,10 +135,16 @@ class Context:
 
     The *_device calls (and a Group's) take torch tensors, which torch's CURRENT stream produced and will consume, so by
     default they run on that stream: whatever stream is current when the call is made (torch.cuda.stream(...) included) is
-    the one the call is ordered on -- no synchronisation is ever needed around them.  (Until round 4 a new context ran on a
-    non-blocking stream of its own unless told otherwise, and a caller who forgot use_torch_stream() raced with the kernels
-    that made its tensors: tests/soak/soak_sharded.py found that the hard way.)  use_own_stream() / use_stream(ptr) opt out:
-    the caller then orders the streams itself.  The C ABI is unchanged: an et_ctx starts on its own stream (et_ctx_set_stream)."""
+    the one the call is ordered on.  (Until round 4 a new context ran on a non-blocking stream of its own unless told
+    otherwise, and a caller who forgot use_torch_stream() raced with the kernels that made its tensors: tests/soak/soak_sharded.py
+    found that the hard way.)  use_own_stream() / use_stream(ptr) opt out: the caller then orders those streams against the ones
+    its tensors live on.  The C ABI is unchanged: an et_ctx starts on its own stream (et_ctx_set_stream).
+
+    Calls return before their kernels finish.  Whichever way the context moves to another stream (a torch.cuda.stream block,
+    use_stream, use_own_stream, use_torch_stream), the new stream is first ordered after all the work the context enqueued on
+    the old one (include/entreepy_hip.h, "STREAM SWITCHES"), and the old stream must still exist at that moment.  So a tensor
+    this context wrote on stream A and a later call of it reads on stream B needs no synchronisation; ordering against work
+    that is not this context's stays the caller's job (torch's usual rules across streams)."""
 
     def __init__(self, device=0):
         self._h = ctypes.c_void_p()

@@ -61,6 +61,7 @@ struct et_ctx {
     hipStream_t own_stream = nullptr;
     et::SideLane side = {};  // second lane for the first/last-block launches of a decode
     hipStream_t stream = nullptr;
+    hipEvent_t switch_ev = nullptr;  // a stream switch orders the new stream after this one, recorded on the old (switch_stream)
     bool timing = false;       // every phase carries events (et_ctx_enable_timing(ctx, 1))
     bool timing_body = false;  // only the decode's write kernel does (et_ctx_enable_timing(ctx, ET_TIMING_DECODE_BODY))
     uint32_t force_rpt = 0;
@@ -168,6 +169,8 @@ int fail(et_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess) {
 int ensure(et_ctx *ctx, DevBuf &b, size_t bytes) {
     if (b.cap >= bytes) return ET_OK;
     if (b.p) {
+        // Synchronising the current stream covers every stream the ctx ran on before it: each switch (switch_stream)
+        // made the new stream wait for all the work the ctx had enqueued on the old one.
         ET_HIP(hipStreamSynchronize(ctx->stream));
         ET_HIP(hipFree(b.p));
         b.p = nullptr;
@@ -378,6 +381,7 @@ extern "C" int et_ctx_create(int device, et_ctx **out) {
     ok = ok && hipStreamCreateWithFlags(&ctx->side.stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->side.fork, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->side.join, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&ctx->switch_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_hist), (256 + et::HIST_REDUCE_GROUPS) * sizeof(uint64_t)) == hipSuccess;
     if (ok) std::memset(ctx->h_hist, 0, (256 + et::HIST_REDUCE_GROUPS) * sizeof(uint64_t));  // (no workgroup's word reads as the first epoch)
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_enc), 768 * sizeof(uint32_t) + HEADER_STAGE) == hipSuccess;
@@ -404,7 +408,7 @@ extern "C" int et_ctx_create(int device, et_ctx **out) {
 extern "C" void et_ctx_destroy(et_ctx *ctx) {
     if (!ctx) return;
     DeviceGuard guard(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);  // (and so every earlier stream of the ctx: switch_stream)
     DevBuf *bufs[] = {&ctx->tile_hist, &ctx->block_hist, &ctx->hist, &ctx->tile_bits, &ctx->tile_off, &ctx->enc_table, &ctx->group_sum,
                       &ctx->sub_state, &ctx->blk_exit, &ctx->blk_count, &ctx->blk_off, &ctx->lut, &ctx->flag,
                       &ctx->worklist, &ctx->lane_maps, &ctx->blk_maps, &ctx->grp_maps, &ctx->blk_in, &ctx->grp_in, &ctx->row_scratch,
@@ -421,19 +425,34 @@ extern "C" void et_ctx_destroy(et_ctx *ctx) {
     if (ctx->side.stream) (void)hipStreamDestroy(ctx->side.stream);
     if (ctx->side.fork) (void)hipEventDestroy(ctx->side.fork);
     if (ctx->side.join) (void)hipEventDestroy(ctx->side.join);
+    if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
     delete ctx;
 }
 
+namespace {
+
+// The ctx onto stream s: s first waits for everything the ctx enqueued on its old stream.  Calls return before their last
+// kernels finish (a decode's write pass, an encode's K4, a whole histogram), and the next call rewrites the workspaces
+// those kernels still read; one event pair per switch keeps the next call behind them wherever it runs.
+int switch_stream(et_ctx *ctx, hipStream_t s) {
+    if (s == ctx->stream) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    ET_HIP(hipEventRecord(ctx->switch_ev, ctx->stream));
+    ET_HIP(hipStreamWaitEvent(s, ctx->switch_ev, 0));
+    ctx->stream = s;
+    return ET_OK;
+}
+
+}  // namespace
+
 extern "C" int et_ctx_set_stream(et_ctx *ctx, void *hip_stream) {
     if (!ctx) return ET_ERR_ARG;
-    ctx->stream = static_cast<hipStream_t>(hip_stream);
-    return ET_OK;
+    return switch_stream(ctx, static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" int et_ctx_use_own_stream(et_ctx *ctx) {
     if (!ctx) return ET_ERR_ARG;
-    ctx->stream = ctx->own_stream;
-    return ET_OK;
+    return switch_stream(ctx, ctx->own_stream);
 }
 
 extern "C" void *et_ctx_stream(const et_ctx *ctx) { return ctx ? static_cast<void *>(ctx->stream) : nullptr; }

@@ -77,9 +77,15 @@ typedef struct et_ctx et_ctx;
 int et_ctx_create(int device, et_ctx **ctx);
 void et_ctx_destroy(et_ctx *ctx);
 /* Run on a caller-owned hipStream_t (e.g. torch's current stream) instead of the
- * ctx's own.  NULL is HIP's default (null) stream, as everywhere in HIP. */
+ * ctx's own.  NULL is HIP's default (null) stream, as everywhere in HIP.
+ * STREAM SWITCHES.  Calls return before their kernels finish.  A switch (this call or
+ * et_ctx_use_own_stream, with a stream other than the current one) orders the new stream
+ * after all the work the ctx enqueued before it, so the ctx may move between streams
+ * with its calls in flight.  The old stream must still be valid at the moment of the
+ * switch.  A buffer the ctx wrote on stream A and a later ctx call reads on stream B is
+ * therefore safe; ordering against work that is not the ctx's stays the caller's job. */
 int et_ctx_set_stream(et_ctx *ctx, void *hip_stream);
-/* Back to the non-blocking stream the ctx created for itself. */
+/* Back to the non-blocking stream the ctx created for itself (a switch, as above). */
 int et_ctx_use_own_stream(et_ctx *ctx);
 /* The hipStream_t the ctx's calls are enqueued on, and its HIP device ordinal. */
 void *et_ctx_stream(const et_ctx *ctx);
