@@ -103,7 +103,7 @@ struct DeviceGuard {
     }
 };
 
-// ---- one rank's compute: the staged entry points of et_api.cpp on its et_ctx ------------------------------------------
+// ---- one rank's compute: the staged entry points of et_api.cpp / et_decode.cpp on its et_ctx ------------------------------------------
 struct HipBackend : et_shard::Backend {
     et_ctx *ctx;
     int device;

@@ -15,6 +15,7 @@
 //            (start, exit, symbols) -- or of the 32-byte exit maps for codes that do not self-synchronise --, repair
 //            where a start is not the predecessor's exit, write.
 #include "et_shard_seq.h"
+#include "et_tables.h"
 
 #include <chrono>
 #include <cstring>
@@ -444,7 +445,7 @@ int cold_plan(const uint8_t *head, size_t head_len, uint64_t len, ColdPlan *p) {
     p->stream_bytes = len - p->base_off;
     p->n_blocks = (p->stream_bytes + 8191) / 8192;
     if (p->n_blocks > 1 && p->stream_bytes - (p->n_blocks - 1) * 8192 < 16) --p->n_blocks;
-    p->exhaustive = p->cb.n_coded > 2 && p->cb.max_length <= p->cb.min_length + 1;
+    p->exhaustive = et::nearly_fixed_length(&p->cb);
     return ET_OK;
 }
 

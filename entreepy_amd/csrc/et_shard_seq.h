@@ -1,7 +1,7 @@
 // et_shard_seq.h -- one stream over the ranks of a group (include/entreepy_hip.h, "groups"): the SEQUENCE of a
 // sharded encode, of the bit-offset-adjusted concatenation and of a cold decode (et_shard_seq.cpp; plain C++, no
 // HIP in it) and the two things that sequence is written against:
-//   Backend   what ONE rank computes on its chunk -- the staged entry points of et_api.cpp on an et_ctx
+//   Backend   what ONE rank computes on its chunk -- the staged entry points of et_api.cpp / et_decode.cpp on an et_ctx
 //             (et_shard_hip.cpp); the CPU tests link the same et_shard_seq.cpp against a stand-in of their own;
 //   Exchange  how the ranks' small rows travel: a callback of the caller's (threads, gloo, MPI) or RCCL over xGMI.
 // The reference has one thread and one buffer (encode.zig:25-337, decode.zig:13-220); nothing of this has a

@@ -42,6 +42,11 @@ constexpr uint32_t STEP_ESCAPE_BITS = 64, STEP_ESCAPE = (1u << 16) - STEP_ESCAPE
 constexpr uint32_t WSTEP_ESCAPE = (1u << 10) - STEP_ESCAPE_BITS;
 constexpr uint32_t DEC_STEP_SUB_WORDS = 1024;  // second-level entries, all tables of one step table together
 
+// A nearly fixed-length code -- codewords of L and L + 1 bits only, more than two of them -- has little to re-synchronise on: the one
+// rule behind "go the exhaustive way at once" on one GPU (et_decode.cpp plan_decode, which then looks closer) and across ranks
+// (et_shard_seq.cpp cold_plan).
+inline bool nearly_fixed_length(const et_codebook *cb) { return cb->n_coded > 2 && cb->max_length <= cb->min_length + 1; }
+
 struct HostDecodeTables {
     uint32_t lut_bits, n_long, sub_bits, n_sub;
 };

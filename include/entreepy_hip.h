@@ -302,7 +302,7 @@ typedef struct et_range_info {
     uint32_t exit_bit;    /* first codeword boundary at or after the range end, bits past it */
     uint64_t n_symbols;   /* codewords that begin inside the range */
     uint32_t sweeps;      /* synchronisation launches of this call */
-    uint32_t reserved;
+    uint32_t reserved;    /* diagnostics: what synchronised the range -- 0 window sweeps, 1 exit maps, 2 tree walk, 3 row walk */
 } et_range_info;
 
 /* d_range: 4-byte aligned pointer to the range's first byte (range_bytes long; a multiple

@@ -473,3 +473,34 @@ def test_decode_path_of_flat_alphabets():
     dup_d[[10, 11, 12]], dup_l[[10, 11, 12]] = [0b0101, 0b0101, 0b0110], 4
     assert path(E.Codebook.from_tables(dup_d, dup_l)) == "M"
 
+
+
+def test_cold_plan_takes_the_exhaustive_exchange_for_nearly_fixed_length_codes():
+    """et::nearly_fixed_length (et_tables.h), the one rule plan_decode and the group sequence's cold_plan share, seen through
+    et_decode_sharded over the CPU stand-in: a group of one with its collectives forced makes TWO exchanges for a code the rule
+    holds for (the ranges' exit maps, then the seams) and ONE otherwise (the seams), and the choice equals the expression the
+    rule replaced -- more than two codewords, all of L or L + 1 bits -- for 255 uniform bytes, a flat 10-symbol alphabet and text."""
+    import torch
+
+    from tests import corpus
+    from tests.test_sharded_cpu import ThreadGather, _cpu_group
+
+    rng = np.random.default_rng(17)
+    texts = {"uniform255": rng.integers(1, 256, size=30_000).astype(np.uint8), "flat10": rng.integers(0, 10, size=30_000).astype(np.uint8),
+             "text": corpus.text_like(30_000, 5)}
+    seen = {}
+    for name, data in texts.items():
+        et = O.encode(data)[4:]
+        cb, _, _ = E.parse_header(et)
+        lengths = np.asarray(cb.length)
+        coded = lengths[lengths > 0]
+        replaced = bool(coded.size > 2 and coded.max() <= coded.min() + 1)
+        x = ThreadGather(1)
+        g = _cpu_group(0, 1, x.of(0))
+        g.force_collectives(True)
+        out = torch.zeros(data.size + 64, dtype=torch.uint8)
+        m, first = g.decode_sharded(torch.from_numpy(np.frombuffer(et, dtype=np.uint8).copy()), out)
+        assert (m, first) == (data.size, 0) and out[:m].numpy().tobytes() == data.tobytes()
+        assert x.calls == [2 if replaced else 1], (name, x.calls, replaced)
+        seen[name] = replaced
+    assert seen == {"uniform255": True, "flat10": True, "text": False}
