@@ -75,6 +75,20 @@ class ShardInfo(ctypes.Structure):
     ]
 
 
+class BatchItem(ctypes.Structure):
+    """struct et_batch_item: one stream of et_encode_batch_device / et_decode_batch_device."""
+
+    _fields_ = [
+        ("in_off", ctypes.c_uint64),
+        ("in_len", ctypes.c_uint64),
+        ("out_off", ctypes.c_uint64),
+        ("out_cap", ctypes.c_uint64),
+        ("out_len", ctypes.c_uint64),
+        ("status", ctypes.c_int32),
+        ("path", ctypes.c_uint32),
+    ]
+
+
 # int (*et_allgather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
@@ -114,6 +128,10 @@ SIGNATURES = {
     "et_decoded_size": (ctypes.c_int, [_vp, _sz, _szp]),
     "et_encode_device": (ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
     "et_decode_device": (ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "et_encode_batch_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz]),
+    "et_decode_batch_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz]),
+    "et_batch_small_max": (_sz, []),
+    "et_batch_item_size": (_sz, []),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),
     "et_histogram_on_host": (ctypes.c_int, [_vp, _vp]),
     "et_histogram_host": (ctypes.c_int, [_vp, _vp]),

@@ -301,6 +301,63 @@ class Context:
         _check(N.lib().et_decode_device(self._h, compressed_text.data_ptr() + skip, length, out.data_ptr(), out.numel(), ctypes.byref(n)), self._h)
         return n.value
 
+    # -- batches of small streams (et_encode_batch_device / et_decode_batch_device) ------------
+    _ITEM = np.dtype([("in_off", "<u8"), ("in_len", "<u8"), ("out_off", "<u8"), ("out_cap", "<u8"), ("out_len", "<u8"), ("status", "<i4"), ("path", "<u4")])
+
+    def _batch_device(self, fn, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps):
+        assert self._ITEM.itemsize == ctypes.sizeof(N.BatchItem) == N.lib().et_batch_item_size()
+        items = np.zeros(len(in_offsets), dtype=self._ITEM)
+        items["in_off"], items["in_len"], items["out_off"], items["out_cap"] = in_offsets, in_lens, out_offsets, out_caps
+        self._bind()
+        _check(fn(self._h, in_tensor.data_ptr(), out_tensor.data_ptr(), items.ctypes.data if items.size else None, items.size), self._h)
+        return items["out_len"].copy(), items["status"].copy(), items["path"].copy()
+
+    def encode_batch_device(self, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps):
+        """Stream b: the text in_tensor[in_offsets[b] : + in_lens[b]] -> its .et image at out_tensor[out_offsets[b] : + out_caps[b]]
+        (uint8 CUDA tensors; out_caps[b] >= encode_bound(in_lens[b]), the output address a multiple of 16; outputs disjoint).
+        One call for all of them.  -> (out_lens, statuses, paths) as numpy arrays: a stream that fails (statuses[b] != 0)
+        fails alone; paths[b] = 0 by the batch kernels, 1 by the single-stream path.  Stream-ordered like encode_device."""
+        return self._batch_device(N.lib().et_encode_batch_device, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps)
+
+    def decode_batch_device(self, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps):
+        """Stream b: the .et file minus its first four bytes at in_tensor[in_offsets[b] : + in_lens[b]] -> its symbols at
+        out_tensor[out_offsets[b] : + out_caps[b]].  Returns as encode_batch_device."""
+        return self._batch_device(N.lib().et_decode_batch_device, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps)
+
+    def _batch_host(self, call, blobs, caps, what):
+        """One upload, one batch call, one download."""
+        import torch
+
+        blobs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blobs]
+        if not blobs:
+            return []
+        lens = np.array([b.size for b in blobs], dtype=np.uint64)
+        in_off = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.uint64)
+        caps = (np.asarray(caps, dtype=np.uint64) + 15) & ~np.uint64(15)
+        out_off = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        dev = torch.device("cuda", self.device)
+        packed = np.concatenate(blobs) if int(lens.sum()) else np.zeros(0, dtype=np.uint8)
+        d_in = torch.empty(max(packed.size, 1), dtype=torch.uint8, device=dev)
+        d_in[: packed.size] = torch.from_numpy(packed).to(dev)
+        d_out = torch.empty(max(int(caps.sum()), 16), dtype=torch.uint8, device=dev)
+        out_lens, statuses, _ = call(d_in, in_off, lens, d_out, out_off, caps)
+        bad = np.flatnonzero(statuses)
+        if bad.size:
+            cls = EmptyInputError if statuses[bad[0]] == N.ET_ERR_EMPTY else EntreepyError
+            raise cls(int(statuses[bad[0]]), f"{what}: item {int(bad[0])}")
+        host = d_out.cpu().numpy()  # (the copy runs on torch's current stream, behind the batch's kernels)
+        return [host[int(o) : int(o) + int(n)].tobytes() for o, n in zip(out_off, out_lens)]
+
+    def encode_batch(self, texts):
+        """[bytes] -> [their .et images], through one encode_batch_device call.  Raises EntreepyError naming the first
+        item that failed (EmptyInputError for an empty text)."""
+        return self._batch_host(self.encode_batch_device, texts, [encode_bound(len(t)) for t in texts], "encode_batch")
+
+    def decode_batch(self, compressed_texts):
+        """[.et files minus their first four bytes] -> [their texts], through one decode_batch_device call."""
+        caps = [int.from_bytes(bytes(c[1:5]), "big") + 16 if len(c) >= 5 else 16 for c in compressed_texts]
+        return self._batch_host(self.decode_batch_device, compressed_texts, caps, "decode_batch")
+
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):
         """text: uint8 CUDA tensor; hist: int64/uint64 CUDA tensor of 256 counters."""

@@ -1,0 +1,295 @@
+// et_batch.cpp -- host side of et_encode_batch_device / et_decode_batch_device (include/entreepy_hip.h): B independent
+// streams in one call.  The fixed price of a call -- its launches and its hand-over to the host -- is paid once per chunk
+// of BATCH_CHUNK streams instead of once per stream:
+//   encode   k_batch_hist -> (poll) code table + header of every stream -> one upload -> k_batch_encode
+//   decode   k_batch_heads -> (poll) et_parse_header of every stream -> one upload -> k_batch_decode -> (poll) symbol totals
+// What the batch kernels are not made for -- texts above et_batch_small_max(), codes beyond 32 bits on encode,
+// dictionaries that are not a full tree on decode -- runs through et_encode_device / et_decode_device for that stream
+// alone, behind the batch launches on the same stream (path = 1): the quirks stay where they are implemented.
+//
+// ONE pinned block serves every chunk and every call.  It may be refilled without asking because each chunk begins
+// with a kernel whose report the host polls for, and that kernel runs behind everything the ctx enqueued before it
+// (stream order; a switch of streams keeps it, et_ctx_set_stream): when its epoch word arrives, the uploads and
+// kernels of the chunk before are over.  The records that first kernel reads are written before it is enqueued, into a
+// region no later upload of a chunk reads.
+#include "et_ctx.h"
+
+#include "et_batch.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace {
+
+constexpr size_t CH = et::BATCH_CHUNK;
+// the pinned block
+constexpr size_t PIN_WORDS = 0;                                   // u64[8]: [0] k_batch_hist, [1] k_batch_heads, [2] k_batch_decode
+constexpr size_t PIN_SPANS = 64;                                  // BatchSpan[CH]
+constexpr size_t PIN_JOBS = PIN_SPANS + CH * sizeof(et::BatchSpan);  // BatchEncJob / BatchDecJob [CH]
+constexpr size_t PIN_TOTALS = PIN_JOBS + CH * sizeof(et::BatchDecJob);
+constexpr size_t PIN_REPORT = PIN_TOTALS + CH * sizeof(uint32_t);   // histograms (1 KiB per stream) or heads (BATCH_HEAD_STRIDE)
+constexpr size_t PIN_BLOB = PIN_REPORT + CH * et::BATCH_HEAD_STRIDE;
+constexpr size_t PIN_BYTES = PIN_BLOB + CH * et::BATCH_ENC_SLOT;
+static_assert(sizeof(et::BatchSpan) == 16 && sizeof(et::BatchEncJob) == 32 && sizeof(et::BatchDecJob) == 40, "job records are plain, packed data");
+static_assert(et::BATCH_HEAD_STRIDE >= 1024 && PIN_BLOB % 16 == 0 && PIN_JOBS % 8 == 0, "layout of the pinned block");
+// the device block of records: spans, then jobs
+constexpr size_t DEV_JOBS = CH * sizeof(et::BatchSpan);
+
+int ensure_batch(et_ctx *ctx, size_t n_items, size_t slot_bytes) {
+    if (!ctx->h_batch) {
+        ET_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_batch), PIN_BYTES));
+        std::memset(ctx->h_batch, 0, 64);
+    }
+    const size_t n = std::min(n_items, CH);
+    ET_TRY(ensure(ctx, ctx->batch_jobs, DEV_JOBS + n * sizeof(et::BatchDecJob)));
+    ET_TRY(ensure(ctx, ctx->batch_blob, n * slot_bytes));
+    if (!ctx->batch_counter.p) {
+        ET_TRY(ensure(ctx, ctx->batch_counter, 64));
+        ET_HIP(hipMemsetAsync(ctx->batch_counter.p, 0, 64, ctx->stream));
+    }
+    return ET_OK;
+}
+
+template <typename T>
+T *pin(et_ctx *ctx, size_t off) { return reinterpret_cast<T *>(ctx->h_batch + off); }
+
+volatile uint64_t *epoch_word(et_ctx *ctx, int which) { return pin<uint64_t>(ctx, PIN_WORDS) + which; }
+
+unsigned long long *epoch_word_dev(et_ctx *ctx, int which) { return reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_WORDS) + which); }
+
+// Outputs of different items may not overlap (items that ask for no room take none).
+bool outputs_overlap(const et_batch_item *items, size_t n) {
+    std::vector<uint32_t> order;
+    order.reserve(n);
+    for (size_t i = 0; i < n; ++i)
+        if (items[i].out_cap) order.push_back(static_cast<uint32_t>(i));
+    auto by_off = [&](uint32_t a, uint32_t b) { return items[a].out_off < items[b].out_off; };
+    if (!std::is_sorted(order.begin(), order.end(), by_off)) std::sort(order.begin(), order.end(), by_off);
+    for (size_t k = 0; k + 1 < order.size(); ++k) {
+        const et_batch_item &a = items[order[k]], &b = items[order[k + 1]];
+        if (a.out_cap > b.out_off - a.out_off) return true;
+    }
+    return false;
+}
+
+int check_call(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {
+    if (!ctx) return ET_ERR_ARG;
+    if (n_items == 0) return ET_OK;
+    if (!items || !d_in || !d_out) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (n_items > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many items");
+    for (size_t i = 0; i < n_items; ++i) {
+        items[i].out_len = 0;
+        items[i].status = ET_OK;
+        items[i].path = 0;
+    }
+    if (outputs_overlap(items, n_items)) return fail(ctx, ET_ERR_ARG, "outputs of different items overlap");
+    return ET_OK;
+}
+
+// An item's own failure is the item's; a failure of the runtime under a delegated stream is the call's.
+bool call_level(int rc) { return rc == ET_ERR_HIP || rc == ET_ERR_NOMEM; }
+
+}  // namespace
+
+extern "C" size_t et_batch_small_max(void) { return et::BATCH_SMALL_MAX; }
+
+extern "C" size_t et_batch_item_size(void) { return sizeof(et_batch_item); }
+
+extern "C" int et_encode_batch_device(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {
+    ET_TRY(check_call(ctx, d_in, d_out, items, n_items));
+    if (n_items == 0) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    uint8_t *out = static_cast<uint8_t *>(d_out);
+
+    std::vector<uint32_t> small, large;  // by the batch kernels; by et_encode_device
+    for (size_t i = 0; i < n_items; ++i) {
+        et_batch_item &it = items[i];
+        if (it.in_len == 0) it.status = ET_ERR_EMPTY;
+        else if (reinterpret_cast<uintptr_t>(out + it.out_off) & 15) it.status = ET_ERR_ARG;
+        else if (it.out_cap < et_encode_bound(it.in_len)) it.status = ET_ERR_CAP;
+        else (it.in_len > et::BATCH_SMALL_MAX ? large : small).push_back(static_cast<uint32_t>(i));
+    }
+    if (!small.empty()) ET_TRY(ensure_batch(ctx, small.size(), et::BATCH_ENC_SLOT));
+
+    for (size_t c0 = 0; c0 < small.size(); c0 += CH) {
+        const uint32_t n = static_cast<uint32_t>(std::min(CH, small.size() - c0));
+        et::BatchSpan *spans = pin<et::BatchSpan>(ctx, PIN_SPANS);
+        for (uint32_t j = 0; j < n; ++j) {
+            const et_batch_item &it = items[small[c0 + j]];
+            spans[j] = et::BatchSpan{it.in_off, static_cast<uint32_t>(it.in_len), 0};
+        }
+        uint8_t *d_rec = static_cast<uint8_t *>(ctx->batch_jobs.p);
+        ET_HIP(hipMemcpyAsync(d_rec, spans, n * sizeof(et::BatchSpan), hipMemcpyHostToDevice, ctx->stream));
+        const uint64_t epoch = ++ctx->batch_epoch;
+        et::launch_batch_hist(ctx->stream, in, reinterpret_cast<const et::BatchSpan *>(d_rec), n, pin<uint32_t>(ctx, PIN_REPORT),
+                              static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 0), epoch);
+        ET_HIP(hipGetLastError());
+        ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 0), epoch, 200.0, "the batch's histograms never reached the host"));
+
+        // per stream: encode.zig:54-299 on the host, as et_encode_device does it
+        et::BatchEncJob *jobs = pin<et::BatchEncJob>(ctx, PIN_JOBS);
+        uint8_t *blob = pin<uint8_t>(ctx, PIN_BLOB);
+        const uint32_t *counts = pin<uint32_t>(ctx, PIN_REPORT);
+        uint32_t n_jobs = 0, blob_len = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            et_batch_item &it = items[small[c0 + j]];
+            uint64_t hist[256];
+            for (int s = 0; s < 256; ++s) hist[s] = counts[static_cast<size_t>(j) * 256 + s];
+            et_codebook cb;
+            int rc = et_build_codebook(hist, &cb);
+            if (rc != ET_OK) {
+                it.status = rc;
+                continue;
+            }
+            if (cb.max_length > 32) {  // (the reference's u32 truncation, quirk Q3: k_encode_tiles_long implements it)
+                large.push_back(small[c0 + j]);
+                continue;
+            }
+            uint8_t *slot = blob + blob_len;
+            uint32_t *tab = reinterpret_cast<uint32_t *>(slot);
+            for (int s = 0; s < 256; ++s) {
+                const uint32_t len = cb.length[s], code = cb.data[s];
+                tab[2 * s] = len ? (len == 32 ? code : (code & ((1u << len) - 1u)) << (32 - len)) : 0u;  // left-aligned
+                tab[2 * s + 1] = len;
+            }
+            size_t header_len = 0;
+            rc = et_write_header(&cb, it.in_len, slot + 2048, et::BATCH_HEADER_PAD - 8, &header_len);
+            if (rc != ET_OK) {
+                it.status = rc;
+                continue;
+            }
+            const uint32_t padded = static_cast<uint32_t>((header_len + 15) & ~static_cast<size_t>(15));
+            std::memset(slot + 2048 + header_len, 0, padded - header_len);
+            uint64_t bits = 0;
+            et_codebook_bits(&cb, hist, &bits);
+            it.out_len = header_len + (bits + 7) / 8;  // encode.zig:318,336
+            jobs[n_jobs++] = et::BatchEncJob{it.in_off, it.out_off, static_cast<uint32_t>(it.in_len), static_cast<uint32_t>(header_len), blob_len, 0};
+            blob_len += 2048 + padded;
+        }
+        if (!n_jobs) continue;
+        ET_HIP(hipMemcpyAsync(d_rec + DEV_JOBS, jobs, n_jobs * sizeof(et::BatchEncJob), hipMemcpyHostToDevice, ctx->stream));
+        ET_HIP(hipMemcpyAsync(ctx->batch_blob.p, blob, blob_len, hipMemcpyHostToDevice, ctx->stream));
+        et::launch_batch_encode(ctx->stream, in, out, reinterpret_cast<const et::BatchEncJob *>(d_rec + DEV_JOBS), n_jobs,
+                                static_cast<const uint8_t *>(ctx->batch_blob.p));
+        ET_HIP(hipGetLastError());
+    }
+
+    std::sort(large.begin(), large.end());
+    for (uint32_t i : large) {
+        et_batch_item &it = items[i];
+        size_t len = 0;
+        const int rc = et_encode_device(ctx, in + it.in_off, it.in_len, out + it.out_off, it.out_cap, &len);
+        it.path = 1;
+        it.status = rc;
+        it.out_len = rc == ET_OK ? len : 0;
+        if (call_level(rc)) return rc;
+    }
+    return ET_OK;
+}
+
+extern "C" int et_decode_batch_device(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {
+    ET_TRY(check_call(ctx, d_in, d_out, items, n_items));
+    if (n_items == 0) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    uint8_t *out = static_cast<uint8_t *>(d_out);
+
+    std::vector<uint32_t> cand, large;
+    for (size_t i = 0; i < n_items; ++i) {
+        et_batch_item &it = items[i];
+        if (it.in_len < 5) it.status = ET_ERR_FORMAT;  // (as et_decode_device: shorter than its header)
+        else cand.push_back(static_cast<uint32_t>(i));
+    }
+    if (!cand.empty()) ET_TRY(ensure_batch(ctx, cand.size(), et::BATCH_DEC_SLOT));
+
+    std::vector<uint32_t> of_job(CH);
+    for (size_t c0 = 0; c0 < cand.size(); c0 += CH) {
+        const uint32_t n = static_cast<uint32_t>(std::min(CH, cand.size() - c0));
+        et::BatchSpan *spans = pin<et::BatchSpan>(ctx, PIN_SPANS);
+        for (uint32_t j = 0; j < n; ++j) {
+            const et_batch_item &it = items[cand[c0 + j]];
+            spans[j] = et::BatchSpan{it.in_off, static_cast<uint32_t>(std::min<uint64_t>(it.in_len, et::BATCH_HEAD_STRIDE)), 0};
+        }
+        uint8_t *d_rec = static_cast<uint8_t *>(ctx->batch_jobs.p);
+        ET_HIP(hipMemcpyAsync(d_rec, spans, n * sizeof(et::BatchSpan), hipMemcpyHostToDevice, ctx->stream));
+        uint64_t epoch = ++ctx->batch_epoch;
+        et::launch_batch_heads(ctx->stream, in, reinterpret_cast<const et::BatchSpan *>(d_rec), n, pin<uint32_t>(ctx, PIN_REPORT),
+                               static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 1), epoch);
+        ET_HIP(hipGetLastError());
+        ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 1), epoch, 200.0, "the batch's headers never reached the host"));
+
+        // per stream: decode.zig:34-141 on the host (et_parse_header validates), the codes sorted for k_batch_decode
+        et::BatchDecJob *jobs = pin<et::BatchDecJob>(ctx, PIN_JOBS);
+        uint8_t *blob = pin<uint8_t>(ctx, PIN_BLOB);
+        uint32_t n_jobs = 0, blob_len = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t i = cand[c0 + j];
+            et_batch_item &it = items[i];
+            const uint8_t *head = pin<uint8_t>(ctx, PIN_REPORT) + static_cast<size_t>(j) * et::BATCH_HEAD_STRIDE;
+            const size_t sent = static_cast<size_t>(std::min<uint64_t>(it.in_len, et::header_bound(head[0])));
+            et_codebook cb;
+            uint64_t n_symbols = 0;
+            size_t body_offset = 0;
+            const int rc = et_parse_header(head, sent, &cb, &n_symbols, &body_offset);
+            if (rc != ET_OK) {
+                it.status = rc;
+                continue;
+            }
+            if (body_offset > it.in_len) {
+                it.status = ET_ERR_FORMAT;
+                continue;
+            }
+            const uint64_t body_bytes = it.in_len - body_offset;
+            if (n_symbols == 0 || body_bytes == 0 || cb.n_coded == 0) continue;  // decodes to nothing (a lone symbol's bare header: Q2)
+            // a full tree: the prefix-free codes (et_parse_header) cover every 32-bit window
+            uint64_t covered = 0;
+            for (int s = 0; s < 256; ++s)
+                if (cb.length[s]) covered += 1ull << (32 - cb.length[s]);
+            if (n_symbols > et::BATCH_SMALL_MAX || covered != (1ull << 32)) {
+                large.push_back(i);
+                continue;
+            }
+            struct Code { uint32_t lo, meta; };
+            Code *codes = reinterpret_cast<Code *>(blob + blob_len);
+            uint32_t k = 0;
+            for (int s = 0; s < 256; ++s)
+                if (cb.length[s]) codes[k++] = Code{cb.length[s] == 32 ? cb.data[s] : cb.data[s] << (32 - cb.length[s]), static_cast<uint32_t>(cb.length[s]) << 8 | static_cast<uint32_t>(s)};
+            std::sort(codes, codes + k, [](const Code &a, const Code &b) { return a.lo < b.lo; });
+            // (n_symbols codewords of at most 32 bits end within 4 n_symbols bytes: the kernel's bit positions stay small)
+            const uint32_t clipped = static_cast<uint32_t>(std::min<uint64_t>(body_bytes, n_symbols * 4 + 8));
+            jobs[n_jobs] = et::BatchDecJob{it.in_off + body_offset, it.out_off, clipped, static_cast<uint32_t>(n_symbols),
+                                           static_cast<uint32_t>(std::min<uint64_t>(it.out_cap, n_symbols)), k, blob_len, 0};
+            of_job[n_jobs++] = i;
+            blob_len += (k * 8 + 15) & ~15u;
+        }
+        if (!n_jobs) continue;
+        ET_HIP(hipMemcpyAsync(d_rec + DEV_JOBS, jobs, n_jobs * sizeof(et::BatchDecJob), hipMemcpyHostToDevice, ctx->stream));
+        ET_HIP(hipMemcpyAsync(ctx->batch_blob.p, blob, blob_len, hipMemcpyHostToDevice, ctx->stream));
+        epoch = ++ctx->batch_epoch;
+        et::launch_batch_decode(ctx->stream, in, out, reinterpret_cast<const et::BatchDecJob *>(d_rec + DEV_JOBS), n_jobs,
+                                static_cast<const uint8_t *>(ctx->batch_blob.p), pin<uint32_t>(ctx, PIN_TOTALS), static_cast<uint32_t *>(ctx->batch_counter.p),
+                                epoch_word_dev(ctx, 2), epoch);
+        ET_HIP(hipGetLastError());
+        // a truncated body's length is only known to the kernel: the totals come back the way the scan report of a single decode does
+        ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 2), epoch, 2000.0, "the batch's symbol totals never reached the host"));
+        const uint32_t *totals = pin<uint32_t>(ctx, PIN_TOTALS);
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            et_batch_item &it = items[of_job[j]];
+            if (totals[j] > it.out_cap) it.status = ET_ERR_CAP;
+            else it.out_len = totals[j];
+        }
+    }
+
+    std::sort(large.begin(), large.end());
+    for (uint32_t i : large) {
+        et_batch_item &it = items[i];
+        size_t len = 0;
+        const int rc = et_decode_device(ctx, in + it.in_off, it.in_len, out + it.out_off, it.out_cap, &len);
+        it.path = 1;
+        it.status = rc;
+        it.out_len = rc == ET_OK ? len : 0;
+        if (call_level(rc)) return rc;
+    }
+    return ET_OK;
+}

@@ -1,0 +1,56 @@
+// et_batch.h -- geometry, job records and launch wrappers of et_batch.hip: many small streams in one call, ONE workgroup
+// per stream from its first byte to its last (et_encode_batch_device / et_decode_batch_device, host side et_batch.cpp).
+// Nothing here is shared with the single-stream kernels; streams these kernels are not made for go to those, whole.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace et {
+
+// The longest text the batch kernels take themselves.  A workgroup packs ~4 KiB per round and decodes 8 KiB of bitstream per
+// block, one after the other: a stream of this size keeps its workgroup for a few hundred rounds, which is about what the
+// five-launch single-stream call costs for the same bytes; beyond it the large path is the faster one.
+constexpr size_t BATCH_SMALL_MAX = 256u << 10;
+constexpr uint32_t BATCH_CHUNK = 1024;          // streams per pair of launches (bounds the pinned blocks)
+constexpr uint32_t BATCH_HEAD_STRIDE = 1544;    // header_bound(255): bytes of pinned memory per stream for k_batch_heads
+constexpr uint32_t BATCH_HEADER_PAD = 4640;     // the longest file header (4631 bytes), padded to 16
+constexpr uint32_t BATCH_ENC_SLOT = 2048 + BATCH_HEADER_PAD;  // most a stream takes of the encode block: code table + header
+constexpr uint32_t BATCH_DEC_SLOT = 2048;       // ... of the decode block: 256 x {left-aligned code, length << 8 | symbol}
+constexpr uint32_t BATCH_LUT_BITS = 11;         // k_batch_decode's first-level table
+constexpr uint32_t BATCH_STAGE_BYTES = 16384;   // k_batch_decode: symbols staged in LDS per flush
+
+struct BatchSpan {  // k_batch_hist / k_batch_heads: stream j reads d_in[in_off, in_off + in_len)
+    uint64_t in_off;
+    uint32_t in_len, pad;
+};
+
+struct BatchEncJob {
+    uint64_t in_off, out_off;  // text at d_in + in_off, image at d_out + out_off (16-byte aligned address)
+    uint32_t in_len;
+    uint32_t header_len;       // bytes of file header in front of the body
+    uint32_t blob_off;         // where in the uploaded block: 256 x {left-aligned code, length}, then the header padded to 16
+    uint32_t pad;
+};
+
+struct BatchDecJob {
+    uint64_t body_off, out_off;  // body at d_in + body_off (any alignment), symbols to d_out + out_off (any alignment)
+    uint32_t body_bytes;         // (clipped by the host to what n_symbols codewords can span)
+    uint32_t n_symbols;          // stop after this many
+    uint32_t write_cap;          // ... but store only the first write_cap of them
+    uint32_t n_codes;            // entries of the sorted code list at blob_off
+    uint32_t blob_off;
+    uint32_t pad;
+};
+
+// counter: one device word, zero between launches (the last workgroup to finish resets it and stores `epoch` into the
+// pinned *host_done, which the host polls).
+void launch_batch_hist(hipStream_t stream, const void *d_in, const BatchSpan *spans, uint32_t n, uint32_t *host_hist, uint32_t *counter,
+                       unsigned long long *host_done, unsigned long long epoch);
+void launch_batch_encode(hipStream_t stream, const void *d_in, void *d_out, const BatchEncJob *jobs, uint32_t n, const uint8_t *blob);
+void launch_batch_heads(hipStream_t stream, const void *d_in, const BatchSpan *spans, uint32_t n, uint32_t *host_heads, uint32_t *counter,
+                        unsigned long long *host_done, unsigned long long epoch);
+void launch_batch_decode(hipStream_t stream, const void *d_in, void *d_out, const BatchDecJob *jobs, uint32_t n, const uint8_t *blob,
+                         uint32_t *host_totals, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
+
+}  // namespace et

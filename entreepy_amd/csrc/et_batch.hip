@@ -1,0 +1,409 @@
+// et_batch.hip -- gfx950 kernels of the batched calls (et_batch.h): B independent small streams, one workgroup of 256
+// per stream from first byte to last, a grid-stride loop over the streams.  No workgroup ever waits for another: there is
+// no look-back, no ticket and no flag, and every loop's trip count is bounded by the stream's own length.
+//
+//   encode   k_batch_hist    256 counts per stream into pinned host memory            (encode.zig:43-47)
+//            (host: code table and header per stream, one upload)
+//            k_batch_encode  header, then the codes MSB-first, rounds of 4 KiB          (encode.zig:259-318)
+//   decode   k_batch_heads   header + dictionary bytes per stream into pinned memory   (decode.zig:34-141 runs on the host)
+//            k_batch_decode  LDS lookup table, then the body 8 KiB at a time, in order  (decode.zig:143-203)
+//
+// The three kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
+// stores the launch's epoch into a pinned word the host polls.
+#include "et_batch.h"
+
+#include "et_kernels.h"
+
+namespace et {
+
+namespace {
+
+constexpr int BB = 256;  // threads per workgroup
+
+// After the workgroup's last store to pinned memory: count it; the last one resets the counter and tells the host.
+__device__ __forceinline__ void batch_done(uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t before = atomicAdd(counter, 1u);
+        if (before == gridDim.x - 1) {
+            atomicExch(counter, 0u);
+            __threadfence_system();
+            __hip_atomic_store(host_done, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// 16 bytes of a stream that occupies [lo, hi) measured from a 16-byte aligned base: one load when the chunk lies
+// inside, byte loads of the valid bytes alone at the stream's two edges (its neighbours in the buffer are other
+// streams, or nothing).
+struct Chunk16 {
+    uint32_t w[4];
+    uint32_t valid;  // bit k: byte k belongs to the stream
+};
+
+__device__ __forceinline__ Chunk16 load16(const uint8_t *__restrict__ base, uint64_t off, uint64_t lo, uint64_t hi) {
+    Chunk16 c;
+    c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0;
+    c.valid = 0;
+    if (off >= lo && off + 16 <= hi) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(base + off);
+        c.w[0] = v.x; c.w[1] = v.y; c.w[2] = v.z; c.w[3] = v.w;
+        c.valid = 0xffffu;
+    } else if (off + 16 > lo && off < hi) {
+        for (int k = 0; k < 16; ++k) {
+            const uint64_t p = off + k;
+            if (p >= lo && p < hi) {
+                c.w[k >> 2] |= static_cast<uint32_t>(base[p]) << (8 * (k & 3));
+                c.valid |= 1u << k;
+            }
+        }
+    }
+    return c;
+}
+
+}  // namespace
+
+// --------------------------------------------------------------------------------
+// k_batch_hist: LDS counters [bin][32] as k_hist_tiles keeps them -- lane l adds to replica l & 31, its own bank
+// whatever the symbol -- 32 KiB, five workgroups per CU.  Thread = bin sums (and clears) the replicas and stores the
+// stream's 256 counts into pinned host memory.
+// --------------------------------------------------------------------------------
+__global__ __launch_bounds__(BB) void k_batch_hist(const uint8_t *__restrict__ d_in, const BatchSpan *__restrict__ spans, uint32_t n,
+                                                   uint32_t *__restrict__ host_hist, uint32_t *__restrict__ counter,
+                                                   unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    __shared__ __attribute__((aligned(16))) uint32_t sh[256 * 32];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 256 * 32; i += BB) sh[i] = 0;
+    __syncthreads();
+    uint32_t *mine = sh + (tid & 31);
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const BatchSpan sp = spans[j];
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + sp.in_off;
+        const uint8_t *base = reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15));
+        const uint64_t lo = a & 15, hi = lo + sp.in_len;
+        for (uint64_t off = static_cast<uint64_t>(tid) * 16; off < hi; off += ROUND_BYTES) {
+            const Chunk16 c = load16(base, off, lo, hi);
+            if (c.valid == 0xffffu) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) atomicAdd(mine + ((c.w[k >> 2] >> (8 * (k & 3))) & 0xffu) * 32, 1u);
+            } else if (c.valid) {
+                for (int k = 0; k < 16; ++k)
+                    if (c.valid & (1u << k)) atomicAdd(mine + ((c.w[k >> 2] >> (8 * (k & 3))) & 0xffu) * 32, 1u);
+            }
+        }
+        __syncthreads();
+        uint32_t total = 0;
+        uint4 *row = reinterpret_cast<uint4 *>(sh + tid * 32);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = (q + tid) & 7;  // (rotated: the 16-lane groups of a ds_read_b128 on different bank quads)
+            const uint4 v = row[r];
+            total += v.x + v.y + v.z + v.w;
+            row[r] = make_uint4(0, 0, 0, 0);
+        }
+        host_hist[static_cast<uint64_t>(j) * 256 + tid] = total;
+        __syncthreads();
+    }
+    batch_done(counter, host_done, epoch);
+}
+
+// --------------------------------------------------------------------------------
+// k_batch_encode: the stream's code table in LDS (2 KiB), its header copied to the image, then rounds of 4 KiB: 16 bytes
+// per lane, the lane's bit total, a workgroup scan whose sum is carried to the next round, and each lane ORs its codes
+// into an LDS image of the round's bits (big-endian words: bit b of the image is bit 31 - b % 32 of word b / 32).  Whole
+// words leave as byte-swapped dword stores; the word the round ends in is carried into the next as `pending` (the
+// header's last, partial word seeds it).  The stream's last word is stored whole, zero bits behind the body: the pad to
+// the byte of encode.zig:316, and at most 3 bytes more inside the caller's et_encode_bound.
+// LDS: 2 KiB + 16.4 KiB stage -> 8 workgroups per CU.
+// --------------------------------------------------------------------------------
+constexpr uint32_t ENC_STAGE_WORDS = ROUND_BYTES * 32 / 32 + 8;  // 4096 symbols of at most 32 bits, + the shared first word
+
+__global__ __launch_bounds__(BB) void k_batch_encode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const BatchEncJob *__restrict__ jobs,
+                                                     uint32_t n, const uint8_t *__restrict__ blob) {
+    __shared__ uint2 s_tab[256];
+    __shared__ uint32_t s_stage[ENC_STAGE_WORDS];
+    __shared__ uint32_t s_wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t i = tid; i < ENC_STAGE_WORDS; i += BB) s_stage[i] = 0;
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const BatchEncJob job = jobs[j];
+        const uint2 *tab = reinterpret_cast<const uint2 *>(blob + job.blob_off);
+        const uint32_t *hdr = reinterpret_cast<const uint32_t *>(blob + job.blob_off + 2048);
+        uint32_t *out32 = reinterpret_cast<uint32_t *>(d_out + job.out_off);
+        __syncthreads();  // (the stream before: its table and stage are done with)
+        s_tab[tid] = tab[tid];
+        const uint32_t hw = job.header_len >> 2;
+        for (uint32_t i = tid; i < hw; i += BB) out32[i] = hdr[i];
+        uint32_t pending = (job.header_len & 3) ? __builtin_bswap32(hdr[hw]) : 0u;  // (the pad behind the header is zero)
+        uint32_t carry = job.header_len * 8;  // image bits written so far
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + job.in_off;
+        const uint8_t *base = reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15));
+        const uint64_t lo = a & 15, hi = lo + job.in_len;
+        __syncthreads();
+        for (uint64_t r0 = 0; r0 < hi; r0 += ROUND_BYTES) {
+            const Chunk16 c = load16(base, r0 + static_cast<uint64_t>(tid) * 16, lo, hi);
+            uint32_t bits = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (c.valid & (1u << k)) bits += s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu].y;
+            uint32_t incl = bits;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += up;
+            }
+            if (lane == 63) s_wsum[wave] = incl;
+            __syncthreads();
+            uint32_t before = 0, round_bits = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t s = s_wsum[w];
+                if (w < wave) before += s;
+                round_bits += s;
+            }
+            if (tid == 0 && pending) atomicOr(&s_stage[0], pending);
+            // the lane's codes, from stage bit p on
+            uint32_t p = (carry & 31) + before + incl - bits;
+            uint32_t wi = p >> 5, fill = p & 31;
+            uint64_t acc = 0;
+            if (bits) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    if (!(c.valid & (1u << k))) continue;
+                    const uint2 e = s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu];
+                    if (!e.y) continue;  // (a symbol without a code: the 256-symbol quirk)
+                    acc |= (static_cast<uint64_t>(e.x) << 32) >> fill;
+                    fill += e.y;
+                    if (fill >= 32) {
+                        atomicOr(&s_stage[wi], static_cast<uint32_t>(acc >> 32));
+                        acc <<= 32;
+                        ++wi;
+                        fill -= 32;
+                    }
+                }
+                if (fill) atomicOr(&s_stage[wi], static_cast<uint32_t>(acc >> 32));
+            }
+            __syncthreads();
+            const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
+            pending = (t_bits & 31) ? s_stage[full] : 0u;
+            __syncthreads();
+            for (uint32_t i = tid; i <= full; i += BB) {
+                if (i < full) out32[w0 + i] = __builtin_bswap32(s_stage[i]);
+                s_stage[i] = 0;
+            }
+            carry += round_bits;
+            __syncthreads();
+        }
+        if (tid == 0 && (carry & 31)) out32[carry >> 5] = __builtin_bswap32(pending);
+    }
+}
+
+// --------------------------------------------------------------------------------
+// k_batch_heads: the first min(in_len, header_bound(d)) bytes of every stream (d = its first byte: the dictionary has
+// d + 1 entries, decode.zig:34) into its BATCH_HEAD_STRIDE bytes of pinned host memory, any source alignment.
+// --------------------------------------------------------------------------------
+__global__ __launch_bounds__(BB) void k_batch_heads(const uint8_t *__restrict__ d_in, const BatchSpan *__restrict__ spans, uint32_t n,
+                                                    uint32_t *__restrict__ host_heads, uint32_t *__restrict__ counter,
+                                                    unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const BatchSpan sp = spans[j];
+        if (!sp.in_len) continue;
+        const uint8_t *src = d_in + sp.in_off;
+        uint32_t len = header_bound(src[0]);
+        if (sp.in_len < len) len = sp.in_len;
+        uint32_t *dst = host_heads + static_cast<uint64_t>(j) * (BATCH_HEAD_STRIDE / 4);
+        for (uint32_t w = threadIdx.x; w * 4 < len; w += BB) {
+            uint32_t v = 0;
+            for (uint32_t k = 0; k < 4 && w * 4 + k < len; ++k) v |= static_cast<uint32_t>(src[w * 4 + k]) << (8 * k);
+            dst[w] = v;
+        }
+    }
+    batch_done(counter, host_done, epoch);
+}
+
+// --------------------------------------------------------------------------------
+// k_batch_decode.  The dictionary arrives as its codes sorted by left-aligned value; it is a full prefix-free tree (the
+// host sends nothing else here), so the code a 32-bit window begins with is the largest one not above the window: a
+// binary search of at most 8 steps.  That search fills the first-level table (2048 x u16: length << 8 | symbol, 0 = longer
+// than 11 bits) and serves the longer codes directly.
+// The body is taken 8 KiB (2048 words from its 4-byte aligned base) at a time, in order, so the bit at which a block's
+// first codeword begins is always known: the body's start, then the exit of the block before.  Lane i owns bits
+// [256 i, 256 i + 256) of the block and walks from its entry until it leaves them; its exit is lane i + 1's entry.  Lane 0's
+// entry is right from the start, so lane i's is after i trips at most: the fixed point is capped at 256 trips and exact for
+// every code, self-synchronising or not.  A codeword counts when it ends inside the body (decode.zig:143-203 stops when
+// the bits run out).  Counts are scanned, the symbols go to an LDS stage laid out at the output's own alignment, and leave
+// as aligned dword stores (bytes at the two ends).
+// LDS: 2 + 4 + 9 + 1 + 16 KiB = 33 KiB -> 4 workgroups per CU.
+// --------------------------------------------------------------------------------
+constexpr uint32_t DEC_WORDS = 2048;                                 // words per block
+constexpr uint32_t DEC_STAGED = DEC_WORDS + 2;                       // + what a window at the block's last bits reads
+__device__ __forceinline__ uint32_t padded(uint32_t k) { return k + (k >> 3); }  // lanes 8 words apart on different banks
+
+struct BatchDecLds {
+    uint2 codes[256];
+    uint16_t lut[1u << BATCH_LUT_BITS];
+    uint32_t bits[DEC_STAGED + (DEC_STAGED >> 3) + 2];
+    uint32_t entry[BB + 1];
+    uint32_t wsum[4];
+    uint32_t out[BATCH_STAGE_BYTES / 4 + 2];
+};
+
+__device__ __forceinline__ uint32_t find_code(const BatchDecLds &s, uint32_t n_codes, uint32_t win) {
+    uint32_t lo = 0, hi = n_codes;  // codes[0] is the all-zero code of a full tree: codes[lo].x <= win throughout
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s.codes[mid].x <= win) lo = mid; else hi = mid;
+    }
+    return s.codes[lo].y;
+}
+
+// The lane's walk from `entry` (bits into its subsequence).  Returns its exit; *count = codewords that end at or before
+// the body's last bit (`room` = bits from the lane's first bit to there; <= 0 when the lane lies behind the body).
+// WRITE: symbol number first + k goes to stage byte first + k - s0 + align for numbers in [s0, s1).
+template <bool WRITE>
+__device__ __forceinline__ uint32_t walk(BatchDecLds &s, uint32_t n_codes, uint32_t lane_bit, uint32_t entry, int64_t room, uint32_t *count,
+                                         uint32_t first = 0, uint32_t s0 = 0, uint32_t s1 = 0, uint32_t align = 0) {
+    uint32_t pos = entry, cnt = 0;
+    uint8_t *stage = reinterpret_cast<uint8_t *>(s.out);
+    while (pos < 256) {
+        const uint32_t p = lane_bit + pos, k = p >> 5, sh = p & 31;
+        const uint64_t two = (static_cast<uint64_t>(s.bits[padded(k)]) << 32) | s.bits[padded(k + 1)];
+        const uint32_t win = static_cast<uint32_t>((two << sh) >> 32);
+        uint32_t meta = s.lut[win >> (32 - BATCH_LUT_BITS)];
+        if (!meta) meta = find_code(s, n_codes, win);
+        const uint32_t len = meta >> 8;
+        if (static_cast<int64_t>(pos + len) > room) {  // the bits ran out inside this codeword: nothing behind it is one,
+            pos = 512;                                  // so the next lane's entry (256) lies behind ITS bits as well
+            break;
+        }
+        if (WRITE) {
+            const uint32_t idx = first + cnt;
+            if (idx >= s1) break;
+            if (idx >= s0) stage[idx - s0 + align] = static_cast<uint8_t>(meta);
+        }
+        ++cnt;
+        pos += len;
+    }
+    *count = cnt;
+    return pos;
+}
+
+__global__ __launch_bounds__(BB) void k_batch_decode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const BatchDecJob *__restrict__ jobs,
+                                                     uint32_t n, const uint8_t *__restrict__ blob, uint32_t *__restrict__ host_totals,
+                                                     uint32_t *__restrict__ counter, unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    __shared__ BatchDecLds s;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const BatchDecJob job = jobs[j];
+        __syncthreads();  // (the stream before is done with the tables)
+        if (tid < job.n_codes) s.codes[tid] = reinterpret_cast<const uint2 *>(blob + job.blob_off)[tid];
+        __syncthreads();
+        for (uint32_t e = tid; e < (1u << BATCH_LUT_BITS); e += BB) {
+            const uint32_t meta = find_code(s, job.n_codes, e << (32 - BATCH_LUT_BITS));
+            s.lut[e] = (meta >> 8) <= BATCH_LUT_BITS ? static_cast<uint16_t>(meta) : static_cast<uint16_t>(0);
+        }
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + job.body_off;
+        const uint32_t *words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
+        const uint32_t first_bit = static_cast<uint32_t>(a & 3) * 8;
+        const uint32_t end_bit = first_bit + job.body_bytes * 8;  // the body's last bit + 1, from the aligned base
+        const uint32_t n_words = (end_bit + 31) >> 5, n_blocks = (n_words + DEC_WORDS - 1) / DEC_WORDS;
+        uint8_t *out = d_out + job.out_off;
+        uint32_t start = first_bit, done = 0;  // the block's first codeword; symbols so far
+        for (uint32_t blk = 0; blk < n_blocks && done < job.n_symbols; ++blk) {
+            __syncthreads();  // (the block before is done with the stages and entry[BB])
+            for (uint32_t k = tid; k < DEC_STAGED; k += BB) {
+                const uint32_t g = blk * DEC_WORDS + k;
+                s.bits[padded(k)] = g < n_words ? __builtin_bswap32(words[g]) : 0u;  // (an aligned word that holds a body byte; zeros behind)
+            }
+            s.entry[tid] = tid == 0 ? start : 0u;
+            __syncthreads();
+            const uint32_t lane_bit = tid * 256;
+            const int64_t room = static_cast<int64_t>(end_bit) - (static_cast<int64_t>(blk) * DEC_WORDS * 32 + lane_bit);
+            uint32_t used = 0xffffffffu, exit = 256, count = 0;
+            for (uint32_t trip = 0; trip < BB; ++trip) {
+                const uint32_t mine = s.entry[tid];
+                int changed = 0;
+                if (mine != used) {
+                    const uint32_t was = exit;
+                    exit = room > 0 ? walk<false>(s, job.n_codes, lane_bit, mine, room, &count) : 256u;
+                    used = mine;
+                    changed = exit != was || trip == 0;
+                }
+                __syncthreads();
+                if (changed) s.entry[tid + 1] = exit - 256;
+                if (!__syncthreads_or(changed)) break;
+            }
+            // counts -> where the lane's symbols go
+            uint32_t incl = count;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = __shfl_up(incl, d, 64);
+                if (lane >= static_cast<uint32_t>(d)) incl += up;
+            }
+            if (lane == 63) s.wsum[wave] = incl;
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < 4; ++w) {
+                const uint32_t v = s.wsum[w];
+                if (w < wave) before += v;
+                total += v;
+            }
+            const uint32_t first = before + incl - count;
+            const uint32_t left = job.n_symbols - done, take = total < left ? total : left;
+            const uint32_t cap_left = job.write_cap > done ? job.write_cap - done : 0u, n_write = take < cap_left ? take : cap_left;
+            for (uint32_t s0 = 0; s0 < n_write; s0 += BATCH_STAGE_BYTES) {
+                const uint32_t s1 = s0 + BATCH_STAGE_BYTES < n_write ? s0 + BATCH_STAGE_BYTES : n_write;
+                uint8_t *dst = out + done + s0;
+                const uint32_t align = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3);
+                if (count && first < s1 && first + count > s0) {
+                    uint32_t again;
+                    (void)walk<true>(s, job.n_codes, lane_bit, used, room, &again, first, s0, s1, align);
+                }
+                __syncthreads();
+                const uint32_t lo = align, hi = align + (s1 - s0);  // stage bytes [lo, hi) -> dst - align + [lo, hi)
+                uint8_t *line = dst - align;
+                const uint8_t *stage = reinterpret_cast<const uint8_t *>(s.out);
+                for (uint32_t w = tid; w * 4 < hi; w += BB) {
+                    if (w * 4 >= lo && w * 4 + 4 <= hi) {
+                        reinterpret_cast<uint32_t *>(line)[w] = s.out[w];
+                    } else {
+                        for (uint32_t b = w * 4; b < w * 4 + 4; ++b)
+                            if (b >= lo && b < hi) line[b] = stage[b];
+                    }
+                }
+                __syncthreads();
+            }
+            start = s.entry[BB];
+            done += take;
+        }
+        if (tid == 0) host_totals[j] = done;
+    }
+    batch_done(counter, host_done, epoch);
+}
+
+// --------------------------------------------------------------------------------
+static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
+
+void launch_batch_hist(hipStream_t stream, const void *d_in, const BatchSpan *spans, uint32_t n, uint32_t *host_hist, uint32_t *counter,
+                       unsigned long long *host_done, unsigned long long epoch) {
+    hipLaunchKernelGGL(k_batch_hist, dim3(batch_grid(n)), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_in), spans, n, host_hist, counter, host_done, epoch);
+}
+
+void launch_batch_encode(hipStream_t stream, const void *d_in, void *d_out, const BatchEncJob *jobs, uint32_t n, const uint8_t *blob) {
+    hipLaunchKernelGGL(k_batch_encode, dim3(batch_grid(n)), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), jobs, n, blob);
+}
+
+void launch_batch_heads(hipStream_t stream, const void *d_in, const BatchSpan *spans, uint32_t n, uint32_t *host_heads, uint32_t *counter,
+                        unsigned long long *host_done, unsigned long long epoch) {
+    hipLaunchKernelGGL(k_batch_heads, dim3(batch_grid(n)), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_in), spans, n, host_heads, counter, host_done, epoch);
+}
+
+void launch_batch_decode(hipStream_t stream, const void *d_in, void *d_out, const BatchDecJob *jobs, uint32_t n, const uint8_t *blob,
+                         uint32_t *host_totals, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
+    hipLaunchKernelGGL(k_batch_decode, dim3(batch_grid(n)), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), jobs, n, blob,
+                       host_totals, counter, host_done, epoch);
+}
+
+}  // namespace et

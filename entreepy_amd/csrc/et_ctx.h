@@ -93,6 +93,11 @@ struct et_ctx {
     DevBuf io_in, io_out;
     et_io::Pipe *io = nullptr;  // pinned double buffer + copy threads, made on first use
 
+    // the batched calls (et_batch.cpp): job records and the uploaded block of the current chunk, the kernels' completion counter
+    DevBuf batch_jobs, batch_blob, batch_counter;
+    uint8_t *h_batch = nullptr;     // pinned: epoch words, job records, what the kernels report, the block to upload (made on first use)
+    uint64_t batch_epoch = 0;       // the h_batch epoch word of a launch == batch_epoch: its report is there
+
     // pinned host staging
     uint64_t *h_hist = nullptr;     // 256
     uint32_t *h_enc = nullptr;      // 768 words: {code,len} x 256, then len x 256; HEADER_STAGE bytes: the file header on its way to the image

@@ -219,6 +219,38 @@ int et_encode_device(et_ctx *ctx, const void *d_text, size_t n,
 int et_decode_device(et_ctx *ctx, const void *d_compressed, size_t len,
                      void *d_out, size_t cap, size_t *out_len);
 
+/* ---- batches of small streams ------------------------------------------------------------------- */
+/* The calls above cost about 0.05 ms each before the first byte moves (their launches, and a hand-over to the host
+ * for the code table / the dictionary); a caller with ten thousand pages or records pays that ten thousand times.
+ * These two take B independent streams in ONE call: one workgroup per stream, two launches and one hand-over per
+ * 1024 streams (csrc/et_batch.h).  The reference has no counterpart (one file per run, main.zig:186-204); every
+ * stream's result is exactly what et_encode_device / et_decode_device give for it alone.
+ * Stream b reads d_in[in_off, in_off + in_len) and may write d_out[out_off, out_off + out_cap), nothing else.
+ *   encode: input = text (any alignment); output = the complete .et image; out_cap >= et_encode_bound(in_len),
+ *           d_out + out_off 16-byte aligned.
+ *   decode: input = the .et file minus its first 4 bytes (any alignment); out_cap >= the symbols it holds.
+ * The return value is about the call: ET_ERR_ARG (a null pointer; outputs of two items that overlap -- checked
+ * on the host before anything is enqueued), ET_ERR_HIP, ET_ERR_NOMEM.  What became of stream b is in
+ * items[b].status -- ET_ERR_EMPTY (no text), ET_ERR_CAP, ET_ERR_FORMAT, ET_ERR_UNSUPPORTED (a code beyond 32 bits in
+ * a dictionary) -- and a stream that fails fails alone.  n_items == 0 is ET_OK and enqueues nothing.
+ * Stream-ordered like et_encode_device: out_len and status are final on return, the bytes once the ctx's stream
+ * has drained.  Streams the batch kernels are not made for -- texts above et_batch_small_max(), codes beyond 32 bits
+ * on encode, dictionaries that are not a full tree on decode -- run through et_encode_device / et_decode_device
+ * inside the same call (path = 1; then d_out + out_off must be 16-byte aligned for a decode, too). */
+typedef struct et_batch_item {
+    uint64_t in_off, in_len;
+    uint64_t out_off, out_cap;
+    uint64_t out_len;   /* result: bytes produced (0 unless status == ET_OK) */
+    int32_t status;     /* result: this stream's et_status */
+    uint32_t path;      /* result: 0 = the batch kernels, 1 = the single-stream path */
+} et_batch_item;
+int et_encode_batch_device(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items, size_t n_items);
+int et_decode_batch_device(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items, size_t n_items);
+/* The longest text the batch kernels take themselves, and sizeof(et_batch_item) as the library was built (bindings
+ * check their mirror of the struct against it). */
+size_t et_batch_small_max(void);
+size_t et_batch_item_size(void);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

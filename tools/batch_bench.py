@@ -1,0 +1,135 @@
+"""Many small streams: the batched calls against a loop over the single-stream calls (bench.py is untouched by this).
+
+For each shape (1 024 x 64 KiB and 4 096 x 4 KiB of text-like data, resident in HBM) three legs are timed, each in a child
+process of its own so that every leg loads exactly one build of the library:
+  single_parent   et_encode_device / et_decode_device, one call per stream -- on the library named by --parent-lib (a build of
+                  the commit before the batched calls; it does not export them).  Left out when no such build is given.
+  single          the same loop on this tree's library (ET_LIB_PATH, or entreepy_amd/libentreepy_hip.so): shows that the
+                  single-stream calls did not move.
+  batch           et_encode_batch_device / et_decode_batch_device, one call per shape, on this tree's library.
+Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
+REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
+text once before timing.  One JSON line on stdout (and into --out).
+
+    python tools/batch_bench.py --parent-lib /path/to/parent/libentreepy_hip.so --out profiles/batch_bench.json
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = [(1024, 64 * 1024), (4096, 4 * 1024)]
+REPS, WARMUP = 20, 3
+
+
+def _leg(leg, lib_path):
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+    from tests import corpus
+
+    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_encode_bound", "et_encode_device", "et_decode_device", "et_last_error"]
+    if leg == "batch":
+        names += ["et_encode_batch_device", "et_decode_batch_device"]
+    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)  # (torch is imported: the process-wide HIP runtime is loaded)
+    dev = torch.device("cuda", 0)
+    h = ctypes.c_void_p()
+    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
+    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+    results = {}
+    for count, size in SHAPES:
+        text = corpus.text_like_torch(count * size, 0xB47C4 + size, dev)
+        bound = L.et_encode_bound(size)
+        enc = torch.zeros(count * bound + 64, dtype=torch.uint8, device=dev)
+        dec = torch.zeros(count * (size + 16) + 64, dtype=torch.uint8, device=dev)
+        enc_len = np.zeros(count, dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        item = np.dtype([(name, {ctypes.c_uint64: "<u8", ctypes.c_int32: "<i4", ctypes.c_uint32: "<u4"}[t]) for name, t in N.BatchItem._fields_])
+        idx = np.arange(count, dtype=np.uint64)
+        items_e, items_d = np.zeros(count, dtype=item), np.zeros(count, dtype=item)
+        items_e["in_off"], items_e["in_len"], items_e["out_off"], items_e["out_cap"] = idx * size, size, idx * bound, bound
+        items_d["in_off"], items_d["out_off"], items_d["out_cap"] = idx * bound + 4, idx * (size + 16), size + 16
+
+        def encode_all():
+            if leg == "batch":
+                assert L.et_encode_batch_device(h, text.data_ptr(), enc.data_ptr(), items_e.ctypes.data, count) == 0, L.et_last_error(h)
+                enc_len[:] = items_e["out_len"]
+            else:
+                for i in range(count):
+                    assert L.et_encode_device(h, text.data_ptr() + i * size, size, enc.data_ptr() + i * bound, bound, ctypes.byref(n)) == 0, L.et_last_error(h)
+                    enc_len[i] = n.value
+
+        def decode_all():
+            if leg == "batch":
+                items_d["in_len"] = enc_len - np.uint64(4)
+                assert L.et_decode_batch_device(h, enc.data_ptr(), dec.data_ptr(), items_d.ctypes.data, count) == 0, L.et_last_error(h)
+                assert not items_d["status"].any() and (items_d["out_len"] == size).all()
+            else:
+                for i in range(count):
+                    assert L.et_decode_device(h, enc.data_ptr() + i * bound + 4, int(enc_len[i]) - 4, dec.data_ptr() + i * (size + 16), size + 16, ctypes.byref(n)) == 0, L.et_last_error(h)
+
+        encode_all()
+        decode_all()
+        torch.cuda.synchronize()
+        assert torch.equal(dec[: count * (size + 16)].view(count, size + 16)[:, :size].reshape(-1), text), "decoded bytes differ from the text"
+        if leg == "batch":
+            assert not items_e["status"].any() and not items_e["path"].any() and not items_d["path"].any()
+        enc_ms, dec_ms = [], []
+        for rep in range(WARMUP + REPS):
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record()
+            encode_all()
+            e1.record()
+            decode_all()
+            e2.record()
+            e2.synchronize()
+            if rep >= WARMUP:
+                enc_ms.append(e0.elapsed_time(e1))
+                dec_ms.append(e1.elapsed_time(e2))
+        both = [a + b for a, b in zip(enc_ms, dec_ms)]
+        results[f"{count}x{size}"] = {
+            "encode_ms": round(statistics.median(enc_ms), 4), "decode_ms": round(statistics.median(dec_ms), 4),
+            "roundtrip_ms": round(statistics.median(both), 4), "roundtrip_min_ms": round(min(both), 4), "roundtrip_max_ms": round(max(both), 4),
+            "text_gb_per_s": round(2 * count * size / statistics.median(both) / 1e6, 2),
+        }
+        del text, enc, dec
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
+    ap.add_argument("--out")
+    ap.add_argument("--leg")  # (internal: the child processes)
+    ap.add_argument("--lib")
+    a = ap.parse_args()
+    if a.leg:
+        return _leg(a.leg, a.lib)
+    here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
+    legs = ([("single_parent", "single", a.parent_lib)] if a.parent_lib else []) + [("single", "single", here), ("batch", "batch", here)]
+    out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP}
+    for name, leg, lib in legs:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib], capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout + r.stderr)
+            sys.exit(f"leg {name} failed ({r.returncode})")
+        out[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    base = out.get("single_parent", out["single"])
+    out["speedup_vs_" + ("parent" if a.parent_lib else "single")] = {k: round(base[k]["roundtrip_ms"] / out["batch"][k]["roundtrip_ms"], 1) for k in out["batch"]}
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
