@@ -10,9 +10,11 @@
 //
 // The three kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
+//
+// The workgroup scans and the hand-over itself are et_device.h's.
 #include "et_batch.h"
 
-#include "et_kernels.h"
+#include "et_device.h"
 
 namespace et {
 
@@ -22,14 +24,13 @@ constexpr int BB = 256;  // threads per workgroup
 
 // After the workgroup's last store to pinned memory: count it; the last one resets the counter and tells the host.
 __device__ __forceinline__ void batch_done(uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
-    __threadfence_system();
+    pinned_stores_visible();
     __syncthreads();
     if (threadIdx.x == 0) {
         const uint32_t before = atomicAdd(counter, 1u);
         if (before == gridDim.x - 1) {
             atomicExch(counter, 0u);
-            __threadfence_system();
-            __hip_atomic_store(host_done, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            hand_over(host_done, epoch);
         }
     }
 }
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(BB) void k_batch_encode(const uint8_t *__restrict__
     __shared__ uint2 s_tab[256];
     __shared__ uint32_t s_stage[ENC_STAGE_WORDS];
     __shared__ uint32_t s_wsum[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     for (uint32_t i = tid; i < ENC_STAGE_WORDS; i += BB) s_stage[i] = 0;
     for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
         const BatchEncJob job = jobs[j];
@@ -147,24 +148,11 @@ __global__ __launch_bounds__(BB) void k_batch_encode(const uint8_t *__restrict__
 #pragma unroll
             for (int k = 0; k < 16; ++k)
                 if (c.valid & (1u << k)) bits += s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu].y;
-            uint32_t incl = bits;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += up;
-            }
-            if (lane == 63) s_wsum[wave] = incl;
-            __syncthreads();
-            uint32_t before = 0, round_bits = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t s = s_wsum[w];
-                if (w < wave) before += s;
-                round_bits += s;
-            }
+            uint32_t round_bits;
+            const uint32_t before = block_exclusive_scan(bits, s_wsum, &round_bits);  // (s_wsum: the barriers below lie between two rounds' scans)
             if (tid == 0 && pending) atomicOr(&s_stage[0], pending);
             // the lane's codes, from stage bit p on
-            uint32_t p = (carry & 31) + before + incl - bits;
+            uint32_t p = (carry & 31) + before;
             uint32_t wi = p >> 5, fill = p & 31;
             uint64_t acc = 0;
             if (bits) {
@@ -293,7 +281,7 @@ __global__ __launch_bounds__(BB) void k_batch_decode(const uint8_t *__restrict__
                                                      uint32_t n, const uint8_t *__restrict__ blob, uint32_t *__restrict__ host_totals,
                                                      uint32_t *__restrict__ counter, unsigned long long *__restrict__ host_done, unsigned long long epoch) {
     __shared__ BatchDecLds s;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
         const BatchDecJob job = jobs[j];
         __syncthreads();  // (the stream before is done with the tables)
@@ -335,22 +323,8 @@ __global__ __launch_bounds__(BB) void k_batch_decode(const uint8_t *__restrict__
                 if (!__syncthreads_or(changed)) break;
             }
             // counts -> where the lane's symbols go
-            uint32_t incl = count;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, 64);
-                if (lane >= static_cast<uint32_t>(d)) incl += up;
-            }
-            if (lane == 63) s.wsum[wave] = incl;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < 4; ++w) {
-                const uint32_t v = s.wsum[w];
-                if (w < wave) before += v;
-                total += v;
-            }
-            const uint32_t first = before + incl - count;
+            uint32_t total;
+            const uint32_t first = block_exclusive_scan(count, s.wsum, &total);  // (s.wsum: the next block's first barrier lies between two scans)
             const uint32_t left = job.n_symbols - done, take = total < left ? total : left;
             const uint32_t cap_left = job.write_cap > done ? job.write_cap - done : 0u, n_write = take < cap_left ? take : cap_left;
             for (uint32_t s0 = 0; s0 < n_write; s0 += BATCH_STAGE_BYTES) {

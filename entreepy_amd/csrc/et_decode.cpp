@@ -437,10 +437,10 @@ struct WriteExtras {
 int write_span(et_ctx *ctx, const Span &s, Family family, uint64_t clamp, uint8_t *out, const WriteExtras &x = {}) {
     switch (family == Family::ROWS && !x.by_rows ? Family::EXIT_MAPS : family) {
     case Family::ROWS:  // by rows (et_rowsync.h): no table chain, no bank conflicts between the lanes' regions
-        et::launch_row_write(ctx->stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.row_code, s.cb, s.sub_state, s.blk_off, clamp, out, x.ev.start, x.ev.stop);
+        et::launch_row_write(ctx->stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.row_code, s.cb, s.sub_state, s.blk_off, clamp, out, x.ev);
         break;
     case Family::FIXED_WRITE:  // symbol i is the L bits at first_bit + i L (et_rowsync.h): no walk, no state
-        et::launch_fixed_write(ctx->stream, s.words, s.n_bytes, s.first_bit, s.cb, clamp, out, x.ev.start, x.ev.stop);
+        et::launch_fixed_write(ctx->stream, s.words, s.n_bytes, s.first_bit, s.cb, clamp, out, x.ev);
         break;
     default:  // over the chained tables (s.chain) or the window tables'
         et::launch_dec_write(ctx->stream, s.words, s.n_bytes, s.n_subs, s.tb_write, s.sub_state, s.blk_off, clamp, out, s.flag + x.ticket, x.side, x.ticket_is_zero, x.void_flags,

@@ -110,10 +110,6 @@ void launch_dec_maps(hipStream_t stream, const uint32_t *words, uint64_t n_bytes
 void launch_dec_resolve(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, bool const_first, uint64_t n_subs,
                         const DecodeTables &tb, uint32_t map_stride, const uint8_t *lane_maps, const uint8_t *blk_maps, const uint8_t *grp_maps,
                         uint8_t *blk_in, uint8_t *grp_in, uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count);
-void launch_dec_exhaustive(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs,
-                           const DecodeTables &tb, uint32_t n_starts, uint32_t map_stride, uint8_t *lane_maps, uint8_t *blk_maps,
-                           uint8_t *grp_maps, uint8_t *blk_in, uint8_t *grp_in, uint32_t *sub_state, uint32_t *blk_exit,
-                           uint32_t *blk_count);
 // Fill the decode tables on the device from the host's plan (d_plan in device memory).  Layout of
 // the outputs as the host builders': lut[1 << lut_bits], longc[2 * n_long], sub[n_sub << sub_bits],
 // sym_len[256], steps[(1 << step_bits) + second level], wsteps[(1 << wstep_bits) + second level].

@@ -15,6 +15,8 @@
 // Encode side: a "round" is 4 KiB of input, one 16-byte load per lane, fully
 // coalesced; a "tile" is 1..16 consecutive rounds and is the unit for which K1
 // leaves a 256-bin histogram and K4 gets a start bit offset.
+// Scans, the guarded stream word, the hand-over to the host that polls, launch helpers: et_device.h; what this file shares
+// with et_kernels_fallback.hip alone: et_kernels_common.h.
 #include "et_kernels_common.h"
 #include "et_treewalk.h"
 
@@ -216,8 +218,7 @@ __global__ __launch_bounds__(BLOCK) void k_hist_reduce(const unsigned long long 
             // for the stream (no completion signal, no wake-up in between)
             host_hist[2 * blockIdx.x] = t0;
             host_hist[2 * blockIdx.x + 1] = t1;
-            __threadfence_system();
-            __hip_atomic_store(host_hist + 256 + blockIdx.x, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            hand_over(host_hist + 256 + blockIdx.x, epoch);
         }
     }
 }
@@ -237,9 +238,9 @@ __global__ __launch_bounds__(1024) void k_header_to_host(const uint8_t *__restri
         for (uint32_t k = 0; k < 4 && w * 4 + k < n; ++k) v |= static_cast<uint32_t>(src[w * 4 + k]) << (8 * k);
         host_dst[w] = v;
     }
-    __threadfence_system();
+    pinned_stores_visible();
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(host_done, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (threadIdx.x == 0) store_epoch(host_done, epoch);
 }
 
 // n_words dwords of device memory into pinned host memory, then `epoch` into *host_done (the gathered histograms of
@@ -247,9 +248,9 @@ __global__ __launch_bounds__(1024) void k_header_to_host(const uint8_t *__restri
 __global__ __launch_bounds__(1024) void k_words_to_host(const uint32_t *__restrict__ src, uint32_t n_words, uint32_t *__restrict__ host_dst,
                                                         unsigned long long *__restrict__ host_done, unsigned long long epoch) {
     for (uint32_t w = threadIdx.x; w < n_words; w += 1024) host_dst[w] = src[w];
-    __threadfence_system();
+    pinned_stores_visible();
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(host_done, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (threadIdx.x == 0) store_epoch(host_done, epoch);
 }
 
 // --------------------------------------------------------------------------------
@@ -392,8 +393,9 @@ __global__ __launch_bounds__(1024) void k_scan_fused(const T *__restrict__ in, u
             if (verify_state) report_dst[2] = (bad_before || bad_any) ? 1u : 0u;
             report_dst[12] = static_cast<uint32_t>(total);
             report_dst[13] = static_cast<uint32_t>(total >> 32);
-            __threadfence_system();
-            // word 14: "the report is there" -- the host polls it (no event behind this kernel, no wake-up)
+            // word 14: "the report is there" -- the host polls it (no event behind this kernel, no wake-up).  hand_over() spelt
+            // out: with the store inside a function, both k_scan_fused instantiations swap the operands of one v_or_b32 (psum).
+            pinned_stores_visible();
             __hip_atomic_store(report_dst + 14, report_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
@@ -663,10 +665,6 @@ typedef __attribute__((address_space(3))) unsigned long long lds_u64;
 // MODE 3 of walk_write_chain: a lane's strip -- c <= 66 bytes at LDS address `at` (4-byte aligned) -- to dst, wherever that lies
 // (gfx950 takes unaligned global stores; the pieces are 16, 8, 4, 2, 1 bytes and never reach past dst + c: behind it lies the next lane's output).
 __device__ __forceinline__ void strip_flush(uint32_t at, uint32_t c, uint8_t *dst) {
-#ifdef ET_PROBE_STRIPS_NO_FLUSH  // (timing probe, wrong output: what the strips' way out costs -- 0.27 -> 0.13 ms at 90 % zeros, 0.20 -> 0.13 at 97 %, 256 MiB)
-    (void)at, (void)c, (void)dst;
-    return;
-#endif
     typedef __attribute__((address_space(3))) uint32_t lds_u32_;
     typedef __attribute__((address_space(3))) uint16_t lds_u16_;
     typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
@@ -776,18 +774,12 @@ __device__ __forceinline__ void walk_write_chain(const ChainWalk cw, uint8_t *sm
         else CH_STEP_SAFE(hi_, lo_)                   \
     }                                                 \
     X += 32;
-// (timing probe, wrong output: the strips' pieces side by side and 16-byte aligned -- lane l's at 64 l of a 4 KiB row per flush -- instead of where they belong)
-#ifdef ET_PROBE_STRIPS_DENSE_DST
-#define ET_PROBE_STRIPS_STEP(c_) 4096u
-#else
-#define ET_PROBE_STRIPS_STEP(c_) (c_)
-#endif
 // MODE 3: two words hold at most 64 codewords; what they left in the strip goes to its place in the output and the strip begins anew
 #define CH_FLUSH()                                                              \
     if (MODE == 3) {                                                            \
         const uint32_t c_ = (X >> 10) - pos0;                                   \
         strip_flush(pos0 + 1u, c_, gdst);                                       \
-        gdst += ET_PROBE_STRIPS_STEP(c_);                                       \
+        gdst += c_;                                                             \
         X = (X & 1023u) | (pos0 << 10);                                         \
     }
     CH_WORD_FAST(W[3], W[4])  // only lanes that start at bit 0
@@ -846,19 +838,6 @@ constexpr uint32_t WV_STAGE_ALLOC = WV_STAGE + 32;
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) { return __builtin_amdgcn_readlane(wave_inclusive_scan(x), 63); }
 
-// (round-4 probe, timing only -- wrong offsets: what D3 would load if D1 handed it per-quarter prefixes: its own state word, not the four quarters')
-// (round-4 probe, timing only -- wrong output: the write pass with its stream words served from the L2 (the stream's first 64 KiB over and
-// over): the floor of the write PHASE of a kernel that has the block in registers already and loads nothing)
-#ifdef ET_PROBE_D3_L2_LOADS
-#define ET_PROBE_D3_SRC(sub_) (((sub_) & 2047u) + 16u)
-#else
-#define ET_PROBE_D3_SRC(sub_) (sub_)
-#endif
-#ifdef ET_PROBE_D3_ONE_STATE
-#define ET_PROBE_ONE_STATE_COND &&q == quarter_
-#else
-#define ET_PROBE_ONE_STATE_COND
-#endif
 // STRIPS (a second instantiation, for streams with more than 128 symbols per 256-bit subsequence -- the host's rule is n_symbols / 128
 // > n_subs, unless ET_NO_STRIPS=1 -- such as a dominant symbol with a 1- or 2-bit codeword, or alphabets of a few symbols): a quarter
 // whose output does not fit the stage is not walked once per 4 KiB window of its output (3-4 times on such streams) but ONCE, every lane into a strip of its own (WS_STRIDE bytes of what is the stage otherwise),
@@ -906,7 +885,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dec_write_wave(const uint32_t *_
         n_edge = block_limit(n_bytes, b_) != 0xffffffffu;                                                         \
         _Pragma("unroll") for (uint32_t q = 0; q < 4; ++q) {                                                      \
             const uint64_t sg = b_ * BLOCK + q * 64 + lane;                                                       \
-            n_stq[q] = (sg < n_subs ET_PROBE_ONE_STATE_COND) ? sub_state[sg] : 0u;                                \
+            n_stq[q] = sg < n_subs ? sub_state[sg] : 0u;                                                          \
         }                                                                                                         \
         const uint64_t sub_g_ = b_ * BLOCK + quarter_ * 64 + lane;                                                \
         if (sub_g_ < n_subs) {                                                                                    \
@@ -914,7 +893,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dec_write_wave(const uint32_t *_
                 _Pragma("unroll") for (int j = 0; j < RW_WORDS; ++j)                                              \
                     n_W[j] = j < 4 ? 0u : __builtin_bswap32(load_be32_guarded(words, sub_g_ * (SUB_BITS / 32) - 4 + j, n_bytes)); \
             } else { /* (as they lie in memory: swapped when they are taken) */                                   \
-                const uint32_t *src_ = words + ET_PROBE_D3_SRC(sub_g_) * (SUB_BITS / 32) - 4;                     \
+                const uint32_t *src_ = words + sub_g_ * (SUB_BITS / 32) - 4;                                      \
                 _Pragma("unroll") for (int j = 0; j < RW_WORDS; ++j) n_W[j] = j < 4 ? 0u : src_[j];               \
             }                                                                                                     \
         } else {                                                                                                  \
@@ -1015,12 +994,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dec_write_wave(const uint32_t *_
             bool strips_unit = false;
             if (STRIPS) strips_unit = span && !one_window && !this_edge && n_out == wave_total;  // (wavefront-uniform)
             if (strips_unit) {
-                if (count) walk_write_chain<3>(cw, smem8, W, start, lds_stage + static_cast<uint32_t>(lane) * WS_STRIDE - 1u, 0, 0, 0,
-#ifdef ET_PROBE_STRIPS_DENSE_DST
-                                                     out + (ow & ~static_cast<uint64_t>(15)) + static_cast<uint32_t>(lane) * 64u);
-#else
-                                                     out + ow + my_off);
-#endif
+                if (count) walk_write_chain<3>(cw, smem8, W, start, lds_stage + static_cast<uint32_t>(lane) * WS_STRIDE - 1u, 0, 0, 0, out + ow + my_off);
                 WV_LDS_ORDER()
             } else if (span) {
                 for (;; win += WV_STAGE) {
@@ -1044,6 +1018,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_dec_write_wave(const uint32_t *_
 // --------------------------------------------------------------------------------
 // launch wrappers (plain C++ callable; everything is enqueued on `stream`)
 // --------------------------------------------------------------------------------
+// Grid of the tile-striding encode kernels: the workgroups the device holds at once (both kernels use
+// < 64 SGPRs, where the query is exact), so that every workgroup gets within one tile of the same share.
 template <typename K>
 static uint32_t tile_grid(K kernel, uint32_t n_tiles) {
     int cus = 256;
@@ -1112,15 +1088,8 @@ void launch_dec_write(hipStream_t stream, const uint32_t *words, uint64_t n_byte
     const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
     if (chain) {  // every block, one launch, no side lane, no ticket; `tb` is not looked at
         // 8 wavefronts per workgroup share the tables (17 KiB) beside their 4 KiB stages: 3 workgroups = 24 wavefronts per CU
-#ifdef ET_PROBE_FUSED_OCC  // (round-4 probe, DESIGN section 4: the write pass at the occupancy a kernel that also holds D1's tree table would have -- one workgroup of ET_PROBE_FUSED_OCC wavefronts per CU)
-        constexpr int WAVES = ET_PROBE_FUSED_OCC;
-#else
         constexpr int WAVES = 8;  // (12 x 2 per CU the same; 16 x 2 with 3.8 KiB stages, 32 wavefronts per CU, the same too: 0.441-0.445 ms; 4 x 4 or 16 x 1: 0.56)
-#endif
-        size_t smem_wave = ((static_cast<size_t>(n_chain) * 8 + 15) & ~static_cast<size_t>(15)) + WAVES * WV_STAGE_ALLOC;
-#ifdef ET_PROBE_FUSED_OCC
-        if (smem_wave < 84u * 1024u) smem_wave = 84u * 1024u;  // more than half the LDS: one workgroup per CU, as beside a 47 KiB tree table
-#endif
+        const size_t smem_wave = ((static_cast<size_t>(n_chain) * 8 + 15) & ~static_cast<size_t>(15)) + WAVES * WV_STAGE_ALLOC;
         const uint32_t n_units = (n_blocks * 4 + WAVES - 1) / WAVES;
         if (strips) {  // (the caller's estimate from the header: many symbols per subsequence)
             const size_t smem_strips = ((static_cast<size_t>(n_chain) * 8 + 15) & ~static_cast<size_t>(15)) + WAVES * WS_ALLOC;

@@ -10,6 +10,7 @@
 //   decode.zig:123-125 -> k_build_dec_tables (their lookup tables, filled on the device from the host's plan)
 // Used when: a hand-made dictionary's completed tree has more than 255 internal nodes or is not prefix-free; a near-fixed-length code
 // that is not a row code; a range of a stream split over GPUs whose code does not self-synchronise; blocks that give up in the first sweep.
+// Scans, the guarded stream word, launch helpers: et_device.h; what this file shares with et_kernels.hip alone: et_kernels_common.h.
 #include "et_kernels_common.h"
 #include "et_treewalk.h"
 
@@ -1632,15 +1633,6 @@ void launch_dec_resolve(hipStream_t stream, const uint32_t *words, uint64_t n_by
     hipLaunchKernelGGL(k_dec_chain, dim3(n_groups), dim3(BLOCK), 0, stream, blk_maps, n_blocks, grp_in, 0u, blk_in);
     if (reg) hipLaunchKernelGGL(k_dec_resolve_reg, dim3(n_blocks), dim3(BLOCK), smem_reg, stream, words, n_bytes, n_blocks, step_table_args(tb), map_stride, lane_maps, blk_in, sub_state, blk_exit, blk_count);
     hipLaunchKernelGGL(k_dec_resolve, dim3(reg ? 3 : n_blocks), dim3(BLOCK), smem, stream, words, n_bytes, first_bit, n_subs, tb, map_stride, lane_maps, blk_in, sub_state, blk_exit, blk_count, reg ? 1u : 0u, const_first ? 1u : 0u);
-}
-
-void launch_dec_exhaustive(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs,
-                           const DecodeTables &tb, uint32_t n_starts, uint32_t map_stride, uint8_t *lane_maps, uint8_t *blk_maps,
-                           uint8_t *grp_maps, uint8_t *blk_in, uint8_t *grp_in, uint32_t *sub_state, uint32_t *blk_exit,
-                           uint32_t *blk_count) {
-    launch_dec_maps(stream, words, n_bytes, first_bit, true, n_subs, tb, n_starts, map_stride, lane_maps, blk_maps, grp_maps);
-    launch_dec_resolve(stream, words, n_bytes, first_bit, true, n_subs, tb, map_stride, lane_maps, blk_maps, grp_maps, blk_in, grp_in, sub_state, blk_exit,
-                       blk_count);
 }
 
 void launch_dec_write_fallback(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint64_t n_subs, const DecodeTables &tb, const uint32_t *sub_state,

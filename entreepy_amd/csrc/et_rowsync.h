@@ -43,6 +43,8 @@ constexpr uint32_t ROW_START_UNKNOWN = 2;  // the range's first codeword may beg
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 
+#include "et_kernels.h"
+
 namespace et {
 
 // Bytes of scratch launch_row_sync needs for a stream of n_blocks 8 KiB blocks (zeroed by the launch itself).
@@ -57,10 +59,9 @@ void launch_row_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes
                      uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count, uint32_t flags = 0, const unsigned long long **d_map = nullptr);
 
 // The write pass for such a stream, by rows (k_row_write): sub_state as launch_row_sync leaves it, blk_off from the scan of
-// blk_count; at most n_symbols symbols to out (16-byte aligned).  ev_start / ev_stop: events the dispatch carries (may be null).
+// blk_count; at most n_symbols symbols to out (16-byte aligned).  ev: events the dispatch carries (may be null).
 void launch_row_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, RowCode rc, const et_codebook *cb,
-                      const uint32_t *sub_state, const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, hipEvent_t ev_start = nullptr,
-                      hipEvent_t ev_stop = nullptr);
+                      const uint32_t *sub_state, const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, KernelEvents ev = {});
 
 // decode.zig:143-203 on a FIXED-length code -- 2^L codewords of L bits each (L <= 32): four symbols of about equal weight (a DNA
 // sequence), 16 (a hex dump), 64 (base64 of random bytes).  Nothing to walk: the k-th codeword begins at bit first_bit + k L, so a
@@ -72,7 +73,7 @@ void launch_fixed_sync(hipStream_t stream, uint64_t n_bytes, uint32_t first_bit,
 // The write pass for such a stream (k_fixed_write): symbol i is the code_bits bits at first_bit + i code_bits; n_out of them to out
 // (16-byte aligned) -- n_out <= the whole codewords the stream holds (callers clamp).  code_bits <= 8.
 void launch_fixed_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, const et_codebook *cb, uint64_t n_out, uint8_t *out,
-                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                        KernelEvents ev = {});
 
 }  // namespace et
 #endif

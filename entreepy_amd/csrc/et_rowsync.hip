@@ -21,10 +21,10 @@
 // (A ticket, not the block index, orders the chunks: a chunk only ever waits for chunks with smaller tickets, and those were
 // taken by workgroups that are running.)
 // At the file's end: fixed-length codes (k_fixed_sync, k_fixed_write) -- the same family's other extreme, where nothing has to be found.
+// The scans' DPP moves, the guarded stream word, the CU count, the residency query and the timed launch are et_device.h's.
 #include "et_rowsync.h"
 
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
+#include "et_device.h"
 
 namespace et {
 
@@ -42,17 +42,6 @@ __device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel)
 __device__ __forceinline__ uint32_t rs_and_not(uint32_t a, uint32_t b) { return a & ~b; }
 // byte `idx` (0..7) of the 8-byte map {lo, hi}
 __device__ __forceinline__ uint32_t map_at(uint32_t lo, uint32_t hi, uint32_t idx) { return perm(hi, lo, idx | 0x0c0c0c00u); }
-
-// stream word idx as it lies in memory, zero outside the stream
-__device__ __attribute__((noinline)) uint32_t rs_load_guarded(const uint32_t *__restrict__ words, uint64_t idx, uint64_t n_bytes) {
-    const uint64_t b0 = idx * 4;
-    if (b0 + 4 <= n_bytes) return words[idx];
-    uint32_t v = 0;
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(words);
-    for (int k = 0; k < 4; ++k)
-        if (b0 + k < n_bytes) v |= static_cast<uint32_t>(bytes[b0 + k]) << (8 * k);
-    return v;
-}
 
 // One codeword at a time from bit `pos` to the subsequence's end, never past the stream's (the few lanes the stream begins
 // and ends in).  A codeword cut by the stream's end is nobody's; the exit then points at the stream's end, where the next
@@ -83,14 +72,11 @@ __device__ __attribute__((noinline)) uint32_t rs_slow_walk(const uint8_t *__rest
     return exit_col | (n << 8);
 }
 
-__device__ __forceinline__ uint32_t rs_wave_sum_scan(uint32_t x) {  // inclusive prefix sum over the wavefront (DPP)
-#define RS_DPP_ADD(ctrl_, mask_) x += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), ctrl_, mask_, 0xf, false))
-    RS_DPP_ADD(0x111, 0xf);
-    RS_DPP_ADD(0x112, 0xf);
-    RS_DPP_ADD(0x114, 0xf);
-    RS_DPP_ADD(0x118, 0xf);
-    RS_DPP_ADD(0x142, 0xa);
-    RS_DPP_ADD(0x143, 0xc);
+// Inclusive prefix sum over the wavefront, as wave_inclusive_scan (et_device.h) -- kept beside it because k_row_sync's and
+// k_row_write's plain adds come out with their two source operands swapped when they go through dpp_add.
+__device__ __forceinline__ uint32_t rs_wave_sum_scan(uint32_t x) {
+#define RS_DPP_ADD(ctrl_, mask_) x += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), ctrl_, mask_, 0xf, false));
+    ET_WAVE_SCAN_STEPS(RS_DPP_ADD)
 #undef RS_DPP_ADD
     return x;
 }
@@ -148,7 +134,7 @@ __global__ __launch_bounds__(RS_THREADS) ET_ROW_SYNC_ATTR void k_row_sync(const 
                     for (int j = 0; j < 9; ++j) w[j] = src[j];
                 } else {
 #pragma unroll
-                    for (int j = 0; j < 9; ++j) w[j] = rs_load_guarded(words, sub_g * 8 + j, n_bytes);
+                    for (int j = 0; j < 9; ++j) w[j] = stream_word_guarded_call(words, sub_g * 8 + j, n_bytes);
                 }
                 // 1. four rows per register: t[k] = bytes k, 8 + k, 16 + k, 24 + k of the subsequence
                 uint32_t t[8];
@@ -263,12 +249,7 @@ __global__ __launch_bounds__(RS_THREADS) ET_ROW_SYNC_ATTR void k_row_sync(const 
         const uint32_t n_lo = perm(p_hi, p_lo, o_lo), n_hi = perm(p_hi, p_lo, o_hi); /* first theirs, then ours */                                 \
         p_lo = n_lo, p_hi = n_hi;                                                                                                                  \
     }
-            RS_SCAN_STEP(0x111, 0xf)  // row_shr:1
-            RS_SCAN_STEP(0x112, 0xf)  // row_shr:2
-            RS_SCAN_STEP(0x114, 0xf)  // row_shr:4
-            RS_SCAN_STEP(0x118, 0xf)  // row_shr:8   -> every row of 16 scanned
-            RS_SCAN_STEP(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
-            RS_SCAN_STEP(0x143, 0xc)  // row_bcast:31 into rows 2 and 3
+            ET_WAVE_SCAN_STEPS(RS_SCAN_STEP)
 #undef RS_SCAN_STEP
             sh.lane_pre[q][tid] = static_cast<unsigned long long>(p_lo) | (static_cast<unsigned long long>(p_hi) << 32);
             sh.lane_cnt[q][tid] = static_cast<unsigned long long>(c_lo) | (static_cast<unsigned long long>(c_hi) << 32);
@@ -382,18 +363,6 @@ struct RowLut {
     uint8_t sym[256];  // the symbol whose codeword the 8 bits begin with
 };
 
-__device__ __forceinline__ uint32_t rwr_scan(uint32_t x) {  // inclusive prefix sum over the wavefront (DPP)
-#define RWR_DPP(ctrl_, mask_) x += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), ctrl_, mask_, 0xf, false))
-    RWR_DPP(0x111, 0xf);
-    RWR_DPP(0x112, 0xf);
-    RWR_DPP(0x114, 0xf);
-    RWR_DPP(0x118, 0xf);
-    RWR_DPP(0x142, 0xa);
-    RWR_DPP(0x143, 0xc);
-#undef RWR_DPP
-    return x;
-}
-
 typedef __attribute__((address_space(3))) uint8_t rwr_lds_u8;
 typedef __attribute__((address_space(3))) uint32_t rwr_lds_u32;
 
@@ -430,9 +399,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_row_write(const uint32_t *__rest
             if (q < quarter) before += v >> 16;
         }
         const unsigned long long o0 = blk_off[b];
-        before = __builtin_amdgcn_readlane(rwr_scan(before), 63);
+        before = __builtin_amdgcn_readlane(rs_wave_sum_scan(before), 63);
         const uint32_t count = live ? st >> 16 : 0u;
-        const uint32_t inc = rwr_scan(count);
+        const uint32_t inc = rs_wave_sum_scan(count);
         const uint32_t wave_total = __builtin_amdgcn_readlane(inc, 63), my_off = inc - count;
         const uint64_t ow = o0 + before;
         const bool nothing = o0 >= n_symbols || ow >= n_symbols || wave_total == 0;  // (pad bits decoded past the declared length)
@@ -456,7 +425,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_row_write(const uint32_t *__rest
                 for (int j = 0; j < 9; ++j) X[j] = __builtin_bswap32(src[j]);
             } else {
 #pragma unroll
-                for (int j = 0; j < 9; ++j) X[j] = __builtin_bswap32(rs_load_guarded(words, sub_g * 8 + j, n_bytes));
+                for (int j = 0; j < 9; ++j) X[j] = __builtin_bswap32(stream_word_guarded_call(words, sub_g * 8 + j, n_bytes));
             }
             uint32_t sh = 8u - (st & 7u);  // 8 - column: how far the codeword's 8 bits lie above the NEXT row's first bit
             uint32_t pos = my_lo;          // stage position of the current row's first symbol, less the row's number
@@ -590,21 +559,14 @@ void launch_row_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes
     uint32_t *ticket = reinterpret_cast<uint32_t *>(pub + n_chunks);
     unsigned long long *map_out = pub + n_chunks + 1;
     if (d_map) *d_map = map_out;
-    static thread_local int seen_dev = -1, cus = 256;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != seen_dev) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        seen_dev = dev;
-    }
-    uint32_t grid = static_cast<uint32_t>(cus) * 8u;  // (workgroups that find no room wait their turn and take later tickets: nobody waits for them)
+    uint32_t grid = static_cast<uint32_t>(device_cus()) * 8u;  // (workgroups that find no room wait their turn and take later tickets: nobody waits for them)
     if (grid > n_chunks) grid = n_chunks;
     hipLaunchKernelGGL(k_row_sync, dim3(grid), dim3(RS_THREADS), 0, stream, words, n_bytes, first_bit, n_subs, n_blocks, n_chunks, rc.t, pub, ticket, fault, sub_state, blk_exit,
                        blk_count, flags, map_out);
 }
 
 void launch_row_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, RowCode rc, const et_codebook *cb,
-                      const uint32_t *sub_state, const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, hipEvent_t ev_start, hipEvent_t ev_stop) {
+                      const uint32_t *sub_state, const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, KernelEvents ev) {
     constexpr int WAVES = 8;
     const uint32_t n_blocks = static_cast<uint32_t>((n_subs + RS_THREADS - 1) / RS_THREADS);
     if (!n_blocks) return;
@@ -614,22 +576,13 @@ void launch_row_write(hipStream_t stream, const uint32_t *words, uint64_t n_byte
         if (len == 7) lut.sym[(cb->data[s] & 0x7fu) << 1] = lut.sym[((cb->data[s] & 0x7fu) << 1) | 1u] = static_cast<uint8_t>(s);
         else if (len == 8) lut.sym[cb->data[s] & 0xffu] = static_cast<uint8_t>(s);
     }
-    static thread_local int seen_dev = -1, cus = 256, per_cu = 4;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != seen_dev) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_row_write<WAVES>, 64 * WAVES, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-        seen_dev = dev;
-    }
+    int cus = 256;
+    int per_cu = resident_per_cu(reinterpret_cast<const void *>(k_row_write<WAVES>), 0, &cus, 64 * WAVES);
+    if (per_cu < 1) per_cu = 4;  // (the query failed)
     const uint32_t n_wg = (n_blocks * 4 + WAVES - 1) / WAVES;
     uint32_t grid = static_cast<uint32_t>(cus) * static_cast<uint32_t>(per_cu);
     if (grid > n_wg) grid = n_wg;
-    if (ev_start || ev_stop)
-        hipExtLaunchKernelGGL(k_row_write<WAVES>, dim3(grid), dim3(64 * WAVES), 0, stream, ev_start, ev_stop, 0, words, n_bytes, n_blocks, n_subs, first_bit, rc.t, lut, sub_state, blk_off,
-                              n_symbols, out);
-    else
-        hipLaunchKernelGGL(k_row_write<WAVES>, dim3(grid), dim3(64 * WAVES), 0, stream, words, n_bytes, n_blocks, n_subs, first_bit, rc.t, lut, sub_state, blk_off, n_symbols, out);
+    ET_LAUNCH_TIMED(k_row_write<WAVES>, dim3(grid), dim3(64 * WAVES), 0, stream, ev, words, n_bytes, n_blocks, n_subs, first_bit, rc.t, lut, sub_state, blk_off, n_symbols, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -658,7 +611,7 @@ __global__ __launch_bounds__(256) void k_fixed_write(const uint32_t *__restrict_
             for (int j = 0; j < 5; ++j) W[j] = __builtin_bswap32(words[w0 + j]);
         } else {
 #pragma unroll
-            for (int j = 0; j < 5; ++j) W[j] = __builtin_bswap32(rs_load_guarded(words, w0 + j, n_bytes));
+            for (int j = 0; j < 5; ++j) W[j] = __builtin_bswap32(stream_word_guarded_call(words, w0 + j, n_bytes));
         }
         uint32_t V[4];  // the 128 bits from `bit` on
 #pragma unroll
@@ -697,25 +650,18 @@ __global__ __launch_bounds__(256) void k_fixed_write(const uint32_t *__restrict_
 }
 
 void launch_fixed_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, const et_codebook *cb, uint64_t n_out, uint8_t *out,
-                        hipEvent_t ev_start, hipEvent_t ev_stop) {
+                        KernelEvents ev) {
     if (!n_out) return;
     const uint32_t L = cb->max_length;
     RowLut lut = {};
     for (int s = 0; s < 256; ++s)
         if (cb->length[s] == L) lut.sym[cb->data[s] & ((1u << L) - 1u)] = static_cast<uint8_t>(s);
-    static thread_local int seen_dev = -1, cus = 256;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != seen_dev) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        seen_dev = dev;
-    }
+    const uint64_t cus = static_cast<uint64_t>(device_cus());
     const uint64_t n_wg = ((n_out + 15) / 16 + 255) / 256;
-    const uint32_t grid = static_cast<uint32_t>(n_wg < static_cast<uint64_t>(cus) * 32 ? n_wg : static_cast<uint64_t>(cus) * 32);
-#define ET_FIXED_CASE(l_)                                                                                                                                  \
-    case l_:                                                                                                                                               \
-        if (ev_start || ev_stop) hipExtLaunchKernelGGL(k_fixed_write<l_>, dim3(grid), dim3(256), 0, stream, ev_start, ev_stop, 0, words, n_bytes, first_bit, n_out, lut, out); \
-        else hipLaunchKernelGGL(k_fixed_write<l_>, dim3(grid), dim3(256), 0, stream, words, n_bytes, first_bit, n_out, lut, out);                         \
+    const uint32_t grid = static_cast<uint32_t>(n_wg < cus * 32 ? n_wg : cus * 32);
+#define ET_FIXED_CASE(l_)                                                                                                          \
+    case l_:                                                                                                                       \
+        ET_LAUNCH_TIMED(k_fixed_write<l_>, dim3(grid), dim3(256), 0, stream, ev, words, n_bytes, first_bit, n_out, lut, out);      \
         break;
     switch (L) {
         ET_FIXED_CASE(1)

@@ -9,10 +9,10 @@
 // fixed point over shuffles.  After the table is staged nothing is shared between wavefronts: no barrier, no
 // LDS traffic besides the lookups, no ticket.  The chain per step is table read -> shift -> and-or -> table
 // read; the byte positions are compile-time constants.
+// The count's scan, the guarded stream word, the CU count and the timed launch are et_device.h's (which declares no LDS).
 #include "et_treewalk.h"
 
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
+#include "et_device.h"
 
 namespace et {
 
@@ -21,33 +21,8 @@ extern __shared__ __attribute__((aligned(16))) uint8_t tw_smem[];
 typedef __attribute__((address_space(3))) uint8_t tw_lds_u8;
 typedef __attribute__((address_space(3))) uint16_t tw_lds_u16;
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t tw_dpp_add(uint32_t x) {
-    return x + static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ uint32_t tw_wave_inclusive_scan(uint32_t x) {
-    x = tw_dpp_add<0x111, 0xf>(x);  // row_shr:1
-    x = tw_dpp_add<0x112, 0xf>(x);  // row_shr:2
-    x = tw_dpp_add<0x114, 0xf>(x);  // row_shr:4
-    x = tw_dpp_add<0x118, 0xf>(x);  // row_shr:8
-    x = tw_dpp_add<0x142, 0xa>(x);  // row_bcast:15
-    x = tw_dpp_add<0x143, 0xc>(x);  // row_bcast:31
-    return x;
-}
-
-// Word `idx` (may be negative: before `words`) of the stream AS IT LIES IN MEMORY (stream byte k of the word is its byte k: the
-// walk picks bytes by SDWA selects, so nothing is swapped), zero outside the stream.  front_ok: the four words in front of `words`
-// are stream bytes too (a range of a stream that began earlier).
-__device__ __attribute__((noinline)) uint32_t tw_load_guarded(const uint32_t *__restrict__ words, long long idx, uint64_t n_bytes, bool front_ok) {
-    if (idx < 0) return front_ok && idx >= -4 ? words[idx] : 0u;
-    const uint64_t b0 = static_cast<uint64_t>(idx) * 4;
-    if (b0 + 4 <= n_bytes) return words[idx];
-    uint32_t v = 0;
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(words);
-    for (int k = 0; k < 4; ++k)
-        if (b0 + k < n_bytes) v |= static_cast<uint32_t>(bytes[b0 + k]) << (8 * k);
-    return v;
-}
+// (The lanes' words at a block's edges are stream_word_guarded_front's, et_device.h: the words AS THEY LIE IN MEMORY -- the walk
+// picks bytes by SDWA selects, so nothing is swapped.)
 
 // ---- the table, filled on the device from the tree -------------------------------------------------
 // One launch fills both tables of a code: the synchronisation walk's (table, may be null) and the write walk's chained
@@ -320,7 +295,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(ET_TW_WAVE
                 for (int j = 0; j < TW_WORDS; ++j) W[u][j] = words[w0 + j];  // (as they lie in memory: no byte swap, see tw_walk)
             } else {
 #pragma unroll
-                for (int j = 0; j < TW_WORDS; ++j) W[u][j] = tw_load_guarded(words, w0 + j, n_bytes, (mode & TW_FRONT_OK) != 0);
+                for (int j = 0; j < TW_WORDS; ++j) W[u][j] = stream_word_guarded_front(words, w0 + j, n_bytes, (mode & TW_FRONT_OK) != 0);
                 // whole bytes of the stream inside the lane's own 64 -> steps that count
                 const uint64_t lane_byte0 = q[u] * 64;
                 limit[u] = static_cast<uint32_t>(n_bytes > lane_byte0 ? (n_bytes - lane_byte0 < 64 ? n_bytes - lane_byte0 : 64) : 0);
@@ -496,7 +471,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(ET_TW_WAVE
                 sum += begun1 + begun2;
             }
         }
-        sum = tw_wave_inclusive_scan(sum);
+        sum = wave_inclusive_scan(sum);
         if (lane_id == 63) {
             blk_count[b] = sum;
             blk_exit[b] = r[1].s_out();  // (lanes past the stream's end stand at the root)
@@ -532,19 +507,9 @@ void launch_tw_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes,
                     uint32_t max_trips, const uint32_t *worklist, const uint32_t *n_work, KernelEvents ev, uint32_t *blk_pub, uint32_t mode, uint32_t *exit_bits) {
     const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
     const uint32_t entries = tw_table_entries(n_int);
-    size_t smem = static_cast<size_t>(entries) * 2;
-#ifdef ET_PROBE_FUSED_OCC
-    if (smem < 84u * 1024u) smem = 84u * 1024u;
-#endif
+    const size_t smem = static_cast<size_t>(entries) * 2;
     // workgroups of 8 wavefronts, as many per CU as the table leaves room for in the LDS, at most 3 (<= 80 VGPRs: 6
     // wavefronts per SIMD); a table that leaves room for one workgroup only gets one of 16 wavefronts
-    static thread_local int seen_dev = -1, cus = 256;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != seen_dev) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        seen_dev = dev;
-    }
     uint32_t per_cu = static_cast<uint32_t>((160u * 1024u) / smem);
 #ifndef ET_TW_PER_CU_MAX
 #define ET_TW_PER_CU_MAX 3
@@ -554,16 +519,12 @@ void launch_tw_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes,
     uint32_t waves = (4u * ET_TW_WAVES_PER_EU + per_cu - 1) / per_cu;
     if (waves * per_cu > 4u * ET_TW_WAVES_PER_EU) --waves;
     waves = waves > 16 ? 16 : waves;
-#ifdef ET_PROBE_FUSED_OCC  // (round-4 probe: the sweep at the occupancy of a kernel that also holds the write pass's tables and stages)
-    per_cu = 1;
-    waves = ET_PROBE_FUSED_OCC;
-#endif
     const uint32_t threads = waves * 64;
-    uint32_t grid = static_cast<uint32_t>(cus) * per_cu;
+    uint32_t grid = static_cast<uint32_t>(device_cus()) * per_cu;
     if (grid > (n_blocks + waves - 1) / waves) grid = (n_blocks + waves - 1) / waves;
     if (worklist && grid > 64) grid = 64;  // a repair sweep: a handful of blocks (workgroups beyond the list leave at once)
-    if (ev.start || ev.stop) hipExtLaunchKernelGGL(k_tw_sync, dim3(grid), dim3(threads), smem, stream, ev.start, ev.stop, 0, words, n_bytes, first_bit, n_subs, n_blocks, table, entries, n_int, sub_state, blk_exit, blk_start, blk_count, changed, max_trips, worklist, n_work, blk_pub, mode, exit_bits);
-    else hipLaunchKernelGGL(k_tw_sync, dim3(grid), dim3(threads), smem, stream, words, n_bytes, first_bit, n_subs, n_blocks, table, entries, n_int, sub_state, blk_exit, blk_start, blk_count, changed, max_trips, worklist, n_work, blk_pub, mode, exit_bits);
+    ET_LAUNCH_TIMED(k_tw_sync, dim3(grid), dim3(threads), smem, stream, ev, words, n_bytes, first_bit, n_subs, n_blocks, table, entries, n_int, sub_state, blk_exit, blk_start,
+                    blk_count, changed, max_trips, worklist, n_work, blk_pub, mode, exit_bits);
 }
 
 void launch_tw_check(hipStream_t stream, const uint32_t *blk_start, const uint32_t *blk_exit, uint32_t n_blocks, uint32_t *worklist, uint32_t *n_work, bool first_known) {

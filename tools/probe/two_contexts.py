@@ -7,6 +7,10 @@ side -- what a service with more than one request in flight does -- fill those h
 context, one step after the other); it is printed beside it.
 
     python3 tools/probe/two_contexts.py [bytes] [steps]
+
+Environment (read by this script alone -- they are not the library's compile-time -DET_PROBE_* switches of tools/probe/*.patch, and
+the script runs on the product build): ET_PROBE_CONTEXTS (contexts side by side, default 2), ET_PROBE_DATA=uniform255 (bytes 1..255
+instead of text: the row walk's kernels), ET_PROBE_DECODE_ONLY=1 (encode once, time the decodes).
 """
 import json
 import os
