@@ -350,14 +350,15 @@ int encode_shard(et_ctx *ctx, const et_codebook *cb, const void *d_text, size_t 
     // concatenation which ORs pieces together never reads what an earlier call left in d_out.
     auto empty_shard = [&]() -> int {
         const size_t head_words = (header_len + 3) / 4;
-        const size_t need = (header_len ? head_words : 1) * 4;
+        const size_t own_word = header_len ? 0 : static_cast<size_t>(start_bit / 32);  // (a body shard's start bit may lie behind d_out's first word)
+        const size_t need = (header_len ? head_words : own_word + 1) * 4;
         if (need > cap_bytes) return fail(ctx, ET_ERR_CAP, "body does not fit d_out");
         if (header_len) {
             std::memset(ctx->h_header, 0, head_words * 4);
             std::memcpy(ctx->h_header, header, header_len);
             ET_HIP(hipMemcpyAsync(d_out, ctx->h_header, head_words * 4, hipMemcpyHostToDevice, ctx->stream));
         } else {
-            ET_HIP(hipMemsetAsync(d_out, 0, 4, ctx->stream));
+            ET_HIP(hipMemsetAsync(static_cast<uint8_t *>(d_out) + own_word * 4, 0, 4, ctx->stream));
         }
         *end_bit = start_bit;
         return ET_OK;
@@ -436,6 +437,7 @@ extern "C" int et_encode_head_shard_device(et_ctx *ctx, const et_codebook *cb, c
 
 extern "C" int et_encode_device(et_ctx *ctx, const void *d_text, size_t n, void *d_out, size_t cap, size_t *out_len) {
     if (!ctx || !d_out || !out_len || (n && !d_text)) return ET_ERR_ARG;
+    *out_len = 0;
     if (n == 0) return fail(ctx, ET_ERR_EMPTY, "empty input");
     if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(ctx, ET_ERR_ARG, "d_out must be 16-byte aligned");
     if (cap < et_encode_bound(n)) return fail(ctx, ET_ERR_CAP, "cap < et_encode_bound(n)");
@@ -519,6 +521,7 @@ int file_size(int fd, uint64_t *size) {
 
 // encode: source -> io_in -> kernels -> io_out -> sink
 int encode_through_pipe(et_ctx *ctx, const et_io::HostEnd &src, size_t n, const et_io::HostEnd *dst, size_t cap, size_t *out_len) {
+    *out_len = 0;
     if (n == 0) return fail(ctx, ET_ERR_EMPTY, "empty input");
     const size_t bound = et_encode_bound(n);
     ET_TRY(ensure_io(ctx));

@@ -503,10 +503,13 @@ int body_scan(BodyDecode &d, bool first) {
 int write_symbols(BodyDecode &d, uint64_t clamp, bool speculative) {
     WriteExtras x{d.plan.row_write, 5, &d.ctx->side, d.write_ticket_zero, speculative ? d.flag : nullptr, timed_body(d.ctx, EV_DEC + 2, EV_DEC + 3), false};
     const bool tables = d.family != Family::FIXED_WRITE && !(d.family == Family::ROWS && d.plan.row_write);
-    // More than 128 symbols per 256-bit subsequence (the header says how many symbols the body's bits hold): a quarter's output is three or more
+    // More than 128 symbols per 256-bit subsequence: a quarter's output is three or more
     // windows of the write's 4 KiB stage, i.e. it would be walked three or more times -- the instantiation that walks it once, into strips
     // (measured: +45 % at 140 symbols per subsequence, +75 % at 200; at 90-110, two windows, the strips' scattered stores cost what they save).
-    d.strips = x.strips = tables && d.plan.strips && d.chain && d.n_symbols / 128 > d.n_subs;
+    // The symbols are the ones this write stores: the header's count when it is speculative, the counted ones behind the report -- a body cut
+    // short of its header's count holds no more per subsequence than the whole stream did, and takes the whole stream's instantiation.
+    // (A preference, not a repair: by the header's count such a body took the strips, and its bytes and extent were right all the same.)
+    d.strips = x.strips = tables && d.plan.strips && d.chain && clamp / 128 > d.n_subs;
     ET_TRY(write_span(d.ctx, d, d.family, clamp, d.out, x));
     if (tables) d.write_ticket_zero = false;
     return ET_OK;

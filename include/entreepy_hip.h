@@ -211,9 +211,14 @@ int et_decode_path(const et_codebook *cb, uint32_t *path);
 int et_decoded_size(const uint8_t *compressed, size_t len, size_t *n_symbols);
 
 /* Same two calls with input and output resident in HBM (benchmarks, pipelines).
- * d_out must hold et_encode_bound(n) bytes / n_symbols (+16 slack) bytes.  Both are
+ * d_out must hold et_encode_bound(n) bytes / n_symbols bytes.  Both are
  * stream-ordered: *out_len is final on return, the bytes in d_out are complete once the
- * ctx's stream has drained (enqueue consumers on it, or synchronise it). */
+ * ctx's stream has drained (enqueue consumers on it, or synchronise it).
+ * WHAT A CALL WRITES (tests/test_gpu_extent.py, guard bytes around d_out): nothing in front of d_out, nothing at or past
+ * d_out + cap; a call that returns ET_ERR_CAP has written nothing and stored *out_len = 0, and the ctx is as good as before
+ * it.  et_decode_device and et_decode_body_device: cap >= n_symbols suffices, and nothing outside [d_out, d_out + *out_len)
+ * is written -- measured on an MI355X for every decode write kernel at ragged, clamped and truncated lengths; none uses the 16 bytes
+ * of slack this comment used to ask for. */
 int et_encode_device(et_ctx *ctx, const void *d_text, size_t n,
                      void *d_out, size_t cap, size_t *out_len);
 int et_decode_device(et_ctx *ctx, const void *d_compressed, size_t len,
@@ -296,7 +301,11 @@ int et_plan_shards(const uint64_t *hists, uint32_t world, et_codebook *cb, uint8
  * (d_out 4-byte aligned).  Every 32-bit word the shard touches is fully overwritten
  * (bits outside [start_bit, *end_bit) in the first/last word become 0), so adjacent
  * shards are concatenated by OR-ing their boundary bytes.  Requires the preceding
- * et_histogram_device on the same (d_text, n). */
+ * et_histogram_device on the same (d_text, n).
+ * d_out is the word that holds bit 0, whatever start_bit is: the words touched are start_bit / 32 .. (*end_bit + 31) / 32 - 1,
+ * cap_bytes is measured from d_out and must reach the end of the last one (else ET_ERR_CAP, nothing written), and the
+ * words in front of start_bit / 32 are left alone.  An EMPTY shard (n = 0, or only symbols without a codeword) still owns the
+ * word its start bit lies in: it zeroes word start_bit / 32, needs cap_bytes >= (start_bit / 32 + 1) * 4, and *end_bit == start_bit. */
 int et_encode_body_device(et_ctx *ctx, const et_codebook *cb, const void *d_text, size_t n,
                           void *d_out, size_t cap_bytes, uint64_t start_bit, uint64_t *end_bit);
 

@@ -1,0 +1,98 @@
+"""Helpers the GPU test modules share: output buffers with guard bytes on both sides (what may a call write?) and two hand-made
+code tables.  A plain module, imported by name; nothing here is a fixture."""
+import numpy as np
+
+FILL = 0xA5
+FRONT = BACK = 64
+
+
+class Guarded:
+    """FRONT + room + BACK bytes, all `fill`; the usable part -- .room, a view of `room` bytes, at address .ptr -- begins on a
+    16-byte boundary.  device=None: host memory (numpy), else a torch device.  After the calls under test, check() takes a
+    snapshot (after a torch.cuda.synchronize() for device memory); front_clean / back_clean / first_dirty / data read it."""
+
+    def __init__(self, room, fill=FILL, device="cuda"):
+        self.n, self.fill, self.on_device = int(room), fill, device is not None
+        total = FRONT + self.n + BACK + 16
+        if self.on_device:
+            import torch
+
+            self.buf = torch.full((total,), fill, dtype=torch.uint8, device=device)
+            base = self.buf.data_ptr()
+        else:
+            self.buf = np.full(total, fill, dtype=np.uint8)
+            base = self.buf.ctypes.data
+        self.lo = FRONT + (-(base + FRONT)) % 16
+        self.ptr = base + self.lo
+        assert self.ptr % 16 == 0 and self.lo >= FRONT
+        self.room = self.buf[self.lo : self.lo + self.n]
+        self.snap = None
+
+    def refill(self):
+        if self.on_device:
+            self.buf.fill_(self.fill)
+        else:
+            self.buf[:] = self.fill
+        self.snap = None
+
+    def check(self):
+        if self.on_device:
+            import torch
+
+            torch.cuda.synchronize()
+            self.snap = self.buf.cpu().numpy()
+        else:
+            self.snap = self.buf.copy()
+        return self
+
+    def data(self, n=None):
+        """The first n bytes of the usable part (default: all of it), as the snapshot holds them."""
+        return self.snap[self.lo : self.lo + (self.n if n is None else n)]
+
+    def front_clean(self):
+        return bool((self.snap[: self.lo] == self.fill).all())
+
+    def back_clean(self, from_byte):
+        """Every byte from offset from_byte of the usable part to the end of the back guard still holds the fill."""
+        return bool((self.snap[self.lo + from_byte :] == self.fill).all())
+
+    def first_dirty(self, from_byte=None):
+        """Offset, relative to the usable part's first byte (negative: in the front guard), of the first byte that no longer
+        holds the fill: in the front guard, or at or behind from_byte (default: the end of the usable part).  None: clean."""
+        from_byte = self.n if from_byte is None else from_byte
+        watched = np.ones(self.snap.size, dtype=bool)
+        watched[self.lo : self.lo + from_byte] = False
+        bad = np.flatnonzero(watched & (self.snap != self.fill))
+        return int(bad[0]) - self.lo if bad.size else None
+
+    def assert_extent(self, out_len, what, slack=0):
+        """Nothing in front of the usable part and nothing from out_len + slack on was written."""
+        dirty = self.first_dirty(out_len + slack)
+        assert dirty is None, f"{what}: byte at offset {dirty} written, outside [0, {out_len}{' + %d' % slack if slack else ''}) of a buffer of {self.n}"
+
+
+def _random_prefix_code(rng, n_sym, max_len):
+    """A prefix-free table with random lengths up to max_len (Kraft-feasible), codes
+    assigned canonically; not optimal, only a legal input for the body kernels."""
+    lens = np.sort(rng.integers(2, max_len + 1, size=n_sym))
+    while sum(2.0 ** -int(l) for l in lens) > 1.0:
+        lens[np.argmin(lens)] += 1
+        lens = np.sort(lens)
+    code, prev, codes = 0, int(lens[0]), []
+    for l in lens:
+        code <<= int(l) - prev
+        prev = int(l)
+        codes.append(code)
+        code += 1
+    return lens, codes
+
+
+def _sparse_dictionary():
+    """A prefix-free table no encoder makes: two 2-bit codes and a hundred 16-bit codes 1iiiiiii00000000 -- completed with a
+    leaf for every bit pattern nobody has, its tree has ~900 internal nodes, beyond the tree walk's table (255)."""
+    data_t, len_t = np.zeros(256, np.uint32), np.zeros(256, np.uint8)
+    data_t[32], len_t[32] = 0b00, 2
+    data_t[101], len_t[101] = 0b01, 2
+    for i in range(100):
+        data_t[120 + i], len_t[120 + i] = 0x8000 | (i << 8), 16
+    return data_t, len_t, np.array([32, 101] + list(range(120, 220)))

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests import corpus
+from tests.guards import _random_prefix_code, _sparse_dictionary
 
 pytestmark = pytest.mark.gpu
 
@@ -123,22 +124,6 @@ def test_device_entry_points_misaligned_input(ctx):
         m = ctx.decode_device(comp[off : off + n - 4], dec)
         torch.cuda.synchronize()
         assert m == view.numel() and (dec[:m] == view).all(), off
-
-
-def _random_prefix_code(rng, n_sym, max_len):
-    """A prefix-free table with random lengths up to max_len (Kraft-feasible), codes
-    assigned canonically; not optimal, only a legal input for the body kernels."""
-    lens = np.sort(rng.integers(2, max_len + 1, size=n_sym))
-    while sum(2.0 ** -int(l) for l in lens) > 1.0:
-        lens[np.argmin(lens)] += 1
-        lens = np.sort(lens)
-    code, prev, codes = 0, int(lens[0]), []
-    for l in lens:
-        code <<= int(l) - prev
-        prev = int(l)
-        codes.append(code)
-        code += 1
-    return lens, codes
 
 
 @pytest.mark.parametrize("max_len,seed", [(12, 1), (16, 2), (24, 3), (32, 4)])
@@ -1030,17 +1015,6 @@ def test_hand_made_tables_with_codes_nobody_has(ctx):
         m = ctx.decode_body_device(cb, junk, text.size, out)
         torch.cuda.synchronize()
         assert 0 <= m <= text.size
-
-
-def _sparse_dictionary():
-    """A prefix-free table no encoder makes: two 2-bit codes and a hundred 16-bit codes 1iiiiiii00000000 -- completed with a
-    leaf for every bit pattern nobody has, its tree has ~900 internal nodes, beyond the tree walk's table (255)."""
-    data_t, len_t = np.zeros(256, np.uint32), np.zeros(256, np.uint8)
-    data_t[32], len_t[32] = 0b00, 2
-    data_t[101], len_t[101] = 0b01, 2
-    for i in range(100):
-        data_t[120 + i], len_t[120 + i] = 0x8000 | (i << 8), 16
-    return data_t, len_t, np.array([32, 101] + list(range(120, 220)))
 
 
 @pytest.mark.parametrize("n", [4_000, 60_000, 2_000_000])

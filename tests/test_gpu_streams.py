@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from tests import corpus
-from tests.test_gpu_parity import _sparse_dictionary
+from tests.guards import _sparse_dictionary
 from tests.test_gpu_rowsync import flat
 from tests.test_gpu_strips import sparse
 

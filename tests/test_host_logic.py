@@ -466,7 +466,7 @@ def test_decode_path_of_flat_alphabets():
     assert path(E.Codebook.from_tables(np.arange(256, dtype=np.uint32), np.where(np.arange(256) < 255, 8, 0).astype(np.uint8))) == "M"
     # hand-made without a tree: the sparse dictionary (its completed tree is too large) takes the windows; one of a single length
     # that does not settle -- three 4-bit codewords, two of them equal, so not prefix-free -- the exit maps, as the decode does
-    from tests.test_gpu_parity import _sparse_dictionary
+    from tests.guards import _sparse_dictionary
 
     assert path(E.Codebook.from_tables(*_sparse_dictionary()[:2])) == "W"
     dup_d, dup_l = np.zeros(256, np.uint32), np.zeros(256, np.uint8)
