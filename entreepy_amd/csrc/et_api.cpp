@@ -80,8 +80,8 @@ int run_body(et_ctx *ctx, const et_codebook *cb, const Geometry &g, uint32_t *ou
              const uint8_t *header, size_t header_len, int ev_scan, int ev_body) {
     const bool long_codes = cb->max_length > 32;
     // (the pinned block is read by the device itself, K2's first workgroup: not before that has happened for the call
-    // before may it be filled again -- it says so in h_scalar[12]; normally long ago)
-    ET_TRY(wait_for_word<uint64_t>(ctx, ctx->h_scalar + 12, ctx->enc_block_epoch, 100.0, "the code table block was never taken"));
+    // before may it be filled again -- it says so in h_scalar[HS_ENC_TAKEN]; normally long ago)
+    ET_TRY(wait_for_word<uint64_t>(ctx, ctx->h_scalar + HS_ENC_TAKEN, ctx->enc_block_epoch, 100.0, "the code table block was never taken"));
     for (int s = 0; s < 256; ++s) {
         const uint32_t len = cb->length[s];
         uint32_t code = cb->data[s];
@@ -102,7 +102,7 @@ int run_body(et_ctx *ctx, const et_codebook *cb, const Geometry &g, uint32_t *ou
     // (no upload: the code lengths ride in K2's kernel arguments, and its first workgroup copies the pinned block --
     // code table, lengths, header -- into enc_table for the kernels behind it)
     et::launch_tile_scan(ctx->stream, static_cast<const uint32_t *>(ctx->tile_hist.p), g.n_tiles, cb->length, ctx->h_enc, static_cast<uint32_t *>(ctx->enc_table.p),
-                         static_cast<uint32_t>(768 + padded / 4), reinterpret_cast<unsigned long long *>(ctx->h_scalar + 12), ++ctx->enc_block_epoch,
+                         static_cast<uint32_t>(768 + padded / 4), reinterpret_cast<unsigned long long *>(ctx->h_scalar + HS_ENC_TAKEN), ++ctx->enc_block_epoch,
                          static_cast<unsigned long long *>(ctx->tile_bits.p),
                          static_cast<unsigned long long *>(ctx->group_sum.p), scan_epoch(ctx), base_bit,
                          static_cast<unsigned long long *>(ctx->tile_off.p), out32, static_cast<const uint32_t *>(ctx->enc_table.p) + 768,
@@ -152,12 +152,9 @@ extern "C" int et_ctx_create(int device, et_ctx **out) {
     if (ok) std::memset(ctx->h_hist, 0, (256 + et::HIST_REDUCE_GROUPS) * sizeof(uint64_t));  // (no workgroup's word reads as the first epoch)
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_enc), 768 * sizeof(uint32_t) + HEADER_STAGE) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_header), HEADER_STAGE) == hipSuccess;
-    for (int i = 0; i < 2; ++i) {
-        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_lut_buf[i]), DEC_TABLES_BYTES) == hipSuccess;
-    }
-    ctx->h_lut = ctx->h_lut_buf[0];
-    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_scalar), 16 * sizeof(uint64_t)) == hipSuccess;
-    if (ok) std::memset(ctx->h_scalar, 0, 16 * sizeof(uint64_t));
+    for (int i = 0; i < 2; ++i) ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_lut_buf[i]), DEC_TABLES_BYTES) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_scalar), HS_SLOTS * sizeof(uint64_t)) == hipSuccess;
+    if (ok) std::memset(ctx->h_scalar, 0, HS_SLOTS * sizeof(uint64_t));
     for (int i = 0; i < 2; ++i) ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ctx->h_tw_tree[i]), sizeof(et::TwUpload)) == hipSuccess;
     // timing-only events: no system-scope fence when they complete (hip_runtime_api.h: "for events that
     // are only being used to measure timing"); with the default flags the ten records of an
@@ -301,7 +298,7 @@ extern "C" int et_ctx_reserve(et_ctx *ctx, size_t max_text_bytes) {
     ET_TRY(ensure(ctx, ctx->worklist, (n_blocks + 1) * sizeof(uint32_t)));
     ET_TRY(ensure(ctx, ctx->group_sum, (n_blocks / 1024 + 2) * sizeof(uint64_t)));
     ET_TRY(ensure(ctx, ctx->lut, DEC_TABLES_BYTES));
-    ET_TRY(ensure(ctx, ctx->flag, 64));
+    ET_TRY(ensure(ctx, ctx->flag, et::DEC_FLAG_WORDS * sizeof(uint32_t)));
     ET_TRY(ensure(ctx, ctx->tw_table, static_cast<size_t>(et::tw_table_entries(et::TW_MAX_NODES)) * sizeof(uint16_t) + 64));
     ET_TRY(ensure(ctx, ctx->tw_tree, sizeof(et::TwUpload)));
     ET_TRY(ensure(ctx, ctx->chain_table, static_cast<size_t>(et::CH_MAX_ENTRIES) * sizeof(uint64_t)));

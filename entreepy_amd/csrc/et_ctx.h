@@ -24,29 +24,18 @@ struct DevBuf {
 };
 
 constexpr size_t HEADER_STAGE = 8192;  // >= 4631-byte worst-case header, padded
-constexpr size_t SUB_TABLE_ONLY = (static_cast<size_t>(et::DEC_SUB_TABLES_MAX) << et::DEC_SUB_BITS_MAX) * sizeof(uint16_t) + 64;
-constexpr size_t SUB_TABLE_BYTES = SUB_TABLE_ONLY + 256;
-constexpr size_t DEC_STEPS_OFFSET = (sizeof(uint32_t) << et::DEC_LUT_BITS_MAX) * 2 + 1024 * sizeof(uint32_t) + 2 * SUB_TABLE_BYTES;  // multiple of 64
-constexpr size_t DEC_TABLES_BYTES = DEC_STEPS_OFFSET + (sizeof(uint32_t) << et::DEC_STEP_BITS_MAX) + (sizeof(uint32_t) << et::DEC_LUT_BITS_MAX) +
-                                    2 * (et::DEC_STEP_SUB_WORDS + 4) * sizeof(uint32_t) + 2 * sizeof(et::DecodeTables) + sizeof(et::TablePlan) + 64;
-//  // the per-symbol code lengths ride behind the tables  // + slack for 16-byte rounded copies
+constexpr size_t DEC_TABLES_BYTES = et::DecTableLayout::BYTES;  // the decode tables' block (et_tables.h)
 
 // The decode families.  The first two are sweeps that may give up on a stream (it then goes to the plan's fallback); the
 // others synchronise whatever the stream, or (FIXED_WRITE) need not.
 enum class Family { TREE_WALK, WINDOWS, ROWS, FIXED_SYNC, FIXED_WRITE, EXIT_MAPS };
 
-// The workspaces every synchronisation writes, as the kernels take them.
-struct DecWs {
-    uint32_t *sub_state, *blk_exit, *blk_count, *flag, *worklist;
-    unsigned long long *blk_off, *group_sum;
-};
+using et::DecWs;
 
 // What is being synchronised -- a whole stream (et_decode_body_device) or a range of one split over GPUs (et_decode_range_*) --
-// as the decode's stages (et_decode.cpp) and through them the kernels take it.
-struct Span : DecWs {
-    const uint32_t *words;     // from a 4-byte aligned base
-    uint64_t n_bytes, n_subs;  // a range's: the bytes after it included, the subsequences after it not
-    uint32_t n_blocks, first_bit;
+// as the decode's stages (et_decode.cpp) take it: the geometry and workspaces the kernels' launches take (et_kernels.h), and
+// what the families add to them.
+struct Span : et::DecSpan {
     uint32_t tw_mode, dec_flags, row_mode;  // the kernels' mode bits: TW_FRONT_OK, TW_START_UNKNOWN / DEC_HAVE_START, DEC_FRONT_OK / ROW_MAP_ONLY, ROW_START_UNKNOWN
     const et_codebook *cb;
     et::RowCode row_code;           // ROWS
@@ -59,6 +48,17 @@ struct Span : DecWs {
     uint32_t n_chain;
 };
 
+// The slots of et_ctx::h_scalar, 8 bytes each: what the device hands to the host in pinned memory.
+enum HostScalar {
+    HS_TOTAL = 1,         // a range's symbol total; the row walk's map of a range
+    HS_RANGE_FLAGS = 2,   // the range calls' words, as uint32_t: RF_* below
+    HS_BODY_FLAGS = 4,    // 4 .. 11, as uint32_t: the body decode's copy of the flag words (et::DecFlag)
+    HS_ENC_TAKEN = 12,    // == enc_block_epoch: the device has taken its copy of h_enc
+    HS_HEADER_DONE = 14,  // == header_epoch: the header bytes of the current decode are in h_header
+    HS_SLOTS = 16
+};
+enum RangeFlag { RF_START = 0, RF_EXIT = 1, RF_ROW_BLIND = 2 };  // (before a range is finished RF_START takes the one word its sweeps wait for: the worklist count, FLAG_CHANGED)
+
 struct et_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -68,21 +68,12 @@ struct et_ctx {
     bool timing = false;       // every phase carries events (et_ctx_enable_timing(ctx, 1))
     bool timing_body = false;  // only the decode's write kernel does (et_ctx_enable_timing(ctx, ET_TIMING_DECODE_BODY))
     uint32_t force_rpt = 0;
-    uint32_t lut_bits_write = et::DEC_LUT_BITS_WRITE;
-    uint32_t step_bits = et::DEC_STEP_BITS_DEFAULT;
     std::string err;
 
     // encode workspaces
     DevBuf tile_hist, block_hist, hist, tile_bits, tile_off, enc_table, group_sum;
     // decode workspaces
-    // flag: 16 device words the decode's kernels and the host share --
-    //   [0]  a sweep changed something (every repair sweep clears it first)
-    //   [1]  blocks that gave up in the first sweep          [2]  the scan's verification failed
-    //   [3]  the row walk: a chunk never saw the chunks before it
-    //   [4]  ticket of the window sweeps (D1), and of a range's write      [5]  ticket of the whole-stream write (D3)
-    //   [8]  worklist count                                   [9]  a tree-walked range's exit bit (k_tw_sync's exit_bits)
-    //   [12..13] symbol total
-    // lut: all decode tables, DEC_TABLES_BYTES
+    // flag: the et::DEC_FLAG_WORDS words the decode's kernels and the host share (et_kernels.h DecFlag); lut: all decode tables, DEC_TABLES_BYTES
     DevBuf sub_state, blk_exit, blk_count, blk_off, lut, flag, worklist;
     DevBuf lane_maps, blk_maps, grp_maps, blk_in, grp_in;  // exhaustive synchronisation only
     DevBuf row_scratch;                                    // the row walk's published words and ticket (et_rowsync.h)
@@ -102,10 +93,9 @@ struct et_ctx {
     uint64_t *h_hist = nullptr;     // 256
     uint32_t *h_enc = nullptr;      // 768 words: {code,len} x 256, then len x 256; HEADER_STAGE bytes: the file header on its way to the image
     uint8_t *h_header = nullptr;    // HEADER_STAGE
-    uint32_t *h_lut = nullptr;      // the decode tables being built (one of h_lut_buf)
-    uint32_t *h_lut_buf[2] = {};    // DEC_TABLES_BYTES each, used in turn: the host fills one while the other's upload may still be queued
+    uint8_t *h_lut_buf[2] = {};     // DEC_TABLES_BYTES each, used in turn: the host fills one while the other's upload may still be queued
     int lut_turn = 0;
-    uint64_t *h_scalar = nullptr;   // 16: [1] a total, [2..3] flags (range decode), [4..11] the body decode's copy of flag[0..15], [12] / [14] "taken" / "done" words the device stores (enc_block_epoch, header_epoch)
+    uint64_t *h_scalar = nullptr;   // HS_SLOTS words (HostScalar above)
 
     // link between et_histogram_device and et_encode_body_device
     const void *hist_text = nullptr;
@@ -116,9 +106,9 @@ struct et_ctx {
     const void *scan_buf = nullptr;  // the group_sum buffer scan_epoch_n counts on
     size_t scan_cap = 0;
     uint32_t scan_epoch_n = 0;
-    uint32_t report_epoch = 0;     // h_scalar word (4 * 2 + 14) == report_epoch: the current decode's flags and total are in h_flags
-    uint64_t enc_block_epoch = 0;  // h_scalar[12] == enc_block_epoch: the device has taken its copy of h_enc
-    uint64_t header_epoch = 0;  // h_scalar[14] == header_epoch: the header bytes of the current decode are in h_header
+    uint32_t report_epoch = 0;     // word FLAG_REPORT_EPOCH of the HS_BODY_FLAGS words == report_epoch: the current decode's flags and total are there
+    uint64_t enc_block_epoch = 0;  // h_scalar[HS_ENC_TAKEN] == enc_block_epoch: the device has taken its copy of h_enc
+    uint64_t header_epoch = 0;  // h_scalar[HS_HEADER_DONE] == header_epoch: the header bytes of the current decode are in h_header
     uint64_t hist_epoch = 0;    // h_hist[256 + w] == hist_epoch: reducing workgroup w of the current histogram has stored its totals
 
     hipEvent_t ev[12] = {};  // 0..5: encode calls, EV_DEC + 0..5: decode calls

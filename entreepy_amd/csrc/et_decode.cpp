@@ -36,49 +36,42 @@ const DecodeSwitches &decode_switches() {
     return sw;
 }
 
-// Build the decode tables on the host and upload them (one pinned block, one device block,
-// one copy): the step tables of the register-window kernels (k_dec_sync_reg: index
-// step_bits, symbol-free; k_dec_write_reg: index lut_bits_write, two symbols) and ONE set of
-// first/second-level tables + long list in the older format (index lut_bits_write, two
-// symbols per entry) for the LDS-window kernels -- first/last blocks, ranges, the exhaustive
-// path -- and the slow path of the step walks.  (A three-symbol set for the counting kernels
-// used to be built as well: 12 us of host time per call for kernels that now see three
-// blocks of a stream; near-fixed-length codes, the exhaustive path's domain, rarely fit two
-// codes in an index anyway.)
 using et::HostDecodeTables;
-using et::build_decode_tables;
-using et::build_step_table;
-using et::build_write_step_table;
+using et::table_at;
+using Layout = et::DecTableLayout;
 
+// The decode tables of cb into the ctx's device block (et_tables.h DecTableLayout), and the two views of them the kernels
+// take: ONE set of first/second-level tables + long list in the older format (index DEC_LUT_BITS_WRITE, two symbols per
+// entry) for the LDS-window kernels -- first/last blocks, ranges, the exhaustive path -- and the slow path of the step walks,
+// with the step table of the register-window sweeps (k_dec_sync_reg: index DEC_STEP_BITS_DEFAULT, symbol-free) in *tb_out and
+// the write's (k_dec_write_reg: index DEC_LUT_BITS_WRITE, two symbols) in *tb_write_out.  The host only decides -- widths,
+// second-level tables, long-list order: a TablePlan -- and uploads the plan and the two structs; k_build_dec_tables fills the
+// tables.  ET_DEC_TABLES_HOST=1: the host builders fill a pinned block instead, and one copy uploads it as far as it is in use.
+// (A three-symbol set for the counting kernels used to be built as well: 12 us of host time per call for kernels that now see
+// three blocks of a stream; near-fixed-length codes, the exhaustive path's domain, rarely fit two codes in an index anyway.)
 // zero16 / zeroed (optional): 16 device words the table-building kernel clears on its way, and
 // whether it did (the host-built variant has no kernel: the caller clears them itself).
 int prepare_decode_tables(et_ctx *ctx, const et_codebook *cb, et::DecodeTables *tb_out, et::DecodeTables *tb_write_out, uint32_t *zero16 = nullptr,
                           bool *zeroed = nullptr) {
     if (zeroed) *zeroed = false;
-    // one pinned block, one device block, one upload: [first-level x 2 | long lists | second-level (+ lengths) x 2]
     ET_TRY(ensure(ctx, ctx->lut, DEC_TABLES_BYTES));
-    ET_TRY(ensure(ctx, ctx->flag, 64));
+    ET_TRY(ensure(ctx, ctx->flag, et::DEC_FLAG_WORDS * sizeof(uint32_t)));
     // Two pinned blocks used in turn, and no wait here: every caller waits for something enqueued
     // behind this upload before it returns (the decode for its flags, the range calls and the
     // self-test for the stream), so the upload from the block filled two calls ago is long done and
     // the host can fill this one while the stream is still busy with whatever precedes this decode.
-    const int turn = ctx->lut_turn ^= 1;
-    ctx->h_lut = ctx->h_lut_buf[turn];
+    uint8_t *h_lut = ctx->h_lut_buf[ctx->lut_turn ^= 1], *d_lut = static_cast<uint8_t *>(ctx->lut.p);
     const bool on_host = decode_switches().dec_tables_host;  // (the host builders are what the device's tables are tested against)
-    HostDecodeTables ht, hw;
-    uint32_t *h_lut_w = ctx->h_lut + (1u << et::DEC_LUT_BITS_MAX);
-    uint32_t *h_long = ctx->h_lut + (2u << et::DEC_LUT_BITS_MAX), *h_long_w = h_long + 512;
-    uint16_t *h_sub = reinterpret_cast<uint16_t *>(h_long + 1024);
-    uint16_t *h_sub_w = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(h_sub) + SUB_TABLE_BYTES);
-    uint32_t *h_steps = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_lut) + DEC_STEPS_OFFSET);
+    HostDecodeTables hw;
     uint32_t step_bits = 0, step_sub_bits = 0, n_step_sub = 0, wstep_bits = 0, wstep_sub_bits = 0, n_wstep_sub = 0;
     et::TablePlan plan;
     if (on_host) {
-        build_decode_tables(cb, ctx->lut_bits_write, et::DEC_WRITE_SYMS, h_lut_w, h_long_w, h_sub_w, &hw);
-        std::memcpy(reinterpret_cast<uint8_t *>(h_sub_w) + SUB_TABLE_ONLY, cb->length, 256);
-        step_bits = build_step_table(cb, ctx->step_bits, h_steps, &step_sub_bits, &n_step_sub);
-    } else {  // the host only decides (widths, second-level tables, long-list order); k_build_dec_tables fills
-        et::plan_tables(cb, ctx->lut_bits_write, et::DEC_WRITE_SYMS, ctx->step_bits, ctx->lut_bits_write, &plan);
+        et::build_decode_tables(cb, et::DEC_LUT_BITS_WRITE, et::DEC_WRITE_SYMS, table_at<uint32_t>(h_lut, Layout::LUT), table_at<uint32_t>(h_lut, Layout::LONG),
+                            table_at<uint16_t>(h_lut, Layout::SUB), &hw);
+        std::memcpy(h_lut + Layout::SYM_LEN, cb->length, Layout::SYM_LEN_BYTES);
+        step_bits = et::build_step_table(cb, et::DEC_STEP_BITS_DEFAULT, table_at<uint32_t>(h_lut, Layout::STEPS), &step_sub_bits, &n_step_sub);
+    } else {
+        et::plan_tables(cb, et::DEC_LUT_BITS_WRITE, et::DEC_WRITE_SYMS, et::DEC_STEP_BITS_DEFAULT, et::DEC_LUT_BITS_WRITE, &plan);
         hw = HostDecodeTables{plan.lut_bits, plan.n_long, plan.sub_bits, plan.n_sub};
         step_bits = plan.step_bits;
         step_sub_bits = plan.step_sub_bits;
@@ -87,41 +80,29 @@ int prepare_decode_tables(et_ctx *ctx, const et_codebook *cb, et::DecodeTables *
         wstep_sub_bits = plan.wstep_sub_bits;
         n_wstep_sub = plan.n_wstep_sub;
     }
-    ht = hw;
-    const size_t step_bytes = (((static_cast<size_t>(1) << step_bits) + (static_cast<size_t>(n_step_sub) << step_sub_bits) + 3) & ~static_cast<size_t>(3)) * sizeof(uint32_t);
-    uint32_t *h_wsteps = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(h_steps) + step_bytes);  // right behind, one upload
-    if (on_host) wstep_bits = build_write_step_table(cb, ctx->lut_bits_write, h_wsteps, &wstep_sub_bits, &n_wstep_sub);
-    const size_t wstep_bytes = (((static_cast<size_t>(1) << wstep_bits) + (static_cast<size_t>(n_wstep_sub) << wstep_sub_bits) + 3) & ~static_cast<size_t>(3)) * sizeof(uint32_t);
-    uint32_t *d_lut = static_cast<uint32_t *>(ctx->lut.p);
-    uint32_t *d_long = d_lut + (2u << et::DEC_LUT_BITS_MAX);
-    uint8_t *subt = reinterpret_cast<uint8_t *>(d_long + 1024);
-    *tb_out = et::DecodeTables{d_lut + (1u << et::DEC_LUT_BITS_MAX), d_long + 512, reinterpret_cast<const uint16_t *>(subt + SUB_TABLE_BYTES),
-                               subt + SUB_TABLE_BYTES + SUB_TABLE_ONLY, ht.lut_bits, ht.n_long, ht.sub_bits,
-                               ht.n_sub, reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(d_lut) + DEC_STEPS_OFFSET), step_bits,
-                               step_sub_bits, n_step_sub, nullptr};
-    *tb_write_out = et::DecodeTables{d_lut + (1u << et::DEC_LUT_BITS_MAX), d_long + 512,
-                                     reinterpret_cast<const uint16_t *>(subt + SUB_TABLE_BYTES), subt + SUB_TABLE_BYTES + SUB_TABLE_ONLY,
-                                     hw.lut_bits, hw.n_long, hw.sub_bits, hw.n_sub,
-                                     reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(d_lut) + DEC_STEPS_OFFSET + step_bytes), wstep_bits,
-                                     wstep_sub_bits, n_wstep_sub, nullptr};
+    const size_t wsteps_at = Layout::STEPS + et::step_table_bytes(step_bits, step_sub_bits, n_step_sub);  // right behind, one upload
+    if (on_host) wstep_bits = et::build_write_step_table(cb, et::DEC_LUT_BITS_WRITE, table_at<uint32_t>(h_lut, wsteps_at), &wstep_sub_bits, &n_wstep_sub);
     // device copies of the two structs ride behind the tables (slow path of the step walks), the plan behind them
-    const size_t structs_at = DEC_STEPS_OFFSET + step_bytes + wstep_bytes;
-    const et::DecodeTables *d_structs = reinterpret_cast<const et::DecodeTables *>(reinterpret_cast<const uint8_t *>(d_lut) + structs_at);
-    tb_out->dev_copy = d_structs;
-    tb_write_out->dev_copy = d_structs + 1;
-    et::DecodeTables *h_structs = reinterpret_cast<et::DecodeTables *>(reinterpret_cast<uint8_t *>(ctx->h_lut) + structs_at);
-    h_structs[0] = *tb_out;
-    h_structs[1] = *tb_write_out;
+    const size_t structs_at = wsteps_at + et::step_table_bytes(wstep_bits, wstep_sub_bits, n_wstep_sub), plan_at = structs_at + 2 * sizeof(et::DecodeTables);
+    const et::DecodeTables *d_structs = table_at<const et::DecodeTables>(d_lut, structs_at);
+    et::DecodeTables &tb = *tb_out, &tbw = *tb_write_out;
+    tb = et::DecodeTables{table_at<uint32_t>(d_lut, Layout::LUT), table_at<uint32_t>(d_lut, Layout::LONG), table_at<uint16_t>(d_lut, Layout::SUB), d_lut + Layout::SYM_LEN, hw.lut_bits, hw.n_long,
+                          hw.sub_bits, hw.n_sub, table_at<uint32_t>(d_lut, Layout::STEPS), step_bits, step_sub_bits, n_step_sub, d_structs};
+    tbw = tb;  // the same tables, another step table
+    tbw.steps = table_at<uint32_t>(d_lut, wsteps_at);
+    tbw.step_bits = wstep_bits;
+    tbw.step_sub_bits = wstep_sub_bits;
+    tbw.n_step_sub = n_wstep_sub;
+    tbw.dev_copy = d_structs + 1;
+    et::DecodeTables *h_structs = table_at<et::DecodeTables>(h_lut, structs_at);
+    h_structs[0] = tb;
+    h_structs[1] = tbw;
     if (on_host) {
-        ET_HIP(hipMemcpyAsync(ctx->lut.p, ctx->h_lut, structs_at + 2 * sizeof(et::DecodeTables), hipMemcpyHostToDevice, ctx->stream));
+        ET_HIP(hipMemcpyAsync(d_lut, h_lut, plan_at, hipMemcpyHostToDevice, ctx->stream));
     } else {
-        std::memcpy(h_structs + 2, &plan, sizeof plan);
-        uint8_t *d_block = reinterpret_cast<uint8_t *>(d_lut);
-        ET_HIP(hipMemcpyAsync(d_block + structs_at, h_structs, 2 * sizeof(et::DecodeTables) + sizeof plan, hipMemcpyHostToDevice, ctx->stream));
-        et::launch_build_dec_tables(ctx->stream, reinterpret_cast<const et::TablePlan *>(d_block + structs_at + 2 * sizeof(et::DecodeTables)),
-                                    d_lut + (1u << et::DEC_LUT_BITS_MAX), d_long + 512, reinterpret_cast<uint16_t *>(subt + SUB_TABLE_BYTES),
-                                    subt + SUB_TABLE_BYTES + SUB_TABLE_ONLY, reinterpret_cast<uint32_t *>(d_block + DEC_STEPS_OFFSET),
-                                    reinterpret_cast<uint32_t *>(d_block + DEC_STEPS_OFFSET + step_bytes), zero16);
+        std::memcpy(h_lut + plan_at, &plan, sizeof plan);
+        ET_HIP(hipMemcpyAsync(d_lut + structs_at, h_structs, 2 * sizeof(et::DecodeTables) + sizeof plan, hipMemcpyHostToDevice, ctx->stream));
+        et::launch_build_dec_tables(ctx->stream, d_lut, wsteps_at, plan_at, zero16);
         ET_HIP(hipGetLastError());
         if (zeroed) *zeroed = zero16 != nullptr;
     }
@@ -140,14 +121,14 @@ extern "C" int et_selftest_decode_tables(et_ctx *ctx, const et_codebook *cb, int
     std::vector<uint8_t> dev(DEC_TABLES_BYTES);
     ET_HIP(hipMemcpyAsync(dev.data(), ctx->lut.p, DEC_TABLES_BYTES, hipMemcpyDeviceToHost, ctx->stream));
     ET_HIP(hipStreamSynchronize(ctx->stream));
-    std::vector<uint32_t> lut(1u << et::DEC_LUT_BITS_MAX), longc(512), steps((1u << et::DEC_STEP_BITS_MAX) + et::DEC_STEP_SUB_WORDS + 8),
-        wsteps((1u << et::DEC_LUT_BITS_MAX) + et::DEC_STEP_SUB_WORDS + 8);
-    std::vector<uint16_t> sub(SUB_TABLE_ONLY / 2);
+    std::vector<uint32_t> lut(Layout::LUT_BYTES / sizeof(uint32_t)), longc(Layout::LONG_BYTES / sizeof(uint32_t)), steps(Layout::STEPS_BYTES / sizeof(uint32_t)),
+        wsteps(Layout::WSTEPS_BYTES / sizeof(uint32_t));
+    std::vector<uint16_t> sub(Layout::SUB_BYTES / sizeof(uint16_t));
     HostDecodeTables hw;
-    build_decode_tables(cb, ctx->lut_bits_write, et::DEC_WRITE_SYMS, lut.data(), longc.data(), sub.data(), &hw);
+    et::build_decode_tables(cb, et::DEC_LUT_BITS_WRITE, et::DEC_WRITE_SYMS, lut.data(), longc.data(), sub.data(), &hw);
     uint32_t ssb = 0, nss = 0, wsb = 0, nws = 0;
-    const uint32_t sbits = build_step_table(cb, ctx->step_bits, steps.data(), &ssb, &nss);
-    const uint32_t wbits = build_write_step_table(cb, ctx->lut_bits_write, wsteps.data(), &wsb, &nws);
+    const uint32_t sbits = et::build_step_table(cb, et::DEC_STEP_BITS_DEFAULT, steps.data(), &ssb, &nss);
+    const uint32_t wbits = et::build_write_step_table(cb, et::DEC_LUT_BITS_WRITE, wsteps.data(), &wsb, &nws);
     auto at = [&](const void *dptr) { return dev.data() + (static_cast<const uint8_t *>(dptr) - static_cast<const uint8_t *>(ctx->lut.p)); };
     const bool meta_ok = hw.lut_bits == tbw.lut_bits && hw.n_long == tbw.n_long && hw.sub_bits == tbw.sub_bits && hw.n_sub == tbw.n_sub &&
                          sbits == tb.step_bits && ssb == tb.step_sub_bits && nss == tb.n_step_sub && wbits == tbw.step_bits &&
@@ -156,7 +137,7 @@ extern "C" int et_selftest_decode_tables(et_ctx *ctx, const et_codebook *cb, int
     else if (std::memcmp(at(tbw.lut), lut.data(), sizeof(uint32_t) << hw.lut_bits)) *where = 1;
     else if (std::memcmp(at(tbw.longc), longc.data(), 2 * sizeof(uint32_t) * hw.n_long)) *where = 2;
     else if (std::memcmp(at(tbw.sub), sub.data(), (sizeof(uint16_t) * hw.n_sub) << hw.sub_bits)) *where = 3;
-    else if (std::memcmp(at(tbw.sym_len), cb->length, 256)) *where = 4;
+    else if (std::memcmp(at(tbw.sym_len), cb->length, Layout::SYM_LEN_BYTES)) *where = 4;
     else if (std::memcmp(at(tb.steps), steps.data(), sizeof(uint32_t) * ((1u << sbits) + (nss << ssb)))) *where = 5;
     else if (std::memcmp(at(tbw.steps), wsteps.data(), sizeof(uint32_t) * ((1u << wbits) + (nws << wsb)))) *where = 6;
     return *where ? fail(ctx, ET_ERR_FORMAT, "device-built decode tables differ from the host builders'") : ET_OK;
@@ -301,7 +282,7 @@ int ensure_dec_ws(et_ctx *ctx, uint64_t n_subs, uint32_t n_blocks) {
     ET_TRY(ensure(ctx, ctx->blk_count, static_cast<size_t>(n_blocks) * sizeof(uint32_t)));
     ET_TRY(ensure(ctx, ctx->blk_off, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint64_t)));
     ET_TRY(ensure(ctx, ctx->group_sum, (static_cast<size_t>(n_blocks) / 1024 + 2) * sizeof(uint64_t)));
-    ET_TRY(ensure(ctx, ctx->flag, 64));
+    ET_TRY(ensure(ctx, ctx->flag, et::DEC_FLAG_WORDS * sizeof(uint32_t)));
     ET_TRY(ensure(ctx, ctx->worklist, (static_cast<size_t>(n_blocks) + 1) * sizeof(uint32_t)));
     return ET_OK;
 }
@@ -313,10 +294,26 @@ DecWs dec_ws(const et_ctx *ctx) {
                  static_cast<unsigned long long *>(ctx->group_sum.p)};
 }
 
+// The geometry of a span whose subsequences cover n_bits bits, and the workspaces for it.
+int span_ws(et_ctx *ctx, et::DecSpan *s, uint64_t n_bits, const char *too_large) {
+    s->n_subs = (n_bits + et::SUB_BITS - 1) / et::SUB_BITS;
+    const uint64_t n_blocks64 = (s->n_subs + et::BLOCK - 1) / et::BLOCK;
+    if (n_blocks64 > 0x7fffffffull) return fail(ctx, ET_ERR_ARG, too_large);
+    s->n_blocks = static_cast<uint32_t>(n_blocks64);
+    ET_TRY(ensure_dec_ws(ctx, s->n_subs, s->n_blocks));
+    static_cast<DecWs &>(*s) = dec_ws(ctx);
+    return ET_OK;
+}
+
 int not_converged(et_ctx *ctx) { return fail(ctx, ET_ERR_HIP, "decode synchronisation did not converge"); }
 
-// blind: the row walk's word (flag[3]) as the host has it
+// blind: the row walk's word (FLAG_ROW_BLIND) as the host has it
 int check_row_walk(et_ctx *ctx, uint32_t blind) { return blind ? fail(ctx, ET_ERR_HIP, "the row walk's chunks never saw the chunks before them") : ET_OK; }
+
+int launched(et_ctx *ctx) {  // behind every launch of a stage
+    ET_HIP(hipGetLastError());
+    return ET_OK;
+}
 
 // ---- the stages, each over a Span: what et_decode_body_device and the range calls are put together from ----
 
@@ -346,34 +343,28 @@ int tw_setup(et_ctx *ctx, Span &s, et::TwUpload *h_up, bool sweeps, bool zero_fl
 // that leaves open -- a block that did not re-synchronise within its 8 KiB -- a verification finds.  listed: a repair sweep over the
 // blocks tw_list has put on the worklist.
 int tw_sweep(et_ctx *ctx, const Span &s, bool listed, et::KernelEvents ev = {}) {
-    et::launch_tw_sync(ctx->stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.tw_table, s.tw_n_int, s.sub_state, s.blk_exit, s.blk_start, s.blk_count, s.flag,
-                       listed ? 0xffffffffu : et::DEC_FIRST_SWEEP_TRIPS, listed ? s.worklist : nullptr, listed ? s.flag + 8 : nullptr, ev, listed ? nullptr : s.blk_pub, s.tw_mode,
+    et::launch_tw_sync(ctx->stream, s, s.tw_table, s.tw_n_int, s.blk_start, listed ? 0xffffffffu : et::DEC_FIRST_SWEEP_TRIPS, listed, ev, listed ? nullptr : s.blk_pub, s.tw_mode,
                        s.exit_bits);
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+    return launched(ctx);
 }
 
-// The blocks whose first lane did not start where the block before ends -> the worklist (flag[8], zeroed by the caller, counts them).
-void tw_list(et_ctx *ctx, const Span &s) {
-    et::launch_tw_check(ctx->stream, s.blk_start, s.blk_exit, s.n_blocks, s.worklist, s.flag + 8, !(s.tw_mode & et::TW_START_UNKNOWN));
-}
+// The blocks whose first lane did not start where the block before ends -> the worklist (FLAG_WORK_COUNT, zeroed by the caller, counts them).
+void tw_list(et_ctx *ctx, const Span &s) { et::launch_tw_check(ctx->stream, s, s.blk_start, !(s.tw_mode & et::TW_START_UNKNOWN)); }
 
 // A window sweep, number iter of its stream or range.  listed: the first sweeps fill the worklist, the later ones go over it.
 int window_sweep(et_ctx *ctx, const Span &s, uint32_t iter, uint32_t max_trips, bool listed, const et::SideLane *side = nullptr, bool ticket_is_zero = false,
                  et::KernelEvents ev = {}) {
-    et::launch_dec_sync(ctx->stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.tb, iter, max_trips, s.sub_state, s.blk_exit, s.blk_count, s.flag, s.flag + 4, s.dec_flags,
-                        listed ? s.worklist : nullptr, listed ? s.flag + 8 : nullptr, side, ticket_is_zero, ev);
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+    et::launch_dec_sync(ctx->stream, s, s.tb, iter, max_trips, s.dec_flags, listed, side, ticket_is_zero, ev);
+    return launched(ctx);
 }
 
-// Repair sweeps until one changes nothing (flag[0], fetched into *h_changed): tree-walk sweeps over the blocks whose start their
+// Repair sweeps until one changes nothing (FLAG_CHANGED, fetched into *h_changed): tree-walk sweeps over the blocks whose start their
 // predecessor's exit contradicts, or window sweeps -- listed: over the worklist their predecessors left, else over every block --
 // numbered from iter.  *sweeps counts them on.
 int repair_sweeps(et_ctx *ctx, const Span &s, Family family, bool listed, uint32_t iter, uint32_t *sweeps, uint32_t *h_changed) {
     for (;;) {
-        ET_HIP(hipMemsetAsync(s.flag, 0, sizeof(uint32_t), ctx->stream));
-        if (listed) ET_HIP(hipMemsetAsync(s.flag + 8, 0, sizeof(uint32_t), ctx->stream));
+        ET_HIP(hipMemsetAsync(s.flag + et::FLAG_CHANGED, 0, sizeof(uint32_t), ctx->stream));
+        if (listed) ET_HIP(hipMemsetAsync(s.flag + et::FLAG_WORK_COUNT, 0, sizeof(uint32_t), ctx->stream));
         if (family == Family::TREE_WALK) {
             tw_list(ctx, s);
             ET_TRY(tw_sweep(ctx, s, true));
@@ -381,7 +372,7 @@ int repair_sweeps(et_ctx *ctx, const Span &s, Family family, bool listed, uint32
             ET_TRY(window_sweep(ctx, s, iter++, 0xffffffffu, listed));
         }
         ++*sweeps;
-        ET_HIP(hipMemcpyAsync(h_changed, s.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ET_HIP(hipMemcpyAsync(h_changed, s.flag + et::FLAG_CHANGED, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         ET_HIP(hipStreamSynchronize(ctx->stream));
         if (*h_changed == 0) return ET_OK;
         if (*sweeps > s.n_blocks + 4) return not_converged(ctx);
@@ -391,9 +382,8 @@ int repair_sweeps(et_ctx *ctx, const Span &s, Family family, bool listed, uint32
 // The row walk (et_rowsync.h) from s.first_bit, under s.row_mode.  d_map: where a ROW_MAP_ONLY walk leaves its map.
 int row_walk(et_ctx *ctx, const Span &s, const unsigned long long **d_map = nullptr) {
     ET_TRY(ensure(ctx, ctx->row_scratch, et::row_sync_scratch_bytes(s.n_blocks)));
-    et::launch_row_sync(ctx->stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.row_code, ctx->row_scratch.p, s.flag + 3, s.sub_state, s.blk_exit, s.blk_count, s.row_mode, d_map);
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+    et::launch_row_sync(ctx->stream, s, s.row_code, ctx->row_scratch.p, s.row_mode, d_map);
+    return launched(ctx);
 }
 
 // The exit maps (et_kernels_fallback.hip): a map of the L = max_length start offsets per lane, block and group of 256 blocks.
@@ -408,28 +398,25 @@ int exit_maps(et_ctx *ctx, const Span &s, bool const_start) {
     ET_TRY(ensure(ctx, ctx->grp_maps, n_groups * 32 + 64));
     ET_TRY(ensure(ctx, ctx->blk_in, static_cast<size_t>(s.n_blocks) + 64));
     ET_TRY(ensure(ctx, ctx->grp_in, n_groups + 64));
-    et::launch_dec_maps(ctx->stream, s.words, s.n_bytes, s.first_bit, const_start, s.n_subs, s.tb, n_starts, stride, static_cast<uint8_t *>(ctx->lane_maps.p),
-                        static_cast<uint8_t *>(ctx->blk_maps.p), static_cast<uint8_t *>(ctx->grp_maps.p));
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+    et::launch_dec_maps(ctx->stream, s, const_start, s.tb, n_starts, stride, static_cast<uint8_t *>(ctx->lane_maps.p), static_cast<uint8_t *>(ctx->blk_maps.p),
+                        static_cast<uint8_t *>(ctx->grp_maps.p));
+    return launched(ctx);
 }
 
-// ... and every lane's start, exit and count from them, the span entered at first_bit.
-int exit_resolve(et_ctx *ctx, const Span &s, uint32_t first_bit, bool const_start) {
-    et::launch_dec_resolve(ctx->stream, s.words, s.n_bytes, first_bit, const_start, s.n_subs, s.tb, map_stride(s.cb->max_length), static_cast<const uint8_t *>(ctx->lane_maps.p),
-                           static_cast<const uint8_t *>(ctx->blk_maps.p), static_cast<const uint8_t *>(ctx->grp_maps.p), static_cast<uint8_t *>(ctx->blk_in.p),
-                           static_cast<uint8_t *>(ctx->grp_in.p), s.sub_state, s.blk_exit, s.blk_count);
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+// ... and every lane's start, exit and count from them, the span entered at s.first_bit.
+int exit_resolve(et_ctx *ctx, const Span &s, bool const_start) {
+    et::launch_dec_resolve(ctx->stream, s, const_start, s.tb, map_stride(s.cb->max_length), static_cast<const uint8_t *>(ctx->lane_maps.p), static_cast<const uint8_t *>(ctx->blk_maps.p),
+                           static_cast<const uint8_t *>(ctx->grp_maps.p), static_cast<uint8_t *>(ctx->blk_in.p), static_cast<uint8_t *>(ctx->grp_in.p));
+    return launched(ctx);
 }
 
 // D3: at most clamp symbols to out, the way the family that synchronised the span left them.  What only the whole-stream decode has:
 struct WriteExtras {
     bool by_rows = true;                   // ROWS by rows (else over the chained tables: ET_NO_ROW_WRITE)
-    uint32_t ticket = 4;                   // the flag word the window tables' write counts on
+    et::DecFlag ticket = et::FLAG_SYNC_TICKET;  // the flag word the window tables' write counts on
     const et::SideLane *side = nullptr;    // beside which its first/last blocks run
     bool ticket_is_zero = false;
-    const uint32_t *void_flags = nullptr;  // speculative: the kernel itself looks at the sweeps' flags and does nothing if the state is not final
+    bool speculative = false;              // the kernel itself looks at the sweeps' flags and does nothing if the state is not final
     et::KernelEvents ev = {};
     bool strips = false;                   // the chained tables' strips instantiation
 };
@@ -437,17 +424,15 @@ struct WriteExtras {
 int write_span(et_ctx *ctx, const Span &s, Family family, uint64_t clamp, uint8_t *out, const WriteExtras &x = {}) {
     switch (family == Family::ROWS && !x.by_rows ? Family::EXIT_MAPS : family) {
     case Family::ROWS:  // by rows (et_rowsync.h): no table chain, no bank conflicts between the lanes' regions
-        et::launch_row_write(ctx->stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.row_code, s.cb, s.sub_state, s.blk_off, clamp, out, x.ev);
+        et::launch_row_write(ctx->stream, s, s.row_code, s.cb, clamp, out, x.ev);
         break;
     case Family::FIXED_WRITE:  // symbol i is the L bits at first_bit + i L (et_rowsync.h): no walk, no state
-        et::launch_fixed_write(ctx->stream, s.words, s.n_bytes, s.first_bit, s.cb, clamp, out, x.ev);
+        et::launch_fixed_write(ctx->stream, s, s.cb, clamp, out, x.ev);
         break;
     default:  // over the chained tables (s.chain) or the window tables'
-        et::launch_dec_write(ctx->stream, s.words, s.n_bytes, s.n_subs, s.tb_write, s.sub_state, s.blk_off, clamp, out, s.flag + x.ticket, x.side, x.ticket_is_zero, x.void_flags,
-                             x.ev, s.chain, s.n_chain, s.cb->max_length, x.strips);
+        et::launch_dec_write(ctx->stream, s, s.tb_write, clamp, out, x.ticket, x.side, x.ticket_is_zero, x.speculative, x.ev, s.chain, s.n_chain, s.cb->max_length, x.strips);
     }
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+    return launched(ctx);
 }
 
 // ---- one whole-stream decode (et_decode_body_device), as its steps share it ----
@@ -456,7 +441,7 @@ struct BodyDecode : Span {
     uint8_t *out;  // cap bytes
     size_t cap;
     uint64_t n_symbols;
-    uint32_t *h_flags;  // the host copy of flag[0..15]
+    uint32_t *h_flags;  // the host copy of the flag words (et::DecFlag)
     float host_ms;
     et::TwUpload *h_up;  // the code as a tree (one of the pinned blocks; nullptr: none)
     DecodePlan plan;
@@ -486,22 +471,22 @@ int body_setup(BodyDecode &d) {
 }
 
 // D2, the scan of the blocks' symbol counts; its last thread stores the flags and the total into the pinned h_flags and then the
-// launch's epoch into word 14, which the host waits for (wait_report).  first: behind the first sweep, whose block starts (tree walk)
+// launch's epoch into FLAG_REPORT_EPOCH, which the host waits for (wait_report).  first: behind the first sweep, whose block starts (tree walk)
 // or lane states (windows) it verifies.
-int wait_report(BodyDecode &d) { return wait_for_word<uint32_t>(d.ctx, d.h_flags + 14, d.ctx->report_epoch, 200.0, "the decode's report never reached the host"); }
+int wait_report(BodyDecode &d) { return wait_for_word<uint32_t>(d.ctx, d.h_flags + et::FLAG_REPORT_EPOCH, d.ctx->report_epoch, 200.0, "the decode's report never reached the host"); }
 
 int body_scan(BodyDecode &d, bool first) {
     et_ctx *ctx = d.ctx;
     const bool tw = first && d.tw_table;
-    et::launch_dec_scan(ctx->stream, d.blk_count, d.n_blocks, d.group_sum, scan_epoch(ctx), d.blk_off, reinterpret_cast<unsigned long long *>(d.flag + 12),
-                        tw ? d.blk_start : (first ? d.sub_state : nullptr), d.blk_exit, d.flag + 2, tw ? 0u : d.first_bit, d.flag, d.h_flags, tw, ++ctx->report_epoch);
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+    const et::ScanVerify verify{tw ? d.blk_start : (first ? d.sub_state : nullptr), tw, tw ? 0u : d.first_bit};
+    const et::ScanReport report{d.h_flags, ++ctx->report_epoch};
+    et::launch_dec_scan(ctx->stream, d, scan_epoch(ctx), &verify, &report);
+    return launched(ctx);
 }
 
-// D3 with what belongs to this caller: the events, the side lane, flag[5] as the ticket, the strips.  speculative: see WriteExtras.
+// D3 with what belongs to this caller: the events, the side lane, FLAG_WRITE_TICKET, the strips.  speculative: see WriteExtras.
 int write_symbols(BodyDecode &d, uint64_t clamp, bool speculative) {
-    WriteExtras x{d.plan.row_write, 5, &d.ctx->side, d.write_ticket_zero, speculative ? d.flag : nullptr, timed_body(d.ctx, EV_DEC + 2, EV_DEC + 3), false};
+    WriteExtras x{d.plan.row_write, et::FLAG_WRITE_TICKET, &d.ctx->side, d.write_ticket_zero, speculative, timed_body(d.ctx, EV_DEC + 2, EV_DEC + 3), false};
     const bool tables = d.family != Family::FIXED_WRITE && !(d.family == Family::ROWS && d.plan.row_write);
     // More than 128 symbols per 256-bit subsequence: a quarter's output is three or more
     // windows of the write's 4 KiB stage, i.e. it would be walked three or more times -- the instantiation that walks it once, into strips
@@ -519,12 +504,12 @@ int write_symbols(BodyDecode &d, uint64_t clamp, bool speculative) {
 // (on text ~0.4 % of the block boundaries); the scan that follows also verifies that every block starts where its predecessor ends
 // (the "sweep that changes nothing").  Everything up to the write kernel is enqueued without waiting, the speculative write
 // included; the flags and the total reach the host with ONE wait, and only if they say so -- blocks that gave up: the plan's
-// fallback; verification failed: more sweeps -- is the tail redone.  (The flag words: et_ctx.h.)
+// fallback; verification failed: more sweeps -- is the tail redone.  (The flag words: et_kernels.h DecFlag.)
 int body_first_sweep(BodyDecode &d) {
     if (!is_sweep(d.family)) return ET_OK;
     et_ctx *ctx = d.ctx;
     const et::SideLane *side = &ctx->side;  // the first/last blocks' small launches run beside the large kernels (2.3 % at 1 GiB)
-    if (!d.flags_zeroed) ET_HIP(hipMemsetAsync(d.flag, 0, 16 * sizeof(uint32_t), ctx->stream));
+    if (!d.flags_zeroed) ET_HIP(hipMemsetAsync(d.flag, 0, et::DEC_FLAG_WORDS * sizeof(uint32_t), ctx->stream));
     d.write_ticket_zero = true;
     if (d.tw_table) {
         ET_TRY(tw_sweep(ctx, d, false, timed(ctx, EV_DEC + 0, EV_DEC + 5)));
@@ -539,10 +524,11 @@ int body_first_sweep(BodyDecode &d) {
         d.wrote = true;
     }
     ET_TRY(wait_report(d));  // not the stream: the write kernel keeps running while the caller moves on
-    const bool gave_up = static_cast<uint64_t>(d.h_flags[1]) * 64 > d.n_blocks;
+    const uint32_t n_gave_up = d.h_flags[et::FLAG_GAVE_UP], verify_failed = d.h_flags[et::FLAG_VERIFY_FAILED];
+    const bool gave_up = static_cast<uint64_t>(n_gave_up) * 64 > d.n_blocks;
     if (gave_up) d.family = d.plan.fallback;
-    d.more_sweeps = !gave_up && d.h_flags[2] != 0;
-    if (!et::dec_state_final(d.h_flags[1], d.h_flags[2], d.n_blocks)) d.wrote = d.strips = false;  // the speculative launch declined by the same rule
+    d.more_sweeps = !gave_up && verify_failed != 0;
+    if (!et::dec_state_final(n_gave_up, verify_failed, d.n_blocks)) d.wrote = d.strips = false;  // the speculative launch declined by the same rule
     return ET_OK;
 }
 
@@ -559,7 +545,7 @@ int body_exhaustive(BodyDecode &d) {
         ET_TRY(row_walk(ctx, d));
         d.iters += 1;
     } else if (d.family == Family::FIXED_SYNC) {
-        et::launch_fixed_sync(ctx->stream, d.n_bytes, d.first_bit, d.n_subs, d.cb->max_length, d.sub_state, d.blk_exit, d.blk_count);
+        et::launch_fixed_sync(ctx->stream, d, d.cb->max_length);
         d.iters += 1;
     } else if (d.family == Family::EXIT_MAPS) {
         if (d.plan.first == Family::TREE_WALK) ET_TRY(prepare_decode_tables(ctx, d.cb, &d.tb, &d.tb_write));  // (the others built them up front)
@@ -568,11 +554,10 @@ int body_exhaustive(BodyDecode &d) {
         // FULL tree (an encoder's) -- for a completed one the write has to count like the synchronisation did.
         if (!d.plan.full_tree) d.chain = nullptr;
         ET_TRY(exit_maps(ctx, d, true));
-        ET_TRY(exit_resolve(ctx, d, d.first_bit, true));
+        ET_TRY(exit_resolve(ctx, d, true));
         d.iters += 5;
     }
-    ET_HIP(hipGetLastError());
-    return ET_OK;
+    return launched(ctx);
 }
 
 // The scan behind the exhaustive families and the repair sweeps (k_fixed_write has nothing to scan).
@@ -580,10 +565,13 @@ int body_final_scan(BodyDecode &d) {
     if ((is_sweep(d.family) && !d.more_sweeps) || d.family == Family::FIXED_WRITE) return ET_OK;
     ET_TRY(body_scan(d, false));
     ET_TRY(wait_report(d));
-    return d.family == Family::ROWS ? check_row_walk(d.ctx, d.h_flags[3]) : ET_OK;
+    return d.family == Family::ROWS ? check_row_walk(d.ctx, d.h_flags[et::FLAG_ROW_BLIND]) : ET_OK;
 }
 
-// What et_last_timings reports; the events' arithmetic waits for the first call that asks.
+// What et_last_timings reports; the events' arithmetic waits for the first call that asks.  The bits of et_timings.reserved, as
+// include/entreepy_hip.h documents them (and entreepy_amd/codec.py reads them):
+enum : uint32_t { TM_EXHAUSTIVE = 1, TM_TREE_WALK = 2, TM_CHAINED_WRITE = 4, TM_ROWS = 8, TM_FIXED = 16, TM_STRIPS = 32 };
+
 void body_timings(const BodyDecode &d) {
     et_ctx *ctx = d.ctx;
     if (!ctx->timing && !ctx->timing_body) return;
@@ -591,8 +579,8 @@ void body_timings(const BodyDecode &d) {
     ctx->tm_dec = et_timings{};
     ctx->tm_dec.host_ms = d.host_ms;
     ctx->tm_dec.sync_iters = d.iters;
-    ctx->tm_dec.reserved = (is_sweep(d.family) ? 0u : 1u) | (d.tw_table ? 2u : 0u) | (d.chain ? 4u : 0u) | (d.family == Family::ROWS ? 8u : 0u) |
-                           (fixed ? 16u : 0u) | (d.strips ? 32u : 0u);
+    ctx->tm_dec.reserved = (is_sweep(d.family) ? 0u : TM_EXHAUSTIVE) | (d.tw_table ? TM_TREE_WALK : 0u) | (d.chain ? TM_CHAINED_WRITE : 0u) |
+                           (d.family == Family::ROWS ? TM_ROWS : 0u) | (fixed ? TM_FIXED : 0u) | (d.strips ? TM_STRIPS : 0u);
     ctx->pend_dec = true;
     ctx->pend_dec_first = is_sweep(d.plan.first);
     ctx->last_kind = 1;
@@ -607,8 +595,13 @@ extern "C" int et_decode_path(const et_codebook *cb, uint32_t *path) {
     if (cb->max_length > 32) return ET_ERR_UNSUPPORTED;
     et::TwTree tree;
     const bool have_tree = et::tw_build_tree(cb, &tree, true) == ET_OK;
-    static const uint32_t path_of[] = {ET_PATH_TREE_WALK, ET_PATH_WINDOWS, ET_PATH_ROWS, ET_PATH_FIXED, ET_PATH_FIXED, ET_PATH_EXIT_MAPS};  // by Family
-    *path = path_of[static_cast<int>(plan_decode(cb, have_tree ? &tree : nullptr, DecodeSwitches{}).first)];
+    switch (plan_decode(cb, have_tree ? &tree : nullptr, DecodeSwitches{}).first) {
+    case Family::TREE_WALK: *path = ET_PATH_TREE_WALK; break;
+    case Family::WINDOWS: *path = ET_PATH_WINDOWS; break;
+    case Family::ROWS: *path = ET_PATH_ROWS; break;
+    case Family::FIXED_SYNC: case Family::FIXED_WRITE: *path = ET_PATH_FIXED; break;
+    case Family::EXIT_MAPS: *path = ET_PATH_EXIT_MAPS; break;
+    }
     return ET_OK;
 }
 
@@ -628,20 +621,15 @@ extern "C" int et_decode_body_device(et_ctx *ctx, const et_codebook *cb, const v
     d.words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
     d.first_bit = static_cast<uint32_t>(a & 3) * 8 + start_bit;
     d.n_bytes = (a & 3) + body_bytes;  // stream bytes measured from the aligned base
-    d.n_subs = (d.n_bytes * 8 + et::SUB_BITS - 1) / et::SUB_BITS;
-    const uint64_t n_blocks64 = (d.n_subs + et::BLOCK - 1) / et::BLOCK;
-    if (n_blocks64 > 0x7fffffffull) return fail(ctx, ET_ERR_ARG, "body too large");
-    d.n_blocks = static_cast<uint32_t>(n_blocks64);
+    ET_TRY(span_ws(ctx, &d, d.n_bytes * 8, "body too large"));
     d.dec_flags = et::DEC_HAVE_START;
-    ET_TRY(ensure_dec_ws(ctx, d.n_subs, d.n_blocks));
-    static_cast<DecWs &>(d) = dec_ws(ctx);
     ctx->range.valid = ctx->range.maps_valid = false;  // shares the workspaces
     d.ctx = ctx;
     d.cb = cb;
     d.out = static_cast<uint8_t *>(d_out);
     d.cap = cap;
     d.n_symbols = n_symbols;
-    d.h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 4);
+    d.h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + HS_BODY_FLAGS);
 
     ET_TRY(body_setup(d));
     ET_TRY(body_first_sweep(d));
@@ -650,7 +638,7 @@ extern "C" int et_decode_body_device(et_ctx *ctx, const et_codebook *cb, const v
     ET_TRY(body_final_scan(d));
     const uint64_t decodable = d.family == Family::FIXED_WRITE
                                    ? (d.n_bytes * 8 >= d.first_bit ? (d.n_bytes * 8 - d.first_bit) / cb->max_length : 0)  // the whole codewords from first_bit on
-                                   : static_cast<uint64_t>(d.h_flags[12]) | (static_cast<uint64_t>(d.h_flags[13]) << 32);
+                                   : static_cast<uint64_t>(d.h_flags[et::FLAG_TOTAL_LO]) | (static_cast<uint64_t>(d.h_flags[et::FLAG_TOTAL_HI]) << 32);
     const uint64_t n_out = decodable < n_symbols ? decodable : n_symbols;
     if (n_out > cap) return fail(ctx, ET_ERR_CAP, "output buffer too small");
     if (n_out && !d.wrote) ET_TRY(write_symbols(d, n_out, false));
@@ -672,14 +660,8 @@ int range_span(et_ctx *ctx, const et_codebook *cb, const void *d_range, size_t r
     *s = Span{};
     s->words = static_cast<const uint32_t *>(d_range);
     s->n_bytes = static_cast<uint64_t>(range_bytes) + tail_bytes;
-    s->n_subs = (static_cast<uint64_t>(range_bytes) * 8 + et::SUB_BITS - 1) / et::SUB_BITS;
-    const uint64_t n_blocks64 = (s->n_subs + et::BLOCK - 1) / et::BLOCK;
-    if (n_blocks64 > 0x7fffffffull) return fail(ctx, ET_ERR_ARG, "range too large");
-    s->n_blocks = static_cast<uint32_t>(n_blocks64);
     s->first_bit = in_start_bit >= 0 ? static_cast<uint32_t>(in_start_bit) : 0u;
-    ET_TRY(ensure_dec_ws(ctx, s->n_subs, s->n_blocks));
-    static_cast<DecWs &>(*s) = dec_ws(ctx);
-    return ET_OK;
+    return span_ws(ctx, s, static_cast<uint64_t>(range_bytes) * 8, "range too large");
 }
 
 // The range the ctx holds becomes s, to be synchronised by family; nothing of it is valid yet.
@@ -700,29 +682,36 @@ bool same_range_again(const et_ctx *ctx, const Span &s, bool known) {
     return rs.valid && rs.family == Family::WINDOWS && rs.s.words == s.words && rs.s.n_subs == s.n_subs && known;
 }
 
+// The range calls' words in pinned host memory (RangeFlag).
+uint32_t *range_flags(et_ctx *ctx) { return reinterpret_cast<uint32_t *>(ctx->h_scalar + HS_RANGE_FLAGS); }
+
 // The tail of every range synchronisation: the scan of its blocks' counts, then its start, exit (the tree walk's exit bit, else the last
 // block's exit) and total to the host; the range is ready for et_decode_range_write.
 int finish_range(et_ctx *ctx, uint32_t sweeps, et_range_info *info) {
     auto &rs = ctx->range;
     const Span &s = rs.s;
-    const uint32_t *row_word = rs.family == Family::ROWS ? s.flag + 3 : nullptr;
-    uint32_t *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 2);
-    et::launch_dec_scan(ctx->stream, s.blk_count, s.n_blocks, s.group_sum, scan_epoch(ctx), s.blk_off);
+    const uint32_t *row_word = rs.family == Family::ROWS ? s.flag + et::FLAG_ROW_BLIND : nullptr;
+    uint32_t *h_flags = range_flags(ctx);
+    et::launch_dec_scan(ctx->stream, s, scan_epoch(ctx));
     ET_HIP(hipGetLastError());
-    ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, s.blk_off + s.n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    ET_HIP(hipMemcpyAsync(h_flags, s.sub_state, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    ET_HIP(hipMemcpyAsync(h_flags + 1, s.exit_bits ? s.exit_bits : s.blk_exit + (s.n_blocks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (row_word) ET_HIP(hipMemcpyAsync(h_flags + 2, row_word, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ET_HIP(hipMemcpyAsync(ctx->h_scalar + HS_TOTAL, s.blk_off + s.n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    ET_HIP(hipMemcpyAsync(h_flags + RF_START, s.sub_state, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ET_HIP(hipMemcpyAsync(h_flags + RF_EXIT, s.exit_bits ? s.exit_bits : s.blk_exit + (s.n_blocks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (row_word) ET_HIP(hipMemcpyAsync(h_flags + RF_ROW_BLIND, row_word, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     ET_HIP(hipStreamSynchronize(ctx->stream));
-    if (row_word) ET_TRY(check_row_walk(ctx, h_flags[2]));
-    static const uint32_t reserved_of[] = {2, 0, 3, 0, 0, 1};  // by Family, as include/entreepy_hip.h documents et_range_info.reserved
-    rs.total = ctx->h_scalar[1];
+    if (row_word) ET_TRY(check_row_walk(ctx, h_flags[RF_ROW_BLIND]));
+    rs.total = ctx->h_scalar[HS_TOTAL];
     rs.valid = true;
-    info->start_bit = h_flags[0] & 0xffu;
-    info->exit_bit = h_flags[1];
+    info->start_bit = h_flags[RF_START] & 0xffu;
+    info->exit_bit = h_flags[RF_EXIT];
     info->n_symbols = rs.total;
     info->sweeps = sweeps;
-    info->reserved = reserved_of[static_cast<int>(rs.family)];
+    switch (rs.family) {  // as include/entreepy_hip.h documents et_range_info.reserved
+    case Family::TREE_WALK: info->reserved = 2; break;
+    case Family::ROWS: info->reserved = 3; break;
+    case Family::EXIT_MAPS: info->reserved = 1; break;
+    default: info->reserved = 0;  // WINDOWS (the fixed-length families never synchronise a range)
+    }
     return ET_OK;
 }
 
@@ -735,7 +724,7 @@ extern "C" int et_decode_range_sync(et_ctx *ctx, const et_codebook *cb, const vo
     Span g;
     ET_TRY(range_span(ctx, cb, d_range, range_bytes, tail_bytes, in_start_bit, has_front != 0, &g));
     const bool known = in_start_bit >= 0;
-    uint32_t *h_flags = reinterpret_cast<uint32_t *>(ctx->h_scalar + 2);
+    uint32_t *h_flags = range_flags(ctx);
     et::TwUpload *h_up = ctx->h_tw_tree[ctx->tw_turn ^= 1];
     const bool have_tree = et::tw_build_tree(cb, &h_up->tree, true) == ET_OK;
     uint32_t sweeps = 0;
@@ -746,18 +735,18 @@ extern "C" int et_decode_range_sync(et_ctx *ctx, const et_codebook *cb, const vo
         // A second call for the same range with the predecessor's exit simply sweeps again from that bit.
         Span &s = begin_range(ctx, g, cb, Family::TREE_WALK);
         s.tw_mode = (has_front ? et::TW_FRONT_OK : 0u) | (known ? 0u : et::TW_START_UNKNOWN);
-        s.exit_bits = s.flag + 9;
+        s.exit_bits = s.flag + et::FLAG_RANGE_EXIT;
         ET_TRY(tw_setup(ctx, s, h_up, true, true));
         ET_TRY(tw_sweep(ctx, s, false));
         ++sweeps;
         // Not repair_sweeps: the whole-stream decode comes here knowing from its scan that a block disagrees and asks each sweep
         // whether it changed anything; a range has no scan yet and asks the list itself, before the first repair sweep.
         for (;;) {  // (normally one look: nothing on the list)
-            ET_HIP(hipMemsetAsync(s.flag + 8, 0, sizeof(uint32_t), ctx->stream));
+            ET_HIP(hipMemsetAsync(s.flag + et::FLAG_WORK_COUNT, 0, sizeof(uint32_t), ctx->stream));
             tw_list(ctx, s);
-            ET_HIP(hipMemcpyAsync(h_flags, s.flag + 8, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            ET_HIP(hipMemcpyAsync(h_flags + RF_START, s.flag + et::FLAG_WORK_COUNT, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
             ET_HIP(hipStreamSynchronize(ctx->stream));
-            if (h_flags[0] == 0) break;
+            if (h_flags[RF_START] == 0) break;
             if (sweeps > s.n_blocks + 4) return not_converged(ctx);
             ET_TRY(tw_sweep(ctx, s, true));
             ++sweeps;
@@ -775,11 +764,11 @@ extern "C" int et_decode_range_sync(et_ctx *ctx, const et_codebook *cb, const vo
         ET_TRY(prepare_decode_tables(ctx, cb, &s.tb, &s.tb_write));
         // Sweep 0 (run-in, local repair with a trip cap); codes that do not synchronise take
         // many capped sweeps here -- the exhaustive path is single-GPU only for now.
-        ET_HIP(hipMemsetAsync(s.flag, 0, 4 * sizeof(uint32_t), ctx->stream));
+        ET_HIP(hipMemsetAsync(s.flag, 0, et::DEC_SWEEP_FLAGS * sizeof(uint32_t), ctx->stream));
         ET_TRY(window_sweep(ctx, s, 0, et::DEC_FIRST_SWEEP_TRIPS, false));
         ++sweeps;
     }
-    ET_TRY(repair_sweeps(ctx, ctx->range.s, Family::WINDOWS, false, 1 + sweeps, &sweeps, h_flags));
+    ET_TRY(repair_sweeps(ctx, ctx->range.s, Family::WINDOWS, false, 1 + sweeps, &sweeps, h_flags + RF_START));
     return finish_range(ctx, sweeps, info);
 }
 
@@ -798,14 +787,14 @@ extern "C" int et_decode_range_maps(et_ctx *ctx, const et_codebook *cb, const vo
         // its map, the last one composes them (k_row_sync, ROW_MAP_ONLY); the resolve is a second run with the start known.
         s.row_code = plan.row_code;
         s.row_mode = et::ROW_MAP_ONLY | (known ? 0u : et::ROW_START_UNKNOWN);
-        ET_HIP(hipMemsetAsync(s.flag, 0, 16 * sizeof(uint32_t), ctx->stream));
+        ET_HIP(hipMemsetAsync(s.flag, 0, et::DEC_FLAG_WORDS * sizeof(uint32_t), ctx->stream));
         const unsigned long long *d_map = nullptr;
         ET_TRY(row_walk(ctx, s, &d_map));
-        ET_HIP(hipMemcpyAsync(ctx->h_scalar + 1, d_map, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        ET_HIP(hipMemcpyAsync(ctx->h_scalar + 2, s.flag + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ET_HIP(hipMemcpyAsync(ctx->h_scalar + HS_TOTAL, d_map, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ET_HIP(hipMemcpyAsync(range_flags(ctx) + RF_ROW_BLIND, s.flag + et::FLAG_ROW_BLIND, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         ET_HIP(hipStreamSynchronize(ctx->stream));
-        ET_TRY(check_row_walk(ctx, *reinterpret_cast<const uint32_t *>(ctx->h_scalar + 2)));
-        const uint64_t m = ctx->h_scalar[1];
+        ET_TRY(check_row_walk(ctx, range_flags(ctx)[RF_ROW_BLIND]));
+        const uint64_t m = ctx->h_scalar[HS_TOTAL];
         for (uint32_t p = 0; p < 32; ++p) map[p] = static_cast<uint8_t>(p < 8 ? (m >> (8 * p)) & 0xffu : (known ? m & 0xffu : p));
         *n_starts_out = 8;
     } else {
@@ -837,13 +826,13 @@ extern "C" int et_decode_range_resolve(et_ctx *ctx, uint32_t in_start_bit, et_ra
     DeviceGuard guard(ctx->device);
     Span &s = rs.s;
     static_cast<DecWs &>(s) = dec_ws(ctx);
+    s.first_bit = in_start_bit;  // (kept in the span for both families; after this call only the row walk's write looks at it)
     if (rs.family == Family::ROWS) {  // the same walk again, the start known: every lane's start, exit and count
-        s.first_bit = in_start_bit;
         s.row_mode = 0;
-        ET_HIP(hipMemsetAsync(s.flag, 0, 16 * sizeof(uint32_t), ctx->stream));
+        ET_HIP(hipMemsetAsync(s.flag, 0, et::DEC_FLAG_WORDS * sizeof(uint32_t), ctx->stream));
         ET_TRY(row_walk(ctx, s));
     } else {
-        ET_TRY(exit_resolve(ctx, s, in_start_bit, rs.maps_const));
+        ET_TRY(exit_resolve(ctx, s, rs.maps_const));
     }
     return finish_range(ctx, 0, info);
 }
@@ -876,7 +865,7 @@ extern "C" int et_decode_device(et_ctx *ctx, const void *d_compressed, size_t le
     // A one-workgroup kernel stores the bytes into the pinned stage and then a "done" word, which the host polls (a
     // copy command and a stream wait cost ~10 us more, between the two halves of an encode + decode pipeline).
     uint8_t *hdr_data = ctx->h_header;
-    volatile uint64_t *done = ctx->h_scalar + 14;
+    volatile uint64_t *done = ctx->h_scalar + HS_HEADER_DONE;
     const uint64_t epoch = ++ctx->header_epoch;
     et::launch_header_to_host(ctx->stream, d_compressed, static_cast<uint32_t>(head), hdr_data, const_cast<unsigned long long *>(reinterpret_cast<volatile unsigned long long *>(done)), epoch);
     ET_HIP(hipGetLastError());

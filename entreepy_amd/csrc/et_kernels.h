@@ -51,22 +51,38 @@ constexpr uint32_t DEC_STAGED_WORDS = DEC_FRONT_WORDS + DEC_BLOCK_WORDS + DEC_GU
 constexpr uint32_t DEC_SDATA_WORDS = (DEC_STAGED_WORDS + (DEC_STAGED_WORDS >> 5) + 4) & ~3u;  // 1 pad word per 32
 constexpr uint32_t DEC_STAGE_BYTES = 16384;                    // LDS staging of decoded symbols
 
-// Device-resident decode tables (built on the host, et_api.cpp build_decode_tables).
-struct DecodeTables {
-    const uint32_t *lut;     // [1 << lut_bits] first-level entries (LUT_* above)
-    const uint32_t *longc;   // [n_long * 2]: {left-aligned code, (len << 8) | sym} of every code longer than lut_bits
-    const uint16_t *sub;     // [n_sub << sub_bits] second-level tables
-    const uint8_t *sym_len;  // [256] code length per symbol (single-symbol steps)
-    uint32_t lut_bits;
-    uint32_t n_long;
-    uint32_t sub_bits;
-    uint32_t n_sub;
-    const uint32_t *steps;   // [1 << step_bits] packed walk increments for k_dec_sync_reg (STEP_* below), or null;
-                             // followed by n_step_sub second-level tables of 1 << step_sub_bits entries
-    uint32_t step_bits;
-    uint32_t step_sub_bits;
-    uint32_t n_step_sub;
-    const DecodeTables *dev_copy;  // this struct in device memory (slow path of the step walks), or null
+// The 16 device words the decode's kernels and the host share (et_ctx::flag; DecWs::flag below), and the host's copy of them
+// (k_scan_fused's report: words 0 .. 11 as they are, then the total and the epoch).
+enum DecFlag : uint32_t {
+    FLAG_CHANGED = 0,        // a sweep changed something (every repair sweep clears it first)
+    FLAG_GAVE_UP = 1,        // blocks that gave up in the first sweep
+    FLAG_VERIFY_FAILED = 2,  // the scan's verification failed
+    FLAG_ROW_BLIND = 3,      // the row walk: a chunk never saw the chunks before it
+    FLAG_SYNC_TICKET = 4,    // ticket of the window sweeps (D1), and of a range's write
+    FLAG_WRITE_TICKET = 5,   // ticket of the whole-stream write (D3)
+    FLAG_WORK_COUNT = 8,     // worklist count
+    FLAG_RANGE_EXIT = 9,     // a tree-walked range's exit bit (k_tw_sync's exit_bits)
+    FLAG_TOTAL_LO = 12,      // symbol total ...
+    FLAG_TOTAL_HI = 13,
+    FLAG_REPORT_EPOCH = 14,  // the host's copy only: the epoch of the report that filled it
+    DEC_FLAG_WORDS = 16
+};
+constexpr uint32_t DEC_SWEEP_FLAGS = 4;  // the words in front of the tickets: all a first window sweep needs cleared
+static_assert(FLAG_CHANGED < DEC_SWEEP_FLAGS && FLAG_GAVE_UP < DEC_SWEEP_FLAGS && FLAG_VERIFY_FAILED < DEC_SWEEP_FLAGS && FLAG_ROW_BLIND < DEC_SWEEP_FLAGS &&
+                  FLAG_SYNC_TICKET >= DEC_SWEEP_FLAGS && FLAG_WRITE_TICKET >= DEC_SWEEP_FLAGS,
+              "the sweeps' flags lie in front of the tickets, which clear themselves");
+
+// The workspaces every synchronisation writes, as the kernels take them.
+struct DecWs {
+    uint32_t *sub_state, *blk_exit, *blk_count, *flag, *worklist;
+    unsigned long long *blk_off, *group_sum;
+};
+
+// What a decode launch runs over: a whole stream, or a range of one split over GPUs.
+struct DecSpan : DecWs {
+    const uint32_t *words;     // from a 4-byte aligned base
+    uint64_t n_bytes, n_subs;  // a range's: the bytes after it included, the subsequences after it not
+    uint32_t n_blocks, first_bit;  // n_blocks = n_subs in workgroups of BLOCK, rounded up
 };
 
 // The three-workgroup launches for the stream's first/last blocks take ~25 us each (one
@@ -100,33 +116,33 @@ void launch_tile_scan(hipStream_t stream, const uint32_t *tile_hist, uint32_t n_
                       unsigned long long *tile_off, uint32_t *out32, const uint32_t *header_src = nullptr, uint32_t header_words = 0);  // header_src (device): the file header, copied to out32[0 .. header_words) behind the seam word's zeroing
 void launch_encode(hipStream_t stream, const uint8_t *base, uint64_t lo, uint64_t hi, uint32_t rounds_per_tile, uint32_t n_tiles,
                    const unsigned long long *tile_off, const uint2 *enc_table, uint32_t max_len, uint32_t *out32, KernelEvents ev = {});
-void launch_dec_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs,
-                     const DecodeTables &tb, uint32_t iter, uint32_t max_trips,
-                     uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count, uint32_t *changed, uint32_t *ticket,
-                     uint32_t flags = DEC_HAVE_START, uint32_t *worklist = nullptr, uint32_t *n_work = nullptr, const SideLane *side = nullptr,
-                     bool ticket_is_zero = false, KernelEvents ev = {});  // ev: the first sweep's main kernel
-void launch_dec_maps(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, bool have_start, uint64_t n_subs,
-                     const DecodeTables &tb, uint32_t n_starts, uint32_t map_stride, uint8_t *lane_maps, uint8_t *blk_maps, uint8_t *grp_maps);
-void launch_dec_resolve(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, bool const_first, uint64_t n_subs,
-                        const DecodeTables &tb, uint32_t map_stride, const uint8_t *lane_maps, const uint8_t *blk_maps, const uint8_t *grp_maps,
-                        uint8_t *blk_in, uint8_t *grp_in, uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count);
-// Fill the decode tables on the device from the host's plan (d_plan in device memory).  Layout of
-// the outputs as the host builders': lut[1 << lut_bits], longc[2 * n_long], sub[n_sub << sub_bits],
+// D1 by window sweeps over s, number iter of it; counts on FLAG_SYNC_TICKET, raises FLAG_CHANGED.  listed (iter >= 1): the blocks that
+// disagree with the one before them go on s.worklist (FLAG_WORK_COUNT, zeroed by the caller, counts them) and the sweep is over
+// those; else over every block.
+void launch_dec_sync(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint32_t iter, uint32_t max_trips, uint32_t flags = DEC_HAVE_START,
+                     bool listed = false, const SideLane *side = nullptr, bool ticket_is_zero = false, KernelEvents ev = {});  // ev: the first sweep's main kernel
+void launch_dec_maps(hipStream_t stream, const DecSpan &s, bool have_start, const DecodeTables &tb, uint32_t n_starts, uint32_t map_stride,
+                     uint8_t *lane_maps, uint8_t *blk_maps, uint8_t *grp_maps);
+void launch_dec_resolve(hipStream_t stream, const DecSpan &s, bool const_first, const DecodeTables &tb, uint32_t map_stride, const uint8_t *lane_maps,
+                        const uint8_t *blk_maps, const uint8_t *grp_maps, uint8_t *blk_in, uint8_t *grp_in);
+// Fill the decode tables in a device block (et_tables.h DecTableLayout) from the host's plan, which lies at plan_at of that block; the
+// write-step table goes to wsteps_at.  The tables as the host builders': lut[1 << lut_bits], longc[2 * n_long], sub[n_sub << sub_bits],
 // sym_len[256], steps[(1 << step_bits) + second level], wsteps[(1 << wstep_bits) + second level].
 // zero16 (optional): 16 words the kernel also clears (the decode's flags).
-void launch_build_dec_tables(hipStream_t stream, const TablePlan *d_plan, uint32_t *lut, uint32_t *longc, uint16_t *sub, uint8_t *sym_len,
-                             uint32_t *steps, uint32_t *wsteps, uint32_t *zero16 = nullptr);
-void launch_dec_scan(hipStream_t stream, const uint32_t *blk_count, uint32_t n_blocks, unsigned long long *group_sum, uint32_t epoch,
-                     unsigned long long *blk_off, unsigned long long *total_copy = nullptr, const uint32_t *verify_state = nullptr,
-                     const uint32_t *verify_exit = nullptr, uint32_t *verify_flag = nullptr, uint32_t verify_first = 0xffffffffu,
-                     const uint32_t *report_src = nullptr, uint32_t *report_dst = nullptr,  // report_dst: 15 words of pinned host memory (flags 0..11 of report_src, symbol total, then report_epoch)
-                     bool verify_rows = false,  // verify_state is the tree walk's blk_start (one row per block) instead of sub_state
-                     uint32_t report_epoch = 0);
-void launch_dec_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint64_t n_subs, const DecodeTables &tb,
-                      const uint32_t *sub_state,
-                      const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, uint32_t *ticket, const SideLane *side = nullptr,
-                      bool ticket_is_zero = false, const uint32_t *void_flags = nullptr, KernelEvents ev = {},  // ev: the main write kernel
-                      const uint64_t *chain = nullptr, uint32_t n_chain = 0, uint32_t chain_max_len = 32,  // chained lookup tables (et_treewalk.h) and the dictionary's longest code: every block by k_dec_write_wave
-                      bool strips = false);  // ... by its instantiation for streams with many symbols per subsequence (quarters that overflow the stage walk once, into strips)
+void launch_build_dec_tables(hipStream_t stream, uint8_t *d_block, size_t wsteps_at, size_t plan_at, uint32_t *zero16 = nullptr);
+// D2, the scan of s.blk_count into s.blk_off, and what it may do on its way.  ScanVerify: every block started where the one before it
+// ends (s.blk_exit), block 0 at `first`, or FLAG_VERIFY_FAILED is raised -- state: s.sub_state, or (rows) the tree walk's blk_start, one
+// row per block; nullptr: nothing is verified.  ScanReport: the total to FLAG_TOTAL_LO / _HI, and FLAG_CHANGED .. 11, the total and then
+// epoch (FLAG_REPORT_EPOCH) to host, 15 words of pinned host memory.
+struct ScanVerify { const uint32_t *state; bool rows; uint32_t first; };
+struct ScanReport { uint32_t *host; uint32_t epoch; };
+void launch_dec_scan(hipStream_t stream, const DecSpan &s, uint32_t epoch, const ScanVerify *verify = nullptr, const ScanReport *report = nullptr);
+// D3 over the chained lookup tables (et_treewalk.h; chain_max_len: the dictionary's longest code), every block by k_dec_write_wave --
+// strips: by its instantiation for streams with many symbols per subsequence (quarters that overflow the stage walk once, into
+// strips) -- or, chain == nullptr, over tb, counting on flag word `ticket` (FLAG_SYNC_TICKET or FLAG_WRITE_TICKET).  speculative: the
+// kernel itself looks at the sweeps' flags and does nothing if the state is not final (dec_state_final).
+void launch_dec_write(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint64_t n_symbols, uint8_t *out, DecFlag ticket = FLAG_SYNC_TICKET,
+                      const SideLane *side = nullptr, bool ticket_is_zero = false, bool speculative = false, KernelEvents ev = {},  // ev: the main write kernel
+                      const uint64_t *chain = nullptr, uint32_t n_chain = 0, uint32_t chain_max_len = 32, bool strips = false);
 
 }  // namespace et

@@ -1072,34 +1072,34 @@ void launch_encode(hipStream_t stream, const uint8_t *base, uint64_t lo, uint64_
         ET_LAUNCH_TIMED(k_encode_tiles<8192>, dim3(tile_grid(k_encode_tiles<8192>, n_tiles)), dim3(BLOCK), 0, stream, ev, base, lo, hi, rounds_per_tile, n_tiles, tile_off, enc_table, out32);
 }
 
-void launch_dec_scan(hipStream_t stream, const uint32_t *blk_count, uint32_t n_blocks, unsigned long long *group_sum, uint32_t epoch,
-                     unsigned long long *blk_off, unsigned long long *total_copy, const uint32_t *verify_state, const uint32_t *verify_exit,
-                     uint32_t *verify_flag, uint32_t verify_first, const uint32_t *report_src, uint32_t *report_dst, bool verify_rows, uint32_t report_epoch) {
-    const uint32_t groups = (n_blocks + 1023) / 1024;
-    hipLaunchKernelGGL(k_scan_fused<uint32_t>, dim3(groups), dim3(1024), 0, stream, blk_count, n_blocks, blk_off, group_sum, epoch, 0ull, static_cast<uint32_t *>(nullptr),
-                       static_cast<const uint32_t *>(nullptr), 0u, total_copy, verify_state, verify_exit, verify_flag, verify_first,
-                       verify_rows ? 1u : static_cast<uint32_t>(BLOCK), verify_rows ? 0xffffffffu : 0xffu, report_src, report_dst, report_epoch);
+void launch_dec_scan(hipStream_t stream, const DecSpan &s, uint32_t epoch, const ScanVerify *verify, const ScanReport *report) {
+    const uint32_t groups = (s.n_blocks + 1023) / 1024;
+    const bool rows = verify && verify->rows;
+    hipLaunchKernelGGL(k_scan_fused<uint32_t>, dim3(groups), dim3(1024), 0, stream, static_cast<const uint32_t *>(s.blk_count), s.n_blocks, s.blk_off, s.group_sum, epoch, 0ull,
+                       static_cast<uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr), 0u,
+                       report ? reinterpret_cast<unsigned long long *>(s.flag + FLAG_TOTAL_LO) : nullptr, verify ? verify->state : nullptr,
+                       verify ? static_cast<const uint32_t *>(s.blk_exit) : nullptr, verify ? s.flag + FLAG_VERIFY_FAILED : nullptr, verify ? verify->first : 0xffffffffu,
+                       rows ? 1u : static_cast<uint32_t>(BLOCK), rows ? 0xffffffffu : 0xffu, report ? static_cast<const uint32_t *>(s.flag) : nullptr,
+                       report ? report->host : nullptr, report ? report->epoch : 0u);
 }
 
-void launch_dec_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint64_t n_subs, const DecodeTables &tb,
-                      const uint32_t *sub_state,
-                      const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, uint32_t *ticket, const SideLane *side, bool ticket_is_zero,
-                      const uint32_t *void_flags, KernelEvents ev, const uint64_t *chain, uint32_t n_chain, uint32_t chain_max_len, bool strips) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
+void launch_dec_write(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint64_t n_symbols, uint8_t *out, DecFlag ticket, const SideLane *side,
+                      bool ticket_is_zero, bool speculative, KernelEvents ev, const uint64_t *chain, uint32_t n_chain, uint32_t chain_max_len, bool strips) {
+    const uint32_t *words = s.words, *sub_state = s.sub_state, *void_flags = speculative ? s.flag : nullptr;
     if (chain) {  // every block, one launch, no side lane, no ticket; `tb` is not looked at
         // 8 wavefronts per workgroup share the tables (17 KiB) beside their 4 KiB stages: 3 workgroups = 24 wavefronts per CU
         constexpr int WAVES = 8;  // (12 x 2 per CU the same; 16 x 2 with 3.8 KiB stages, 32 wavefronts per CU, the same too: 0.441-0.445 ms; 4 x 4 or 16 x 1: 0.56)
         const size_t smem_wave = ((static_cast<size_t>(n_chain) * 8 + 15) & ~static_cast<size_t>(15)) + WAVES * WV_STAGE_ALLOC;
-        const uint32_t n_units = (n_blocks * 4 + WAVES - 1) / WAVES;
+        const uint32_t n_units = (s.n_blocks * 4 + WAVES - 1) / WAVES;
         if (strips) {  // (the caller's estimate from the header: many symbols per subsequence)
             const size_t smem_strips = ((static_cast<size_t>(n_chain) * 8 + 15) & ~static_cast<size_t>(15)) + WAVES * WS_ALLOC;
-            ET_LAUNCH_TIMED((k_dec_write_wave<WAVES, true>), dim3(decode_grid(k_dec_write_wave<WAVES, true>, smem_strips, n_units, true, 64 * WAVES)), dim3(64 * WAVES), smem_strips, stream, ev, words, n_bytes, n_blocks, reinterpret_cast<const uint2 *>(chain), n_chain, sub_state, blk_off, n_symbols, out, void_flags, n_subs, chain_max_len);
+            ET_LAUNCH_TIMED((k_dec_write_wave<WAVES, true>), dim3(decode_grid(k_dec_write_wave<WAVES, true>, smem_strips, n_units, true, 64 * WAVES)), dim3(64 * WAVES), smem_strips, stream, ev, words, s.n_bytes, s.n_blocks, reinterpret_cast<const uint2 *>(chain), n_chain, sub_state, s.blk_off, n_symbols, out, void_flags, s.n_subs, chain_max_len);
             return;
         }
-        ET_LAUNCH_TIMED(k_dec_write_wave<WAVES>, dim3(decode_grid(k_dec_write_wave<WAVES>, smem_wave, n_units, true, 64 * WAVES)), dim3(64 * WAVES), smem_wave, stream, ev, words, n_bytes, n_blocks, reinterpret_cast<const uint2 *>(chain), n_chain, sub_state, blk_off, n_symbols, out, void_flags, n_subs, chain_max_len);
+        ET_LAUNCH_TIMED(k_dec_write_wave<WAVES>, dim3(decode_grid(k_dec_write_wave<WAVES>, smem_wave, n_units, true, 64 * WAVES)), dim3(64 * WAVES), smem_wave, stream, ev, words, s.n_bytes, s.n_blocks, reinterpret_cast<const uint2 *>(chain), n_chain, sub_state, s.blk_off, n_symbols, out, void_flags, s.n_subs, chain_max_len);
         return;
     }
-    launch_dec_write_fallback(stream, words, n_bytes, n_subs, tb, sub_state, blk_off, n_symbols, out, ticket, side, ticket_is_zero, void_flags, ev);
+    launch_dec_write_fallback(stream, s, tb, n_symbols, out, ticket, side, ticket_is_zero, speculative, ev);
 }
 
 

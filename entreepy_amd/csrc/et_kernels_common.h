@@ -56,8 +56,7 @@ constexpr int RW_WORDS = 13;  // W[j] = stream word 8 * sub - 4 + j (host order)
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
 // k_dec_write_wave's fallback pair (et_kernels_fallback.hip): k_dec_write_reg for the interior blocks, k_dec_write for the first / last ones
-void launch_dec_write_fallback(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint64_t n_subs, const DecodeTables &tb, const uint32_t *sub_state,
-                               const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, uint32_t *ticket, const SideLane *side, bool ticket_is_zero,
-                               const uint32_t *void_flags, KernelEvents ev);
+void launch_dec_write_fallback(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint64_t n_symbols, uint8_t *out, DecFlag ticket_word,
+                               const SideLane *side, bool ticket_is_zero, bool speculative, KernelEvents ev);
 
 }  // namespace et

@@ -1534,9 +1534,11 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_build_dec_tables(const TableP
     }
 }
 
-void launch_build_dec_tables(hipStream_t stream, const TablePlan *d_plan, uint32_t *lut, uint32_t *longc, uint16_t *sub, uint8_t *sym_len,
-                             uint32_t *steps, uint32_t *wsteps, uint32_t *zero16) {
-    hipLaunchKernelGGL(k_build_dec_tables, dim3(1), dim3(BUILD_THREADS), 0, stream, d_plan, lut, longc, sub, sym_len, steps, wsteps, zero16);
+void launch_build_dec_tables(hipStream_t stream, uint8_t *d_block, size_t wsteps_at, size_t plan_at, uint32_t *zero16) {
+    using L = DecTableLayout;
+    hipLaunchKernelGGL(k_build_dec_tables, dim3(1), dim3(BUILD_THREADS), 0, stream, table_at<const TablePlan>(d_block, plan_at), table_at<uint32_t>(d_block, L::LUT),
+                       table_at<uint32_t>(d_block, L::LONG), table_at<uint16_t>(d_block, L::SUB), d_block + L::SYM_LEN, table_at<uint32_t>(d_block, L::STEPS),
+                       table_at<uint32_t>(d_block, wsteps_at), zero16);
 }
 
 // `special` = the stream the three-workgroup launch goes to: the side lane's (made to wait
@@ -1559,48 +1561,46 @@ static void join_special(const SideLane *side, hipStream_t stream) {
     (void)hipStreamWaitEvent(stream, side->join, 0);
 }
 
-void launch_dec_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs,
-                     const DecodeTables &tb, uint32_t iter, uint32_t max_trips,
-                     uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count, uint32_t *changed, uint32_t *ticket, uint32_t flags,
-                     uint32_t *worklist, uint32_t *n_work, const SideLane *side, bool ticket_is_zero, KernelEvents ev) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
-    const uint32_t n_chunks = (n_blocks + SYNC_CHUNK - 1) / SYNC_CHUNK;
+void launch_dec_sync(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint32_t iter, uint32_t max_trips, uint32_t flags, bool listed,
+                     const SideLane *side, bool ticket_is_zero, KernelEvents ev) {
+    uint32_t *changed = s.flag + FLAG_CHANGED, *ticket = s.flag + FLAG_SYNC_TICKET, *worklist = listed ? s.worklist : nullptr, *n_work = listed ? s.flag + FLAG_WORK_COUNT : nullptr;
+    const uint32_t n_chunks = (s.n_blocks + SYNC_CHUNK - 1) / SYNC_CHUNK;
     const size_t smem = decode_smem_bytes(tb, false);
-    if (use_reg_kernels(n_blocks)) {
+    if (use_reg_kernels(s.n_blocks)) {
         const size_t smem_reg = (step_table_words(tb) + BLOCK + 8) * sizeof(uint32_t);
         constexpr uint32_t chunk = 4;  // blocks per ticket; measured 1 / 4 / 8 / 16
-        if (iter == 0 && n_blocks >= 16) {
+        if (iter == 0 && s.n_blocks >= 16) {
             if (!ticket_is_zero) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
             constexpr uint32_t chunk2 = 4;  // superblocks per ticket; measured 1 / 2 / 4 / 8 / 16: 0.54 / 0.37 / 0.35 / 0.37 / 0.44 ms
             fork_mark(side, stream);
-            ET_LAUNCH_TIMED(k_dec_sync_reg2, dim3(decode_grid(k_dec_sync_reg2, smem_reg, (n_blocks / 2 + chunk2 - 1) / chunk2, true)), dim3(BLOCK), smem_reg, stream, ev, words, n_bytes, n_blocks, step_table_args(tb), sub_state, blk_exit, blk_count, changed, ticket, max_trips, chunk2);
+            ET_LAUNCH_TIMED(k_dec_sync_reg2, dim3(decode_grid(k_dec_sync_reg2, smem_reg, (s.n_blocks / 2 + chunk2 - 1) / chunk2, true)), dim3(BLOCK), smem_reg, stream, ev, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, chunk2);
             const hipStream_t special = fork_special(side, stream);
-            hipLaunchKernelGGL(k_dec_sync<true>, dim3(8), dim3(BLOCK), smem, special, words, n_bytes, first_bit, n_subs, n_blocks, tb, sub_state, blk_exit, blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY | DEC_SPECIAL_SUPER);
+            hipLaunchKernelGGL(k_dec_sync<true>, dim3(8), dim3(BLOCK), smem, special, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY | DEC_SPECIAL_SUPER);
             join_special(side, stream);
         } else if (iter == 0) {
             if (!ticket_is_zero) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
             fork_mark(side, stream);
-            ET_LAUNCH_TIMED((k_dec_sync_reg<true, true>), dim3(decode_grid(k_dec_sync_reg<true, true>, smem_reg, (n_blocks + chunk - 1) / chunk, true)), dim3(BLOCK), smem_reg, stream, ev, words, n_bytes, n_blocks, step_table_args(tb), sub_state, blk_exit, blk_count, changed, ticket, max_trips, chunk, static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr));
+            ET_LAUNCH_TIMED((k_dec_sync_reg<true, true>), dim3(decode_grid(k_dec_sync_reg<true, true>, smem_reg, (s.n_blocks + chunk - 1) / chunk, true)), dim3(BLOCK), smem_reg, stream, ev, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, chunk, static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr));
             const hipStream_t special = fork_special(side, stream);
-            hipLaunchKernelGGL(k_dec_sync<true>, dim3(3), dim3(BLOCK), smem, special, words, n_bytes, first_bit, n_subs, n_blocks, tb, sub_state, blk_exit, blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY);
+            hipLaunchKernelGGL(k_dec_sync<true>, dim3(3), dim3(BLOCK), smem, special, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY);
             join_special(side, stream);
         } else {
             if (worklist) {  // n_work zeroed by the caller
-                hipLaunchKernelGGL(k_dec_check, dim3((n_blocks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, sub_state, blk_exit, n_blocks, worklist, n_work);
-                hipLaunchKernelGGL((k_dec_sync_reg<false, false>), dim3(n_blocks < 512 ? n_blocks : 512), dim3(BLOCK), smem_reg, stream, words, n_bytes, n_blocks, step_table_args(tb), sub_state, blk_exit, blk_count, changed, ticket, max_trips, 1u, static_cast<const uint32_t *>(worklist), static_cast<const uint32_t *>(n_work));
+                hipLaunchKernelGGL(k_dec_check, dim3((s.n_blocks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, s.sub_state, s.blk_exit, s.n_blocks, worklist, n_work);
+                hipLaunchKernelGGL((k_dec_sync_reg<false, false>), dim3(s.n_blocks < 512 ? s.n_blocks : 512), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, 1u, static_cast<const uint32_t *>(worklist), static_cast<const uint32_t *>(n_work));
             } else {
-                hipLaunchKernelGGL((k_dec_sync_reg<false, false>), dim3(n_blocks), dim3(BLOCK), smem_reg, stream, words, n_bytes, n_blocks, step_table_args(tb), sub_state, blk_exit, blk_count, changed, ticket, max_trips, 1u, static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr));
+                hipLaunchKernelGGL((k_dec_sync_reg<false, false>), dim3(s.n_blocks), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, 1u, static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr));
             }
             // (not on the side lane: the fork/join events cost more than these ~5 us)
-            hipLaunchKernelGGL(k_dec_sync<false>, dim3(3), dim3(BLOCK), smem, stream, words, n_bytes, first_bit, n_subs, n_blocks, tb, sub_state, blk_exit, blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY);
+            hipLaunchKernelGGL(k_dec_sync<false>, dim3(3), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY);
         }
         return;
     }
     if (SYNC_TICKET) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
     if (iter == 0)
-        ET_LAUNCH_TIMED(k_dec_sync<true>, dim3(decode_grid(k_dec_sync<true>, smem, n_chunks, SYNC_TICKET)), dim3(BLOCK), smem, stream, ev, words, n_bytes, first_bit, n_subs, n_blocks, tb, sub_state, blk_exit, blk_count, changed, ticket, max_trips, flags);
+        ET_LAUNCH_TIMED(k_dec_sync<true>, dim3(decode_grid(k_dec_sync<true>, smem, n_chunks, SYNC_TICKET)), dim3(BLOCK), smem, stream, ev, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags);
     else
-        hipLaunchKernelGGL(k_dec_sync<false>, dim3(decode_grid(k_dec_sync<false>, smem, n_chunks, SYNC_TICKET)), dim3(BLOCK), smem, stream, words, n_bytes, first_bit, n_subs, n_blocks, tb, sub_state, blk_exit, blk_count, changed, ticket, max_trips, flags);
+        hipLaunchKernelGGL(k_dec_sync<false>, dim3(decode_grid(k_dec_sync<false>, smem, n_chunks, SYNC_TICKET)), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags);
 }
 
 // Exhaustive synchronisation (see k_dec_maps).  Workspaces: lane_maps n_subs * stride,
@@ -1608,50 +1608,47 @@ void launch_dec_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes
 // one per 256 blocks (launch_dec_maps), and, once the input start is known, the way back down
 // and the counting walk (launch_dec_resolve).  A single GPU runs them back to back; ranges of
 // a stream split over GPUs exchange their composed maps in between.
-void launch_dec_maps(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, bool have_start, uint64_t n_subs,
-                     const DecodeTables &tb, uint32_t n_starts, uint32_t map_stride, uint8_t *lane_maps, uint8_t *blk_maps, uint8_t *grp_maps) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
-    const uint32_t n_groups = (n_blocks + 255) / 256;
+void launch_dec_maps(hipStream_t stream, const DecSpan &s, bool have_start, const DecodeTables &tb, uint32_t n_starts, uint32_t map_stride,
+                     uint8_t *lane_maps, uint8_t *blk_maps, uint8_t *grp_maps) {
+    const uint32_t n_groups = (s.n_blocks + 255) / 256;
     const size_t smem = decode_smem_bytes(tb, true);
-    const bool reg = use_reg_kernels(n_blocks) && tb.steps != nullptr;
+    const bool reg = use_reg_kernels(s.n_blocks) && tb.steps != nullptr;
     const size_t smem_reg = (step_table_words(tb) + BLOCK * 32 / 4 + BLOCK + 8) * sizeof(uint32_t);
-    if (reg) hipLaunchKernelGGL(k_dec_maps_reg, dim3(n_blocks), dim3(BLOCK), smem_reg, stream, words, n_bytes, n_blocks, step_table_args(tb), n_starts, map_stride, lane_maps, blk_maps);
-    hipLaunchKernelGGL(k_dec_maps, dim3(reg ? 3 : n_blocks), dim3(BLOCK), smem, stream, words, n_bytes, first_bit, n_subs, tb, n_starts, map_stride, lane_maps, blk_maps, reg ? 1u : 0u, have_start ? 1u : 0u);
-    hipLaunchKernelGGL(k_dec_compose, dim3(n_groups), dim3(BLOCK), 0, stream, blk_maps, n_blocks, grp_maps);
+    if (reg) hipLaunchKernelGGL(k_dec_maps_reg, dim3(s.n_blocks), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), n_starts, map_stride, lane_maps, blk_maps);
+    hipLaunchKernelGGL(k_dec_maps, dim3(reg ? 3 : s.n_blocks), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, tb, n_starts, map_stride, lane_maps, blk_maps, reg ? 1u : 0u, have_start ? 1u : 0u);
+    hipLaunchKernelGGL(k_dec_compose, dim3(n_groups), dim3(BLOCK), 0, stream, blk_maps, s.n_blocks, grp_maps);
 }
 
-void launch_dec_resolve(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, bool const_first, uint64_t n_subs,
-                        const DecodeTables &tb, uint32_t map_stride, const uint8_t *lane_maps, const uint8_t *blk_maps, const uint8_t *grp_maps,
-                        uint8_t *blk_in, uint8_t *grp_in, uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
-    const uint32_t n_groups = (n_blocks + 255) / 256;
+void launch_dec_resolve(hipStream_t stream, const DecSpan &s, bool const_first, const DecodeTables &tb, uint32_t map_stride, const uint8_t *lane_maps,
+                        const uint8_t *blk_maps, const uint8_t *grp_maps, uint8_t *blk_in, uint8_t *grp_in) {
+    const uint32_t n_groups = (s.n_blocks + 255) / 256;
     const size_t smem = decode_smem_bytes(tb, true);
-    const bool reg = use_reg_kernels(n_blocks) && tb.steps != nullptr;
+    const bool reg = use_reg_kernels(s.n_blocks) && tb.steps != nullptr;
     const size_t smem_reg = (step_table_words(tb) + BLOCK * 32 / 4 + BLOCK + 8) * sizeof(uint32_t);
     // one workgroup walks all group maps (256 per LDS refill), then every group resolves its blocks
-    hipLaunchKernelGGL(k_dec_chain, dim3(1), dim3(BLOCK), 0, stream, grp_maps, n_groups, static_cast<const uint8_t *>(nullptr), first_bit, grp_in);
-    hipLaunchKernelGGL(k_dec_chain, dim3(n_groups), dim3(BLOCK), 0, stream, blk_maps, n_blocks, grp_in, 0u, blk_in);
-    if (reg) hipLaunchKernelGGL(k_dec_resolve_reg, dim3(n_blocks), dim3(BLOCK), smem_reg, stream, words, n_bytes, n_blocks, step_table_args(tb), map_stride, lane_maps, blk_in, sub_state, blk_exit, blk_count);
-    hipLaunchKernelGGL(k_dec_resolve, dim3(reg ? 3 : n_blocks), dim3(BLOCK), smem, stream, words, n_bytes, first_bit, n_subs, tb, map_stride, lane_maps, blk_in, sub_state, blk_exit, blk_count, reg ? 1u : 0u, const_first ? 1u : 0u);
+    hipLaunchKernelGGL(k_dec_chain, dim3(1), dim3(BLOCK), 0, stream, grp_maps, n_groups, static_cast<const uint8_t *>(nullptr), s.first_bit, grp_in);
+    hipLaunchKernelGGL(k_dec_chain, dim3(n_groups), dim3(BLOCK), 0, stream, blk_maps, s.n_blocks, grp_in, 0u, blk_in);
+    if (reg) hipLaunchKernelGGL(k_dec_resolve_reg, dim3(s.n_blocks), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), map_stride, lane_maps, blk_in, s.sub_state, s.blk_exit, s.blk_count);
+    hipLaunchKernelGGL(k_dec_resolve, dim3(reg ? 3 : s.n_blocks), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, tb, map_stride, lane_maps, blk_in, s.sub_state, s.blk_exit, s.blk_count, reg ? 1u : 0u, const_first ? 1u : 0u);
 }
 
-void launch_dec_write_fallback(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint64_t n_subs, const DecodeTables &tb, const uint32_t *sub_state,
-                               const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, uint32_t *ticket, const SideLane *side, bool ticket_is_zero,
-                               const uint32_t *void_flags, KernelEvents ev) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
+void launch_dec_write_fallback(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint64_t n_symbols, uint8_t *out, DecFlag ticket_word,
+                               const SideLane *side, bool ticket_is_zero, bool speculative, KernelEvents ev) {
+    const uint32_t *words = s.words, *sub_state = s.sub_state, *void_flags = speculative ? s.flag : nullptr;
+    uint32_t *ticket = s.flag + ticket_word;
     if (!ticket_is_zero) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
-    const uint32_t n_chunks = (n_blocks + WRITE_CHUNK - 1) / WRITE_CHUNK;
+    const uint32_t n_chunks = (s.n_blocks + WRITE_CHUNK - 1) / WRITE_CHUNK;
     const size_t smem = decode_smem_bytes(tb, true, false);
-    if (use_reg_kernels(n_blocks)) {
+    if (use_reg_kernels(s.n_blocks)) {
         const size_t smem_reg = (step_table_words(tb) + 64 + 8) * sizeof(uint32_t) + DEC_STAGE_BYTES + 16;
         fork_mark(side, stream);
-        ET_LAUNCH_TIMED(k_dec_write_reg, dim3(decode_grid(k_dec_write_reg, smem_reg, n_chunks, true)), dim3(BLOCK), smem_reg, stream, ev, words, n_bytes, n_blocks, step_table_args(tb), tb.sym_len, sub_state, blk_off, n_symbols, out, ticket, void_flags);
+        ET_LAUNCH_TIMED(k_dec_write_reg, dim3(decode_grid(k_dec_write_reg, smem_reg, n_chunks, true)), dim3(BLOCK), smem_reg, stream, ev, words, s.n_bytes, s.n_blocks, step_table_args(tb), tb.sym_len, sub_state, s.blk_off, n_symbols, out, ticket, void_flags);
         const hipStream_t special = fork_special(side, stream);
-        hipLaunchKernelGGL(k_dec_write, dim3(3), dim3(BLOCK), smem, special, words, n_bytes, n_subs, n_blocks, tb, sub_state, blk_off, n_symbols, out, ticket, 1u, void_flags);
+        hipLaunchKernelGGL(k_dec_write, dim3(3), dim3(BLOCK), smem, special, words, s.n_bytes, s.n_subs, s.n_blocks, tb, sub_state, s.blk_off, n_symbols, out, ticket, 1u, void_flags);
         join_special(side, stream);
         return;
     }
-    ET_LAUNCH_TIMED(k_dec_write, dim3(decode_grid(k_dec_write, smem, n_chunks, WRITE_TICKET)), dim3(BLOCK), smem, stream, ev, words, n_bytes, n_subs, n_blocks, tb, sub_state, blk_off, n_symbols, out, ticket, 0u, void_flags);
+    ET_LAUNCH_TIMED(k_dec_write, dim3(decode_grid(k_dec_write, smem, n_chunks, WRITE_TICKET)), dim3(BLOCK), smem, stream, ev, words, s.n_bytes, s.n_subs, s.n_blocks, tb, sub_state, s.blk_off, n_symbols, out, ticket, 0u, void_flags);
 }
 
 

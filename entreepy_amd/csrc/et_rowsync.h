@@ -50,30 +50,26 @@ namespace et {
 // Bytes of scratch launch_row_sync needs for a stream of n_blocks 8 KiB blocks (zeroed by the launch itself).
 size_t row_sync_scratch_bytes(uint32_t n_blocks);
 
-// words / n_bytes / first_bit / n_subs as for the other synchronisation kernels (et_kernels.h: the stream from its 4-byte
-// aligned base, its first codeword at bit first_bit < 32).  Outputs as k_dec_resolve's: sub_state[s] = start bit | exit << 8 |
-// codewords that begin in s << 16; blk_count[b]; blk_exit[b].
-// fault: a device word (zeroed by the caller) that the kernel raises if a chunk never saw what the chunks before it publish (bit 0).
+// Over s as the other synchronisation kernels take it (et_kernels.h DecSpan: the stream from its 4-byte aligned base, its first
+// codeword at bit first_bit < 32).  Outputs as k_dec_resolve's: sub_state[s] = start bit | exit << 8 | codewords that begin in
+// s << 16; blk_count[b]; blk_exit[b].  FLAG_ROW_BLIND (zeroed by the caller): raised if a chunk never saw what the chunks before
+// it publish (bit 0).
 // flags: 0, or ROW_* above; d_map (optional): receives the device address (inside scratch) of the 8-byte map a ROW_MAP_ONLY launch leaves.
-void launch_row_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, RowCode rc, void *scratch, uint32_t *fault,
-                     uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count, uint32_t flags = 0, const unsigned long long **d_map = nullptr);
+void launch_row_sync(hipStream_t stream, const DecSpan &s, RowCode rc, void *scratch, uint32_t flags = 0, const unsigned long long **d_map = nullptr);
 
 // The write pass for such a stream, by rows (k_row_write): sub_state as launch_row_sync leaves it, blk_off from the scan of
 // blk_count; at most n_symbols symbols to out (16-byte aligned).  ev: events the dispatch carries (may be null).
-void launch_row_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, RowCode rc, const et_codebook *cb,
-                      const uint32_t *sub_state, const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, KernelEvents ev = {});
+void launch_row_write(hipStream_t stream, const DecSpan &s, RowCode rc, const et_codebook *cb, uint64_t n_symbols, uint8_t *out, KernelEvents ev = {});
 
 // decode.zig:143-203 on a FIXED-length code -- 2^L codewords of L bits each (L <= 32): four symbols of about equal weight (a DNA
 // sequence), 16 (a hex dump), 64 (base64 of random bytes).  Nothing to walk: the k-th codeword begins at bit first_bit + k L, so a
 // subsequence's start, exit and count are three divisions (k_fixed_sync; outputs as launch_row_sync's).  A codeword cut by the
 // stream's end is nobody's, as everywhere.
-void launch_fixed_sync(hipStream_t stream, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, uint32_t code_bits, uint32_t *sub_state, uint32_t *blk_exit,
-                       uint32_t *blk_count);
+void launch_fixed_sync(hipStream_t stream, const DecSpan &s, uint32_t code_bits);
 
 // The write pass for such a stream (k_fixed_write): symbol i is the code_bits bits at first_bit + i code_bits; n_out of them to out
 // (16-byte aligned) -- n_out <= the whole codewords the stream holds (callers clamp).  code_bits <= 8.
-void launch_fixed_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, const et_codebook *cb, uint64_t n_out, uint8_t *out,
-                        KernelEvents ev = {});
+void launch_fixed_write(hipStream_t stream, const DecSpan &s, const et_codebook *cb, uint64_t n_out, uint8_t *out, KernelEvents ev = {});
 
 }  // namespace et
 #endif

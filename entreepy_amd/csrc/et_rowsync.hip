@@ -536,12 +536,11 @@ __global__ __launch_bounds__(256) void k_fixed_sync(uint64_t n_bits, uint32_t fi
     }
 }
 
-void launch_fixed_sync(hipStream_t stream, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, uint32_t code_bits, uint32_t *sub_state, uint32_t *blk_exit,
-                       uint32_t *blk_count) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + 255) / 256);
+void launch_fixed_sync(hipStream_t stream, const DecSpan &s, uint32_t code_bits) {
+    const uint32_t n_blocks = s.n_blocks;
     if (!n_blocks) return;
     const uint32_t grid = n_blocks < 16384u ? n_blocks : 16384u;
-    hipLaunchKernelGGL(k_fixed_sync, dim3(grid), dim3(256), 0, stream, n_bytes * 8, first_bit, n_subs, n_blocks, code_bits, sub_state, blk_exit, blk_count);
+    hipLaunchKernelGGL(k_fixed_sync, dim3(grid), dim3(256), 0, stream, s.n_bytes * 8, s.first_bit, s.n_subs, n_blocks, code_bits, s.sub_state, s.blk_exit, s.blk_count);
 }
 
 size_t row_sync_scratch_bytes(uint32_t n_blocks) {
@@ -549,9 +548,8 @@ size_t row_sync_scratch_bytes(uint32_t n_blocks) {
     return n_chunks * sizeof(unsigned long long) + 64;  // the chunks' words, then: ticket (4 bytes), pad, the range's map (8 bytes at + 8)
 }
 
-void launch_row_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, RowCode rc, void *scratch, uint32_t *fault,
-                     uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_count, uint32_t flags, const unsigned long long **d_map) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + RS_THREADS - 1) / RS_THREADS);
+void launch_row_sync(hipStream_t stream, const DecSpan &s, RowCode rc, void *scratch, uint32_t flags, const unsigned long long **d_map) {
+    const uint32_t n_blocks = s.n_blocks;
     const uint32_t n_chunks = (n_blocks + RS_CH - 1) / RS_CH;
     if (!n_chunks) return;
     (void)hipMemsetAsync(scratch, 0, row_sync_scratch_bytes(n_blocks), stream);  // "nothing published", ticket 0
@@ -561,14 +559,13 @@ void launch_row_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes
     if (d_map) *d_map = map_out;
     uint32_t grid = static_cast<uint32_t>(device_cus()) * 8u;  // (workgroups that find no room wait their turn and take later tickets: nobody waits for them)
     if (grid > n_chunks) grid = n_chunks;
-    hipLaunchKernelGGL(k_row_sync, dim3(grid), dim3(RS_THREADS), 0, stream, words, n_bytes, first_bit, n_subs, n_blocks, n_chunks, rc.t, pub, ticket, fault, sub_state, blk_exit,
-                       blk_count, flags, map_out);
+    hipLaunchKernelGGL(k_row_sync, dim3(grid), dim3(RS_THREADS), 0, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, n_blocks, n_chunks, rc.t, pub, ticket,
+                       s.flag + FLAG_ROW_BLIND, s.sub_state, s.blk_exit, s.blk_count, flags, map_out);
 }
 
-void launch_row_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, RowCode rc, const et_codebook *cb,
-                      const uint32_t *sub_state, const unsigned long long *blk_off, uint64_t n_symbols, uint8_t *out, KernelEvents ev) {
+void launch_row_write(hipStream_t stream, const DecSpan &s, RowCode rc, const et_codebook *cb, uint64_t n_symbols, uint8_t *out, KernelEvents ev) {
     constexpr int WAVES = 8;
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + RS_THREADS - 1) / RS_THREADS);
+    const uint32_t n_blocks = s.n_blocks;
     if (!n_blocks) return;
     RowLut lut = {};
     for (int s = 0; s < 256; ++s) {  // every 8-bit pattern begins with exactly one codeword (the code is complete)
@@ -582,7 +579,8 @@ void launch_row_write(hipStream_t stream, const uint32_t *words, uint64_t n_byte
     const uint32_t n_wg = (n_blocks * 4 + WAVES - 1) / WAVES;
     uint32_t grid = static_cast<uint32_t>(cus) * static_cast<uint32_t>(per_cu);
     if (grid > n_wg) grid = n_wg;
-    ET_LAUNCH_TIMED(k_row_write<WAVES>, dim3(grid), dim3(64 * WAVES), 0, stream, ev, words, n_bytes, n_blocks, n_subs, first_bit, rc.t, lut, sub_state, blk_off, n_symbols, out);
+    ET_LAUNCH_TIMED(k_row_write<WAVES>, dim3(grid), dim3(64 * WAVES), 0, stream, ev, s.words, s.n_bytes, n_blocks, s.n_subs, s.first_bit, rc.t, lut, static_cast<const uint32_t *>(s.sub_state),
+                    static_cast<const unsigned long long *>(s.blk_off), n_symbols, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -649,8 +647,7 @@ __global__ __launch_bounds__(256) void k_fixed_write(const uint32_t *__restrict_
     }
 }
 
-void launch_fixed_write(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, const et_codebook *cb, uint64_t n_out, uint8_t *out,
-                        KernelEvents ev) {
+void launch_fixed_write(hipStream_t stream, const DecSpan &s, const et_codebook *cb, uint64_t n_out, uint8_t *out, KernelEvents ev) {
     if (!n_out) return;
     const uint32_t L = cb->max_length;
     RowLut lut = {};
@@ -661,7 +658,7 @@ void launch_fixed_write(hipStream_t stream, const uint32_t *words, uint64_t n_by
     const uint32_t grid = static_cast<uint32_t>(n_wg < cus * 32 ? n_wg : cus * 32);
 #define ET_FIXED_CASE(l_)                                                                                                          \
     case l_:                                                                                                                       \
-        ET_LAUNCH_TIMED(k_fixed_write<l_>, dim3(grid), dim3(256), 0, stream, ev, words, n_bytes, first_bit, n_out, lut, out);      \
+        ET_LAUNCH_TIMED(k_fixed_write<l_>, dim3(grid), dim3(256), 0, stream, ev, s.words, s.n_bytes, s.first_bit, n_out, lut, out); \
         break;
     switch (L) {
         ET_FIXED_CASE(1)

@@ -3,6 +3,7 @@
 // runs the builders under AddressSanitizer/UBSan against a brute-force decoder).
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "entreepy_hip.h"
@@ -68,6 +69,56 @@ struct TablePlan {
     uint32_t pad_;
 };
 void plan_tables(const et_codebook *cb, uint32_t lut_bits_max, uint32_t max_syms, uint32_t step_bits_max, uint32_t wstep_bits_max, TablePlan *plan);
+
+// The decode tables as the kernels take them: pointers into the device's table block (DecTableLayout below).
+struct DecodeTables {
+    const uint32_t *lut;     // [1 << lut_bits] first-level entries (LUT_* above)
+    const uint32_t *longc;   // [n_long * 2]: {left-aligned code, (len << 8) | sym} of every code longer than lut_bits
+    const uint16_t *sub;     // [n_sub << sub_bits] second-level tables
+    const uint8_t *sym_len;  // [256] code length per symbol (single-symbol steps)
+    uint32_t lut_bits;
+    uint32_t n_long;
+    uint32_t sub_bits;
+    uint32_t n_sub;
+    const uint32_t *steps;   // [1 << step_bits] packed walk increments for k_dec_sync_reg (STEP_* above), or null;
+                             // followed by n_step_sub second-level tables of 1 << step_sub_bits entries
+    uint32_t step_bits;
+    uint32_t step_sub_bits;
+    uint32_t n_step_sub;
+    const DecodeTables *dev_copy;  // this struct in device memory (slow path of the step walks), or null
+};
+
+// Bytes a step table of this shape takes in the block: index and second level, rounded up to 16.
+inline size_t step_table_bytes(uint32_t bits, uint32_t sub_bits, uint32_t n_sub) {
+    return (((static_cast<size_t>(1) << bits) + (static_cast<size_t>(n_sub) << sub_bits) + 3) & ~static_cast<size_t>(3)) * sizeof(uint32_t);
+}
+
+// The block all decode tables of a code lie in -- one in device memory, two in pinned host memory filled in turn -- described
+// once: offsets and capacities in bytes.  ONE set of older-format tables (index DEC_LUT_BITS_WRITE, DEC_WRITE_SYMS symbols per
+// entry), the code lengths right behind its second level, then the step table (k_dec_sync_reg: index DEC_STEP_BITS_DEFAULT).
+// From there on the block is packed, so that one upload covers what is in use and no more: the write-step table
+// (k_dec_write_reg) step_table_bytes behind STEPS, the two DecodeTables structs (the sweeps' and the write's: dev_copy) behind
+// its step_table_bytes, and the TablePlan of device-built tables behind them.
+struct DecTableLayout {
+    static constexpr size_t LUT = 0, LUT_BYTES = sizeof(uint32_t) << DEC_LUT_BITS_MAX;
+    static constexpr size_t LONG = LUT + LUT_BYTES, LONG_BYTES = 256 * 2 * sizeof(uint32_t);  // every symbol a long code
+    static constexpr size_t SUB = LONG + LONG_BYTES, SUB_BYTES = (static_cast<size_t>(DEC_SUB_TABLES_MAX) << DEC_SUB_BITS_MAX) * sizeof(uint16_t) + 64;
+    static constexpr size_t SYM_LEN = SUB + SUB_BYTES, SYM_LEN_BYTES = 256;
+    static constexpr size_t STEPS = SYM_LEN + SYM_LEN_BYTES;
+    static constexpr size_t STEPS_BYTES = (sizeof(uint32_t) << DEC_STEP_BITS_MAX) + (DEC_STEP_SUB_WORDS + 4) * sizeof(uint32_t);
+    static constexpr size_t WSTEPS_BYTES = (sizeof(uint32_t) << DEC_LUT_BITS_MAX) + (DEC_STEP_SUB_WORDS + 4) * sizeof(uint32_t);
+    static constexpr size_t TAIL_BYTES = 2 * sizeof(DecodeTables) + sizeof(TablePlan);
+    static constexpr size_t BYTES = STEPS + STEPS_BYTES + WSTEPS_BYTES + TAIL_BYTES + 64;  // + slack for 16-byte rounded copies
+};
+// The kernels stage these tables with wide loads.
+static_assert(DecTableLayout::LUT % 64 == 0 && DecTableLayout::LONG % 64 == 0 && DecTableLayout::SUB % 64 == 0 && DecTableLayout::SYM_LEN % 64 == 0 &&
+                  DecTableLayout::STEPS % 64 == 0,
+              "every decode table begins at a multiple of 64 bytes");
+static_assert(DEC_LUT_BITS_WRITE <= DEC_LUT_BITS_MAX && DEC_STEP_BITS_DEFAULT <= DEC_STEP_BITS_MAX, "the index widths in use fit their tables");
+
+// The table (or struct) at `offset` of a block, in host or in device memory.
+template <typename T>
+T *table_at(uint8_t *block, size_t offset) { return reinterpret_cast<T *>(block + offset); }
 
 // Older-format tables: lut[1 << k], longc[2 * n_long], sub[n_sub << sub_bits]; k =
 // min(longest code, lut_bits_max).

@@ -502,10 +502,10 @@ void launch_tw_build(hipStream_t stream, const TwUpload *d_up, uint32_t up_bytes
                        zero_words ? n_zero : 0u);
 }
 
-void launch_tw_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes, uint32_t first_bit, uint64_t n_subs, const uint16_t *table,
-                    uint32_t n_int, uint32_t *sub_state, uint32_t *blk_exit, uint32_t *blk_start, uint32_t *blk_count, uint32_t *changed,
-                    uint32_t max_trips, const uint32_t *worklist, const uint32_t *n_work, KernelEvents ev, uint32_t *blk_pub, uint32_t mode, uint32_t *exit_bits) {
-    const uint32_t n_blocks = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
+void launch_tw_sync(hipStream_t stream, const DecSpan &s, const uint16_t *table, uint32_t n_int, uint32_t *blk_start, uint32_t max_trips, bool listed,
+                    KernelEvents ev, uint32_t *blk_pub, uint32_t mode, uint32_t *exit_bits) {
+    const uint32_t n_blocks = s.n_blocks;
+    const uint32_t *worklist = listed ? s.worklist : nullptr, *n_work = listed ? s.flag + FLAG_WORK_COUNT : nullptr;
     const uint32_t entries = tw_table_entries(n_int);
     const size_t smem = static_cast<size_t>(entries) * 2;
     // workgroups of 8 wavefronts, as many per CU as the table leaves room for in the LDS, at most 3 (<= 80 VGPRs: 6
@@ -523,12 +523,13 @@ void launch_tw_sync(hipStream_t stream, const uint32_t *words, uint64_t n_bytes,
     uint32_t grid = static_cast<uint32_t>(device_cus()) * per_cu;
     if (grid > (n_blocks + waves - 1) / waves) grid = (n_blocks + waves - 1) / waves;
     if (worklist && grid > 64) grid = 64;  // a repair sweep: a handful of blocks (workgroups beyond the list leave at once)
-    ET_LAUNCH_TIMED(k_tw_sync, dim3(grid), dim3(threads), smem, stream, ev, words, n_bytes, first_bit, n_subs, n_blocks, table, entries, n_int, sub_state, blk_exit, blk_start,
-                    blk_count, changed, max_trips, worklist, n_work, blk_pub, mode, exit_bits);
+    ET_LAUNCH_TIMED(k_tw_sync, dim3(grid), dim3(threads), smem, stream, ev, s.words, s.n_bytes, s.first_bit, s.n_subs, n_blocks, table, entries, n_int, s.sub_state, s.blk_exit,
+                    blk_start, s.blk_count, s.flag + FLAG_CHANGED, max_trips, worklist, n_work, blk_pub, mode, exit_bits);
 }
 
-void launch_tw_check(hipStream_t stream, const uint32_t *blk_start, const uint32_t *blk_exit, uint32_t n_blocks, uint32_t *worklist, uint32_t *n_work, bool first_known) {
-    hipLaunchKernelGGL(k_tw_check, dim3((n_blocks + 255) / 256), dim3(256), 0, stream, blk_start, blk_exit, n_blocks, worklist, n_work, first_known ? 1u : 0u);
+void launch_tw_check(hipStream_t stream, const DecSpan &s, const uint32_t *blk_start, bool first_known) {
+    hipLaunchKernelGGL(k_tw_check, dim3((s.n_blocks + 255) / 256), dim3(256), 0, stream, blk_start, static_cast<const uint32_t *>(s.blk_exit), s.n_blocks, s.worklist,
+                       s.flag + FLAG_WORK_COUNT, first_known ? 1u : 0u);
 }
 
 }  // namespace et

@@ -8,7 +8,8 @@ d_out + cap.
   A. decode extent, one family per write kernel, at ragged lengths and at declared lengths shorter than the body;
   B. ET_ERR_CAP of every single-stream call (nothing written, *out_len == 0, the context sound afterwards), exact capacities,
      truncated bodies (the write that is not speculative), the range write, the shard encode's words;
-  C. the write kernels behind ET_NO_STRIPS / ET_NO_ROW_WRITE / ET_NO_FIXED_WRITE / ET_NO_ROW_SYNC, one child process each.
+  C. the write kernels behind ET_NO_STRIPS / ET_NO_ROW_WRITE / ET_NO_FIXED_WRITE / ET_NO_ROW_SYNC, and the window tables'
+     families behind ET_DEC_TABLES_HOST, one child process each.
 
 Every family decodes with ONE code table -- the reference builder's for the family's byte distribution, or a hand-made one --
 and a body the oracle packs from the first n bytes of the family's text, so that every length, n = 1 included, reaches the
@@ -570,12 +571,14 @@ def test_host_memory_calls_capacity():
 
 # --- C. the same kernels behind their switches --------------------------------------------------------------------------------
 
-# switch -> (families it affects, the flags their decodes then report)
+# switch -> (families it affects, the flags their decodes then report; None: what they report without it)
 SWITCHES = {
     "ET_NO_STRIPS": (("strips",), dict(tree_walk_sync=True, chained_write=True, strips_write=False)),
     "ET_NO_ROW_WRITE": (("rows",), dict(row_sync=True, exhaustive_sync=True, chained_write=True)),
     "ET_NO_FIXED_WRITE": (("fixed2", "fixed4", "fixed16", "fixed64", "fixed256"), dict(fixed_sync=True, exhaustive_sync=True)),
     "ET_NO_ROW_SYNC": (("rows",), dict(row_sync=False, exhaustive_sync=True, chained_write=True)),
+    # the families that run on the window tables, those built by the host: the flags are the families' own (None)
+    "ET_DEC_TABLES_HOST": (("exitmaps", "round1"), None),
 }
 SWITCH_LENGTHS = (17, 4097, 65_537, OWN)
 
