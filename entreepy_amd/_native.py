@@ -132,6 +132,10 @@ SIGNATURES = {
     "et_decode_batch_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz]),
     "et_batch_small_max": (_sz, []),
     "et_batch_item_size": (_sz, []),
+    "et_encode_shared_device": (ctypes.c_int, [_vp, _cbp, _vp, _vp, _vp, _sz]),
+    "et_decode_shared_device": (ctypes.c_int, [_vp, _cbp, _vp, _vp, _vp, _sz]),
+    "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
+    "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),
     "et_histogram_on_host": (ctypes.c_int, [_vp, _vp]),
     "et_histogram_host": (ctypes.c_int, [_vp, _vp]),

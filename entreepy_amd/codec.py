@@ -115,6 +115,14 @@ class Codebook:
         _check(N.lib().et_codebook_bits(ctypes.byref(self.raw), h.ctypes.data, ctypes.byref(b)))
         return b.value
 
+    def is_complete(self):
+        """A full prefix-free tree of codes up to 32 bits (et_codebook_is_complete): what the shared-table calls ask for."""
+        return N.lib().et_codebook_is_complete(ctypes.byref(self.raw)) == N.ET_OK
+
+    def body_bound(self, n):
+        """Bytes that always hold the body of n symbols (et_body_bound)."""
+        return N.lib().et_body_bound(ctypes.byref(self.raw), int(n))
+
 
 def parse_header(compressed_text):
     """decode.zig:34-141 via et_parse_header -> (Codebook, n_symbols, body_offset)."""
@@ -357,6 +365,67 @@ class Context:
         """[.et files minus their first four bytes] -> [their texts], through one decode_batch_device call."""
         caps = [int.from_bytes(bytes(c[1:5]), "big") + 16 if len(c) >= 5 else 16 for c in compressed_texts]
         return self._batch_host(self.decode_batch_device, compressed_texts, caps, "decode_batch")
+
+    # -- batched bodies under one shared code table (et_encode_shared_device / et_decode_shared_device) ------------
+    def _shared_device(self, fn, codebook, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps):
+        items = np.zeros(len(in_offsets), dtype=self._ITEM)
+        items["in_off"], items["in_len"], items["out_off"], items["out_cap"] = in_offsets, in_lens, out_offsets, out_caps
+        self._bind()
+        _check(fn(self._h, ctypes.byref(codebook.raw), in_tensor.data_ptr(), None if out_tensor is None else out_tensor.data_ptr(),
+                  items.ctypes.data if items.size else None, items.size), self._h)
+        return items["out_len"].copy(), items["status"].copy(), items["path"].copy()
+
+    def encode_shared_device(self, codebook, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps):
+        """Record b: the text in_tensor[in_offsets[b] : + in_lens[b]] -> its body alone under `codebook` (a complete table:
+        Codebook.is_complete) at out_tensor[out_offsets[b] : + out_lens[b]], any alignment, not a byte beyond it;
+        out_caps[b] >= codebook.body_bound(in_lens[b]) always suffices.  out_tensor=None: sizes only -- nothing is written,
+        out_lens and statuses are the writing call's.  -> (out_lens, statuses, paths) as encode_batch_device; paths are 0."""
+        return self._shared_device(N.lib().et_encode_shared_device, codebook, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps)
+
+    def decode_shared_device(self, codebook, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps):
+        """Record b: the body in_tensor[in_offsets[b] : + in_lens[b]] -> out_caps[b] symbols (the record's length, which the
+        caller keeps; fewer when the body ends early) at out_tensor[out_offsets[b] : ...].  Returns as encode_shared_device."""
+        return self._shared_device(N.lib().et_decode_shared_device, codebook, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps)
+
+    def _shared_host(self, call, codebook, blobs, what, out_lens=None):
+        """One upload, the call(s), one download; the outputs lie back to back.  out_lens=None: a sizes-only call finds them."""
+        import torch
+
+        blobs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blobs]
+        if not blobs:
+            return []
+        lens = np.array([b.size for b in blobs], dtype=np.uint64)
+        in_off = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.uint64)
+        dev = torch.device("cuda", self.device)
+        packed = np.concatenate(blobs)
+        d_in = torch.empty(max(packed.size, 1), dtype=torch.uint8, device=dev)
+        d_in[: packed.size] = torch.from_numpy(packed).to(dev)
+
+        def first_failure(statuses):
+            bad = np.flatnonzero(statuses)
+            if bad.size:
+                raise EntreepyError(int(statuses[bad[0]]), f"{what}: item {int(bad[0])}")
+
+        if out_lens is None:
+            out_lens, statuses, _ = call(codebook, d_in, in_off, lens, None, np.zeros(lens.size, np.uint64), np.zeros(lens.size, np.uint64))
+            first_failure(statuses)
+        caps = np.asarray(out_lens, dtype=np.uint64)
+        out_off = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        d_out = torch.empty(max(int(caps.sum()), 1), dtype=torch.uint8, device=dev)
+        out_lens, statuses, _ = call(codebook, d_in, in_off, lens, d_out, out_off, caps)
+        first_failure(statuses)
+        host = d_out.cpu().numpy()  # (the copy runs on torch's current stream, behind the call's kernels)
+        return [host[int(o) : int(o) + int(n)].tobytes() for o, n in zip(out_off, out_lens)]
+
+    def encode_shared(self, codebook, texts):
+        """[bytes] -> [their bodies under `codebook`]: a sizes-only call, a prefix sum, then one call that packs the bodies
+        back to back.  Raises EntreepyError naming the first item that failed (a byte the table has no code for)."""
+        return self._shared_host(self.encode_shared_device, codebook, texts, "encode_shared")
+
+    def decode_shared(self, codebook, bodies, lengths):
+        """[bodies], [the records' lengths] -> [their texts], through one decode_shared_device call."""
+        assert len(bodies) == len(lengths)
+        return self._shared_host(self.decode_shared_device, codebook, bodies, "decode_shared", out_lens=lengths)
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

@@ -12,6 +12,16 @@
 // (stream order; a switch of streams keeps it, et_ctx_set_stream): when its epoch word arrives, the uploads and
 // kernels of the chunk before are over.  The records that first kernel reads are written before it is enqueued, into a
 // region no later upload of a chunk reads.
+//
+// The shared-table calls (et_encode_shared_device / et_decode_shared_device) need no hand-over in front of their kernel:
+//   per chunk of SHARED_CHUNK streams   job records -> one upload -> k_shared_encode / k_shared_decode -> (poll) lengths and statuses
+// and the table goes up once per call, in front of the first chunk.  They keep a region of their own at the pinned block's
+// end (table, job records, results).  It may be refilled without asking, by the next chunk and by the next call -- with
+// another table, and with no synchronisation in between -- because EVERY chunk ends with a poll for its kernel's report:
+// when that epoch word has arrived, the kernel is over, and so are the uploads in front of it on the stream, the table's
+// among them; a call returns only behind its last chunk's poll.  (That region is kept apart from the batch calls' because
+// et_encode_batch_device ends with uploads and a kernel nobody polls for.)  On the device, table and records are rewritten
+// in stream order behind the kernel that read them.
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -23,13 +33,19 @@ namespace {
 
 constexpr size_t CH = et::BATCH_CHUNK;
 // the pinned block
-constexpr size_t PIN_WORDS = 0;                                   // u64[8]: [0] k_batch_hist, [1] k_batch_heads, [2] k_batch_decode
+constexpr size_t PIN_WORDS = 0;                                   // u64[8]: [0] k_batch_hist, [1] k_batch_heads, [2] k_batch_decode, [3] k_shared_*
 constexpr size_t PIN_SPANS = 64;                                  // BatchSpan[CH]
 constexpr size_t PIN_JOBS = PIN_SPANS + CH * sizeof(et::BatchSpan);  // BatchEncJob / BatchDecJob [CH]
 constexpr size_t PIN_TOTALS = PIN_JOBS + CH * sizeof(et::BatchDecJob);
 constexpr size_t PIN_REPORT = PIN_TOTALS + CH * sizeof(uint32_t);   // histograms (1 KiB per stream) or heads (BATCH_HEAD_STRIDE)
 constexpr size_t PIN_BLOB = PIN_REPORT + CH * et::BATCH_HEAD_STRIDE;
-constexpr size_t PIN_BYTES = PIN_BLOB + CH * et::BATCH_ENC_SLOT;
+// ... and the shared-table calls' region
+constexpr size_t SCH = et::SHARED_CHUNK;
+constexpr size_t PIN_SH_TABLE = PIN_BLOB + CH * et::BATCH_ENC_SLOT;  // 2 KiB: {left-aligned code, length} x 256, or the sorted codes
+constexpr size_t PIN_SH_JOBS = PIN_SH_TABLE + 2048;                  // SharedJob[SCH]
+constexpr size_t PIN_SH_RESULTS = PIN_SH_JOBS + SCH * sizeof(et::SharedJob);  // uint2[SCH]
+constexpr size_t PIN_BYTES = PIN_SH_RESULTS + SCH * 8;
+static_assert(sizeof(et::SharedJob) == 24 && PIN_SH_TABLE % 16 == 0, "layout of the pinned block");
 static_assert(sizeof(et::BatchSpan) == 16 && sizeof(et::BatchEncJob) == 32 && sizeof(et::BatchDecJob) == 40, "job records are plain, packed data");
 static_assert(et::BATCH_HEAD_STRIDE >= 1024 && PIN_BLOB % 16 == 0 && PIN_JOBS % 8 == 0, "layout of the pinned block");
 // the device block of records: spans, then jobs
@@ -49,6 +65,9 @@ int ensure_batch(et_ctx *ctx, size_t n_items, size_t slot_bytes) {
     }
     return ET_OK;
 }
+
+// The low `len` bits of `code` (1 <= len <= 32) at the top of a word.
+uint32_t et_left_aligned(uint32_t code, uint32_t len) { return len == 32 ? code : (code & ((1u << len) - 1u)) << (32 - len); }
 
 template <typename T>
 T *pin(et_ctx *ctx, size_t off) { return reinterpret_cast<T *>(ctx->h_batch + off); }
@@ -86,6 +105,83 @@ int check_call(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items,
     return ET_OK;
 }
 
+// Both shared-table calls.  encode: d_out may be null (sizes only).
+int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_out, et_batch_item *items, size_t n_items, bool encode) {
+    if (!ctx) return ET_ERR_ARG;
+    if (n_items == 0) return ET_OK;
+    if (!cb || !items || !d_in || (!d_out && !encode)) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (n_items > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many items");
+    for (size_t i = 0; i < n_items; ++i) {
+        items[i].out_len = 0;
+        items[i].status = ET_OK;
+        items[i].path = 0;
+    }
+    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    if (d_out && outputs_overlap(items, n_items)) return fail(ctx, ET_ERR_ARG, "outputs of different items overlap");
+    DeviceGuard guard(ctx->device);
+
+    std::vector<uint32_t> todo;
+    for (size_t i = 0; i < n_items; ++i) {
+        et_batch_item &it = items[i];
+        if (it.in_len == 0 || (!encode && it.out_cap == 0)) continue;  // an empty record is a record: ET_OK, nothing to do
+        if ((encode ? it.in_len : it.out_cap) > et::BATCH_SMALL_MAX) it.status = ET_ERR_UNSUPPORTED;
+        else todo.push_back(static_cast<uint32_t>(i));
+    }
+    if (todo.empty()) return ET_OK;
+    ET_TRY(ensure_batch(ctx, 1, 2048));
+    ET_TRY(ensure(ctx, ctx->batch_jobs, std::min(todo.size(), SCH) * sizeof(et::SharedJob)));
+
+    // the table: free to fill (this file's header), up in front of the first chunk
+    uint32_t *tab = pin<uint32_t>(ctx, PIN_SH_TABLE);
+    uint32_t n_codes = 0;
+    if (encode) {
+        for (int s = 0; s < 256; ++s) {
+            const uint32_t len = cb->length[s];
+            tab[2 * s] = len ? et_left_aligned(cb->data[s], len) : 0u;
+            tab[2 * s + 1] = len;
+        }
+    } else {
+        struct Code { uint32_t lo, meta; };
+        Code *codes = reinterpret_cast<Code *>(tab);
+        for (int s = 0; s < 256; ++s)
+            if (cb->length[s]) codes[n_codes++] = Code{et_left_aligned(cb->data[s], cb->length[s]), static_cast<uint32_t>(cb->length[s]) << 8 | static_cast<uint32_t>(s)};
+        std::sort(codes, codes + n_codes, [](const Code &a, const Code &b) { return a.lo < b.lo; });
+    }
+    ET_HIP(hipMemcpyAsync(ctx->batch_blob.p, tab, 2048, hipMemcpyHostToDevice, ctx->stream));
+
+    for (size_t c0 = 0; c0 < todo.size(); c0 += SCH) {
+        const uint32_t n = static_cast<uint32_t>(std::min(SCH, todo.size() - c0));
+        et::SharedJob *jobs = pin<et::SharedJob>(ctx, PIN_SH_JOBS);
+        for (uint32_t j = 0; j < n; ++j) {
+            const et_batch_item &it = items[todo[c0 + j]];
+            if (encode) {
+                const uint64_t cap = d_out ? it.out_cap : ~0ull;
+                jobs[j] = et::SharedJob{it.in_off, it.out_off, static_cast<uint32_t>(it.in_len), static_cast<uint32_t>(std::min<uint64_t>(cap, 0xffffffffu))};
+            } else {
+                // (out_cap codewords of at most 32 bits end within 4 out_cap bytes: the kernel's bit positions stay small)
+                jobs[j] = et::SharedJob{it.in_off, it.out_off, static_cast<uint32_t>(std::min<uint64_t>(it.in_len, it.out_cap * 4 + 8)), static_cast<uint32_t>(it.out_cap)};
+            }
+        }
+        ET_HIP(hipMemcpyAsync(ctx->batch_jobs.p, jobs, n * sizeof(et::SharedJob), hipMemcpyHostToDevice, ctx->stream));
+        const uint64_t epoch = ++ctx->batch_epoch;
+        uint2 *results = pin<uint2>(ctx, PIN_SH_RESULTS);
+        if (encode)
+            et::launch_shared_encode(ctx->stream, d_in, d_out, static_cast<const et::SharedJob *>(ctx->batch_jobs.p), n, static_cast<const uint2 *>(ctx->batch_blob.p),
+                                     results, static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 3), epoch);
+        else
+            et::launch_shared_decode(ctx->stream, d_in, d_out, static_cast<const et::SharedJob *>(ctx->batch_jobs.p), n, static_cast<const uint2 *>(ctx->batch_blob.p),
+                                     n_codes, results, static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 3), epoch);
+        ET_HIP(hipGetLastError());
+        ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 3), epoch, 2000.0, "the shared-table batch's results never reached the host"));
+        for (uint32_t j = 0; j < n; ++j) {
+            et_batch_item &it = items[todo[c0 + j]];
+            it.status = results[j].y == et::SHARED_OK ? ET_OK : results[j].y == et::SHARED_CAP ? ET_ERR_CAP : ET_ERR_UNSUPPORTED;
+            it.out_len = results[j].x;
+        }
+    }
+    return ET_OK;
+}
+
 // An item's own failure is the item's; a failure of the runtime under a delegated stream is the call's.
 bool call_level(int rc) { return rc == ET_ERR_HIP || rc == ET_ERR_NOMEM; }
 
@@ -94,6 +190,14 @@ bool call_level(int rc) { return rc == ET_ERR_HIP || rc == ET_ERR_NOMEM; }
 extern "C" size_t et_batch_small_max(void) { return et::BATCH_SMALL_MAX; }
 
 extern "C" size_t et_batch_item_size(void) { return sizeof(et_batch_item); }
+
+extern "C" int et_encode_shared_device(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {
+    return shared_call(ctx, cb, d_in, d_out, items, n_items, true);
+}
+
+extern "C" int et_decode_shared_device(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {
+    return shared_call(ctx, cb, d_in, d_out, items, n_items, false);
+}
 
 extern "C" int et_encode_batch_device(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {
     ET_TRY(check_call(ctx, d_in, d_out, items, n_items));

@@ -1,6 +1,8 @@
 // et_batch.h -- geometry, job records and launch wrappers of et_batch.hip: many small streams in one call, ONE workgroup
 // per stream from its first byte to its last (et_encode_batch_device / et_decode_batch_device, host side et_batch.cpp).
 // Nothing here is shared with the single-stream kernels; streams these kernels are not made for go to those, whole.
+// The shared-table calls (et_encode_shared_device / et_decode_shared_device) have the same shape -- one workgroup per
+// stream -- but ONE code table for the whole batch, set up once per workgroup: SharedJob and its two launches below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -43,6 +45,20 @@ struct BatchDecJob {
     uint32_t pad;
 };
 
+// et_encode_shared_device / et_decode_shared_device: a body alone, under the call's one table.
+struct SharedJob {
+    uint64_t in_off, out_off;  // any alignment, both
+    uint32_t in_len;           // encode: text bytes; decode: body bytes (clipped like BatchDecJob's)
+    uint32_t cap;              // encode: bytes the body may take (0xffffffff: no limit); decode: symbols to decode
+};
+// Streams per launch and hand-over of the shared-table calls (a stream costs 24 + 8 bytes of pinned memory here, not a
+// table), and the grids: what is resident at once on 256 CUs (8 and 4 workgroups per CU by LDS), so that a workgroup's
+// tables serve several streams of a full chunk.
+constexpr uint32_t SHARED_CHUNK = 4096;
+constexpr uint32_t SHARED_ENC_GRID = 2048, SHARED_DEC_GRID = 1024;
+// What k_shared_encode reports per stream beside its length (the host turns it into an et_status).
+enum SharedStatus : uint32_t { SHARED_OK = 0, SHARED_UNCODED = 1, SHARED_CAP = 2 };
+
 // counter: one device word, zero between launches (the last workgroup to finish resets it and stores `epoch` into the
 // pinned *host_done, which the host polls).
 void launch_batch_hist(hipStream_t stream, const void *d_in, const BatchSpan *spans, uint32_t n, uint32_t *host_hist, uint32_t *counter,
@@ -52,5 +68,14 @@ void launch_batch_heads(hipStream_t stream, const void *d_in, const BatchSpan *s
                         unsigned long long *host_done, unsigned long long epoch);
 void launch_batch_decode(hipStream_t stream, const void *d_in, void *d_out, const BatchDecJob *jobs, uint32_t n, const uint8_t *blob,
                          uint32_t *host_totals, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
+
+// table: 256 x {left-aligned code, length} on the device.  d_out == nullptr: sizes only.  host_results (pinned): per stream
+// {body bytes (0 unless SHARED_OK), SharedStatus}.
+void launch_shared_encode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *table,
+                          uint2 *host_results, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
+// codes: the n_codes codes of a full prefix-free tree sorted by left-aligned value, {code, length << 8 | symbol}, on the device.
+// host_results (pinned): per stream {symbols written, 0}.
+void launch_shared_decode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *codes,
+                          uint32_t n_codes, uint2 *host_results, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
 
 }  // namespace et

@@ -7,8 +7,12 @@
 //            k_batch_encode  header, then the codes MSB-first, rounds of 4 KiB          (encode.zig:259-318)
 //   decode   k_batch_heads   header + dictionary bytes per stream into pinned memory   (decode.zig:34-141 runs on the host)
 //            k_batch_decode  LDS lookup table, then the body 8 KiB at a time, in order  (decode.zig:143-203)
+// and of the shared-table calls, where ONE table serves the whole batch and is set up once per workgroup, in front of the loop:
+//   encode   k_shared_encode count pass (length, uncoded bytes, capacity), then k_batch_encode's rounds: the body alone, at any
+//            output alignment, not a byte beyond it
+//   decode   k_shared_decode k_batch_decode's stream loop under that one table
 //
-// The three kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
+// The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
 //
 // The workgroup scans and the hand-over itself are et_device.h's.
@@ -120,6 +124,42 @@ __global__ __launch_bounds__(BB) void k_batch_hist(const uint8_t *__restrict__ d
 // --------------------------------------------------------------------------------
 constexpr uint32_t ENC_STAGE_WORDS = ROUND_BYTES * 32 / 32 + 8;  // 4096 symbols of at most 32 bits, + the shared first word
 
+// One round of the pack, shared by k_batch_encode and k_shared_encode: the lane's bit total over its 16 bytes, the workgroup
+// scan, and the lane's codes ORed into the LDS image from stage bit (carry & 31) + what lies before the lane; `pending` (the
+// partial word the round before ended in) goes into stage word 0.  Returns the round's bits.  The caller's barrier follows.
+__device__ __forceinline__ uint32_t pack_round(const Chunk16 &c, const uint2 *s_tab, uint32_t *s_stage, uint32_t *s_wsum, uint32_t carry, uint32_t pending) {
+    const int tid = threadIdx.x;
+    uint32_t bits = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (c.valid & (1u << k)) bits += s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu].y;
+    uint32_t round_bits;
+    const uint32_t before = block_exclusive_scan(bits, s_wsum, &round_bits);  // (s_wsum: the caller's barriers lie between two rounds' scans)
+    if (tid == 0 && pending) atomicOr(&s_stage[0], pending);
+    // the lane's codes, from stage bit p on
+    uint32_t p = (carry & 31) + before;
+    uint32_t wi = p >> 5, fill = p & 31;
+    uint64_t acc = 0;
+    if (bits) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (!(c.valid & (1u << k))) continue;
+            const uint2 e = s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu];
+            if (!e.y) continue;  // (a symbol without a code: the 256-symbol quirk)
+            acc |= (static_cast<uint64_t>(e.x) << 32) >> fill;
+            fill += e.y;
+            if (fill >= 32) {
+                atomicOr(&s_stage[wi], static_cast<uint32_t>(acc >> 32));
+                acc <<= 32;
+                ++wi;
+                fill -= 32;
+            }
+        }
+        if (fill) atomicOr(&s_stage[wi], static_cast<uint32_t>(acc >> 32));
+    }
+    return round_bits;
+}
+
 __global__ __launch_bounds__(BB) void k_batch_encode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const BatchEncJob *__restrict__ jobs,
                                                      uint32_t n, const uint8_t *__restrict__ blob) {
     __shared__ uint2 s_tab[256];
@@ -144,34 +184,7 @@ __global__ __launch_bounds__(BB) void k_batch_encode(const uint8_t *__restrict__
         __syncthreads();
         for (uint64_t r0 = 0; r0 < hi; r0 += ROUND_BYTES) {
             const Chunk16 c = load16(base, r0 + static_cast<uint64_t>(tid) * 16, lo, hi);
-            uint32_t bits = 0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (c.valid & (1u << k)) bits += s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu].y;
-            uint32_t round_bits;
-            const uint32_t before = block_exclusive_scan(bits, s_wsum, &round_bits);  // (s_wsum: the barriers below lie between two rounds' scans)
-            if (tid == 0 && pending) atomicOr(&s_stage[0], pending);
-            // the lane's codes, from stage bit p on
-            uint32_t p = (carry & 31) + before;
-            uint32_t wi = p >> 5, fill = p & 31;
-            uint64_t acc = 0;
-            if (bits) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    if (!(c.valid & (1u << k))) continue;
-                    const uint2 e = s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu];
-                    if (!e.y) continue;  // (a symbol without a code: the 256-symbol quirk)
-                    acc |= (static_cast<uint64_t>(e.x) << 32) >> fill;
-                    fill += e.y;
-                    if (fill >= 32) {
-                        atomicOr(&s_stage[wi], static_cast<uint32_t>(acc >> 32));
-                        acc <<= 32;
-                        ++wi;
-                        fill -= 32;
-                    }
-                }
-                if (fill) atomicOr(&s_stage[wi], static_cast<uint32_t>(acc >> 32));
-            }
+            const uint32_t round_bits = pack_round(c, s_tab, s_stage, s_wsum, carry, pending);
             __syncthreads();
             const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
             pending = (t_bits & 31) ? s_stage[full] : 0u;
@@ -277,6 +290,84 @@ __device__ __forceinline__ uint32_t walk(BatchDecLds &s, uint32_t n_codes, uint3
     return pos;
 }
 
+// The first-level table from the sorted codes in s.codes (a barrier lies between their stores and this).
+__device__ __forceinline__ void fill_lut(BatchDecLds &s, uint32_t n_codes) {
+    for (uint32_t e = threadIdx.x; e < (1u << BATCH_LUT_BITS); e += BB) {
+        const uint32_t meta = find_code(s, n_codes, e << (32 - BATCH_LUT_BITS));
+        s.lut[e] = (meta >> 8) <= BATCH_LUT_BITS ? static_cast<uint16_t>(meta) : static_cast<uint16_t>(0);
+    }
+}
+
+// One stream under the tables in `s` (k_batch_decode, k_shared_decode): its blocks in order.  Returns the symbols it holds, at
+// most n_symbols; the first write_cap of them are stored.  Every block begins with a barrier: that is the one between
+// fill_lut, or the stream before, and this stream's first walk.
+__device__ __forceinline__ uint32_t decode_stream(BatchDecLds &s, uint32_t n_codes, const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, uint64_t body_off,
+                                                  uint64_t out_off, uint32_t body_bytes, uint32_t n_symbols, uint32_t write_cap) {
+    const uint32_t tid = threadIdx.x;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + body_off;
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
+    const uint32_t first_bit = static_cast<uint32_t>(a & 3) * 8;
+    const uint32_t end_bit = first_bit + body_bytes * 8;  // the body's last bit + 1, from the aligned base
+    const uint32_t n_words = (end_bit + 31) >> 5, n_blocks = (n_words + DEC_WORDS - 1) / DEC_WORDS;
+    uint8_t *out = d_out + out_off;
+    uint32_t start = first_bit, done = 0;  // the block's first codeword; symbols so far
+    for (uint32_t blk = 0; blk < n_blocks && done < n_symbols; ++blk) {
+        __syncthreads();  // (the block before is done with the stages and entry[BB])
+        for (uint32_t k = tid; k < DEC_STAGED; k += BB) {
+            const uint32_t g = blk * DEC_WORDS + k;
+            s.bits[padded(k)] = g < n_words ? __builtin_bswap32(words[g]) : 0u;  // (an aligned word that holds a body byte; zeros behind)
+        }
+        s.entry[tid] = tid == 0 ? start : 0u;
+        __syncthreads();
+        const uint32_t lane_bit = tid * 256;
+        const int64_t room = static_cast<int64_t>(end_bit) - (static_cast<int64_t>(blk) * DEC_WORDS * 32 + lane_bit);
+        uint32_t used = 0xffffffffu, exit = 256, count = 0;
+        for (uint32_t trip = 0; trip < BB; ++trip) {
+            const uint32_t mine = s.entry[tid];
+            int changed = 0;
+            if (mine != used) {
+                const uint32_t was = exit;
+                exit = room > 0 ? walk<false>(s, n_codes, lane_bit, mine, room, &count) : 256u;
+                used = mine;
+                changed = exit != was || trip == 0;
+            }
+            __syncthreads();
+            if (changed) s.entry[tid + 1] = exit - 256;
+            if (!__syncthreads_or(changed)) break;
+        }
+        // counts -> where the lane's symbols go
+        uint32_t total;
+        const uint32_t first = block_exclusive_scan(count, s.wsum, &total);  // (s.wsum: the next block's first barrier lies between two scans)
+        const uint32_t left = n_symbols - done, take = total < left ? total : left;
+        const uint32_t cap_left = write_cap > done ? write_cap - done : 0u, n_write = take < cap_left ? take : cap_left;
+        for (uint32_t s0 = 0; s0 < n_write; s0 += BATCH_STAGE_BYTES) {
+            const uint32_t s1 = s0 + BATCH_STAGE_BYTES < n_write ? s0 + BATCH_STAGE_BYTES : n_write;
+            uint8_t *dst = out + done + s0;
+            const uint32_t align = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3);
+            if (count && first < s1 && first + count > s0) {
+                uint32_t again;
+                (void)walk<true>(s, n_codes, lane_bit, used, room, &again, first, s0, s1, align);
+            }
+            __syncthreads();
+            const uint32_t lo = align, hi = align + (s1 - s0);  // stage bytes [lo, hi) -> dst - align + [lo, hi)
+            uint8_t *line = dst - align;
+            const uint8_t *stage = reinterpret_cast<const uint8_t *>(s.out);
+            for (uint32_t w = tid; w * 4 < hi; w += BB) {
+                if (w * 4 >= lo && w * 4 + 4 <= hi) {
+                    reinterpret_cast<uint32_t *>(line)[w] = s.out[w];
+                } else {
+                    for (uint32_t b = w * 4; b < w * 4 + 4; ++b)
+                        if (b >= lo && b < hi) line[b] = stage[b];
+                }
+            }
+            __syncthreads();
+        }
+        start = s.entry[BB];
+        done += take;
+    }
+    return done;
+}
+
 __global__ __launch_bounds__(BB) void k_batch_decode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const BatchDecJob *__restrict__ jobs,
                                                      uint32_t n, const uint8_t *__restrict__ blob, uint32_t *__restrict__ host_totals,
                                                      uint32_t *__restrict__ counter, unsigned long long *__restrict__ host_done, unsigned long long epoch) {
@@ -287,78 +378,126 @@ __global__ __launch_bounds__(BB) void k_batch_decode(const uint8_t *__restrict__
         __syncthreads();  // (the stream before is done with the tables)
         if (tid < job.n_codes) s.codes[tid] = reinterpret_cast<const uint2 *>(blob + job.blob_off)[tid];
         __syncthreads();
-        for (uint32_t e = tid; e < (1u << BATCH_LUT_BITS); e += BB) {
-            const uint32_t meta = find_code(s, job.n_codes, e << (32 - BATCH_LUT_BITS));
-            s.lut[e] = (meta >> 8) <= BATCH_LUT_BITS ? static_cast<uint16_t>(meta) : static_cast<uint16_t>(0);
-        }
-        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + job.body_off;
-        const uint32_t *words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
-        const uint32_t first_bit = static_cast<uint32_t>(a & 3) * 8;
-        const uint32_t end_bit = first_bit + job.body_bytes * 8;  // the body's last bit + 1, from the aligned base
-        const uint32_t n_words = (end_bit + 31) >> 5, n_blocks = (n_words + DEC_WORDS - 1) / DEC_WORDS;
-        uint8_t *out = d_out + job.out_off;
-        uint32_t start = first_bit, done = 0;  // the block's first codeword; symbols so far
-        for (uint32_t blk = 0; blk < n_blocks && done < job.n_symbols; ++blk) {
-            __syncthreads();  // (the block before is done with the stages and entry[BB])
-            for (uint32_t k = tid; k < DEC_STAGED; k += BB) {
-                const uint32_t g = blk * DEC_WORDS + k;
-                s.bits[padded(k)] = g < n_words ? __builtin_bswap32(words[g]) : 0u;  // (an aligned word that holds a body byte; zeros behind)
-            }
-            s.entry[tid] = tid == 0 ? start : 0u;
-            __syncthreads();
-            const uint32_t lane_bit = tid * 256;
-            const int64_t room = static_cast<int64_t>(end_bit) - (static_cast<int64_t>(blk) * DEC_WORDS * 32 + lane_bit);
-            uint32_t used = 0xffffffffu, exit = 256, count = 0;
-            for (uint32_t trip = 0; trip < BB; ++trip) {
-                const uint32_t mine = s.entry[tid];
-                int changed = 0;
-                if (mine != used) {
-                    const uint32_t was = exit;
-                    exit = room > 0 ? walk<false>(s, job.n_codes, lane_bit, mine, room, &count) : 256u;
-                    used = mine;
-                    changed = exit != was || trip == 0;
-                }
-                __syncthreads();
-                if (changed) s.entry[tid + 1] = exit - 256;
-                if (!__syncthreads_or(changed)) break;
-            }
-            // counts -> where the lane's symbols go
-            uint32_t total;
-            const uint32_t first = block_exclusive_scan(count, s.wsum, &total);  // (s.wsum: the next block's first barrier lies between two scans)
-            const uint32_t left = job.n_symbols - done, take = total < left ? total : left;
-            const uint32_t cap_left = job.write_cap > done ? job.write_cap - done : 0u, n_write = take < cap_left ? take : cap_left;
-            for (uint32_t s0 = 0; s0 < n_write; s0 += BATCH_STAGE_BYTES) {
-                const uint32_t s1 = s0 + BATCH_STAGE_BYTES < n_write ? s0 + BATCH_STAGE_BYTES : n_write;
-                uint8_t *dst = out + done + s0;
-                const uint32_t align = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3);
-                if (count && first < s1 && first + count > s0) {
-                    uint32_t again;
-                    (void)walk<true>(s, job.n_codes, lane_bit, used, room, &again, first, s0, s1, align);
-                }
-                __syncthreads();
-                const uint32_t lo = align, hi = align + (s1 - s0);  // stage bytes [lo, hi) -> dst - align + [lo, hi)
-                uint8_t *line = dst - align;
-                const uint8_t *stage = reinterpret_cast<const uint8_t *>(s.out);
-                for (uint32_t w = tid; w * 4 < hi; w += BB) {
-                    if (w * 4 >= lo && w * 4 + 4 <= hi) {
-                        reinterpret_cast<uint32_t *>(line)[w] = s.out[w];
-                    } else {
-                        for (uint32_t b = w * 4; b < w * 4 + 4; ++b)
-                            if (b >= lo && b < hi) line[b] = stage[b];
-                    }
-                }
-                __syncthreads();
-            }
-            start = s.entry[BB];
-            done += take;
-        }
+        fill_lut(s, job.n_codes);
+        const uint32_t done = decode_stream(s, job.n_codes, d_in, d_out, job.body_off, job.out_off, job.body_bytes, job.n_symbols, job.write_cap);
         if (tid == 0) host_totals[j] = done;
     }
     batch_done(counter, host_done, epoch);
 }
 
 // --------------------------------------------------------------------------------
+// k_shared_encode: ONE code table for every stream, in LDS before the loop.  Per stream a count pass over the text -- the
+// body's bits, and whether a byte has no code -- decides its status and length before a byte is stored (and is all there
+// is when d_out is null: sizes only).  Then k_batch_encode's rounds, with the LDS bit image beginning at bit 8 * (address & 3)
+// of the output's aligned word: whole words inside the body leave as dword stores, the bytes of the first and the last
+// word that belong to it as byte stores, so that [out_off, out_off + bytes) is all the stream writes and bodies may lie
+// back to back.  LDS as k_batch_encode.
+// --------------------------------------------------------------------------------
+// Word g of the image at `line` (4-byte aligned): whole when it lies inside the image bytes [lo, hi), else its bytes that do.
+__device__ __forceinline__ void store_image_word(uint8_t *line, uint32_t g, uint32_t v, uint32_t lo, uint32_t hi) {
+    const uint32_t b0 = g * 4;
+    if (b0 >= lo && b0 + 4 <= hi) {
+        reinterpret_cast<uint32_t *>(line)[g] = v;
+    } else {
+        for (uint32_t k = 0; k < 4; ++k)
+            if (b0 + k >= lo && b0 + k < hi) line[b0 + k] = static_cast<uint8_t>(v >> (8 * k));
+    }
+}
+
+__global__ __launch_bounds__(BB) void k_shared_encode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const SharedJob *__restrict__ jobs,
+                                                      uint32_t n, const uint2 *__restrict__ table, uint2 *__restrict__ host_results,
+                                                      uint32_t *__restrict__ counter, unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    __shared__ uint2 s_tab[256];
+    __shared__ uint32_t s_stage[ENC_STAGE_WORDS];
+    __shared__ uint32_t s_wsum[4];
+    const int tid = threadIdx.x;
+    s_tab[tid] = table[tid];
+    for (uint32_t i = tid; i < ENC_STAGE_WORDS; i += BB) s_stage[i] = 0;
+    __syncthreads();
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const SharedJob job = jobs[j];
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + job.in_off;
+        const uint8_t *base = reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15));
+        const uint64_t lo = a & 15, hi = lo + job.in_len;
+        // the count pass
+        uint32_t bits = 0;
+        int uncoded = 0;
+        for (uint64_t off = static_cast<uint64_t>(tid) * 16; off < hi; off += ROUND_BYTES) {
+            const Chunk16 c = load16(base, off, lo, hi);
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (c.valid & (1u << k)) {
+                    const uint32_t len = s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu].y;
+                    bits += len;
+                    uncoded |= !len;
+                }
+        }
+        uint32_t total;
+        (void)block_exclusive_scan(bits, s_wsum, &total);
+        uncoded = __syncthreads_or(uncoded);  // (and the barrier between this scan and the next one's s_wsum)
+        const uint32_t bytes = (total + 7) >> 3;
+        const uint32_t status = uncoded ? SHARED_UNCODED : bytes > job.cap ? SHARED_CAP : SHARED_OK;
+        if (tid == 0) host_results[j] = make_uint2(status == SHARED_OK ? bytes : 0u, status);
+        if (status != SHARED_OK || !d_out || !bytes) continue;  // (the same for every lane)
+        // the pack pass
+        uint8_t *dst = d_out + job.out_off;
+        const uint32_t lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3), end_byte = lead + bytes;  // image bytes [lead, end_byte) are the body
+        uint8_t *line = dst - lead;
+        uint32_t pending = 0, carry = lead * 8;  // image bits written so far
+        for (uint64_t r0 = 0; r0 < hi; r0 += ROUND_BYTES) {
+            const Chunk16 c = load16(base, r0 + static_cast<uint64_t>(tid) * 16, lo, hi);
+            const uint32_t round_bits = pack_round(c, s_tab, s_stage, s_wsum, carry, pending);
+            __syncthreads();
+            const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
+            pending = (t_bits & 31) ? s_stage[full] : 0u;
+            __syncthreads();
+            for (uint32_t i = tid; i <= full; i += BB) {
+                if (i < full) store_image_word(line, w0 + i, __builtin_bswap32(s_stage[i]), lead, end_byte);
+                s_stage[i] = 0;
+            }
+            carry += round_bits;
+            __syncthreads();
+        }
+        if (tid == 0 && (carry & 31)) store_image_word(line, carry >> 5, __builtin_bswap32(pending), lead, end_byte);
+    }
+    batch_done(counter, host_done, epoch);
+}
+
+// --------------------------------------------------------------------------------
+// k_shared_decode: the sorted codes and the first-level table ONCE per workgroup, then k_batch_decode's loop for every
+// stream the workgroup takes.  A stream decodes job.cap symbols (the caller keeps a record's length: the pad bits behind
+// the last codeword would decode as symbols otherwise) or as many codewords as end inside its body.  LDS as k_batch_decode.
+// --------------------------------------------------------------------------------
+__global__ __launch_bounds__(BB) void k_shared_decode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const SharedJob *__restrict__ jobs,
+                                                      uint32_t n, const uint2 *__restrict__ codes, uint32_t n_codes, uint2 *__restrict__ host_results,
+                                                      uint32_t *__restrict__ counter, unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    __shared__ BatchDecLds s;
+    const uint32_t tid = threadIdx.x;
+    if (tid < n_codes) s.codes[tid] = codes[tid];
+    __syncthreads();
+    fill_lut(s, n_codes);
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const SharedJob job = jobs[j];
+        const uint32_t done = decode_stream(s, n_codes, d_in, d_out, job.in_off, job.out_off, job.in_len, job.cap, job.cap);
+        if (tid == 0) host_results[j] = make_uint2(done, 0u);
+    }
+    batch_done(counter, host_done, epoch);
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
+
+void launch_shared_encode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *table,
+                          uint2 *host_results, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
+    hipLaunchKernelGGL(k_shared_encode, dim3(n < SHARED_ENC_GRID ? n : SHARED_ENC_GRID), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), jobs, n, table,
+                       host_results, counter, host_done, epoch);
+}
+
+void launch_shared_decode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *codes,
+                          uint32_t n_codes, uint2 *host_results, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
+    hipLaunchKernelGGL(k_shared_decode, dim3(n < SHARED_DEC_GRID ? n : SHARED_DEC_GRID), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), jobs, n, codes,
+                       n_codes, host_results, counter, host_done, epoch);
+}
 
 void launch_batch_hist(hipStream_t stream, const void *d_in, const BatchSpan *spans, uint32_t n, uint32_t *host_hist, uint32_t *counter,
                        unsigned long long *host_done, unsigned long long epoch) {

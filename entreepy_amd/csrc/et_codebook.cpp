@@ -241,6 +241,32 @@ extern "C" int et_codebook_bits(const et_codebook *cb, const uint64_t hist[256],
     return ET_OK;
 }
 
+// The coded symbols form a full prefix-free tree of codes up to 32 bits: what the batch kernels' decode needs (the code a
+// window begins with is then the largest left-aligned code not above it) and what the shared-table calls ask of their table.
+extern "C" int et_codebook_is_complete(const et_codebook *cb) {
+    if (!cb) return ET_ERR_ARG;
+    struct Iv { uint64_t lo, hi; };
+    Iv iv[256];
+    unsigned k = 0;
+    uint64_t covered = 0;
+    for (int s = 0; s < 256; ++s) {
+        const unsigned len = cb->length[s];
+        if (!len) continue;
+        if (len > 32) return ET_ERR_UNSUPPORTED;
+        const uint64_t span = 1ull << (32 - len);
+        const uint64_t lo = (static_cast<uint64_t>(cb->data[s]) << (32 - len)) & 0xffffffffull;  // (bits above the code's length do not count)
+        iv[k++] = Iv{lo, lo + span};
+        covered += span;
+    }
+    if (k < 2 || covered != (1ull << 32)) return ET_ERR_UNSUPPORTED;
+    std::sort(iv, iv + k, [](const Iv &a, const Iv &b) { return a.lo < b.lo; });
+    for (unsigned i = 0; i + 1 < k; ++i)
+        if (iv[i].hi > iv[i + 1].lo) return ET_ERR_UNSUPPORTED;  // one code is a prefix of another
+    return ET_OK;
+}
+
+extern "C" size_t et_body_bound(const et_codebook *cb, size_t n) { return cb ? (n * cb->max_length + 7) / 8 : 0; }
+
 // encode.zig:221-247, the -d self-check, loop for loop -- including its k = 0 round, which compares the bit
 // ABOVE each code (bit `length`, index truncated to u5).
 extern "C" int et_prefix_collisions(const et_codebook *cb, uint8_t *pairs, size_t cap_pairs, size_t *n_pairs) {

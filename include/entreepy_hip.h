@@ -256,6 +256,38 @@ int et_decode_batch_device(et_ctx *ctx, const void *d_in, void *d_out, et_batch_
 size_t et_batch_small_max(void);
 size_t et_batch_item_size(void);
 
+/* Batched BODIES under ONE code table given by the caller (what a record store calls a dictionary): no magic, no
+ * header and no dictionary per record, and no per-record table work on either side -- the kernels set their tables up
+ * once per workgroup, and the only hand-over to the host is each chunk's lengths and statuses (4096 records per chunk,
+ * csrc/et_batch.h).  The calls do NOT store the table: the caller writes it once with et_write_header and reads it
+ * back with et_parse_header.  A table from et_build_codebook covers at most 255 byte values (and only those its
+ * histogram saw); a record with a byte outside it comes back ET_ERR_UNSUPPORTED and the caller stores it raw.
+ * et_batch_item as above, path always 0; stream-ordered as above (out_len and status final on return, the bytes once the
+ * ctx's stream has drained); a record that fails fails alone.
+ *   et_codebook_is_complete (host only): ET_OK when the coded symbols form a full prefix-free tree -- at least two of
+ *     them, every length <= 32, no code a prefix of another, sum of 2^(32 - length) == 2^32; ET_ERR_UNSUPPORTED otherwise
+ *     (a lone symbol, a hand-made table with holes, a code beyond 32 bits).  Both calls ask it first: for a table that
+ *     fails they return ET_ERR_UNSUPPORTED with nothing enqueued and every out_len = 0.
+ *   et_body_bound (host only): (n * max_length + 7) / 8, an out_cap that always suffices for n bytes of text.
+ *   encode: d_in[in_off, in_off + in_len) (any alignment) -> its codewords MSB-first from bit 7 of d_out[out_off] (ANY
+ *     alignment), the last byte padded with zero bits; out_len = ceil(bits / 8).  Exactly [out_off, out_off + out_len) is
+ *     written -- not the rest of a word, unlike et_encode_batch_device -- so bodies may lie back to back.  in_len == 0:
+ *     ET_OK, out_len 0.  in_len > et_batch_small_max(): ET_ERR_UNSUPPORTED.  A byte without a code: ET_ERR_UNSUPPORTED.
+ *     ceil(bits / 8) > out_cap: ET_ERR_CAP.  A failed record has written nothing and has out_len 0.
+ *     SIZES ONLY: with d_out == NULL nothing is written and no overlap is checked; out_len and status are what the
+ *     writing call gives with out_cap unlimited.  A caller sizes first, prefix-sums, then packs densely.
+ *   decode: the body d_in[in_off, in_off + in_len) (any alignment); out_cap is THE NUMBER OF SYMBOLS TO DECODE -- the
+ *     caller keeps a record's length; the pad bits may decode as symbols otherwise.  out_len = min(out_cap, codewords
+ *     that end inside the body) symbols go to d_out[out_off, ...) (any alignment), and nothing outside
+ *     [out_off, out_off + out_len) is written.  A body that ends early: ET_OK with the shorter out_len.  in_len == 0 or
+ *     out_cap == 0: ET_OK, out_len 0.  out_cap > et_batch_small_max(): ET_ERR_UNSUPPORTED.
+ * The call's own status: ET_ERR_ARG (null ctx, cb, items or d_in; null d_out on decode; overlapping outputs, checked
+ * before anything is enqueued), ET_ERR_UNSUPPORTED (the table), ET_ERR_HIP, ET_ERR_NOMEM.  n_items == 0: ET_OK. */
+int et_encode_shared_device(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_out, et_batch_item *items, size_t n_items);
+int et_decode_shared_device(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_out, et_batch_item *items, size_t n_items);
+int et_codebook_is_complete(const et_codebook *cb);
+size_t et_body_bound(const et_codebook *cb, size_t n);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

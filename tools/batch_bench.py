@@ -6,12 +6,19 @@ process of its own so that every leg loads exactly one build of the library:
                   the commit before the batched calls; it does not export them).  Left out when no such build is given.
   single          the same loop on this tree's library (ET_LIB_PATH, or entreepy_amd/libentreepy_hip.so): shows that the
                   single-stream calls did not move.
-  batch           et_encode_batch_device / et_decode_batch_device, one call per shape, on this tree's library.
+  batch           et_encode_batch_device / et_decode_batch_device, one call per shape, on this tree's library -- or on the one
+                  named by --batch-lib (a build of the commit before the shared-table calls, to set `shared` against).
+  shared          et_encode_shared_device / et_decode_shared_device, one call per shape, on this tree's library: the bodies alone
+                  under ONE table built from the histogram of the whole shape's text, each body in a slot of et_body_bound bytes.
+                  Also reports what the records take: body_bytes (all bodies), header_bytes (the one header that stores the
+                  table) -- against the batch leg's image_bytes (all per-stream .et images).
+--legs picks the legs (default: all).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
 text once before timing.  One JSON line on stdout (and into --out).
 
     python tools/batch_bench.py --parent-lib /path/to/parent/libentreepy_hip.so --out profiles/batch_bench.json
+    python tools/batch_bench.py --legs batch,shared --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/shared_bench.json
 """
 import argparse
 import ctypes
@@ -38,6 +45,8 @@ def _leg(leg, lib_path):
     names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_encode_bound", "et_encode_device", "et_decode_device", "et_last_error"]
     if leg == "batch":
         names += ["et_encode_batch_device", "et_decode_batch_device"]
+    if leg == "shared":
+        names += ["et_encode_shared_device", "et_decode_shared_device", "et_build_codebook", "et_write_header", "et_body_bound", "et_codebook_is_complete"]
     L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)  # (torch is imported: the process-wide HIP runtime is loaded)
     dev = torch.device("cuda", 0)
     h = ctypes.c_void_p()
@@ -47,6 +56,13 @@ def _leg(leg, lib_path):
     for count, size in SHAPES:
         text = corpus.text_like_torch(count * size, 0xB47C4 + size, dev)
         bound = L.et_encode_bound(size)
+        if leg == "shared":  # one table for the whole shape, from the histogram of all of its text
+            hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
+            cb = N.Codebook()
+            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+            bound = (L.et_body_bound(ctypes.byref(cb), size) + 15) // 16 * 16
+            head, head_len = np.zeros(8192, np.uint8), ctypes.c_size_t(0)
+            assert L.et_write_header(ctypes.byref(cb), count * size, head.ctypes.data, head.size, ctypes.byref(head_len)) == 0
         enc = torch.zeros(count * bound + 64, dtype=torch.uint8, device=dev)
         dec = torch.zeros(count * (size + 16) + 64, dtype=torch.uint8, device=dev)
         enc_len = np.zeros(count, dtype=np.uint64)
@@ -57,8 +73,14 @@ def _leg(leg, lib_path):
         items_e["in_off"], items_e["in_len"], items_e["out_off"], items_e["out_cap"] = idx * size, size, idx * bound, bound
         items_d["in_off"], items_d["out_off"], items_d["out_cap"] = idx * bound + 4, idx * (size + 16), size + 16
 
+        if leg == "shared":  # (bodies: nothing to skip in front of them, and out_cap is the record's length)
+            items_d["in_off"], items_d["out_cap"] = idx * bound, size
+
         def encode_all():
-            if leg == "batch":
+            if leg == "shared":
+                assert L.et_encode_shared_device(h, ctypes.byref(cb), text.data_ptr(), enc.data_ptr(), items_e.ctypes.data, count) == 0, L.et_last_error(h)
+                enc_len[:] = items_e["out_len"]
+            elif leg == "batch":
                 assert L.et_encode_batch_device(h, text.data_ptr(), enc.data_ptr(), items_e.ctypes.data, count) == 0, L.et_last_error(h)
                 enc_len[:] = items_e["out_len"]
             else:
@@ -67,7 +89,11 @@ def _leg(leg, lib_path):
                     enc_len[i] = n.value
 
         def decode_all():
-            if leg == "batch":
+            if leg == "shared":
+                items_d["in_len"] = enc_len
+                assert L.et_decode_shared_device(h, ctypes.byref(cb), enc.data_ptr(), dec.data_ptr(), items_d.ctypes.data, count) == 0, L.et_last_error(h)
+                assert not items_d["status"].any() and (items_d["out_len"] == size).all()
+            elif leg == "batch":
                 items_d["in_len"] = enc_len - np.uint64(4)
                 assert L.et_decode_batch_device(h, enc.data_ptr(), dec.data_ptr(), items_d.ctypes.data, count) == 0, L.et_last_error(h)
                 assert not items_d["status"].any() and (items_d["out_len"] == size).all()
@@ -79,8 +105,9 @@ def _leg(leg, lib_path):
         decode_all()
         torch.cuda.synchronize()
         assert torch.equal(dec[: count * (size + 16)].view(count, size + 16)[:, :size].reshape(-1), text), "decoded bytes differ from the text"
-        if leg == "batch":
+        if leg in ("batch", "shared"):
             assert not items_e["status"].any() and not items_e["path"].any() and not items_d["path"].any()
+        sizes = {"image_bytes": int(enc_len.sum())} if leg != "shared" else {"body_bytes": int(enc_len.sum()), "header_bytes": int(head_len.value)}
         enc_ms, dec_ms = [], []
         for rep in range(WARMUP + REPS):
             e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
@@ -96,8 +123,9 @@ def _leg(leg, lib_path):
         both = [a + b for a, b in zip(enc_ms, dec_ms)]
         results[f"{count}x{size}"] = {
             "encode_ms": round(statistics.median(enc_ms), 4), "decode_ms": round(statistics.median(dec_ms), 4),
+            "encode_min_ms": round(min(enc_ms), 4), "encode_max_ms": round(max(enc_ms), 4), "decode_min_ms": round(min(dec_ms), 4), "decode_max_ms": round(max(dec_ms), 4),
             "roundtrip_ms": round(statistics.median(both), 4), "roundtrip_min_ms": round(min(both), 4), "roundtrip_max_ms": round(max(both), 4),
-            "text_gb_per_s": round(2 * count * size / statistics.median(both) / 1e6, 2),
+            "text_gb_per_s": round(2 * count * size / statistics.median(both) / 1e6, 2), **sizes,
         }
         del text, enc, dec
     L.et_ctx_destroy(h)
@@ -107,6 +135,8 @@ def _leg(leg, lib_path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
+    ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
+    ap.add_argument("--legs", default="single_parent,single,batch,shared")
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
     ap.add_argument("--lib")
@@ -114,16 +144,20 @@ def main():
     if a.leg:
         return _leg(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
-    legs = ([("single_parent", "single", a.parent_lib)] if a.parent_lib else []) + [("single", "single", here), ("batch", "batch", here)]
-    out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP}
+    legs = ([("single_parent", "single", a.parent_lib)] if a.parent_lib else []) + [("single", "single", here), ("batch", "batch", a.batch_lib or here), ("shared", "shared", here)]
+    legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
+    out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
     for name, leg, lib in legs:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib], capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"leg {name} failed ({r.returncode})")
         out[name] = json.loads(r.stdout.strip().splitlines()[-1])
-    base = out.get("single_parent", out["single"])
-    out["speedup_vs_" + ("parent" if a.parent_lib else "single")] = {k: round(base[k]["roundtrip_ms"] / out["batch"][k]["roundtrip_ms"], 1) for k in out["batch"]}
+    base = out.get("single_parent", out.get("single"))
+    if base and "batch" in out:
+        out["speedup_vs_" + ("parent" if a.parent_lib else "single")] = {k: round(base[k]["roundtrip_ms"] / out["batch"][k]["roundtrip_ms"], 1) for k in out["batch"]}
+    if "batch" in out and "shared" in out:
+        out["shared_vs_batch"] = {k: {w: round(out["batch"][k][w] / out["shared"][k][w], 2) for w in ("encode_ms", "decode_ms")} for k in out["shared"]}
     line = json.dumps(out)
     print(line)
     if a.out:
