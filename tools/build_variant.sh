@@ -13,8 +13,8 @@ mkdir -p $out
 HIPCC=/opt/rocm/bin/hipcc
 SRCDIR=entreepy_amd/csrc
 CXX="-O3 -std=c++17 -fPIC -Iinclude -Ientreepy_amd/csrc $flags"
-for f in $(cd $SRCDIR && ls *.hip | sed s/.hip//); do $HIPCC $CXX --offload-arch=gfx950 -c entreepy_amd/csrc/$f.hip -o $out/$f.o & done
-for f in $(cd $SRCDIR && ls *.cpp | grep -v entreepy_cli | sed s/.cpp//); do $HIPCC $CXX -c entreepy_amd/csrc/$f.cpp -o $out/$f.o & done
+for f in $(cd $SRCDIR && ls *.hip | sed s/.hip//); do $HIPCC $CXX --offload-arch=gfx950 -c entreepy_amd/csrc/$f.hip -o $out/$f.hip.o & done
+for f in $(cd $SRCDIR && ls *.cpp | grep -v entreepy_cli | sed s/.cpp//); do $HIPCC $CXX -c entreepy_amd/csrc/$f.cpp -o $out/$f.cpp.o & done
 wait
 $HIPCC -shared -fPIC --offload-arch=gfx950 -o variants/libet_$name.so $out/*.o -lpthread -ldl
 echo "variants/libet_$name.so"
