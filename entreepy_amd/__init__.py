@@ -11,6 +11,7 @@ from .codec import (  # noqa: F401
     EmptyInputError,
     EncodeFlags,
     EntreepyError,
+    PackedResult,
     decode,
     default_context,
     encode,

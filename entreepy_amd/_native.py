@@ -89,6 +89,19 @@ class BatchItem(ctypes.Structure):
     ]
 
 
+class PackedResult(ctypes.Structure):
+    """struct et_packed_result: what et_encode_packed_device / et_decode_packed_device report about the whole batch."""
+
+    _fields_ = [
+        ("out_bytes", ctypes.c_uint64),
+        ("n_failed", ctypes.c_uint64),
+        ("first_failed", ctypes.c_uint64),
+        ("n_short", ctypes.c_uint64),
+        ("first_status", ctypes.c_int32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
 # int (*et_allgather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
@@ -134,6 +147,9 @@ SIGNATURES = {
     "et_batch_item_size": (_sz, []),
     "et_encode_shared_device": (ctypes.c_int, [_vp, _cbp, _vp, _vp, _vp, _sz]),
     "et_decode_shared_device": (ctypes.c_int, [_vp, _cbp, _vp, _vp, _vp, _sz]),
+    "et_packed_result_size": (_sz, []),
+    "et_encode_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, ctypes.POINTER(PackedResult)]),
+    "et_decode_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, ctypes.POINTER(PackedResult)]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),
@@ -214,6 +230,8 @@ def lib():
             import torch  # noqa: F401  (loads the process-wide HIP runtime)
         except ImportError:
             pass
-        L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        _lib = declare(L)
+        L = declare(ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL))
+        if L.et_packed_result_size() != ctypes.sizeof(PackedResult):
+            raise ImportError(f"{LIB_PATH}: et_packed_result is {L.et_packed_result_size()} bytes there, {ctypes.sizeof(PackedResult)} in this binding")
+        _lib = L
     return _lib

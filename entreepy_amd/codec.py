@@ -45,6 +45,16 @@ class DecodeFlags:  # decode.zig:7-11
     debug: bool = False
 
 
+@dataclass
+class PackedResult:  # struct et_packed_result, and the call's own status in front
+    status: int
+    out_bytes: int
+    n_failed: int
+    first_failed: int
+    n_short: int
+    first_status: int
+
+
 def _check(status, ctx=None):
     if status == N.ET_OK:
         return
@@ -426,6 +436,95 @@ class Context:
         """[bodies], [the records' lengths] -> [their texts], through one decode_shared_device call."""
         assert len(bodies) == len(lengths)
         return self._shared_host(self.decode_shared_device, codebook, bodies, "decode_shared", out_lens=lengths)
+
+    # -- packed record batches (et_encode_packed_device / et_decode_packed_device) ------------
+    @staticmethod
+    def _index_ptr(t, n=None):
+        """A device offsets array: a 1-D CUDA tensor of 8-byte integers (torch.int64 holds the u64 values), n + 1 entries."""
+        assert t.is_cuda and t.dim() == 1 and t.element_size() == 8 and t.is_contiguous() and not t.is_floating_point(), "an offsets array is a 1-D CUDA tensor of 64-bit integers"
+        assert t.numel() >= 1 and (n is None or t.numel() == n + 1), "an offsets array holds one entry more than there are records"
+        return t.data_ptr()
+
+    def _packed_result(self, status, res):
+        if status != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
+            _check(status, self._h)
+        return PackedResult(status, res.out_bytes, res.n_failed, res.first_failed, res.n_short, res.first_status)
+
+    def encode_packed_device(self, codebook, text, text_index, out, out_index, status=None):
+        """Record b: text[text_index[b] : text_index[b + 1]] -> its body under `codebook` at out[out_index[b] : out_index[b + 1]],
+        the bodies back to back from out_index[0] = 0; the scan that lays them out runs on the GPU.  text, out: uint8 CUDA tensors;
+        text_index (given), out_index (written): CUDA tensors of n + 1 64-bit integers; status: optional uint8 CUDA tensor of n
+        et_status bytes.  A failed record (a byte without a code, a record above batch small_max, a bad pair of offsets) takes no
+        bytes.  out=None: sizes only.  -> PackedResult; .status is ET_OK or ET_ERR_CAP (nothing written, .out_bytes = the room
+        needed); any other failure of the call raises.  Stream-ordered: the result is final, the tensors once the stream drained."""
+        n = text_index.numel() - 1
+        res = N.PackedResult()
+        self._bind()
+        rc = N.lib().et_encode_packed_device(self._h, ctypes.byref(codebook.raw), text.data_ptr(), text.numel(), self._index_ptr(text_index), n,
+                                             None if out is None else out.data_ptr(), 0 if out is None else out.numel(), self._index_ptr(out_index, n),
+                                             None if status is None else status.data_ptr(), ctypes.byref(res))
+        return self._packed_result(rc, res)
+
+    def decode_packed_device(self, codebook, bodies, body_index, text_index, out, written=None, status=None):
+        """Record b: text_index[b + 1] - text_index[b] symbols from bodies[body_index[b] : body_index[b + 1]] -> out[text_index[b] : ...].
+        The three arrays may be the encoder's own (bodies = its out, body_index = its out_index), or sub-ranges of the two
+        offsets arrays: records [i, j) are body_index[i : j + 1] and text_index[i : j + 1].  written: optional int32/uint32 CUDA
+        tensor of n counts; status as encode_packed_device.  -> PackedResult (.n_short: bodies that ended early)."""
+        n = text_index.numel() - 1
+        res = N.PackedResult()
+        self._bind()
+        rc = N.lib().et_decode_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                             out.data_ptr(), out.numel(), None if written is None else written.data_ptr(), None if status is None else status.data_ptr(),
+                                             ctypes.byref(res))
+        return self._packed_result(rc, res)
+
+    def _packed_upload(self, blob, index):
+        """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        d = torch.empty(max(blob.size, 1), dtype=torch.uint8, device=dev)
+        d[: blob.size] = torch.from_numpy(blob).to(dev)
+        return d, torch.from_numpy(np.ascontiguousarray(index, dtype=np.uint64).view(np.int64)).to(dev)
+
+    def encode_packed(self, codebook, texts):
+        """[bytes] -> (the bodies back to back as bytes, out_index as a numpy u64 array of len(texts) + 1): ONE encode_packed_device
+        call.  Raises EntreepyError naming the first item that failed (a byte the table has no code for)."""
+        import torch
+
+        texts = [np.frombuffer(bytes(t), dtype=np.uint8) for t in texts]
+        if not texts:
+            return b"", np.zeros(1, np.uint64)
+        index = np.concatenate(([0], np.cumsum([t.size for t in texts]))).astype(np.uint64)
+        d_text, d_index = self._packed_upload(np.concatenate(texts), index)
+        d_out = torch.empty(max(codebook.body_bound(int(index[-1])) + len(texts), 1), dtype=torch.uint8, device=d_text.device)  # (each body rounds up to a byte)
+        d_out_index = torch.empty(len(texts) + 1, dtype=torch.int64, device=d_text.device)
+        res = self.encode_packed_device(codebook, d_text, d_index, d_out, d_out_index)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"encode_packed: item {res.first_failed}")
+        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_out_index.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
+
+    def decode_packed(self, codebook, blob, out_index, lengths):
+        """The bodies back to back, their offsets (encode_packed's pair) and the records' lengths -> [their texts] (shorter where a
+        body ends early)."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        assert out_index.size == len(lengths) + 1
+        if not len(lengths):
+            return []
+        text_index = np.concatenate(([0], np.cumsum(np.asarray(lengths, dtype=np.uint64)))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+        d_out = torch.empty(max(int(text_index[-1]), 1), dtype=torch.uint8, device=d_blob.device)
+        d_written = torch.empty(len(lengths), dtype=torch.int32, device=d_blob.device)
+        res = self.decode_packed_device(codebook, d_blob, d_body_index, d_text_index, d_out, written=d_written)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"decode_packed: item {res.first_failed}")
+        host, written = d_out.cpu().numpy(), d_written.cpu().numpy()  # (a body that ends early gives the shorter text, as decode_shared)
+        return [host[int(a) : int(a) + int(w)].tobytes() for a, w in zip(text_index[:-1], written)]
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

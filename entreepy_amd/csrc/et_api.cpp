@@ -176,7 +176,7 @@ extern "C" void et_ctx_destroy(et_ctx *ctx) {
                       &ctx->sub_state, &ctx->blk_exit, &ctx->blk_count, &ctx->blk_off, &ctx->lut, &ctx->flag,
                       &ctx->worklist, &ctx->lane_maps, &ctx->blk_maps, &ctx->grp_maps, &ctx->blk_in, &ctx->grp_in, &ctx->row_scratch,
                       &ctx->tw_table, &ctx->tw_tree, &ctx->blk_start, &ctx->blk_pub, &ctx->chain_table, &ctx->io_in, &ctx->io_out,
-                      &ctx->batch_jobs, &ctx->batch_blob, &ctx->batch_counter};
+                      &ctx->batch_jobs, &ctx->batch_blob, &ctx->batch_counter, &ctx->packed_ws};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     delete ctx->io;

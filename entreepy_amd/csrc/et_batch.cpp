@@ -22,6 +22,16 @@
 // among them; a call returns only behind its last chunk's poll.  (That region is kept apart from the batch calls' because
 // et_encode_batch_device ends with uploads and a kernel nobody polls for.)  On the device, table and records are rewritten
 // in stream order behind the kernel that read them.
+//
+// The packed calls (et_encode_packed_device / et_decode_packed_device) take their records from u64 offset arrays ON THE DEVICE,
+// so there are no job records, no chunks and no host loop over the records:
+//   encode   table + zeroed counters -> one upload -> k_packed_count -> k_packed_scan -> (unless sizes only) k_packed_pack; (poll) the report
+//   decode   table + zeroed counters -> one upload -> k_packed_decode -> (poll) the report
+// The encode's report leaves with the scan: the pack kernel behind it decides from the offsets the scan stored whether the
+// bodies fit, so the host returns ET_ERR_CAP (or ET_OK) from the same figures without waiting for it.  The calls keep a third
+// region of the pinned block (table, counters' first values, report) and a device workspace of their own (ctx->packed_ws: table,
+// counters, one size word per record).  Both may be refilled without asking for the shared-table calls' reason: every call ends
+// with a poll for a kernel that runs behind its upload, and on the device everything is rewritten in stream order.
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -33,7 +43,7 @@ namespace {
 
 constexpr size_t CH = et::BATCH_CHUNK;
 // the pinned block
-constexpr size_t PIN_WORDS = 0;                                   // u64[8]: [0] k_batch_hist, [1] k_batch_heads, [2] k_batch_decode, [3] k_shared_*
+constexpr size_t PIN_WORDS = 0;                                   // u64[8]: [0] k_batch_hist, [1] k_batch_heads, [2] k_batch_decode, [3] k_shared_*, [4] k_packed_*
 constexpr size_t PIN_SPANS = 64;                                  // BatchSpan[CH]
 constexpr size_t PIN_JOBS = PIN_SPANS + CH * sizeof(et::BatchSpan);  // BatchEncJob / BatchDecJob [CH]
 constexpr size_t PIN_TOTALS = PIN_JOBS + CH * sizeof(et::BatchDecJob);
@@ -44,7 +54,15 @@ constexpr size_t SCH = et::SHARED_CHUNK;
 constexpr size_t PIN_SH_TABLE = PIN_BLOB + CH * et::BATCH_ENC_SLOT;  // 2 KiB: {left-aligned code, length} x 256, or the sorted codes
 constexpr size_t PIN_SH_JOBS = PIN_SH_TABLE + 2048;                  // SharedJob[SCH]
 constexpr size_t PIN_SH_RESULTS = PIN_SH_JOBS + SCH * sizeof(et::SharedJob);  // uint2[SCH]
-constexpr size_t PIN_BYTES = PIN_SH_RESULTS + SCH * 8;
+// ... and the packed calls': what goes up in one copy (table, then the counters' first values), and the report
+constexpr size_t PIN_PK_TABLE = PIN_SH_RESULTS + SCH * 8;  // 2 KiB, as PIN_SH_TABLE
+constexpr size_t PIN_PK_STATS = PIN_PK_TABLE + 2048;       // u64[PACKED_WORDS]
+constexpr size_t PIN_PK_REPORT = PIN_PK_STATS + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
+constexpr size_t PIN_BYTES = PIN_PK_REPORT + et::PACKED_WORDS * 8;
+static_assert(PIN_PK_TABLE % 16 == 0, "layout of the pinned block");
+// the packed calls' device workspace: the same table and counters, then a size word per record
+constexpr size_t PK_UPLOAD = 2048 + et::PACKED_WORDS * 8, PK_SIZES = 4096;
+static_assert(int(et::PACKED_OK) == int(ET_OK) && int(et::PACKED_ARG) == int(ET_ERR_ARG) && int(et::PACKED_UNSUPPORTED) == int(ET_ERR_UNSUPPORTED), "a record's status byte is its et_status");
 static_assert(sizeof(et::SharedJob) == 24 && PIN_SH_TABLE % 16 == 0, "layout of the pinned block");
 static_assert(sizeof(et::BatchSpan) == 16 && sizeof(et::BatchEncJob) == 32 && sizeof(et::BatchDecJob) == 40, "job records are plain, packed data");
 static_assert(et::BATCH_HEAD_STRIDE >= 1024 && PIN_BLOB % 16 == 0 && PIN_JOBS % 8 == 0, "layout of the pinned block");
@@ -105,6 +123,27 @@ int check_call(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items,
     return ET_OK;
 }
 
+// The 2 KiB a shared-table or packed kernel keeps in LDS: 256 x {left-aligned code, length} for an encode; the codes sorted by
+// left-aligned value, {code, length << 8 | symbol}, for a decode.  Returns how many codes there are.
+uint32_t fill_shared_table(const et_codebook *cb, uint32_t *tab, bool encode) {
+    uint32_t n_codes = 0;
+    if (encode) {
+        for (int s = 0; s < 256; ++s) {
+            const uint32_t len = cb->length[s];
+            tab[2 * s] = len ? et_left_aligned(cb->data[s], len) : 0u;
+            tab[2 * s + 1] = len;
+            n_codes += len != 0;
+        }
+    } else {
+        struct Code { uint32_t lo, meta; };
+        Code *codes = reinterpret_cast<Code *>(tab);
+        for (int s = 0; s < 256; ++s)
+            if (cb->length[s]) codes[n_codes++] = Code{et_left_aligned(cb->data[s], cb->length[s]), static_cast<uint32_t>(cb->length[s]) << 8 | static_cast<uint32_t>(s)};
+        std::sort(codes, codes + n_codes, [](const Code &a, const Code &b) { return a.lo < b.lo; });
+    }
+    return n_codes;
+}
+
 // Both shared-table calls.  encode: d_out may be null (sizes only).
 int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_out, et_batch_item *items, size_t n_items, bool encode) {
     if (!ctx) return ET_ERR_ARG;
@@ -133,20 +172,7 @@ int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_ou
 
     // the table: free to fill (this file's header), up in front of the first chunk
     uint32_t *tab = pin<uint32_t>(ctx, PIN_SH_TABLE);
-    uint32_t n_codes = 0;
-    if (encode) {
-        for (int s = 0; s < 256; ++s) {
-            const uint32_t len = cb->length[s];
-            tab[2 * s] = len ? et_left_aligned(cb->data[s], len) : 0u;
-            tab[2 * s + 1] = len;
-        }
-    } else {
-        struct Code { uint32_t lo, meta; };
-        Code *codes = reinterpret_cast<Code *>(tab);
-        for (int s = 0; s < 256; ++s)
-            if (cb->length[s]) codes[n_codes++] = Code{et_left_aligned(cb->data[s], cb->length[s]), static_cast<uint32_t>(cb->length[s]) << 8 | static_cast<uint32_t>(s)};
-        std::sort(codes, codes + n_codes, [](const Code &a, const Code &b) { return a.lo < b.lo; });
-    }
+    const uint32_t n_codes = fill_shared_table(cb, tab, encode);
     ET_HIP(hipMemcpyAsync(ctx->batch_blob.p, tab, 2048, hipMemcpyHostToDevice, ctx->stream));
 
     for (size_t c0 = 0; c0 < todo.size(); c0 += SCH) {
@@ -182,6 +208,44 @@ int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_ou
     return ET_OK;
 }
 
+// Both packed calls, up to the launch: the arguments, the table, the workspaces, the upload.  *go = false: the call is over
+// (an error, or n == 0) with the returned status.
+int packed_begin(et_ctx *ctx, const et_codebook *cb, const void *d_in, const void *d_out, const uint64_t *idx_a, const uint64_t *idx_b, size_t n, et_packed_result *res,
+                 bool encode, uint32_t *n_codes, bool *go) {
+    *go = false;
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_in || !idx_a || !idx_b || (!d_out && !encode)) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(idx_a) | reinterpret_cast<uintptr_t>(idx_b)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (n > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    *res = et_packed_result{};
+    if (n == 0) return ET_OK;
+    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    ET_TRY(ensure_batch(ctx, 1, 2048));
+    ET_TRY(ensure(ctx, ctx->packed_ws, PK_SIZES + (encode ? n * sizeof(uint32_t) : 0)));
+    *n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), encode);
+    uint64_t *first = pin<uint64_t>(ctx, PIN_PK_STATS);
+    std::memset(first, 0, et::PACKED_WORDS * 8);
+    first[et::PACKED_FIRST] = ~0ull;
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_UPLOAD, hipMemcpyHostToDevice, ctx->stream));
+    *go = true;
+    return ET_OK;
+}
+
+// ... and behind it: the poll, the report into *res.
+int packed_end(et_ctx *ctx, uint64_t epoch, et_packed_result *res) {
+    ET_HIP(hipGetLastError());
+    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the packed batch's report never reached the host"));
+    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+    res->out_bytes = rep[et::PACKED_BYTES];
+    res->n_failed = rep[et::PACKED_N_FAILED];
+    res->n_short = rep[et::PACKED_N_SHORT];
+    if (res->n_failed) {
+        res->first_failed = rep[et::PACKED_FIRST] >> 8;
+        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
+    }
+    return ET_OK;
+}
+
 // An item's own failure is the item's; a failure of the runtime under a delegated stream is the call's.
 bool call_level(int rc) { return rc == ET_ERR_HIP || rc == ET_ERR_NOMEM; }
 
@@ -197,6 +261,44 @@ extern "C" int et_encode_shared_device(et_ctx *ctx, const et_codebook *cb, const
 
 extern "C" int et_decode_shared_device(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {
     return shared_call(ctx, cb, d_in, d_out, items, n_items, false);
+}
+
+extern "C" size_t et_packed_result_size(void) { return sizeof(et_packed_result); }
+
+extern "C" int et_encode_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_text, size_t text_bytes, const uint64_t *d_text_index, size_t n, void *d_out,
+                                       size_t cap, uint64_t *d_out_index, uint8_t *d_status, et_packed_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    uint32_t n_codes = 0;
+    bool go = false;
+    ET_TRY(packed_begin(ctx, cb, d_text, d_out, d_text_index, d_out_index, n, res, true, &n_codes, &go));
+    if (!go) return ET_OK;
+    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
+    const uint64_t epoch = ++ctx->batch_epoch;
+    et::launch_packed_encode(ctx->stream, d_text, text_bytes, d_text_index, static_cast<uint32_t>(n), d_out, cap, d_out_index, d_status, reinterpret_cast<const uint2 *>(ws),
+                             reinterpret_cast<uint32_t *>(ws + PK_SIZES), reinterpret_cast<unsigned long long *>(ws + 2048),
+                             reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
+    ET_TRY(packed_end(ctx, epoch, res));
+    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the bodies take more than cap bytes");  // (k_packed_pack saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" int et_decode_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                       const uint64_t *d_text_index, size_t n, void *d_out, size_t cap, uint32_t *d_written, uint8_t *d_status, et_packed_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    uint32_t n_codes = 0;
+    bool go = false;
+    ET_TRY(packed_begin(ctx, cb, d_bodies, d_out, d_body_index, d_text_index, n, res, false, &n_codes, &go));
+    if (!go) return ET_OK;
+    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
+    const uint64_t epoch = ++ctx->batch_epoch;
+    et::launch_packed_decode(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n), d_out, cap, reinterpret_cast<const uint2 *>(ws), n_codes,
+                             d_written, d_status, reinterpret_cast<unsigned long long *>(ws + 2048), reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)),
+                             static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 4), epoch);
+    ET_TRY(packed_end(ctx, epoch, res));
+    if (res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "text_index[n] lies beyond cap");  // (k_packed_decode saw the same two figures)
+    return ET_OK;
 }
 
 extern "C" int et_encode_batch_device(et_ctx *ctx, const void *d_in, void *d_out, et_batch_item *items, size_t n_items) {

@@ -78,4 +78,22 @@ void launch_shared_encode(hipStream_t stream, const void *d_in, void *d_out, con
 void launch_shared_decode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *codes,
                           uint32_t n_codes, uint2 *host_results, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
 
+// The packed calls (et_encode_packed_device / et_decode_packed_device): the shared-table kernels with their jobs read from
+// u64 offset arrays on the device.  What a record's status byte holds is its et_status itself (et_batch.cpp asserts the values).
+enum PackedStatus : uint32_t { PACKED_OK = 0, PACKED_ARG = 6, PACKED_UNSUPPORTED = 7 };
+// The words of the counters in device memory (`stats`; the host uploads {0, ~0, 0} in front of a call) and of the report in
+// pinned memory (`host_result`): PACKED_FIRST = the lowest failed record << 8 | its status.
+enum PackedWord { PACKED_BYTES = 0, PACKED_N_FAILED = 1, PACKED_FIRST = 2, PACKED_N_SHORT = 3, PACKED_WORDS = 8 };
+constexpr uint32_t PACKED_SCAN_TILE = 4096;  // records per trip of k_packed_scan's one workgroup
+
+// k_packed_count, k_packed_scan and -- unless d_out is null: sizes only -- k_packed_pack, in stream order.  sizes: n words of
+// workspace.  The report (host_result, then `epoch` into *host_done) leaves with the scan, in front of the pack.
+void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_bytes, const uint64_t *text_index, uint32_t n, void *d_out, uint64_t cap,
+                          uint64_t *out_index, uint8_t *d_status, const uint2 *table, uint32_t *sizes, unsigned long long *stats,
+                          unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
+// k_packed_decode.  codes as launch_shared_decode's; counter as above.
+void launch_packed_decode(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n, void *d_out,
+                          uint64_t cap, const uint2 *codes, uint32_t n_codes, uint32_t *d_written, uint8_t *d_status, unsigned long long *stats,
+                          unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
+
 }  // namespace et

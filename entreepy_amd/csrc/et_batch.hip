@@ -11,6 +11,12 @@
 //   encode   k_shared_encode count pass (length, uncoded bytes, capacity), then k_batch_encode's rounds: the body alone, at any
 //            output alignment, not a byte beyond it
 //   decode   k_shared_decode k_batch_decode's stream loop under that one table
+// and of the packed calls: the shared-table kernels with their jobs read from u64 offset arrays on the device, each record judged
+// from its own pair of entries, and the bodies laid back to back by a scan on the device:
+//   encode   k_packed_count  k_shared_encode's count pass alone: body bytes per record into a workspace, its status
+//            k_packed_scan   ONE workgroup, a loop over tiles of 4096 records: sizes -> u64 offsets, the total, the report to the host
+//            k_packed_pack   k_shared_encode's pack pass alone, destination and length from the offsets the scan stored
+//   decode   k_packed_decode k_shared_decode's loop; counters in device memory, the last workgroup reports them
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -65,6 +71,24 @@ __device__ __forceinline__ Chunk16 load16(const uint8_t *__restrict__ base, uint
         }
     }
     return c;
+}
+
+// block_exclusive_scan in u64 (k_packed_scan: a tile of body sizes can reach 2^32).  `scratch` is 4 LDS words of 8 bytes; ONE
+// barrier, and the caller separates two calls by another.
+__device__ __forceinline__ uint64_t block_exclusive_scan64(uint64_t x, uint64_t *scratch, uint64_t *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t inc = wave_inclusive_scan64(x);
+    if (lane == 63) scratch[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint64_t v = scratch[w];
+        if (w < wave) before += v;
+        sum += v;
+    }
+    *total = sum;
+    return before + (inc - x);
 }
 
 }  // namespace
@@ -404,6 +428,53 @@ __device__ __forceinline__ void store_image_word(uint8_t *line, uint32_t g, uint
     }
 }
 
+// The count pass of a text that occupies [lo, hi) from its 16-byte aligned base (k_shared_encode, k_packed_count): the bytes
+// its body takes, and *uncoded = whether a byte of it has no code (the same for every lane).  Ends with a barrier: s_wsum is
+// free for the next scan.
+__device__ __forceinline__ uint32_t count_body(const uint8_t *__restrict__ base, uint64_t lo, uint64_t hi, const uint2 *s_tab, uint32_t *s_wsum, int *uncoded) {
+    uint32_t bits = 0;
+    int none = 0;
+    for (uint64_t off = static_cast<uint64_t>(threadIdx.x) * 16; off < hi; off += ROUND_BYTES) {
+        const Chunk16 c = load16(base, off, lo, hi);
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (c.valid & (1u << k)) {
+                const uint32_t len = s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu].y;
+                bits += len;
+                none |= !len;
+            }
+    }
+    uint32_t total;
+    (void)block_exclusive_scan(bits, s_wsum, &total);
+    *uncoded = __syncthreads_or(none);  // (and the barrier between this scan and the next one's s_wsum)
+    return (total + 7) >> 3;
+}
+
+// The pack pass of that text (k_shared_encode, k_packed_pack): its body, `bytes` long, to dst at any alignment -- image bytes
+// [lead, end_byte) of the aligned line are the body, and all that is stored.  s_stage is zero on entry and on return.
+__device__ __forceinline__ void pack_body(const uint8_t *__restrict__ base, uint64_t lo, uint64_t hi, uint8_t *__restrict__ dst, uint32_t bytes, const uint2 *s_tab,
+                                          uint32_t *s_stage, uint32_t *s_wsum) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3), end_byte = lead + bytes;
+    uint8_t *line = dst - lead;
+    uint32_t pending = 0, carry = lead * 8;  // image bits written so far
+    for (uint64_t r0 = 0; r0 < hi; r0 += ROUND_BYTES) {
+        const Chunk16 c = load16(base, r0 + static_cast<uint64_t>(tid) * 16, lo, hi);
+        const uint32_t round_bits = pack_round(c, s_tab, s_stage, s_wsum, carry, pending);
+        __syncthreads();
+        const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
+        pending = (t_bits & 31) ? s_stage[full] : 0u;
+        __syncthreads();
+        for (uint32_t i = tid; i <= full; i += BB) {
+            if (i < full) store_image_word(line, w0 + i, __builtin_bswap32(s_stage[i]), lead, end_byte);
+            s_stage[i] = 0;
+        }
+        carry += round_bits;
+        __syncthreads();
+    }
+    if (tid == 0 && (carry & 31)) store_image_word(line, carry >> 5, __builtin_bswap32(pending), lead, end_byte);
+}
+
 __global__ __launch_bounds__(BB) void k_shared_encode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const SharedJob *__restrict__ jobs,
                                                       uint32_t n, const uint2 *__restrict__ table, uint2 *__restrict__ host_results,
                                                       uint32_t *__restrict__ counter, unsigned long long *__restrict__ host_done, unsigned long long epoch) {
@@ -420,45 +491,12 @@ __global__ __launch_bounds__(BB) void k_shared_encode(const uint8_t *__restrict_
         const uint8_t *base = reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15));
         const uint64_t lo = a & 15, hi = lo + job.in_len;
         // the count pass
-        uint32_t bits = 0;
-        int uncoded = 0;
-        for (uint64_t off = static_cast<uint64_t>(tid) * 16; off < hi; off += ROUND_BYTES) {
-            const Chunk16 c = load16(base, off, lo, hi);
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (c.valid & (1u << k)) {
-                    const uint32_t len = s_tab[(c.w[k >> 2] >> (8 * (k & 3))) & 0xffu].y;
-                    bits += len;
-                    uncoded |= !len;
-                }
-        }
-        uint32_t total;
-        (void)block_exclusive_scan(bits, s_wsum, &total);
-        uncoded = __syncthreads_or(uncoded);  // (and the barrier between this scan and the next one's s_wsum)
-        const uint32_t bytes = (total + 7) >> 3;
+        int uncoded;
+        const uint32_t bytes = count_body(base, lo, hi, s_tab, s_wsum, &uncoded);
         const uint32_t status = uncoded ? SHARED_UNCODED : bytes > job.cap ? SHARED_CAP : SHARED_OK;
         if (tid == 0) host_results[j] = make_uint2(status == SHARED_OK ? bytes : 0u, status);
         if (status != SHARED_OK || !d_out || !bytes) continue;  // (the same for every lane)
-        // the pack pass
-        uint8_t *dst = d_out + job.out_off;
-        const uint32_t lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3), end_byte = lead + bytes;  // image bytes [lead, end_byte) are the body
-        uint8_t *line = dst - lead;
-        uint32_t pending = 0, carry = lead * 8;  // image bits written so far
-        for (uint64_t r0 = 0; r0 < hi; r0 += ROUND_BYTES) {
-            const Chunk16 c = load16(base, r0 + static_cast<uint64_t>(tid) * 16, lo, hi);
-            const uint32_t round_bits = pack_round(c, s_tab, s_stage, s_wsum, carry, pending);
-            __syncthreads();
-            const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
-            pending = (t_bits & 31) ? s_stage[full] : 0u;
-            __syncthreads();
-            for (uint32_t i = tid; i <= full; i += BB) {
-                if (i < full) store_image_word(line, w0 + i, __builtin_bswap32(s_stage[i]), lead, end_byte);
-                s_stage[i] = 0;
-            }
-            carry += round_bits;
-            __syncthreads();
-        }
-        if (tid == 0 && (carry & 31)) store_image_word(line, carry >> 5, __builtin_bswap32(pending), lead, end_byte);
+        pack_body(base, lo, hi, d_out + job.out_off, bytes, s_tab, s_stage, s_wsum);
     }
     batch_done(counter, host_done, epoch);
 }
@@ -485,7 +523,215 @@ __global__ __launch_bounds__(BB) void k_shared_decode(const uint8_t *__restrict_
 }
 
 // --------------------------------------------------------------------------------
+// The packed calls.  Record j is bytes [index[j], index[j + 1]) of a dense buffer, and that pair of entries is all that is
+// believed about it: a pair that decreases or leaves the buffer fails its record (PACKED_ARG) before a byte is read.
+// What failed is counted per workgroup in thread 0's registers and added to PackedStats in device memory once, at the end.
+// --------------------------------------------------------------------------------
+struct PackedTally {  // thread 0's
+    unsigned long long failed = 0, first = ~0ull, n_short = 0;
+    __device__ __forceinline__ void note(uint32_t j, uint32_t status) {
+        if (!status) return;
+        ++failed;
+        const unsigned long long key = static_cast<unsigned long long>(j) << 8 | status;  // (j ascends: the first is the lowest)
+        if (key < first) first = key;
+    }
+    __device__ __forceinline__ void add_to(unsigned long long *stats) const {
+        if (failed) {
+            atomicAdd(stats + PACKED_N_FAILED, failed);
+            atomicMin(stats + PACKED_FIRST, first);
+        }
+        if (n_short) atomicAdd(stats + PACKED_N_SHORT, n_short);
+    }
+};
+
+// k_packed_count: the table in LDS once, then per record k_shared_encode's count pass.  sizes[j] = bytes of body (0 for a
+// record that failed, or is empty), d_status[j] (may be null) = its et_status.  LDS 2 KiB.
+__global__ __launch_bounds__(BB) void k_packed_count(const uint8_t *__restrict__ d_text, uint64_t text_bytes, const uint64_t *__restrict__ text_index, uint32_t n,
+                                                     const uint2 *__restrict__ table, uint32_t *__restrict__ sizes, uint8_t *__restrict__ d_status,
+                                                     unsigned long long *__restrict__ stats) {
+    __shared__ uint2 s_tab[256];
+    __shared__ uint32_t s_wsum[4];
+    const int tid = threadIdx.x;
+    s_tab[tid] = table[tid];
+    __syncthreads();
+    PackedTally tally;
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const uint64_t t0 = text_index[j], t1 = text_index[j + 1];
+        uint32_t status = PACKED_OK, bytes = 0;
+        if (!(t0 <= t1 && t1 <= text_bytes)) {
+            status = PACKED_ARG;
+        } else if (t1 - t0 > BATCH_SMALL_MAX) {
+            status = PACKED_UNSUPPORTED;
+        } else if (t1 > t0) {  // (the same for every lane, like every branch above)
+            const uintptr_t a = reinterpret_cast<uintptr_t>(d_text) + t0;
+            const uint64_t lo = a & 15, hi = lo + (t1 - t0);
+            int uncoded;
+            bytes = count_body(reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15)), lo, hi, s_tab, s_wsum, &uncoded);
+            if (uncoded) {
+                status = PACKED_UNSUPPORTED;
+                bytes = 0;
+            }
+        }
+        if (tid == 0) {
+            sizes[j] = bytes;
+            if (d_status) d_status[j] = static_cast<uint8_t>(status);
+            tally.note(j, status);
+        }
+    }
+    if (tid == 0) tally.add_to(stats);
+}
+
+// k_packed_scan: ONE workgroup; per trip a tile of 4096 sizes, 16 consecutive ones per lane, becomes 4096 u64 offsets (an
+// exclusive scan, the tiles before carried in a register); the total goes to out_index[n].  The trip count is n / 4096, fixed
+// by the host.  Thread 0 then reports to the host: {total, records that failed, the first of them << 8 | its status} and the
+// epoch.  k_packed_pack, enqueued behind, takes everything it needs from out_index: the host does not wait in between.
+__global__ __launch_bounds__(BB) void k_packed_scan(const uint32_t *__restrict__ sizes, uint32_t n, uint64_t *__restrict__ out_index,
+                                                    const unsigned long long *__restrict__ stats, unsigned long long *__restrict__ host_result,
+                                                    unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    __shared__ uint64_t s_sum[4];
+    const uint32_t tid = threadIdx.x;
+    uint64_t carry = 0;
+    for (uint32_t tile = 0; tile < n; tile += PACKED_SCAN_TILE) {
+        const uint32_t i0 = tile + tid * 16;
+        uint32_t v[16];
+        if (i0 + 16 <= n) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint4 x = reinterpret_cast<const uint4 *>(sizes + i0)[q];
+                v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = i0 + k < n ? sizes[i0 + k] : 0u;
+        }
+        uint64_t mine = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) mine += v[k];
+        uint64_t total;
+        uint64_t at = carry + block_exclusive_scan64(mine, s_sum, &total);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (i0 + k < n) out_index[i0 + k] = at;
+            at += v[k];
+        }
+        carry += total;
+        __syncthreads();  // (s_sum: between two scans)
+    }
+    if (tid == 0) {
+        out_index[n] = carry;
+        host_result[PACKED_BYTES] = carry;
+        host_result[PACKED_N_FAILED] = stats[PACKED_N_FAILED];
+        host_result[PACKED_FIRST] = stats[PACKED_FIRST];
+        host_result[PACKED_N_SHORT] = 0;
+        hand_over(host_done, epoch);
+    }
+}
+
+// k_packed_pack: k_shared_encode's pack pass; record j's body goes to d_out[out_index[j], out_index[j + 1]), and a record
+// that takes no bytes (empty, or failed in k_packed_count) is passed over without a look at its text.  No count pass: the
+// length comes from the scan.  Every workgroup returns at once when the bodies do not fit: ET_ERR_CAP writes nothing.
+// LDS as k_batch_encode.
+__global__ __launch_bounds__(BB) void k_packed_pack(const uint8_t *__restrict__ d_text, uint64_t text_bytes, const uint64_t *__restrict__ text_index, uint32_t n,
+                                                    uint8_t *__restrict__ d_out, uint64_t cap, const uint64_t *__restrict__ out_index, const uint2 *__restrict__ table) {
+    __shared__ uint2 s_tab[256];
+    __shared__ uint32_t s_stage[ENC_STAGE_WORDS];
+    __shared__ uint32_t s_wsum[4];
+    const int tid = threadIdx.x;
+    if (out_index[n] > cap) return;
+    s_tab[tid] = table[tid];
+    for (uint32_t i = tid; i < ENC_STAGE_WORDS; i += BB) s_stage[i] = 0;
+    __syncthreads();
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        const uint64_t o0 = out_index[j], o1 = out_index[j + 1];
+        if (o1 <= o0) continue;
+        const uint64_t t0 = text_index[j], t1 = text_index[j + 1];
+        if (!(t0 < t1 && t1 <= text_bytes && t1 - t0 <= BATCH_SMALL_MAX)) continue;  // (k_packed_count gave such a record no bytes; asked again, for what is read below)
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_text) + t0;
+        const uint64_t lo = a & 15, hi = lo + (t1 - t0);
+        pack_body(reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15)), lo, hi, d_out + o0, static_cast<uint32_t>(o1 - o0), s_tab, s_stage, s_wsum);
+    }
+}
+
+// k_packed_decode: k_shared_decode with record j's job made here: text_index[j + 1] - text_index[j] symbols from the body
+// d_bodies[body_index[j], body_index[j + 1]) to d_out + text_index[j].  d_written[j] (may be null) = symbols stored, d_status[j]
+// (may be null) = its et_status.  Nothing is decoded when text_index[n] > cap (the host returns ET_ERR_CAP from the report).
+// The last workgroup to finish reports {text_index[n], failed, first << 8 | status, short} and the epoch.  LDS as k_batch_decode.
+__global__ __launch_bounds__(BB) void k_packed_decode(const uint8_t *__restrict__ d_bodies, uint64_t body_bytes, const uint64_t *__restrict__ body_index,
+                                                      const uint64_t *__restrict__ text_index, uint32_t n, uint8_t *__restrict__ d_out, uint64_t cap,
+                                                      const uint2 *__restrict__ codes, uint32_t n_codes, uint32_t *__restrict__ d_written, uint8_t *__restrict__ d_status,
+                                                      unsigned long long *__restrict__ stats, unsigned long long *__restrict__ host_result, uint32_t *__restrict__ counter,
+                                                      unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    __shared__ BatchDecLds s;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t out_bytes = text_index[n];
+    PackedTally tally;
+    if (out_bytes <= cap) {
+        if (tid < n_codes) s.codes[tid] = codes[tid];
+        __syncthreads();
+        fill_lut(s, n_codes);
+        for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+            const uint64_t b0 = body_index[j], b1 = body_index[j + 1], t0 = text_index[j], t1 = text_index[j + 1];
+            uint32_t status = PACKED_OK, done = 0;
+            if (!(b0 <= b1 && b1 <= body_bytes && t0 <= t1 && t1 <= cap)) {
+                status = PACKED_ARG;
+            } else if (t1 == t0 || b1 == b0) {  // decodes to nothing, as in the shared-table call; an empty body is a short one
+                if (tid == 0 && t1 > t0) ++tally.n_short;
+            } else if (t1 - t0 > BATCH_SMALL_MAX) {
+                status = PACKED_UNSUPPORTED;
+            } else {
+                const uint32_t count = static_cast<uint32_t>(t1 - t0);
+                // (count codewords of at most 32 bits end within 4 count bytes: decode_stream's bit positions stay small)
+                const uint64_t most = static_cast<uint64_t>(count) * 4 + 8;
+                const uint32_t len = static_cast<uint32_t>(b1 - b0 < most ? b1 - b0 : most);
+                done = decode_stream(s, n_codes, d_bodies, d_out, b0, t0, len, count, count);
+                if (tid == 0 && done < count) ++tally.n_short;
+            }
+            if (tid == 0) {
+                if (d_written) d_written[j] = done;
+                if (d_status) d_status[j] = static_cast<uint8_t>(status);
+                tally.note(j, status);
+            }
+        }
+    }
+    // the report: every workgroup's counts are in `stats` before its tick of the counter; the last one reads them back
+    if (tid == 0) {
+        tally.add_to(stats);  // (device-scope atomics, like the tick and the read-back below: no cache in between)
+        __threadfence();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the counts have landed before the tick leaves
+        const uint32_t before = atomicAdd(counter, 1u);
+        if (before == gridDim.x - 1) {
+            __threadfence();
+            atomicExch(counter, 0u);
+            host_result[PACKED_BYTES] = out_bytes;
+            host_result[PACKED_N_FAILED] = atomicAdd(stats + PACKED_N_FAILED, 0ull);
+            host_result[PACKED_FIRST] = atomicMin(stats + PACKED_FIRST, ~0ull);
+            host_result[PACKED_N_SHORT] = atomicAdd(stats + PACKED_N_SHORT, 0ull);
+            hand_over(host_done, epoch);
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
+
+void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_bytes, const uint64_t *text_index, uint32_t n, void *d_out, uint64_t cap,
+                          uint64_t *out_index, uint8_t *d_status, const uint2 *table, uint32_t *sizes, unsigned long long *stats,
+                          unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
+    const uint8_t *text = static_cast<const uint8_t *>(d_text);
+    hipLaunchKernelGGL(k_packed_count, dim3(batch_grid(n)), dim3(BB), 0, stream, text, text_bytes, text_index, n, table, sizes, d_status, stats);
+    hipLaunchKernelGGL(k_packed_scan, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(sizes), n, out_index, static_cast<const unsigned long long *>(stats), host_result,
+                       host_done, epoch);
+    if (d_out)
+        hipLaunchKernelGGL(k_packed_pack, dim3(n < SHARED_ENC_GRID ? n : SHARED_ENC_GRID), dim3(BB), 0, stream, text, text_bytes, text_index, n, static_cast<uint8_t *>(d_out), cap,
+                           static_cast<const uint64_t *>(out_index), table);
+}
+
+void launch_packed_decode(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n, void *d_out,
+                          uint64_t cap, const uint2 *codes, uint32_t n_codes, uint32_t *d_written, uint8_t *d_status, unsigned long long *stats,
+                          unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
+    hipLaunchKernelGGL(k_packed_decode, dim3(n < SHARED_DEC_GRID ? n : SHARED_DEC_GRID), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), body_bytes, body_index, text_index,
+                       n, static_cast<uint8_t *>(d_out), cap, codes, n_codes, d_written, d_status, stats, host_result, counter, host_done, epoch);
+}
 
 void launch_shared_encode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *table,
                           uint2 *host_results, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {

@@ -288,6 +288,55 @@ int et_decode_shared_device(et_ctx *ctx, const et_codebook *cb, const void *d_in
 int et_codebook_is_complete(const et_codebook *cb);
 size_t et_body_bound(const et_codebook *cb, size_t n);
 
+/* PACKED record batches: the same bodies under the same one table, but input and output are both what a record store keeps --
+ * dense bytes plus n + 1 offsets of 64 bits, all in device memory -- and the offsets of the bodies are computed on the GPU.
+ * One call where the shared-table calls need a sizes-only call, a prefix sum on the host and a writing call; no per-record
+ * structs on the host at all.  Passing a sub-range of the offsets decodes that sub-range of the records (random access).
+ * All d_* pointers are device pointers on the ctx's GPU.  The offset arrays hold n + 1 entries and must be 8-byte aligned; the
+ * data pointers may have any alignment.  Each record is judged from its own pair of entries: a pair that decreases or
+ * leaves its buffer fails that record alone (ET_ERR_ARG), and no kernel reads or writes where such a pair points.
+ *   encode: record b = d_text[text_index[b], text_index[b+1]) -> exactly the bytes the shared-table encode gives for it, at
+ *     d_out[out_index[b], out_index[b+1]); out_index[0] = 0, the bodies lie back to back, nothing at or beyond
+ *     d_out + out_index[n] is written.  A failed record takes no bytes (out_index[b+1] == out_index[b]); d_status[b] (one
+ *     et_status byte per record; d_status may be NULL) says why: ET_ERR_UNSUPPORTED for a byte without a code or a record above
+ *     the small-stream limit, ET_ERR_ARG unless text_index[b] <= text_index[b+1] <= text_bytes.  An empty record: ET_OK, no bytes.
+ *     d_out == NULL: sizes only -- d_out_index, d_status and *res are the writing call's, cap is ignored.
+ *     out_index[n] > cap: the call returns ET_ERR_CAP, not a byte of d_out is written, d_out_index is still complete and
+ *     res->out_bytes is the room needed.
+ *   decode: record b = text_index[b+1] - text_index[b] symbols from d_bodies[body_index[b], body_index[b+1]) to
+ *     d_out + text_index[b]: the text offsets are the store's record lengths and lay the output out.  d_written[b] (may be
+ *     NULL) = symbols stored; nothing outside [text_index[b], text_index[b] + written[b]) is written for any record.  A body
+ *     that ends early: ET_OK with fewer symbols, counted in n_short, the rest of its room untouched.  An empty body or a
+ *     count of zero: ET_OK, nothing written -- so a record the encoder failed (kept raw elsewhere) leaves its room alone
+ *     (an empty body under a count above zero ended early like any other: n_short counts it).
+ *     ET_ERR_ARG unless body_index[b] <= body_index[b+1] <= body_bytes and text_index[b] <= text_index[b+1] <= cap;
+ *     ET_ERR_UNSUPPORTED for a count above the small-stream limit.  text_index[n] > cap: the call returns ET_ERR_CAP and
+ *     nothing is written (d_written and d_status neither).
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, input pointer or offset array; a null d_out_index on encode; a null
+ * d_out on decode; a misaligned offset array; n > 0x7fffffff), ET_ERR_UNSUPPORTED (the table is not complete: nothing is
+ * enqueued), ET_ERR_CAP, ET_ERR_HIP, ET_ERR_NOMEM.  n == 0: ET_OK, nothing enqueued, *res zeroed.  Stream-ordered like the other
+ * device calls: *res is final on return, the device arrays once the ctx's stream has drained.  Packed and shared-table calls
+ * may follow each other on one ctx, with different tables, with nothing in between. */
+typedef struct et_packed_result {
+    uint64_t out_bytes;     /* encode: out_index[n] = bytes the bodies take, also when the call returns ET_ERR_CAP or d_out is NULL;
+                               decode: text_index[n] */
+    uint64_t n_failed;      /* records whose status is not ET_OK */
+    uint64_t first_failed;  /* the lowest such record (valid when n_failed > 0) */
+    uint64_t n_short;       /* decode: ET_OK records whose body ended before their symbol count; encode: 0 */
+    int32_t first_status;   /* et_status of record first_failed */
+    uint32_t pad;
+} et_packed_result;
+size_t et_packed_result_size(void);
+int et_encode_packed_device(et_ctx *ctx, const et_codebook *cb,
+                            const void *d_text, size_t text_bytes, const uint64_t *d_text_index, size_t n,
+                            void *d_out, size_t cap, uint64_t *d_out_index, uint8_t *d_status,
+                            et_packed_result *res);
+int et_decode_packed_device(et_ctx *ctx, const et_codebook *cb,
+                            const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                            const uint64_t *d_text_index, size_t n,
+                            void *d_out, size_t cap, uint32_t *d_written, uint8_t *d_status,
+                            et_packed_result *res);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

@@ -12,6 +12,11 @@ process of its own so that every leg loads exactly one build of the library:
                   under ONE table built from the histogram of the whole shape's text, each body in a slot of et_body_bound bytes.
                   Also reports what the records take: body_bytes (all bodies), header_bytes (the one header that stores the
                   table) -- against the batch leg's image_bytes (all per-stream .et images).
+  packed          et_encode_packed_device / et_decode_packed_device, one call per shape, on this tree's library: text and bodies
+                  dense, u64 offsets on the device, under the shared leg's table.  With it runs packed_baseline, what the packed
+                  encode replaces -- a sizes-only et_encode_shared_device, a prefix sum on the host, the writing call into the dense
+                  layout -- and et_decode_shared_device out of that layout, on this tree's library or on the one named by
+                  --batch-lib (a build of the commit before the packed calls).
 --legs picks the legs (default: all).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
@@ -19,6 +24,7 @@ text once before timing.  One JSON line on stdout (and into --out).
 
     python tools/batch_bench.py --parent-lib /path/to/parent/libentreepy_hip.so --out profiles/batch_bench.json
     python tools/batch_bench.py --legs batch,shared --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/shared_bench.json
+    python tools/batch_bench.py --legs packed --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/packed_bench.json
 """
 import argparse
 import ctypes
@@ -45,7 +51,9 @@ def _leg(leg, lib_path):
     names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_encode_bound", "et_encode_device", "et_decode_device", "et_last_error"]
     if leg == "batch":
         names += ["et_encode_batch_device", "et_decode_batch_device"]
-    if leg == "shared":
+    if leg == "packed":
+        names += ["et_encode_packed_device", "et_decode_packed_device"]
+    if leg in ("shared", "packed", "dense"):
         names += ["et_encode_shared_device", "et_decode_shared_device", "et_build_codebook", "et_write_header", "et_body_bound", "et_codebook_is_complete"]
     L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)  # (torch is imported: the process-wide HIP runtime is loaded)
     dev = torch.device("cuda", 0)
@@ -56,7 +64,7 @@ def _leg(leg, lib_path):
     for count, size in SHAPES:
         text = corpus.text_like_torch(count * size, 0xB47C4 + size, dev)
         bound = L.et_encode_bound(size)
-        if leg == "shared":  # one table for the whole shape, from the histogram of all of its text
+        if leg in ("shared", "packed", "dense"):  # one table for the whole shape, from the histogram of all of its text
             hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
             cb = N.Codebook()
             assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
@@ -75,9 +83,26 @@ def _leg(leg, lib_path):
 
         if leg == "shared":  # (bodies: nothing to skip in front of them, and out_cap is the record's length)
             items_d["in_off"], items_d["out_cap"] = idx * bound, size
+        if leg == "dense":  # (text and symbols dense; where the bodies lie comes out of encode_all's prefix sum)
+            items_d["out_off"], items_d["out_cap"] = idx * size, size
+        if leg == "packed":
+            text_index = torch.arange(count + 1, dtype=torch.int64, device=dev) * size
+            out_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+            res = N.PackedResult()
 
         def encode_all():
-            if leg == "shared":
+            if leg == "packed":
+                assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), count * size, text_index.data_ptr(), count, enc.data_ptr(), count * bound,
+                                                 out_index.data_ptr(), None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                assert res.n_failed == 0
+                enc_len[0] = res.out_bytes
+            elif leg == "dense":  # sizes only, the prefix sum, the writing call
+                assert L.et_encode_shared_device(h, ctypes.byref(cb), text.data_ptr(), None, items_e.ctypes.data, count) == 0, L.et_last_error(h)
+                items_e["out_cap"] = items_e["out_len"]
+                items_e["out_off"][1:] = np.cumsum(items_e["out_len"][:-1])
+                assert L.et_encode_shared_device(h, ctypes.byref(cb), text.data_ptr(), enc.data_ptr(), items_e.ctypes.data, count) == 0, L.et_last_error(h)
+                enc_len[:] = items_e["out_len"]
+            elif leg == "shared":
                 assert L.et_encode_shared_device(h, ctypes.byref(cb), text.data_ptr(), enc.data_ptr(), items_e.ctypes.data, count) == 0, L.et_last_error(h)
                 enc_len[:] = items_e["out_len"]
             elif leg == "batch":
@@ -89,7 +114,15 @@ def _leg(leg, lib_path):
                     enc_len[i] = n.value
 
         def decode_all():
-            if leg == "shared":
+            if leg == "packed":
+                assert L.et_decode_packed_device(h, ctypes.byref(cb), enc.data_ptr(), count * bound, out_index.data_ptr(), text_index.data_ptr(), count, dec.data_ptr(),
+                                                 count * size, None, None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                assert res.n_failed == 0 and res.n_short == 0
+            elif leg == "dense":
+                items_d["in_off"], items_d["in_len"] = items_e["out_off"], enc_len
+                assert L.et_decode_shared_device(h, ctypes.byref(cb), enc.data_ptr(), dec.data_ptr(), items_d.ctypes.data, count) == 0, L.et_last_error(h)
+                assert not items_d["status"].any() and (items_d["out_len"] == size).all()
+            elif leg == "shared":
                 items_d["in_len"] = enc_len
                 assert L.et_decode_shared_device(h, ctypes.byref(cb), enc.data_ptr(), dec.data_ptr(), items_d.ctypes.data, count) == 0, L.et_last_error(h)
                 assert not items_d["status"].any() and (items_d["out_len"] == size).all()
@@ -104,10 +137,13 @@ def _leg(leg, lib_path):
         encode_all()
         decode_all()
         torch.cuda.synchronize()
-        assert torch.equal(dec[: count * (size + 16)].view(count, size + 16)[:, :size].reshape(-1), text), "decoded bytes differ from the text"
-        if leg in ("batch", "shared"):
+        if leg in ("packed", "dense"):
+            assert torch.equal(dec[: count * size], text), "decoded bytes differ from the text"
+        else:
+            assert torch.equal(dec[: count * (size + 16)].view(count, size + 16)[:, :size].reshape(-1), text), "decoded bytes differ from the text"
+        if leg in ("batch", "shared", "dense"):
             assert not items_e["status"].any() and not items_e["path"].any() and not items_d["path"].any()
-        sizes = {"image_bytes": int(enc_len.sum())} if leg != "shared" else {"body_bytes": int(enc_len.sum()), "header_bytes": int(head_len.value)}
+        sizes = {"image_bytes": int(enc_len.sum())} if leg in ("single", "batch") else {"body_bytes": int(enc_len.sum()), "header_bytes": int(head_len.value)}
         enc_ms, dec_ms = [], []
         for rep in range(WARMUP + REPS):
             e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
@@ -136,7 +172,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed")
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
     ap.add_argument("--lib")
@@ -146,6 +182,8 @@ def main():
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
     legs = ([("single_parent", "single", a.parent_lib)] if a.parent_lib else []) + [("single", "single", here), ("batch", "batch", a.batch_lib or here), ("shared", "shared", here)]
     legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
+    if "packed" in a.legs.split(","):
+        legs += [("packed_baseline", "dense", a.batch_lib or here), ("packed", "packed", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
     for name, leg, lib in legs:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib], capture_output=True, text=True, timeout=600)
@@ -158,6 +196,8 @@ def main():
         out["speedup_vs_" + ("parent" if a.parent_lib else "single")] = {k: round(base[k]["roundtrip_ms"] / out["batch"][k]["roundtrip_ms"], 1) for k in out["batch"]}
     if "batch" in out and "shared" in out:
         out["shared_vs_batch"] = {k: {w: round(out["batch"][k][w] / out["shared"][k][w], 2) for w in ("encode_ms", "decode_ms")} for k in out["shared"]}
+    if "packed" in out:  # > 1: the packed call is the faster one
+        out["packed_vs_baseline"] = {k: {w: round(out["packed_baseline"][k][w] / out["packed"][k][w], 2) for w in ("encode_ms", "decode_ms")} for k in out["packed"]}
     line = json.dumps(out)
     print(line)
     if a.out:
