@@ -150,6 +150,7 @@ SIGNATURES = {
     "et_packed_result_size": (_sz, []),
     "et_encode_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, ctypes.POINTER(PackedResult)]),
     "et_decode_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, ctypes.POINTER(PackedResult)]),
+    "et_decode_packed_gather_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(PackedResult)]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),

@@ -478,6 +478,24 @@ class Context:
                                              ctypes.byref(res))
         return self._packed_result(rc, res)
 
+    def decode_packed_gather_device(self, codebook, bodies, body_index, text_index, rows, out, out_index, written=None, status=None):
+        """Row k of the result is record rows[k] of the store (bodies, body_index, text_index: decode_packed_device's, the text offsets
+        serving as record lengths only), in any order, with repeats: its symbols go to out[out_index[k] : out_index[k + 1]], the rows
+        back to back from out_index[0] = 0 -- the layout is computed on the GPU.  rows: int32/uint32 CUDA tensor of record numbers;
+        out_index (written): CUDA tensor of len(rows) + 1 64-bit integers; written, status: optional, one entry per ROW.  A row that
+        fails (a record number beyond the store, a bad pair of offsets, a record above batch small_max) takes no bytes; the result's
+        first_failed is a row.  out=None: sizes only.  -> PackedResult; .status is ET_OK or ET_ERR_CAP (nothing written, .out_bytes =
+        the room needed); any other failure of the call raises.  Stream-ordered like decode_packed_device."""
+        n = text_index.numel() - 1
+        assert rows.is_cuda and rows.dim() == 1 and rows.element_size() == 4 and rows.is_contiguous() and not rows.is_floating_point(), "rows is a 1-D CUDA tensor of 32-bit integers"
+        res = N.PackedResult()
+        self._bind()
+        rc = N.lib().et_decode_packed_gather_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                                    rows.data_ptr(), rows.numel(), None if out is None else out.data_ptr(), 0 if out is None else out.numel(),
+                                                    self._index_ptr(out_index, rows.numel()), None if written is None else written.data_ptr(),
+                                                    None if status is None else status.data_ptr(), ctypes.byref(res))
+        return self._packed_result(rc, res)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -525,6 +543,32 @@ class Context:
             raise EntreepyError(res.first_status, f"decode_packed: item {res.first_failed}")
         host, written = d_out.cpu().numpy(), d_written.cpu().numpy()  # (a body that ends early gives the shorter text, as decode_shared)
         return [host[int(a) : int(a) + int(w)].tobytes() for a, w in zip(text_index[:-1], written)]
+
+    def decode_packed_rows(self, codebook, blob, out_index, lengths, rows):
+        """decode_packed's store and a list of record numbers (any order, repeats allowed) -> [the texts of those records], through
+        one decode_packed_gather_device call."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert out_index.size == lengths.size + 1
+        if not rows.size:
+            return []
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
+        room = int(lengths[rows[rows < lengths.size]].sum())  # (a row beyond the store fails below, and takes none)
+        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=d_blob.device)
+        d_rows_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        d_written = torch.empty(rows.size, dtype=torch.int32, device=d_blob.device)
+        res = self.decode_packed_gather_device(codebook, d_blob, d_body_index, d_text_index, d_rows, d_out, d_rows_index, written=d_written)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"decode_packed_rows: row {res.first_failed}")
+        host, at, written = d_out.cpu().numpy(), d_rows_index.cpu().numpy(), d_written.cpu().numpy()  # (the copies run behind the call's kernels)
+        return [host[int(a) : int(a) + int(w)].tobytes() for a, w in zip(at[:-1], written)]
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

@@ -27,11 +27,15 @@
 // so there are no job records, no chunks and no host loop over the records:
 //   encode   table + zeroed counters -> one upload -> k_packed_count -> k_packed_scan -> (unless sizes only) k_packed_pack; (poll) the report
 //   decode   table + zeroed counters -> one upload -> k_packed_decode -> (poll) the report
+//   gather   table + zeroed counters -> one upload -> k_gather_plan -> k_packed_scan -> (unless sizes only) k_packed_gather; (poll) the report
+// (et_decode_packed_gather_device: a selection of records, rows[] on the device, into a dense output the scan lays out.  Its report
+// leaves with the decode kernel, which alone knows the rows whose bodies ended early -- with the scan when the call is sizes only.)
 // The encode's report leaves with the scan: the pack kernel behind it decides from the offsets the scan stored whether the
 // bodies fit, so the host returns ET_ERR_CAP (or ET_OK) from the same figures without waiting for it.  The calls keep a third
 // region of the pinned block (table, counters' first values, report) and a device workspace of their own (ctx->packed_ws: table,
-// counters, one size word per record).  Both may be refilled without asking for the shared-table calls' reason: every call ends
-// with a poll for a kernel that runs behind its upload, and on the device everything is rewritten in stream order.
+// counters, one size word per record of an encode or row of a gather).  Both may be refilled without asking for the shared-table
+// calls' reason: every call ends with a poll for a kernel that runs behind its upload, and on the device everything is rewritten
+// in stream order.
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -208,7 +212,21 @@ int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_ou
     return ET_OK;
 }
 
-// Both packed calls, up to the launch: the arguments, the table, the workspaces, the upload.  *go = false: the call is over
+// Every packed call's one upload, behind its argument check: the table is judged, the workspaces made (ws_words size words behind
+// the table and the counters), then the table and the counters' first values go up in one copy.
+int packed_upload(et_ctx *ctx, const et_codebook *cb, bool encode, size_t ws_words, uint32_t *n_codes) {
+    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    ET_TRY(ensure_batch(ctx, 1, 2048));
+    ET_TRY(ensure(ctx, ctx->packed_ws, PK_SIZES + ws_words * sizeof(uint32_t)));
+    *n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), encode);
+    uint64_t *first = pin<uint64_t>(ctx, PIN_PK_STATS);
+    std::memset(first, 0, et::PACKED_WORDS * 8);
+    first[et::PACKED_FIRST] = ~0ull;
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_UPLOAD, hipMemcpyHostToDevice, ctx->stream));
+    return ET_OK;
+}
+
+// The encode and the range decode, up to the launch: the arguments, then packed_upload.  *go = false: the call is over
 // (an error, or n == 0) with the returned status.
 int packed_begin(et_ctx *ctx, const et_codebook *cb, const void *d_in, const void *d_out, const uint64_t *idx_a, const uint64_t *idx_b, size_t n, et_packed_result *res,
                  bool encode, uint32_t *n_codes, bool *go) {
@@ -219,14 +237,7 @@ int packed_begin(et_ctx *ctx, const et_codebook *cb, const void *d_in, const voi
     if (n > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
     *res = et_packed_result{};
     if (n == 0) return ET_OK;
-    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
-    ET_TRY(ensure_batch(ctx, 1, 2048));
-    ET_TRY(ensure(ctx, ctx->packed_ws, PK_SIZES + (encode ? n * sizeof(uint32_t) : 0)));
-    *n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), encode);
-    uint64_t *first = pin<uint64_t>(ctx, PIN_PK_STATS);
-    std::memset(first, 0, et::PACKED_WORDS * 8);
-    first[et::PACKED_FIRST] = ~0ull;
-    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_UPLOAD, hipMemcpyHostToDevice, ctx->stream));
+    ET_TRY(packed_upload(ctx, cb, encode, encode ? n : 0, n_codes));
     *go = true;
     return ET_OK;
 }
@@ -298,6 +309,31 @@ extern "C" int et_decode_packed_device(et_ctx *ctx, const et_codebook *cb, const
                              static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 4), epoch);
     ET_TRY(packed_end(ctx, epoch, res));
     if (res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "text_index[n] lies beyond cap");  // (k_packed_decode saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                              const uint64_t *d_text_index, size_t n_records, const uint32_t *d_rows, size_t n_rows, void *d_out, size_t cap,
+                                              uint64_t *d_out_index, uint32_t *d_written, uint8_t *d_status, et_packed_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || !d_rows || !d_out_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index) | reinterpret_cast<uintptr_t>(d_out_index)) & 7)
+        return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_rows) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
+    *res = et_packed_result{};
+    if (n_rows == 0) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    uint32_t n_codes = 0;
+    ET_TRY(packed_upload(ctx, cb, false, n_rows, &n_codes));
+    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
+    const uint64_t epoch = ++ctx->batch_epoch;
+    et::launch_packed_gather(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), d_rows, static_cast<uint32_t>(n_rows), d_out, cap,
+                             d_out_index, reinterpret_cast<const uint2 *>(ws), n_codes, d_written, d_status, reinterpret_cast<uint32_t *>(ws + PK_SIZES),
+                             reinterpret_cast<unsigned long long *>(ws + 2048), reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)),
+                             static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 4), epoch);
+    ET_TRY(packed_end(ctx, epoch, res));
+    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the rows take more than cap bytes");  // (k_packed_gather saw the same two figures)
     return ET_OK;
 }
 

@@ -95,5 +95,14 @@ void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_
 void launch_packed_decode(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n, void *d_out,
                           uint64_t cap, const uint2 *codes, uint32_t n_codes, uint32_t *d_written, uint8_t *d_status, unsigned long long *stats,
                           unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
+// The gather call (et_decode_packed_gather_device): k_gather_plan (one lane per row: the room of record rows[k], or none and why,
+// into `sizes`, n_rows words of workspace, and d_status), k_packed_scan (sizes -> out_index) and -- unless d_out is null: sizes
+// only -- k_packed_gather (k_packed_decode's loop over the rows), in stream order.  The report leaves with the last of them: with
+// the decode, which alone knows the short rows, or with the scan of a sizes-only call.
+constexpr uint32_t GATHER_PLAN_GRID = 1024;  // workgroups of k_gather_plan at most: a row per lane and trip
+void launch_packed_gather(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
+                          const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_index, const uint2 *codes, uint32_t n_codes, uint32_t *d_written,
+                          uint8_t *d_status, uint32_t *sizes, unsigned long long *stats, unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done,
+                          unsigned long long epoch);
 
 }  // namespace et

@@ -17,6 +17,9 @@
 //            k_packed_scan   ONE workgroup, a loop over tiles of 4096 records: sizes -> u64 offsets, the total, the report to the host
 //            k_packed_pack   k_shared_encode's pack pass alone, destination and length from the offsets the scan stored
 //   decode   k_packed_decode k_shared_decode's loop; counters in device memory, the last workgroup reports them
+//   gather   k_gather_plan   one lane per row of a selection: its record's offsets judged, its room into the workspace, its status
+//            k_packed_scan   the rooms -> out_index (its report optional: a writing call's leaves with the decode)
+//            k_packed_gather k_packed_decode's loop over the rows, each to its place in a dense output
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -544,6 +547,26 @@ struct PackedTally {  // thread 0's
     }
 };
 
+// The report of a decode kernel (k_packed_decode, k_packed_gather), by thread 0 of every workgroup at its end: the workgroup's
+// counts are in `stats` before its tick of the counter; the last one to tick reads them all back, stores {out_bytes, failed,
+// first << 8 | status, short} and hands over.
+__device__ __forceinline__ void packed_report(const PackedTally &tally, uint64_t out_bytes, unsigned long long *stats, unsigned long long *host_result, uint32_t *counter,
+                                              unsigned long long *host_done, unsigned long long epoch) {
+    tally.add_to(stats);  // (device-scope atomics, like the tick and the read-back below: no cache in between)
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the counts have landed before the tick leaves
+    const uint32_t before = atomicAdd(counter, 1u);
+    if (before == gridDim.x - 1) {
+        __threadfence();
+        atomicExch(counter, 0u);
+        host_result[PACKED_BYTES] = out_bytes;
+        host_result[PACKED_N_FAILED] = atomicAdd(stats + PACKED_N_FAILED, 0ull);
+        host_result[PACKED_FIRST] = atomicMin(stats + PACKED_FIRST, ~0ull);
+        host_result[PACKED_N_SHORT] = atomicAdd(stats + PACKED_N_SHORT, 0ull);
+        hand_over(host_done, epoch);
+    }
+}
+
 // k_packed_count: the table in LDS once, then per record k_shared_encode's count pass.  sizes[j] = bytes of body (0 for a
 // record that failed, or is empty), d_status[j] (may be null) = its et_status.  LDS 2 KiB.
 __global__ __launch_bounds__(BB) void k_packed_count(const uint8_t *__restrict__ d_text, uint64_t text_bytes, const uint64_t *__restrict__ text_index, uint32_t n,
@@ -583,8 +606,10 @@ __global__ __launch_bounds__(BB) void k_packed_count(const uint8_t *__restrict__
 
 // k_packed_scan: ONE workgroup; per trip a tile of 4096 sizes, 16 consecutive ones per lane, becomes 4096 u64 offsets (an
 // exclusive scan, the tiles before carried in a register); the total goes to out_index[n].  The trip count is n / 4096, fixed
-// by the host.  Thread 0 then reports to the host: {total, records that failed, the first of them << 8 | its status} and the
-// epoch.  k_packed_pack, enqueued behind, takes everything it needs from out_index: the host does not wait in between.
+// by the host.  REPORT: thread 0 then reports to the host: {total, records that failed, the first of them << 8 | its status} and
+// the epoch.  k_packed_pack, enqueued behind, takes everything it needs from out_index: the host does not wait in between.
+// Without REPORT (a writing gather call: k_packed_gather reports, behind its decode) the offsets are all it leaves.
+template <bool REPORT>
 __global__ __launch_bounds__(BB) void k_packed_scan(const uint32_t *__restrict__ sizes, uint32_t n, uint64_t *__restrict__ out_index,
                                                     const unsigned long long *__restrict__ stats, unsigned long long *__restrict__ host_result,
                                                     unsigned long long *__restrict__ host_done, unsigned long long epoch) {
@@ -619,6 +644,7 @@ __global__ __launch_bounds__(BB) void k_packed_scan(const uint32_t *__restrict__
     }
     if (tid == 0) {
         out_index[n] = carry;
+        if (!REPORT) return;
         host_result[PACKED_BYTES] = carry;
         host_result[PACKED_N_FAILED] = stats[PACKED_N_FAILED];
         host_result[PACKED_FIRST] = stats[PACKED_FIRST];
@@ -693,22 +719,104 @@ __global__ __launch_bounds__(BB) void k_packed_decode(const uint8_t *__restrict_
             }
         }
     }
-    // the report: every workgroup's counts are in `stats` before its tick of the counter; the last one reads them back
-    if (tid == 0) {
-        tally.add_to(stats);  // (device-scope atomics, like the tick and the read-back below: no cache in between)
-        __threadfence();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the counts have landed before the tick leaves
-        const uint32_t before = atomicAdd(counter, 1u);
-        if (before == gridDim.x - 1) {
-            __threadfence();
-            atomicExch(counter, 0u);
-            host_result[PACKED_BYTES] = out_bytes;
-            host_result[PACKED_N_FAILED] = atomicAdd(stats + PACKED_N_FAILED, 0ull);
-            host_result[PACKED_FIRST] = atomicMin(stats + PACKED_FIRST, ~0ull);
-            host_result[PACKED_N_SHORT] = atomicAdd(stats + PACKED_N_SHORT, 0ull);
-            hand_over(host_done, epoch);
+    if (tid == 0) packed_report(tally, out_bytes, stats, host_result, counter, host_done, epoch);
+}
+
+// --------------------------------------------------------------------------------
+// The gather call: row k of the result is record rows[k] of a packed store, in any order, with repeats; the rows lie back to
+// back in d_out, laid out here.  Three launches in stream order, the host waiting for the last alone:
+//   k_gather_plan    per row: its record's two pairs of offsets judged, its room (the record's length; 0 when it failed) into the
+//                    workspace, its status byte
+//   k_packed_scan    rooms -> out_index (with the report when the call is sizes only: nothing follows)
+//   k_packed_gather  k_packed_decode's loop over the rows, the job made from rows[k], the record's body pair and out_index[k]
+// --------------------------------------------------------------------------------
+// k_gather_plan: one lane per row, a grid-stride loop; rows[] is loaded coalesced, the four offsets are gathered.  What failed is
+// counted per lane, reduced over the wavefront by shuffles and over the workgroup through LDS: one pair of atomics per workgroup
+// that saw a failure.  No LDS beyond those 4 + 4 words.
+__global__ __launch_bounds__(BB) void k_gather_plan(const uint32_t *__restrict__ rows, uint32_t n_rows, const uint64_t *__restrict__ body_index,
+                                                    const uint64_t *__restrict__ text_index, uint32_t n_records, uint64_t body_bytes, uint32_t *__restrict__ sizes,
+                                                    uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    unsigned long long failed = 0, first = ~0ull;
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * BB + threadIdx.x; k < n_rows; k += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t r = rows[k];
+        uint32_t status = PACKED_ARG, room = 0;
+        if (r < n_records) {
+            const uint64_t b0 = body_index[r], b1 = body_index[r + 1], t0 = text_index[r], t1 = text_index[r + 1];
+            if (b0 <= b1 && b1 <= body_bytes && t0 <= t1) {
+                if (t1 - t0 > BATCH_SMALL_MAX) {
+                    status = PACKED_UNSUPPORTED;
+                } else {
+                    status = PACKED_OK;
+                    room = static_cast<uint32_t>(t1 - t0);
+                }
+            }
+        }
+        sizes[k] = room;
+        if (d_status) d_status[k] = static_cast<uint8_t>(status);
+        if (status) {
+            ++failed;
+            const unsigned long long key = k << 8 | status;  // (k ascends in a lane: its first is its lowest)
+            if (key < first) first = key;
         }
     }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        failed += __shfl_xor(failed, d, 64);
+        const unsigned long long other = __shfl_xor(first, d, 64);
+        if (other < first) first = other;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_failed[threadIdx.x >> 6] = failed;
+        s_first[threadIdx.x >> 6] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PackedTally tally;
+        for (int w = 0; w < BB / 64; ++w) {
+            tally.failed += s_failed[w];
+            if (s_first[w] < tally.first) tally.first = s_first[w];
+        }
+        tally.add_to(stats);
+    }
+}
+
+// k_packed_gather: k_packed_decode with row k's job made from rows[k]: out_index[k + 1] - out_index[k] symbols (the room
+// k_gather_plan gave it) from the body d_bodies[body_index[r], body_index[r + 1]) to d_out + out_index[k].  A row without room
+// (failed, or of length zero) is passed over without a look at its record; a row with room was judged by k_gather_plan, so its
+// pairs are believed.  d_written[k] (may be null) = symbols stored.  Nothing is decoded when out_index[n_rows] > cap.  The failure
+// counters in `stats` are k_gather_plan's; this kernel adds the short rows, and its last workgroup reports.  LDS as k_batch_decode.
+__global__ __launch_bounds__(BB) void k_packed_gather(const uint8_t *__restrict__ d_bodies, const uint64_t *__restrict__ body_index, const uint32_t *__restrict__ rows,
+                                                      uint32_t n_rows, uint8_t *__restrict__ d_out, uint64_t cap, const uint64_t *__restrict__ out_index,
+                                                      const uint2 *__restrict__ codes, uint32_t n_codes, uint32_t *__restrict__ d_written,
+                                                      unsigned long long *__restrict__ stats, unsigned long long *__restrict__ host_result, uint32_t *__restrict__ counter,
+                                                      unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    __shared__ BatchDecLds s;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t out_bytes = out_index[n_rows];
+    PackedTally tally;
+    if (out_bytes <= cap) {
+        if (tid < n_codes) s.codes[tid] = codes[tid];
+        __syncthreads();
+        fill_lut(s, n_codes);
+        for (uint32_t k = blockIdx.x; k < n_rows; k += gridDim.x) {
+            const uint64_t o0 = out_index[k], o1 = out_index[k + 1];
+            uint32_t done = 0;
+            if (o1 > o0) {  // (the same for every lane)
+                const uint32_t r = rows[k], count = static_cast<uint32_t>(o1 - o0);
+                const uint64_t b0 = body_index[r], b1 = body_index[r + 1];
+                if (b1 > b0) {
+                    // (count codewords of at most 32 bits end within 4 count bytes: decode_stream's bit positions stay small)
+                    const uint64_t most = static_cast<uint64_t>(count) * 4 + 8;
+                    const uint32_t len = static_cast<uint32_t>(b1 - b0 < most ? b1 - b0 : most);
+                    done = decode_stream(s, n_codes, d_bodies, d_out, b0, o0, len, count, count);
+                }
+                if (tid == 0 && done < count) ++tally.n_short;  // (an empty body under a length above zero is a short one)
+            }
+            if (tid == 0 && d_written) d_written[k] = done;
+        }
+    }
+    if (tid == 0) packed_report(tally, out_bytes, stats, host_result, counter, host_done, epoch);
 }
 
 // --------------------------------------------------------------------------------
@@ -719,7 +827,7 @@ void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_
                           unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
     const uint8_t *text = static_cast<const uint8_t *>(d_text);
     hipLaunchKernelGGL(k_packed_count, dim3(batch_grid(n)), dim3(BB), 0, stream, text, text_bytes, text_index, n, table, sizes, d_status, stats);
-    hipLaunchKernelGGL(k_packed_scan, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(sizes), n, out_index, static_cast<const unsigned long long *>(stats), host_result,
+    hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(sizes), n, out_index, static_cast<const unsigned long long *>(stats), host_result,
                        host_done, epoch);
     if (d_out)
         hipLaunchKernelGGL(k_packed_pack, dim3(n < SHARED_ENC_GRID ? n : SHARED_ENC_GRID), dim3(BB), 0, stream, text, text_bytes, text_index, n, static_cast<uint8_t *>(d_out), cap,
@@ -731,6 +839,24 @@ void launch_packed_decode(hipStream_t stream, const void *d_bodies, uint64_t bod
                           unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
     hipLaunchKernelGGL(k_packed_decode, dim3(n < SHARED_DEC_GRID ? n : SHARED_DEC_GRID), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), body_bytes, body_index, text_index,
                        n, static_cast<uint8_t *>(d_out), cap, codes, n_codes, d_written, d_status, stats, host_result, counter, host_done, epoch);
+}
+
+void launch_packed_gather(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
+                          const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_index, const uint2 *codes, uint32_t n_codes, uint32_t *d_written,
+                          uint8_t *d_status, uint32_t *sizes, unsigned long long *stats, unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done,
+                          unsigned long long epoch) {
+    const uint32_t plan_grid = (n_rows + BB - 1) / BB;
+    hipLaunchKernelGGL(k_gather_plan, dim3(plan_grid < GATHER_PLAN_GRID ? plan_grid : GATHER_PLAN_GRID), dim3(BB), 0, stream, rows, n_rows, body_index, text_index, n_records, body_bytes,
+                       sizes, d_status, stats);
+    const uint32_t *rooms = sizes;
+    const unsigned long long *counts = stats;
+    if (!d_out) {
+        hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, rooms, n_rows, out_index, counts, host_result, host_done, epoch);
+        return;
+    }
+    hipLaunchKernelGGL(k_packed_scan<false>, dim3(1), dim3(BB), 0, stream, rooms, n_rows, out_index, counts, host_result, host_done, epoch);
+    hipLaunchKernelGGL(k_packed_gather, dim3(n_rows < SHARED_DEC_GRID ? n_rows : SHARED_DEC_GRID), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), body_index, rows, n_rows,
+                       static_cast<uint8_t *>(d_out), cap, static_cast<const uint64_t *>(out_index), codes, n_codes, d_written, stats, host_result, counter, host_done, epoch);
 }
 
 void launch_shared_encode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *table,

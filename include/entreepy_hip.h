@@ -291,7 +291,8 @@ size_t et_body_bound(const et_codebook *cb, size_t n);
 /* PACKED record batches: the same bodies under the same one table, but input and output are both what a record store keeps --
  * dense bytes plus n + 1 offsets of 64 bits, all in device memory -- and the offsets of the bodies are computed on the GPU.
  * One call where the shared-table calls need a sizes-only call, a prefix sum on the host and a writing call; no per-record
- * structs on the host at all.  Passing a sub-range of the offsets decodes that sub-range of the records (random access).
+ * structs on the host at all.  Passing a sub-range of the offsets decodes that sub-range of the records (random access to one
+ * run of records; a selection of records in any order goes through et_decode_packed_gather_device, below).
  * All d_* pointers are device pointers on the ctx's GPU.  The offset arrays hold n + 1 entries and must be 8-byte aligned; the
  * data pointers may have any alignment.  Each record is judged from its own pair of entries: a pair that decreases or
  * leaves its buffer fails that record alone (ET_ERR_ARG), and no kernel reads or writes where such a pair points.
@@ -336,6 +337,39 @@ int et_decode_packed_device(et_ctx *ctx, const et_codebook *cb,
                             const uint64_t *d_text_index, size_t n,
                             void *d_out, size_t cap, uint32_t *d_written, uint8_t *d_status,
                             et_packed_result *res);
+/* GATHER: a SELECTION of a packed store's records -- what a filter, a join or an index lookup leaves -- decoded into a dense
+ * output with offsets, on the device, in one call.  The store is et_decode_packed_device's: d_bodies, and d_body_index and
+ * d_text_index of n_records + 1 entries each; the text offsets serve as record lengths only.  d_rows[k] (n_rows of them, 32 bits,
+ * 4-byte aligned, on the device) is the record that row k of the result is; rows may come in any order and may repeat.  The output
+ * is laid out by the call, on the GPU: out_index[0] = 0, row k owns d_out[out_index[k], out_index[k+1]), and its room is its
+ * record's length text_index[r+1] - text_index[r] when its status is ET_OK, 0 when it failed.  d_written[k] (may be NULL) = symbols
+ * stored at d_out + out_index[k]; nothing outside [out_index[k], out_index[k] + written[k]) is written for any row, and nothing at
+ * or beyond d_out + out_index[n_rows].
+ *   A body that ends early: ET_OK with fewer symbols, counted in n_short, the rest of its room untouched -- an empty body under a
+ *     length above zero among them, whose room is kept so that a record the encoder failed (kept raw elsewhere) can be patched into
+ *     place; as in et_decode_packed_device.
+ *   d_status[k] (one et_status byte per ROW; may be NULL): ET_ERR_ARG when d_rows[k] >= n_records, and unless
+ *     body_index[r] <= body_index[r+1] <= body_bytes and text_index[r] <= text_index[r+1]; ET_ERR_UNSUPPORTED for a length above
+ *     the small-stream limit.  A row fails alone, no kernel reads or writes where a bad pair points, and a bad record that no row
+ *     selects does not matter.  In *res, n_failed, first_failed and first_status are about ROWS (positions k), and out_bytes is
+ *     out_index[n_rows].
+ *   d_out == NULL: sizes only -- d_out_index, d_status and *res are the writing call's except that n_short is 0; cap is ignored
+ *     and d_written is not touched.
+ *   out_index[n_rows] > cap: the call returns ET_ERR_CAP, not a byte of d_out is written and d_written is not touched;
+ *     d_out_index and d_status are complete and res->out_bytes is the room needed.  d_written is complete whenever the call
+ *     returns ET_OK with d_out given.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_bodies, d_body_index, d_text_index, d_rows or d_out_index; an offset
+ * array that is not 8-byte aligned, d_rows not 4-byte aligned; n_records or n_rows above 0x7fffffff -- all checked before
+ * anything touches a device), ET_ERR_UNSUPPORTED (the table is not complete: nothing is enqueued), ET_ERR_CAP, ET_ERR_HIP,
+ * ET_ERR_NOMEM.  n_rows == 0: ET_OK, nothing enqueued, *res zeroed.  One upload (the table and zeroed counters), three launches
+ * and one hand-over per call; stream-ordered like the other packed calls, and it may follow or precede packed, shared-table and
+ * single-stream calls on one ctx with nothing in between. */
+int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb,
+                                   const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                   const uint64_t *d_text_index, size_t n_records,
+                                   const uint32_t *d_rows, size_t n_rows,
+                                   void *d_out, size_t cap, uint64_t *d_out_index,
+                                   uint32_t *d_written, uint8_t *d_status, et_packed_result *res);
 
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).

@@ -17,6 +17,12 @@ process of its own so that every leg loads exactly one build of the library:
                   encode replaces -- a sizes-only et_encode_shared_device, a prefix sum on the host, the writing call into the dense
                   layout -- and et_decode_shared_device out of that layout, on this tree's library or on the one named by
                   --batch-lib (a build of the commit before the packed calls).
+  gather          et_decode_packed_gather_device, one call per shape and selection, on this tree's library: a selection of the packed
+                  leg's records -- every row in order, a random 10 % (ascending, as a filter leaves them), a random permutation of
+                  all rows -- decoded into a dense output.  Beside the writing call it times the sizes-only call on the same rows and,
+                  for the identity, et_decode_packed_device of the same batch.  With it runs gather_baseline, what the call replaces
+                  -- both offset arrays copied to the host, the items and their prefix sum built there, et_decode_shared_device on
+                  those items -- on this tree's library or on the one named by --batch-lib (a build of the commit before the call).
 --legs picks the legs (default: all).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
@@ -25,6 +31,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --parent-lib /path/to/parent/libentreepy_hip.so --out profiles/batch_bench.json
     python tools/batch_bench.py --legs batch,shared --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/shared_bench.json
     python tools/batch_bench.py --legs packed --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/packed_bench.json
+    python tools/batch_bench.py --legs gather --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/gather_bench.json
 """
 import argparse
 import ctypes
@@ -168,22 +175,126 @@ def _leg(leg, lib_path):
     print(json.dumps(results))
 
 
+SELECTIONS = ("identity", "random_tenth", "permutation")
+
+
+def _selection(name, count):
+    import numpy as np
+
+    rng = np.random.default_rng(0x6A7E4 + count)
+    if name == "identity":
+        return np.arange(count, dtype=np.uint32)
+    if name == "random_tenth":
+        return np.sort(rng.choice(count, size=count // 10, replace=False)).astype(np.uint32)
+    return rng.permutation(count).astype(np.uint32)
+
+
+def _gather_leg(leg, lib_path):
+    """gather / gather_baseline: per shape a packed store (et_encode_packed_device, untimed), then per selection the timed decode."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+    from tests import corpus
+
+    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
+             "et_decode_packed_device", "et_decode_shared_device"] + (["et_decode_packed_gather_device"] if leg == "gather" else [])
+    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
+    dev = torch.device("cuda", 0)
+    h = ctypes.c_void_p()
+    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
+    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+    item = np.dtype([(name, {ctypes.c_uint64: "<u8", ctypes.c_int32: "<i4", ctypes.c_uint32: "<u4"}[t]) for name, t in N.BatchItem._fields_])
+
+    def timed(fn):
+        ms = []
+        for rep in range(WARMUP + REPS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep >= WARMUP:
+                ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+    results = {}
+    for count, size in SHAPES:
+        text = corpus.text_like_torch(count * size, 0xB47C4 + size, dev)
+        hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
+        cb = N.Codebook()
+        assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+        cap = count * L.et_body_bound(ctypes.byref(cb), size)
+        bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+        text_index = torch.arange(count + 1, dtype=torch.int64, device=dev) * size
+        body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        res = N.PackedResult()
+        assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), count * size, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
+                                         ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+        body_bytes = int(res.out_bytes)
+        torch.cuda.synchronize()
+        shape = {"body_bytes": body_bytes}
+        for name in SELECTIONS:
+            rows = _selection(name, count)
+            d_rows = torch.from_numpy(rows.view(np.int32)).to(dev)
+            need = rows.size * size
+            dec = torch.zeros(need + 64, dtype=torch.uint8, device=dev)
+            out_index = torch.zeros(rows.size + 1, dtype=torch.int64, device=dev)
+            want = text.view(count, size)[d_rows.long()].reshape(-1)
+
+            def gather(d_out=dec):
+                assert L.et_decode_packed_gather_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, d_rows.data_ptr(),
+                                                        rows.size, None if d_out is None else d_out.data_ptr(), need, out_index.data_ptr(), None, None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                assert res.out_bytes == need and res.n_failed == 0 and res.n_short == 0
+
+            def baseline():
+                bi, ti = (t.cpu().numpy().view(np.uint64) for t in (body_index, text_index))  # both offset arrays, to the host
+                at = rows.astype(np.int64)
+                items = np.zeros(rows.size, dtype=item)
+                items["in_off"], items["in_len"], items["out_cap"] = bi[at], bi[at + 1] - bi[at], ti[at + 1] - ti[at]
+                items["out_off"][1:] = np.cumsum(items["out_cap"][:-1])
+                assert L.et_decode_shared_device(h, ctypes.byref(cb), bodies.data_ptr(), dec.data_ptr(), items.ctypes.data, rows.size) == 0, L.et_last_error(h)
+                assert not items["status"].any() and (items["out_len"] == items["out_cap"]).all()
+
+            def packed():
+                assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, dec.data_ptr(), need, None, None,
+                                                 ctypes.byref(res)) == 0, L.et_last_error(h)
+                assert res.n_failed == 0 and res.n_short == 0
+
+            run = gather if leg == "gather" else baseline
+            run()
+            torch.cuda.synchronize()
+            assert torch.equal(dec[:need], want), "decoded rows differ from the text"
+            shape[name] = {"rows": int(rows.size), **timed(run)}
+            if leg == "gather":
+                shape[name]["sizes_only"] = timed(lambda: gather(None))
+                if name == "identity":
+                    shape[name]["packed_decode"] = timed(packed)
+            del dec, want
+        results[f"{count}x{size}"] = shape
+        del text, bodies
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather")
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
     ap.add_argument("--lib")
     a = ap.parse_args()
     if a.leg:
-        return _leg(a.leg, a.lib)
+        return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
     legs = ([("single_parent", "single", a.parent_lib)] if a.parent_lib else []) + [("single", "single", here), ("batch", "batch", a.batch_lib or here), ("shared", "shared", here)]
     legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
     if "packed" in a.legs.split(","):
         legs += [("packed_baseline", "dense", a.batch_lib or here), ("packed", "packed", here)]
+    if "gather" in a.legs.split(","):
+        legs += [("gather_baseline", "gather_baseline", a.batch_lib or here), ("gather", "gather", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
     for name, leg, lib in legs:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib], capture_output=True, text=True, timeout=600)
@@ -198,6 +309,9 @@ def main():
         out["shared_vs_batch"] = {k: {w: round(out["batch"][k][w] / out["shared"][k][w], 2) for w in ("encode_ms", "decode_ms")} for k in out["shared"]}
     if "packed" in out:  # > 1: the packed call is the faster one
         out["packed_vs_baseline"] = {k: {w: round(out["packed_baseline"][k][w] / out["packed"][k][w], 2) for w in ("encode_ms", "decode_ms")} for k in out["packed"]}
+    if "gather" in out:  # > 1: the gather call is the faster one; identity_extra_ms: what the identity takes beyond a packed decode plus a sizes-only gather
+        out["gather_vs_baseline"] = {k: {n: round(out["gather_baseline"][k][n]["ms"] / out["gather"][k][n]["ms"], 2) for n in SELECTIONS} for k in out["gather"]}
+        out["gather_identity_extra_ms"] = {k: round(v["identity"]["ms"] - v["identity"]["packed_decode"]["ms"] - v["identity"]["sizes_only"]["ms"], 4) for k, v in out["gather"].items()}
     line = json.dumps(out)
     print(line)
     if a.out:
