@@ -1,0 +1,212 @@
+"""The serial decoder as a table: for every bit of a stream, the codeword that begins there; walks over that table give where a
+range is left, how many codewords begin in it and which -- what the synchronisation kernels compute in parallel, here one step
+at a time.  Plain numpy, a module like limits.py and guards.py, imported by name; it knows nothing about the library.
+tests/test_syncwork_host.py checks it against the oracle, tests/test_gpu_syncwork.py holds the kernels against it.
+
+Bit q of a stream is bit 7 - q % 8 of its byte q // 8; the streams handed in begin at the 4-byte aligned word their body starts
+in, which is how the range calls count."""
+import numpy as np
+
+# The tree walk's geometry, as csrc/et_treewalk.hip has it: k_tw_sync's lane (q[u]: "512-bit lane = subsequences 2q, 2q + 1") and
+# its run-in (tw_walk<0, 4 * TW_RUN, ...>: "from the root, 128 bits before the lane's own"; TW_RUN = 4 words, also DEC_WARMUP_BITS).
+LANE_BITS = 512
+RUN_IN_BITS = 128
+BLOCK_BYTES = 8192  # what the ranges of a split stream are multiples of
+BLOCK_BITS = BLOCK_BYTES * 8
+NEVER = np.iinfo(np.int64).max  # merge_distances: the walk met a bit pattern without a codeword
+
+
+class Unmatched(ValueError):
+    """A walk stands on a bit pattern that is no codeword's (hand-made tables): nothing says how to go on."""
+
+
+def windows32(stream_bytes):
+    """The 32 bits that begin at every bit of the stream (zeros behind its end), as uint32."""
+    b = np.frombuffer(bytes(stream_bytes), dtype=np.uint8) if not isinstance(stream_bytes, np.ndarray) else stream_bytes
+    n = b.size
+    b = np.concatenate([b, np.zeros(8, np.uint8)]).astype(np.uint64)
+    v = (b[0:n] << np.uint64(32)) | (b[1 : n + 1] << np.uint64(24)) | (b[2 : n + 2] << np.uint64(16)) | (b[3 : n + 3] << np.uint64(8)) | b[4 : n + 4]
+    shifts = (8 - np.arange(8)).astype(np.uint64)
+    return ((v[:, None] >> shifts[None, :]) & np.uint64(0xFFFFFFFF)).astype(np.uint32).reshape(-1)
+
+
+def next_table(stream_bytes, data, length):
+    """-> (L, S), one entry per bit of the stream: the length of the codeword that begins at bit q and its symbol; L[q] = 0
+    where no codeword matches.  (The bits behind the stream's end count as zeros: a codeword with q + L[q] beyond the last bit
+    is cut by the end -- walk() knows.)  One shift per code length, one compare per coded symbol (a lookup for the lengths up
+    to 16 bits, which is the same compare for all symbols of a length at once)."""
+    data, length = np.asarray(data, np.uint32), np.asarray(length, np.uint8)
+    win = windows32(stream_bytes)
+    L, S = np.zeros(win.size, np.uint8), np.zeros(win.size, np.uint8)
+    for l in sorted(set(length[length > 0].tolist())):
+        w = win >> np.uint32(32 - l)
+        syms = np.flatnonzero(length == l)
+        if l <= 16:
+            lut = np.zeros(1 << l, np.uint16)
+            lut[data[syms]] = syms + 1
+            hit = lut[w]
+            m = hit > 0
+            L[m], S[m] = l, (hit[m] - 1).astype(np.uint8)
+        else:
+            for s in syms:
+                m = w == data[s]
+                L[m], S[m] = l, s
+    return L, S
+
+
+def boundaries(first_bit, length, text):
+    """The true codeword boundaries of a text packed from first_bit: entry i is where codeword i begins, the last entry where
+    the last one ends."""
+    bits = np.asarray(length, np.uint8)[np.asarray(text, np.uint8)].astype(np.int64)
+    return first_bit + np.concatenate([[0], np.cumsum(bits)])
+
+
+def _cut(Lb, p):
+    """The codeword at p is cut by the stream's end (it is nobody's); a pattern without a codeword further in raises."""
+    l = Lb[p]
+    if l and p + l <= len(Lb):
+        return False
+    if p + 32 > len(Lb):
+        return True
+    raise Unmatched(f"no codeword begins at bit {p}")
+
+
+def walk(L, p, end):
+    """Follow L from bit p until the position is at or past bit `end` -> (exit, count): the first boundary at or past `end`
+    and the codewords that began in front of it.  A codeword cut by the stream's end ends the walk at `end`, uncounted."""
+    Lb = L if isinstance(L, bytes) else np.asarray(L, np.uint8).tobytes()
+    n, size = 0, len(Lb)
+    while p < end:
+        l = Lb[p]
+        if l == 0 or p + l > size:
+            if _cut(Lb, p):
+                return end, n
+        p += l
+        n += 1
+    return p, n
+
+
+def walk_positions(L, p, end):
+    """walk() that keeps where it stood -> (exit, the bits at which the counted codewords begin, as int64)."""
+    Lb = L if isinstance(L, bytes) else np.asarray(L, np.uint8).tobytes()
+    at, size = [], len(Lb)
+    while p < end:
+        l = Lb[p]
+        if l == 0 or p + l > size:
+            if _cut(Lb, p):
+                p = end
+                break
+        at.append(p)
+        p += l
+    return p, np.asarray(at, np.int64)
+
+
+def walk_symbols(L, S, p, end):
+    """walk() that also returns the symbols -> (exit, symbols as uint8): what a write of the walked range produces."""
+    exit_, at = walk_positions(L, p, end)
+    return exit_, np.asarray(S)[at].astype(np.uint8)
+
+
+class Jumps:
+    """walk() for many (start, end) pairs at once -- all start offsets of a map, every cut of a stream: J[k][q] is where 2^k
+    codewords from bit q lead (pointer doubling; 4 bytes per bit and level, so for streams of a megabit, not of sixteen)."""
+
+    def __init__(self, L):
+        L = np.asarray(L, np.uint8)
+        self.n = n = L.size
+        self.L = L
+        self.dead = dead = n + 64  # where the codewords the stream's end cuts and the patterns without a codeword lead; absorbing
+        nxt = np.full(dead + 1, dead, np.int32)
+        q = np.arange(n, dtype=np.int64)
+        to = q + L
+        ok = (L > 0) & (to <= n)
+        nxt[:n][ok] = to[ok]
+        self.J = [nxt]
+        while (1 << len(self.J)) < n + 1:
+            j = self.J[-1]
+            self.J.append(j[j])
+
+    def walk(self, starts, ends):
+        """-> (exits, counts) as int64 arrays; starts below ends.  An exit of -1: the walk met a pattern without a codeword."""
+        pos = np.array(starts, dtype=np.int64, ndmin=1)
+        ends = np.broadcast_to(np.asarray(ends, np.int64), pos.shape)
+        assert (pos < ends).all() and (ends <= self.n).all()
+        count = np.zeros(pos.shape, np.int64)
+        for k in range(len(self.J) - 1, -1, -1):
+            to = self.J[k][pos].astype(np.int64)
+            go = to < ends
+            pos = np.where(go, to, pos)
+            count += go.astype(np.int64) << k
+        last = self.J[0][pos].astype(np.int64)  # at or past the end, or dead
+        cut = last == self.dead
+        unmatched = cut & (pos + 32 <= self.n)
+        exits = np.where(cut, ends, last)
+        exits[unmatched] = -1
+        return exits, count + (~cut).astype(np.int64)
+
+
+def chain(L, first_bit, at=None):
+    """is_boundary, one flag per bit and one for the stream's end: the bits at which the whole codewords of the walk from
+    first_bit begin (the text's, and those in the pad bits behind it; `at`: walk_positions' answer, if the caller has it), and
+    the end itself."""
+    n = len(L)
+    if at is None:
+        _, at = walk_positions(L, first_bit, n)
+    on = np.zeros(n + 1, bool)
+    on[at] = True
+    on[n] = True
+    return on
+
+
+def unsettled_runs(dist, lanes_per_block=BLOCK_BITS // LANE_BITS, settled_below=LANE_BITS + RUN_IN_BITS):
+    """Per block of lanes: the longest run of consecutive lanes whose blind walk (merge_distances) is NOT on the true chain
+    before the lane's own bits end.  Such a lane leaves its bits wrongly until the lane before it hands it its true start,
+    one lane per trip of the block's fixed point: a run of r lanes takes r trips behind the first, and a block whose run
+    reaches the trip cap gives up.  A lane whose walk met a pattern without a codeword (NEVER) is nobody's to judge: it ends
+    a run."""
+    dist = np.asarray(dist)
+    bad = (dist >= settled_below) & (dist != NEVER)
+    runs = np.zeros((bad.size + lanes_per_block - 1) // lanes_per_block, np.int64)
+    cur = 0
+    for i, b in enumerate(bad.tolist()):
+        if i % lanes_per_block == 0:  # (a block's first lane gets its start from the block before, not from a lane)
+            cur = 0
+        cur = cur + 1 if b else 0
+        runs[i // lanes_per_block] = max(runs[i // lanes_per_block], cur)
+    return runs
+
+
+def longest_unsettled_run(stream_bytes, first_bit, data, length, lane_bits=LANE_BITS, run_in_bits=RUN_IN_BITS):
+    """A whole stream under the reference: over all 8 KiB blocks, the longest run of consecutive lanes that leave their own
+    bits off the true chain (unsettled_runs of merge_distances)."""
+    L, _ = next_table(stream_bytes, data, length)
+    dist = merge_distances(L, chain(L, first_bit), lane_bits, run_in_bits, enough=lane_bits + run_in_bits)
+    return int(unsettled_runs(dist, BLOCK_BITS // lane_bits, lane_bits + run_in_bits).max())
+
+
+def merge_distances(L, is_boundary, lane_bits=LANE_BITS, run_in_bits=RUN_IN_BITS, enough=None):
+    """For every lane of lane_bits bits: the distance from `lane start - run_in_bits` to the first true boundary that a walk
+    begun at that bit (as if a codeword began there) reaches -- how far a lane that runs in blind is from the truth.  Lane 0
+    has nothing in front of it: 0.  NEVER: the walk met a pattern without a codeword.  A walk that leaves the stream has met
+    everybody (the lanes behind the end stand at the root).  enough: a walk that has gone that many bits without meeting the
+    truth stops there, and where it stands is its answer (at least `enough`: all that a caller with a threshold needs)."""
+    L = np.asarray(L, np.uint8)
+    n = L.size
+    n_lanes = (n + lane_bits - 1) // lane_bits
+    p0 = np.arange(n_lanes, dtype=np.int64) * lane_bits - run_in_bits
+    dist = np.zeros(n_lanes, np.int64)
+    live = np.flatnonzero(p0 >= 0)
+    pos = p0[live].copy()
+    while live.size:
+        done = (pos >= n) | is_boundary[np.minimum(pos, n)]
+        if enough is not None:
+            done |= pos - p0[live] >= enough
+        dist[live[done]] = np.minimum(pos[done], n) - p0[live[done]]
+        live, pos = live[~done], pos[~done]
+        step = L[pos].astype(np.int64)
+        stuck = (step == 0) | (pos + step > n)
+        cut = stuck & (pos + 32 > n)
+        dist[live[stuck & ~cut]] = NEVER
+        dist[live[cut]] = n - p0[live[cut]]
+        live, pos = live[~stuck], (pos + step)[~stuck]
+    return dist

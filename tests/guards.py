@@ -1,4 +1,4 @@
-"""Helpers the GPU test modules share: output buffers with guard bytes on both sides (what may a call write?) and two hand-made
+"""Helpers the GPU test modules share: output buffers with guard bytes on both sides (what may a call write?) and hand-made
 code tables.  A plain module, imported by name; nothing here is a fixture."""
 import numpy as np
 
@@ -96,3 +96,62 @@ def _sparse_dictionary():
     for i in range(100):
         data_t[120 + i], len_t[120 + i] = 0x8000 | (i << 8), 16
     return data_t, len_t, np.array([32, 101] + list(range(120, 220)))
+
+
+def ones_longest(lengths):
+    """{symbol: length} -> (data, length) of the canonical code of those lengths (tests/test_shared_host.py): the shortest
+    codeword all zeros, the LONGEST all ones -- a run of 0xff bytes is that codeword over and over, from whatever bit."""
+    from tests.test_shared_host import canonical
+
+    data, length = canonical(lengths)
+    longest = int(length.max())
+    assert int(data[length == longest].max()) == (1 << longest) - 1
+    return data, length
+
+
+def image_under(data, length, text):
+    """The .et image (less its first four bytes) of a text under a hand-made table: the library's header, the oracle's body."""
+    import entreepy_amd as E
+    from oracle import oracle as O
+
+    return (E.Codebook.from_tables(data, length).header(len(text)) + O.pack_body(data, length, text)[0])[4:]
+
+
+def _skewed_flat_dictionary():
+    """A spread-length code with a flat class that never re-synchronises, in a table the tree walk cannot hold:
+      skewed  00, 010, 0110, 01110, 011110, 011111                           (the bytes 1 .. 6: 2 to 6 bits, complete under 0)
+      flat    1x1x1x1x, the sixteen 8-bit codewords with ones at their even bits  (the bytes 16 .. 31)
+      filler  100 iiiiiii 000000 for i < 100, 16 bits, in no text            (the bytes 120 .. 219: with a leaf for every bit
+              pattern nobody has, ~700 internal nodes, beyond the tree walk's 255 -- as _sparse_dictionary)
+    Two bits into a flat codeword another flat codeword begins, whatever the x: a walk that stands at an even offset inside
+    the flat codewords reads flat codewords for good and meets the true boundaries only if its offset is 0 mod 8.
+    -> (data, length, the skewed symbols, the flat symbols)."""
+    data_t, len_t = np.zeros(256, np.uint32), np.zeros(256, np.uint8)
+    for s, (c, l) in enumerate([(0b00, 2), (0b010, 3), (0b0110, 4), (0b01110, 5), (0b011110, 6), (0b011111, 6)], start=1):
+        data_t[s], len_t[s] = c, l
+    for j in range(16):
+        x = [(j >> k) & 1 for k in (3, 2, 1, 0)]
+        data_t[16 + j], len_t[16 + j] = int("".join("1%d" % b for b in x), 2), 8
+    for i in range(100):
+        data_t[120 + i], len_t[120 + i] = (0b100 << 13) | (i << 6), 16
+    return data_t, len_t, np.arange(1, 7, dtype=np.uint8), np.arange(16, 32, dtype=np.uint8)
+
+
+def skewed_then_flat(n_head=40_000, n_flat=60_000, seed=5):
+    """-> (data, length, text): skewed symbols (the short ones the likelier), then flat symbols only, then a thousand skewed
+    ones again, under _skewed_flat_dictionary.  The skewed part is padded with one or two symbols so that the flat part begins
+    2, 4 or 6 bits behind a byte boundary: every blind run-in, which begins at a byte boundary, then stands at an even offset
+    that is not 0 mod 8 -- in the phase that never meets the truth."""
+    data_t, len_t, skewed, flat = _skewed_flat_dictionary()
+    rng = np.random.default_rng(seed)
+    head = skewed[np.minimum(rng.geometric(0.5, size=n_head) - 1, skewed.size - 1)]
+    bits = int(len_t[head].astype(np.int64).sum())
+    pad = []
+    if bits % 2:
+        pad.append(2)  # the 3-bit codeword
+    if (bits + 3 * len(pad)) % 8 == 0:
+        pad.append(1)  # the 2-bit codeword
+    head = np.concatenate([head, np.array(pad, np.uint8)])
+    assert int(len_t[head].astype(np.int64).sum()) % 8 in (2, 4, 6)
+    text = np.concatenate([head, flat[rng.integers(0, flat.size, size=n_flat)], head[:1000]]).astype(np.uint8)
+    return data_t, len_t, text

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from tests import corpus
-from tests.guards import _random_prefix_code, _sparse_dictionary
+from tests.guards import _random_prefix_code, _sparse_dictionary, image_under, ones_longest, skewed_then_flat
 
 pytestmark = pytest.mark.gpu
 
@@ -273,14 +273,35 @@ def test_uniform_alphabets_fast_and_exhaustive_sync(ctx, k):
 
 
 def test_skewed_then_flat_stream_hits_the_sync_cap(ctx):
-    """A code with spread lengths (fast path chosen by the host) on a stream whose second
-    half uses only the long, equal-length codes: many blocks exceed the local trip cap,
-    and the decoder must still be exact (sweep-0 give-up -> exhaustive path or repairs)."""
+    """A code with spread lengths (fast path chosen by the host) on a stream whose second half uses only long, equal-length
+    codes; the decoder must be exact whether or not blocks exceed the local trip cap (sweep-0 give-up -> exhaustive path or
+    repairs).  Two streams (tests/test_gpu_syncwork.py check_repair_reach holds each against the serial reference):
+
+    - The encoder's code for a text-like half followed by 64 rare bytes.  It was written for the window sweeps' cap; under the
+      tree walk it does NOT reach any cap, and the reference says so from the input alone: every lane's blind run-in is on the
+      true chain before the lane's own bits end (a wrong walk in the flat half reads short codewords of the skewed half and soon
+      stands on a multiple of the flat codewords' length).  That is the clean condition: the decode is held to the tree walk's
+      two launches and nothing exhaustive.  This stream is kept for its bytes and for that.
+    - tests/guards.py skewed_then_flat: skewed codewords of 2 to 6 bits, then 8-bit codewords 1x1x1x1x only, in a table the
+      tree walk cannot hold, so the window sweeps run.  Two bits into a flat codeword another one begins, and the flat half is
+      laid 2, 4 or 6 bits behind a byte boundary: every subsequence's run-in stands in a phase that never meets the truth, whole
+      blocks of 256 unsettled subsequences, far beyond the first sweep's trips and the second's.  The blocks give up, and the
+      timing must say so."""
+    from tests.test_gpu_syncwork import check_repair_reach
+
     rng = np.random.default_rng(5)
     head = corpus.text_like(300_000, 8)
     rare = np.array([s for s in range(256) if s not in set(head.tolist())][:64], dtype=np.uint8)
     tail = rare[rng.integers(0, rare.size, size=400_000)]
-    _roundtrip(ctx, np.concatenate([head, tail, head[:1000]]))
+    et = _roundtrip(ctx, np.concatenate([head, tail, head[:1000]]))
+    check_repair_reach(ctx, et[4:], _oracle().decode(et[4:]), certain=False)
+    data_t, len_t, text = skewed_then_flat()
+    comp = image_under(data_t, len_t, text)
+    want = _oracle().decode(comp)
+    assert want == text.tobytes()
+    for _ in range(2):
+        assert ctx.decode(comp) == want
+    check_repair_reach(ctx, comp, want, certain=True)
 
 
 @pytest.mark.parametrize("p_short", [0.02, 0.1, 0.3])
@@ -379,6 +400,13 @@ def test_decode_fuzzed_bodies_match_the_oracle(ctx):
         assert ctx.decode(bytes(good)) == want, f"trial {trial} kind {kind}"
 
 
+def _long_runs(good, off, where):
+    spans = {"front": [(off, 30_000)], "middle": [(off + 150_000, 40_000)],
+             "several": [(off + 20_000, 9_000), (off + 100_000, 25_000), (off + 300_000, 17_000)]}[where]
+    for i, (a, ln) in enumerate(spans):
+        good[a : a + ln] = (b"\xff" if i % 2 == 0 else b"\x00") * ln
+
+
 @pytest.mark.parametrize("where", ["front", "middle", "several"])
 def test_runs_of_one_long_code_do_not_settle(ctx, where):
     """Long runs of 0xff / 0x00 inside a text stream decode as one long code repeated: a wrong
@@ -386,21 +414,39 @@ def test_runs_of_one_long_code_do_not_settle(ctx, where):
     speculative write must not act on that state (it once walked from the marker and
     overwrote its own LDS tables: an intermittent hang) and the result must still be the
     oracle's -- also when the run covers the stream's FIRST block, whose start the
-    verification has to check against the known first bit."""
+    verification has to check against the known first bit.
+
+    Whether the blocks hit the cap is held against the input itself (tests/test_gpu_syncwork.py check_repair_reach).  A run
+    of one codeword of l bits that reads the same from every bit (all ones, all zeros) keeps a wrong walk in its phase for
+    good; the lanes' run-ins begin 512 bits apart, so their phases repeat every l / gcd(512, l) lanes and the lanes in between
+    leave their bits off the true chain: l / gcd(512, l) - 1 in a row, whatever else happens.  Six in a row
+    (DEC_FIRST_SWEEP_TRIPS) make a give-up certain.  Under the encoder's code for this text the all-ones codeword has 5 bits
+    and the all-zeros one 4: 4 in a row (5 at a run's edge), and for 0x00 all lanes right or all wrong -- the reference is
+    certain of "several" alone, through its run of zeros; "front" and "middle" are kept for their bytes only.  So every
+    stream is decoded a second time under the canonical code of the same lengths, whose all-ones codeword is the longest, 17
+    bits: 16 unsettled lanes in a row in every block of a 0xff run, and there "not clean" is asserted."""
+    from tests.test_gpu_syncwork import check_repair_reach
+
     import entreepy_amd as E
 
     O = _oracle()
     rng = np.random.default_rng(11)
     text = corpus.text_like(700_000, 41)
     good = bytearray(O.encode(text)[4:])
-    _, _, off = E.parse_header(bytes(good))
-    spans = {"front": [(off, 30_000)], "middle": [(off + 150_000, 40_000)],
-             "several": [(off + 20_000, 9_000), (off + 100_000, 25_000), (off + 300_000, 17_000)]}[where]
-    for i, (a, ln) in enumerate(spans):
-        good[a : a + ln] = (b"\xff" if i % 2 == 0 else b"\x00") * ln
+    cb, _, off = E.parse_header(bytes(good))
+    _long_runs(good, off, where)
     want = O.decode(bytes(good))
     for _ in range(6):  # the failure was timing dependent
         assert ctx.decode(bytes(good)) == want
+    check_repair_reach(ctx, bytes(good), want, certain=where == "several")
+    data_t, len_t = ones_longest({s: int(l) for s, l in enumerate(cb.length) if l})
+    assert int(len_t.max()) == 17
+    good = bytearray(image_under(data_t, len_t, text))
+    _long_runs(good, E.parse_header(bytes(good))[2], where)
+    want = O.decode(bytes(good))
+    for _ in range(2):
+        assert ctx.decode(bytes(good)) == want
+    check_repair_reach(ctx, bytes(good), want, certain=True)
 
 
 @pytest.mark.parametrize("p_common", [0.9, 0.99, 0.999])
@@ -549,7 +595,18 @@ def test_blocks_that_give_up_and_are_repaired(ctx, k, where, run):
     the blocks it covers hit the first sweep's trip cap, the repair sweep settles them and the
     verification passes.  The speculative write and the host must judge that state by the same
     rule -- a long soak found the kernel declining ("blocks gave up") while the host kept its
-    output ("verification passed"): all zeros, no error."""
+    output ("verification passed"): all zeros, no error.
+
+    Whether the blocks give up is held against the input itself (tests/test_gpu_syncwork.py check_repair_reach; the
+    argument is test_runs_of_one_long_code_do_not_settle's).  Under the encoder's code for this text 0xff is NOT a long code:
+    the codewords are 0, 11, 101, 1001, ... (20 bits at most, whatever k), a run of 0xff is the 2-bit codeword 11, and the
+    lanes, which all begin at even bits, are all right or all wrong together: the reference is certain of none of the five,
+    and these streams are kept for their bytes only.  So the first 300 000 symbols are decoded a second time under a ladder
+    (lengths 1, 2, ..., l, l) in canonical order, whose l-bit codeword is all ones, with l = 27, 21, 13 for k = 28, 20, 12:
+    l / gcd(512, l) - 1 = 26, 20, 12 unsettled lanes in a row wherever the run covers them; the same run at the same place
+    gives blocks that do give up, and there "not clean" is asserted."""
+    from tests.test_gpu_syncwork import check_repair_reach
+
     import entreepy_amd as E
 
     O = _oracle()
@@ -563,6 +620,18 @@ def test_blocks_that_give_up_and_are_repaired(ctx, k, where, run):
     assert len(want) > 2_000_000
     for _ in range(2):
         assert ctx.decode(bytes(good)) == want
+    check_repair_reach(ctx, bytes(good), want, certain=False)
+    ones = {28: 27, 20: 21, 12: 13}[k]
+    data_t, len_t = ones_longest({j: min(j + 1, ones) for j in range(ones + 1)})
+    good = bytearray(image_under(data_t, len_t, np.minimum(text[:300_000], ones)))
+    _, _, off = E.parse_header(bytes(good))
+    a = len(good) - run if where == "end" else off + (len(good) - off) // 2 + 1234
+    good[a : a + run] = b"\xff" * run
+    want = O.decode(bytes(good))
+    assert len(want) > 250_000
+    for _ in range(2):
+        assert ctx.decode(bytes(good)) == want
+    check_repair_reach(ctx, bytes(good), want, certain=True)
 
 
 def test_cut_code_across_the_last_subsequence_boundary(ctx):
