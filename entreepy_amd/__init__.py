@@ -11,6 +11,10 @@ from .codec import (  # noqa: F401
     EmptyInputError,
     EncodeFlags,
     EntreepyError,
+    MATCH_EQUAL,
+    MATCH_NOT,
+    MATCH_PREFIX,
+    MatchResult,
     PackedResult,
     decode,
     default_context,

@@ -102,6 +102,20 @@ class PackedResult(ctypes.Structure):
     ]
 
 
+class MatchResult(ctypes.Structure):
+    """struct et_match_result: what et_match_packed_device reports about the whole store."""
+
+    _fields_ = [
+        ("n_match", ctypes.c_uint64),
+        ("n_failed", ctypes.c_uint64),
+        ("first_failed", ctypes.c_uint64),
+        ("first_status", ctypes.c_int32),
+        ("pattern_bits", ctypes.c_uint32),
+    ]
+
+
+ET_MATCH_EQUAL, ET_MATCH_PREFIX, ET_MATCH_NOT = 0, 1, 0x100  # et_match_packed_device's mode
+
 # int (*et_allgather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
@@ -151,6 +165,10 @@ SIGNATURES = {
     "et_encode_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, ctypes.POINTER(PackedResult)]),
     "et_decode_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, ctypes.POINTER(PackedResult)]),
     "et_decode_packed_gather_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(PackedResult)]),
+    "et_encode_pattern": (ctypes.c_int, [_cbp, _vp, _sz, _vp, _sz, _u64p]),
+    "et_match_pattern_max": (_sz, []),
+    "et_match_result_size": (_sz, []),
+    "et_match_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _sz, _vp, ctypes.POINTER(MatchResult)]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),
@@ -234,5 +252,7 @@ def lib():
         L = declare(ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL))
         if L.et_packed_result_size() != ctypes.sizeof(PackedResult):
             raise ImportError(f"{LIB_PATH}: et_packed_result is {L.et_packed_result_size()} bytes there, {ctypes.sizeof(PackedResult)} in this binding")
+        if L.et_match_result_size() != ctypes.sizeof(MatchResult):
+            raise ImportError(f"{LIB_PATH}: et_match_result is {L.et_match_result_size()} bytes there, {ctypes.sizeof(MatchResult)} in this binding")
         _lib = L
     return _lib

@@ -55,6 +55,19 @@ class PackedResult:  # struct et_packed_result, and the call's own status in fro
     first_status: int
 
 
+@dataclass
+class MatchResult:  # struct et_match_result, and the call's own status in front
+    status: int
+    n_match: int
+    n_failed: int
+    first_failed: int
+    first_status: int
+    pattern_bits: int
+
+
+MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT = N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_MATCH_NOT  # match_packed_device's mode
+
+
 def _check(status, ctx=None):
     if status == N.ET_OK:
         return
@@ -132,6 +145,15 @@ class Codebook:
     def body_bound(self, n):
         """Bytes that always hold the body of n symbols (et_body_bound)."""
         return N.lib().et_body_bound(ctypes.byref(self.raw), int(n))
+
+    def encode_pattern(self, text):
+        """text -> (its body under this table as bytes, the number of bits): what match_packed_device compares the records' bodies
+        with (et_encode_pattern, on the host).  Raises EntreepyError(ET_ERR_UNSUPPORTED) for a byte without a code."""
+        a, p = _host_u8(bytes(text))
+        out = np.zeros(max(4 * a.size, 1), dtype=np.uint8)
+        bits = ctypes.c_uint64(0)
+        _check(N.lib().et_encode_pattern(ctypes.byref(self.raw), p, a.size, out.ctypes.data, out.size, ctypes.byref(bits)))
+        return out[: (bits.value + 7) // 8].tobytes(), bits.value
 
 
 def parse_header(compressed_text):
@@ -496,6 +518,26 @@ class Context:
                                                     None if status is None else status.data_ptr(), ctypes.byref(res))
         return self._packed_result(rc, res)
 
+    def match_packed_device(self, codebook, bodies, body_index, text_index, needle, mode, rows=None, status=None):
+        """The records of the store (bodies, body_index, text_index: decode_packed_gather_device's) whose text equals `needle`
+        (MATCH_EQUAL) or begins with it (MATCH_PREFIX) -- with MATCH_NOT or-ed in, the valid records that do not -- found on the
+        compressed bytes, nothing decoded.  needle: bytes on the host.  rows: int32/uint32 CUDA tensor that takes the selected record
+        numbers, ascending (decode_packed_gather_device's rows); None: count only.  status: optional uint8 CUDA tensor of one et_status
+        byte per record; a failed record is never selected.  -> MatchResult; .status is ET_OK or ET_ERR_CAP (no row written, .n_match =
+        the room needed); any other failure of the call raises.  Stream-ordered like decode_packed_device."""
+        n = text_index.numel() - 1
+        a, p = _host_u8(bytes(needle))
+        if rows is not None:
+            assert rows.is_cuda and rows.dim() == 1 and rows.element_size() == 4 and rows.is_contiguous() and not rows.is_floating_point(), "rows is a 1-D CUDA tensor of 32-bit integers"
+        res = N.MatchResult()
+        self._bind()
+        rc = N.lib().et_match_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                            p, a.size, int(mode), None if rows is None else rows.data_ptr(), 0 if rows is None else rows.numel(),
+                                            None if status is None else status.data_ptr(), ctypes.byref(res))
+        if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
+            _check(rc, self._h)
+        return MatchResult(rc, res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -569,6 +611,26 @@ class Context:
             raise EntreepyError(res.first_status, f"decode_packed_rows: row {res.first_failed}")
         host, at, written = d_out.cpu().numpy(), d_rows_index.cpu().numpy(), d_written.cpu().numpy()  # (the copies run behind the call's kernels)
         return [host[int(a) : int(a) + int(w)].tobytes() for a, w in zip(at[:-1], written)]
+
+    def match_packed(self, codebook, blob, out_index, lengths, needle, mode):
+        """decode_packed's store, a needle and a mode -> [the numbers of the records that match], ascending, through one
+        match_packed_device call: what decode_packed_rows takes."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        assert out_index.size == lengths.size + 1
+        if not lengths.size:
+            return []
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
+        res = self.match_packed_device(codebook, d_blob, d_body_index, d_text_index, needle, mode, rows=d_rows)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"match_packed: record {res.first_failed}")
+        return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

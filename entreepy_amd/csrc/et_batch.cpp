@@ -36,6 +36,12 @@
 // counters, one size word per record of an encode or row of a gather).  Both may be refilled without asking for the shared-table
 // calls' reason: every call ends with a poll for a kernel that runs behind its upload, and on the device everything is rewritten
 // in stream order.
+//
+// The match call (et_match_packed_device) is a packed call without a table: the host encodes the needle (et_encode_pattern) and
+//   match    zeroed counters + the needle's bits -> one upload -> k_match_flag -> k_packed_scan; (poll) the report -> (unless count only) k_match_emit
+// It has a pinned region for that upload, shares the report slot and the epoch word, and lays ctx->packed_ws out its own way (the
+// counters where the other calls keep them; the pattern, the tile counts, the tiles' first places and the ballot masks behind).
+// Its report leaves with the scan: k_match_emit decides from the total the scan stored whether the rows fit, as k_packed_pack does.
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -62,10 +68,17 @@ constexpr size_t PIN_SH_RESULTS = PIN_SH_JOBS + SCH * sizeof(et::SharedJob);  //
 constexpr size_t PIN_PK_TABLE = PIN_SH_RESULTS + SCH * 8;  // 2 KiB, as PIN_SH_TABLE
 constexpr size_t PIN_PK_STATS = PIN_PK_TABLE + 2048;       // u64[PACKED_WORDS]
 constexpr size_t PIN_PK_REPORT = PIN_PK_STATS + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
-constexpr size_t PIN_BYTES = PIN_PK_REPORT + et::PACKED_WORDS * 8;
-static_assert(PIN_PK_TABLE % 16 == 0, "layout of the pinned block");
+// ... and the match call's one copy: the counters' first values, then the encoded needle (zero-padded to a multiple of 4 bytes)
+constexpr size_t PIN_MT_STATS = PIN_PK_REPORT + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
+constexpr size_t PIN_MT_PATTERN = PIN_MT_STATS + et::PACKED_WORDS * 8;  // MATCH_PATTERN_BYTES
+constexpr size_t PIN_BYTES = PIN_MT_PATTERN + et::MATCH_PATTERN_BYTES;
+static_assert(PIN_PK_TABLE % 16 == 0 && PIN_MT_STATS % 16 == 0, "layout of the pinned block");
 // the packed calls' device workspace: the same table and counters, then a size word per record
 constexpr size_t PK_UPLOAD = 2048 + et::PACKED_WORDS * 8, PK_SIZES = 4096;
+// ... as the match call lays it out: the counters where the other calls keep theirs, the pattern behind them (one copy), then a
+// count per tile, the tiles' first places (tiles + 1) and four masks per tile
+constexpr size_t MT_STATS = 2048, MT_PATTERN = MT_STATS + et::PACKED_WORDS * 8, MT_COUNTS = MT_PATTERN + et::MATCH_PATTERN_BYTES;
+static_assert(MT_PATTERN % 16 == 0 && MT_COUNTS % 16 == 0, "k_match_flag loads pattern words, k_packed_scan 16 bytes of counts");
 static_assert(int(et::PACKED_OK) == int(ET_OK) && int(et::PACKED_ARG) == int(ET_ERR_ARG) && int(et::PACKED_UNSUPPORTED) == int(ET_ERR_UNSUPPORTED), "a record's status byte is its et_status");
 static_assert(sizeof(et::SharedJob) == 24 && PIN_SH_TABLE % 16 == 0, "layout of the pinned block");
 static_assert(sizeof(et::BatchSpan) == 16 && sizeof(et::BatchEncJob) == 32 && sizeof(et::BatchDecJob) == 40, "job records are plain, packed data");
@@ -334,6 +347,71 @@ extern "C" int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb
                              static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 4), epoch);
     ET_TRY(packed_end(ctx, epoch, res));
     if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the rows take more than cap bytes");  // (k_packed_gather saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_match_pattern_max(void) { return et::MATCH_NEEDLE_MAX; }
+
+extern "C" size_t et_match_result_size(void) { return sizeof(et_match_result); }
+
+extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                      const uint64_t *d_text_index, size_t n_records, const uint8_t *needle, size_t needle_len, int mode, uint32_t *d_rows,
+                                      size_t cap_rows, uint8_t *d_status, et_match_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || (!needle && needle_len)) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_rows) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    if (needle_len > et::MATCH_NEEDLE_MAX) return fail(ctx, ET_ERR_ARG, "the needle is longer than et_match_pattern_max()");
+    const int what = mode & ~ET_MATCH_NOT;
+    if (what != ET_MATCH_EQUAL && what != ET_MATCH_PREFIX) return fail(ctx, ET_ERR_ARG, "unknown mode");
+    *res = et_match_result{};
+    if (n_records == 0) return ET_OK;
+    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    DeviceGuard guard(ctx->device);
+    const uint32_t n = static_cast<uint32_t>(n_records), n_tiles = (n + et::MATCH_TILE - 1) / et::MATCH_TILE;
+    const size_t counts_bytes = (static_cast<size_t>(n_tiles) * 4 + 15) & ~static_cast<size_t>(15);
+    const size_t at_base = MT_COUNTS + counts_bytes, at_masks = at_base + (static_cast<size_t>(n_tiles) + 1) * 8;
+    ET_TRY(ensure_batch(ctx, 1, 2048));
+    ET_TRY(ensure(ctx, ctx->packed_ws, at_masks + static_cast<size_t>(n_tiles) * (et::MATCH_TILE / 64) * 8));
+
+    // the needle's bits and the counters' first values: free to fill (this file's header), up in one copy
+    uint64_t *first = pin<uint64_t>(ctx, PIN_MT_STATS);
+    std::memset(first, 0, et::PACKED_WORDS * 8);
+    first[et::PACKED_FIRST] = ~0ull;
+    uint8_t *pattern = pin<uint8_t>(ctx, PIN_MT_PATTERN);
+    uint64_t bits = 0;
+    const int rc = et_encode_pattern(cb, needle, needle_len, pattern, et::MATCH_PATTERN_BYTES, &bits);
+    if (rc != ET_OK && rc != ET_ERR_UNSUPPORTED) return fail(ctx, rc, "et_encode_pattern");
+    const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
+    std::memset(pattern + pat_bytes, 0, padded - pat_bytes);
+    et::MatchJob job{};
+    job.pat_bits = static_cast<uint32_t>(bits);
+    job.needle_len = static_cast<uint32_t>(needle_len);
+    job.flags = (what == ET_MATCH_EQUAL ? et::MATCH_F_EQUAL : 0u) | ((mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u) | (rc == ET_ERR_UNSUPPORTED ? et::MATCH_F_NEVER : 0u);
+    const uint64_t head_bits = std::min<uint64_t>(bits, et::MATCH_HEAD_BITS);
+    for (uint32_t k = 0; k < (head_bits + 7) / 8; ++k) {  // (memory order: byte k of the body is bits 8k .. 8k + 7 of the word)
+        const uint64_t left = head_bits - 8 * k;
+        job.head |= static_cast<uint64_t>(pattern[k]) << (8 * k);
+        job.head_mask |= static_cast<uint64_t>(left >= 8 ? 0xffu : (0xffu << (8 - left)) & 0xffu) << (8 * k);
+    }
+    res->pattern_bits = job.pat_bits;
+    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
+    ET_HIP(hipMemcpyAsync(ws + MT_STATS, first, et::PACKED_WORDS * 8 + padded, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t epoch = ++ctx->batch_epoch;
+    et::launch_match(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, n, reinterpret_cast<const uint32_t *>(ws + MT_PATTERN), job, d_rows, cap_rows, d_status,
+                     reinterpret_cast<unsigned long long *>(ws + at_masks), reinterpret_cast<uint32_t *>(ws + MT_COUNTS), reinterpret_cast<uint64_t *>(ws + at_base),
+                     reinterpret_cast<unsigned long long *>(ws + MT_STATS), reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
+    ET_HIP(hipGetLastError());
+    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the match's report never reached the host"));
+    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+    res->n_match = rep[et::PACKED_BYTES];
+    res->n_failed = rep[et::PACKED_N_FAILED];
+    if (res->n_failed) {
+        res->first_failed = rep[et::PACKED_FIRST] >> 8;
+        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
+    }
+    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records match than cap_rows");  // (k_match_emit saw the same two figures)
     return ET_OK;
 }
 

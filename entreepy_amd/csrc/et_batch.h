@@ -105,4 +105,31 @@ void launch_packed_gather(hipStream_t stream, const void *d_bodies, uint64_t bod
                           uint8_t *d_status, uint32_t *sizes, unsigned long long *stats, unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done,
                           unsigned long long epoch);
 
+// The match call (et_match_packed_device): which records of a packed store begin with, or equal, a needle -- judged on the
+// compressed bytes, against the needle's own bits under the table (et_encode_pattern, on the host); no table on the device.
+//   k_match_flag   one record per lane, tiles of MATCH_TILE records: the record judged as k_gather_plan judges it, its status byte, the
+//                  first MATCH_HEAD_BITS bits of the pattern compared per lane, the rest by the whole wavefront for one surviving lane
+//                  at a time; a u64 ballot mask per 64 records and a u32 count per tile into the workspace
+//   k_packed_scan  the tile counts -> the tiles' first places in d_rows, n_match; its report is the call's
+//   k_match_emit   (unless d_rows is null: count only) per tile, a record's rank is a popcount prefix over the tile's masks
+constexpr uint32_t MATCH_HEAD_BITS = 64;                      // what a lane compares alone: one aligned 8-byte load, or two
+constexpr uint32_t MATCH_TILE = 256;                          // records per tile: one trip of a workgroup
+constexpr uint32_t MATCH_GRID = 2048;                         // workgroups of k_match_flag and k_match_emit at most
+constexpr uint32_t MATCH_NEEDLE_MAX = 4096;                   // bytes of text in a needle
+constexpr uint32_t MATCH_PATTERN_BYTES = MATCH_NEEDLE_MAX * 4;  // ... which take at most 32 bits each
+enum MatchFlag : uint32_t { MATCH_F_EQUAL = 1, MATCH_F_NOT = 2, MATCH_F_NEVER = 4 };  // NEVER: a needle byte without a code
+struct MatchJob {
+    uint64_t head, head_mask;  // the pattern's first min(8, bytes) bytes as they lie in memory, and which of their bits count
+    uint32_t pat_bits;         // bits of the encoded needle
+    uint32_t needle_len;       // its bytes of text
+    uint32_t flags;            // MatchFlag
+    uint32_t pad;
+};
+// pattern: the encoded needle on the device, zero-padded to a multiple of 4 bytes (4-byte aligned).  masks: 4 u64 per tile,
+// counts: a u32 per tile (16-byte aligned), base: tiles + 1 u64 (k_packed_scan's out_index) -- all workspace.  The report
+// ({n_match, failed, first << 8 | status}, then `epoch`) leaves with the scan, in front of k_match_emit.
+void launch_match(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
+                  const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, unsigned long long *masks, uint32_t *counts,
+                  uint64_t *base, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
+
 }  // namespace et

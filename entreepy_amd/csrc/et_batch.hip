@@ -20,6 +20,9 @@
 //   gather   k_gather_plan   one lane per row of a selection: its record's offsets judged, its room into the workspace, its status
 //            k_packed_scan   the rooms -> out_index (its report optional: a writing call's leaves with the decode)
 //            k_packed_gather k_packed_decode's loop over the rows, each to its place in a dense output
+//   match    k_match_flag    one lane per record: judged, compared with the encoded needle on the compressed bytes; ballot masks, tile counts
+//            k_packed_scan   the tile counts -> each tile's first place among the rows, the report
+//            k_match_emit    the selected record numbers, ascending, by popcount ranks
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -547,6 +550,32 @@ struct PackedTally {  // thread 0's
     }
 };
 
+// The end of a kernel that judges an item per lane (k_gather_plan, k_match_flag): what each lane counted -- how many failed, the lowest
+// of them << 8 | its status -- reduced over the wavefront by shuffles and over the workgroup through 4 + 4 words of LDS: one pair of
+// atomics per workgroup that saw a failure.
+__device__ __forceinline__ void tally_lanes(unsigned long long failed, unsigned long long first, unsigned long long *s_failed, unsigned long long *s_first,
+                                            unsigned long long *stats) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        failed += __shfl_xor(failed, d, 64);
+        const unsigned long long other = __shfl_xor(first, d, 64);
+        if (other < first) first = other;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_failed[threadIdx.x >> 6] = failed;
+        s_first[threadIdx.x >> 6] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PackedTally tally;
+        for (int w = 0; w < BB / 64; ++w) {
+            tally.failed += s_failed[w];
+            if (s_first[w] < tally.first) tally.first = s_first[w];
+        }
+        tally.add_to(stats);
+    }
+}
+
 // The report of a decode kernel (k_packed_decode, k_packed_gather), by thread 0 of every workgroup at its end: the workgroup's
 // counts are in `stats` before its tick of the counter; the last one to tick reads them all back, stores {out_bytes, failed,
 // first << 8 | status, short} and hands over.
@@ -760,25 +789,7 @@ __global__ __launch_bounds__(BB) void k_gather_plan(const uint32_t *__restrict__
             if (key < first) first = key;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        failed += __shfl_xor(failed, d, 64);
-        const unsigned long long other = __shfl_xor(first, d, 64);
-        if (other < first) first = other;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_failed[threadIdx.x >> 6] = failed;
-        s_first[threadIdx.x >> 6] = first;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        PackedTally tally;
-        for (int w = 0; w < BB / 64; ++w) {
-            tally.failed += s_failed[w];
-            if (s_first[w] < tally.first) tally.first = s_first[w];
-        }
-        tally.add_to(stats);
-    }
+    tally_lanes(failed, first, s_failed, s_first, stats);
 }
 
 // k_packed_gather: k_packed_decode with row k's job made from rows[k]: out_index[k + 1] - out_index[k] symbols (the room
@@ -820,7 +831,137 @@ __global__ __launch_bounds__(BB) void k_packed_gather(const uint8_t *__restrict_
 }
 
 // --------------------------------------------------------------------------------
+// The match call: which records of a packed store begin with (or equal) a needle, decided on the compressed bytes.  Under one
+// complete prefix-free table a record's text begins with the needle exactly when its body begins with the needle's codewords, its
+// length is at least the needle's and its body holds those bits; equality asks for the same length.  The host encodes the needle;
+// no table comes to the device.  Three launches in stream order, the host waiting for the second alone:
+//   k_match_flag   per record: judged from its own two pairs (k_gather_plan's rule), its status byte, the comparison; a ballot mask
+//                  per 64 records and a count per tile of MATCH_TILE records into the workspace
+//   k_packed_scan  the tile counts -> each tile's first place in d_rows, and the report: n_match, the failure counters
+//   k_match_emit   per tile: rows[base[tile] + rank] = record, the rank a popcount prefix over the tile's four masks
+// --------------------------------------------------------------------------------
+// k_match_flag: a workgroup takes tiles of 256 consecutive records, one per lane, so both offset arrays are read coalesced.  A lane
+// whose record can match (valid, the length fits, the body holds the pattern's bytes) compares the pattern's first 8 bytes alone:
+// the aligned 8-byte words that hold them -- one, or two; each holds a byte of the body -- shifted into place, against job.head
+// under job.head_mask.  Where the pattern is longer, the lanes that passed are taken one at a time from the ballot and all 64
+// lanes compare 4 bytes each per step (aligned words that hold a byte of THAT body, shifted), the wavefront leaving at the first
+// step with a mismatch: keys share long prefixes, and one lane walking 16 KiB alone would hold its wavefront.  The pattern's last
+// byte counts with its top pat_bits % 8 bits only: the body's next codeword begins behind them.
+// A failed record is never read and never selected; failures are tallied as in k_gather_plan.  LDS: 8 + 8 + 8 words.
+__global__ __launch_bounds__(BB) void k_match_flag(const uint8_t *__restrict__ d_bodies, uint64_t body_bytes, const uint64_t *__restrict__ body_index,
+                                                   const uint64_t *__restrict__ text_index, uint32_t n, const uint32_t *__restrict__ pattern, MatchJob job,
+                                                   unsigned long long *__restrict__ masks, uint32_t *__restrict__ counts, uint8_t *__restrict__ d_status,
+                                                   unsigned long long *__restrict__ stats) {
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    __shared__ uint32_t s_count[2][BB / 64];  // (two sets: a tile's counts are read while the next tile's are stored)
+    constexpr uint32_t HEAD_BYTES = MATCH_HEAD_BITS / 8;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t pat_bytes = (job.pat_bits + 7) >> 3, head_bytes = pat_bytes < HEAD_BYTES ? pat_bytes : HEAD_BYTES;
+    const uint32_t last_bits = job.pat_bits & 7;
+    const uint32_t n_tiles = (n + MATCH_TILE - 1) / MATCH_TILE;
+    const bool equal = job.flags & MATCH_F_EQUAL, negate = job.flags & MATCH_F_NOT, never = job.flags & MATCH_F_NEVER;
+    unsigned long long failed = 0, first = ~0ull;
+    uint32_t set = 0;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, set ^= 1) {
+        const uint32_t b = tile * MATCH_TILE + tid;  // (n <= 0x7fffffff: no wrap)
+        bool valid = false, hit = false;
+        uint64_t b0 = 0;
+        if (b < n) {
+            b0 = body_index[b];
+            const uint64_t b1 = body_index[b + 1], t0 = text_index[b], t1 = text_index[b + 1];
+            uint32_t status = PACKED_ARG;
+            if (b0 <= b1 && b1 <= body_bytes && t0 <= t1) status = t1 - t0 > BATCH_SMALL_MAX ? PACKED_UNSUPPORTED : PACKED_OK;
+            if (d_status) d_status[b] = static_cast<uint8_t>(status);
+            if (status) {
+                ++failed;
+                const unsigned long long key = static_cast<unsigned long long>(b) << 8 | status;  // (b ascends in a lane: its first is its lowest)
+                if (key < first) first = key;
+            } else {
+                valid = true;
+                const uint64_t len = t1 - t0;
+                hit = !never && (equal ? len == job.needle_len : len >= job.needle_len) && b1 - b0 >= pat_bytes;
+                if (hit && head_bytes) {
+                    const uintptr_t a = reinterpret_cast<uintptr_t>(d_bodies) + b0;
+                    const uint64_t *q = reinterpret_cast<const uint64_t *>(a & ~static_cast<uintptr_t>(7));
+                    const uint32_t lead = static_cast<uint32_t>(a & 7);
+                    uint64_t v = q[0] >> (8 * lead);
+                    if (lead + head_bytes > 8) v |= q[1] << (64 - 8 * lead);  // (lead > 0 here; q[1] holds a byte of the head)
+                    hit = ((v ^ job.head) & job.head_mask) == 0;
+                }
+            }
+        }
+        if (pat_bytes > HEAD_BYTES) {  // (the same for every lane)
+            unsigned long long survivors = __ballot(hit);
+            while (survivors) {
+                const int src = __ffsll(survivors) - 1;
+                survivors &= survivors - 1;
+                const uintptr_t body = reinterpret_cast<uintptr_t>(d_bodies) + __shfl(b0, src, 64);
+                bool same = true;
+                for (uint32_t step = HEAD_BYTES; step < pat_bytes; step += 64 * 4) {
+                    const uint32_t off = step + lane * 4;
+                    bool differs = false;
+                    if (off < pat_bytes) {
+                        const uint32_t nb = pat_bytes - off < 4 ? pat_bytes - off : 4;
+                        const uintptr_t a = body + off;
+                        const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
+                        const uint32_t lead = static_cast<uint32_t>(a & 3);
+                        uint32_t v = w[0] >> (8 * lead);
+                        if (lead + nb > 4) v |= w[1] << (32 - 8 * lead);  // (lead > 0 here; w[1] holds one of the nb bytes)
+                        uint32_t m = nb == 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u;
+                        if (off + nb == pat_bytes && last_bits) m &= ~(((1u << (8 - last_bits)) - 1u) << (8 * (nb - 1)));
+                        differs = ((v ^ pattern[off >> 2]) & m) != 0;
+                    }
+                    if (__any(differs)) {
+                        same = false;
+                        break;
+                    }
+                }
+                if (static_cast<int>(lane) == src) hit = same;
+            }
+        }
+        const unsigned long long mask = __ballot(valid && hit != negate);
+        if (lane == 0) {
+            masks[static_cast<uint64_t>(tile) * (MATCH_TILE / 64) + wave] = mask;
+            s_count[set][wave] = __popcll(mask);
+        }
+        __syncthreads();
+        if (tid == 0) counts[tile] = s_count[set][0] + s_count[set][1] + s_count[set][2] + s_count[set][3];
+    }
+    tally_lanes(failed, first, s_failed, s_first, stats);
+}
+
+// k_match_emit: a tile per trip, a record per lane: the tile's four masks (the same 32 bytes for every lane), the record's rank
+// among the tile's selected ones by popcounts, its number to rows[base[tile] + rank] -- ascending, as tiles and ranks are.  Every
+// workgroup returns at once when the rows do not fit: ET_ERR_CAP writes nothing.  No LDS.
+__global__ __launch_bounds__(BB) void k_match_emit(const unsigned long long *__restrict__ masks, const uint64_t *__restrict__ base, uint32_t n_tiles,
+                                                   uint32_t *__restrict__ rows, uint64_t cap_rows) {
+    if (base[n_tiles] > cap_rows) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const unsigned long long *m = masks + static_cast<uint64_t>(tile) * (MATCH_TILE / 64);
+        const unsigned long long mine = m[wave];
+        if (!((mine >> lane) & 1)) continue;
+        uint32_t rank = __popcll(mine & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wave; ++w) rank += __popcll(m[w]);
+        rows[base[tile] + rank] = tile * MATCH_TILE + tid;
+    }
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
+
+void launch_match(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
+                  const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, unsigned long long *masks, uint32_t *counts,
+                  uint64_t *base, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
+    const uint32_t n_tiles = (n_records + MATCH_TILE - 1) / MATCH_TILE, grid = n_tiles < MATCH_GRID ? n_tiles : MATCH_GRID;
+    hipLaunchKernelGGL(k_match_flag, dim3(grid), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), body_bytes, body_index, text_index, n_records, pattern, job, masks,
+                       counts, d_status, stats);
+    hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(counts), n_tiles, base, static_cast<const unsigned long long *>(stats),
+                       host_result, host_done, epoch);
+    if (d_rows)
+        hipLaunchKernelGGL(k_match_emit, dim3(grid), dim3(BB), 0, stream, static_cast<const unsigned long long *>(masks), static_cast<const uint64_t *>(base), n_tiles, d_rows,
+                           cap_rows);
+}
 
 void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_bytes, const uint64_t *text_index, uint32_t n, void *d_out, uint64_t cap,
                           uint64_t *out_index, uint8_t *d_status, const uint2 *table, uint32_t *sizes, unsigned long long *stats,

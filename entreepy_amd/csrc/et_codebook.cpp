@@ -265,6 +265,26 @@ extern "C" int et_codebook_is_complete(const et_codebook *cb) {
     return ET_OK;
 }
 
+// A needle of et_match_packed_device: the body the shared-table encode would give `text`, made here on the host.
+extern "C" int et_encode_pattern(const et_codebook *cb, const uint8_t *text, size_t n, uint8_t *out, size_t cap, uint64_t *n_bits) {
+    if (!cb || !n_bits || (!text && n)) return ET_ERR_ARG;
+    *n_bits = 0;
+    uint64_t bits = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned len = cb->length[text[i]];
+        if (len == 0 || len > 32) return ET_ERR_UNSUPPORTED;
+        bits += len;
+    }
+    *n_bits = bits;
+    const uint64_t bytes = (bits + 7) / 8;
+    if (bytes > cap) return ET_ERR_CAP;
+    if (bytes && !out) return ET_ERR_ARG;
+    BitSink sink(out, cap);
+    for (size_t i = 0; i < n; ++i) sink.put(cb->data[text[i]], cb->length[text[i]]);
+    sink.pad_to_byte();
+    return ET_OK;
+}
+
 extern "C" size_t et_body_bound(const et_codebook *cb, size_t n) { return cb ? (n * cb->max_length + 7) / 8 : 0; }
 
 // encode.zig:221-247, the -d self-check, loop for loop -- including its k = 0 round, which compares the bit

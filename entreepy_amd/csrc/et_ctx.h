@@ -86,7 +86,7 @@ struct et_ctx {
 
     // the batched calls (et_batch.cpp): job records and the uploaded block of the current chunk, the kernels' completion counter
     DevBuf batch_jobs, batch_blob, batch_counter;
-    DevBuf packed_ws;               // the packed calls: table, counters, a size word per record
+    DevBuf packed_ws;               // the packed calls: table, counters, a size word per record (the match call: counters, pattern, tile counts, masks)
     uint8_t *h_batch = nullptr;     // pinned: epoch words, job records, what the kernels report, the block to upload (made on first use)
     uint64_t batch_epoch = 0;       // the h_batch epoch word of a launch == batch_epoch: its report is there
 

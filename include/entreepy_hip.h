@@ -371,6 +371,53 @@ int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb,
                                    void *d_out, size_t cap, uint64_t *d_out_index,
                                    uint32_t *d_written, uint8_t *d_status, et_packed_result *res);
 
+/* MATCH: which records of a packed store equal a key, or begin with it -- the list of record numbers the gather call consumes,
+ * produced on the device WITHOUT decoding.  Under one complete prefix-free table a record's body begins at bit 7 of its first
+ * byte, so its text begins with the needle exactly when its body begins with the needle's codewords and its length is at least
+ * the needle's; the filter reads two pairs of offsets and usually one cache line of body per record.
+ *   et_encode_pattern (host only, HIP-free): the bits of `text` under cb exactly as the shared-table encode lays a body out --
+ *     MSB-first from bit 7 of out[0], the last byte zero-padded; *n_bits = their number.  n == 0: ET_OK, 0 bits.
+ *     ET_ERR_UNSUPPORTED: a byte without a code, or a code beyond 32 bits (*n_bits = 0).  ET_ERR_CAP: (n_bits + 7) / 8 > cap
+ *     (*n_bits is still the need).  ET_ERR_ARG: null cb or n_bits, null text with n > 0, null out with bytes to store.
+ *   The store is the gather call's: d_bodies, and d_body_index and d_text_index of n_records + 1 entries each, 8-byte aligned; the
+ *     text offsets serve as record lengths only.  A record is judged from its own two pairs: ET_ERR_ARG unless
+ *     body_index[b] <= body_index[b+1] <= body_bytes and text_index[b] <= text_index[b+1]; ET_ERR_UNSUPPORTED for a length above
+ *     the small-stream limit.  A failed record is never selected -- not under ET_MATCH_NOT either -- it fails alone, and no kernel
+ *     reads where its pair points.  d_status[b] (one et_status byte per record; may be NULL) holds its status.
+ *   A match: let text_b be what et_decode_packed_device would store for record b, the first min(length_b, codewords that end
+ *     inside its body) symbols.  ET_MATCH_PREFIX: text_b starts with the needle.  ET_MATCH_EQUAL: length_b == needle_len and
+ *     text_b == needle -- so a record whose body ends before its length (kept raw elsewhere, or cut) can match a prefix of what is
+ *     there and never matches EQUAL.  ET_MATCH_NOT, or-ed in, selects the valid records that do NOT match.  The empty needle
+ *     matches every valid record under PREFIX, every valid record of length 0 under EQUAL.  A needle byte without a code matches
+ *     nothing: the call is ET_OK, pattern_bits is 0, and under NOT every valid record is selected.  needle is HOST memory.
+ *   d_rows[0 .. n_match) (32 bits each, 4-byte aligned, on the device) = the selected record numbers, ascending: the gather
+ *     call's d_rows.  Nothing at or beyond d_rows + n_match is written.  d_rows == NULL: count only -- cap_rows is ignored,
+ *     d_status and *res are the writing call's.  n_match > cap_rows: the call returns ET_ERR_CAP, no entry of d_rows is written,
+ *     d_status is complete and res->n_match is the room needed.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_bodies, d_body_index or d_text_index; a null needle with
+ * needle_len > 0; an offset array that is not 8-byte aligned, d_rows not 4-byte aligned; n_records above 0x7fffffff; needle_len
+ * above et_match_pattern_max(); an unknown mode -- all checked before anything touches a device, *res untouched),
+ * ET_ERR_UNSUPPORTED (the table is not complete: nothing is enqueued), ET_ERR_CAP, ET_ERR_HIP, ET_ERR_NOMEM.  n_records == 0:
+ * ET_OK, nothing enqueued, *res zeroed.  One upload (zeroed counters and the encoded needle, 16 KiB at most), three launches and
+ * one hand-over per call; stream-ordered like the other packed calls -- *res is final on return, the device arrays once the ctx's
+ * stream has drained -- and it may follow or precede packed, gather, shared-table and single-stream calls on one ctx with nothing
+ * in between and with different tables: d_rows may go straight into et_decode_packed_gather_device on the same ctx. */
+int et_encode_pattern(const et_codebook *cb, const uint8_t *text, size_t n, uint8_t *out, size_t cap, uint64_t *n_bits);
+enum { ET_MATCH_EQUAL = 0, ET_MATCH_PREFIX = 1, ET_MATCH_NOT = 0x100 /* or-ed in: select the valid records that do NOT match */ };
+size_t et_match_pattern_max(void);          /* longest needle in bytes of text: 4096 */
+typedef struct et_match_result {
+    uint64_t n_match;       /* rows selected -- also when the call returns ET_ERR_CAP or d_rows is NULL */
+    uint64_t n_failed, first_failed;   /* records whose status is not ET_OK, the lowest of them (valid when n_failed > 0) */
+    int32_t first_status;   /* et_status of record first_failed */
+    uint32_t pattern_bits;  /* bits of the encoded needle (0 when a needle byte has no code) */
+} et_match_result;
+size_t et_match_result_size(void);
+int et_match_packed_device(et_ctx *ctx, const et_codebook *cb,
+                           const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                           const uint64_t *d_text_index, size_t n_records,
+                           const uint8_t *needle, size_t needle_len, int mode,   /* needle: HOST memory */
+                           uint32_t *d_rows, size_t cap_rows, uint8_t *d_status, et_match_result *res);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

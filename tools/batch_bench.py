@@ -23,6 +23,12 @@ process of its own so that every leg loads exactly one build of the library:
                   for the identity, et_decode_packed_device of the same batch.  With it runs gather_baseline, what the call replaces
                   -- both offset arrays copied to the host, the items and their prefix sum built there, et_decode_shared_device on
                   those items -- on this tree's library or on the one named by --batch-lib (a build of the commit before the call).
+  match           et_match_packed_device, one call per shape, selectivity and mode, on this tree's library: the records of a packed
+                  store that begin with a 12-byte needle (PREFIX) or equal a whole record of at most 4 096 bytes (EQUAL), at about 0.1 %,
+                  10 % and 100 % of the records, with d_rows and count only.  Beside the two shapes it runs on 262 144 key-like records
+                  of 16 .. 48 bytes.  With it runs match_baseline, what the call replaces -- et_decode_packed_device of the whole store,
+                  then the first L bytes of every record gathered, compared, the lengths tested and nonzero, in torch on the device -- on
+                  this tree's library or on the one named by --batch-lib (a build of the commit before the call).  --shapes picks shapes.
 --legs picks the legs (default: all).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
@@ -32,6 +38,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs batch,shared --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/shared_bench.json
     python tools/batch_bench.py --legs packed --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/packed_bench.json
     python tools/batch_bench.py --legs gather --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/gather_bench.json
+    python tools/batch_bench.py --legs match --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/match_bench.json
 """
 import argparse
 import ctypes
@@ -277,15 +284,145 @@ def _gather_leg(leg, lib_path):
     print(json.dumps(results))
 
 
+KEY_SHAPE = (262144, (16, 48))  # the match legs' third shape: key-like records of 16 .. 48 bytes
+SELECTIVITIES = (("0.1%", 0.001), ("10%", 0.1), ("100%", 1.0))
+MATCH_PREFIX_LEN = 12
+
+
+def _match_store(count, size, fraction, dev):
+    """-> (text on the device, text_index as numpy u64, the chosen records ascending, record 0's text): `fraction` of the records, record
+    0 among them, are copies of record 0; the others are text-like and as long as `size` says (a number, or a range)."""
+    import numpy as np
+    import torch
+
+    from tests import corpus
+
+    rng = np.random.default_rng(0x3A7C4 + count + int(fraction * 1000))
+    chosen = np.arange(count) if fraction >= 1.0 else np.union1d([0], rng.choice(count, size=max(int(count * fraction), 1), replace=False))
+    if isinstance(size, int):
+        text = corpus.text_like_torch(count * size, 0xB47C4 + size, dev)
+        rec = text.view(count, size)
+        rec[torch.from_numpy(chosen).to(dev)] = rec[0].clone()
+        return text, np.arange(count + 1, dtype=np.uint64) * np.uint64(size), chosen, rec[0].cpu().numpy().tobytes()
+    lengths = rng.integers(size[0], size[1] + 1, size=count)
+    lengths[chosen] = lengths[0]
+    index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+    host = corpus.text_like(int(index[-1]), 0xB47C4 + count).copy()
+    key = host[: lengths[0]].copy()
+    at = (index[chosen].astype(np.int64)[:, None] + np.arange(lengths[0])[None, :]).reshape(-1)
+    host[at] = np.tile(key, chosen.size)
+    return torch.from_numpy(host).to(dev), index, chosen, key.tobytes()
+
+
+def _match_leg(leg, lib_path, shapes):
+    """match / match_baseline: per shape and selectivity a packed store (et_encode_packed_device, untimed), then the timed filter: the
+    call under PREFIX and EQUAL (and count only) -- or what it replaces: et_decode_packed_device of the whole store, then the first L
+    bytes of every record gathered, compared, the lengths tested and nonzero, in torch on the device."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
+             "et_decode_packed_device"] + (["et_match_packed_device"] if leg == "match" else [])
+    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
+    dev = torch.device("cuda", 0)
+    h = ctypes.c_void_p()
+    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
+    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+
+    def timed(fn):
+        ms = []
+        for rep in range(WARMUP + REPS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep >= WARMUP:
+                ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+    results = {}
+    for count, size in SHAPES + [KEY_SHAPE]:
+        shape_name = f"{count}x{size}" if isinstance(size, int) else f"{count}x{size[0]}-{size[1]}"
+        if shapes and shape_name not in shapes:
+            continue
+        shape = {}
+        for sel_name, fraction in SELECTIVITIES:
+            text, index, chosen, key = _match_store(count, size, fraction, dev)
+            hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
+            cb = N.Codebook()
+            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+            total = int(index[-1])
+            cap = L.et_body_bound(ctypes.byref(cb), total) + count
+            bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+            text_index = torch.from_numpy(index.view(np.int64)).to(dev)
+            body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+            res = N.PackedResult()
+            assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
+                                             ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+            body_bytes = int(res.out_bytes)
+            torch.cuda.synchronize()
+            lengths = text_index[1:] - text_index[:-1]
+
+            def torch_filter(buf, needle, equal):  # the first len(needle) bytes of every record gathered and compared, the lengths tested, nonzero
+                d_needle = torch.frombuffer(bytearray(needle), dtype=torch.uint8).to(dev)
+                at = (text_index[:-1].unsqueeze(1) + torch.arange(len(needle), device=dev).unsqueeze(0)).clamp_(max=total - 1)
+                same = (buf[at] == d_needle.unsqueeze(0)).all(dim=1) & ((lengths == len(needle)) if equal else (lengths >= len(needle)))
+                return same.nonzero().squeeze(1)
+
+            needles = {"prefix": (key[:MATCH_PREFIX_LEN], N.ET_MATCH_PREFIX), "equal": (key[:4096], N.ET_MATCH_EQUAL)}
+            needles = {name: (needle, mode, torch_filter(text, needle, name == "equal")) for name, (needle, mode) in needles.items()}
+            assert needles["prefix"][2].numel() >= chosen.size and needles["equal"][2].numel() == (chosen.size if len(key) <= 4096 else 0)
+            entry = {"records": count, "chosen": int(chosen.size), "text_bytes": total, "body_bytes": body_bytes}
+            if leg == "match":
+                d_rows = torch.zeros(count, dtype=torch.int32, device=dev)
+                mres = N.MatchResult()
+
+                def call(needle, mode, rows=d_rows):
+                    assert L.et_match_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, needle, len(needle), mode,
+                                                    None if rows is None else rows.data_ptr(), count, None, ctypes.byref(mres)) == 0, L.et_last_error(h)
+                    assert mres.n_failed == 0
+
+                for name, (needle, mode, want) in needles.items():
+                    call(needle, mode)
+                    torch.cuda.synchronize()
+                    assert mres.n_match == want.numel() and torch.equal(d_rows[: mres.n_match].long(), want), "the rows differ from the records chosen"
+                    entry[name] = {"needle_bytes": len(needle), "rows": int(mres.n_match), **timed(lambda: call(needle, mode))}
+                    entry[name]["count_only"] = timed(lambda: call(needle, mode, None))
+            else:
+                dec = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
+
+                def baseline(needle, equal):
+                    assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, dec.data_ptr(), total, None,
+                                                     None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.n_failed == 0 and res.n_short == 0
+                    return torch_filter(dec, needle, equal)
+
+                for name, (needle, mode, want) in needles.items():
+                    assert torch.equal(baseline(needle, name == "equal"), want), "the rows differ from the records chosen"
+                    entry[name] = {"needle_bytes": len(needle), "rows": int(want.numel()), **timed(lambda: baseline(needle, name == "equal"))}
+                del dec
+            shape[sel_name] = entry
+            del text, bodies
+        results[shape_name] = shape
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match")
+    ap.add_argument("--shapes", default="")  # (the match legs: a comma list of shape names, e.g. 262144x16-48; default: all)
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
     ap.add_argument("--lib")
     a = ap.parse_args()
+    if a.leg and a.leg.startswith("match"):
+        return _match_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -295,9 +432,11 @@ def main():
         legs += [("packed_baseline", "dense", a.batch_lib or here), ("packed", "packed", here)]
     if "gather" in a.legs.split(","):
         legs += [("gather_baseline", "gather_baseline", a.batch_lib or here), ("gather", "gather", here)]
+    if "match" in a.legs.split(","):
+        legs += [("match_baseline", "match_baseline", a.batch_lib or here), ("match", "match", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
     for name, leg, lib in legs:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib], capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib, "--shapes", a.shapes], capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"leg {name} failed ({r.returncode})")
@@ -312,6 +451,8 @@ def main():
     if "gather" in out:  # > 1: the gather call is the faster one; identity_extra_ms: what the identity takes beyond a packed decode plus a sizes-only gather
         out["gather_vs_baseline"] = {k: {n: round(out["gather_baseline"][k][n]["ms"] / out["gather"][k][n]["ms"], 2) for n in SELECTIONS} for k in out["gather"]}
         out["gather_identity_extra_ms"] = {k: round(v["identity"]["ms"] - v["identity"]["packed_decode"]["ms"] - v["identity"]["sizes_only"]["ms"], 4) for k, v in out["gather"].items()}
+    if "match" in out:  # > 1: the match call is the faster one
+        out["match_vs_baseline"] = {k: {sel: {m: round(out["match_baseline"][k][sel][m]["ms"] / e[m]["ms"], 2) for m in ("prefix", "equal")} for sel, e in v.items()} for k, v in out["match"].items()}
     line = json.dumps(out)
     print(line)
     if a.out:
