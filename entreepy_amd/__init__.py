@@ -11,6 +11,7 @@ from .codec import (  # noqa: F401
     EmptyInputError,
     EncodeFlags,
     EntreepyError,
+    JoinResult,
     MATCH_EQUAL,
     MATCH_NOT,
     MATCH_PREFIX,

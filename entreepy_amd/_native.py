@@ -116,6 +116,21 @@ class MatchResult(ctypes.Structure):
 
 ET_MATCH_EQUAL, ET_MATCH_PREFIX, ET_MATCH_NOT = 0, 1, 0x100  # et_match_packed_device's mode
 
+
+class JoinResult(ctypes.Structure):
+    """struct et_join_result: what et_join_packed_device reports about the store and the key set."""
+
+    _fields_ = [
+        ("n_match", ctypes.c_uint64),
+        ("n_failed", ctypes.c_uint64),
+        ("first_failed", ctypes.c_uint64),
+        ("n_keys_failed", ctypes.c_uint64),
+        ("first_key_failed", ctypes.c_uint64),
+        ("first_status", ctypes.c_int32),
+        ("first_key_status", ctypes.c_int32),
+    ]
+
+
 # int (*et_allgather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
@@ -169,6 +184,12 @@ SIGNATURES = {
     "et_match_pattern_max": (_sz, []),
     "et_match_result_size": (_sz, []),
     "et_match_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _sz, _vp, ctypes.POINTER(MatchResult)]),
+    "et_join_result_size": (_sz, []),
+    "et_join_keys_max": (_sz, []),
+    "et_join_hash": (_u64, [_vp, _sz, _u64]),
+    "et_join_table_slots": (_sz, [_sz]),
+    "et_join_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(JoinResult)]),
+    "et_selftest_join_hash": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),
@@ -254,5 +275,7 @@ def lib():
             raise ImportError(f"{LIB_PATH}: et_packed_result is {L.et_packed_result_size()} bytes there, {ctypes.sizeof(PackedResult)} in this binding")
         if L.et_match_result_size() != ctypes.sizeof(MatchResult):
             raise ImportError(f"{LIB_PATH}: et_match_result is {L.et_match_result_size()} bytes there, {ctypes.sizeof(MatchResult)} in this binding")
+        if L.et_join_result_size() != ctypes.sizeof(JoinResult):
+            raise ImportError(f"{LIB_PATH}: et_join_result is {L.et_join_result_size()} bytes there, {ctypes.sizeof(JoinResult)} in this binding")
         _lib = L
     return _lib

@@ -65,6 +65,18 @@ class MatchResult:  # struct et_match_result, and the call's own status in front
     pattern_bits: int
 
 
+@dataclass
+class JoinResult:  # struct et_join_result, and the call's own status in front
+    status: int
+    n_match: int
+    n_failed: int
+    first_failed: int
+    n_keys_failed: int
+    first_key_failed: int
+    first_status: int
+    first_key_status: int
+
+
 MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT = N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_MATCH_NOT  # match_packed_device's mode
 
 
@@ -538,6 +550,32 @@ class Context:
             _check(rc, self._h)
         return MatchResult(rc, res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
 
+    def join_packed_device(self, codebook, bodies, body_index, text_index, key_bodies, key_body_index, key_text_index, mode=0, rows=None, key_of_row=None, status=None,
+                           key_status=None):
+        """The records of the store (bodies, body_index, text_index: match_packed_device's) that equal SOME key of the key set
+        (key_bodies, key_body_index, key_text_index: a packed store under the same codebook, on the device) -- with mode=MATCH_NOT the
+        valid records that equal none -- decided on the compressed bytes through a hash table, nothing decoded and no key brought to
+        the host.  rows: int32/uint32 CUDA tensor that takes the selected record numbers, ascending; None: count only.  key_of_row:
+        optional tensor like rows (not with MATCH_NOT): the lowest key number equal to each selected record.  status, key_status:
+        optional uint8 CUDA tensors of one et_status byte per record / per key; a failed record is never selected, a failed key
+        equals nothing.  An empty key set (key_body_index of one entry) selects nothing.  -> JoinResult; .status is ET_OK or
+        ET_ERR_CAP (no row written, .n_match = the room needed); any other failure of the call raises.  Stream-ordered like
+        decode_packed_device."""
+        n, n_keys = text_index.numel() - 1, key_text_index.numel() - 1
+        for t in (rows, key_of_row):
+            if t is not None:
+                assert t.is_cuda and t.dim() == 1 and t.element_size() == 4 and t.is_contiguous() and not t.is_floating_point(), "rows and key_of_row are 1-D CUDA tensors of 32-bit integers"
+        assert key_of_row is None or (rows is not None and key_of_row.numel() >= rows.numel()), "key_of_row is as large as rows"
+        res = N.JoinResult()
+        self._bind()
+        rc = N.lib().et_join_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                           key_bodies.data_ptr(), key_bodies.numel(), self._index_ptr(key_body_index, n_keys), self._index_ptr(key_text_index), n_keys, int(mode),
+                                           None if rows is None else rows.data_ptr(), 0 if rows is None else rows.numel(), None if key_of_row is None else key_of_row.data_ptr(),
+                                           None if status is None else status.data_ptr(), None if key_status is None else key_status.data_ptr(), ctypes.byref(res))
+        if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
+            _check(rc, self._h)
+        return JoinResult(rc, res.n_match, res.n_failed, res.first_failed, res.n_keys_failed, res.first_key_failed, res.first_status, res.first_key_status)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -630,6 +668,30 @@ class Context:
         _check(res.status, self._h)
         if res.n_failed:
             raise EntreepyError(res.first_status, f"match_packed: record {res.first_failed}")
+        return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
+
+    def join_packed(self, codebook, blob, out_index, lengths, key_blob, key_index, key_lengths, mode=0):
+        """decode_packed's store and a key set of the same form (e.g. encode_packed's of the keys) -> [the numbers of the records that
+        equal some key] -- with MATCH_NOT those that equal none --, ascending, through one join_packed_device call."""
+        import torch
+
+        out_index, key_index = np.asarray(out_index, dtype=np.uint64), np.asarray(key_index, dtype=np.uint64)
+        lengths, key_lengths = np.asarray(lengths, dtype=np.uint64), np.asarray(key_lengths, dtype=np.uint64)
+        assert out_index.size == lengths.size + 1 and key_index.size == key_lengths.size + 1
+        if not lengths.size:
+            return []
+        sides = []
+        for b, index, lens in ((blob, out_index, lengths), (key_blob, key_index, key_lengths)):
+            d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(b), dtype=np.uint8)), index)
+            text_index = np.concatenate(([0], np.cumsum(lens))).astype(np.uint64)
+            sides += [d_blob, d_body_index, torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)]
+        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=sides[0].device)
+        res = self.join_packed_device(codebook, *sides, mode=mode, rows=d_rows)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"join_packed: record {res.first_failed}")
+        if res.n_keys_failed:
+            raise EntreepyError(res.first_key_status, f"join_packed: key {res.first_key_failed}")
         return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
 
     # -- staged calls (sharded encode) ----------------------------------------------

@@ -42,9 +42,17 @@
 // It has a pinned region for that upload, shares the report slot and the epoch word, and lays ctx->packed_ws out its own way (the
 // counters where the other calls keep them; the pattern, the tile counts, the tiles' first places and the ballot masks behind).
 // Its report leaves with the scan: k_match_emit decides from the total the scan stored whether the rows fit, as k_packed_pack does.
+//
+// The join call (et_join_packed_device) takes its keys from device memory too -- a second packed store -- so nothing but counters goes up:
+//   join     zeroed counters -> one upload -> clear -> k_join_build -> k_join_flag -> k_packed_scan; (poll) the report -> (unless count only) the emit
+// It has a pinned region for the 64 bytes of first counter values, shares the report slot and the epoch word, and lays ctx->packed_ws
+// out its own way (the counters where the other calls keep them; the tile counts, the tiles' first places, the ballot masks, a key
+// number per record and the hash table behind).  The report's words come from two kernels: the keys' counters from k_join_flag's first
+// workgroup (they are final when it starts), the rest from the scan behind it, which hands over.
 #include "et_ctx.h"
 
 #include "et_batch.h"
+#include "et_join.h"
 
 #include <algorithm>
 #include <vector>
@@ -71,7 +79,9 @@ constexpr size_t PIN_PK_REPORT = PIN_PK_STATS + et::PACKED_WORDS * 8;  // u64[PA
 // ... and the match call's one copy: the counters' first values, then the encoded needle (zero-padded to a multiple of 4 bytes)
 constexpr size_t PIN_MT_STATS = PIN_PK_REPORT + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
 constexpr size_t PIN_MT_PATTERN = PIN_MT_STATS + et::PACKED_WORDS * 8;  // MATCH_PATTERN_BYTES
-constexpr size_t PIN_BYTES = PIN_MT_PATTERN + et::MATCH_PATTERN_BYTES;
+// ... and the join call's: the counters' first values
+constexpr size_t PIN_JN_STATS = PIN_MT_PATTERN + et::MATCH_PATTERN_BYTES;  // u64[PACKED_WORDS]
+constexpr size_t PIN_BYTES = PIN_JN_STATS + et::PACKED_WORDS * 8;
 static_assert(PIN_PK_TABLE % 16 == 0 && PIN_MT_STATS % 16 == 0, "layout of the pinned block");
 // the packed calls' device workspace: the same table and counters, then a size word per record
 constexpr size_t PK_UPLOAD = 2048 + et::PACKED_WORDS * 8, PK_SIZES = 4096;
@@ -79,6 +89,10 @@ constexpr size_t PK_UPLOAD = 2048 + et::PACKED_WORDS * 8, PK_SIZES = 4096;
 // count per tile, the tiles' first places (tiles + 1) and four masks per tile
 constexpr size_t MT_STATS = 2048, MT_PATTERN = MT_STATS + et::PACKED_WORDS * 8, MT_COUNTS = MT_PATTERN + et::MATCH_PATTERN_BYTES;
 static_assert(MT_PATTERN % 16 == 0 && MT_COUNTS % 16 == 0, "k_match_flag loads pattern words, k_packed_scan 16 bytes of counts");
+// ... as the join call lays it out: the counters, then a count per tile, the tiles' first places (tiles + 1), four masks per tile, a
+// key number per record and the table's slots
+constexpr size_t JN_STATS = 2048, JN_COUNTS = JN_STATS + et::PACKED_WORDS * 8;
+static_assert(JN_COUNTS % 16 == 0 && PIN_JN_STATS % 8 == 0, "k_packed_scan loads 16 bytes of counts");
 static_assert(int(et::PACKED_OK) == int(ET_OK) && int(et::PACKED_ARG) == int(ET_ERR_ARG) && int(et::PACKED_UNSUPPORTED) == int(ET_ERR_UNSUPPORTED), "a record's status byte is its et_status");
 static_assert(sizeof(et::SharedJob) == 24 && PIN_SH_TABLE % 16 == 0, "layout of the pinned block");
 static_assert(sizeof(et::BatchSpan) == 16 && sizeof(et::BatchEncJob) == 32 && sizeof(et::BatchDecJob) == 40, "job records are plain, packed data");
@@ -412,6 +426,97 @@ extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const 
         res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
     }
     if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records match than cap_rows");  // (k_match_emit saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_join_keys_max(void) { return et::ET_JOIN_KEYS_MAX; }
+
+extern "C" size_t et_join_result_size(void) { return sizeof(et_join_result); }
+
+extern "C" size_t et_join_table_slots(size_t n_keys) { return et::et_join_slots_for(std::min(n_keys, et::ET_JOIN_KEYS_MAX)); }
+
+extern "C" uint64_t et_join_hash(const uint8_t *body, size_t n_bytes, uint64_t length) {
+    uint64_t sum = 0;
+    for (size_t i = 0; 8 * i < n_bytes; ++i) {
+        uint64_t word = 0;
+        for (size_t k = 0; k < std::min<size_t>(8, n_bytes - 8 * i); ++k) word |= static_cast<uint64_t>(body[8 * i + k]) << (8 * k);
+        sum += et::et_join_term(i, word);
+    }
+    return et::et_join_finish(sum, n_bytes, length);
+}
+
+extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                     const uint64_t *d_text_index, size_t n_records, const void *d_key_bodies, size_t key_body_bytes, const uint64_t *d_key_body_index,
+                                     const uint64_t *d_key_text_index, size_t n_keys, int mode, uint32_t *d_rows, size_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status,
+                                     uint8_t *d_key_status, et_join_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (n_keys && (!d_key_bodies || !d_key_body_index || !d_key_text_index)) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_key_body_index) | reinterpret_cast<uintptr_t>(d_key_text_index)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_key_of_row)) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    if (n_keys > et::ET_JOIN_KEYS_MAX) return fail(ctx, ET_ERR_ARG, "more keys than et_join_keys_max()");
+    if (mode != 0 && mode != ET_MATCH_NOT) return fail(ctx, ET_ERR_ARG, "unknown mode");
+    if (d_key_of_row && (mode & ET_MATCH_NOT)) return fail(ctx, ET_ERR_ARG, "a record no key equals has no key number");
+    if (d_key_of_row && !d_rows) return fail(ctx, ET_ERR_ARG, "key numbers without rows");
+    *res = et_join_result{};
+    if (n_records == 0) return ET_OK;
+    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    DeviceGuard guard(ctx->device);
+    const uint32_t n = static_cast<uint32_t>(n_records), n_tiles = (n + et::MATCH_TILE - 1) / et::MATCH_TILE;
+    const size_t slots = et::et_join_slots_for(n_keys);
+    const size_t counts_bytes = (static_cast<size_t>(n_tiles) * 4 + 15) & ~static_cast<size_t>(15);
+    const size_t at_base = JN_COUNTS + counts_bytes, at_masks = at_base + (static_cast<size_t>(n_tiles) + 1) * 8;
+    const size_t at_table = at_masks + static_cast<size_t>(n_tiles) * (et::MATCH_TILE / 64) * 8, at_key_of = at_table + slots * 8;
+    ET_TRY(ensure_batch(ctx, 1, 2048));
+    ET_TRY(ensure(ctx, ctx->packed_ws, at_key_of + static_cast<size_t>(n) * 4));
+
+    // the counters' first values: free to fill (this file's header)
+    uint64_t *first = pin<uint64_t>(ctx, PIN_JN_STATS);
+    std::memset(first, 0, et::PACKED_WORDS * 8);
+    first[et::PACKED_FIRST] = first[et::JOIN_KEYS_FIRST] = first[et::JOIN_MIN] = ~0ull;
+    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
+    ET_HIP(hipMemcpyAsync(ws + JN_STATS, first, et::PACKED_WORDS * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_keys) ET_HIP(hipMemsetAsync(ws + at_table, 0xff, slots * 8, ctx->stream));
+    const et::JoinSide records{d_bodies, body_bytes, d_body_index, d_text_index, n, 0};
+    const et::JoinSide keys{d_key_bodies, key_body_bytes, d_key_body_index, d_key_text_index, static_cast<uint32_t>(n_keys), 0};
+    const uint64_t epoch = ++ctx->batch_epoch;
+    et::launch_join(ctx->stream, records, keys, (mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u, reinterpret_cast<unsigned long long *>(ws + at_table), slots, d_rows, cap_rows,
+                    d_key_of_row, d_status, d_key_status, reinterpret_cast<unsigned long long *>(ws + at_masks), reinterpret_cast<uint32_t *>(ws + JN_COUNTS),
+                    reinterpret_cast<uint64_t *>(ws + at_base), reinterpret_cast<uint32_t *>(ws + at_key_of), reinterpret_cast<unsigned long long *>(ws + JN_STATS),
+                    reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
+    ET_HIP(hipGetLastError());
+    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the join's report never reached the host"));
+    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+    if (rep[et::PACKED_N_FAILED] & et::JOIN_FAULT_BIT) return fail(ctx, ET_ERR_HIP, "a probe sequence of the join's table met no empty slot");
+    res->n_match = rep[et::PACKED_BYTES];
+    res->n_failed = rep[et::PACKED_N_FAILED];
+    if (res->n_failed) {
+        res->first_failed = rep[et::PACKED_FIRST] >> 8;
+        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
+    }
+    res->n_keys_failed = rep[et::JOIN_KEYS_FAILED];
+    if (res->n_keys_failed) {
+        res->first_key_failed = rep[et::JOIN_KEYS_FIRST] >> 8;
+        res->first_key_status = static_cast<int32_t>(rep[et::JOIN_KEYS_FIRST] & 0xffu);
+    }
+    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_join_emit saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" int et_selftest_join_hash(et_ctx *ctx, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index, const uint64_t *d_text_index, size_t n,
+                                     uint64_t *d_hash) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!d_bodies || !d_body_index || !d_text_index || !d_hash) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index) | reinterpret_cast<uintptr_t>(d_hash)) & 7)
+        return fail(ctx, ET_ERR_ARG, "an array is not 8-byte aligned");
+    if (n > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    if (n == 0) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    et::launch_join_hash(ctx->stream, et::JoinSide{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n), 0}, d_hash);
+    ET_HIP(hipGetLastError());
+    ET_HIP(hipStreamSynchronize(ctx->stream));
     return ET_OK;
 }
 

@@ -132,4 +132,38 @@ void launch_match(hipStream_t stream, const void *d_bodies, uint64_t body_bytes,
                   const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, unsigned long long *masks, uint32_t *counts,
                   uint64_t *base, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
 
+// The join call (et_join_packed_device): which records of a packed store equal SOME key of a key set -- a packed store itself --
+// decided on the compressed bytes through a hash table in the workspace (et_join.h: the hash, the slot format, the table's size).
+//   (clear)        the table's slots to ET_JOIN_EMPTY: one hipMemsetAsync
+//   k_join_build   one key per lane: judged, its status byte, hashed, inserted by compare-and-swap and linear probing; equal keys
+//                  meet in one slot and atomicMin leaves the lowest number there; the smallest and largest body of the valid keys
+//   k_join_flag    one record per lane, tiles of MATCH_TILE records: judged, its status byte; a record whose body is no longer or
+//                  shorter than some key's is hashed, probed and confirmed by bytes; a u64 ballot mask per 64 records, a u32 count
+//                  per tile and a u32 key number per record into the workspace; its first workgroup reports the keys' counters
+//   k_packed_scan  the tile counts -> the tiles' first places in d_rows, n_match; its report is the call's
+//   k_join_emit    (unless d_rows is null: count only) k_match_emit's ranks; the record's number and, when asked for, its key's
+// A lane hashes and compares a body of up to JOIN_LANE_BYTES alone; a longer one is taken from the ballot and handled by its
+// whole wavefront, 8 bytes per lane and step, as k_match_flag handles its survivors.
+constexpr uint32_t JOIN_LANE_BYTES = 128;  // 16 words of the hash
+constexpr uint32_t JOIN_GRID = 2048;       // workgroups of k_join_build, k_join_flag and k_join_emit at most
+// The join's words of the counters and of the report, beside PACKED_N_FAILED and PACKED_FIRST (the records'): the keys' two, and in
+// the counters the smallest and largest body of a valid key (first values ~0 and 0).  A probe or insert loop that ran through the
+// whole table -- a bug -- sets JOIN_FAULT_BIT in PACKED_N_FAILED (a count is below 2^31), which k_packed_scan reports as it finds it.
+enum JoinWord { JOIN_KEYS_FAILED = 4, JOIN_KEYS_FIRST = 5, JOIN_MIN = 6, JOIN_MAX = 7 };
+constexpr unsigned long long JOIN_FAULT_BIT = 1ull << 63;
+struct JoinSide {  // a packed store on the device: the records', or the keys'
+    const void *bodies;
+    uint64_t body_bytes;
+    const uint64_t *body_index, *text_index;
+    uint32_t n, pad;
+};
+// table: `slots` u64 (a power of two, at least 2 * keys.n); masks, counts, base: launch_match's; key_of: a u32 per record -- all
+// workspace.  flags: MATCH_F_NOT or 0.  The report ({n_match, failed, first << 8 | status} by the scan, the keys' two by k_join_flag
+// in front of it, then `epoch`) leaves with the scan.
+void launch_join(hipStream_t stream, const JoinSide &records, const JoinSide &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,
+                 uint64_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status, uint8_t *d_key_status, unsigned long long *masks, uint32_t *counts, uint64_t *base,
+                 uint32_t *key_of, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
+// et_selftest_join_hash: d_hash[b] = the hash of record b as k_join_build and k_join_flag compute it (a failed record's entry is left).
+void launch_join_hash(hipStream_t stream, const JoinSide &records, uint64_t *d_hash);
+
 }  // namespace et

@@ -23,6 +23,10 @@
 //   match    k_match_flag    one lane per record: judged, compared with the encoded needle on the compressed bytes; ballot masks, tile counts
 //            k_packed_scan   the tile counts -> each tile's first place among the rows, the report
 //            k_match_emit    the selected record numbers, ascending, by popcount ranks
+//   join     k_join_build    one lane per key of a key set: judged, hashed on the compressed bytes, inserted into a table in the workspace
+//            k_join_flag     one lane per record: judged, hashed, probed, every hit confirmed by bytes; ballot masks, tile counts, key numbers
+//            k_packed_scan   as in the match
+//            k_join_emit     k_match_emit, with the lowest equal key's number beside the record's
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -31,6 +35,9 @@
 #include "et_batch.h"
 
 #include "et_device.h"
+
+#define ET_JOIN_FN __host__ __device__ __forceinline__
+#include "et_join.h"
 
 namespace et {
 
@@ -948,7 +955,329 @@ __global__ __launch_bounds__(BB) void k_match_emit(const unsigned long long *__r
 }
 
 // --------------------------------------------------------------------------------
+// The join call: which records of a packed store equal SOME key of a key set, itself a packed store under the same table, decided on
+// the compressed bytes.  Under one table the encoder is deterministic, so two records have the same text exactly when they have the
+// same length (symbols), the same body byte count and the same body bytes -- for bodies as the encoders write them; a body of no
+// bytes under a length above zero (a record kept raw elsewhere) equals nothing, on either side.  The keys go into a hash table in the
+// workspace (et_join.h: the hash, a slot = tag << 32 | key number, ET_JOIN_EMPTY), the records probe it, and every hit is confirmed by
+// length, byte count and bytes.  In stream order, the host waiting for the scan alone:
+//   (clear)        hipMemsetAsync: every slot ET_JOIN_EMPTY
+//   k_join_build   per key: judged (k_gather_plan's rule), its status byte, hashed, inserted
+//   k_join_flag    per record: judged, its status byte, hashed, probed, confirmed; masks, tile counts and key numbers into the workspace
+//   k_packed_scan  the tile counts -> each tile's first place in d_rows, and the report
+//   k_join_emit    k_match_emit, with the key number beside the record number where asked for
+// No workgroup waits for another: an insert is a compare-and-swap per slot visited, and every probe and insert loop ends after
+// `slots` trips at the latest -- with a table at most half full it ends at an empty slot long before; a loop that runs out sets the
+// fault bit (JOIN_FAULT_BIT of the records' failure count, which the scan reports as it is), and the host returns ET_ERR_HIP.
+// --------------------------------------------------------------------------------
+constexpr uint32_t JOIN_NONE = 0xffffffffu;  // key_of[b] of a record that equals no key
+
+// Word i (8 i < nb) of the body of nb bytes at `body`, any alignment, zero-extended: from the aligned 8-byte words that hold a byte of
+// it -- one, or two -- shifted into place, as k_match_flag reads its head.
+__device__ __forceinline__ uint64_t body_word(uintptr_t body, uint64_t nb, uint64_t i) {
+    const uint64_t left = nb - 8 * i;
+    const uint32_t cnt = left < 8 ? static_cast<uint32_t>(left) : 8u;
+    const uintptr_t a = body + 8 * i;
+    const uint64_t *q = reinterpret_cast<const uint64_t *>(a & ~static_cast<uintptr_t>(7));
+    const uint32_t lead = static_cast<uint32_t>(a & 7);
+    uint64_t v = q[0] >> (8 * lead);
+    if (lead + cnt > 8) v |= q[1] << (64 - 8 * lead);  // (lead > 0 here; q[1] holds one of the cnt bytes)
+    if (cnt < 8) v &= (1ull << (8 * cnt)) - 1ull;
+    return v;
+}
+
+// The sum of the hash's terms over a whole body by one lane, and over a body shared by the 64 lanes of a wavefront (every lane gets it).
+__device__ __forceinline__ uint64_t lane_terms(uintptr_t body, uint64_t nb) {
+    uint64_t sum = 0;
+    for (uint64_t i = 0; 8 * i < nb; ++i) sum += et_join_term(i, body_word(body, nb, i));
+    return sum;
+}
+
+__device__ __forceinline__ uint64_t wave_terms(uintptr_t body, uint64_t nb, uint32_t lane) {
+    uint64_t sum = 0;
+    for (uint64_t i = lane; 8 * i < nb; i += 64) sum += et_join_term(i, body_word(body, nb, i));
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    return sum;
+}
+
+// Are the nb bytes at a and at b the same?  By one lane; by a wavefront (the same answer in every lane), which leaves at the first
+// step of 512 bytes with a difference.
+__device__ __forceinline__ bool lane_same(uintptr_t a, uintptr_t b, uint64_t nb) {
+    for (uint64_t i = 0; 8 * i < nb; ++i)
+        if (body_word(a, nb, i) != body_word(b, nb, i)) return false;
+    return true;
+}
+
+__device__ __forceinline__ bool wave_same(uintptr_t a, uintptr_t b, uint64_t nb, uint32_t lane) {
+    for (uint64_t i0 = 0; 8 * i0 < nb; i0 += 64) {
+        const uint64_t i = i0 + lane;
+        const bool differs = 8 * i < nb && body_word(a, nb, i) != body_word(b, nb, i);
+        if (__any(differs)) return false;
+    }
+    return true;
+}
+
+// The hash of one item per lane, called by whole wavefronts: a lane that wants one and whose body is at most JOIN_LANE_BYTES long walks
+// it alone; the lanes with longer ones are taken one at a time from the ballot and the wavefront walks that body together.
+__device__ __forceinline__ uint64_t join_hash_lanes(bool want, uintptr_t body, uint64_t nb, uint64_t len, uint32_t lane) {
+    uint64_t h = 0;
+    if (want && nb <= JOIN_LANE_BYTES) h = et_join_finish(lane_terms(body, nb), nb, len);
+    unsigned long long longs = __ballot(want && nb > JOIN_LANE_BYTES);
+    while (longs) {
+        const int src = __ffsll(longs) - 1;
+        longs &= longs - 1;
+        const uint64_t sum = wave_terms(__shfl(static_cast<uint64_t>(body), src, 64), __shfl(nb, src, 64), lane);
+        if (static_cast<int>(lane) == src) h = et_join_finish(sum, nb, len);
+    }
+    return h;
+}
+
+// An item as its kernel judged it: where its body lies, its byte count and its length.  Of a key in a slot: read again from the keys'
+// offsets -- only a valid key is ever inserted.
+struct JoinItem {
+    uintptr_t body;
+    uint64_t nb, len;
+};
+
+__device__ __forceinline__ JoinItem key_item(const JoinSide &keys, uint32_t k) {
+    const uint64_t b0 = keys.body_index[k], b1 = keys.body_index[k + 1];
+    return JoinItem{reinterpret_cast<uintptr_t>(keys.bodies) + b0, b1 - b0, keys.text_index[k + 1] - keys.text_index[k]};
+}
+
+// Key k into the table: linear probing from hash & slot_mask.  An empty slot is taken by compare-and-swap.  A slot with this tag
+// holds a key that may be equal: if it is, the slot keeps the lower of the two numbers (atomicMin; the tags are the same) and the
+// insert is over -- a slot never becomes empty again and keeps its content's text, so equal keys all end in the first slot of their
+// common probe sequence that no other text holds, whatever the order.  false: `slots` trips without an end.
+// WAVE: the whole wavefront inserts one key (the arguments are the same in every lane); lane 0 issues the atomics.
+template <bool WAVE>
+__device__ __forceinline__ bool join_insert(const JoinSide &keys, unsigned long long *table, uint64_t slot_mask, uint32_t k, uint64_t h, const JoinItem &me, uint32_t lane) {
+    const unsigned long long word = (h & 0xffffffff00000000ull) | k;
+    uint64_t pos = h & slot_mask;
+    for (uint64_t trip = 0; trip <= slot_mask; ++trip, pos = (pos + 1) & slot_mask) {
+        unsigned long long old = 0;
+        if (!WAVE || lane == 0) old = atomicCAS(table + pos, ET_JOIN_EMPTY, word);
+        if (WAVE) old = __shfl(old, 0, 64);
+        if (old == ET_JOIN_EMPTY) return true;
+        if ((old ^ word) >> 32) continue;
+        const JoinItem other = key_item(keys, static_cast<uint32_t>(old));
+        if (other.len != me.len || other.nb != me.nb) continue;
+        if (!(WAVE ? wave_same(me.body, other.body, me.nb, lane) : lane_same(me.body, other.body, me.nb))) continue;
+        if (!WAVE || lane == 0) atomicMin(table + pos, word);
+        return true;
+    }
+    return false;
+}
+
+// The key that equals `me`, or JOIN_NONE: the probe sequence up to its first empty slot; a slot with the hash's tag is confirmed by
+// length, byte count and bytes, and passed when they differ.  The table is final (k_join_build is over): plain loads.
+template <bool WAVE>
+__device__ __forceinline__ uint32_t join_probe(const JoinSide &keys, const unsigned long long *table, uint64_t slot_mask, uint64_t h, const JoinItem &me, uint32_t lane, bool *fault) {
+    uint64_t pos = h & slot_mask;
+    for (uint64_t trip = 0; trip <= slot_mask; ++trip, pos = (pos + 1) & slot_mask) {
+        const unsigned long long slot = table[pos];
+        if (slot == ET_JOIN_EMPTY) return JOIN_NONE;
+        if ((slot ^ h) >> 32) continue;
+        const JoinItem other = key_item(keys, static_cast<uint32_t>(slot));
+        if (other.len != me.len || other.nb != me.nb) continue;
+        if (WAVE ? wave_same(me.body, other.body, me.nb, lane) : lane_same(me.body, other.body, me.nb)) return static_cast<uint32_t>(slot);
+    }
+    *fault = true;
+    return JOIN_NONE;
+}
+
+// k_join_build: tiles of 256 keys, one per lane.  A key is judged as k_match_flag judges a record, its status byte stored, its failure
+// tallied into the keys' two counters; a valid key -- unless it is a body of no bytes under a length above zero, which equals
+// nothing -- is hashed and inserted, alone up to JOIN_LANE_BYTES of body, by its wavefront above.  The smallest and largest body of
+// the inserted keys go to JOIN_MIN and JOIN_MAX: one pair of atomics per workgroup.  LDS: 8 + 8 + 8 + 8 words.
+__global__ __launch_bounds__(BB) void k_join_build(JoinSide keys, unsigned long long *__restrict__ table, uint64_t slot_mask, uint8_t *__restrict__ d_key_status,
+                                                   unsigned long long *__restrict__ stats) {
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64], s_min[BB / 64], s_max[BB / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n_tiles = (keys.n + MATCH_TILE - 1) / MATCH_TILE;
+    unsigned long long failed = 0, first = ~0ull, lo = ~0ull, hi = 0;
+    bool fault = false;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t k = tile * MATCH_TILE + tid;  // (n <= 2^24: no wrap)
+        bool enter = false;
+        JoinItem me{0, 0, 0};
+        if (k < keys.n) {
+            const uint64_t b0 = keys.body_index[k], b1 = keys.body_index[k + 1], t0 = keys.text_index[k], t1 = keys.text_index[k + 1];
+            uint32_t status = PACKED_ARG;
+            if (b0 <= b1 && b1 <= keys.body_bytes && t0 <= t1) status = t1 - t0 > BATCH_SMALL_MAX ? PACKED_UNSUPPORTED : PACKED_OK;
+            if (d_key_status) d_key_status[k] = static_cast<uint8_t>(status);
+            if (status) {
+                ++failed;
+                const unsigned long long key = static_cast<unsigned long long>(k) << 8 | status;  // (k ascends in a lane: its first is its lowest)
+                if (key < first) first = key;
+            } else {
+                me = JoinItem{reinterpret_cast<uintptr_t>(keys.bodies) + b0, b1 - b0, t1 - t0};
+                enter = me.nb > 0 || me.len == 0;
+                if (enter) {
+                    if (me.nb < lo) lo = me.nb;
+                    if (me.nb > hi) hi = me.nb;
+                }
+            }
+        }
+        const uint64_t h = join_hash_lanes(enter, me.body, me.nb, me.len, lane);
+        if (enter && me.nb <= JOIN_LANE_BYTES && !join_insert<false>(keys, table, slot_mask, k, h, me, lane)) fault = true;
+        unsigned long long longs = __ballot(enter && me.nb > JOIN_LANE_BYTES);
+        while (longs) {
+            const int src = __ffsll(longs) - 1;
+            longs &= longs - 1;
+            const JoinItem it{static_cast<uintptr_t>(__shfl(static_cast<uint64_t>(me.body), src, 64)), __shfl(me.nb, src, 64), __shfl(me.len, src, 64)};
+            if (!join_insert<true>(keys, table, slot_mask, __shfl(k, src, 64), __shfl(h, src, 64), it, lane)) fault = true;
+        }
+    }
+    if (fault) atomicOr(stats + PACKED_N_FAILED, JOIN_FAULT_BIT);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long other_lo = __shfl_xor(lo, d, 64), other_hi = __shfl_xor(hi, d, 64);
+        if (other_lo < lo) lo = other_lo;
+        if (other_hi > hi) hi = other_hi;
+    }
+    if (lane == 0) {
+        s_min[wave] = lo;
+        s_max[wave] = hi;
+    }
+    tally_lanes(failed, first, s_failed, s_first, stats + (JOIN_KEYS_FAILED - PACKED_N_FAILED));  // (the keys' pair of counters lies like the records')
+    if (tid == 0) {
+        for (int w = 0; w < BB / 64; ++w) {
+            if (s_min[w] < lo) lo = s_min[w];
+            if (s_max[w] > hi) hi = s_max[w];
+        }
+        if (lo <= hi) {  // (a key went in)
+            atomicMin(stats + JOIN_MIN, lo);
+            atomicMax(stats + JOIN_MAX, hi);
+        }
+    }
+}
+
+// k_join_flag: k_match_flag's tiles, judgement, status bytes, tally, masks and counts.  A valid record whose body is shorter than
+// every inserted key's or longer (JOIN_MIN, JOIN_MAX: final, k_join_build is over) is decided without a look at its body -- a store
+// of pages joined against short keys hashes no page -- as is the body of no bytes under a length above zero.  The others are hashed
+// and probed: alone up to JOIN_LANE_BYTES of body, by their wavefront above.  key_of[b] = the key record b equals, or JOIN_NONE.
+// Its first workgroup puts the keys' two counters -- final as well -- into the report, in front of the scan that hands it over; a
+// tick per workgroup to find the last one costs more than the whole kernel (a device-scope fence each).  LDS: 8 + 8 + 8 words.
+__global__ __launch_bounds__(BB) void k_join_flag(JoinSide recs, JoinSide keys, const unsigned long long *__restrict__ table, uint64_t slot_mask, uint32_t flags,
+                                                  unsigned long long *__restrict__ masks, uint32_t *__restrict__ counts, uint32_t *__restrict__ key_of,
+                                                  uint8_t *__restrict__ d_status, unsigned long long *stats, unsigned long long *__restrict__ host_result) {
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    __shared__ uint32_t s_count[2][BB / 64];  // (two sets: a tile's counts are read while the next tile's are stored)
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n_tiles = (recs.n + MATCH_TILE - 1) / MATCH_TILE;
+    const bool negate = flags & MATCH_F_NOT;
+    const unsigned long long lo = stats[JOIN_MIN], hi = stats[JOIN_MAX];
+    if (blockIdx.x == 0 && tid == 0) {
+        host_result[JOIN_KEYS_FAILED] = stats[JOIN_KEYS_FAILED];
+        host_result[JOIN_KEYS_FIRST] = stats[JOIN_KEYS_FIRST];
+        pinned_stores_visible();
+    }
+    unsigned long long failed = 0, first = ~0ull;
+    bool fault = false;
+    uint32_t set = 0;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, set ^= 1) {
+        const uint32_t b = tile * MATCH_TILE + tid;  // (n <= 0x7fffffff: no wrap)
+        bool valid = false, probe = false;
+        JoinItem me{0, 0, 0};
+        if (b < recs.n) {
+            const uint64_t b0 = recs.body_index[b], b1 = recs.body_index[b + 1], t0 = recs.text_index[b], t1 = recs.text_index[b + 1];
+            uint32_t status = PACKED_ARG;
+            if (b0 <= b1 && b1 <= recs.body_bytes && t0 <= t1) status = t1 - t0 > BATCH_SMALL_MAX ? PACKED_UNSUPPORTED : PACKED_OK;
+            if (d_status) d_status[b] = static_cast<uint8_t>(status);
+            if (status) {
+                ++failed;
+                const unsigned long long key = static_cast<unsigned long long>(b) << 8 | status;  // (b ascends in a lane: its first is its lowest)
+                if (key < first) first = key;
+            } else {
+                valid = true;
+                me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + b0, b1 - b0, t1 - t0};
+                probe = (me.nb > 0 || me.len == 0) && me.nb >= lo && me.nb <= hi;
+            }
+        }
+        const uint64_t h = join_hash_lanes(probe, me.body, me.nb, me.len, lane);
+        uint32_t key = JOIN_NONE;
+        if (probe && me.nb <= JOIN_LANE_BYTES) key = join_probe<false>(keys, table, slot_mask, h, me, lane, &fault);
+        unsigned long long longs = __ballot(probe && me.nb > JOIN_LANE_BYTES);
+        while (longs) {
+            const int src = __ffsll(longs) - 1;
+            longs &= longs - 1;
+            const JoinItem it{static_cast<uintptr_t>(__shfl(static_cast<uint64_t>(me.body), src, 64)), __shfl(me.nb, src, 64), __shfl(me.len, src, 64)};
+            const uint32_t found = join_probe<true>(keys, table, slot_mask, __shfl(h, src, 64), it, lane, &fault);
+            if (static_cast<int>(lane) == src) key = found;
+        }
+        if (b < recs.n) key_of[b] = key;
+        const unsigned long long mask = __ballot(valid && (key != JOIN_NONE) != negate);
+        if (lane == 0) {
+            masks[static_cast<uint64_t>(tile) * (MATCH_TILE / 64) + wave] = mask;
+            s_count[set][wave] = __popcll(mask);
+        }
+        __syncthreads();
+        if (tid == 0) counts[tile] = s_count[set][0] + s_count[set][1] + s_count[set][2] + s_count[set][3];
+    }
+    if (fault) atomicOr(stats + PACKED_N_FAILED, JOIN_FAULT_BIT);
+    tally_lanes(failed, first, s_failed, s_first, stats);
+}
+
+// k_join_emit: k_match_emit; beside the record's number its key's (key_of[record]) where key_rows is given.  No LDS.
+__global__ __launch_bounds__(BB) void k_join_emit(const unsigned long long *__restrict__ masks, const uint64_t *__restrict__ base, uint32_t n_tiles,
+                                                  const uint32_t *__restrict__ key_of, uint32_t *__restrict__ rows, uint32_t *__restrict__ key_rows, uint64_t cap_rows) {
+    if (base[n_tiles] > cap_rows) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const unsigned long long *m = masks + static_cast<uint64_t>(tile) * (MATCH_TILE / 64);
+        const unsigned long long mine = m[wave];
+        if (!((mine >> lane) & 1)) continue;
+        uint32_t rank = __popcll(mine & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wave; ++w) rank += __popcll(m[w]);
+        const uint32_t record = tile * MATCH_TILE + tid;
+        rows[base[tile] + rank] = record;
+        if (key_rows) key_rows[base[tile] + rank] = key_of[record];
+    }
+}
+
+// k_join_hash: et_selftest_join_hash -- the hash of every valid record as k_join_build and k_join_flag compute it (join_hash_lanes).
+__global__ __launch_bounds__(BB) void k_join_hash(JoinSide recs, uint64_t *__restrict__ d_hash) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t n_tiles = (recs.n + MATCH_TILE - 1) / MATCH_TILE;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t b = tile * MATCH_TILE + tid;
+        bool valid = false;
+        JoinItem me{0, 0, 0};
+        if (b < recs.n) {
+            const uint64_t b0 = recs.body_index[b], b1 = recs.body_index[b + 1], t0 = recs.text_index[b], t1 = recs.text_index[b + 1];
+            valid = b0 <= b1 && b1 <= recs.body_bytes && t0 <= t1 && t1 - t0 <= BATCH_SMALL_MAX;
+            if (valid) me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + b0, b1 - b0, t1 - t0};
+        }
+        const uint64_t h = join_hash_lanes(valid, me.body, me.nb, me.len, lane);
+        if (valid) d_hash[b] = h;
+    }
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
+
+void launch_join(hipStream_t stream, const JoinSide &records, const JoinSide &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,
+                 uint64_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status, uint8_t *d_key_status, unsigned long long *masks, uint32_t *counts, uint64_t *base,
+                 uint32_t *key_of, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
+    const uint32_t n_tiles = (records.n + MATCH_TILE - 1) / MATCH_TILE, grid = n_tiles < JOIN_GRID ? n_tiles : JOIN_GRID;
+    if (keys.n) {
+        const uint32_t key_tiles = (keys.n + MATCH_TILE - 1) / MATCH_TILE;
+        hipLaunchKernelGGL(k_join_build, dim3(key_tiles < JOIN_GRID ? key_tiles : JOIN_GRID), dim3(BB), 0, stream, keys, table, slots - 1, d_key_status, stats);
+    }
+    hipLaunchKernelGGL(k_join_flag, dim3(grid), dim3(BB), 0, stream, records, keys, static_cast<const unsigned long long *>(table), slots - 1, flags, masks, counts, key_of,
+                       d_status, stats, host_result);
+    hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(counts), n_tiles, base, static_cast<const unsigned long long *>(stats),
+                       host_result, host_done, epoch);
+    if (d_rows)
+        hipLaunchKernelGGL(k_join_emit, dim3(grid), dim3(BB), 0, stream, static_cast<const unsigned long long *>(masks), static_cast<const uint64_t *>(base), n_tiles,
+                           static_cast<const uint32_t *>(key_of), d_rows, d_key_of_row, cap_rows);
+}
+
+void launch_join_hash(hipStream_t stream, const JoinSide &records, uint64_t *d_hash) {
+    const uint32_t n_tiles = (records.n + MATCH_TILE - 1) / MATCH_TILE;
+    hipLaunchKernelGGL(k_join_hash, dim3(n_tiles < JOIN_GRID ? n_tiles : JOIN_GRID), dim3(BB), 0, stream, records, d_hash);
+}
 
 void launch_match(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
                   const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, unsigned long long *masks, uint32_t *counts,

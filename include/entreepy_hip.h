@@ -418,6 +418,70 @@ int et_match_packed_device(et_ctx *ctx, const et_codebook *cb,
                            const uint8_t *needle, size_t needle_len, int mode,   /* needle: HOST memory */
                            uint32_t *d_rows, size_t cap_rows, uint8_t *d_status, et_match_result *res);
 
+/* JOIN: which records of a packed store equal SOME key of a key set -- itself a packed store under the same table, in device
+ * memory (e.g. what et_encode_packed_device made of a key column, or a run of another store) -- decided on the compressed bytes:
+ * key IN (...), a semi-join against another table's key column, with ET_MATCH_NOT an anti-join.  One build pass over the keys (a
+ * hash table in the ctx's workspace) and one probe pass over the records replace one et_match_packed_device call per key.
+ *   Both sides are judged by the match call's rule, each from its own arrays: ET_ERR_ARG unless
+ *     body_index[i] <= body_index[i+1] <= its buffer's bytes (body_bytes, key_body_bytes) and text_index[i] <= text_index[i+1];
+ *     ET_ERR_UNSUPPORTED for a length above the small-stream limit.  A failed record is never selected -- not under ET_MATCH_NOT
+ *     either --, a failed key equals nothing, either fails alone, and no kernel reads where a bad pair points.  d_status[b] (one
+ *     et_status byte per record) and d_key_status[k] (one per key) hold the statuses; either may be NULL.
+ *   Record b EQUALS key k when both are valid, their lengths (text_index differences) are equal, their body byte counts are equal
+ *     and those bytes are identical -- except that a body of no bytes under a length above zero, which is how a record looks whose
+ *     encode failed and which is kept raw elsewhere, equals nothing on either side (not even its like).  A length of 0 with an empty
+ *     body equals a key of the same kind.  Under one table the encoder is deterministic, so for bodies exactly as this library's
+ *     encoders write them (ceil(bits / 8) bytes, the pad bits zero) the join selects b exactly when
+ *     et_match_packed_device(ET_MATCH_EQUAL, needle = key k's text) selects it for some k.  A hand-made body with bytes behind its
+ *     last codeword, or with pad bits that are not zero, can equal a needle under ET_MATCH_EQUAL and does not equal that needle's
+ *     encoder-made key here; the join never selects a record whose stored text differs from every key's.
+ *   mode: 0, or ET_MATCH_NOT: the valid records that equal NO key.  n_keys == 0: nothing equals -- under ET_MATCH_NOT every valid
+ *     record is selected -- and the records are still judged; the key pointers may then be NULL.
+ *   d_rows[0 .. n_match) (32 bits each, 4-byte aligned, on the device) = the selected record numbers, ascending: the gather call's
+ *     d_rows.  Nothing at or beyond d_rows + n_match is written.  d_rows == NULL: count only -- cap_rows is ignored, the status
+ *     bytes and *res are the writing call's.  n_match > cap_rows: the call returns ET_ERR_CAP, no entry of d_rows or d_key_of_row
+ *     is written, d_status and d_key_status are complete and res->n_match is the room needed.
+ *   d_key_of_row (may be NULL; as large as d_rows and written only where d_rows is): d_key_of_row[i] = the LOWEST key number whose
+ *     content equals record d_rows[i] -- key sets may hold duplicates, and the answer does not depend on the order in which the
+ *     device inserted them.
+ *   et_join_hash, et_join_table_slots (host only): the 64-bit hash of (length, n_bytes, body bytes) the table is built on -- a
+ *     key's first slot is hash & (slots - 1), the next ones follow with wrap-around -- and the slots of a table for n_keys keys: a
+ *     power of two, at least 2 * n_keys.  For tests that craft collisions; the hash never decides alone, every hit is confirmed by
+ *     length, byte count and bytes.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_bodies, d_body_index or d_text_index; with n_keys > 0 a null
+ * d_key_bodies, d_key_body_index or d_key_text_index; an offset array that is not 8-byte aligned, d_rows or d_key_of_row not 4-byte
+ * aligned; n_records above 0x7fffffff; n_keys above et_join_keys_max(); a mode other than 0 or ET_MATCH_NOT; d_key_of_row with
+ * ET_MATCH_NOT, or with d_rows == NULL -- all checked before anything touches a device, *res untouched), ET_ERR_UNSUPPORTED (the
+ * table is not complete: nothing is enqueued), ET_ERR_CAP, ET_ERR_HIP, ET_ERR_NOMEM.  n_records == 0: ET_OK, nothing enqueued,
+ * *res zeroed.  One upload (64 bytes of counters), a clear of the table, four launches and one hand-over per call;
+ * stream-ordered like the other packed calls -- *res is final on return, the device arrays once the ctx's stream has drained -- and
+ * it may follow or precede packed, gather, match, shared-table and single-stream calls on one ctx with nothing in between and with
+ * different tables: the keys may come straight from et_encode_packed_device, and d_rows may go straight into
+ * et_decode_packed_gather_device, on the same ctx. */
+typedef struct et_join_result {
+    uint64_t n_match;                       /* rows selected -- also when the call returns ET_ERR_CAP or d_rows is NULL */
+    uint64_t n_failed, first_failed;        /* records whose status is not ET_OK, the lowest of them (valid when n_failed > 0) */
+    uint64_t n_keys_failed, first_key_failed;   /* the same for keys */
+    int32_t first_status, first_key_status; /* et_status of record first_failed, of key first_key_failed */
+} et_join_result;
+size_t et_join_result_size(void);
+size_t et_join_keys_max(void);              /* most keys per call: 1 << 24 */
+uint64_t et_join_hash(const uint8_t *body, size_t n_bytes, uint64_t length);
+size_t et_join_table_slots(size_t n_keys);
+int et_join_packed_device(et_ctx *ctx, const et_codebook *cb,
+                          const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                          const uint64_t *d_text_index, size_t n_records,
+                          const void *d_key_bodies, size_t key_body_bytes, const uint64_t *d_key_body_index,
+                          const uint64_t *d_key_text_index, size_t n_keys,
+                          int mode,             /* 0, or ET_MATCH_NOT: the valid records that equal NO key (anti-join) */
+                          uint32_t *d_rows, size_t cap_rows, uint32_t *d_key_of_row,
+                          uint8_t *d_status, uint8_t *d_key_status, et_join_result *res);
+/* Diagnostics: d_hash[b] (8-byte aligned, on the device) = et_join_hash of every valid record of a packed store as the join's
+ * kernels compute it -- a lane alone, or a wavefront together for a long body; a failed record's entry is left alone.  Returns with
+ * the stream drained. */
+int et_selftest_join_hash(et_ctx *ctx, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                          const uint64_t *d_text_index, size_t n, uint64_t *d_hash);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

@@ -29,6 +29,12 @@ process of its own so that every leg loads exactly one build of the library:
                   of 16 .. 48 bytes.  With it runs match_baseline, what the call replaces -- et_decode_packed_device of the whole store,
                   then the first L bytes of every record gathered, compared, the lengths tested and nonzero, in torch on the device -- on
                   this tree's library or on the one named by --batch-lib (a build of the commit before the call).  --shapes picks shapes.
+  join            et_join_packed_device, one call per key set and selectivity, on this tree's library: the 262 144 key-like records of
+                  16 .. 48 bytes against key sets of 16, 1 024 and 65 536 keys (packed stores on the device themselves), about 0.1 % and
+                  10 % of the records equal to some key, with d_rows and d_key_of_row, and count only.  With it runs join_baseline, what
+                  the call replaces -- one et_match_packed_device(ET_MATCH_EQUAL) per key, the keys' texts on the host, then the union of
+                  their rows sorted in torch -- on this tree's library or on the one named by --batch-lib (a build of the commit before
+                  the call).  Both check their rows against set membership over the plain texts first.
 --legs picks the legs (default: all).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
@@ -39,6 +45,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs packed --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/packed_bench.json
     python tools/batch_bench.py --legs gather --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/gather_bench.json
     python tools/batch_bench.py --legs match --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/match_bench.json
+    python tools/batch_bench.py --legs join --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/join_bench.json
 """
 import argparse
 import ctypes
@@ -411,11 +418,140 @@ def _match_leg(leg, lib_path, shapes):
     print(json.dumps(results))
 
 
+JOIN_KEYS = (16, 1024, 65536)
+JOIN_SELECTIVITIES = (("0.1%", 0.001), ("10%", 0.1))
+
+
+def _join_store(count, size, n_keys, fraction):
+    """-> (text, text_index, key text, key text_index) as numpy arrays: `count` text-like records of size[0] .. size[1] bytes, `fraction` of
+    them copies of one of n_keys text-like keys (the chosen records take the keys in turn; keys beyond their number equal no record)."""
+    import numpy as np
+
+    from tests import corpus
+
+    rng = np.random.default_rng(0x10A5E + count + n_keys + int(fraction * 1000))
+    key_lengths = rng.integers(size[0], size[1] + 1, size=n_keys)
+    key_index = np.concatenate(([0], np.cumsum(key_lengths))).astype(np.uint64)
+    key_text = corpus.text_like(int(key_index[-1]), 0x10A5E + n_keys).copy()
+    chosen = np.sort(rng.choice(count, size=max(int(count * fraction), 1), replace=False))
+    which = np.arange(chosen.size) % n_keys
+    lengths = rng.integers(size[0], size[1] + 1, size=count)
+    lengths[chosen] = key_lengths[which]
+    index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+    text = corpus.text_like(int(index[-1]), 0xB47C4 + count).copy()
+    for r, k in zip(chosen, which):
+        text[int(index[r]) : int(index[r + 1])] = key_text[int(key_index[k]) : int(key_index[k + 1])]
+    return text, index, key_text, key_index
+
+
+def _join_leg(leg, lib_path):
+    """join / join_baseline: per key set and selectivity two packed stores (et_encode_packed_device, untimed), then the timed join: the
+    call with d_rows and d_key_of_row (and count only) -- or what it replaces: one et_match_packed_device(ET_MATCH_EQUAL) per key, then
+    the union of their rows sorted in torch."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
+             "et_match_packed_device"] + (["et_join_packed_device"] if leg == "join" else [])
+    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
+    dev = torch.device("cuda", 0)
+    h = ctypes.c_void_p()
+    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
+    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+
+    def timed(fn):
+        ms = []
+        for rep in range(WARMUP + REPS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep >= WARMUP:
+                ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+    def pack(cb, host_text, index):
+        """-> (bodies, body bytes, body_index, text_index) on the device"""
+        n, total = index.size - 1, int(index[-1])
+        text = torch.from_numpy(host_text).to(dev)
+        cap = L.et_body_bound(ctypes.byref(cb), total) + n
+        bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+        text_index = torch.from_numpy(index.view(np.int64)).to(dev)
+        body_index = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        res = N.PackedResult()
+        assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), n, bodies.data_ptr(), cap, body_index.data_ptr(), None,
+                                         ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+        torch.cuda.synchronize()
+        return bodies, int(res.out_bytes), body_index, text_index
+
+    count, size = KEY_SHAPE
+    shape = {}
+    for n_keys in JOIN_KEYS:
+        per_keys = {}
+        for sel_name, fraction in JOIN_SELECTIVITIES:
+            text, index, key_text, key_index = _join_store(count, size, n_keys, fraction)
+            hist = (np.bincount(text, minlength=256) + np.bincount(key_text, minlength=256)).astype(np.uint64)
+            cb = N.Codebook()
+            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+            bodies, body_bytes, body_index, text_index = pack(cb, text, index)
+            # the expected rows: set membership over the plain texts; the key of a row: the first index of its text among the keys
+            blob, key_blob = text.tobytes(), key_text.tobytes()
+            keys = [key_blob[int(a) : int(b)] for a, b in zip(key_index[:-1], key_index[1:])]
+            first = {}
+            for k, t in enumerate(keys):
+                first.setdefault(t, k)
+            found = [(r, first.get(blob[int(a) : int(b)])) for r, (a, b) in enumerate(zip(index[:-1], index[1:]))]
+            want_rows = [r for r, k in found if k is not None]
+            want_keys = [k for r, k in found if k is not None]
+            entry = {"records": count, "keys": n_keys, "rows": len(want_rows), "body_bytes": body_bytes}
+            d_rows = torch.zeros(count, dtype=torch.int32, device=dev)
+            if leg == "join":
+                key_bodies, key_body_bytes, key_body_index, key_text_index = pack(cb, key_text, key_index)
+                d_key_of_row = torch.zeros(count, dtype=torch.int32, device=dev)
+                jres = N.JoinResult()
+
+                def call(rows=d_rows):
+                    assert L.et_join_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, key_bodies.data_ptr(),
+                                                   key_body_bytes, key_body_index.data_ptr(), key_text_index.data_ptr(), n_keys, 0, None if rows is None else rows.data_ptr(), count,
+                                                   None if rows is None else d_key_of_row.data_ptr(), None, None, ctypes.byref(jres)) == 0, L.et_last_error(h)
+                    assert jres.n_failed == 0 and jres.n_keys_failed == 0
+
+                call()
+                torch.cuda.synchronize()
+                assert jres.n_match == len(want_rows) and d_rows[: jres.n_match].tolist() == want_rows, "the rows differ from set membership over the texts"
+                assert d_key_of_row[: jres.n_match].tolist() == want_keys, "a key number is not the first index of the row's text"
+                entry.update(timed(call))
+                entry["count_only"] = timed(lambda: call(None))
+            else:
+                mres = N.MatchResult()
+
+                def baseline():
+                    at = 0
+                    for t in keys:
+                        assert L.et_match_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, t, len(t),
+                                                        N.ET_MATCH_EQUAL, d_rows.data_ptr() + 4 * at, count - at, None, ctypes.byref(mres)) == 0, L.et_last_error(h)
+                        at += mres.n_match
+                    return torch.sort(d_rows[:at])[0]
+
+                got = baseline()
+                torch.cuda.synchronize()
+                assert got.tolist() == want_rows, "the rows differ from set membership over the texts"
+                entry.update(timed(baseline))
+            per_keys[sel_name] = entry
+            del bodies
+        shape[f"{n_keys}_keys"] = per_keys
+    L.et_ctx_destroy(h)
+    print(json.dumps({f"{count}x{size[0]}-{size[1]}": shape}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join")
     ap.add_argument("--shapes", default="")  # (the match legs: a comma list of shape names, e.g. 262144x16-48; default: all)
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
@@ -423,6 +559,8 @@ def main():
     a = ap.parse_args()
     if a.leg and a.leg.startswith("match"):
         return _match_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
+    if a.leg and a.leg.startswith("join"):
+        return _join_leg(a.leg, a.lib)
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -434,6 +572,8 @@ def main():
         legs += [("gather_baseline", "gather_baseline", a.batch_lib or here), ("gather", "gather", here)]
     if "match" in a.legs.split(","):
         legs += [("match_baseline", "match_baseline", a.batch_lib or here), ("match", "match", here)]
+    if "join" in a.legs.split(","):
+        legs += [("join_baseline", "join_baseline", a.batch_lib or here), ("join", "join", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
     for name, leg, lib in legs:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib, "--shapes", a.shapes], capture_output=True, text=True, timeout=600)
@@ -453,6 +593,9 @@ def main():
         out["gather_identity_extra_ms"] = {k: round(v["identity"]["ms"] - v["identity"]["packed_decode"]["ms"] - v["identity"]["sizes_only"]["ms"], 4) for k, v in out["gather"].items()}
     if "match" in out:  # > 1: the match call is the faster one
         out["match_vs_baseline"] = {k: {sel: {m: round(out["match_baseline"][k][sel][m]["ms"] / e[m]["ms"], 2) for m in ("prefix", "equal")} for sel, e in v.items()} for k, v in out["match"].items()}
+    if "join" in out:  # > 1: the join call is the faster one
+        out["join_vs_baseline"] = {k: {keys: {sel: round(out["join_baseline"][k][keys][sel]["ms"] / e["ms"], 2) for sel, e in v.items()} for keys, v in shape.items()}
+                                   for k, shape in out["join"].items()}
     line = json.dumps(out)
     print(line)
     if a.out:
