@@ -17,6 +17,7 @@ from .codec import (  # noqa: F401
     MATCH_PREFIX,
     MatchResult,
     PackedResult,
+    TakeResult,
     decode,
     default_context,
     encode,

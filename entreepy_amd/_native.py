@@ -131,6 +131,19 @@ class JoinResult(ctypes.Structure):
     ]
 
 
+class TakeResult(ctypes.Structure):
+    """struct et_take_result: what et_take_packed_device reports about the rows and the store it made of them."""
+
+    _fields_ = [
+        ("out_bytes", ctypes.c_uint64),
+        ("text_bytes", ctypes.c_uint64),
+        ("n_failed", ctypes.c_uint64),
+        ("first_failed", ctypes.c_uint64),
+        ("first_status", ctypes.c_int32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
 # int (*et_allgather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
@@ -190,6 +203,8 @@ SIGNATURES = {
     "et_join_table_slots": (_sz, [_sz]),
     "et_join_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(JoinResult)]),
     "et_selftest_join_hash": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "et_take_result_size": (_sz, []),
+    "et_take_packed_device": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(TakeResult)]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),
@@ -277,5 +292,7 @@ def lib():
             raise ImportError(f"{LIB_PATH}: et_match_result is {L.et_match_result_size()} bytes there, {ctypes.sizeof(MatchResult)} in this binding")
         if L.et_join_result_size() != ctypes.sizeof(JoinResult):
             raise ImportError(f"{LIB_PATH}: et_join_result is {L.et_join_result_size()} bytes there, {ctypes.sizeof(JoinResult)} in this binding")
+        if L.et_take_result_size() != ctypes.sizeof(TakeResult):
+            raise ImportError(f"{LIB_PATH}: et_take_result is {L.et_take_result_size()} bytes there, {ctypes.sizeof(TakeResult)} in this binding")
         _lib = L
     return _lib

@@ -77,7 +77,17 @@ class JoinResult:  # struct et_join_result, and the call's own status in front
     first_key_status: int
 
 
-MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT = N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_MATCH_NOT  # match_packed_device's mode
+@dataclass
+class TakeResult:  # struct et_take_result, and the call's own status in front
+    status: int
+    out_bytes: int
+    text_bytes: int
+    n_failed: int
+    first_failed: int
+    first_status: int
+
+
+MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT =N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_MATCH_NOT  # match_packed_device's mode
 
 
 def _check(status, ctx=None):
@@ -576,6 +586,27 @@ class Context:
             _check(rc, self._h)
         return JoinResult(rc, res.n_match, res.n_failed, res.first_failed, res.n_keys_failed, res.first_key_failed, res.first_status, res.first_key_status)
 
+    def take_packed_device(self, bodies, body_index, text_index, rows, out, out_body_index, out_text_index, status=None):
+        """Row k of the NEW store is record rows[k] of the store (bodies, body_index, text_index: decode_packed_gather_device's), in any
+        order, with repeats: its body goes as it is to out[out_body_index[k] : out_body_index[k + 1]], the bodies back to back from 0,
+        and out_text_index[k + 1] - out_text_index[k] is its length -- nothing decoded, no codebook.  rows: int32/uint32 CUDA tensor of
+        record numbers (match_packed_device's or join_packed_device's); out_body_index, out_text_index (written): CUDA tensors of
+        len(rows) + 1 64-bit integers; status: optional uint8 CUDA tensor of one et_status byte per ROW.  A row that fails (a record
+        number beyond the store, a bad pair of offsets, a record above the limits) becomes an empty record.  out=None: sizes only.  out
+        may not overlap bodies.  -> TakeResult; .status is ET_OK or ET_ERR_CAP (nothing written, .out_bytes = the room needed); any
+        other failure of the call raises.  Stream-ordered like decode_packed_device: the three outputs may go straight into
+        join_packed_device (as the key set), decode_packed_device or decode_packed_gather_device."""
+        n = text_index.numel() - 1
+        assert rows.is_cuda and rows.dim() == 1 and rows.element_size() == 4 and rows.is_contiguous() and not rows.is_floating_point(), "rows is a 1-D CUDA tensor of 32-bit integers"
+        res = N.TakeResult()
+        self._bind()
+        rc = N.lib().et_take_packed_device(self._h, bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n, rows.data_ptr(), rows.numel(),
+                                           None if out is None else out.data_ptr(), 0 if out is None else out.numel(), self._index_ptr(out_body_index, rows.numel()),
+                                           self._index_ptr(out_text_index, rows.numel()), None if status is None else status.data_ptr(), ctypes.byref(res))
+        if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
+            _check(rc, self._h)
+        return TakeResult(rc, res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -693,6 +724,34 @@ class Context:
         if res.n_keys_failed:
             raise EntreepyError(res.first_key_status, f"join_packed: key {res.first_key_failed}")
         return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
+
+    def take_packed(self, blob, out_index, lengths, rows):
+        """decode_packed's store and a list of record numbers (any order, repeats allowed) -> (the bodies of those records back to back
+        as bytes, their offsets as a numpy u64 array of len(rows) + 1, their lengths as a numpy u64 array): a store of the same form,
+        as encode_packed of those records' texts gives it, through one take_packed_device call."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert out_index.size == lengths.size + 1
+        if not rows.size:
+            return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
+        good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none)
+        room = int((out_index[good + 1] - out_index[good]).sum())
+        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=d_blob.device)
+        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        res = self.take_packed_device(d_blob, d_body_index, d_text_index, d_rows, d_out, d_new_index, d_new_text)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"take_packed: row {res.first_failed}")
+        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
+        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

@@ -49,6 +49,12 @@
 // out its own way (the counters where the other calls keep them; the tile counts, the tiles' first places, the ballot masks, a key
 // number per record and the hash table behind).  The report's words come from two kernels: the keys' counters from k_join_flag's first
 // workgroup (they are final when it starts), the rest from the scan behind it, which hands over.
+//
+// The take call (et_take_packed_device) has no table at all -- it copies bodies as they are -- so it too sends up nothing but counters:
+//   take     zeroed counters -> one upload -> k_take_plan -> k_take_scan; (poll) the report -> (unless sizes only) k_take_copy
+// It has a pinned region for the 64 bytes of first counter values, shares the report slot and the epoch word, and lays ctx->packed_ws
+// out its own way (the counters where the other calls keep them; a TakeRow of 16 bytes per row behind).  Its report leaves with the scan:
+// k_take_copy decides from the total the scan stored whether the bodies fit, as k_packed_pack does.
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -81,7 +87,9 @@ constexpr size_t PIN_MT_STATS = PIN_PK_REPORT + et::PACKED_WORDS * 8;  // u64[PA
 constexpr size_t PIN_MT_PATTERN = PIN_MT_STATS + et::PACKED_WORDS * 8;  // MATCH_PATTERN_BYTES
 // ... and the join call's: the counters' first values
 constexpr size_t PIN_JN_STATS = PIN_MT_PATTERN + et::MATCH_PATTERN_BYTES;  // u64[PACKED_WORDS]
-constexpr size_t PIN_BYTES = PIN_JN_STATS + et::PACKED_WORDS * 8;
+// ... and the take call's: the counters' first values
+constexpr size_t PIN_TK_STATS = PIN_JN_STATS + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
+constexpr size_t PIN_BYTES = PIN_TK_STATS + et::PACKED_WORDS * 8;
 static_assert(PIN_PK_TABLE % 16 == 0 && PIN_MT_STATS % 16 == 0, "layout of the pinned block");
 // the packed calls' device workspace: the same table and counters, then a size word per record
 constexpr size_t PK_UPLOAD = 2048 + et::PACKED_WORDS * 8, PK_SIZES = 4096;
@@ -93,6 +101,9 @@ static_assert(MT_PATTERN % 16 == 0 && MT_COUNTS % 16 == 0, "k_match_flag loads p
 // key number per record and the table's slots
 constexpr size_t JN_STATS = 2048, JN_COUNTS = JN_STATS + et::PACKED_WORDS * 8;
 static_assert(JN_COUNTS % 16 == 0 && PIN_JN_STATS % 8 == 0, "k_packed_scan loads 16 bytes of counts");
+// ... as the take call lays it out: the counters, then a TakeRow per row where the other calls keep their size words
+constexpr size_t TK_STATS = 2048, TK_PLAN = PK_SIZES;
+static_assert(sizeof(et::TakeRow) == 16 && TK_PLAN % 16 == 0 && PIN_TK_STATS % 8 == 0, "k_take_plan stores a TakeRow as 16 bytes");
 static_assert(int(et::PACKED_OK) == int(ET_OK) && int(et::PACKED_ARG) == int(ET_ERR_ARG) && int(et::PACKED_UNSUPPORTED) == int(ET_ERR_UNSUPPORTED), "a record's status byte is its et_status");
 static_assert(sizeof(et::SharedJob) == 24 && PIN_SH_TABLE % 16 == 0, "layout of the pinned block");
 static_assert(sizeof(et::BatchSpan) == 16 && sizeof(et::BatchEncJob) == 32 && sizeof(et::BatchDecJob) == 40, "job records are plain, packed data");
@@ -502,6 +513,52 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
         res->first_key_status = static_cast<int32_t>(rep[et::JOIN_KEYS_FIRST] & 0xffu);
     }
     if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_join_emit saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_take_result_size(void) { return sizeof(et_take_result); }
+
+extern "C" int et_take_packed_device(et_ctx *ctx, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index, const uint64_t *d_text_index, size_t n_records,
+                                     const uint32_t *d_rows, size_t n_rows, void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index, uint8_t *d_status,
+                                     et_take_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!res || !d_bodies || !d_body_index || !d_text_index || !d_rows || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index) | reinterpret_cast<uintptr_t>(d_out_body_index) |
+         reinterpret_cast<uintptr_t>(d_out_text_index)) & 7)
+        return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_rows) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
+    if (d_out && cap && body_bytes) {  // (in-place compaction is not this call's)
+        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
+        if (o < b + body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps d_bodies");
+    }
+    *res = et_take_result{};
+    if (n_rows == 0) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    ET_TRY(ensure_batch(ctx, 1, 2048));
+    ET_TRY(ensure(ctx, ctx->packed_ws, TK_PLAN + n_rows * sizeof(et::TakeRow)));
+
+    // the counters' first values: free to fill (this file's header)
+    uint64_t *first = pin<uint64_t>(ctx, PIN_TK_STATS);
+    std::memset(first, 0, et::PACKED_WORDS * 8);
+    first[et::PACKED_FIRST] = ~0ull;
+    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
+    ET_HIP(hipMemcpyAsync(ws + TK_STATS, first, et::PACKED_WORDS * 8, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t epoch = ++ctx->batch_epoch;
+    et::launch_take(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), d_rows, static_cast<uint32_t>(n_rows), d_out, cap,
+                    d_out_body_index, d_out_text_index, d_status, reinterpret_cast<et::TakeRow *>(ws + TK_PLAN), reinterpret_cast<unsigned long long *>(ws + TK_STATS),
+                    reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
+    ET_HIP(hipGetLastError());
+    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the take's report never reached the host"));
+    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+    res->out_bytes = rep[et::PACKED_BYTES];
+    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
+    res->n_failed = rep[et::PACKED_N_FAILED];
+    if (res->n_failed) {
+        res->first_failed = rep[et::PACKED_FIRST] >> 8;
+        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
+    }
+    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the taken bodies need more than cap bytes");  // (k_take_copy saw the same two figures)
     return ET_OK;
 }
 

@@ -166,4 +166,29 @@ void launch_join(hipStream_t stream, const JoinSide &records, const JoinSide &ke
 // et_selftest_join_hash: d_hash[b] = the hash of record b as k_join_build and k_join_flag compute it (a failed record's entry is left).
 void launch_join_hash(hipStream_t stream, const JoinSide &records, uint64_t *d_hash);
 
+// The take call (et_take_packed_device): a selection of a packed store's records as a NEW packed store -- the bodies of rows[] copied
+// back to back as they are, both offset arrays made by a scan -- without a table: no bit is interpreted.
+//   k_take_plan   one row per lane (k_gather_plan's shape and rule, plus: a body above TAKE_BODY_MAX is unsupported): a TakeRow per
+//                 row into the workspace, its status byte
+//   k_take_scan   ONE workgroup, tiles of TAKE_SCAN_TILE rows: the rows' body sizes -> out_body_index, their lengths ->
+//                 out_text_index; the report ({body bytes, failed, first << 8 | status, text bytes}, then `epoch`) leaves with it
+//   k_take_copy   (unless d_out is null: sizes only) destination-driven: the dense output is cut into tiles of TAKE_TILE_BYTES at
+//                 multiples of that size of d_out's ADDRESS; a lane owns aligned 16-byte words of a tile, finds the rows that own the
+//                 word's bytes in out_body_index and assembles it from the aligned 8-byte source words that hold them
+struct TakeRow {  // what k_take_plan leaves per row: 16 bytes, one load of k_take_copy
+    uint32_t body_bytes;  // 0 for a failed row
+    uint32_t length;      // the record's text_index difference; 0 for a failed row
+    uint64_t src;         // body_index[rows[k]]: where in d_bodies the body begins (0 for a failed row)
+};
+constexpr uint64_t TAKE_BODY_MAX = 4 * BATCH_SMALL_MAX;  // no body of symbols with codes of at most 32 bits is longer
+constexpr uint32_t TAKE_SCAN_TILE = 4096;    // rows per trip of k_take_scan's one workgroup
+constexpr uint32_t TAKE_TILE_BYTES = 8192;   // k_take_copy: bytes of output per trip of a workgroup, two 16-byte words per lane
+constexpr uint32_t TAKE_STAGE_ROWS = 1024;   // ... entries of out_body_index a workgroup keeps in LDS for a tile (more: read in place)
+constexpr uint32_t TAKE_GRID = 2048;         // workgroups of k_take_copy at most: what is resident at once on 256 CUs
+enum TakeWord { TAKE_TEXT_BYTES = 3 };       // the report's word beside PACKED_BYTES, PACKED_N_FAILED and PACKED_FIRST
+// plan: n_rows TakeRow of workspace (16-byte aligned).  stats, host_result, host_done, epoch: launch_packed_encode's.
+void launch_take(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
+                 const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan,
+                 unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
+
 }  // namespace et

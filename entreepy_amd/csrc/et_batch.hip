@@ -27,6 +27,9 @@
 //            k_join_flag     one lane per record: judged, hashed, probed, every hit confirmed by bytes; ballot masks, tile counts, key numbers
 //            k_packed_scan   as in the match
 //            k_join_emit     k_match_emit, with the lowest equal key's number beside the record's
+//   take     k_take_plan     one lane per row of a selection: its record judged, {body bytes, length, where the body begins} into the workspace
+//            k_take_scan     ONE workgroup: the two sizes -> out_body_index and out_text_index, the report
+//            k_take_copy     the selected bodies back to back as they are: one lane per aligned 16-byte word of the OUTPUT
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -1255,7 +1258,263 @@ __global__ __launch_bounds__(BB) void k_join_hash(JoinSide recs, uint64_t *__res
 }
 
 // --------------------------------------------------------------------------------
+// The take call: rows[] of a packed store as a new packed store.  Under one table a body is a self-contained byte string, so row k of
+// the result is the bytes d_bodies[body_index[r], body_index[r + 1]) of its record r = rows[k] as they are, and its length is r's; no
+// bit is interpreted and no table comes to the device.  Three launches in stream order, the host waiting for the second alone:
+//   k_take_plan   per row: its record judged (k_gather_plan's rule; a body above TAKE_BODY_MAX is unsupported too), a TakeRow -- body
+//                 bytes, length, where the body begins -- into the workspace, its status byte
+//   k_take_scan   body bytes -> out_body_index, lengths -> out_text_index, both totals and the failure counters to the host
+//   k_take_copy   the ragged byte copy, driven by the DESTINATION: every aligned 16-byte word of the output is assembled and stored
+//                 by one lane, whatever the rows' sizes -- a 20-byte body does not scatter byte stores, a 40 KiB body is spread over
+//                 ten wavefronts
+// --------------------------------------------------------------------------------
+// k_take_plan: k_gather_plan with a record per row in place of a size word.  A failed row is an empty record: {0, 0, 0}.
+__global__ __launch_bounds__(BB) void k_take_plan(const uint32_t *__restrict__ rows, uint32_t n_rows, const uint64_t *__restrict__ body_index,
+                                                  const uint64_t *__restrict__ text_index, uint32_t n_records, uint64_t body_bytes, TakeRow *__restrict__ plan,
+                                                  uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    unsigned long long failed = 0, first = ~0ull;
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * BB + threadIdx.x; k < n_rows; k += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t r = rows[k];
+        uint32_t status = PACKED_ARG;
+        uint4 row = make_uint4(0u, 0u, 0u, 0u);
+        if (r < n_records) {
+            const uint64_t b0 = body_index[r], b1 = body_index[r + 1], t0 = text_index[r], t1 = text_index[r + 1];
+            if (b0 <= b1 && b1 <= body_bytes && t0 <= t1) {
+                if (t1 - t0 > BATCH_SMALL_MAX || b1 - b0 > TAKE_BODY_MAX) {
+                    status = PACKED_UNSUPPORTED;
+                } else {
+                    status = PACKED_OK;
+                    row = make_uint4(static_cast<uint32_t>(b1 - b0), static_cast<uint32_t>(t1 - t0), static_cast<uint32_t>(b0), static_cast<uint32_t>(b0 >> 32));
+                }
+            }
+        }
+        reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
+        if (d_status) d_status[k] = static_cast<uint8_t>(status);
+        if (status) {
+            ++failed;
+            const unsigned long long key = k << 8 | status;  // (k ascends in a lane: its first is its lowest)
+            if (key < first) first = key;
+        }
+    }
+    tally_lanes(failed, first, s_failed, s_first, stats);
+}
+
+// k_take_scan: k_packed_scan over pairs -- ONE workgroup; per trip a tile of TAKE_SCAN_TILE rows; two exclusive scans in u64, the tiles
+// before carried in two registers; both totals go to entry n.  The trip count is n / 4096, fixed by the host.  A lane scans 16
+// consecutive rows, but global memory is read and written with consecutive lanes at consecutive rows (a lane at its own 16 rows reads
+// 256 bytes and writes 2 x 128 bytes apart from its neighbour: one workgroup then spends its time on cache lines, 7 - 10 us per trip):
+// the sizes pass through LDS, where a lane's 16 words lie 17 apart from its neighbour's (take_pad: different banks), are replaced
+// there by their exclusive prefixes within the lane -- 16 bodies of at most TAKE_BODY_MAX fit 32 bits --, and a row's offset is its
+// lane's base plus that prefix.  Thread 0 then reports {body bytes, rows that failed, the first of them << 8 | its status, text bytes}
+// and the epoch; k_take_copy, enqueued behind, takes everything it needs from out_body_index and the plan: the host does not wait in
+// between.  LDS 38 KiB.
+__device__ __forceinline__ uint32_t take_pad(uint32_t k) { return k + (k >> 4); }
+
+__global__ __launch_bounds__(BB) void k_take_scan(const TakeRow *__restrict__ plan, uint32_t n, uint64_t *__restrict__ out_body_index, uint64_t *__restrict__ out_text_index,
+                                                  const unsigned long long *__restrict__ stats, unsigned long long *__restrict__ host_result,
+                                                  unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+    constexpr uint32_t PER = TAKE_SCAN_TILE / BB;
+    static_assert(PER == 16 && PER * TAKE_BODY_MAX <= 0xffffffffull, "take_pad; a lane's prefixes fit 32 bits");
+    __shared__ uint32_t s_b[TAKE_SCAN_TILE + BB], s_t[TAKE_SCAN_TILE + BB];  // sizes, then prefixes within a lane, at take_pad(row)
+    __shared__ uint64_t s_base_b[BB], s_base_t[BB];                          // where a lane's 16 rows begin
+    __shared__ uint64_t s_body[4], s_text[4];
+    const uint32_t tid = threadIdx.x;
+    uint64_t carry_body = 0, carry_text = 0;
+    for (uint32_t tile = 0; tile < n; tile += TAKE_SCAN_TILE) {
+#pragma unroll
+        for (uint32_t j = 0; j < PER; ++j) {
+            const uint32_t k = j * BB + tid;
+            uint2 x = make_uint2(0u, 0u);
+            if (tile + k < n) x = *reinterpret_cast<const uint2 *>(plan + tile + k);  // {body_bytes, length}
+            s_b[take_pad(k)] = x.x;
+            s_t[take_pad(k)] = x.y;
+        }
+        __syncthreads();
+        uint32_t my_body = 0, my_text = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < PER; ++i) {
+            const uint32_t p = take_pad(tid * PER + i);
+            const uint32_t vb = s_b[p], vt = s_t[p];
+            s_b[p] = my_body;
+            s_t[p] = my_text;
+            my_body += vb;
+            my_text += vt;
+        }
+        uint64_t total_body, total_text;
+        s_base_b[tid] = carry_body + block_exclusive_scan64(my_body, s_body, &total_body);
+        s_base_t[tid] = carry_text + block_exclusive_scan64(my_text, s_text, &total_text);
+        carry_body += total_body;
+        carry_text += total_text;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t j = 0; j < PER; ++j) {
+            const uint32_t k = j * BB + tid;
+            if (tile + k < n) {
+                out_body_index[tile + k] = s_base_b[k >> 4] + s_b[take_pad(k)];
+                out_text_index[tile + k] = s_base_t[k >> 4] + s_t[take_pad(k)];
+            }
+        }
+        __syncthreads();  // (every LDS array: between two trips)
+    }
+    if (tid == 0) {
+        out_body_index[n] = carry_body;
+        out_text_index[n] = carry_text;
+        host_result[PACKED_BYTES] = carry_body;
+        host_result[PACKED_N_FAILED] = stats[PACKED_N_FAILED];
+        host_result[PACKED_FIRST] = stats[PACKED_FIRST];
+        host_result[TAKE_TEXT_BYTES] = carry_text;
+        hand_over(host_done, epoch);
+    }
+}
+
+// How many threads of the workgroup hold `p`.  Two barriers: s_cnt (4 words) is free again on return.
+__device__ __forceinline__ uint32_t block_count(bool p, uint32_t *s_cnt) {
+    const unsigned long long m = __ballot(p);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(m));
+    __syncthreads();
+    const uint32_t c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    __syncthreads();
+    return c;
+}
+
+// The first i in [lo, hi] with i == hi or index[i] > target, by the whole workgroup; index ascends (not strictly) and every entry in
+// front of `lo` is at most `target`.  The first trip probes the 256 entries from lo on -- the answer of a tile that follows its
+// neighbour lies there unless a long run of empty rows does --, every later trip 256 evenly spaced ones, which leaves at most a 256th of
+// the range: 2^32 entries are done in six trips.  Every thread returns the same value.
+__device__ __forceinline__ uint32_t wg_upper_bound(const uint64_t *__restrict__ index, uint32_t lo, uint32_t hi, uint64_t target, uint32_t *s_cnt) {
+    uint64_t step = 1;
+    for (int trip = 0; trip < 8 && lo < hi; ++trip) {
+        const uint64_t p = lo + threadIdx.x * step;
+        const uint32_t c = block_count(p < hi && index[p] <= target, s_cnt);  // (the probes ascend: the first c of them)
+        if (c == 0) return lo;
+        const uint64_t above = lo + c * step;  // probe c, when there was one, lies above the target
+        lo = static_cast<uint32_t>(lo + (c - 1) * step + 1);
+        if (c < BB && above < hi) hi = static_cast<uint32_t>(above);
+        step = (static_cast<uint64_t>(hi - lo) + BB - 1) / BB;
+    }
+    return lo;
+}
+
+// `cnt` bytes (1 .. 8) at address a, all of them bytes of one body, zero-extended: from the aligned 8-byte words that hold them --
+// one, or two -- shifted into place (body_word's rule: a word that holds no byte of the body is never loaded).
+__device__ __forceinline__ uint64_t span_word(uintptr_t a, uint32_t cnt) {
+    const uint64_t *q = reinterpret_cast<const uint64_t *>(a & ~static_cast<uintptr_t>(7));
+    const uint32_t lead = static_cast<uint32_t>(a & 7);
+    uint64_t v = q[0] >> (8 * lead);
+    if (lead + cnt > 8) v |= q[1] << (64 - 8 * lead);  // (lead > 0 here; q[1] holds the last of the cnt bytes)
+    if (cnt < 8) v &= (1ull << (8 * cnt)) - 1ull;
+    return v;
+}
+
+// x's bytes to bytes d, d + 1, ... (d < 16) of the 16-byte word {v0, v1}.
+__device__ __forceinline__ void put_bytes(uint64_t &v0, uint64_t &v1, uint64_t x, uint32_t d) {
+    if (d < 8) {
+        v0 |= x << (8 * d);
+        if (d) v1 |= x >> (64 - 8 * d);
+    } else {
+        v1 |= x << (8 * (d - 8));
+    }
+}
+
+// k_take_copy: the output's bytes [0, total) lie at d_out, any alignment; tile t is what of them lies in the t-th TAKE_TILE_BYTES
+// block counted from d_out's address rounded down, so every word below is an aligned 16 bytes of MEMORY.  A workgroup takes a run of
+// consecutive tiles.  Per tile it finds, together, the rows that own the tile's first and last byte (wg_upper_bound: a run of empty rows
+// shares its offset with the row behind it, and the LAST row at an offset is the one that owns the byte) and keeps that stretch of
+// out_body_index in LDS when it fits (TAKE_STAGE_ROWS entries: 8 KiB), else reads it in place.  A lane then owns words tid and
+// tid + 256 of the tile.  For a word it finds the row that owns its first byte (binary search over the tile's stretch: at most 31
+// steps), and walks the rows that own the rest -- a step to the next row, or where empty rows follow a search again --, at most 16
+// trips: each takes a byte of the word at least.  A row's piece comes from its TakeRow (one 16-byte load) and one to three aligned
+// 8-byte source words.  A full word leaves as ONE 16-byte store; the first and the last word of the whole output, where d_out or its
+// end is not aligned, leave as byte stores of their own bytes.  Nothing is written when total > cap, no workgroup waits for another,
+// and a row that owns a byte was judged by k_take_plan, so its TakeRow is believed.  LDS 8 KiB + 16 bytes.
+__global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_bodies, const TakeRow *__restrict__ plan, const uint64_t *__restrict__ out_index,
+                                                  uint32_t n_rows, uint8_t *__restrict__ d_out, uint64_t cap) {
+    __shared__ uint64_t s_idx[TAKE_STAGE_ROWS];
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t total = out_index[n_rows];
+    if (total > cap || total == 0) return;
+    const uintptr_t out = reinterpret_cast<uintptr_t>(d_out), bodies = reinterpret_cast<uintptr_t>(d_bodies);
+    const uint64_t skew = out & (TAKE_TILE_BYTES - 1);  // bytes of tile 0 in front of d_out
+    const uint64_t n_tiles = (skew + total + TAKE_TILE_BYTES - 1) / TAKE_TILE_BYTES;
+    const uint64_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
+    const uint64_t t_begin = blockIdx.x * per, t_end = t_begin + per < n_tiles ? t_begin + per : n_tiles;
+    uint32_t hint = 0;  // every entry of out_index in front of it is at most the tile's first offset
+    for (uint64_t t = t_begin; t < t_end; ++t) {
+        // the tile's bytes as offsets into the output: [o0, o1), o0 < o1 <= total
+        const uint64_t o0 = t ? t * TAKE_TILE_BYTES - skew : 0, o1_full = (t + 1) * TAKE_TILE_BYTES - skew, o1 = o1_full < total ? o1_full : total;
+        // out_index[row_lo] <= o0 < out_index[row_lo + 1], out_index[row_end - 1] < o1 <= out_index[row_end]: rows [row_lo, row_end) own the tile
+        const uint32_t row_lo = wg_upper_bound(out_index, hint, n_rows + 1, o0, s_cnt) - 1;  // (out_index[0] = 0 <= o0: at least 1)
+        const uint32_t row_end = wg_upper_bound(out_index, row_lo + 1, n_rows + 1, o1 - 1, s_cnt);  // (out_index[n_rows] = total > o1 - 1: at most n_rows)
+        hint = row_end;
+        const uint32_t entries = row_end - row_lo + 1;
+        const bool staged = entries <= TAKE_STAGE_ROWS;  // (the same for every thread)
+        if (staged)
+            for (uint32_t i = tid; i < entries; i += BB) s_idx[i] = out_index[row_lo + i];
+        __syncthreads();
+        auto idx = [&](uint32_t r) -> uint64_t { return staged ? s_idx[r - row_lo] : out_index[r]; };  // r in [row_lo, row_end]
+        const uintptr_t tile_addr = (out - skew) + t * TAKE_TILE_BYTES;
+#pragma unroll
+        for (uint32_t j = 0; j < TAKE_TILE_BYTES / (16 * BB); ++j) {
+            const uintptr_t aw = tile_addr + (j * BB + tid) * 16;
+            const int64_t rel = static_cast<int64_t>(aw) - static_cast<int64_t>(out);  // the word's first byte as an offset: negative in front of d_out
+            if (rel + 16 <= 0 || rel >= static_cast<int64_t>(total)) continue;
+            const uint64_t w0 = rel < 0 ? 0 : static_cast<uint64_t>(rel), w1 = static_cast<uint64_t>(rel + 16) < total ? static_cast<uint64_t>(rel + 16) : total;
+            // the row that owns byte w0: the last r in [row_lo, row_end) with out_index[r] <= w0
+            uint32_t k = row_lo, hi = row_end;
+            while (hi - k > 1) {
+                const uint32_t mid = k + (hi - k) / 2;
+                if (idx(mid) <= w0) k = mid;
+                else hi = mid;
+            }
+            uint64_t v0 = 0, v1 = 0, pos = w0;
+            for (int trip = 0; trip < 16; ++trip) {  // row k owns byte pos: out_index[k] <= pos < out_index[k + 1]
+                const uint64_t s = idx(k), e = idx(k + 1), piece_end = e < w1 ? e : w1;
+                const uint32_t c = static_cast<uint32_t>(piece_end - pos);  // 1 .. 16
+                const uintptr_t a = bodies + plan[k].src + (pos - s);
+                const uint32_t d = static_cast<uint32_t>(static_cast<int64_t>(pos) - rel);
+                put_bytes(v0, v1, span_word(a, c < 8 ? c : 8u), d);
+                if (c > 8) put_bytes(v0, v1, span_word(a + 8, c - 8), d + 8);
+                pos = piece_end;
+                if (pos >= w1) break;
+                ++k;  // (a row behind owns byte pos < o1: k < row_end)
+                if (idx(k + 1) <= pos) {  // empty rows follow: the last r in [k, row_end) with out_index[r] <= pos
+                    hi = row_end;
+                    while (hi - k > 1) {
+                        const uint32_t mid = k + (hi - k) / 2;
+                        if (idx(mid) <= pos) k = mid;
+                        else hi = mid;
+                    }
+                }
+            }
+            if (w1 - w0 == 16) {
+                *reinterpret_cast<uint4 *>(aw) = make_uint4(static_cast<uint32_t>(v0), static_cast<uint32_t>(v0 >> 32), static_cast<uint32_t>(v1), static_cast<uint32_t>(v1 >> 32));
+            } else {  // the output's first or last word: its own bytes alone
+                for (uint32_t i = static_cast<uint32_t>(static_cast<int64_t>(w0) - rel); i < static_cast<uint32_t>(static_cast<int64_t>(w1) - rel); ++i)
+                    reinterpret_cast<uint8_t *>(aw)[i] = static_cast<uint8_t>((i < 8 ? v0 >> (8 * i) : v1 >> (8 * (i - 8))) & 0xffu);
+            }
+        }
+        __syncthreads();  // (s_idx: between two tiles)
+    }
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
+
+void launch_take(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
+                 const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan,
+                 unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
+    const uint32_t plan_grid = (n_rows + BB - 1) / BB;
+    hipLaunchKernelGGL(k_take_plan, dim3(plan_grid < GATHER_PLAN_GRID ? plan_grid : GATHER_PLAN_GRID), dim3(BB), 0, stream, rows, n_rows, body_index, text_index, n_records, body_bytes,
+                       plan, d_status, stats);
+    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
+                       static_cast<const unsigned long long *>(stats), host_result, host_done, epoch);
+    if (!d_out) return;
+    const uint64_t tiles = cap / TAKE_TILE_BYTES + 2;  // (what fits into cap spans no more tiles, at any alignment)
+    hipLaunchKernelGGL(k_take_copy, dim3(static_cast<uint32_t>(tiles < TAKE_GRID ? tiles : TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies),
+                       static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+}
 
 void launch_join(hipStream_t stream, const JoinSide &records, const JoinSide &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,
                  uint64_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status, uint8_t *d_key_status, unsigned long long *masks, uint32_t *counts, uint64_t *base,

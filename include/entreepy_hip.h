@@ -482,6 +482,55 @@ int et_join_packed_device(et_ctx *ctx, const et_codebook *cb,
 int et_selftest_join_hash(et_ctx *ctx, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
                           const uint64_t *d_text_index, size_t n, uint64_t *d_hash);
 
+/* TAKE: a SELECTION of a packed store's records as a NEW packed store, on the device, nothing decoded and nothing encoded again: what
+ * keeps the result of a match or a join compressed -- as the key set of the next join, as the store that is left when rows are
+ * deleted or reordered, or as the bytes that go to another rank or a file.  Under one table a record's body is a self-contained byte
+ * string, so row k of the result is the body of record r = d_rows[k] as it is, and its length is r's.  There is NO et_codebook
+ * argument: the call never interprets a bit, so it works under any table, complete or not, and the new store is read under the table
+ * the old one was written with.
+ *   The store and d_rows are the gather call's: d_bodies, and d_body_index and d_text_index of n_records + 1 entries each, 8-byte
+ *     aligned, the text offsets serving as record lengths only; d_rows[k] (n_rows of them, 32 bits, 4-byte aligned, on the device) in
+ *     any order, repeats allowed.
+ *   A row whose status is ET_OK: d_out[out_body_index[k], out_body_index[k+1]) holds exactly the bytes
+ *     d_bodies[body_index[r], body_index[r+1]), and out_text_index[k+1] - out_text_index[k] == text_index[r+1] - text_index[r].  Both
+ *     output arrays have n_rows + 1 entries (8-byte aligned, on the device) and begin with 0; the bodies lie back to back.  A body of
+ *     no bytes under a length above zero (a record kept raw elsewhere) is valid and is taken as such -- no bytes, the length kept --
+ *     so the new store behaves under decode, match and join as the old record did.
+ *   d_status[k] (one et_status byte per ROW; may be NULL): the gather call's rule -- ET_ERR_ARG when d_rows[k] >= n_records, and unless
+ *     body_index[r] <= body_index[r+1] <= body_bytes and text_index[r] <= text_index[r+1]; ET_ERR_UNSUPPORTED for a length above the
+ *     small-stream limit -- and one more: ET_ERR_UNSUPPORTED for a body of more than 4 * et_batch_small_max() bytes, which no record
+ *     of codes up to 32 bits has.  A failed row becomes an EMPTY record of the new store: no bytes, length 0.  A row fails alone, no
+ *     kernel reads where a bad pair points, and a bad record that no row selects does not matter.  In *res, n_failed, first_failed and
+ *     first_status are about ROWS (positions k).
+ *   Nothing outside [d_out, d_out + out_body_index[n_rows]) is written, at any alignment of d_out and of d_bodies.
+ *   d_out == NULL: sizes only -- both output arrays, d_status and *res are the writing call's; cap is ignored.
+ *   out_body_index[n_rows] > cap: the call returns ET_ERR_CAP, not a byte of d_out is written; both output arrays and d_status are
+ *     complete and res->out_bytes is the room needed.
+ * Out of scope: compaction in place -- [d_out, d_out + cap) may not overlap [d_bodies, d_bodies + body_bytes) --, taking from several
+ * stores in one call, and records above the limits named above.
+ * The call's own status: ET_ERR_ARG (a null ctx, res, d_bodies, d_body_index, d_text_index, d_rows, d_out_body_index or
+ * d_out_text_index; an offset array that is not 8-byte aligned, d_rows not 4-byte aligned; n_records or n_rows above 0x7fffffff; d_out
+ * overlapping d_bodies -- all checked before anything touches a device, *res untouched), ET_ERR_CAP, ET_ERR_HIP, ET_ERR_NOMEM.
+ * n_rows == 0: ET_OK, nothing enqueued, *res zeroed.  One upload (64 bytes of counters), three launches and one hand-over per call;
+ * stream-ordered like the other packed calls -- *res is final on return, the device arrays once the ctx's stream has drained -- and it
+ * may follow or precede packed, gather, match, join, shared-table and single-stream calls on one ctx with nothing in between: d_rows
+ * may come straight from et_match_packed_device or et_join_packed_device, and the outputs may go straight into et_join_packed_device
+ * (as the key set), et_decode_packed_device or et_decode_packed_gather_device. */
+typedef struct et_take_result {
+    uint64_t out_bytes;      /* out_body_index[n_rows]: bytes the taken bodies need -- also when the call returns ET_ERR_CAP or d_out is NULL */
+    uint64_t text_bytes;     /* out_text_index[n_rows]: the sum of the taken records' lengths */
+    uint64_t n_failed, first_failed;   /* rows whose status is not ET_OK, the lowest of them (valid when n_failed > 0) */
+    int32_t first_status;    /* et_status of row first_failed */
+    uint32_t pad;
+} et_take_result;
+size_t et_take_result_size(void);
+int et_take_packed_device(et_ctx *ctx,
+                          const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                          const uint64_t *d_text_index, size_t n_records,
+                          const uint32_t *d_rows, size_t n_rows,
+                          void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
+                          uint8_t *d_status, et_take_result *res);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

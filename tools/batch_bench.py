@@ -35,6 +35,13 @@ process of its own so that every leg loads exactly one build of the library:
                   the call replaces -- one et_match_packed_device(ET_MATCH_EQUAL) per key, the keys' texts on the host, then the union of
                   their rows sorted in torch -- on this tree's library or on the one named by --batch-lib (a build of the commit before
                   the call).  Both check their rows against set membership over the plain texts first.
+  take            et_take_packed_device, one call per shape and selection, on this tree's library: a selection of a packed store's
+                  records as a new packed store -- the two shapes with every row in order, a random 10 % and a random permutation, and the
+                  262 144 key-like records with a random 0.1 % and 10 %.  Beside the writing call it times the sizes-only call and, as
+                  the floor, a plain device-to-device copy (torch.Tensor.copy_) of as many bytes in the same process; vs_copy_floor is
+                  the call's time over that copy's.  With it runs take_baseline, what the call replaces -- et_decode_packed_gather_device
+                  of the rows, then et_encode_packed_device of that text -- on this tree's library or on the one named by --batch-lib (a
+                  build of the commit before the call).  Both check their bodies against slices of the store's first.
 --legs picks the legs (default: all).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
@@ -46,6 +53,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs gather --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/gather_bench.json
     python tools/batch_bench.py --legs match --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/match_bench.json
     python tools/batch_bench.py --legs join --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/join_bench.json
+    python tools/batch_bench.py --legs take --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/take_bench.json
 """
 import argparse
 import ctypes
@@ -547,11 +555,116 @@ def _join_leg(leg, lib_path):
     print(json.dumps({f"{count}x{size[0]}-{size[1]}": shape}))
 
 
+def _take_leg(leg, lib_path):
+    """take / take_baseline: per shape a packed store (et_encode_packed_device, untimed), then per selection the timed call: the take
+    with d_out -- beside it the sizes-only call and a plain device-to-device copy of as many bytes (torch.Tensor.copy_, the floor) -- or
+    what it replaces: et_decode_packed_gather_device of the rows, then et_encode_packed_device of that text."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+    from tests import corpus
+
+    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
+             "et_decode_packed_gather_device"] + (["et_take_packed_device"] if leg == "take" else [])
+    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
+    dev = torch.device("cuda", 0)
+    h = ctypes.c_void_p()
+    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
+    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+
+    def timed(fn):
+        ms = []
+        for rep in range(WARMUP + REPS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep >= WARMUP:
+                ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+    rng = np.random.default_rng(0x7A4E5)
+    count, size = KEY_SHAPE
+    key_lengths = rng.integers(size[0], size[1] + 1, size=count)
+    stores = [(f"{c}x{s}", c, np.arange(c + 1, dtype=np.uint64) * np.uint64(s), SELECTIONS) for c, s in SHAPES]
+    stores.append((f"{count}x{size[0]}-{size[1]}", count, np.concatenate(([0], np.cumsum(key_lengths))).astype(np.uint64), ("random_0.1%", "random_tenth")))
+    results = {}
+    for shape_name, count, index, selections in stores:
+        total = int(index[-1])
+        text = corpus.text_like_torch(total, 0xB47C4 + count, dev)
+        hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
+        cb = N.Codebook()
+        assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+        cap = L.et_body_bound(ctypes.byref(cb), total) + count
+        bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+        text_index = torch.from_numpy(index.view(np.int64)).to(dev)
+        body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        res = N.PackedResult()
+        assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
+                                         ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+        body_bytes = int(res.out_bytes)
+        torch.cuda.synchronize()
+        host_bodies, bi = bodies[:body_bytes].cpu().numpy(), body_index.cpu().numpy().view(np.uint64)
+        shape = {"body_bytes": body_bytes}
+        for name in selections:
+            rows = np.sort(rng.choice(count, size=max(count // 1000, 1), replace=False)).astype(np.uint32) if name == "random_0.1%" else _selection(name, count)
+            d_rows = torch.from_numpy(rows.view(np.int32)).to(dev)
+            at = rows.astype(np.int64)
+            need, text_need = int((bi[at + 1] - bi[at]).sum()), int((index[at + 1] - index[at]).sum())
+            want = np.concatenate([host_bodies[int(bi[r]) : int(bi[r + 1])] for r in at])
+            out = torch.zeros(need + 64, dtype=torch.uint8, device=dev)
+            out_body_index = torch.zeros(rows.size + 1, dtype=torch.int64, device=dev)
+            out_text_index = torch.zeros(rows.size + 1, dtype=torch.int64, device=dev)
+            entry = {"rows": int(rows.size), "bytes": need}
+            if leg == "take":
+                tres = N.TakeResult()
+
+                def take(d_out=out):
+                    assert L.et_take_packed_device(h, bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, d_rows.data_ptr(), rows.size,
+                                                   None if d_out is None else d_out.data_ptr(), need, out_body_index.data_ptr(), out_text_index.data_ptr(), None,
+                                                   ctypes.byref(tres)) == 0, L.et_last_error(h)
+                    assert tres.out_bytes == need and tres.text_bytes == text_need and tres.n_failed == 0
+
+                take()
+                torch.cuda.synchronize()
+                assert np.array_equal(out[:need].cpu().numpy(), want), "the taken bodies differ from the store's"
+                assert np.array_equal(np.diff(out_body_index.cpu().numpy()), (bi[at + 1] - bi[at]).astype(np.int64)) and int(out_text_index[-1]) == text_need
+                entry.update(timed(take))
+                entry["sizes_only"] = timed(lambda: take(None))
+                src = bodies[:need] if need <= body_bytes else torch.zeros(need, dtype=torch.uint8, device=dev)
+                entry["copy_floor"] = timed(lambda: out[:need].copy_(src))
+                entry["vs_copy_floor"] = round(entry["ms"] / entry["copy_floor"]["ms"], 2)
+            else:
+                dec = torch.zeros(text_need + 64, dtype=torch.uint8, device=dev)
+
+                def baseline():
+                    assert L.et_decode_packed_gather_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, d_rows.data_ptr(),
+                                                            rows.size, dec.data_ptr(), text_need, out_text_index.data_ptr(), None, None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.out_bytes == text_need and res.n_failed == 0 and res.n_short == 0
+                    assert L.et_encode_packed_device(h, ctypes.byref(cb), dec.data_ptr(), text_need, out_text_index.data_ptr(), rows.size, out.data_ptr(), need,
+                                                     out_body_index.data_ptr(), None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.out_bytes == need and res.n_failed == 0
+
+                baseline()
+                torch.cuda.synchronize()
+                assert np.array_equal(out[:need].cpu().numpy(), want), "the re-encoded bodies differ from the store's"
+                entry.update(timed(baseline))
+                del dec
+            shape[name] = entry
+            del out, want
+        results[shape_name] = shape
+        del text, bodies
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take")
     ap.add_argument("--shapes", default="")  # (the match legs: a comma list of shape names, e.g. 262144x16-48; default: all)
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
@@ -561,6 +674,8 @@ def main():
         return _match_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg and a.leg.startswith("join"):
         return _join_leg(a.leg, a.lib)
+    if a.leg and a.leg.startswith("take"):
+        return _take_leg(a.leg, a.lib)
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -574,6 +689,8 @@ def main():
         legs += [("match_baseline", "match_baseline", a.batch_lib or here), ("match", "match", here)]
     if "join" in a.legs.split(","):
         legs += [("join_baseline", "join_baseline", a.batch_lib or here), ("join", "join", here)]
+    if "take" in a.legs.split(","):
+        legs += [("take_baseline", "take_baseline", a.batch_lib or here), ("take", "take", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
     for name, leg, lib in legs:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib, "--shapes", a.shapes], capture_output=True, text=True, timeout=600)
@@ -596,6 +713,8 @@ def main():
     if "join" in out:  # > 1: the join call is the faster one
         out["join_vs_baseline"] = {k: {keys: {sel: round(out["join_baseline"][k][keys][sel]["ms"] / e["ms"], 2) for sel, e in v.items()} for keys, v in shape.items()}
                                    for k, shape in out["join"].items()}
+    if "take" in out:  # > 1: the take call is the faster one; vs_copy_floor (in the take leg): its time over a plain copy of as many bytes
+        out["take_vs_baseline"] = {k: {n: round(out["take_baseline"][k][n]["ms"] / e["ms"], 2) for n, e in v.items() if isinstance(e, dict)} for k, v in out["take"].items()}
     line = json.dumps(out)
     print(line)
     if a.out:
