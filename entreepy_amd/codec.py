@@ -425,8 +425,7 @@ class Context:
         items = np.zeros(len(in_offsets), dtype=self._ITEM)
         items["in_off"], items["in_len"], items["out_off"], items["out_cap"] = in_offsets, in_lens, out_offsets, out_caps
         self._bind()
-        _check(fn(self._h, ctypes.byref(codebook.raw), in_tensor.data_ptr(), None if out_tensor is None else out_tensor.data_ptr(),
-                  items.ctypes.data if items.size else None, items.size), self._h)
+        _check(fn(self._h, ctypes.byref(codebook.raw), in_tensor.data_ptr(), self._opt_ptr(out_tensor), items.ctypes.data if items.size else None, items.size), self._h)
         return items["out_len"].copy(), items["status"].copy(), items["path"].copy()
 
     def encode_shared_device(self, codebook, in_tensor, in_offsets, in_lens, out_tensor, out_offsets, out_caps):
@@ -489,10 +488,23 @@ class Context:
         assert t.numel() >= 1 and (n is None or t.numel() == n + 1), "an offsets array holds one entry more than there are records"
         return t.data_ptr()
 
+    @staticmethod
+    def _rows_ptr(t, what="rows is a 1-D CUDA tensor of 32-bit integers"):
+        """Record or key numbers on the device: a 1-D CUDA tensor of 4-byte integers."""
+        assert t.is_cuda and t.dim() == 1 and t.element_size() == 4 and t.is_contiguous() and not t.is_floating_point(), what
+        return t.data_ptr()
+
+    @staticmethod
+    def _opt_ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def _cap_or_raise(self, rc):
+        if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
+            _check(rc, self._h)
+        return rc
+
     def _packed_result(self, status, res):
-        if status != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
-            _check(status, self._h)
-        return PackedResult(status, res.out_bytes, res.n_failed, res.first_failed, res.n_short, res.first_status)
+        return PackedResult(self._cap_or_raise(status), res.out_bytes, res.n_failed, res.first_failed, res.n_short, res.first_status)
 
     def encode_packed_device(self, codebook, text, text_index, out, out_index, status=None):
         """Record b: text[text_index[b] : text_index[b + 1]] -> its body under `codebook` at out[out_index[b] : out_index[b + 1]],
@@ -505,8 +517,7 @@ class Context:
         res = N.PackedResult()
         self._bind()
         rc = N.lib().et_encode_packed_device(self._h, ctypes.byref(codebook.raw), text.data_ptr(), text.numel(), self._index_ptr(text_index), n,
-                                             None if out is None else out.data_ptr(), 0 if out is None else out.numel(), self._index_ptr(out_index, n),
-                                             None if status is None else status.data_ptr(), ctypes.byref(res))
+                                             self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_index, n), self._opt_ptr(status), ctypes.byref(res))
         return self._packed_result(rc, res)
 
     def decode_packed_device(self, codebook, bodies, body_index, text_index, out, written=None, status=None):
@@ -518,8 +529,7 @@ class Context:
         res = N.PackedResult()
         self._bind()
         rc = N.lib().et_decode_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
-                                             out.data_ptr(), out.numel(), None if written is None else written.data_ptr(), None if status is None else status.data_ptr(),
-                                             ctypes.byref(res))
+                                             out.data_ptr(), out.numel(), self._opt_ptr(written), self._opt_ptr(status), ctypes.byref(res))
         return self._packed_result(rc, res)
 
     def decode_packed_gather_device(self, codebook, bodies, body_index, text_index, rows, out, out_index, written=None, status=None):
@@ -531,13 +541,12 @@ class Context:
         first_failed is a row.  out=None: sizes only.  -> PackedResult; .status is ET_OK or ET_ERR_CAP (nothing written, .out_bytes =
         the room needed); any other failure of the call raises.  Stream-ordered like decode_packed_device."""
         n = text_index.numel() - 1
-        assert rows.is_cuda and rows.dim() == 1 and rows.element_size() == 4 and rows.is_contiguous() and not rows.is_floating_point(), "rows is a 1-D CUDA tensor of 32-bit integers"
+        rows_p = self._rows_ptr(rows)
         res = N.PackedResult()
         self._bind()
         rc = N.lib().et_decode_packed_gather_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
-                                                    rows.data_ptr(), rows.numel(), None if out is None else out.data_ptr(), 0 if out is None else out.numel(),
-                                                    self._index_ptr(out_index, rows.numel()), None if written is None else written.data_ptr(),
-                                                    None if status is None else status.data_ptr(), ctypes.byref(res))
+                                                    rows_p, rows.numel(), self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_index, rows.numel()),
+                                                    self._opt_ptr(written), self._opt_ptr(status), ctypes.byref(res))
         return self._packed_result(rc, res)
 
     def match_packed_device(self, codebook, bodies, body_index, text_index, needle, mode, rows=None, status=None):
@@ -549,16 +558,12 @@ class Context:
         the room needed); any other failure of the call raises.  Stream-ordered like decode_packed_device."""
         n = text_index.numel() - 1
         a, p = _host_u8(bytes(needle))
-        if rows is not None:
-            assert rows.is_cuda and rows.dim() == 1 and rows.element_size() == 4 and rows.is_contiguous() and not rows.is_floating_point(), "rows is a 1-D CUDA tensor of 32-bit integers"
+        rows_p = None if rows is None else self._rows_ptr(rows)
         res = N.MatchResult()
         self._bind()
         rc = N.lib().et_match_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
-                                            p, a.size, int(mode), None if rows is None else rows.data_ptr(), 0 if rows is None else rows.numel(),
-                                            None if status is None else status.data_ptr(), ctypes.byref(res))
-        if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
-            _check(rc, self._h)
-        return MatchResult(rc, res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
+                                            p, a.size, int(mode), rows_p, 0 if rows is None else rows.numel(), self._opt_ptr(status), ctypes.byref(res))
+        return MatchResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
 
     def join_packed_device(self, codebook, bodies, body_index, text_index, key_bodies, key_body_index, key_text_index, mode=0, rows=None, key_of_row=None, status=None,
                            key_status=None):
@@ -572,19 +577,14 @@ class Context:
         ET_ERR_CAP (no row written, .n_match = the room needed); any other failure of the call raises.  Stream-ordered like
         decode_packed_device."""
         n, n_keys = text_index.numel() - 1, key_text_index.numel() - 1
-        for t in (rows, key_of_row):
-            if t is not None:
-                assert t.is_cuda and t.dim() == 1 and t.element_size() == 4 and t.is_contiguous() and not t.is_floating_point(), "rows and key_of_row are 1-D CUDA tensors of 32-bit integers"
+        rows_p, key_of_p = (None if t is None else self._rows_ptr(t, "rows and key_of_row are 1-D CUDA tensors of 32-bit integers") for t in (rows, key_of_row))
         assert key_of_row is None or (rows is not None and key_of_row.numel() >= rows.numel()), "key_of_row is as large as rows"
         res = N.JoinResult()
         self._bind()
         rc = N.lib().et_join_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
                                            key_bodies.data_ptr(), key_bodies.numel(), self._index_ptr(key_body_index, n_keys), self._index_ptr(key_text_index), n_keys, int(mode),
-                                           None if rows is None else rows.data_ptr(), 0 if rows is None else rows.numel(), None if key_of_row is None else key_of_row.data_ptr(),
-                                           None if status is None else status.data_ptr(), None if key_status is None else key_status.data_ptr(), ctypes.byref(res))
-        if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
-            _check(rc, self._h)
-        return JoinResult(rc, res.n_match, res.n_failed, res.first_failed, res.n_keys_failed, res.first_key_failed, res.first_status, res.first_key_status)
+                                           rows_p, 0 if rows is None else rows.numel(), key_of_p, self._opt_ptr(status), self._opt_ptr(key_status), ctypes.byref(res))
+        return JoinResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.n_keys_failed, res.first_key_failed, res.first_status, res.first_key_status)
 
     def take_packed_device(self, bodies, body_index, text_index, rows, out, out_body_index, out_text_index, status=None):
         """Row k of the NEW store is record rows[k] of the store (bodies, body_index, text_index: decode_packed_gather_device's), in any
@@ -597,15 +597,13 @@ class Context:
         other failure of the call raises.  Stream-ordered like decode_packed_device: the three outputs may go straight into
         join_packed_device (as the key set), decode_packed_device or decode_packed_gather_device."""
         n = text_index.numel() - 1
-        assert rows.is_cuda and rows.dim() == 1 and rows.element_size() == 4 and rows.is_contiguous() and not rows.is_floating_point(), "rows is a 1-D CUDA tensor of 32-bit integers"
+        rows_p = self._rows_ptr(rows)
         res = N.TakeResult()
         self._bind()
-        rc = N.lib().et_take_packed_device(self._h, bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n, rows.data_ptr(), rows.numel(),
-                                           None if out is None else out.data_ptr(), 0 if out is None else out.numel(), self._index_ptr(out_body_index, rows.numel()),
-                                           self._index_ptr(out_text_index, rows.numel()), None if status is None else status.data_ptr(), ctypes.byref(res))
-        if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
-            _check(rc, self._h)
-        return TakeResult(rc, res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+        rc = N.lib().et_take_packed_device(self._h, bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n, rows_p, rows.numel(),
+                                           self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, rows.numel()),
+                                           self._index_ptr(out_text_index, rows.numel()), self._opt_ptr(status), ctypes.byref(res))
+        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
 
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""

@@ -1,60 +1,30 @@
-// et_batch.cpp -- host side of et_encode_batch_device / et_decode_batch_device (include/entreepy_hip.h): B independent
-// streams in one call.  The fixed price of a call -- its launches and its hand-over to the host -- is paid once per chunk
-// of BATCH_CHUNK streams instead of once per stream:
-//   encode   k_batch_hist -> (poll) code table + header of every stream -> one upload -> k_batch_encode
-//   decode   k_batch_heads -> (poll) et_parse_header of every stream -> one upload -> k_batch_decode -> (poll) symbol totals
-// What the batch kernels are not made for -- texts above et_batch_small_max(), codes beyond 32 bits on encode,
-// dictionaries that are not a full tree on decode -- runs through et_encode_device / et_decode_device for that stream
-// alone, behind the batch launches on the same stream (path = 1): the quirks stay where they are implemented.
+// et_batch.cpp -- host side of the calls of include/entreepy_hip.h that take many small streams or records at once.  A call's
+// fixed price -- its launches and its hand-over to the host -- is paid once per chunk or per call, not once per stream.
 //
-// ONE pinned block serves every chunk and every call.  It may be refilled without asking because each chunk begins
-// with a kernel whose report the host polls for, and that kernel runs behind everything the ctx enqueued before it
-// (stream order; a switch of streams keeps it, et_ctx_set_stream): when its epoch word arrives, the uploads and
-// kernels of the chunk before are over.  The records that first kernel reads are written before it is enqueued, into a
-// region no later upload of a chunk reads.
-//
-// The shared-table calls (et_encode_shared_device / et_decode_shared_device) need no hand-over in front of their kernel:
-//   per chunk of SHARED_CHUNK streams   job records -> one upload -> k_shared_encode / k_shared_decode -> (poll) lengths and statuses
-// and the table goes up once per call, in front of the first chunk.  They keep a region of their own at the pinned block's
-// end (table, job records, results).  It may be refilled without asking, by the next chunk and by the next call -- with
-// another table, and with no synchronisation in between -- because EVERY chunk ends with a poll for its kernel's report:
-// when that epoch word has arrived, the kernel is over, and so are the uploads in front of it on the stream, the table's
-// among them; a call returns only behind its last chunk's poll.  (That region is kept apart from the batch calls' because
-// et_encode_batch_device ends with uploads and a kernel nobody polls for.)  On the device, table and records are rewritten
-// in stream order behind the kernel that read them.
-//
-// The packed calls (et_encode_packed_device / et_decode_packed_device) take their records from u64 offset arrays ON THE DEVICE,
-// so there are no job records, no chunks and no host loop over the records:
-//   encode   table + zeroed counters -> one upload -> k_packed_count -> k_packed_scan -> (unless sizes only) k_packed_pack; (poll) the report
-//   decode   table + zeroed counters -> one upload -> k_packed_decode -> (poll) the report
-//   gather   table + zeroed counters -> one upload -> k_gather_plan -> k_packed_scan -> (unless sizes only) k_packed_gather; (poll) the report
-// (et_decode_packed_gather_device: a selection of records, rows[] on the device, into a dense output the scan lays out.  Its report
-// leaves with the decode kernel, which alone knows the rows whose bodies ended early -- with the scan when the call is sizes only.)
-// The encode's report leaves with the scan: the pack kernel behind it decides from the offsets the scan stored whether the
-// bodies fit, so the host returns ET_ERR_CAP (or ET_OK) from the same figures without waiting for it.  The calls keep a third
-// region of the pinned block (table, counters' first values, report) and a device workspace of their own (ctx->packed_ws: table,
-// counters, one size word per record of an encode or row of a gather).  Both may be refilled without asking for the shared-table
-// calls' reason: every call ends with a poll for a kernel that runs behind its upload, and on the device everything is rewritten
-// in stream order.
-//
-// The match call (et_match_packed_device) is a packed call without a table: the host encodes the needle (et_encode_pattern) and
-//   match    zeroed counters + the needle's bits -> one upload -> k_match_flag -> k_packed_scan; (poll) the report -> (unless count only) k_match_emit
-// It has a pinned region for that upload, shares the report slot and the epoch word, and lays ctx->packed_ws out its own way (the
-// counters where the other calls keep them; the pattern, the tile counts, the tiles' first places and the ballot masks behind).
-// Its report leaves with the scan: k_match_emit decides from the total the scan stored whether the rows fit, as k_packed_pack does.
-//
-// The join call (et_join_packed_device) takes its keys from device memory too -- a second packed store -- so nothing but counters goes up:
-//   join     zeroed counters -> one upload -> clear -> k_join_build -> k_join_flag -> k_packed_scan; (poll) the report -> (unless count only) the emit
-// It has a pinned region for the 64 bytes of first counter values, shares the report slot and the epoch word, and lays ctx->packed_ws
-// out its own way (the counters where the other calls keep them; the tile counts, the tiles' first places, the ballot masks, a key
-// number per record and the hash table behind).  The report's words come from two kernels: the keys' counters from k_join_flag's first
-// workgroup (they are final when it starts), the rest from the scan behind it, which hands over.
-//
-// The take call (et_take_packed_device) has no table at all -- it copies bodies as they are -- so it too sends up nothing but counters:
-//   take     zeroed counters -> one upload -> k_take_plan -> k_take_scan; (poll) the report -> (unless sizes only) k_take_copy
-// It has a pinned region for the 64 bytes of first counter values, shares the report slot and the epoch word, and lays ctx->packed_ws
-// out its own way (the counters where the other calls keep them; a TakeRow of 16 bytes per row behind).  Its report leaves with the scan:
-// k_take_copy decides from the total the scan stored whether the bodies fit, as k_packed_pack does.
+// ONE pinned block (ctx->h_batch) serves every call, in three regions, and each may be refilled WITHOUT ASKING.  The invariant:
+// every call that uploads from a region ends with a poll for the report of a kernel that runs behind that upload on the stream
+// (stream order; a switch of streams keeps it, et_ctx_set_stream), or with a terminal ET_ERR_HIP.  When that epoch word has
+// arrived, the kernel is over, and so is every upload in front of it: whoever fills the region next finds it free.  On the device
+// the workspaces are rewritten in stream order behind the kernels that read them.
+//   batch    its chunks BEGIN with the polled kernel, whose records lie where no later upload of a chunk reads; the region is
+//            kept apart because et_encode_batch_device ends with uploads and a kernel nobody polls for.  What the batch kernels are
+//            not made for -- texts above et_batch_small_max(), codes beyond 32 bits on encode, dictionaries that are not a full tree
+//            on decode -- runs through et_encode_device / et_decode_device for that stream alone, behind the batch launches (path = 1)
+//   shared   the table goes up once per call, the job records once per chunk of SHARED_CHUNK streams; every chunk ends with its poll
+//   packed   [table 2 KiB][the counters' first values][the match's pattern]: one upload per call of the part it needs, then the
+//            launches, then one poll.  The records are u64 offset arrays ON THE DEVICE: no job records, no chunks, no host loop.  A
+//            report that leaves in front of the call's last kernel carries the figures that kernel decides by (do the bodies, or the
+//            rows, fit?), so the host returns ET_ERR_CAP or ET_OK from the same figures without waiting for it.
+// The launches, (poll) where the host waits:
+//   batch encode  per chunk: k_batch_hist (poll) -> code table + header per stream, one upload -> k_batch_encode
+//   batch decode  per chunk: k_batch_heads (poll) -> et_parse_header per stream, one upload -> k_batch_decode (poll)
+//   shared        per chunk: k_shared_encode / k_shared_decode (poll)
+//   encode        table + counters -> k_packed_count -> k_packed_scan (poll) -> unless sizes only: k_packed_pack
+//   decode        table + counters -> k_packed_decode (poll)
+//   gather        table + counters -> k_gather_plan -> k_packed_scan -> k_packed_gather (poll: it alone knows the short rows); sizes only: the scan's (poll)
+//   match         counters + pattern (et_encode_pattern, on the host) -> k_match_flag -> k_packed_scan (poll) -> unless count only: k_rows_emit
+//   join          counters -> clear the table -> k_join_build -> k_join_flag (the keys' counters into the report) -> k_packed_scan (poll) -> unless count only: k_rows_emit
+//   take          counters -> k_take_plan -> k_take_scan (poll) -> unless sizes only: k_take_copy
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -78,32 +48,22 @@ constexpr size_t SCH = et::SHARED_CHUNK;
 constexpr size_t PIN_SH_TABLE = PIN_BLOB + CH * et::BATCH_ENC_SLOT;  // 2 KiB: {left-aligned code, length} x 256, or the sorted codes
 constexpr size_t PIN_SH_JOBS = PIN_SH_TABLE + 2048;                  // SharedJob[SCH]
 constexpr size_t PIN_SH_RESULTS = PIN_SH_JOBS + SCH * sizeof(et::SharedJob);  // uint2[SCH]
-// ... and the packed calls': what goes up in one copy (table, then the counters' first values), and the report
+// ... and the packed calls': what goes up -- the table, the counters' first values, the match's encoded needle (zero-padded to a
+// multiple of 4 bytes), each call one copy of the part it needs -- and the report
+constexpr size_t PK_COUNTER_BYTES = et::PACKED_WORDS * 8;
 constexpr size_t PIN_PK_TABLE = PIN_SH_RESULTS + SCH * 8;  // 2 KiB, as PIN_SH_TABLE
 constexpr size_t PIN_PK_STATS = PIN_PK_TABLE + 2048;       // u64[PACKED_WORDS]
-constexpr size_t PIN_PK_REPORT = PIN_PK_STATS + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
-// ... and the match call's one copy: the counters' first values, then the encoded needle (zero-padded to a multiple of 4 bytes)
-constexpr size_t PIN_MT_STATS = PIN_PK_REPORT + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
-constexpr size_t PIN_MT_PATTERN = PIN_MT_STATS + et::PACKED_WORDS * 8;  // MATCH_PATTERN_BYTES
-// ... and the join call's: the counters' first values
-constexpr size_t PIN_JN_STATS = PIN_MT_PATTERN + et::MATCH_PATTERN_BYTES;  // u64[PACKED_WORDS]
-// ... and the take call's: the counters' first values
-constexpr size_t PIN_TK_STATS = PIN_JN_STATS + et::PACKED_WORDS * 8;  // u64[PACKED_WORDS]
-constexpr size_t PIN_BYTES = PIN_TK_STATS + et::PACKED_WORDS * 8;
-static_assert(PIN_PK_TABLE % 16 == 0 && PIN_MT_STATS % 16 == 0, "layout of the pinned block");
-// the packed calls' device workspace: the same table and counters, then a size word per record
-constexpr size_t PK_UPLOAD = 2048 + et::PACKED_WORDS * 8, PK_SIZES = 4096;
-// ... as the match call lays it out: the counters where the other calls keep theirs, the pattern behind them (one copy), then a
-// count per tile, the tiles' first places (tiles + 1) and four masks per tile
-constexpr size_t MT_STATS = 2048, MT_PATTERN = MT_STATS + et::PACKED_WORDS * 8, MT_COUNTS = MT_PATTERN + et::MATCH_PATTERN_BYTES;
-static_assert(MT_PATTERN % 16 == 0 && MT_COUNTS % 16 == 0, "k_match_flag loads pattern words, k_packed_scan 16 bytes of counts");
-// ... as the join call lays it out: the counters, then a count per tile, the tiles' first places (tiles + 1), four masks per tile, a
-// key number per record and the table's slots
-constexpr size_t JN_STATS = 2048, JN_COUNTS = JN_STATS + et::PACKED_WORDS * 8;
-static_assert(JN_COUNTS % 16 == 0 && PIN_JN_STATS % 8 == 0, "k_packed_scan loads 16 bytes of counts");
-// ... as the take call lays it out: the counters, then a TakeRow per row where the other calls keep their size words
-constexpr size_t TK_STATS = 2048, TK_PLAN = PK_SIZES;
-static_assert(sizeof(et::TakeRow) == 16 && TK_PLAN % 16 == 0 && PIN_TK_STATS % 8 == 0, "k_take_plan stores a TakeRow as 16 bytes");
+constexpr size_t PIN_PK_PATTERN = PIN_PK_STATS + PK_COUNTER_BYTES;  // MATCH_PATTERN_BYTES
+constexpr size_t PIN_PK_REPORT = PIN_PK_PATTERN + et::MATCH_PATTERN_BYTES;  // u64[PACKED_WORDS]
+constexpr size_t PIN_BYTES = PIN_PK_REPORT + PK_COUNTER_BYTES;
+static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the pinned block");
+// The packed calls' device workspace (ctx->packed_ws) begins as the pinned region does, so an upload lands where it came from: the
+// table, the counters at PK_STATS for EVERY call, the match's pattern.  Behind the counters each call has its own layout:
+//   encode, gather   from PK_SIZES: a size word per record, or per row        take   from PK_SIZES: a TakeRow per row
+//   match   behind the pattern: the tile workspace (tile_ws)                   join   behind the counters: the tile workspace, the table's slots, a key number per record
+constexpr size_t PK_STATS = 2048, PK_PATTERN = PK_STATS + PK_COUNTER_BYTES, PK_SIZES = 4096, PK_MATCH_TILES = PK_PATTERN + et::MATCH_PATTERN_BYTES;
+static_assert(PK_PATTERN % 16 == 0 && PK_MATCH_TILES % 16 == 0 && PK_SIZES % 16 == 0 && sizeof(et::TakeRow) == 16,
+              "k_match_flag loads pattern words, k_packed_scan 16 bytes of counts or sizes, k_take_plan stores a TakeRow as 16 bytes");
 static_assert(int(et::PACKED_OK) == int(ET_OK) && int(et::PACKED_ARG) == int(ET_ERR_ARG) && int(et::PACKED_UNSUPPORTED) == int(ET_ERR_UNSUPPORTED), "a record's status byte is its et_status");
 static_assert(sizeof(et::SharedJob) == 24 && PIN_SH_TABLE % 16 == 0, "layout of the pinned block");
 static_assert(sizeof(et::BatchSpan) == 16 && sizeof(et::BatchEncJob) == 32 && sizeof(et::BatchDecJob) == 40, "job records are plain, packed data");
@@ -135,6 +95,16 @@ T *pin(et_ctx *ctx, size_t off) { return reinterpret_cast<T *>(ctx->h_batch + of
 volatile uint64_t *epoch_word(et_ctx *ctx, int which) { return pin<uint64_t>(ctx, PIN_WORDS) + which; }
 
 unsigned long long *epoch_word_dev(et_ctx *ctx, int which) { return reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_WORDS) + which); }
+
+// Has one of the addresses a bit of low_bits set?
+template <typename... P>
+bool misaligned(uintptr_t low_bits, P... ptrs) { return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & low_bits) != 0; }
+
+// The shared-table and the packed kernels decode, and compare, under a full tree alone.
+int require_complete(et_ctx *ctx, const et_codebook *cb) {
+    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    return ET_OK;
+}
 
 // Outputs of different items may not overlap (items that ask for no room take none).
 bool outputs_overlap(const et_batch_item *items, size_t n) {
@@ -197,7 +167,7 @@ int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_ou
         items[i].status = ET_OK;
         items[i].path = 0;
     }
-    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    ET_TRY(require_complete(ctx, cb));
     if (d_out && outputs_overlap(items, n_items)) return fail(ctx, ET_ERR_ARG, "outputs of different items overlap");
     DeviceGuard guard(ctx->device);
 
@@ -226,8 +196,7 @@ int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_ou
                 const uint64_t cap = d_out ? it.out_cap : ~0ull;
                 jobs[j] = et::SharedJob{it.in_off, it.out_off, static_cast<uint32_t>(it.in_len), static_cast<uint32_t>(std::min<uint64_t>(cap, 0xffffffffu))};
             } else {
-                // (out_cap codewords of at most 32 bits end within 4 out_cap bytes: the kernel's bit positions stay small)
-                jobs[j] = et::SharedJob{it.in_off, it.out_off, static_cast<uint32_t>(std::min<uint64_t>(it.in_len, it.out_cap * 4 + 8)), static_cast<uint32_t>(it.out_cap)};
+                jobs[j] = et::SharedJob{it.in_off, it.out_off, static_cast<uint32_t>(et::clip_body(it.in_len, it.out_cap)), static_cast<uint32_t>(it.out_cap)};
             }
         }
         ET_HIP(hipMemcpyAsync(ctx->batch_jobs.p, jobs, n * sizeof(et::SharedJob), hipMemcpyHostToDevice, ctx->stream));
@@ -250,48 +219,99 @@ int shared_call(et_ctx *ctx, const et_codebook *cb, const void *d_in, void *d_ou
     return ET_OK;
 }
 
-// Every packed call's one upload, behind its argument check: the table is judged, the workspaces made (ws_words size words behind
-// the table and the counters), then the table and the counters' first values go up in one copy.
-int packed_upload(et_ctx *ctx, const et_codebook *cb, bool encode, size_t ws_words, uint32_t *n_codes) {
-    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+// ---- what the packed calls are made of -------------------------------------------------------------------------------------
+// Offsets into ctx->packed_ws, handed out from `end` on: a call lays its workspace out ONCE, sizes ensure() by `end` and forms its
+// pointers from the offsets it got.
+struct Bump {
+    size_t end;
+    size_t take(size_t bytes, size_t align) {
+        const size_t at = (end + align - 1) & ~(align - 1);
+        end = at + bytes;
+        return at;
+    }
+};
+
+template <typename T>
+T *ws(et_ctx *ctx, size_t off) { return reinterpret_cast<T *>(static_cast<uint8_t *>(ctx->packed_ws.p) + off); }
+
+// The tile workspace of the match and the join: a count per tile (padded to 16 bytes), the tiles' first places (tiles + 1), four masks per tile.
+struct TileOffsets { size_t counts, base, masks; };
+
+TileOffsets tile_ws(Bump &b, size_t n_tiles) {
+    TileOffsets t;
+    t.counts = b.take((n_tiles * 4 + 15) & ~static_cast<size_t>(15), 16);
+    t.base = b.take((n_tiles + 1) * 8, 16);
+    t.masks = b.take(n_tiles * (et::MATCH_TILE / 64) * 8, 8);
+    return t;
+}
+
+et::TileWs tile_ptrs(et_ctx *ctx, const TileOffsets &t) { return et::TileWs{ws<unsigned long long>(ctx, t.masks), ws<uint32_t>(ctx, t.counts), ws<uint64_t>(ctx, t.base)}; }
+
+// The pinned block and a workspace of ws_bytes.
+int packed_ensure(et_ctx *ctx, size_t ws_bytes) {
     ET_TRY(ensure_batch(ctx, 1, 2048));
-    ET_TRY(ensure(ctx, ctx->packed_ws, PK_SIZES + ws_words * sizeof(uint32_t)));
-    *n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), encode);
+    return ensure(ctx, ctx->packed_ws, ws_bytes);
+}
+
+// The counters' first values in the pinned region (free to fill: this file's header): zero, and no failed record yet.
+uint64_t *first_counters(et_ctx *ctx) {
     uint64_t *first = pin<uint64_t>(ctx, PIN_PK_STATS);
-    std::memset(first, 0, et::PACKED_WORDS * 8);
+    std::memset(first, 0, PK_COUNTER_BYTES);
     first[et::PACKED_FIRST] = ~0ull;
-    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_UPLOAD, hipMemcpyHostToDevice, ctx->stream));
+    return first;
+}
+
+// The next epoch, and where the kernels of this call count and report.
+et::PackedReport next_report(et_ctx *ctx) {
+    return et::PackedReport{ws<unsigned long long>(ctx, PK_STATS), reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), ++ctx->batch_epoch};
+}
+
+// Behind the launches: the poll; the report's words are there when it returns ET_OK.
+int packed_poll(et_ctx *ctx, uint64_t epoch, const char *what) {
+    ET_HIP(hipGetLastError());
+    return wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, what);
+}
+
+const uint64_t *report_words(et_ctx *ctx) { return pin<uint64_t>(ctx, PIN_PK_REPORT); }
+
+// The pair of failure counters at rep[word]: how many failed and, when any did, the lowest of them and its status.
+void read_failures(const uint64_t *rep, int word, uint64_t *n, uint64_t *first, int32_t *status) {
+    *n = rep[word];
+    if (!*n) return;
+    *first = rep[word + 1] >> 8;
+    *status = static_cast<int32_t>(rep[word + 1] & 0xffu);
+}
+static_assert(et::PACKED_FIRST == et::PACKED_N_FAILED + 1 && et::JOIN_KEYS_FIRST == et::JOIN_KEYS_FAILED + 1, "read_failures");
+
+// The calls with a table on the device (encode, decode, gather), behind their argument check: the table is judged, the workspace
+// made (ws_words size words behind the table and the counters), then the table and the counters' first values go up in one copy.
+int packed_upload(et_ctx *ctx, const et_codebook *cb, bool encode, size_t ws_words, uint32_t *n_codes) {
+    ET_TRY(require_complete(ctx, cb));
+    ET_TRY(packed_ensure(ctx, PK_SIZES + ws_words * sizeof(uint32_t)));
+    *n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), encode);
+    first_counters(ctx);
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_STATS + PK_COUNTER_BYTES, hipMemcpyHostToDevice, ctx->stream));
     return ET_OK;
 }
 
-// The encode and the range decode, up to the launch: the arguments, then packed_upload.  *go = false: the call is over
-// (an error, or n == 0) with the returned status.
-int packed_begin(et_ctx *ctx, const et_codebook *cb, const void *d_in, const void *d_out, const uint64_t *idx_a, const uint64_t *idx_b, size_t n, et_packed_result *res,
-                 bool encode, uint32_t *n_codes, bool *go) {
-    *go = false;
-    if (!ctx) return ET_ERR_ARG;
+// ... their arguments (the encode's and the range decode's), and *res cleared ...
+int packed_args(et_ctx *ctx, const et_codebook *cb, const void *d_in, const void *d_out, const uint64_t *idx_a, const uint64_t *idx_b, size_t n, et_packed_result *res,
+                bool encode) {
     if (!cb || !res || !d_in || !idx_a || !idx_b || (!d_out && !encode)) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(idx_a) | reinterpret_cast<uintptr_t>(idx_b)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(7, idx_a, idx_b)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
     if (n > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
     *res = et_packed_result{};
-    if (n == 0) return ET_OK;
-    ET_TRY(packed_upload(ctx, cb, encode, encode ? n : 0, n_codes));
-    *go = true;
     return ET_OK;
 }
 
-// ... and behind it: the poll, the report into *res.
-int packed_end(et_ctx *ctx, uint64_t epoch, et_packed_result *res) {
-    ET_HIP(hipGetLastError());
-    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the packed batch's report never reached the host"));
-    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+// ... and their end: the poll, the report into *res; ET_ERR_CAP (`too_much`) when a capacity was given and the report exceeds it.
+int packed_end(et_ctx *ctx, uint64_t epoch, et_packed_result *res, bool capped, uint64_t cap, const char *too_much) {
+    ET_TRY(packed_poll(ctx, epoch, "the packed batch's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
     res->out_bytes = rep[et::PACKED_BYTES];
-    res->n_failed = rep[et::PACKED_N_FAILED];
     res->n_short = rep[et::PACKED_N_SHORT];
-    if (res->n_failed) {
-        res->first_failed = rep[et::PACKED_FIRST] >> 8;
-        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
-    }
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (capped && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, too_much);  // (the call's last kernel saw the same two figures)
     return ET_OK;
 }
 
@@ -318,36 +338,28 @@ extern "C" int et_encode_packed_device(et_ctx *ctx, const et_codebook *cb, const
                                        size_t cap, uint64_t *d_out_index, uint8_t *d_status, et_packed_result *res) {
     if (!ctx) return ET_ERR_ARG;
     DeviceGuard guard(ctx->device);
+    ET_TRY(packed_args(ctx, cb, d_text, d_out, d_text_index, d_out_index, n, res, true));
+    if (n == 0) return ET_OK;
     uint32_t n_codes = 0;
-    bool go = false;
-    ET_TRY(packed_begin(ctx, cb, d_text, d_out, d_text_index, d_out_index, n, res, true, &n_codes, &go));
-    if (!go) return ET_OK;
-    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
-    const uint64_t epoch = ++ctx->batch_epoch;
-    et::launch_packed_encode(ctx->stream, d_text, text_bytes, d_text_index, static_cast<uint32_t>(n), d_out, cap, d_out_index, d_status, reinterpret_cast<const uint2 *>(ws),
-                             reinterpret_cast<uint32_t *>(ws + PK_SIZES), reinterpret_cast<unsigned long long *>(ws + 2048),
-                             reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
-    ET_TRY(packed_end(ctx, epoch, res));
-    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the bodies take more than cap bytes");  // (k_packed_pack saw the same two figures)
-    return ET_OK;
+    ET_TRY(packed_upload(ctx, cb, true, n, &n_codes));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_packed_encode(ctx->stream, d_text, text_bytes, d_text_index, static_cast<uint32_t>(n), d_out, cap, d_out_index, d_status, ws<const uint2>(ctx, 0),
+                             ws<uint32_t>(ctx, PK_SIZES), report);
+    return packed_end(ctx, report.epoch, res, d_out != nullptr, cap, "the bodies take more than cap bytes");
 }
 
 extern "C" int et_decode_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
                                        const uint64_t *d_text_index, size_t n, void *d_out, size_t cap, uint32_t *d_written, uint8_t *d_status, et_packed_result *res) {
     if (!ctx) return ET_ERR_ARG;
     DeviceGuard guard(ctx->device);
+    ET_TRY(packed_args(ctx, cb, d_bodies, d_out, d_body_index, d_text_index, n, res, false));
+    if (n == 0) return ET_OK;
     uint32_t n_codes = 0;
-    bool go = false;
-    ET_TRY(packed_begin(ctx, cb, d_bodies, d_out, d_body_index, d_text_index, n, res, false, &n_codes, &go));
-    if (!go) return ET_OK;
-    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
-    const uint64_t epoch = ++ctx->batch_epoch;
-    et::launch_packed_decode(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n), d_out, cap, reinterpret_cast<const uint2 *>(ws), n_codes,
-                             d_written, d_status, reinterpret_cast<unsigned long long *>(ws + 2048), reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)),
-                             static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 4), epoch);
-    ET_TRY(packed_end(ctx, epoch, res));
-    if (res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "text_index[n] lies beyond cap");  // (k_packed_decode saw the same two figures)
-    return ET_OK;
+    ET_TRY(packed_upload(ctx, cb, false, 0, &n_codes));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_packed_decode(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n), 0}, d_out, cap, ws<const uint2>(ctx, 0),
+                             n_codes, d_written, d_status, report, static_cast<uint32_t *>(ctx->batch_counter.p));
+    return packed_end(ctx, report.epoch, res, true, cap, "text_index[n] lies beyond cap");
 }
 
 extern "C" int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
@@ -355,24 +367,19 @@ extern "C" int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb
                                               uint64_t *d_out_index, uint32_t *d_written, uint8_t *d_status, et_packed_result *res) {
     if (!ctx) return ET_ERR_ARG;
     if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || !d_rows || !d_out_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index) | reinterpret_cast<uintptr_t>(d_out_index)) & 7)
-        return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_rows) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (misaligned(7, d_body_index, d_text_index, d_out_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
     if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
     *res = et_packed_result{};
     if (n_rows == 0) return ET_OK;
     DeviceGuard guard(ctx->device);
     uint32_t n_codes = 0;
     ET_TRY(packed_upload(ctx, cb, false, n_rows, &n_codes));
-    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
-    const uint64_t epoch = ++ctx->batch_epoch;
-    et::launch_packed_gather(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), d_rows, static_cast<uint32_t>(n_rows), d_out, cap,
-                             d_out_index, reinterpret_cast<const uint2 *>(ws), n_codes, d_written, d_status, reinterpret_cast<uint32_t *>(ws + PK_SIZES),
-                             reinterpret_cast<unsigned long long *>(ws + 2048), reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)),
-                             static_cast<uint32_t *>(ctx->batch_counter.p), epoch_word_dev(ctx, 4), epoch);
-    ET_TRY(packed_end(ctx, epoch, res));
-    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the rows take more than cap bytes");  // (k_packed_gather saw the same two figures)
-    return ET_OK;
+    const et::PackedReport report = next_report(ctx);
+    et::launch_packed_gather(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, d_rows,
+                             static_cast<uint32_t>(n_rows), d_out, cap, d_out_index, ws<const uint2>(ctx, 0), n_codes, d_written, d_status, ws<uint32_t>(ctx, PK_SIZES), report,
+                             static_cast<uint32_t *>(ctx->batch_counter.p));
+    return packed_end(ctx, report.epoch, res, d_out != nullptr, cap, "the rows take more than cap bytes");
 }
 
 extern "C" size_t et_match_pattern_max(void) { return et::MATCH_NEEDLE_MAX; }
@@ -384,27 +391,24 @@ extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const 
                                       size_t cap_rows, uint8_t *d_status, et_match_result *res) {
     if (!ctx) return ET_ERR_ARG;
     if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || (!needle && needle_len)) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_rows) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (misaligned(7, d_body_index, d_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
     if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
     if (needle_len > et::MATCH_NEEDLE_MAX) return fail(ctx, ET_ERR_ARG, "the needle is longer than et_match_pattern_max()");
     const int what = mode & ~ET_MATCH_NOT;
     if (what != ET_MATCH_EQUAL && what != ET_MATCH_PREFIX) return fail(ctx, ET_ERR_ARG, "unknown mode");
     *res = et_match_result{};
     if (n_records == 0) return ET_OK;
-    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    ET_TRY(require_complete(ctx, cb));
     DeviceGuard guard(ctx->device);
-    const uint32_t n = static_cast<uint32_t>(n_records), n_tiles = (n + et::MATCH_TILE - 1) / et::MATCH_TILE;
-    const size_t counts_bytes = (static_cast<size_t>(n_tiles) * 4 + 15) & ~static_cast<size_t>(15);
-    const size_t at_base = MT_COUNTS + counts_bytes, at_masks = at_base + (static_cast<size_t>(n_tiles) + 1) * 8;
-    ET_TRY(ensure_batch(ctx, 1, 2048));
-    ET_TRY(ensure(ctx, ctx->packed_ws, at_masks + static_cast<size_t>(n_tiles) * (et::MATCH_TILE / 64) * 8));
+    const et::PackedStore store{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    Bump layout{PK_MATCH_TILES};
+    const TileOffsets tiles = tile_ws(layout, (store.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    ET_TRY(packed_ensure(ctx, layout.end));
 
-    // the needle's bits and the counters' first values: free to fill (this file's header), up in one copy
-    uint64_t *first = pin<uint64_t>(ctx, PIN_MT_STATS);
-    std::memset(first, 0, et::PACKED_WORDS * 8);
-    first[et::PACKED_FIRST] = ~0ull;
-    uint8_t *pattern = pin<uint8_t>(ctx, PIN_MT_PATTERN);
+    // the counters' first values and the needle's bits, up in one copy
+    const uint64_t *first = first_counters(ctx);
+    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
     uint64_t bits = 0;
     const int rc = et_encode_pattern(cb, needle, needle_len, pattern, et::MATCH_PATTERN_BYTES, &bits);
     if (rc != ET_OK && rc != ET_ERR_UNSUPPORTED) return fail(ctx, rc, "et_encode_pattern");
@@ -421,22 +425,14 @@ extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const 
         job.head_mask |= static_cast<uint64_t>(left >= 8 ? 0xffu : (0xffu << (8 - left)) & 0xffu) << (8 * k);
     }
     res->pattern_bits = job.pat_bits;
-    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
-    ET_HIP(hipMemcpyAsync(ws + MT_STATS, first, et::PACKED_WORDS * 8 + padded, hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t epoch = ++ctx->batch_epoch;
-    et::launch_match(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, n, reinterpret_cast<const uint32_t *>(ws + MT_PATTERN), job, d_rows, cap_rows, d_status,
-                     reinterpret_cast<unsigned long long *>(ws + at_masks), reinterpret_cast<uint32_t *>(ws + MT_COUNTS), reinterpret_cast<uint64_t *>(ws + at_base),
-                     reinterpret_cast<unsigned long long *>(ws + MT_STATS), reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
-    ET_HIP(hipGetLastError());
-    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the match's report never reached the host"));
-    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+    ET_HIP(hipMemcpyAsync(ws<uint8_t>(ctx, PK_STATS), first, PK_COUNTER_BYTES + padded, hipMemcpyHostToDevice, ctx->stream));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_match(ctx->stream, store, ws<const uint32_t>(ctx, PK_PATTERN), job, d_rows, cap_rows, d_status, tile_ptrs(ctx, tiles), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the match's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
     res->n_match = rep[et::PACKED_BYTES];
-    res->n_failed = rep[et::PACKED_N_FAILED];
-    if (res->n_failed) {
-        res->first_failed = rep[et::PACKED_FIRST] >> 8;
-        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
-    }
-    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records match than cap_rows");  // (k_match_emit saw the same two figures)
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records match than cap_rows");  // (k_rows_emit saw the same two figures)
     return ET_OK;
 }
 
@@ -463,9 +459,8 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
     if (!ctx) return ET_ERR_ARG;
     if (!cb || !res || !d_bodies || !d_body_index || !d_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
     if (n_keys && (!d_key_bodies || !d_key_body_index || !d_key_text_index)) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_key_body_index) | reinterpret_cast<uintptr_t>(d_key_text_index)) & 7) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_key_of_row)) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (misaligned(7, d_body_index, d_text_index, d_key_body_index, d_key_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_rows, d_key_of_row)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
     if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
     if (n_keys > et::ET_JOIN_KEYS_MAX) return fail(ctx, ET_ERR_ARG, "more keys than et_join_keys_max()");
     if (mode != 0 && mode != ET_MATCH_NOT) return fail(ctx, ET_ERR_ARG, "unknown mode");
@@ -473,46 +468,31 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
     if (d_key_of_row && !d_rows) return fail(ctx, ET_ERR_ARG, "key numbers without rows");
     *res = et_join_result{};
     if (n_records == 0) return ET_OK;
-    if (et_codebook_is_complete(cb) != ET_OK) return fail(ctx, ET_ERR_UNSUPPORTED, "the code table is not a full prefix-free tree of codes up to 32 bits");
+    ET_TRY(require_complete(ctx, cb));
     DeviceGuard guard(ctx->device);
-    const uint32_t n = static_cast<uint32_t>(n_records), n_tiles = (n + et::MATCH_TILE - 1) / et::MATCH_TILE;
+    const et::PackedStore records{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    const et::PackedStore keys{d_key_bodies, key_body_bytes, d_key_body_index, d_key_text_index, static_cast<uint32_t>(n_keys), 0};
     const size_t slots = et::et_join_slots_for(n_keys);
-    const size_t counts_bytes = (static_cast<size_t>(n_tiles) * 4 + 15) & ~static_cast<size_t>(15);
-    const size_t at_base = JN_COUNTS + counts_bytes, at_masks = at_base + (static_cast<size_t>(n_tiles) + 1) * 8;
-    const size_t at_table = at_masks + static_cast<size_t>(n_tiles) * (et::MATCH_TILE / 64) * 8, at_key_of = at_table + slots * 8;
-    ET_TRY(ensure_batch(ctx, 1, 2048));
-    ET_TRY(ensure(ctx, ctx->packed_ws, at_key_of + static_cast<size_t>(n) * 4));
+    Bump layout{PK_STATS + PK_COUNTER_BYTES};
+    const TileOffsets tiles = tile_ws(layout, (records.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const size_t at_table = layout.take(slots * 8, 8), at_key_of = layout.take(static_cast<size_t>(records.n) * 4, 4);
+    ET_TRY(packed_ensure(ctx, layout.end));
 
-    // the counters' first values: free to fill (this file's header)
-    uint64_t *first = pin<uint64_t>(ctx, PIN_JN_STATS);
-    std::memset(first, 0, et::PACKED_WORDS * 8);
-    first[et::PACKED_FIRST] = first[et::JOIN_KEYS_FIRST] = first[et::JOIN_MIN] = ~0ull;
-    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
-    ET_HIP(hipMemcpyAsync(ws + JN_STATS, first, et::PACKED_WORDS * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (n_keys) ET_HIP(hipMemsetAsync(ws + at_table, 0xff, slots * 8, ctx->stream));
-    const et::JoinSide records{d_bodies, body_bytes, d_body_index, d_text_index, n, 0};
-    const et::JoinSide keys{d_key_bodies, key_body_bytes, d_key_body_index, d_key_text_index, static_cast<uint32_t>(n_keys), 0};
-    const uint64_t epoch = ++ctx->batch_epoch;
-    et::launch_join(ctx->stream, records, keys, (mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u, reinterpret_cast<unsigned long long *>(ws + at_table), slots, d_rows, cap_rows,
-                    d_key_of_row, d_status, d_key_status, reinterpret_cast<unsigned long long *>(ws + at_masks), reinterpret_cast<uint32_t *>(ws + JN_COUNTS),
-                    reinterpret_cast<uint64_t *>(ws + at_base), reinterpret_cast<uint32_t *>(ws + at_key_of), reinterpret_cast<unsigned long long *>(ws + JN_STATS),
-                    reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
-    ET_HIP(hipGetLastError());
-    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the join's report never reached the host"));
-    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+    // the counters' first values: the keys' lowest failure and the smallest body of a key beside the records'
+    uint64_t *first = first_counters(ctx);
+    first[et::JOIN_KEYS_FIRST] = first[et::JOIN_MIN] = ~0ull;
+    ET_HIP(hipMemcpyAsync(ws<uint8_t>(ctx, PK_STATS), first, PK_COUNTER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    if (n_keys) ET_HIP(hipMemsetAsync(ws<uint8_t>(ctx, at_table), 0xff, slots * 8, ctx->stream));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_join(ctx->stream, records, keys, (mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u, ws<unsigned long long>(ctx, at_table), slots, d_rows, cap_rows, d_key_of_row,
+                    d_status, d_key_status, tile_ptrs(ctx, tiles), ws<uint32_t>(ctx, at_key_of), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the join's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
     if (rep[et::PACKED_N_FAILED] & et::JOIN_FAULT_BIT) return fail(ctx, ET_ERR_HIP, "a probe sequence of the join's table met no empty slot");
     res->n_match = rep[et::PACKED_BYTES];
-    res->n_failed = rep[et::PACKED_N_FAILED];
-    if (res->n_failed) {
-        res->first_failed = rep[et::PACKED_FIRST] >> 8;
-        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
-    }
-    res->n_keys_failed = rep[et::JOIN_KEYS_FAILED];
-    if (res->n_keys_failed) {
-        res->first_key_failed = rep[et::JOIN_KEYS_FIRST] >> 8;
-        res->first_key_status = static_cast<int32_t>(rep[et::JOIN_KEYS_FIRST] & 0xffu);
-    }
-    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_join_emit saw the same two figures)
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    read_failures(rep, et::JOIN_KEYS_FAILED, &res->n_keys_failed, &res->first_key_failed, &res->first_key_status);
+    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_rows_emit saw the same two figures)
     return ET_OK;
 }
 
@@ -523,10 +503,8 @@ extern "C" int et_take_packed_device(et_ctx *ctx, const void *d_bodies, size_t b
                                      et_take_result *res) {
     if (!ctx) return ET_ERR_ARG;
     if (!res || !d_bodies || !d_body_index || !d_text_index || !d_rows || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index) | reinterpret_cast<uintptr_t>(d_out_body_index) |
-         reinterpret_cast<uintptr_t>(d_out_text_index)) & 7)
-        return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_rows) & 3) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (misaligned(7, d_body_index, d_text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
     if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
     if (d_out && cap && body_bytes) {  // (in-place compaction is not this call's)
         const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
@@ -535,29 +513,16 @@ extern "C" int et_take_packed_device(et_ctx *ctx, const void *d_bodies, size_t b
     *res = et_take_result{};
     if (n_rows == 0) return ET_OK;
     DeviceGuard guard(ctx->device);
-    ET_TRY(ensure_batch(ctx, 1, 2048));
-    ET_TRY(ensure(ctx, ctx->packed_ws, TK_PLAN + n_rows * sizeof(et::TakeRow)));
-
-    // the counters' first values: free to fill (this file's header)
-    uint64_t *first = pin<uint64_t>(ctx, PIN_TK_STATS);
-    std::memset(first, 0, et::PACKED_WORDS * 8);
-    first[et::PACKED_FIRST] = ~0ull;
-    uint8_t *ws = static_cast<uint8_t *>(ctx->packed_ws.p);
-    ET_HIP(hipMemcpyAsync(ws + TK_STATS, first, et::PACKED_WORDS * 8, hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t epoch = ++ctx->batch_epoch;
-    et::launch_take(ctx->stream, d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), d_rows, static_cast<uint32_t>(n_rows), d_out, cap,
-                    d_out_body_index, d_out_text_index, d_status, reinterpret_cast<et::TakeRow *>(ws + TK_PLAN), reinterpret_cast<unsigned long long *>(ws + TK_STATS),
-                    reinterpret_cast<unsigned long long *>(pin<uint64_t>(ctx, PIN_PK_REPORT)), epoch_word_dev(ctx, 4), epoch);
-    ET_HIP(hipGetLastError());
-    ET_TRY(wait_for_word<uint64_t>(ctx, epoch_word(ctx, 4), epoch, 2000.0, "the take's report never reached the host"));
-    const uint64_t *rep = pin<uint64_t>(ctx, PIN_PK_REPORT);
+    ET_TRY(packed_ensure(ctx, PK_SIZES + n_rows * sizeof(et::TakeRow)));
+    ET_HIP(hipMemcpyAsync(ws<uint8_t>(ctx, PK_STATS), first_counters(ctx), PK_COUNTER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_take(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, d_rows, static_cast<uint32_t>(n_rows),
+                    d_out, cap, d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, PK_SIZES), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the take's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
     res->out_bytes = rep[et::PACKED_BYTES];
     res->text_bytes = rep[et::TAKE_TEXT_BYTES];
-    res->n_failed = rep[et::PACKED_N_FAILED];
-    if (res->n_failed) {
-        res->first_failed = rep[et::PACKED_FIRST] >> 8;
-        res->first_status = static_cast<int32_t>(rep[et::PACKED_FIRST] & 0xffu);
-    }
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
     if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the taken bodies need more than cap bytes");  // (k_take_copy saw the same two figures)
     return ET_OK;
 }
@@ -566,12 +531,11 @@ extern "C" int et_selftest_join_hash(et_ctx *ctx, const void *d_bodies, size_t b
                                      uint64_t *d_hash) {
     if (!ctx) return ET_ERR_ARG;
     if (!d_bodies || !d_body_index || !d_text_index || !d_hash) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_body_index) | reinterpret_cast<uintptr_t>(d_text_index) | reinterpret_cast<uintptr_t>(d_hash)) & 7)
-        return fail(ctx, ET_ERR_ARG, "an array is not 8-byte aligned");
+    if (misaligned(7, d_body_index, d_text_index, d_hash)) return fail(ctx, ET_ERR_ARG, "an array is not 8-byte aligned");
     if (n > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
     if (n == 0) return ET_OK;
     DeviceGuard guard(ctx->device);
-    et::launch_join_hash(ctx->stream, et::JoinSide{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n), 0}, d_hash);
+    et::launch_join_hash(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n), 0}, d_hash);
     ET_HIP(hipGetLastError());
     ET_HIP(hipStreamSynchronize(ctx->stream));
     return ET_OK;
@@ -629,12 +593,7 @@ extern "C" int et_encode_batch_device(et_ctx *ctx, const void *d_in, void *d_out
                 continue;
             }
             uint8_t *slot = blob + blob_len;
-            uint32_t *tab = reinterpret_cast<uint32_t *>(slot);
-            for (int s = 0; s < 256; ++s) {
-                const uint32_t len = cb.length[s], code = cb.data[s];
-                tab[2 * s] = len ? (len == 32 ? code : (code & ((1u << len) - 1u)) << (32 - len)) : 0u;  // left-aligned
-                tab[2 * s + 1] = len;
-            }
+            fill_shared_table(&cb, reinterpret_cast<uint32_t *>(slot), true);
             size_t header_len = 0;
             rc = et_write_header(&cb, it.in_len, slot + 2048, et::BATCH_HEADER_PAD - 8, &header_len);
             if (rc != ET_OK) {

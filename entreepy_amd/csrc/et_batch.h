@@ -78,43 +78,56 @@ void launch_shared_encode(hipStream_t stream, const void *d_in, void *d_out, con
 void launch_shared_decode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *codes,
                           uint32_t n_codes, uint2 *host_results, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
 
-// The packed calls (et_encode_packed_device / et_decode_packed_device): the shared-table kernels with their jobs read from
-// u64 offset arrays on the device.  What a record's status byte holds is its et_status itself (et_batch.cpp asserts the values).
+// The packed calls: the shared-table kernels with their jobs read from u64 offset arrays on the device.  What a record's status
+// byte holds is its et_status itself (et_batch.cpp asserts the values).
 enum PackedStatus : uint32_t { PACKED_OK = 0, PACKED_ARG = 6, PACKED_UNSUPPORTED = 7 };
 // The words of the counters in device memory (`stats`; the host uploads {0, ~0, 0} in front of a call) and of the report in
 // pinned memory (`host_result`): PACKED_FIRST = the lowest failed record << 8 | its status.
 enum PackedWord { PACKED_BYTES = 0, PACKED_N_FAILED = 1, PACKED_FIRST = 2, PACKED_N_SHORT = 3, PACKED_WORDS = 8 };
 constexpr uint32_t PACKED_SCAN_TILE = 4096;  // records per trip of k_packed_scan's one workgroup
 
-// k_packed_count, k_packed_scan and -- unless d_out is null: sizes only -- k_packed_pack, in stream order.  sizes: n words of
-// workspace.  The report (host_result, then `epoch` into *host_done) leaves with the scan, in front of the pack.
-void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_bytes, const uint64_t *text_index, uint32_t n, void *d_out, uint64_t cap,
-                          uint64_t *out_index, uint8_t *d_status, const uint2 *table, uint32_t *sizes, unsigned long long *stats,
-                          unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
-// k_packed_decode.  codes as launch_shared_decode's; counter as above.
-void launch_packed_decode(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n, void *d_out,
-                          uint64_t cap, const uint2 *codes, uint32_t n_codes, uint32_t *d_written, uint8_t *d_status, unsigned long long *stats,
-                          unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch);
-// The gather call (et_decode_packed_gather_device): k_gather_plan (one lane per row: the room of record rows[k], or none and why,
-// into `sizes`, n_rows words of workspace, and d_status), k_packed_scan (sizes -> out_index) and -- unless d_out is null: sizes
-// only -- k_packed_gather (k_packed_decode's loop over the rows), in stream order.  The report leaves with the last of them: with
-// the decode, which alone knows the short rows, or with the scan of a sizes-only call.
-constexpr uint32_t GATHER_PLAN_GRID = 1024;  // workgroups of k_gather_plan at most: a row per lane and trip
-void launch_packed_gather(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
-                          const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_index, const uint2 *codes, uint32_t n_codes, uint32_t *d_written,
-                          uint8_t *d_status, uint32_t *sizes, unsigned long long *stats, unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done,
-                          unsigned long long epoch);
+struct PackedStore {  // a packed store on the device: record j is bodies[body_index[j], body_index[j + 1]), text_index[j + 1] - text_index[j] symbols
+    const void *bodies;
+    uint64_t body_bytes;
+    const uint64_t *body_index, *text_index;
+    uint32_t n, pad;
+};
+// Where a call's counters lie and where its report goes: `stats` on the device (PackedWord), host_result and host_done pinned; the
+// kernel that reports stores host_result, then `epoch` into *host_done.
+struct PackedReport {
+    unsigned long long *stats, *host_result, *host_done;
+    unsigned long long epoch;
+};
+// count codewords of at most 32 bits end within 4 count bytes: what of a body of `bytes` the decode kernels look at, so that
+// decode_stream's bit positions stay small.
+constexpr uint64_t clip_body(uint64_t bytes, uint64_t count) { return bytes < count * 4 + 8 ? bytes : count * 4 + 8; }
 
-// The match call (et_match_packed_device): which records of a packed store begin with, or equal, a needle -- judged on the
-// compressed bytes, against the needle's own bits under the table (et_encode_pattern, on the host); no table on the device.
-//   k_match_flag   one record per lane, tiles of MATCH_TILE records: the record judged as k_gather_plan judges it, its status byte, the
-//                  first MATCH_HEAD_BITS bits of the pattern compared per lane, the rest by the whole wavefront for one surviving lane
-//                  at a time; a u64 ballot mask per 64 records and a u32 count per tile into the workspace
+// The encode (et_encode_packed_device): k_packed_count, k_packed_scan and -- unless d_out is null: sizes only -- k_packed_pack, in
+// stream order.  table: 256 x {left-aligned code, length} on the device; sizes: n words of workspace.  The report leaves with the
+// scan, in front of the pack.
+void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_bytes, const uint64_t *text_index, uint32_t n, void *d_out, uint64_t cap,
+                          uint64_t *out_index, uint8_t *d_status, const uint2 *table, uint32_t *sizes, const PackedReport &report);
+// The decode (et_decode_packed_device): k_packed_decode.  codes as launch_shared_decode's; counter as above.
+void launch_packed_decode(hipStream_t stream, const PackedStore &store, void *d_out, uint64_t cap, const uint2 *codes, uint32_t n_codes, uint32_t *d_written,
+                          uint8_t *d_status, const PackedReport &report, uint32_t *counter);
+// The gather (et_decode_packed_gather_device): k_gather_plan (one lane per row: the room of record rows[k], or none and why, into
+// `sizes`, n_rows words of workspace, and d_status), k_packed_scan (sizes -> out_index) and -- unless d_out is null: sizes only --
+// k_packed_gather (k_packed_decode's loop over the rows), in stream order.  The report leaves with the last of them: with the
+// decode, which alone knows the short rows, or with the scan of a sizes-only call.
+constexpr uint32_t GATHER_PLAN_GRID = 1024;  // workgroups of k_gather_plan at most: a row per lane and trip
+void launch_packed_gather(hipStream_t stream, const PackedStore &store, const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_index,
+                          const uint2 *codes, uint32_t n_codes, uint32_t *d_written, uint8_t *d_status, uint32_t *sizes, const PackedReport &report, uint32_t *counter);
+
+// The match (et_match_packed_device): which records of a packed store begin with, or equal, a needle -- judged on the compressed
+// bytes, against the needle's own bits under the table (et_encode_pattern, on the host); no table on the device.
+//   k_match_flag   one record per lane, tiles of MATCH_TILE records: the record judged, its status byte, the first MATCH_HEAD_BITS
+//                  bits of the pattern compared per lane, the rest by the whole wavefront for one surviving lane at a time; a u64
+//                  ballot mask per 64 records and a u32 count per tile into the workspace
 //   k_packed_scan  the tile counts -> the tiles' first places in d_rows, n_match; its report is the call's
-//   k_match_emit   (unless d_rows is null: count only) per tile, a record's rank is a popcount prefix over the tile's masks
+//   k_rows_emit    (unless d_rows is null: count only) per tile, a record's rank is a popcount prefix over the tile's masks
 constexpr uint32_t MATCH_HEAD_BITS = 64;                      // what a lane compares alone: one aligned 8-byte load, or two
 constexpr uint32_t MATCH_TILE = 256;                          // records per tile: one trip of a workgroup
-constexpr uint32_t MATCH_GRID = 2048;                         // workgroups of k_match_flag and k_match_emit at most
+constexpr uint32_t MATCH_GRID = 2048;                         // workgroups of k_match_flag and k_rows_emit at most
 constexpr uint32_t MATCH_NEEDLE_MAX = 4096;                   // bytes of text in a needle
 constexpr uint32_t MATCH_PATTERN_BYTES = MATCH_NEEDLE_MAX * 4;  // ... which take at most 32 bits each
 enum MatchFlag : uint32_t { MATCH_F_EQUAL = 1, MATCH_F_NOT = 2, MATCH_F_NEVER = 4 };  // NEVER: a needle byte without a code
@@ -125,15 +138,18 @@ struct MatchJob {
     uint32_t flags;            // MatchFlag
     uint32_t pad;
 };
-// pattern: the encoded needle on the device, zero-padded to a multiple of 4 bytes (4-byte aligned).  masks: 4 u64 per tile,
-// counts: a u32 per tile (16-byte aligned), base: tiles + 1 u64 (k_packed_scan's out_index) -- all workspace.  The report
-// ({n_match, failed, first << 8 | status}, then `epoch`) leaves with the scan, in front of k_match_emit.
-void launch_match(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
-                  const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, unsigned long long *masks, uint32_t *counts,
-                  uint64_t *base, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
+struct TileWs {  // the tile workspace of the match and the join
+    unsigned long long *masks;  // 4 u64 per tile: a ballot per 64 records
+    uint32_t *counts;           // a u32 per tile (16-byte aligned)
+    uint64_t *base;             // tiles + 1 u64: k_packed_scan's out_index
+};
+// pattern: the encoded needle on the device, zero-padded to a multiple of 4 bytes (4-byte aligned).  The report ({n_match, failed,
+// first << 8 | status}, then `epoch`) leaves with the scan, in front of k_rows_emit.
+void launch_match(hipStream_t stream, const PackedStore &store, const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status,
+                  const TileWs &tiles, const PackedReport &report);
 
-// The join call (et_join_packed_device): which records of a packed store equal SOME key of a key set -- a packed store itself --
-// decided on the compressed bytes through a hash table in the workspace (et_join.h: the hash, the slot format, the table's size).
+// The join (et_join_packed_device): which records of a packed store equal SOME key of a key set -- a packed store itself -- decided
+// on the compressed bytes through a hash table in the workspace (et_join.h: the hash, the slot format, the table's size).
 //   (clear)        the table's slots to ET_JOIN_EMPTY: one hipMemsetAsync
 //   k_join_build   one key per lane: judged, its status byte, hashed, inserted by compare-and-swap and linear probing; equal keys
 //                  meet in one slot and atomicMin leaves the lowest number there; the smallest and largest body of the valid keys
@@ -141,35 +157,28 @@ void launch_match(hipStream_t stream, const void *d_bodies, uint64_t body_bytes,
 //                  shorter than some key's is hashed, probed and confirmed by bytes; a u64 ballot mask per 64 records, a u32 count
 //                  per tile and a u32 key number per record into the workspace; its first workgroup reports the keys' counters
 //   k_packed_scan  the tile counts -> the tiles' first places in d_rows, n_match; its report is the call's
-//   k_join_emit    (unless d_rows is null: count only) k_match_emit's ranks; the record's number and, when asked for, its key's
+//   k_rows_emit    (unless d_rows is null: count only) the match's; the record's number and, when asked for, its key's
 // A lane hashes and compares a body of up to JOIN_LANE_BYTES alone; a longer one is taken from the ballot and handled by its
 // whole wavefront, 8 bytes per lane and step, as k_match_flag handles its survivors.
 constexpr uint32_t JOIN_LANE_BYTES = 128;  // 16 words of the hash
-constexpr uint32_t JOIN_GRID = 2048;       // workgroups of k_join_build, k_join_flag and k_join_emit at most
+constexpr uint32_t JOIN_GRID = 2048;       // workgroups of k_join_build, k_join_flag and k_rows_emit at most
 // The join's words of the counters and of the report, beside PACKED_N_FAILED and PACKED_FIRST (the records'): the keys' two, and in
 // the counters the smallest and largest body of a valid key (first values ~0 and 0).  A probe or insert loop that ran through the
 // whole table -- a bug -- sets JOIN_FAULT_BIT in PACKED_N_FAILED (a count is below 2^31), which k_packed_scan reports as it finds it.
 enum JoinWord { JOIN_KEYS_FAILED = 4, JOIN_KEYS_FIRST = 5, JOIN_MIN = 6, JOIN_MAX = 7 };
 constexpr unsigned long long JOIN_FAULT_BIT = 1ull << 63;
-struct JoinSide {  // a packed store on the device: the records', or the keys'
-    const void *bodies;
-    uint64_t body_bytes;
-    const uint64_t *body_index, *text_index;
-    uint32_t n, pad;
-};
-// table: `slots` u64 (a power of two, at least 2 * keys.n); masks, counts, base: launch_match's; key_of: a u32 per record -- all
-// workspace.  flags: MATCH_F_NOT or 0.  The report ({n_match, failed, first << 8 | status} by the scan, the keys' two by k_join_flag
-// in front of it, then `epoch`) leaves with the scan.
-void launch_join(hipStream_t stream, const JoinSide &records, const JoinSide &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,
-                 uint64_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status, uint8_t *d_key_status, unsigned long long *masks, uint32_t *counts, uint64_t *base,
-                 uint32_t *key_of, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
+// table: `slots` u64 (a power of two, at least 2 * keys.n); key_of: a u32 per record -- workspace.  flags: MATCH_F_NOT or 0.  The
+// report ({n_match, failed, first << 8 | status} by the scan, the keys' two by k_join_flag in front of it, then `epoch`) leaves with
+// the scan.
+void launch_join(hipStream_t stream, const PackedStore &records, const PackedStore &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,
+                 uint64_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status, uint8_t *d_key_status, const TileWs &tiles, uint32_t *key_of, const PackedReport &report);
 // et_selftest_join_hash: d_hash[b] = the hash of record b as k_join_build and k_join_flag compute it (a failed record's entry is left).
-void launch_join_hash(hipStream_t stream, const JoinSide &records, uint64_t *d_hash);
+void launch_join_hash(hipStream_t stream, const PackedStore &records, uint64_t *d_hash);
 
-// The take call (et_take_packed_device): a selection of a packed store's records as a NEW packed store -- the bodies of rows[] copied
+// The take (et_take_packed_device): a selection of a packed store's records as a NEW packed store -- the bodies of rows[] copied
 // back to back as they are, both offset arrays made by a scan -- without a table: no bit is interpreted.
-//   k_take_plan   one row per lane (k_gather_plan's shape and rule, plus: a body above TAKE_BODY_MAX is unsupported): a TakeRow per
-//                 row into the workspace, its status byte
+//   k_take_plan   one row per lane (k_gather_plan's shape, plus: a body above TAKE_BODY_MAX is unsupported): a TakeRow per row into
+//                 the workspace, its status byte
 //   k_take_scan   ONE workgroup, tiles of TAKE_SCAN_TILE rows: the rows' body sizes -> out_body_index, their lengths ->
 //                 out_text_index; the report ({body bytes, failed, first << 8 | status, text bytes}, then `epoch`) leaves with it
 //   k_take_copy   (unless d_out is null: sizes only) destination-driven: the dense output is cut into tiles of TAKE_TILE_BYTES at
@@ -186,9 +195,8 @@ constexpr uint32_t TAKE_TILE_BYTES = 8192;   // k_take_copy: bytes of output per
 constexpr uint32_t TAKE_STAGE_ROWS = 1024;   // ... entries of out_body_index a workgroup keeps in LDS for a tile (more: read in place)
 constexpr uint32_t TAKE_GRID = 2048;         // workgroups of k_take_copy at most: what is resident at once on 256 CUs
 enum TakeWord { TAKE_TEXT_BYTES = 3 };       // the report's word beside PACKED_BYTES, PACKED_N_FAILED and PACKED_FIRST
-// plan: n_rows TakeRow of workspace (16-byte aligned).  stats, host_result, host_done, epoch: launch_packed_encode's.
-void launch_take(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
-                 const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan,
-                 unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch);
+// plan: n_rows TakeRow of workspace (16-byte aligned).
+void launch_take(hipStream_t stream, const PackedStore &store, const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index,
+                 uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, const PackedReport &report);
 
 }  // namespace et

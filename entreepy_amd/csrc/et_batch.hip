@@ -22,11 +22,11 @@
 //            k_packed_gather k_packed_decode's loop over the rows, each to its place in a dense output
 //   match    k_match_flag    one lane per record: judged, compared with the encoded needle on the compressed bytes; ballot masks, tile counts
 //            k_packed_scan   the tile counts -> each tile's first place among the rows, the report
-//            k_match_emit    the selected record numbers, ascending, by popcount ranks
+//            k_rows_emit     the selected record numbers, ascending, by popcount ranks
 //   join     k_join_build    one lane per key of a key set: judged, hashed on the compressed bytes, inserted into a table in the workspace
 //            k_join_flag     one lane per record: judged, hashed, probed, every hit confirmed by bytes; ballot masks, tile counts, key numbers
 //            k_packed_scan   as in the match
-//            k_join_emit     k_match_emit, with the lowest equal key's number beside the record's
+//            k_rows_emit     as in the match, with the lowest equal key's number beside the record's where asked for
 //   take     k_take_plan     one lane per row of a selection: its record judged, {body bytes, length, where the body begins} into the workspace
 //            k_take_scan     ONE workgroup: the two sizes -> out_body_index and out_text_index, the report
 //            k_take_copy     the selected bodies back to back as they are: one lane per aligned 16-byte word of the OUTPUT
@@ -541,9 +541,26 @@ __global__ __launch_bounds__(BB) void k_shared_decode(const uint8_t *__restrict_
 // --------------------------------------------------------------------------------
 // The packed calls.  Record j is bytes [index[j], index[j + 1]) of a dense buffer, and that pair of entries is all that is
 // believed about it: a pair that decreases or leaves the buffer fails its record (PACKED_ARG) before a byte is read.
-// What failed is counted per workgroup in thread 0's registers and added to PackedStats in device memory once, at the end.
+// What failed is counted in registers -- thread 0's in the kernels that give a record to a workgroup, every lane's in those that give
+// it to a lane (tally_lanes) -- and added to the counters in device memory once per workgroup, at the end.
 // --------------------------------------------------------------------------------
-struct PackedTally {  // thread 0's
+// THE rule for believing a record's two pairs of offsets, for every kernel that takes a record by its number (k_packed_decode, which
+// also asks where the text goes, has its own): PACKED_ARG for a number beyond the store or a pair that decreases or leaves the
+// bodies, PACKED_UNSUPPORTED for a text above BATCH_SMALL_MAX.  b0, nb and len mean something under PACKED_OK alone, and only such a
+// record's body is read.
+struct Judged {
+    uint32_t status;
+    uint64_t b0, nb, len;  // where in the bodies it begins, its bytes, its symbols
+};
+
+__device__ __forceinline__ Judged judge_record(const PackedStore &store, uint32_t r) {
+    if (r >= store.n) return Judged{PACKED_ARG, 0, 0, 0};
+    const uint64_t b0 = store.body_index[r], b1 = store.body_index[r + 1], t0 = store.text_index[r], t1 = store.text_index[r + 1];
+    const bool sound = b0 <= b1 && b1 <= store.body_bytes && t0 <= t1;
+    return Judged{!sound ? PACKED_ARG : t1 - t0 > BATCH_SMALL_MAX ? PACKED_UNSUPPORTED : PACKED_OK, b0, b1 - b0, t1 - t0};
+}
+
+struct PackedTally {
     unsigned long long failed = 0, first = ~0ull, n_short = 0;
     __device__ __forceinline__ void note(uint32_t j, uint32_t status) {
         if (!status) return;
@@ -560,11 +577,11 @@ struct PackedTally {  // thread 0's
     }
 };
 
-// The end of a kernel that judges an item per lane (k_gather_plan, k_match_flag): what each lane counted -- how many failed, the lowest
-// of them << 8 | its status -- reduced over the wavefront by shuffles and over the workgroup through 4 + 4 words of LDS: one pair of
+// The end of a kernel that judges an item per lane: what each lane noted -- how many failed, the lowest of them << 8 | its status (a
+// lane's items ascend) -- reduced over the wavefront by shuffles and over the workgroup through 4 + 4 words of LDS: one pair of
 // atomics per workgroup that saw a failure.
-__device__ __forceinline__ void tally_lanes(unsigned long long failed, unsigned long long first, unsigned long long *s_failed, unsigned long long *s_first,
-                                            unsigned long long *stats) {
+__device__ __forceinline__ void tally_lanes(const PackedTally &mine, unsigned long long *s_failed, unsigned long long *s_first, unsigned long long *stats) {
+    unsigned long long failed = mine.failed, first = mine.first;
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
         failed += __shfl_xor(failed, d, 64);
@@ -589,8 +606,8 @@ __device__ __forceinline__ void tally_lanes(unsigned long long failed, unsigned 
 // The report of a decode kernel (k_packed_decode, k_packed_gather), by thread 0 of every workgroup at its end: the workgroup's
 // counts are in `stats` before its tick of the counter; the last one to tick reads them all back, stores {out_bytes, failed,
 // first << 8 | status, short} and hands over.
-__device__ __forceinline__ void packed_report(const PackedTally &tally, uint64_t out_bytes, unsigned long long *stats, unsigned long long *host_result, uint32_t *counter,
-                                              unsigned long long *host_done, unsigned long long epoch) {
+__device__ __forceinline__ void packed_report(const PackedTally &tally, uint64_t out_bytes, const PackedReport &report, uint32_t *counter) {
+    unsigned long long *stats = report.stats, *host_result = report.host_result;
     tally.add_to(stats);  // (device-scope atomics, like the tick and the read-back below: no cache in between)
     __threadfence();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the counts have landed before the tick leaves
@@ -602,7 +619,7 @@ __device__ __forceinline__ void packed_report(const PackedTally &tally, uint64_t
         host_result[PACKED_N_FAILED] = atomicAdd(stats + PACKED_N_FAILED, 0ull);
         host_result[PACKED_FIRST] = atomicMin(stats + PACKED_FIRST, ~0ull);
         host_result[PACKED_N_SHORT] = atomicAdd(stats + PACKED_N_SHORT, 0ull);
-        hand_over(host_done, epoch);
+        hand_over(report.host_done, report.epoch);
     }
 }
 
@@ -721,23 +738,23 @@ __global__ __launch_bounds__(BB) void k_packed_pack(const uint8_t *__restrict__ 
 // d_bodies[body_index[j], body_index[j + 1]) to d_out + text_index[j].  d_written[j] (may be null) = symbols stored, d_status[j]
 // (may be null) = its et_status.  Nothing is decoded when text_index[n] > cap (the host returns ET_ERR_CAP from the report).
 // The last workgroup to finish reports {text_index[n], failed, first << 8 | status, short} and the epoch.  LDS as k_batch_decode.
-__global__ __launch_bounds__(BB) void k_packed_decode(const uint8_t *__restrict__ d_bodies, uint64_t body_bytes, const uint64_t *__restrict__ body_index,
-                                                      const uint64_t *__restrict__ text_index, uint32_t n, uint8_t *__restrict__ d_out, uint64_t cap,
-                                                      const uint2 *__restrict__ codes, uint32_t n_codes, uint32_t *__restrict__ d_written, uint8_t *__restrict__ d_status,
-                                                      unsigned long long *__restrict__ stats, unsigned long long *__restrict__ host_result, uint32_t *__restrict__ counter,
-                                                      unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+__global__ __launch_bounds__(BB) void k_packed_decode(PackedStore store, uint8_t *__restrict__ d_out, uint64_t cap, const uint2 *__restrict__ codes, uint32_t n_codes,
+                                                      uint32_t *__restrict__ d_written, uint8_t *__restrict__ d_status, PackedReport report, uint32_t *__restrict__ counter) {
     __shared__ BatchDecLds s;
     const uint32_t tid = threadIdx.x;
-    const uint64_t out_bytes = text_index[n];
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    const uint64_t out_bytes = store.text_index[store.n];
     PackedTally tally;
     if (out_bytes <= cap) {
         if (tid < n_codes) s.codes[tid] = codes[tid];
         __syncthreads();
         fill_lut(s, n_codes);
-        for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
-            const uint64_t b0 = body_index[j], b1 = body_index[j + 1], t0 = text_index[j], t1 = text_index[j + 1];
+        for (uint32_t j = blockIdx.x; j < store.n; j += gridDim.x) {
+            const uint64_t b0 = store.body_index[j], b1 = store.body_index[j + 1], t0 = store.text_index[j], t1 = store.text_index[j + 1];
             uint32_t status = PACKED_OK, done = 0;
-            if (!(b0 <= b1 && b1 <= body_bytes && t0 <= t1 && t1 <= cap)) {
+            // (not judge_record's rule: the text pair says where the symbols GO, so it must end within cap as well, and a record that
+            // decodes to nothing is judged empty before it is judged oversize)
+            if (!(b0 <= b1 && b1 <= store.body_bytes && t0 <= t1 && t1 <= cap)) {
                 status = PACKED_ARG;
             } else if (t1 == t0 || b1 == b0) {  // decodes to nothing, as in the shared-table call; an empty body is a short one
                 if (tid == 0 && t1 > t0) ++tally.n_short;
@@ -745,10 +762,7 @@ __global__ __launch_bounds__(BB) void k_packed_decode(const uint8_t *__restrict_
                 status = PACKED_UNSUPPORTED;
             } else {
                 const uint32_t count = static_cast<uint32_t>(t1 - t0);
-                // (count codewords of at most 32 bits end within 4 count bytes: decode_stream's bit positions stay small)
-                const uint64_t most = static_cast<uint64_t>(count) * 4 + 8;
-                const uint32_t len = static_cast<uint32_t>(b1 - b0 < most ? b1 - b0 : most);
-                done = decode_stream(s, n_codes, d_bodies, d_out, b0, t0, len, count, count);
+                done = decode_stream(s, n_codes, d_bodies, d_out, b0, t0, static_cast<uint32_t>(clip_body(b1 - b0, count)), count, count);
                 if (tid == 0 && done < count) ++tally.n_short;
             }
             if (tid == 0) {
@@ -758,48 +772,26 @@ __global__ __launch_bounds__(BB) void k_packed_decode(const uint8_t *__restrict_
             }
         }
     }
-    if (tid == 0) packed_report(tally, out_bytes, stats, host_result, counter, host_done, epoch);
+    if (tid == 0) packed_report(tally, out_bytes, report, counter);
 }
 
 // --------------------------------------------------------------------------------
 // The gather call: row k of the result is record rows[k] of a packed store, in any order, with repeats; the rows lie back to
-// back in d_out, laid out here.  Three launches in stream order, the host waiting for the last alone:
-//   k_gather_plan    per row: its record's two pairs of offsets judged, its room (the record's length; 0 when it failed) into the
-//                    workspace, its status byte
-//   k_packed_scan    rooms -> out_index (with the report when the call is sizes only: nothing follows)
-//   k_packed_gather  k_packed_decode's loop over the rows, the job made from rows[k], the record's body pair and out_index[k]
+// back in d_out, laid out here.  Three launches in stream order (et_batch.h), the host waiting for the last alone.
 // --------------------------------------------------------------------------------
-// k_gather_plan: one lane per row, a grid-stride loop; rows[] is loaded coalesced, the four offsets are gathered.  What failed is
-// counted per lane, reduced over the wavefront by shuffles and over the workgroup through LDS: one pair of atomics per workgroup
-// that saw a failure.  No LDS beyond those 4 + 4 words.
-__global__ __launch_bounds__(BB) void k_gather_plan(const uint32_t *__restrict__ rows, uint32_t n_rows, const uint64_t *__restrict__ body_index,
-                                                    const uint64_t *__restrict__ text_index, uint32_t n_records, uint64_t body_bytes, uint32_t *__restrict__ sizes,
+// k_gather_plan: one lane per row, a grid-stride loop; rows[] is loaded coalesced, the four offsets are gathered.  The record judged,
+// its room (its length; 0 when it failed) into the workspace, its status byte.  No LDS beyond tally_lanes' 4 + 4 words.
+__global__ __launch_bounds__(BB) void k_gather_plan(PackedStore store, const uint32_t *__restrict__ rows, uint32_t n_rows, uint32_t *__restrict__ sizes,
                                                     uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
     __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    unsigned long long failed = 0, first = ~0ull;
+    PackedTally tally;
     for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * BB + threadIdx.x; k < n_rows; k += static_cast<uint64_t>(gridDim.x) * BB) {
-        const uint32_t r = rows[k];
-        uint32_t status = PACKED_ARG, room = 0;
-        if (r < n_records) {
-            const uint64_t b0 = body_index[r], b1 = body_index[r + 1], t0 = text_index[r], t1 = text_index[r + 1];
-            if (b0 <= b1 && b1 <= body_bytes && t0 <= t1) {
-                if (t1 - t0 > BATCH_SMALL_MAX) {
-                    status = PACKED_UNSUPPORTED;
-                } else {
-                    status = PACKED_OK;
-                    room = static_cast<uint32_t>(t1 - t0);
-                }
-            }
-        }
-        sizes[k] = room;
-        if (d_status) d_status[k] = static_cast<uint8_t>(status);
-        if (status) {
-            ++failed;
-            const unsigned long long key = k << 8 | status;  // (k ascends in a lane: its first is its lowest)
-            if (key < first) first = key;
-        }
+        const Judged rec = judge_record(store, rows[k]);
+        sizes[k] = rec.status ? 0u : static_cast<uint32_t>(rec.len);
+        if (d_status) d_status[k] = static_cast<uint8_t>(rec.status);
+        tally.note(static_cast<uint32_t>(k), rec.status);
     }
-    tally_lanes(failed, first, s_failed, s_first, stats);
+    tally_lanes(tally, s_failed, s_first, stats);
 }
 
 // k_packed_gather: k_packed_decode with row k's job made from rows[k]: out_index[k + 1] - out_index[k] symbols (the room
@@ -807,13 +799,12 @@ __global__ __launch_bounds__(BB) void k_gather_plan(const uint32_t *__restrict__
 // (failed, or of length zero) is passed over without a look at its record; a row with room was judged by k_gather_plan, so its
 // pairs are believed.  d_written[k] (may be null) = symbols stored.  Nothing is decoded when out_index[n_rows] > cap.  The failure
 // counters in `stats` are k_gather_plan's; this kernel adds the short rows, and its last workgroup reports.  LDS as k_batch_decode.
-__global__ __launch_bounds__(BB) void k_packed_gather(const uint8_t *__restrict__ d_bodies, const uint64_t *__restrict__ body_index, const uint32_t *__restrict__ rows,
-                                                      uint32_t n_rows, uint8_t *__restrict__ d_out, uint64_t cap, const uint64_t *__restrict__ out_index,
-                                                      const uint2 *__restrict__ codes, uint32_t n_codes, uint32_t *__restrict__ d_written,
-                                                      unsigned long long *__restrict__ stats, unsigned long long *__restrict__ host_result, uint32_t *__restrict__ counter,
-                                                      unsigned long long *__restrict__ host_done, unsigned long long epoch) {
+__global__ __launch_bounds__(BB) void k_packed_gather(PackedStore store, const uint32_t *__restrict__ rows, uint32_t n_rows, uint8_t *__restrict__ d_out, uint64_t cap,
+                                                      const uint64_t *__restrict__ out_index, const uint2 *__restrict__ codes, uint32_t n_codes,
+                                                      uint32_t *__restrict__ d_written, PackedReport report, uint32_t *__restrict__ counter) {
     __shared__ BatchDecLds s;
     const uint32_t tid = threadIdx.x;
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
     const uint64_t out_bytes = out_index[n_rows];
     PackedTally tally;
     if (out_bytes <= cap) {
@@ -825,31 +816,36 @@ __global__ __launch_bounds__(BB) void k_packed_gather(const uint8_t *__restrict_
             uint32_t done = 0;
             if (o1 > o0) {  // (the same for every lane)
                 const uint32_t r = rows[k], count = static_cast<uint32_t>(o1 - o0);
-                const uint64_t b0 = body_index[r], b1 = body_index[r + 1];
-                if (b1 > b0) {
-                    // (count codewords of at most 32 bits end within 4 count bytes: decode_stream's bit positions stay small)
-                    const uint64_t most = static_cast<uint64_t>(count) * 4 + 8;
-                    const uint32_t len = static_cast<uint32_t>(b1 - b0 < most ? b1 - b0 : most);
-                    done = decode_stream(s, n_codes, d_bodies, d_out, b0, o0, len, count, count);
-                }
+                const uint64_t b0 = store.body_index[r], b1 = store.body_index[r + 1];
+                if (b1 > b0) done = decode_stream(s, n_codes, d_bodies, d_out, b0, o0, static_cast<uint32_t>(clip_body(b1 - b0, count)), count, count);
                 if (tid == 0 && done < count) ++tally.n_short;  // (an empty body under a length above zero is a short one)
             }
             if (tid == 0 && d_written) d_written[k] = done;
         }
     }
-    if (tid == 0) packed_report(tally, out_bytes, stats, host_result, counter, host_done, epoch);
+    if (tid == 0) packed_report(tally, out_bytes, report, counter);
 }
 
 // --------------------------------------------------------------------------------
 // The match call: which records of a packed store begin with (or equal) a needle, decided on the compressed bytes.  Under one
 // complete prefix-free table a record's text begins with the needle exactly when its body begins with the needle's codewords, its
 // length is at least the needle's and its body holds those bits; equality asks for the same length.  The host encodes the needle;
-// no table comes to the device.  Three launches in stream order, the host waiting for the second alone:
-//   k_match_flag   per record: judged from its own two pairs (k_gather_plan's rule), its status byte, the comparison; a ballot mask
-//                  per 64 records and a count per tile of MATCH_TILE records into the workspace
-//   k_packed_scan  the tile counts -> each tile's first place in d_rows, and the report: n_match, the failure counters
-//   k_match_emit   per tile: rows[base[tile] + rank] = record, the rank a popcount prefix over the tile's four masks
+// no table comes to the device.  Three launches in stream order (et_batch.h), the host waiting for the second alone.
 // --------------------------------------------------------------------------------
+// The end of a tile of a flag kernel (k_match_flag, k_join_flag): the ballot of the lanes whose record is selected is the wavefront's
+// mask, the four popcounts meet in s_count[set] -- two sets: a tile's counts are read while the next tile's are stored -- and thread 0
+// stores their sum as the tile's count.  One barrier.
+__device__ __forceinline__ void end_tile(bool selected, uint32_t tile, uint32_t set, const TileWs &tiles, uint32_t (*s_count)[BB / 64]) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long mask = __ballot(selected);
+    if (lane == 0) {
+        tiles.masks[static_cast<uint64_t>(tile) * (MATCH_TILE / 64) + wave] = mask;
+        s_count[set][wave] = __popcll(mask);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) tiles.counts[tile] = s_count[set][0] + s_count[set][1] + s_count[set][2] + s_count[set][3];
+}
+
 // k_match_flag: a workgroup takes tiles of 256 consecutive records, one per lane, so both offset arrays are read coalesced.  A lane
 // whose record can match (valid, the length fits, the body holds the pattern's bytes) compares the pattern's first 8 bytes alone:
 // the aligned 8-byte words that hold them -- one, or two; each holds a byte of the body -- shifted into place, against job.head
@@ -857,39 +853,32 @@ __global__ __launch_bounds__(BB) void k_packed_gather(const uint8_t *__restrict_
 // lanes compare 4 bytes each per step (aligned words that hold a byte of THAT body, shifted), the wavefront leaving at the first
 // step with a mismatch: keys share long prefixes, and one lane walking 16 KiB alone would hold its wavefront.  The pattern's last
 // byte counts with its top pat_bits % 8 bits only: the body's next codeword begins behind them.
-// A failed record is never read and never selected; failures are tallied as in k_gather_plan.  LDS: 8 + 8 + 8 words.
-__global__ __launch_bounds__(BB) void k_match_flag(const uint8_t *__restrict__ d_bodies, uint64_t body_bytes, const uint64_t *__restrict__ body_index,
-                                                   const uint64_t *__restrict__ text_index, uint32_t n, const uint32_t *__restrict__ pattern, MatchJob job,
-                                                   unsigned long long *__restrict__ masks, uint32_t *__restrict__ counts, uint8_t *__restrict__ d_status,
+// A failed record is never read and never selected.  LDS: 8 + 8 + 8 words.
+__global__ __launch_bounds__(BB) void k_match_flag(PackedStore store, const uint32_t *__restrict__ pattern, MatchJob job, TileWs tiles, uint8_t *__restrict__ d_status,
                                                    unsigned long long *__restrict__ stats) {
     __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    __shared__ uint32_t s_count[2][BB / 64];  // (two sets: a tile's counts are read while the next tile's are stored)
+    __shared__ uint32_t s_count[2][BB / 64];
     constexpr uint32_t HEAD_BYTES = MATCH_HEAD_BITS / 8;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
     const uint32_t pat_bytes = (job.pat_bits + 7) >> 3, head_bytes = pat_bytes < HEAD_BYTES ? pat_bytes : HEAD_BYTES;
     const uint32_t last_bits = job.pat_bits & 7;
-    const uint32_t n_tiles = (n + MATCH_TILE - 1) / MATCH_TILE;
+    const uint32_t n_tiles = (store.n + MATCH_TILE - 1) / MATCH_TILE;
     const bool equal = job.flags & MATCH_F_EQUAL, negate = job.flags & MATCH_F_NOT, never = job.flags & MATCH_F_NEVER;
-    unsigned long long failed = 0, first = ~0ull;
+    PackedTally tally;
     uint32_t set = 0;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, set ^= 1) {
         const uint32_t b = tile * MATCH_TILE + tid;  // (n <= 0x7fffffff: no wrap)
         bool valid = false, hit = false;
         uint64_t b0 = 0;
-        if (b < n) {
-            b0 = body_index[b];
-            const uint64_t b1 = body_index[b + 1], t0 = text_index[b], t1 = text_index[b + 1];
-            uint32_t status = PACKED_ARG;
-            if (b0 <= b1 && b1 <= body_bytes && t0 <= t1) status = t1 - t0 > BATCH_SMALL_MAX ? PACKED_UNSUPPORTED : PACKED_OK;
-            if (d_status) d_status[b] = static_cast<uint8_t>(status);
-            if (status) {
-                ++failed;
-                const unsigned long long key = static_cast<unsigned long long>(b) << 8 | status;  // (b ascends in a lane: its first is its lowest)
-                if (key < first) first = key;
-            } else {
+        if (b < store.n) {
+            const Judged rec = judge_record(store, b);
+            if (d_status) d_status[b] = static_cast<uint8_t>(rec.status);
+            tally.note(b, rec.status);
+            if (!rec.status) {
                 valid = true;
-                const uint64_t len = t1 - t0;
-                hit = !never && (equal ? len == job.needle_len : len >= job.needle_len) && b1 - b0 >= pat_bytes;
+                b0 = rec.b0;
+                hit = !never && (equal ? rec.len == job.needle_len : rec.len >= job.needle_len) && rec.nb >= pat_bytes;
                 if (hit && head_bytes) {
                     const uintptr_t a = reinterpret_cast<uintptr_t>(d_bodies) + b0;
                     const uint64_t *q = reinterpret_cast<const uint64_t *>(a & ~static_cast<uintptr_t>(7));
@@ -929,22 +918,18 @@ __global__ __launch_bounds__(BB) void k_match_flag(const uint8_t *__restrict__ d
                 if (static_cast<int>(lane) == src) hit = same;
             }
         }
-        const unsigned long long mask = __ballot(valid && hit != negate);
-        if (lane == 0) {
-            masks[static_cast<uint64_t>(tile) * (MATCH_TILE / 64) + wave] = mask;
-            s_count[set][wave] = __popcll(mask);
-        }
-        __syncthreads();
-        if (tid == 0) counts[tile] = s_count[set][0] + s_count[set][1] + s_count[set][2] + s_count[set][3];
+        end_tile(valid && hit != negate, tile, set, tiles, s_count);
     }
-    tally_lanes(failed, first, s_failed, s_first, stats);
+    tally_lanes(tally, s_failed, s_first, stats);
 }
 
-// k_match_emit: a tile per trip, a record per lane: the tile's four masks (the same 32 bytes for every lane), the record's rank
-// among the tile's selected ones by popcounts, its number to rows[base[tile] + rank] -- ascending, as tiles and ranks are.  Every
-// workgroup returns at once when the rows do not fit: ET_ERR_CAP writes nothing.  No LDS.
-__global__ __launch_bounds__(BB) void k_match_emit(const unsigned long long *__restrict__ masks, const uint64_t *__restrict__ base, uint32_t n_tiles,
-                                                   uint32_t *__restrict__ rows, uint64_t cap_rows) {
+// k_rows_emit (the match's and the join's last launch): a tile per trip, a record per lane: the tile's four masks (the same 32 bytes
+// for every lane), the record's rank among the tile's selected ones by popcounts, its number to rows[base[tile] + rank] -- ascending,
+// as tiles and ranks are -- and, KEYS, its key's (key_of[record]) to key_rows at the same place.  Every workgroup returns at once when
+// the rows do not fit: ET_ERR_CAP writes nothing.  No LDS.
+template <bool KEYS>
+__global__ __launch_bounds__(BB) void k_rows_emit(const unsigned long long *__restrict__ masks, const uint64_t *__restrict__ base, uint32_t n_tiles,
+                                                  uint32_t *__restrict__ rows, uint64_t cap_rows, const uint32_t *__restrict__ key_of, uint32_t *__restrict__ key_rows) {
     if (base[n_tiles] > cap_rows) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -953,7 +938,9 @@ __global__ __launch_bounds__(BB) void k_match_emit(const unsigned long long *__r
         if (!((mine >> lane) & 1)) continue;
         uint32_t rank = __popcll(mine & ((1ull << lane) - 1ull));
         for (uint32_t w = 0; w < wave; ++w) rank += __popcll(m[w]);
-        rows[base[tile] + rank] = tile * MATCH_TILE + tid;
+        const uint32_t record = tile * MATCH_TILE + tid;
+        rows[base[tile] + rank] = record;
+        if (KEYS) key_rows[base[tile] + rank] = key_of[record];
     }
 }
 
@@ -963,12 +950,7 @@ __global__ __launch_bounds__(BB) void k_match_emit(const unsigned long long *__r
 // same length (symbols), the same body byte count and the same body bytes -- for bodies as the encoders write them; a body of no
 // bytes under a length above zero (a record kept raw elsewhere) equals nothing, on either side.  The keys go into a hash table in the
 // workspace (et_join.h: the hash, a slot = tag << 32 | key number, ET_JOIN_EMPTY), the records probe it, and every hit is confirmed by
-// length, byte count and bytes.  In stream order, the host waiting for the scan alone:
-//   (clear)        hipMemsetAsync: every slot ET_JOIN_EMPTY
-//   k_join_build   per key: judged (k_gather_plan's rule), its status byte, hashed, inserted
-//   k_join_flag    per record: judged, its status byte, hashed, probed, confirmed; masks, tile counts and key numbers into the workspace
-//   k_packed_scan  the tile counts -> each tile's first place in d_rows, and the report
-//   k_join_emit    k_match_emit, with the key number beside the record number where asked for
+// length, byte count and bytes.  The launches (et_batch.h) run in stream order, the host waiting for the scan alone.
 // No workgroup waits for another: an insert is a compare-and-swap per slot visited, and every probe and insert loop ends after
 // `slots` trips at the latest -- with a table at most half full it ends at an empty slot long before; a loop that runs out sets the
 // fault bit (JOIN_FAULT_BIT of the records' failure count, which the scan reports as it is), and the host returns ET_ERR_HIP.
@@ -1043,7 +1025,7 @@ struct JoinItem {
     uint64_t nb, len;
 };
 
-__device__ __forceinline__ JoinItem key_item(const JoinSide &keys, uint32_t k) {
+__device__ __forceinline__ JoinItem key_item(const PackedStore &keys, uint32_t k) {
     const uint64_t b0 = keys.body_index[k], b1 = keys.body_index[k + 1];
     return JoinItem{reinterpret_cast<uintptr_t>(keys.bodies) + b0, b1 - b0, keys.text_index[k + 1] - keys.text_index[k]};
 }
@@ -1054,7 +1036,7 @@ __device__ __forceinline__ JoinItem key_item(const JoinSide &keys, uint32_t k) {
 // common probe sequence that no other text holds, whatever the order.  false: `slots` trips without an end.
 // WAVE: the whole wavefront inserts one key (the arguments are the same in every lane); lane 0 issues the atomics.
 template <bool WAVE>
-__device__ __forceinline__ bool join_insert(const JoinSide &keys, unsigned long long *table, uint64_t slot_mask, uint32_t k, uint64_t h, const JoinItem &me, uint32_t lane) {
+__device__ __forceinline__ bool join_insert(const PackedStore &keys, unsigned long long *table, uint64_t slot_mask, uint32_t k, uint64_t h, const JoinItem &me, uint32_t lane) {
     const unsigned long long word = (h & 0xffffffff00000000ull) | k;
     uint64_t pos = h & slot_mask;
     for (uint64_t trip = 0; trip <= slot_mask; ++trip, pos = (pos + 1) & slot_mask) {
@@ -1075,7 +1057,7 @@ __device__ __forceinline__ bool join_insert(const JoinSide &keys, unsigned long 
 // The key that equals `me`, or JOIN_NONE: the probe sequence up to its first empty slot; a slot with the hash's tag is confirmed by
 // length, byte count and bytes, and passed when they differ.  The table is final (k_join_build is over): plain loads.
 template <bool WAVE>
-__device__ __forceinline__ uint32_t join_probe(const JoinSide &keys, const unsigned long long *table, uint64_t slot_mask, uint64_t h, const JoinItem &me, uint32_t lane, bool *fault) {
+__device__ __forceinline__ uint32_t join_probe(const PackedStore &keys, const unsigned long long *table, uint64_t slot_mask, uint64_t h, const JoinItem &me, uint32_t lane, bool *fault) {
     uint64_t pos = h & slot_mask;
     for (uint64_t trip = 0; trip <= slot_mask; ++trip, pos = (pos + 1) & slot_mask) {
         const unsigned long long slot = table[pos];
@@ -1093,28 +1075,24 @@ __device__ __forceinline__ uint32_t join_probe(const JoinSide &keys, const unsig
 // tallied into the keys' two counters; a valid key -- unless it is a body of no bytes under a length above zero, which equals
 // nothing -- is hashed and inserted, alone up to JOIN_LANE_BYTES of body, by its wavefront above.  The smallest and largest body of
 // the inserted keys go to JOIN_MIN and JOIN_MAX: one pair of atomics per workgroup.  LDS: 8 + 8 + 8 + 8 words.
-__global__ __launch_bounds__(BB) void k_join_build(JoinSide keys, unsigned long long *__restrict__ table, uint64_t slot_mask, uint8_t *__restrict__ d_key_status,
+__global__ __launch_bounds__(BB) void k_join_build(PackedStore keys, unsigned long long *__restrict__ table, uint64_t slot_mask, uint8_t *__restrict__ d_key_status,
                                                    unsigned long long *__restrict__ stats) {
     __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64], s_min[BB / 64], s_max[BB / 64];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t n_tiles = (keys.n + MATCH_TILE - 1) / MATCH_TILE;
-    unsigned long long failed = 0, first = ~0ull, lo = ~0ull, hi = 0;
+    unsigned long long lo = ~0ull, hi = 0;
+    PackedTally tally;
     bool fault = false;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint32_t k = tile * MATCH_TILE + tid;  // (n <= 2^24: no wrap)
         bool enter = false;
         JoinItem me{0, 0, 0};
         if (k < keys.n) {
-            const uint64_t b0 = keys.body_index[k], b1 = keys.body_index[k + 1], t0 = keys.text_index[k], t1 = keys.text_index[k + 1];
-            uint32_t status = PACKED_ARG;
-            if (b0 <= b1 && b1 <= keys.body_bytes && t0 <= t1) status = t1 - t0 > BATCH_SMALL_MAX ? PACKED_UNSUPPORTED : PACKED_OK;
-            if (d_key_status) d_key_status[k] = static_cast<uint8_t>(status);
-            if (status) {
-                ++failed;
-                const unsigned long long key = static_cast<unsigned long long>(k) << 8 | status;  // (k ascends in a lane: its first is its lowest)
-                if (key < first) first = key;
-            } else {
-                me = JoinItem{reinterpret_cast<uintptr_t>(keys.bodies) + b0, b1 - b0, t1 - t0};
+            const Judged rec = judge_record(keys, k);
+            if (d_key_status) d_key_status[k] = static_cast<uint8_t>(rec.status);
+            tally.note(k, rec.status);
+            if (!rec.status) {
+                me = JoinItem{reinterpret_cast<uintptr_t>(keys.bodies) + rec.b0, rec.nb, rec.len};
                 enter = me.nb > 0 || me.len == 0;
                 if (enter) {
                     if (me.nb < lo) lo = me.nb;
@@ -1143,7 +1121,7 @@ __global__ __launch_bounds__(BB) void k_join_build(JoinSide keys, unsigned long 
         s_min[wave] = lo;
         s_max[wave] = hi;
     }
-    tally_lanes(failed, first, s_failed, s_first, stats + (JOIN_KEYS_FAILED - PACKED_N_FAILED));  // (the keys' pair of counters lies like the records')
+    tally_lanes(tally, s_failed, s_first, stats + (JOIN_KEYS_FAILED - PACKED_N_FAILED));  // (the keys' pair of counters lies like the records')
     if (tid == 0) {
         for (int w = 0; w < BB / 64; ++w) {
             if (s_min[w] < lo) lo = s_min[w];
@@ -1162,12 +1140,12 @@ __global__ __launch_bounds__(BB) void k_join_build(JoinSide keys, unsigned long 
 // and probed: alone up to JOIN_LANE_BYTES of body, by their wavefront above.  key_of[b] = the key record b equals, or JOIN_NONE.
 // Its first workgroup puts the keys' two counters -- final as well -- into the report, in front of the scan that hands it over; a
 // tick per workgroup to find the last one costs more than the whole kernel (a device-scope fence each).  LDS: 8 + 8 + 8 words.
-__global__ __launch_bounds__(BB) void k_join_flag(JoinSide recs, JoinSide keys, const unsigned long long *__restrict__ table, uint64_t slot_mask, uint32_t flags,
-                                                  unsigned long long *__restrict__ masks, uint32_t *__restrict__ counts, uint32_t *__restrict__ key_of,
-                                                  uint8_t *__restrict__ d_status, unsigned long long *stats, unsigned long long *__restrict__ host_result) {
+__global__ __launch_bounds__(BB) void k_join_flag(PackedStore recs, PackedStore keys, const unsigned long long *__restrict__ table, uint64_t slot_mask, uint32_t flags,
+                                                  TileWs tiles, uint32_t *__restrict__ key_of, uint8_t *__restrict__ d_status, unsigned long long *stats,
+                                                  unsigned long long *__restrict__ host_result) {
     __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    __shared__ uint32_t s_count[2][BB / 64];  // (two sets: a tile's counts are read while the next tile's are stored)
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ uint32_t s_count[2][BB / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t n_tiles = (recs.n + MATCH_TILE - 1) / MATCH_TILE;
     const bool negate = flags & MATCH_F_NOT;
     const unsigned long long lo = stats[JOIN_MIN], hi = stats[JOIN_MAX];
@@ -1176,7 +1154,7 @@ __global__ __launch_bounds__(BB) void k_join_flag(JoinSide recs, JoinSide keys, 
         host_result[JOIN_KEYS_FIRST] = stats[JOIN_KEYS_FIRST];
         pinned_stores_visible();
     }
-    unsigned long long failed = 0, first = ~0ull;
+    PackedTally tally;
     bool fault = false;
     uint32_t set = 0;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, set ^= 1) {
@@ -1184,17 +1162,12 @@ __global__ __launch_bounds__(BB) void k_join_flag(JoinSide recs, JoinSide keys, 
         bool valid = false, probe = false;
         JoinItem me{0, 0, 0};
         if (b < recs.n) {
-            const uint64_t b0 = recs.body_index[b], b1 = recs.body_index[b + 1], t0 = recs.text_index[b], t1 = recs.text_index[b + 1];
-            uint32_t status = PACKED_ARG;
-            if (b0 <= b1 && b1 <= recs.body_bytes && t0 <= t1) status = t1 - t0 > BATCH_SMALL_MAX ? PACKED_UNSUPPORTED : PACKED_OK;
-            if (d_status) d_status[b] = static_cast<uint8_t>(status);
-            if (status) {
-                ++failed;
-                const unsigned long long key = static_cast<unsigned long long>(b) << 8 | status;  // (b ascends in a lane: its first is its lowest)
-                if (key < first) first = key;
-            } else {
+            const Judged rec = judge_record(recs, b);
+            if (d_status) d_status[b] = static_cast<uint8_t>(rec.status);
+            tally.note(b, rec.status);
+            if (!rec.status) {
                 valid = true;
-                me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + b0, b1 - b0, t1 - t0};
+                me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + rec.b0, rec.nb, rec.len};
                 probe = (me.nb > 0 || me.len == 0) && me.nb >= lo && me.nb <= hi;
             }
         }
@@ -1210,37 +1183,14 @@ __global__ __launch_bounds__(BB) void k_join_flag(JoinSide recs, JoinSide keys, 
             if (static_cast<int>(lane) == src) key = found;
         }
         if (b < recs.n) key_of[b] = key;
-        const unsigned long long mask = __ballot(valid && (key != JOIN_NONE) != negate);
-        if (lane == 0) {
-            masks[static_cast<uint64_t>(tile) * (MATCH_TILE / 64) + wave] = mask;
-            s_count[set][wave] = __popcll(mask);
-        }
-        __syncthreads();
-        if (tid == 0) counts[tile] = s_count[set][0] + s_count[set][1] + s_count[set][2] + s_count[set][3];
+        end_tile(valid && (key != JOIN_NONE) != negate, tile, set, tiles, s_count);
     }
     if (fault) atomicOr(stats + PACKED_N_FAILED, JOIN_FAULT_BIT);
-    tally_lanes(failed, first, s_failed, s_first, stats);
-}
-
-// k_join_emit: k_match_emit; beside the record's number its key's (key_of[record]) where key_rows is given.  No LDS.
-__global__ __launch_bounds__(BB) void k_join_emit(const unsigned long long *__restrict__ masks, const uint64_t *__restrict__ base, uint32_t n_tiles,
-                                                  const uint32_t *__restrict__ key_of, uint32_t *__restrict__ rows, uint32_t *__restrict__ key_rows, uint64_t cap_rows) {
-    if (base[n_tiles] > cap_rows) return;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const unsigned long long *m = masks + static_cast<uint64_t>(tile) * (MATCH_TILE / 64);
-        const unsigned long long mine = m[wave];
-        if (!((mine >> lane) & 1)) continue;
-        uint32_t rank = __popcll(mine & ((1ull << lane) - 1ull));
-        for (uint32_t w = 0; w < wave; ++w) rank += __popcll(m[w]);
-        const uint32_t record = tile * MATCH_TILE + tid;
-        rows[base[tile] + rank] = record;
-        if (key_rows) key_rows[base[tile] + rank] = key_of[record];
-    }
+    tally_lanes(tally, s_failed, s_first, stats);
 }
 
 // k_join_hash: et_selftest_join_hash -- the hash of every valid record as k_join_build and k_join_flag compute it (join_hash_lanes).
-__global__ __launch_bounds__(BB) void k_join_hash(JoinSide recs, uint64_t *__restrict__ d_hash) {
+__global__ __launch_bounds__(BB) void k_join_hash(PackedStore recs, uint64_t *__restrict__ d_hash) {
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t n_tiles = (recs.n + MATCH_TILE - 1) / MATCH_TILE;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -1248,9 +1198,9 @@ __global__ __launch_bounds__(BB) void k_join_hash(JoinSide recs, uint64_t *__res
         bool valid = false;
         JoinItem me{0, 0, 0};
         if (b < recs.n) {
-            const uint64_t b0 = recs.body_index[b], b1 = recs.body_index[b + 1], t0 = recs.text_index[b], t1 = recs.text_index[b + 1];
-            valid = b0 <= b1 && b1 <= recs.body_bytes && t0 <= t1 && t1 - t0 <= BATCH_SMALL_MAX;
-            if (valid) me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + b0, b1 - b0, t1 - t0};
+            const Judged rec = judge_record(recs, b);
+            valid = !rec.status;
+            if (valid) me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + rec.b0, rec.nb, rec.len};
         }
         const uint64_t h = join_hash_lanes(valid, me.body, me.nb, me.len, lane);
         if (valid) d_hash[b] = h;
@@ -1260,44 +1210,26 @@ __global__ __launch_bounds__(BB) void k_join_hash(JoinSide recs, uint64_t *__res
 // --------------------------------------------------------------------------------
 // The take call: rows[] of a packed store as a new packed store.  Under one table a body is a self-contained byte string, so row k of
 // the result is the bytes d_bodies[body_index[r], body_index[r + 1]) of its record r = rows[k] as they are, and its length is r's; no
-// bit is interpreted and no table comes to the device.  Three launches in stream order, the host waiting for the second alone:
-//   k_take_plan   per row: its record judged (k_gather_plan's rule; a body above TAKE_BODY_MAX is unsupported too), a TakeRow -- body
-//                 bytes, length, where the body begins -- into the workspace, its status byte
-//   k_take_scan   body bytes -> out_body_index, lengths -> out_text_index, both totals and the failure counters to the host
-//   k_take_copy   the ragged byte copy, driven by the DESTINATION: every aligned 16-byte word of the output is assembled and stored
-//                 by one lane, whatever the rows' sizes -- a 20-byte body does not scatter byte stores, a 40 KiB body is spread over
-//                 ten wavefronts
+// bit is interpreted and no table comes to the device.  Three launches in stream order (et_batch.h), the host waiting for the second
+// alone; the copy is driven by the DESTINATION: every aligned 16-byte word of the output is assembled and stored by one lane, whatever
+// the rows' sizes -- a 20-byte body does not scatter byte stores, a 40 KiB body is spread over ten wavefronts.
 // --------------------------------------------------------------------------------
-// k_take_plan: k_gather_plan with a record per row in place of a size word.  A failed row is an empty record: {0, 0, 0}.
-__global__ __launch_bounds__(BB) void k_take_plan(const uint32_t *__restrict__ rows, uint32_t n_rows, const uint64_t *__restrict__ body_index,
-                                                  const uint64_t *__restrict__ text_index, uint32_t n_records, uint64_t body_bytes, TakeRow *__restrict__ plan,
+// k_take_plan: k_gather_plan with a TakeRow per row in place of a size word, and one more test behind the record's judgement: a body
+// above TAKE_BODY_MAX is unsupported too.  A failed row is an empty record: {0, 0, 0}.
+__global__ __launch_bounds__(BB) void k_take_plan(PackedStore store, const uint32_t *__restrict__ rows, uint32_t n_rows, TakeRow *__restrict__ plan,
                                                   uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
     __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    unsigned long long failed = 0, first = ~0ull;
+    PackedTally tally;
     for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * BB + threadIdx.x; k < n_rows; k += static_cast<uint64_t>(gridDim.x) * BB) {
-        const uint32_t r = rows[k];
-        uint32_t status = PACKED_ARG;
+        const Judged rec = judge_record(store, rows[k]);
+        const uint32_t status = !rec.status && rec.nb > TAKE_BODY_MAX ? PACKED_UNSUPPORTED : rec.status;
         uint4 row = make_uint4(0u, 0u, 0u, 0u);
-        if (r < n_records) {
-            const uint64_t b0 = body_index[r], b1 = body_index[r + 1], t0 = text_index[r], t1 = text_index[r + 1];
-            if (b0 <= b1 && b1 <= body_bytes && t0 <= t1) {
-                if (t1 - t0 > BATCH_SMALL_MAX || b1 - b0 > TAKE_BODY_MAX) {
-                    status = PACKED_UNSUPPORTED;
-                } else {
-                    status = PACKED_OK;
-                    row = make_uint4(static_cast<uint32_t>(b1 - b0), static_cast<uint32_t>(t1 - t0), static_cast<uint32_t>(b0), static_cast<uint32_t>(b0 >> 32));
-                }
-            }
-        }
+        if (!status) row = make_uint4(static_cast<uint32_t>(rec.nb), static_cast<uint32_t>(rec.len), static_cast<uint32_t>(rec.b0), static_cast<uint32_t>(rec.b0 >> 32));
         reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
         if (d_status) d_status[k] = static_cast<uint8_t>(status);
-        if (status) {
-            ++failed;
-            const unsigned long long key = k << 8 | status;  // (k ascends in a lane: its first is its lowest)
-            if (key < first) first = key;
-        }
+        tally.note(static_cast<uint32_t>(k), status);
     }
-    tally_lanes(failed, first, s_failed, s_first, stats);
+    tally_lanes(tally, s_failed, s_first, stats);
 }
 
 // k_take_scan: k_packed_scan over pairs -- ONE workgroup; per trip a tile of TAKE_SCAN_TILE rows; two exclusive scans in u64, the tiles
@@ -1502,90 +1434,81 @@ __global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_
 // --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
 
-void launch_take(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
-                 const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan,
-                 unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
-    const uint32_t plan_grid = (n_rows + BB - 1) / BB;
-    hipLaunchKernelGGL(k_take_plan, dim3(plan_grid < GATHER_PLAN_GRID ? plan_grid : GATHER_PLAN_GRID), dim3(BB), 0, stream, rows, n_rows, body_index, text_index, n_records, body_bytes,
-                       plan, d_status, stats);
+static uint32_t capped(uint64_t n, uint32_t most) { return n < most ? static_cast<uint32_t>(n) : most; }
+
+static uint32_t tiles_of(uint32_t n) { return (n + MATCH_TILE - 1) / MATCH_TILE; }
+
+// k_packed_scan over n sizes; REPORT: the call's report leaves with it.
+template <bool REPORT>
+static void launch_scan(hipStream_t stream, const uint32_t *sizes, uint32_t n, uint64_t *out_index, const PackedReport &r) {
+    hipLaunchKernelGGL(k_packed_scan<REPORT>, dim3(1), dim3(BB), 0, stream, sizes, n, out_index, static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
+}
+
+// The match's and the join's last two launches: the scan of the tile counts, which reports, and -- unless d_rows is null -- the emit.
+static void launch_scan_emit(hipStream_t stream, uint32_t n_tiles, uint32_t grid, const TileWs &tiles, uint32_t *d_rows, uint64_t cap_rows, const uint32_t *key_of,
+                             uint32_t *d_key_of_row, const PackedReport &r) {
+    launch_scan<true>(stream, tiles.counts, n_tiles, tiles.base, r);
+    if (!d_rows) return;
+    const unsigned long long *masks = tiles.masks;
+    const uint64_t *base = tiles.base;
+    if (d_key_of_row) hipLaunchKernelGGL(k_rows_emit<true>, dim3(grid), dim3(BB), 0, stream, masks, base, n_tiles, d_rows, cap_rows, key_of, d_key_of_row);
+    else hipLaunchKernelGGL(k_rows_emit<false>, dim3(grid), dim3(BB), 0, stream, masks, base, n_tiles, d_rows, cap_rows, key_of, d_key_of_row);
+}
+
+void launch_take(hipStream_t stream, const PackedStore &store, const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index,
+                 uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, const PackedReport &r) {
+    hipLaunchKernelGGL(k_take_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, rows, n_rows, plan, d_status, r.stats);
     hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
-                       static_cast<const unsigned long long *>(stats), host_result, host_done, epoch);
+                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
     if (!d_out) return;
-    const uint64_t tiles = cap / TAKE_TILE_BYTES + 2;  // (what fits into cap spans no more tiles, at any alignment)
-    hipLaunchKernelGGL(k_take_copy, dim3(static_cast<uint32_t>(tiles < TAKE_GRID ? tiles : TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies),
+    // (what fits into cap spans no more than cap / TAKE_TILE_BYTES + 2 tiles, at any alignment)
+    hipLaunchKernelGGL(k_take_copy, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(store.bodies),
                        static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
 }
 
-void launch_join(hipStream_t stream, const JoinSide &records, const JoinSide &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,
-                 uint64_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status, uint8_t *d_key_status, unsigned long long *masks, uint32_t *counts, uint64_t *base,
-                 uint32_t *key_of, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
-    const uint32_t n_tiles = (records.n + MATCH_TILE - 1) / MATCH_TILE, grid = n_tiles < JOIN_GRID ? n_tiles : JOIN_GRID;
-    if (keys.n) {
-        const uint32_t key_tiles = (keys.n + MATCH_TILE - 1) / MATCH_TILE;
-        hipLaunchKernelGGL(k_join_build, dim3(key_tiles < JOIN_GRID ? key_tiles : JOIN_GRID), dim3(BB), 0, stream, keys, table, slots - 1, d_key_status, stats);
-    }
-    hipLaunchKernelGGL(k_join_flag, dim3(grid), dim3(BB), 0, stream, records, keys, static_cast<const unsigned long long *>(table), slots - 1, flags, masks, counts, key_of,
-                       d_status, stats, host_result);
-    hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(counts), n_tiles, base, static_cast<const unsigned long long *>(stats),
-                       host_result, host_done, epoch);
-    if (d_rows)
-        hipLaunchKernelGGL(k_join_emit, dim3(grid), dim3(BB), 0, stream, static_cast<const unsigned long long *>(masks), static_cast<const uint64_t *>(base), n_tiles,
-                           static_cast<const uint32_t *>(key_of), d_rows, d_key_of_row, cap_rows);
+void launch_join(hipStream_t stream, const PackedStore &records, const PackedStore &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,
+                 uint64_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status, uint8_t *d_key_status, const TileWs &tiles, uint32_t *key_of, const PackedReport &r) {
+    const uint32_t n_tiles = tiles_of(records.n), grid = capped(n_tiles, JOIN_GRID);
+    if (keys.n) hipLaunchKernelGGL(k_join_build, dim3(capped(tiles_of(keys.n), JOIN_GRID)), dim3(BB), 0, stream, keys, table, slots - 1, d_key_status, r.stats);
+    hipLaunchKernelGGL(k_join_flag, dim3(grid), dim3(BB), 0, stream, records, keys, static_cast<const unsigned long long *>(table), slots - 1, flags, tiles, key_of, d_status,
+                       r.stats, r.host_result);
+    launch_scan_emit(stream, n_tiles, grid, tiles, d_rows, cap_rows, key_of, d_key_of_row, r);
 }
 
-void launch_join_hash(hipStream_t stream, const JoinSide &records, uint64_t *d_hash) {
-    const uint32_t n_tiles = (records.n + MATCH_TILE - 1) / MATCH_TILE;
-    hipLaunchKernelGGL(k_join_hash, dim3(n_tiles < JOIN_GRID ? n_tiles : JOIN_GRID), dim3(BB), 0, stream, records, d_hash);
+void launch_join_hash(hipStream_t stream, const PackedStore &records, uint64_t *d_hash) {
+    hipLaunchKernelGGL(k_join_hash, dim3(capped(tiles_of(records.n), JOIN_GRID)), dim3(BB), 0, stream, records, d_hash);
 }
 
-void launch_match(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
-                  const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, unsigned long long *masks, uint32_t *counts,
-                  uint64_t *base, unsigned long long *stats, unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
-    const uint32_t n_tiles = (n_records + MATCH_TILE - 1) / MATCH_TILE, grid = n_tiles < MATCH_GRID ? n_tiles : MATCH_GRID;
-    hipLaunchKernelGGL(k_match_flag, dim3(grid), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), body_bytes, body_index, text_index, n_records, pattern, job, masks,
-                       counts, d_status, stats);
-    hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(counts), n_tiles, base, static_cast<const unsigned long long *>(stats),
-                       host_result, host_done, epoch);
-    if (d_rows)
-        hipLaunchKernelGGL(k_match_emit, dim3(grid), dim3(BB), 0, stream, static_cast<const unsigned long long *>(masks), static_cast<const uint64_t *>(base), n_tiles, d_rows,
-                           cap_rows);
+void launch_match(hipStream_t stream, const PackedStore &store, const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status,
+                  const TileWs &tiles, const PackedReport &r) {
+    const uint32_t n_tiles = tiles_of(store.n), grid = capped(n_tiles, MATCH_GRID);
+    hipLaunchKernelGGL(k_match_flag, dim3(grid), dim3(BB), 0, stream, store, pattern, job, tiles, d_status, r.stats);
+    launch_scan_emit(stream, n_tiles, grid, tiles, d_rows, cap_rows, nullptr, nullptr, r);
 }
 
 void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_bytes, const uint64_t *text_index, uint32_t n, void *d_out, uint64_t cap,
-                          uint64_t *out_index, uint8_t *d_status, const uint2 *table, uint32_t *sizes, unsigned long long *stats,
-                          unsigned long long *host_result, unsigned long long *host_done, unsigned long long epoch) {
+                          uint64_t *out_index, uint8_t *d_status, const uint2 *table, uint32_t *sizes, const PackedReport &r) {
     const uint8_t *text = static_cast<const uint8_t *>(d_text);
-    hipLaunchKernelGGL(k_packed_count, dim3(batch_grid(n)), dim3(BB), 0, stream, text, text_bytes, text_index, n, table, sizes, d_status, stats);
-    hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, static_cast<const uint32_t *>(sizes), n, out_index, static_cast<const unsigned long long *>(stats), host_result,
-                       host_done, epoch);
+    hipLaunchKernelGGL(k_packed_count, dim3(batch_grid(n)), dim3(BB), 0, stream, text, text_bytes, text_index, n, table, sizes, d_status, r.stats);
+    launch_scan<true>(stream, sizes, n, out_index, r);
     if (d_out)
-        hipLaunchKernelGGL(k_packed_pack, dim3(n < SHARED_ENC_GRID ? n : SHARED_ENC_GRID), dim3(BB), 0, stream, text, text_bytes, text_index, n, static_cast<uint8_t *>(d_out), cap,
+        hipLaunchKernelGGL(k_packed_pack, dim3(capped(n, SHARED_ENC_GRID)), dim3(BB), 0, stream, text, text_bytes, text_index, n, static_cast<uint8_t *>(d_out), cap,
                            static_cast<const uint64_t *>(out_index), table);
 }
 
-void launch_packed_decode(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n, void *d_out,
-                          uint64_t cap, const uint2 *codes, uint32_t n_codes, uint32_t *d_written, uint8_t *d_status, unsigned long long *stats,
-                          unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done, unsigned long long epoch) {
-    hipLaunchKernelGGL(k_packed_decode, dim3(n < SHARED_DEC_GRID ? n : SHARED_DEC_GRID), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), body_bytes, body_index, text_index,
-                       n, static_cast<uint8_t *>(d_out), cap, codes, n_codes, d_written, d_status, stats, host_result, counter, host_done, epoch);
+void launch_packed_decode(hipStream_t stream, const PackedStore &store, void *d_out, uint64_t cap, const uint2 *codes, uint32_t n_codes, uint32_t *d_written,
+                          uint8_t *d_status, const PackedReport &r, uint32_t *counter) {
+    hipLaunchKernelGGL(k_packed_decode, dim3(capped(store.n, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, static_cast<uint8_t *>(d_out), cap, codes, n_codes, d_written, d_status,
+                       r, counter);
 }
 
-void launch_packed_gather(hipStream_t stream, const void *d_bodies, uint64_t body_bytes, const uint64_t *body_index, const uint64_t *text_index, uint32_t n_records,
-                          const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_index, const uint2 *codes, uint32_t n_codes, uint32_t *d_written,
-                          uint8_t *d_status, uint32_t *sizes, unsigned long long *stats, unsigned long long *host_result, uint32_t *counter, unsigned long long *host_done,
-                          unsigned long long epoch) {
-    const uint32_t plan_grid = (n_rows + BB - 1) / BB;
-    hipLaunchKernelGGL(k_gather_plan, dim3(plan_grid < GATHER_PLAN_GRID ? plan_grid : GATHER_PLAN_GRID), dim3(BB), 0, stream, rows, n_rows, body_index, text_index, n_records, body_bytes,
-                       sizes, d_status, stats);
-    const uint32_t *rooms = sizes;
-    const unsigned long long *counts = stats;
-    if (!d_out) {
-        hipLaunchKernelGGL(k_packed_scan<true>, dim3(1), dim3(BB), 0, stream, rooms, n_rows, out_index, counts, host_result, host_done, epoch);
-        return;
-    }
-    hipLaunchKernelGGL(k_packed_scan<false>, dim3(1), dim3(BB), 0, stream, rooms, n_rows, out_index, counts, host_result, host_done, epoch);
-    hipLaunchKernelGGL(k_packed_gather, dim3(n_rows < SHARED_DEC_GRID ? n_rows : SHARED_DEC_GRID), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), body_index, rows, n_rows,
-                       static_cast<uint8_t *>(d_out), cap, static_cast<const uint64_t *>(out_index), codes, n_codes, d_written, stats, host_result, counter, host_done, epoch);
+void launch_packed_gather(hipStream_t stream, const PackedStore &store, const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_index,
+                          const uint2 *codes, uint32_t n_codes, uint32_t *d_written, uint8_t *d_status, uint32_t *sizes, const PackedReport &r, uint32_t *counter) {
+    hipLaunchKernelGGL(k_gather_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, rows, n_rows, sizes, d_status, r.stats);
+    if (!d_out) return launch_scan<true>(stream, sizes, n_rows, out_index, r);
+    launch_scan<false>(stream, sizes, n_rows, out_index, r);
+    hipLaunchKernelGGL(k_packed_gather, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, rows, n_rows, static_cast<uint8_t *>(d_out), cap,
+                       static_cast<const uint64_t *>(out_index), codes, n_codes, d_written, r, counter);
 }
 
 void launch_shared_encode(hipStream_t stream, const void *d_in, void *d_out, const SharedJob *jobs, uint32_t n, const uint2 *table,

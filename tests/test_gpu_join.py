@@ -17,9 +17,10 @@ import pytest
 
 from tests import corpus
 from tests.test_gpu_batch import SENTINEL, _small_max, _u8
-from tests.test_gpu_gather import _mixed_store, make_store, upload, want_rows  # noqa: F401  (want_rows, want_decode: through judged)
-from tests.test_gpu_match import EQUAL, ROW_SENTINEL, _pack, _store, judged, run_match
+from tests.test_gpu_gather import _mixed_store, dev_rows, make_store, upload, want_rows  # noqa: F401  (want_rows, want_decode: through judged)
+from tests.test_gpu_match import EQUAL, HEAD_BITS, PREFIX, ROW_SENTINEL, _pack, _store, judged, pattern_bits, run_match, want_match
 from tests.test_gpu_packed import TAIL, _dev_bytes, _dev_index, _index_of
+from tests.test_gpu_take import model
 from tests.test_gpu_shared import _cb, want_decode  # noqa: F401
 from tests.test_shared_host import oracle_table, table_255, table_2bit, table_ladder
 
@@ -631,7 +632,96 @@ def test_encode_keys_then_join_then_gather_with_no_synchronisation(ctx):
     assert (j2.status, j2.n_match) == (OK, len(other_rows)) and d_rows2[: j2.n_match].tolist() == other_rows and d_keys2[: j2.n_match].tolist() == other_key_rows
 
 
-# --- 11. the Python layer -------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def family_fixture():
+    """-> (store, 40 key texts, rows, a needle whose pattern is longer than the head).  600 records of 0 .. 40 bytes -- three tiles, the
+    last one partial -- under the table of their own text; records 100, 300 and 599 are one text of 30 bytes, record 450 begins with it;
+    record 3's body pair decreases (the empty record 4 begins 2 bytes early).  30 keys are records' texts, none empty, 10 are no
+    record's.  The rows hold record 3, a number beyond the store, and repeats."""
+    rng = np.random.default_rng(0x10A5EA00)
+    sizes = rng.integers(0, 41, size=600)
+    sizes[3], sizes[4] = 20, 0
+    sizes[5::20] = np.maximum(sizes[5::20], 1)
+    pool = corpus.text_like(int(sizes.sum()) + 400, 0x10A5EA01)
+    cuts = _index_of(sizes)
+    texts = [pool[int(cuts[i]) : int(cuts[i + 1])].tobytes() for i in range(600)]
+    stem = pool[int(cuts[-1]) : int(cuts[-1]) + 30].tobytes()
+    texts[100] = texts[300] = texts[599] = stem
+    texts[450] = stem + b"tail"
+    st = _store(oracle_table(pool), texts)
+    st.body_index[4] = st.body_index[3] - np.uint64(2)
+    key_texts = [texts[b] for b in range(5, 600, 20)] + [pool[int(cuts[-1]) + 40 + 36 * i : int(cuts[-1]) + 40 + 36 * i + 33].tobytes() for i in range(10)]
+    rows = [int(r) for r in rng.integers(4, 600, size=300)] + [3, 599, st.n + 7, 0, 599]
+    return st, key_texts, rows, stem[:24]
+
+
+def test_every_call_of_the_family_shares_one_upload_region_with_no_synchronisation(ctx):
+    """match (a pattern beyond the head) -> encode -> join -> take -> gather -> match (one byte), twice round on one ctx with nothing in
+    between: each call refills the pinned region the call before it uploaded from -- table, counters, pattern -- and every result is the
+    oracle's, never another run's."""
+    import torch
+
+    st, key_texts, rows, needle = family_fixture()
+    ks = _store(st.tab, key_texts)
+    one = key_texts[0][:1]
+    assert len(key_texts) == 40 and pattern_bits(st.tab, needle) > HEAD_BITS and 0 < pattern_bits(st.tab, one) <= HEAD_BITS
+    wants = judged(st)
+    statuses = [s for s, _, _ in wants]
+    assert [b for b, s in enumerate(statuses) if s] == [3] and statuses[3] == ARG
+    want_long, want_one = want_match(st, needle, PREFIX), want_match(st, one, PREFIX)
+    want_j, want_k = want_join(st, ks, 0)
+    assert want_long == [100, 300, 450, 599] and len(want_one) > 4 and len(want_j) >= 30
+    taken, gathered = model(st, rows), want_rows(st, rows)
+    row_failed = [k for k, s in enumerate(taken.status) if s]
+    assert len(row_failed) == 2 and [s for s, _, _ in gathered] == list(taken.status)
+    room = sum(r for _, r, _ in gathered)
+    g_index = _index_of([r for _, r, _ in gathered])
+
+    dev, d_rows = upload(st), dev_rows(rows)
+    d_key_text, d_key_text_index = _dev_bytes(np.frombuffer(b"".join(key_texts), np.uint8)), _dev_index(ks.text_index)
+
+    def outputs():
+        u8 = lambda n: torch.full((n,), SENTINEL, dtype=torch.uint8, device="cuda")  # noqa: E731
+        i32 = lambda n: torch.full((n,), -1, dtype=torch.int32, device="cuda")  # noqa: E731
+        i64 = lambda n: torch.full((n,), -1, dtype=torch.int64, device="cuda")  # noqa: E731
+        return SimpleNamespace(m_rows=i32(st.n), m_status=u8(st.n), key_bodies=u8(ks.bodies.size + TAIL), key_index=i64(ks.n + 1), j_rows=i32(st.n), j_keys=i32(st.n), j_status=u8(st.n),
+                               t_out=u8(taken.total + TAIL), t_body_index=i64(len(rows) + 1), t_text_index=i64(len(rows) + 1), t_status=u8(len(rows)), g_out=u8(room + TAIL),
+                               g_index=i64(len(rows) + 1), g_status=u8(len(rows)), o_rows=i32(st.n), o_status=u8(st.n))
+
+    rounds = [outputs(), outputs()]
+    torch.cuda.synchronize()
+    for o in rounds:
+        o.m = ctx.match_packed_device(st.cb, *dev, needle, PREFIX, rows=o.m_rows, status=o.m_status)
+        o.e = ctx.encode_packed_device(st.cb, d_key_text, d_key_text_index, o.key_bodies[: ks.bodies.size], o.key_index)
+        o.j = ctx.join_packed_device(st.cb, *dev, o.key_bodies[: ks.bodies.size], o.key_index, d_key_text_index, rows=o.j_rows, key_of_row=o.j_keys, status=o.j_status)
+        o.t = ctx.take_packed_device(*dev, d_rows, o.t_out[: max(taken.total, 1)], o.t_body_index, o.t_text_index, status=o.t_status)
+        o.g = ctx.decode_packed_gather_device(st.cb, *dev, d_rows, o.g_out[:room], o.g_index, status=o.g_status)
+        o.o = ctx.match_packed_device(st.cb, *dev, one, PREFIX, rows=o.o_rows, status=o.o_status)
+    torch.cuda.synchronize()
+
+    def selected(d, want):
+        return d[: len(want)].tolist() == want and bool((d[len(want) :] == -1).all())
+
+    for o in rounds:
+        for m, d, status, want, bits in ((o.m, o.m_rows, o.m_status, want_long, pattern_bits(st.tab, needle)), (o.o, o.o_rows, o.o_status, want_one, pattern_bits(st.tab, one))):
+            assert (m.status, m.n_match, m.n_failed, m.first_failed, m.first_status, m.pattern_bits) == (OK, len(want), 1, 3, ARG, bits), m
+            assert selected(d, want) and status.tolist() == statuses
+        assert (o.e.status, o.e.out_bytes, o.e.n_failed) == (OK, ks.bodies.size, 0), o.e
+        key_bodies = o.key_bodies.cpu().numpy()
+        assert key_bodies[: ks.bodies.size].tobytes() == ks.bodies.tobytes() and bool((key_bodies[ks.bodies.size :] == SENTINEL).all())
+        assert np.array_equal(o.key_index.cpu().numpy().view(np.uint64), ks.body_index)
+        assert (o.j.status, o.j.n_match, o.j.n_failed, o.j.first_failed, o.j.first_status, o.j.n_keys_failed) == (OK, len(want_j), 1, 3, ARG, 0), o.j
+        assert selected(o.j_rows, want_j) and selected(o.j_keys, want_k) and o.j_status.tolist() == statuses
+        assert (o.t.status, o.t.out_bytes, o.t.text_bytes, o.t.n_failed, o.t.first_failed, o.t.first_status) == (OK, taken.total, taken.text_total, 2, row_failed[0], ARG), o.t
+        t_out = o.t_out.cpu().numpy()
+        assert t_out[: taken.total].tobytes() == taken.data.tobytes() and bool((t_out[taken.total :] == SENTINEL).all())
+        assert np.array_equal(o.t_body_index.cpu().numpy().view(np.uint64), taken.body_index) and np.array_equal(o.t_text_index.cpu().numpy().view(np.uint64), taken.text_index)
+        assert o.t_status.tolist() == list(taken.status)
+        assert (o.g.status, o.g.out_bytes, o.g.n_failed, o.g.first_failed, o.g.first_status, o.g.n_short) == (OK, room, 2, row_failed[0], ARG, 0), o.g
+        g_out = o.g_out.cpu().numpy()
+        assert g_out[:room].tobytes() == b"".join(data for _, _, data in gathered) and bool((g_out[room:] == SENTINEL).all())
+        assert np.array_equal(o.g_index.cpu().numpy().view(np.uint64), g_index) and o.g_status.tolist() == list(taken.status)
+
 
 
 def test_python_calls_give_the_same_rows(ctx):
