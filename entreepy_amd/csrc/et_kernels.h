@@ -28,10 +28,10 @@ constexpr uint32_t MAX_GRID = 2048;           // 256 CUs x 8 workgroups, grid-st
 constexpr uint32_t SUB_BITS = 256;                             // decode: bits per lane subsequence
 constexpr uint32_t DEC_BLOCK_WORDS = BLOCK * SUB_BITS / 32;    // 8 KiB of bitstream per workgroup
 constexpr uint32_t DEC_GUARD_WORDS = 4;                        // words a lane may read past its workgroup's 8 KiB
-// How the LDS-window decode kernels take their 8 KiB blocks (measured choices): k_dec_sync one block per
-// workgroup, k_dec_write chunks of four by ticket.
-constexpr uint32_t SYNC_CHUNK = 1, WRITE_CHUNK = 4;  // consecutive blocks per chunk
-constexpr bool SYNC_TICKET = false, WRITE_TICKET = true;  // chunks by ticket counter vs one per workgroup
+// How the round-1 decode kernels take their 8 KiB blocks: the LDS-window kernels (k_dec_sync, k_dec_maps, k_dec_resolve,
+// k_dec_write) one block per workgroup -- they run over three blocks at the most, or over a call's special blocks; the
+// register-window kernels by ticket, k_dec_write_reg in chunks of
+constexpr uint32_t WRITE_CHUNK = 4;  // consecutive blocks (k_dec_sync_reg / _reg2: the chunk sizes in launch_dec_sync)
 constexpr uint32_t DEC_FIRST_SWEEP_TRIPS = 6;                   // local fixed-point trips before a block is declared non-synchronising
 constexpr uint32_t DEC_REPAIR_SWEEP_TRIPS = 8;                  // same cap for the two speculatively enqueued repair sweeps
 // ONE rule for "the sweeps left a final synchronisation state", applied by the host to its copy of
@@ -44,7 +44,7 @@ __host__ __device__ inline bool dec_state_final(uint32_t gave_up, uint32_t verif
 }
 constexpr uint32_t DEC_HAVE_START = 1, DEC_FRONT_OK = 2;       // k_dec_sync flags (ranges of a stream split over GPUs)
 constexpr uint32_t DEC_SPECIAL_SUPER = 8;                      // with DEC_SPECIAL_ONLY: the blocks of 16 KiB superblocks k_dec_sync_reg2 leaves out
-constexpr uint32_t DEC_SPECIAL_ONLY = 4;                       // k_dec_sync flag: first/last blocks only (k_dec_sync_reg has the rest)
+constexpr uint32_t DEC_SPECIAL_ONLY = 4;                       // k_dec_sync flag, k_dec_maps / _resolve / _write mode: first/last blocks only (the _reg kernel has the rest)
 constexpr uint32_t DEC_FRONT_WORDS = 4;                        // words staged BEFORE the workgroup's 8 KiB (warm-up run-in)
 constexpr uint32_t DEC_WARMUP_BITS = DEC_FRONT_WORDS * 32;     // run-in before each subsequence in the first sync sweep
 constexpr uint32_t DEC_STAGED_WORDS = DEC_FRONT_WORDS + DEC_BLOCK_WORDS + DEC_GUARD_WORDS;
@@ -58,8 +58,8 @@ enum DecFlag : uint32_t {
     FLAG_GAVE_UP = 1,        // blocks that gave up in the first sweep
     FLAG_VERIFY_FAILED = 2,  // the scan's verification failed
     FLAG_ROW_BLIND = 3,      // the row walk: a chunk never saw the chunks before it
-    FLAG_SYNC_TICKET = 4,    // ticket of the window sweeps (D1), and of a range's write
-    FLAG_WRITE_TICKET = 5,   // ticket of the whole-stream write (D3)
+    FLAG_SYNC_TICKET = 4,    // ticket of k_dec_sync_reg / _reg2 (D1's first sweep), and of k_dec_write_reg in a range's write
+    FLAG_WRITE_TICKET = 5,   // ticket of k_dec_write_reg in the whole-stream write (D3); no LDS-window kernel draws a ticket
     FLAG_WORK_COUNT = 8,     // worklist count
     FLAG_RANGE_EXIT = 9,     // a tree-walked range's exit bit (k_tw_sync's exit_bits)
     FLAG_TOTAL_LO = 12,      // symbol total ...
@@ -70,7 +70,7 @@ enum DecFlag : uint32_t {
 constexpr uint32_t DEC_SWEEP_FLAGS = 4;  // the words in front of the tickets: all a first window sweep needs cleared
 static_assert(FLAG_CHANGED < DEC_SWEEP_FLAGS && FLAG_GAVE_UP < DEC_SWEEP_FLAGS && FLAG_VERIFY_FAILED < DEC_SWEEP_FLAGS && FLAG_ROW_BLIND < DEC_SWEEP_FLAGS &&
                   FLAG_SYNC_TICKET >= DEC_SWEEP_FLAGS && FLAG_WRITE_TICKET >= DEC_SWEEP_FLAGS,
-              "the sweeps' flags lie in front of the tickets, which clear themselves");
+              "the sweeps' flags lie in front of the tickets, which the launches that draw on them clear (unless told they are zero)");
 
 // The workspaces every synchronisation writes, as the kernels take them.
 struct DecWs {
@@ -116,7 +116,8 @@ void launch_tile_scan(hipStream_t stream, const uint32_t *tile_hist, uint32_t n_
                       unsigned long long *tile_off, uint32_t *out32, const uint32_t *header_src = nullptr, uint32_t header_words = 0);  // header_src (device): the file header, copied to out32[0 .. header_words) behind the seam word's zeroing
 void launch_encode(hipStream_t stream, const uint8_t *base, uint64_t lo, uint64_t hi, uint32_t rounds_per_tile, uint32_t n_tiles,
                    const unsigned long long *tile_off, const uint2 *enc_table, uint32_t max_len, uint32_t *out32, KernelEvents ev = {});
-// D1 by window sweeps over s, number iter of it; counts on FLAG_SYNC_TICKET, raises FLAG_CHANGED.  listed (iter >= 1): the blocks that
+// D1 by window sweeps over s, number iter of it; raises FLAG_CHANGED; a first sweep over more than three blocks counts on FLAG_SYNC_TICKET
+// (ticket_is_zero: the caller has just cleared it).  listed (iter >= 1): the blocks that
 // disagree with the one before them go on s.worklist (FLAG_WORK_COUNT, zeroed by the caller, counts them) and the sweep is over
 // those; else over every block.
 void launch_dec_sync(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint32_t iter, uint32_t max_trips, uint32_t flags = DEC_HAVE_START,
@@ -139,7 +140,8 @@ struct ScanReport { uint32_t *host; uint32_t epoch; };
 void launch_dec_scan(hipStream_t stream, const DecSpan &s, uint32_t epoch, const ScanVerify *verify = nullptr, const ScanReport *report = nullptr);
 // D3 over the chained lookup tables (et_treewalk.h; chain_max_len: the dictionary's longest code), every block by k_dec_write_wave --
 // strips: by its instantiation for streams with many symbols per subsequence (quarters that overflow the stage walk once, into
-// strips) -- or, chain == nullptr, over tb, counting on flag word `ticket` (FLAG_SYNC_TICKET or FLAG_WRITE_TICKET).  speculative: the
+// strips) -- or, chain == nullptr, over tb, a span of more than three blocks counting on flag word `ticket` (FLAG_SYNC_TICKET or
+// FLAG_WRITE_TICKET; a smaller one leaves the word alone).  speculative: the
 // kernel itself looks at the sweeps' flags and does nothing if the state is not final (dec_state_final).
 void launch_dec_write(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint64_t n_symbols, uint8_t *out, DecFlag ticket = FLAG_SYNC_TICKET,
                       const SideLane *side = nullptr, bool ticket_is_zero = false, bool speculative = false, KernelEvents ev = {},  // ev: the main write kernel

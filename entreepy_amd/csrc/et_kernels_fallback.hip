@@ -11,6 +11,21 @@
 // Used when: a hand-made dictionary's completed tree has more than 255 internal nodes or is not prefix-free; a near-fixed-length code
 // that is not a row code; a range of a stream split over GPUs whose code does not self-synchronise; blocks that give up in the first sweep.
 // Scans, the guarded stream word, launch helpers: et_device.h; what this file shares with et_kernels.hip alone: et_kernels_common.h.
+//
+// What runs where.  A block is 8 KiB of stream; "special" = the stream's first block and the one or two whose staged words
+// reach its end (special_block); "interior" = every other one; a superblock = two blocks, both interior (super_interior).
+//   block class        kernels                                           LDS layout          a workgroup takes
+//   special            k_dec_sync, k_dec_maps, k_dec_resolve, k_dec_write  DecodeSmem          one block (window_block)
+//   interior           k_dec_sync_reg, k_dec_maps_reg, k_dec_resolve_reg   StepSmem SS_SYNC /  tickets of 4 blocks, the worklist, or
+//                      k_dec_write_reg                                     SS_EXIT_MAPS / SS_WRITE  one block (maps, resolve)
+//   superblock         k_dec_sync_reg2 (first sweep, >= 16 blocks)         StepSmem SS_SYNC    tickets of 4 superblocks
+//   call               <= 3 blocks           4 .. 15 blocks                                  >= 16 blocks
+//   sweep              k_dec_sync<true>      k_dec_sync_reg<true, true> + k_dec_sync<true> x 3   k_dec_sync_reg2 + k_dec_sync<true> x 8
+//   repair sweep       k_dec_sync<false>     (k_dec_check +) k_dec_sync_reg<false, false> + k_dec_sync<false> x 3
+//   maps               k_dec_maps            k_dec_maps_reg + k_dec_maps x 3                     (then k_dec_compose)
+//   resolve            k_dec_resolve         (k_dec_chain x 2, then) k_dec_resolve_reg + k_dec_resolve x 3
+//   write              k_dec_write           k_dec_write_reg + k_dec_write x 3
+// (x 3 / x 8: a special-only launch of that many workgroups, each of which takes its candidate block if the big kernel leaves it out.)
 #include "et_kernels_common.h"
 #include "et_treewalk.h"
 
@@ -36,7 +51,7 @@ namespace et {
 // of SUB_BITS / 32 = 8 words, fall on different LDS banks.
 __device__ __forceinline__ uint32_t phys(uint32_t logical_word) { return logical_word + (logical_word >> 5); }
 
-// Dynamic LDS carve (all offsets multiples of 16 bytes).
+// Dynamic LDS carve of the LDS-window kernels (all offsets multiples of 16 bytes).
 struct DecodeSmem {
     uint32_t *sdata;   // DEC_SDATA_WORDS
     uint32_t *lut;     // 1 << lut_bits
@@ -44,11 +59,10 @@ struct DecodeSmem {
     uint8_t *sym_len;  // 256
     uint32_t *exits;   // BLOCK
     uint32_t *scratch; // 8 (scan scratch [0..3], flag [4])
-    uint8_t *stage;    // DEC_STAGE_BYTES (write kernel only)
+    uint8_t *stage;    // DEC_STAGE_BYTES (write kernel), or maps [BLOCK][32] (k_dec_maps, k_dec_resolve)
 };
 
-
-__device__ __forceinline__ uint32_t sub_words(const DecodeTables &tb) { return (((tb.n_sub << tb.sub_bits) + 7u) & ~7u) / 2; }
+__host__ __device__ __forceinline__ uint32_t sub_words(const DecodeTables &tb) { return (((tb.n_sub << tb.sub_bits) + 7u) & ~7u) / 2; }
 
 // WITH_EXITS: the sync kernels exchange exits through LDS; the write kernel does not and
 // must stay under 32 KiB (5 workgroups per CU).
@@ -64,20 +78,55 @@ __device__ __forceinline__ DecodeSmem carve_decode_smem(const DecodeTables &tb) 
     m.stage = reinterpret_cast<uint8_t *>(m.scratch + 8);
     return m;
 }
+// the bytes of that carve (with_stage: the stage and the 16 bytes a window's last 16-byte store may reach into)
+static inline size_t decode_smem_bytes(const DecodeTables &tb, bool with_stage, bool with_exits = true) {
+    return (DEC_SDATA_WORDS + (1u << tb.lut_bits) + sub_words(tb) + 64 + (with_exits ? BLOCK : 0) + 8) * sizeof(uint32_t) + (with_stage ? DEC_STAGE_BYTES + 16 : 0);
+}
 
-// Staging.  A decode workgroup handles chunks of SYNC_CHUNK / WRITE_CHUNK consecutive
-// 8 KiB blocks (et_kernels.h): it copies the lookup tables into LDS once and then walks
-// the blocks; while it works on one block, the next block's words are already in flight
-// into registers
-// (prefetch_block) and are written to LDS (commit_block) only when the current block
-// is done with the staging area.  LDS holds host-order words whose numeric MSB is the
-// first stream bit; logical word i of the stage = stream word
+// Dynamic LDS of the register-window kernels: the step table (both levels; step_words words), and behind it the parts a
+// kernel names, in DecodeSmem's order.  ONE description (step_layout) gives a kernel its pointers and its launch the bytes.
+enum : uint32_t { SS_MAPS = 1, SS_LENS = 2, SS_EXITS = 4, SS_STAGE = 8 };  // scratch is everybody's
+struct StepLayout {
+    uint32_t maps, sym_len, exits, scratch, stage, bytes;  // byte offsets behind the table; bytes: all of them
+};
+__host__ __device__ constexpr StepLayout step_layout(uint32_t parts) {
+    StepLayout l{};
+    l.maps = 0;  // [BLOCK][32]
+    l.sym_len = l.maps + ((parts & SS_MAPS) ? BLOCK * 32 : 0);
+    l.exits = l.sym_len + ((parts & SS_LENS) ? 256 : 0);
+    l.scratch = l.exits + ((parts & SS_EXITS) ? BLOCK * 4 : 0);
+    l.stage = l.scratch + 8 * 4;
+    l.bytes = l.stage + ((parts & SS_STAGE) ? DEC_STAGE_BYTES + 16 : 0);
+    return l;
+}
+struct StepSmem {
+    uint32_t *steps;
+    uint8_t *maps, *sym_len;
+    uint32_t *exits, *scratch;
+    uint8_t *stage;
+    uint32_t stage_off;  // the stage's offset in dec_smem_raw
+};
+template <uint32_t PARTS>
+__device__ __forceinline__ StepSmem carve_step_smem(uint32_t step_words) {
+    constexpr StepLayout l = step_layout(PARTS);
+    uint32_t *tail = reinterpret_cast<uint32_t *>(dec_smem_raw) + step_words;
+    StepSmem m;
+    m.steps = reinterpret_cast<uint32_t *>(dec_smem_raw);
+    m.maps = reinterpret_cast<uint8_t *>(tail + l.maps / 4);
+    m.sym_len = reinterpret_cast<uint8_t *>(tail + l.sym_len / 4);
+    m.exits = tail + l.exits / 4;
+    m.scratch = tail + l.scratch / 4;
+    m.stage_off = step_words * 4 + l.stage;
+    m.stage = dec_smem_raw + m.stage_off;
+    return m;
+}
+static inline size_t step_smem_bytes(uint32_t step_words, uint32_t parts) { return step_words * sizeof(uint32_t) + step_layout(parts).bytes; }
+constexpr uint32_t SS_SYNC = SS_EXITS, SS_EXIT_MAPS = SS_MAPS | SS_EXITS, SS_WRITE = SS_LENS | SS_STAGE;  // the three layouts in use
+
+// Staging.  An LDS-window workgroup copies the lookup tables and its ONE 8 KiB block into LDS.  LDS holds host-order
+// words whose numeric MSB is the first stream bit; logical word i of the stage = stream word
 // first_word - DEC_FRONT_WORDS + i (zero before and after the stream).
 constexpr int DEC_WORDS_PER_THREAD = (DEC_STAGED_WORDS + BLOCK - 1) / BLOCK;
-
-struct Prefetch {
-    uint32_t w[DEC_WORDS_PER_THREAD];
-};
 
 __device__ __forceinline__ void stage_tables(const DecodeSmem &m, const DecodeTables &tb) {
     const uint32_t n_lut = 1u << tb.lut_bits;
@@ -89,8 +138,8 @@ __device__ __forceinline__ void stage_tables(const DecodeSmem &m, const DecodeTa
 
 // front_ok: the DEC_FRONT_WORDS words BEFORE `words` are readable stream bytes (a rank's
 // range of a stream decoded on several GPUs); otherwise they read as zero.
-__device__ __forceinline__ void prefetch_block(Prefetch &p, const uint32_t *__restrict__ words, uint64_t block, uint64_t n_bytes,
-                                               bool front_ok = false) {
+__device__ __forceinline__ void stage_block(const DecodeSmem &m, const uint32_t *__restrict__ words, uint64_t block, uint64_t n_bytes,
+                                            bool front_ok = false) {
     const uint64_t first_word = block * DEC_BLOCK_WORDS;
     // workgroup-uniform: every staged word lies wholly inside the stream
     const bool interior = (first_word >= DEC_FRONT_WORDS || front_ok) && (first_word + DEC_STAGED_WORDS - DEC_FRONT_WORDS) * 4 <= n_bytes;
@@ -99,19 +148,31 @@ __device__ __forceinline__ void prefetch_block(Prefetch &p, const uint32_t *__re
         const uint32_t i = j * BLOCK + threadIdx.x;
         if (i < DEC_STAGED_WORDS) {
             const long long w = static_cast<long long>(first_word + i) - DEC_FRONT_WORDS;  // negative: before `words`
-            if (interior) p.w[j] = __builtin_bswap32(words[w]);
-            else if (w < 0) p.w[j] = front_ok ? __builtin_bswap32(words[w]) : 0u;
-            else p.w[j] = load_be32_guarded(words, static_cast<uint64_t>(w), n_bytes);
+            uint32_t v;
+            if (interior) v = __builtin_bswap32(words[w]);
+            else if (w < 0) v = front_ok ? __builtin_bswap32(words[w]) : 0u;
+            else v = load_be32_guarded(words, static_cast<uint64_t>(w), n_bytes);
+            m.sdata[phys(i)] = v;
         }
     }
 }
 
-__device__ __forceinline__ void commit_block(const DecodeSmem &m, const Prefetch &p) {
-#pragma unroll
-    for (int j = 0; j < DEC_WORDS_PER_THREAD; ++j) {
-        const uint32_t i = j * BLOCK + threadIdx.x;
-        if (i < DEC_STAGED_WORDS) m.sdata[phys(i)] = p.w[j];
+// The block of workgroup blockIdx.x in an LDS-window launch, NO_BLOCK if it has none.  mode 0: every block (grid n_blocks);
+// DEC_SPECIAL_ONLY: the special ones among the candidates (grid 3), the others belong to the register-window kernel of the
+// same call; with DEC_SPECIAL_SUPER: the blocks of superblocks that k_dec_sync_reg2 leaves out (grid 8).
+constexpr uint64_t NO_BLOCK = ~0ull;
+__device__ __forceinline__ uint64_t window_block(uint32_t mode, uint64_t n_bytes, uint32_t n_blocks) {
+    if (!(mode & DEC_SPECIAL_ONLY)) return blockIdx.x < n_blocks ? blockIdx.x : NO_BLOCK;
+    if (mode & DEC_SPECIAL_SUPER) {
+        const uint64_t b = special_candidate2(blockIdx.x, n_blocks);
+        return b < n_blocks && !super_interior(b >> 1, n_bytes, n_blocks) ? b : NO_BLOCK;
     }
+    const uint64_t b = special_candidate(blockIdx.x, n_blocks);
+    return b < n_blocks && special_block(b, n_bytes) ? b : NO_BLOCK;
+}
+// the subsequences of block b that exist (1 .. BLOCK)
+__device__ __forceinline__ uint32_t live_lanes(uint64_t n_subs, uint64_t b) {
+    return static_cast<uint32_t>(n_subs - b * BLOCK >= BLOCK ? BLOCK : n_subs - b * BLOCK);
 }
 
 struct SubResult {
@@ -120,13 +181,49 @@ struct SubResult {
     uint32_t count;
 };
 
+// The sub_state word of a subsequence: start | exit << 8 | count << 16.
+__device__ __forceinline__ uint32_t pack_state(uint32_t start, uint32_t exit_rel, uint32_t count) { return start | (exit_rel << 8) | (count << 16); }
+__device__ __forceinline__ SubResult unpack_state(uint32_t st) { return SubResult{st & 0xffu, (st >> 8) & 0xffu, st >> 16}; }
+
+// A block's results: the state word of every live lane (n_live of them, 1 .. BLOCK), the block's symbol count, and the
+// exit of its last live lane.  Every lane of the workgroup calls it (the scan has a barrier).
+__device__ __forceinline__ void publish_block(uint32_t *__restrict__ sub_state, uint32_t *__restrict__ blk_exit, uint32_t *__restrict__ blk_count,
+                                              uint32_t *scratch, uint64_t b, uint32_t n_live, uint32_t start, uint32_t exit_rel, uint32_t count) {
+    const uint32_t tid = threadIdx.x;
+    const bool live = tid < n_live;
+    if (live) sub_state[b * BLOCK + tid] = pack_state(start, exit_rel, count);
+    uint32_t total;
+    block_exclusive_scan(live ? count : 0u, scratch, &total);
+    if (tid == 0) blk_count[b] = total;
+    if (tid == n_live - 1) blk_exit[b] = exit_rel;
+}
+
 // Escape of a table step: the first code at the top of `window` is longer than the
 // first-level table (or nothing starts here).  Returns (len << 8) | sym, 0 = no code.
+// sub: the second-level table (LDS or global memory); bits = lut_bits | sub_bits << 8.
+__device__ __forceinline__ uint32_t long_code_flat(const uint16_t *sub, const uint32_t *longc, uint32_t n_long, uint32_t bits, uint32_t e,
+                                                  uint32_t window) {
+    const uint32_t lut_bits = bits & 0xffu, sub_bits = bits >> 8;
+    uint32_t hit = 0;
+    if ((e >> LUT_SUB_SHIFT) & 1u) hit = sub[((e & 0xffu) << sub_bits) | ((window << lut_bits) >> (32 - sub_bits))];
+    if (hit == 0) {  // deeper than both tables (or no table slot left): search the list in global memory
+        for (uint32_t i = 0; i < n_long; ++i) {
+            const uint32_t meta = longc[2 * i + 1], l = meta >> 8;
+            if (((window ^ longc[2 * i]) >> (32 - l)) == 0) {
+                hit = meta;
+                break;
+            }
+        }
+    }
+    return hit;
+}
+// The same search over the LDS-window kernels' tables.  (Not a call of long_code_flat: packing the two widths for it costs
+// k_dec_sync<true>, k_dec_maps and k_dec_resolve two SGPRs each and k_dec_write one.)
 __device__ __forceinline__ uint32_t long_code(const DecodeSmem &m, const DecodeTables &tb, uint32_t e, uint32_t window) {
     uint32_t hit = 0;
     if ((e >> LUT_SUB_SHIFT) & 1u)
         hit = m.sub[((e & 0xffu) << tb.sub_bits) | ((window << tb.lut_bits) >> (32 - tb.sub_bits))];
-    if (hit == 0) {  // deeper than both tables (or no table slot left): search the list in global memory
+    if (hit == 0) {
         for (uint32_t i = 0; i < tb.n_long; ++i) {
             const uint32_t meta = tb.longc[2 * i + 1], l = meta >> 8;
             if (((window ^ tb.longc[2 * i]) >> (32 - l)) == 0) {
@@ -285,136 +382,87 @@ __global__ __launch_bounds__(BLOCK) void k_dec_sync(const uint32_t *__restrict__
                                                     uint64_t n_subs, uint32_t n_blocks, DecodeTables tb,
                                                     uint32_t *__restrict__ sub_state, uint32_t *__restrict__ blk_exit,
                                                     uint32_t *__restrict__ blk_count, uint32_t *__restrict__ changed,
-                                                    uint32_t *__restrict__ ticket, uint32_t max_trips, uint32_t flags) {
-    // flags: DEC_SPECIAL_ONLY: handle only the special blocks (first, last one or two; one
-    // per workgroup), the others belong to k_dec_sync_reg.  (DEC_HAVE_START: first_bit is the exact start of subsequence 0; DEC_FRONT_OK:
-    // the words before `words` belong to the stream) differ from {1, 0} only for a rank's
-    // range of a stream decoded on several GPUs.
+                                                    uint32_t max_trips, uint32_t flags) {
+    // One block per workgroup.  flags: which block (window_block: DEC_SPECIAL_ONLY, DEC_SPECIAL_SUPER), and DEC_HAVE_START
+    // (first_bit is the exact start of subsequence 0), DEC_FRONT_OK (the words before `words` belong to the stream), which
+    // differ from {1, 0} only for a rank's range of a stream decoded on several GPUs.
     const bool have_start = flags & DEC_HAVE_START, front_ok = flags & DEC_FRONT_OK;
     const DecodeSmem m = carve_decode_smem(tb);
     const int tid = threadIdx.x;
-    bool tables_staged = FIRST;  // repair sweeps copy the tables only if a block needs repair
-    if (FIRST) stage_tables(m, tb);
-    Prefetch pf;
-    uint32_t round = 0;
-    // Blocks are handed out in chunks of SYNC_CHUNK consecutive blocks (tables staged
-    // once per workgroup, next block prefetched inside a chunk): either one chunk per
-    // workgroup, dispatched by the hardware, or (SYNC_TICKET) through a ticket counter
-    // to a grid sized to the device, so that a workgroup that becomes resident late --
-    // or never -- costs nothing.
-    for (bool first_trip = true;; first_trip = false) {
-        uint64_t b0;
-        if (SYNC_TICKET && !(flags & DEC_SPECIAL_ONLY)) {
-            __syncthreads();  // tables staged (first trip); everybody is done with scratch[7]
-            if (tid == 0) m.scratch[7] = atomicAdd(ticket, SYNC_CHUNK);
-            __syncthreads();
-            b0 = m.scratch[7];
-        } else {
-            if (!first_trip) break;
-            b0 = static_cast<uint64_t>(blockIdx.x) * SYNC_CHUNK;
-            __syncthreads();
-        }
-        if (flags & DEC_SPECIAL_ONLY) {
-            if (!first_trip) break;
-            if (flags & DEC_SPECIAL_SUPER) {
-                b0 = special_candidate2(blockIdx.x, n_blocks);
-                if (b0 >= n_blocks || super_interior(b0 >> 1, n_bytes, n_blocks)) break;
-            } else {
-                b0 = special_candidate(blockIdx.x, n_blocks);
-                if (b0 >= n_blocks || !special_block(b0, n_bytes)) break;
-            }
-        }
-        if (b0 >= n_blocks) break;
-        const uint64_t b1 = (flags & DEC_SPECIAL_ONLY) ? b0 + 1 : (b0 + SYNC_CHUNK < n_blocks ? b0 + SYNC_CHUNK : n_blocks);
-        if (FIRST) prefetch_block(pf, words, b0, n_bytes, front_ok);
-    for (uint64_t b = b0; b < b1; ++b, ++round) {
-        const uint64_t sub_g = b * BLOCK + tid;
-        const bool live = sub_g < n_subs;
-        uint32_t start, exit_rel = 0, count = 0, first_cand = 0;
-        bool need, warm = false;
-        if (FIRST) {
-            start = first_bit;  // exact for the stream's first subsequence; every other one runs in
-            warm = sub_g != 0 || !have_start;
-            need = live;
-            commit_block(m, pf);
-            if (b + 1 < b1) prefetch_block(pf, words, b + 1, n_bytes, front_ok);
-        } else {
-            const uint32_t st = live ? sub_state[sub_g] : 0u;
-            start = st & 0xffu;
-            exit_rel = (st >> 8) & 0xffu;
-            count = st >> 16;
-            need = false;
-            uint32_t *flag = m.scratch + 4 + (round & 1);
-            if (tid == 0) {
-                const uint32_t in = (b == 0) ? (have_start ? first_bit : start) : blk_exit[b - 1];
-                // a range whose start is still unknown and whose first block gave up: run in again
-                warm = b == 0 && !have_start && start == 0xffu;
-                need = warm || in != start;
-                first_cand = in;
-                *flag = need;
-            }
-            __syncthreads();
-            if (!*flag) continue;
-            if (tid == 0) *changed = 1;
-            if (!tables_staged) {
-                stage_tables(m, tb);
-                tables_staged = true;
-            }
-            prefetch_block(pf, words, b, n_bytes, front_ok);
-            commit_block(m, pf);
+    const uint64_t b = window_block(flags, n_bytes, n_blocks);
+    if (b == NO_BLOCK) return;
+    const uint64_t sub_g = b * BLOCK + tid;
+    const bool live = sub_g < n_subs;
+    uint32_t start, exit_rel = 0, count = 0, first_cand = 0;
+    bool need, warm = false;
+    if (FIRST) {
+        start = first_bit;  // exact for the stream's first subsequence; every other one runs in
+        warm = sub_g != 0 || !have_start;
+        need = live;
+    } else {
+        const SubResult st = unpack_state(live ? sub_state[sub_g] : 0u);
+        start = st.start_rel;
+        exit_rel = st.exit_rel;
+        count = st.count;
+        need = false;
+        if (tid == 0) {
+            const uint32_t in = (b == 0) ? (have_start ? first_bit : start) : blk_exit[b - 1];
+            // a range whose start is still unknown and whose first block gave up: run in again
+            warm = b == 0 && !have_start && start == 0xffu;
+            need = warm || in != start;
+            first_cand = in;
+            m.scratch[4] = need;
         }
         __syncthreads();
+        if (!m.scratch[4]) return;  // a repair sweep copies the tables and the block only if the block needs repair
+        if (tid == 0) *changed = 1;
+    }
+    stage_tables(m, tb);
+    stage_block(m, words, b, n_bytes, front_ok);
+    __syncthreads();
 
-        const uint32_t lim = block_limit(n_bytes, b);
-        // `start` is always the start that (exit_rel, count) belong to; `cand` is the start
-        // the predecessor's exit asks for.  Only a walk moves cand into start, so whatever
-        // is stored -- also after giving up -- is self-consistent per lane.
-        uint32_t cand = (!FIRST && tid == 0) ? first_cand : start;
-        for (uint32_t trip = 0;; ++trip) {
-            if (trip == max_trips) {
-                // Codes that do not self-synchronise (near-fixed-length ones) would crawl
-                // one lane per trip: give up on this block for now.  The first sweep counts
-                // such blocks so that the host can pick the exhaustive path (k_dec_maps
-                // ...); a start of 0xff makes any later sweep redo the block.
-                if (tid == 0) {
-                    if (FIRST) atomicAdd(changed + 1, 1u);
-                    else *changed = 1;
-                    start = 0xffu;
-                }
-                break;
+    const uint32_t lim = block_limit(n_bytes, b);
+    // `start` is always the start that (exit_rel, count) belong to; `cand` is the start
+    // the predecessor's exit asks for.  Only a walk moves cand into start, so whatever
+    // is stored -- also after giving up -- is self-consistent per lane.
+    uint32_t cand = (!FIRST && tid == 0) ? first_cand : start;
+    for (uint32_t trip = 0;; ++trip) {
+        if (trip == max_trips) {
+            // Codes that do not self-synchronise (near-fixed-length ones) would crawl
+            // one lane per trip: give up on this block for now.  The first sweep counts
+            // such blocks so that the host can pick the exhaustive path (k_dec_maps
+            // ...); a start of 0xff makes any later sweep redo the block.
+            if (tid == 0) {
+                if (FIRST) atomicAdd(changed + 1, 1u);
+                else *changed = 1;
+                start = 0xffu;
             }
-            if (need) {
-                SubResult r;
-                if (lim != 0xffffffffu) {  // workgroup-uniform: the stream ends in this block
-                    r = warm ? walk_subsequence<0, true, true>(m, tb, tid, 0, lim, 0, 0, 0) : walk_subsequence<0, true, false>(m, tb, tid, cand, lim, 0, 0, 0);
-                } else if (warm) {
-                    r = walk_subsequence<0, false, true>(m, tb, tid, 0, lim, 0, 0, 0);
-                } else {
-                    r = walk_subsequence<0, false, false>(m, tb, tid, cand, lim, 0, 0, 0);
-                }
-                start = r.start_rel;
-                exit_rel = r.exit_rel;
-                count = r.count;
-                warm = false;
-            }
-            m.exits[tid] = exit_rel;
-            __syncthreads();
-            need = false;
-            if (tid > 0 && live) {
-                cand = m.exits[tid - 1];
-                need = cand != start;
-            }
-            if (!__syncthreads_or(need)) break;
+            break;
         }
-        if (live) sub_state[sub_g] = start | (exit_rel << 8) | (count << 16);
-        uint32_t total;
-        block_exclusive_scan(live ? count : 0u, m.scratch, &total);
-        if (tid == 0) blk_count[b] = total;
-        // exit of the last live subsequence of this block
-        const uint64_t last_live = (n_subs - b * BLOCK >= BLOCK) ? BLOCK - 1 : (n_subs - b * BLOCK - 1);
-        if (tid == static_cast<int>(last_live)) blk_exit[b] = exit_rel;
+        if (need) {
+            SubResult r;
+            if (lim != 0xffffffffu) {  // workgroup-uniform: the stream ends in this block
+                r = warm ? walk_subsequence<0, true, true>(m, tb, tid, 0, lim, 0, 0, 0) : walk_subsequence<0, true, false>(m, tb, tid, cand, lim, 0, 0, 0);
+            } else if (warm) {
+                r = walk_subsequence<0, false, true>(m, tb, tid, 0, lim, 0, 0, 0);
+            } else {
+                r = walk_subsequence<0, false, false>(m, tb, tid, cand, lim, 0, 0, 0);
+            }
+            start = r.start_rel;
+            exit_rel = r.exit_rel;
+            count = r.count;
+            warm = false;
+        }
+        m.exits[tid] = exit_rel;
+        __syncthreads();
+        need = false;
+        if (tid > 0 && live) {
+            cand = m.exits[tid - 1];
+            need = cand != start;
+        }
+        if (!__syncthreads_or(need)) break;
     }
-    }
+    publish_block(sub_state, blk_exit, blk_count, m.scratch, b, live_lanes(n_subs, b), start, exit_rel, count);
 }
 
 // ---- exhaustive synchronisation -----------------------------------------------------
@@ -426,24 +474,36 @@ __global__ __launch_bounds__(BLOCK) void k_dec_sync(const uint32_t *__restrict__
 // sequential chains over LDS-resident maps instead of sweeps over the stream.
 // Cost: n_starts + 1 walks per subsequence, independent of the data.
 
+// Through n consecutive 32-byte maps, entered at sidx: the entry the last one leaves by.  The recording form also notes
+// the entry into every map: inputs[i] = entry into map i.
+__device__ __forceinline__ uint32_t chain_maps(const uint8_t *maps, uint32_t n, uint32_t sidx) {
+    for (uint32_t i = 0; i < n; ++i) sidx = maps[i * 32 + sidx];
+    return sidx;
+}
+template <typename T>
+__device__ __forceinline__ uint32_t chain_maps(const uint8_t *maps, uint32_t n, uint32_t sidx, T *inputs) {
+    for (uint32_t i = 0; i < n; ++i) {
+        inputs[i] = static_cast<T>(sidx);
+        sidx = maps[i * 32 + sidx];
+    }
+    return sidx;
+}
+
 // X1: lane maps (stride map_stride bytes per subsequence) and the block's composed map.
 __global__ __launch_bounds__(BLOCK) void k_dec_maps(const uint32_t *__restrict__ words, uint64_t n_bytes, uint32_t first_bit,
                                                     uint64_t n_subs, DecodeTables tb, uint32_t n_starts, uint32_t map_stride,
-                                                    uint8_t *__restrict__ lane_maps, uint8_t *__restrict__ blk_maps, uint32_t special_only,
+                                                    uint8_t *__restrict__ lane_maps, uint8_t *__restrict__ blk_maps, uint32_t mode,
                                                     uint32_t have_start) {
     // have_start: the first subsequence starts exactly at first_bit (a stream's beginning, or a
     // range whose start is known): its map is constant.  Otherwise (a range of a stream split
     // over GPUs, et_decode_range_maps) it is a subsequence like any other.
     const DecodeSmem m = carve_decode_smem(tb);
     const int tid = threadIdx.x;
-    const uint32_t n_blocks_all = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
-    // special_only: grid 3, the stream's first/last blocks (k_dec_maps_reg has the rest)
-    const uint64_t b = special_only ? special_candidate(blockIdx.x, n_blocks_all) : blockIdx.x;
-    if (special_only && (b >= n_blocks_all || !special_block(b, n_bytes))) return;
+    // mode DEC_SPECIAL_ONLY: the stream's first/last blocks (k_dec_maps_reg has the rest)
+    const uint64_t b = window_block(mode, n_bytes, static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK));
+    if (b == NO_BLOCK) return;
     stage_tables(m, tb);
-    Prefetch pf;
-    prefetch_block(pf, words, b, n_bytes);
-    commit_block(m, pf);
+    stage_block(m, words, b, n_bytes);
     __syncthreads();
 
     const uint64_t sub_g = b * BLOCK + tid;
@@ -466,11 +526,9 @@ __global__ __launch_bounds__(BLOCK) void k_dec_maps(const uint32_t *__restrict__
         for (uint32_t k = 0; k < map_stride; k += 8)
             *reinterpret_cast<uint2 *>(lane_maps + sub_g * map_stride + k) = *reinterpret_cast<const uint2 *>(maps + tid * 32 + k);
     }
-    const uint32_t n_live = static_cast<uint32_t>(n_subs - b * BLOCK >= BLOCK ? BLOCK : n_subs - b * BLOCK);
     if (tid < 32) {
         uint32_t sidx = tid;
-        if (static_cast<uint32_t>(tid) < n_starts || (b == 0 && have_start))
-            for (uint32_t i = 0; i < n_live; ++i) sidx = maps[i * 32 + sidx];
+        if (static_cast<uint32_t>(tid) < n_starts || (b == 0 && have_start)) sidx = chain_maps(maps, live_lanes(n_subs, b), sidx);
         blk_maps[b * 32 + tid] = static_cast<uint8_t>(sidx);
     }
 }
@@ -485,11 +543,7 @@ __global__ __launch_bounds__(BLOCK) void k_dec_compose(const uint8_t *__restrict
     for (uint32_t i = threadIdx.x; i < count * 2; i += BLOCK)
         reinterpret_cast<uint4 *>(sm)[i] = reinterpret_cast<const uint4 *>(maps_in + static_cast<uint64_t>(first) * 32)[i];
     __syncthreads();
-    if (threadIdx.x < 32) {
-        uint32_t sidx = threadIdx.x;
-        for (uint32_t i = 0; i < count; ++i) sidx = sm[i * 32 + sidx];
-        maps_out[g * 32 + threadIdx.x] = static_cast<uint8_t>(sidx);
-    }
+    if (threadIdx.x < 32) maps_out[g * 32 + threadIdx.x] = static_cast<uint8_t>(chain_maps(sm, count, threadIdx.x));
 }
 
 // inputs[i] = input of map i, for the maps [g*256, g*256+256) given the group's input
@@ -509,14 +563,7 @@ __global__ __launch_bounds__(BLOCK) void k_dec_chain(const uint8_t *__restrict__
         for (uint32_t i = threadIdx.x; i < count * 2; i += BLOCK)
             reinterpret_cast<uint4 *>(sm)[i] = reinterpret_cast<const uint4 *>(maps + static_cast<uint64_t>(first) * 32)[i];
         __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t sidx = carry;
-            for (uint32_t i = 0; i < count; ++i) {
-                s_in[i] = static_cast<uint8_t>(sidx);
-                sidx = sm[i * 32 + sidx];
-            }
-            carry = sidx;
-        }
+        if (threadIdx.x == 0) carry = chain_maps(sm, count, carry, s_in);
         __syncthreads();
         if (threadIdx.x < count) inputs[first + threadIdx.x] = s_in[threadIdx.x];
     }
@@ -528,16 +575,13 @@ __global__ __launch_bounds__(BLOCK) void k_dec_resolve(const uint32_t *__restric
                                                        uint64_t n_subs, DecodeTables tb, uint32_t map_stride,
                                                        const uint8_t *__restrict__ lane_maps, const uint8_t *__restrict__ blk_in,
                                                        uint32_t *__restrict__ sub_state, uint32_t *__restrict__ blk_exit,
-                                                       uint32_t *__restrict__ blk_count, uint32_t special_only, uint32_t const_first) {
+                                                       uint32_t *__restrict__ blk_count, uint32_t mode, uint32_t const_first) {
     const DecodeSmem m = carve_decode_smem(tb);
     const int tid = threadIdx.x;
-    const uint32_t n_blocks_all = static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK);
-    const uint64_t b = special_only ? special_candidate(blockIdx.x, n_blocks_all) : blockIdx.x;  // as k_dec_maps
-    if (special_only && (b >= n_blocks_all || !special_block(b, n_bytes))) return;
+    const uint64_t b = window_block(mode, n_bytes, static_cast<uint32_t>((n_subs + BLOCK - 1) / BLOCK));  // as k_dec_maps
+    if (b == NO_BLOCK) return;
     stage_tables(m, tb);
-    Prefetch pf;
-    prefetch_block(pf, words, b, n_bytes);
-    commit_block(m, pf);
+    stage_block(m, words, b, n_bytes);
     const uint64_t sub_g = b * BLOCK + tid;
     const bool live = sub_g < n_subs;
     uint8_t *maps = m.stage;  // [BLOCK][32]
@@ -545,15 +589,17 @@ __global__ __launch_bounds__(BLOCK) void k_dec_resolve(const uint32_t *__restric
         for (uint32_t k = 0; k < map_stride; k += 8)
             *reinterpret_cast<uint2 *>(maps + tid * 32 + k) = *reinterpret_cast<const uint2 *>(lane_maps + sub_g * map_stride + k);
     __syncthreads();
-    const uint32_t n_live = static_cast<uint32_t>(n_subs - b * BLOCK >= BLOCK ? BLOCK : n_subs - b * BLOCK);
+    const uint32_t n_live = live_lanes(n_subs, b);
     if (tid == 0) {
-        uint32_t sidx = b == 0 ? first_bit : blk_in[b];
-        for (uint32_t i = 0; i < n_live; ++i) {
-            m.exits[i] = sidx;
+        uint32_t sidx = b == 0 ? first_bit : blk_in[b], first = 0;
+        if (b == 0 && const_first) {
             // the stream's first subsequence has a constant map, of which only the first
             // map_stride entries were stored; first_bit may lie beyond them
-            sidx = maps[i * 32 + ((b == 0 && i == 0 && const_first) ? 0u : sidx)];
+            m.exits[0] = sidx;
+            sidx = maps[0];
+            first = 1;
         }
+        chain_maps(maps + first * 32, n_live - first, sidx, m.exits + first);
     }
     __syncthreads();
     const uint32_t lim = block_limit(n_bytes, b);
@@ -564,12 +610,8 @@ __global__ __launch_bounds__(BLOCK) void k_dec_resolve(const uint32_t *__restric
                                                : walk_subsequence<0, false, false>(m, tb, tid, start, lim, 0, 0, 0);
         exit_rel = r.exit_rel;
         count = r.count;
-        sub_state[sub_g] = start | (exit_rel << 8) | (count << 16);
     }
-    uint32_t total;
-    block_exclusive_scan(live ? count : 0u, m.scratch, &total);
-    if (tid == 0) blk_count[b] = total;
-    if (tid == static_cast<int>(n_live - 1)) blk_exit[b] = exit_rel;
+    publish_block(sub_state, blk_exit, blk_count, m.scratch, b, n_live, start, exit_rel, count);
 }
 
 // ---- register-window walk (interior blocks) ----------------------------------------------
@@ -582,25 +624,8 @@ __global__ __launch_bounds__(BLOCK) void k_dec_resolve(const uint32_t *__restric
 // `sh` stays in [1, 32], then sh -= 32.  No rotation, no window addressing, no bitstream
 // in LDS.  Only the last word of a stretch needs the multi/single phase split.  The walk
 // state is one packed register and table entries are added to it (walk_steps, walk_write).
-// The slow path's search for a code longer than the first-level table (as long_code, with
-// every table in global memory).
-__device__ __forceinline__ uint32_t long_code_flat(const uint16_t *sub, const uint32_t *longc, uint32_t n_long, uint32_t bits, uint32_t e,
-                                                  uint32_t window) {
-    const uint32_t lut_bits = bits & 0xffu, sub_bits = bits >> 8;
-    uint32_t hit = 0;
-    if ((e >> LUT_SUB_SHIFT) & 1u) hit = sub[((e & 0xffu) << sub_bits) | ((window << lut_bits) >> (32 - sub_bits))];
-    if (hit == 0) {
-        for (uint32_t i = 0; i < n_long; ++i) {
-            const uint32_t meta = longc[2 * i + 1], l = meta >> 8;
-            if (((window ^ longc[2 * i]) >> (32 - l)) == 0) {
-                hit = meta;
-                break;
-            }
-        }
-    }
-    return hit;
-}
-
+// The slow path's search for a code longer than the first-level table is long_code_flat with
+// every table in global memory (decode_one_slow_p).
 __host__ __device__ __forceinline__ uint32_t step_table_words(const DecodeTables &tb) {
     return ((1u << tb.step_bits) + (tb.n_step_sub << tb.step_sub_bits) + 3u) & ~3u;
 }
@@ -626,6 +651,13 @@ struct StepWalk {
     const DecodeTables *slow;   // global memory
     uint32_t idx_shift, step_bits, sub_bits, multi_floor;
 };
+__device__ __forceinline__ StepWalk step_walk(const uint32_t *steps, const StepTableArgs &ta) {
+    return StepWalk{steps, ta.slow, 32 - ta.step_bits, ta.step_bits, ta.sub_bits, 64 + ta.step_bits};
+}
+// the table into LDS, 16 bytes per lane and turn (no barrier)
+__device__ __forceinline__ void stage_step_table(uint32_t *steps, const StepTableArgs &ta) {
+    for (uint32_t i = threadIdx.x * 4; i < ta.words; i += BLOCK * 4) *reinterpret_cast<uint4 *>(steps + i) = *reinterpret_cast<const uint4 *>(ta.table + i);
+}
 
 __device__ __attribute__((noinline)) uint32_t decode_one_slow_p(const DecodeTables *tb, uint32_t window) {
     const uint32_t bits = tb->lut_bits | (tb->sub_bits << 8);
@@ -904,13 +936,8 @@ __global__ __launch_bounds__(BLOCK) ET_SYNC_ATTR void k_dec_sync_reg(const uint3
                                                         uint32_t *__restrict__ blk_exit, uint32_t *__restrict__ blk_count,
                                                         uint32_t *__restrict__ changed, uint32_t *__restrict__ ticket, uint32_t max_trips, uint32_t chunk,
                                                         const uint32_t *__restrict__ worklist, const uint32_t *__restrict__ n_work) {
-    // LDS: step table, its second-level tables | exits | scratch
-    uint32_t *steps = reinterpret_cast<uint32_t *>(dec_smem_raw);
-    const uint32_t step_words = ta.words;
-    const StepWalk sw = {steps, ta.slow, 32 - ta.step_bits, ta.step_bits, ta.sub_bits, 64 + ta.step_bits};
-    DecodeSmem m;
-    m.exits = steps + step_words;
-    m.scratch = m.exits + BLOCK;
+    const StepSmem m = carve_step_smem<SS_SYNC>(ta.words);  // step table | exits | scratch
+    const StepWalk sw = step_walk(m.steps, ta);
     const int tid = threadIdx.x;
     bool staged = false;
     // TICKET: resident workgroups draw blocks from a counter and stage the table once;
@@ -941,10 +968,10 @@ __global__ __launch_bounds__(BLOCK) ET_SYNC_ATTR void k_dec_sync_reg(const uint3
             bool need = FIRST, warm = FIRST, skip = false, have_ck = false;
             uint32_t ck[8];
             if (!FIRST) {
-                const uint32_t st = sub_state[sub_g];
-                start = cand = st & 0xffu;
-                exit_rel = (st >> 8) & 0xffu;
-                count = st >> 16;
+                const SubResult st = unpack_state(sub_state[sub_g]);
+                start = cand = st.start_rel;
+                exit_rel = st.exit_rel;
+                count = st.count;
                 if (tid == 0) {
                     cand = blk_exit[b - 1];
                     need = cand != start;
@@ -958,8 +985,7 @@ __global__ __launch_bounds__(BLOCK) ET_SYNC_ATTR void k_dec_sync_reg(const uint3
                 uint32_t W[RW_WORDS];
                 load_window<true>(W, words, sub_g);
                 if (!staged) {
-                    for (uint32_t i = tid * 4; i < step_words; i += BLOCK * 4)
-                        *reinterpret_cast<uint4 *>(steps + i) = *reinterpret_cast<const uint4 *>(ta.table + i);
+                    stage_step_table(m.steps, ta);
                     staged = true;
                     __syncthreads();
                 }
@@ -991,11 +1017,7 @@ __global__ __launch_bounds__(BLOCK) ET_SYNC_ATTR void k_dec_sync_reg(const uint3
                     }
                     if (!__syncthreads_or(need)) break;
                 }
-                sub_state[sub_g] = start | (exit_rel << 8) | (count << 16);
-                uint32_t total;
-                block_exclusive_scan(count, m.scratch, &total);
-                if (tid == 0) blk_count[b] = total;
-                if (tid == BLOCK - 1) blk_exit[b] = exit_rel;
+                publish_block(sub_state, blk_exit, blk_count, m.scratch, b, BLOCK, start, exit_rel, count);
             }
         }
         if (!TICKET && !worklist) break;
@@ -1009,13 +1031,12 @@ __global__ __launch_bounds__(BLOCK) ET_SYNC_ATTR void k_dec_sync_reg2(const uint
                                                                      uint32_t *__restrict__ blk_exit, uint32_t *__restrict__ blk_count,
                                                                      uint32_t *__restrict__ changed, uint32_t *__restrict__ ticket,
                                                                      uint32_t max_trips, uint32_t chunk) {
-    uint32_t *steps = reinterpret_cast<uint32_t *>(dec_smem_raw);
-    const StepWalk sw = {steps, ta.slow, 32 - ta.step_bits, ta.step_bits, ta.sub_bits, 64 + ta.step_bits};
-    uint32_t *exits = steps + ta.words;
-    uint32_t *scratch = exits + BLOCK;
+    const StepSmem m = carve_step_smem<SS_SYNC>(ta.words);
+    const StepWalk sw = step_walk(m.steps, ta);
+    uint32_t *exits = m.exits, *scratch = m.scratch;
     const int tid = threadIdx.x;
     const uint32_t n_super = n_blocks / 2;
-    for (uint32_t i = tid * 4; i < ta.words; i += BLOCK * 4) *reinterpret_cast<uint4 *>(steps + i) = *reinterpret_cast<const uint4 *>(ta.table + i);
+    stage_step_table(m.steps, ta);
     for (uint64_t sb = 0, sb_end = 0;; ++sb) {
         __syncthreads();  // table staged (first trip); everybody is done with scratch and exits
         if (sb >= sb_end) {
@@ -1052,8 +1073,9 @@ __global__ __launch_bounds__(BLOCK) ET_SYNC_ATTR void k_dec_sync_reg2(const uint
                 start = cand;
             }
         }
-        sub_state[2 * q] = start | (r.exit1 << 8) | (r.count1 << 16);
-        sub_state[2 * q + 1] = r.exit1 | (r.exit2 << 8) | (r.count2 << 16);
+        // (its own publish_block: two blocks from one scan, a lane's two subsequences each)
+        sub_state[2 * q] = pack_state(start, r.exit1, r.count1);
+        sub_state[2 * q + 1] = pack_state(r.exit1, r.exit2, r.count2);
         uint32_t total;
         const uint32_t before = block_exclusive_scan(r.count1 + r.count2, scratch, &total);
         if (tid == BLOCK / 2) {  // symbols of lanes 0..127 = first block of the pair
@@ -1083,12 +1105,12 @@ __global__ __launch_bounds__(BLOCK) void k_dec_maps_reg(const uint32_t *__restri
                                                         uint8_t *__restrict__ blk_maps) {
     const uint64_t b = blockIdx.x;
     if (b >= n_blocks || special_block(b, n_bytes)) return;
-    uint32_t *steps = reinterpret_cast<uint32_t *>(dec_smem_raw);
-    uint8_t *maps = reinterpret_cast<uint8_t *>(steps + ta.words);
-    const StepWalk sw = {steps, ta.slow, 32 - ta.step_bits, ta.step_bits, ta.sub_bits, 64 + ta.step_bits};
+    const StepSmem m = carve_step_smem<SS_EXIT_MAPS>(ta.words);
+    uint8_t *maps = m.maps;
+    const StepWalk sw = step_walk(m.steps, ta);
     const int tid = threadIdx.x;
     const uint64_t sub_g = b * BLOCK + tid;
-    for (uint32_t i = tid * 4; i < ta.words; i += BLOCK * 4) *reinterpret_cast<uint4 *>(steps + i) = *reinterpret_cast<const uint4 *>(ta.table + i);
+    stage_step_table(m.steps, ta);
     uint32_t W[RW_WORDS], ck[8];
     load_window<false>(W, words, sub_g);
     __syncthreads();
@@ -1103,8 +1125,7 @@ __global__ __launch_bounds__(BLOCK) void k_dec_maps_reg(const uint32_t *__restri
         *reinterpret_cast<uint2 *>(lane_maps + sub_g * map_stride + k) = *reinterpret_cast<const uint2 *>(maps + tid * 32 + k);
     if (tid < 32) {
         uint32_t sidx = tid;
-        if (static_cast<uint32_t>(tid) < n_starts)
-            for (uint32_t i = 0; i < BLOCK; ++i) sidx = maps[i * 32 + sidx];
+        if (static_cast<uint32_t>(tid) < n_starts) sidx = chain_maps(maps, BLOCK, sidx);
         blk_maps[b * 32 + tid] = static_cast<uint8_t>(sidx);
     }
 }
@@ -1115,34 +1136,22 @@ __global__ __launch_bounds__(BLOCK) void k_dec_resolve_reg(const uint32_t *__res
                                                            uint32_t *__restrict__ blk_exit, uint32_t *__restrict__ blk_count) {
     const uint64_t b = blockIdx.x;
     if (b >= n_blocks || special_block(b, n_bytes)) return;
-    uint32_t *steps = reinterpret_cast<uint32_t *>(dec_smem_raw);
-    uint8_t *maps = reinterpret_cast<uint8_t *>(steps + ta.words);
-    uint32_t *exits = steps + ta.words + BLOCK * 32 / 4;
-    uint32_t *scratch = exits + BLOCK;
-    const StepWalk sw = {steps, ta.slow, 32 - ta.step_bits, ta.step_bits, ta.sub_bits, 64 + ta.step_bits};
+    const StepSmem m = carve_step_smem<SS_EXIT_MAPS>(ta.words);
+    uint8_t *maps = m.maps;
+    const StepWalk sw = step_walk(m.steps, ta);
     const int tid = threadIdx.x;
     const uint64_t sub_g = b * BLOCK + tid;
-    for (uint32_t i = tid * 4; i < ta.words; i += BLOCK * 4) *reinterpret_cast<uint4 *>(steps + i) = *reinterpret_cast<const uint4 *>(ta.table + i);
+    stage_step_table(m.steps, ta);
     for (uint32_t k = 0; k < map_stride; k += 8)
         *reinterpret_cast<uint2 *>(maps + tid * 32 + k) = *reinterpret_cast<const uint2 *>(lane_maps + sub_g * map_stride + k);
     uint32_t W[RW_WORDS], ck[8];
     load_window<false>(W, words, sub_g);
     __syncthreads();
-    if (tid == 0) {
-        uint32_t sidx = blk_in[b];
-        for (uint32_t i = 0; i < BLOCK; ++i) {
-            exits[i] = sidx;
-            sidx = maps[i * 32 + sidx];
-        }
-    }
+    if (tid == 0) chain_maps(maps, BLOCK, blk_in[b], m.exits);
     __syncthreads();
-    const uint32_t start = exits[tid];
+    const uint32_t start = m.exits[tid];
     const SubResult r = walk_steps<false>(sw, W, start, ck);
-    sub_state[sub_g] = start | (r.exit_rel << 8) | (r.count << 16);
-    uint32_t total;
-    block_exclusive_scan(r.count, scratch, &total);
-    if (tid == 0) blk_count[b] = total;
-    if (tid == BLOCK - 1) blk_exit[b] = r.exit_rel;
+    publish_block(sub_state, blk_exit, blk_count, m.scratch, b, BLOCK, start, r.exit_rel, r.count);
 }
 
 // The write walk over a lane's registers (et_kernels.h WSTEP_*): as walk_steps, with the
@@ -1237,7 +1246,38 @@ __device__ __forceinline__ void walk_write(const StepWalk &sw, const uint8_t *sy
 #undef ET_F
 }
 
-// D3 for interior blocks (tickets of WRITE_CHUNK blocks, as k_dec_write).
+// Where a block's symbols go.  They are staged in LDS so that the workgroup's contiguous output range leaves as 16-byte
+// stores: stage positions are `phase + symbol index`, position j maps to out_base[j], and the positions [0, end) are
+// flushed in windows of DEC_STAGE_BYTES.  one_window (the usual case): they fit one window and none is clamped away.
+struct OutWindow {
+    uint8_t *out_base;
+    uint32_t phase, end;  // stage position of the first symbol (out offset & 15); one past the last symbol kept
+    bool one_window;
+};
+__device__ __forceinline__ OutWindow out_window(uint8_t *__restrict__ out, uint64_t o0, uint32_t block_total, uint64_t n_symbols) {
+    uint64_t o1 = o0 + block_total;
+    if (o1 > n_symbols) o1 = n_symbols;
+    const uint32_t n_out = static_cast<uint32_t>(o1 - o0);
+    OutWindow ow;
+    ow.phase = static_cast<uint32_t>(o0 & 15);
+    ow.out_base = out + (o0 - ow.phase);
+    ow.end = ow.phase + n_out;
+    ow.one_window = ow.phase + block_total <= DEC_STAGE_BYTES && n_out == block_total;
+    return ow;
+}
+// stage positions [win, win_hi) of the window that begins at win -> out: 16-byte stores inside, bytes at both edges
+__device__ __forceinline__ void flush_stage_window(const OutWindow &ow, const uint8_t *stage, uint32_t win, uint32_t win_hi) {
+    const uint32_t lo_valid = max(win, ow.phase);  // first stage position holding a symbol in this window
+    for (uint32_t g = win + threadIdx.x * 16; g < win_hi; g += BLOCK * 16) {
+        if (g >= lo_valid && g + 16 <= win_hi) {
+            *reinterpret_cast<uint4 *>(ow.out_base + g) = *reinterpret_cast<const uint4 *>(stage + (g - win));
+        } else {
+            for (uint32_t k = max(g, lo_valid); k < min(g + 16, win_hi); ++k) ow.out_base[k] = stage[k - win];
+        }
+    }
+}
+
+// D3 for interior blocks, by tickets of WRITE_CHUNK blocks (et_kernels.h).
 __global__ __launch_bounds__(BLOCK) void k_dec_write_reg(const uint32_t *__restrict__ words, uint64_t n_bytes, uint32_t n_blocks,
                                                          StepTableArgs ta, const uint8_t *__restrict__ sym_len_g, const uint32_t *__restrict__ sub_state,
                                                          const unsigned long long *__restrict__ blk_off, uint64_t n_symbols,
@@ -1251,19 +1291,14 @@ __global__ __launch_bounds__(BLOCK) void k_dec_write_reg(const uint32_t *__restr
     // output in exactly these cases and writes again once the state is final.  (Walking from the marker would send the packed walk state's
     // address field through the LDS tables: a stream with long runs of one code hung this kernel.)
     if (void_flags && !dec_state_final(void_flags[1], void_flags[2], n_blocks)) return;
-    // LDS: step table, its second-level tables | code lengths | scratch | stage
-    uint32_t *wsteps = reinterpret_cast<uint32_t *>(dec_smem_raw);
-    const uint32_t step_words = ta.words;
-    const StepWalk sw = {wsteps, ta.slow, 32 - ta.step_bits, ta.step_bits, ta.sub_bits, 64 + ta.step_bits};
-    uint8_t *sym_len = reinterpret_cast<uint8_t *>(wsteps + step_words);
-    uint32_t *scratch = wsteps + step_words + 64;
-    const uint32_t stage_off = (step_words + 64 + 8) * sizeof(uint32_t);
-    uint8_t *smem8 = reinterpret_cast<uint8_t *>(dec_smem_raw);
-    uint8_t *stage = smem8 + stage_off;
+    const StepSmem m = carve_step_smem<SS_WRITE>(ta.words);  // step table | code lengths | scratch | stage
+    const StepWalk sw = step_walk(m.steps, ta);
+    uint8_t *sym_len = m.sym_len, *smem8 = dec_smem_raw, *stage = m.stage;
+    uint32_t *scratch = m.scratch;
+    const uint32_t stage_off = m.stage_off;
     const uint32_t lds_stage = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_u8 *)stage));  // the stage's LDS address
     const int tid = threadIdx.x;
-    for (uint32_t i = tid * 4; i < step_words; i += BLOCK * 4)
-        *reinterpret_cast<uint4 *>(wsteps + i) = *reinterpret_cast<const uint4 *>(ta.table + i);
+    stage_step_table(m.steps, ta);
     sym_len[tid] = sym_len_g[tid];
     for (;;) {
         __syncthreads();  // tables staged (first trip); everybody is done with scratch[7] and the stage
@@ -1277,36 +1312,24 @@ __global__ __launch_bounds__(BLOCK) void k_dec_write_reg(const uint32_t *__restr
             const uint64_t o0 = blk_off[b];
             if (o0 >= n_symbols) break;  // pad bits decoded past the declared length; offsets only grow from here
             const uint64_t sub_g = b * BLOCK + tid;
-            const uint32_t st = sub_state[sub_g];
-            const uint32_t start = st & 31u, count = st >> 16;  // (a start is < 32 in a settled state; masked so that nothing else can reach the walk)
+            const SubResult st = unpack_state(sub_state[sub_g]);
+            const uint32_t start = st.start_rel & 31u, count = st.count;  // (a start is < 32 in a settled state; masked so that nothing else can reach the walk)
             uint32_t W[RW_WORDS];
             load_window<false>(W, words, sub_g);
             uint32_t block_total;
             const uint32_t my_off = block_exclusive_scan(count, scratch, &block_total);  // its barrier also separates the blocks' use of the stage
 
-            uint64_t o1 = o0 + block_total;
-            if (o1 > n_symbols) o1 = n_symbols;
-            const uint32_t n_out = static_cast<uint32_t>(o1 - o0);
-            const uint32_t phase = static_cast<uint32_t>(o0 & 15);  // stage offset of the first symbol
-            uint8_t *out_base = out + (o0 - phase);
-            const bool one_window = phase + block_total <= DEC_STAGE_BYTES && n_out == block_total;
-            for (uint32_t win = 0; win < phase + n_out; win += DEC_STAGE_BYTES) {
-                const uint32_t win_hi = min(win + DEC_STAGE_BYTES, phase + n_out);
-                const uint32_t my_lo = phase + my_off, my_hi = my_lo + count;
-                if (one_window) {
+            const OutWindow ow = out_window(out, o0, block_total, n_symbols);
+            for (uint32_t win = 0; win < ow.end; win += DEC_STAGE_BYTES) {
+                const uint32_t win_hi = min(win + DEC_STAGE_BYTES, ow.end);
+                const uint32_t my_lo = ow.phase + my_off, my_hi = my_lo + count;
+                if (ow.one_window) {
                     if (count) walk_write<1>(sw, sym_len, smem8, W, start, lds_stage + my_lo - 1u, 0, 0, 0);
                 } else if (my_lo < win_hi && my_hi > win) {
                     walk_write<2>(sw, sym_len, smem8, W, start, my_lo, win, win_hi, stage_off);
                 }
                 __syncthreads();
-                const uint32_t lo_valid = max(win, phase);  // first stage position holding a symbol in this window
-                for (uint32_t g = win + tid * 16; g < win_hi; g += BLOCK * 16) {
-                    if (g >= lo_valid && g + 16 <= win_hi) {
-                        *reinterpret_cast<uint4 *>(out_base + g) = *reinterpret_cast<const uint4 *>(stage + (g - win));
-                    } else {
-                        for (uint32_t k = max(g, lo_valid); k < min(g + 16, win_hi); ++k) out_base[k] = stage[k - win];
-                    }
-                }
+                flush_stage_window(ow, stage, win, win_hi);
                 __syncthreads();
             }
         }
@@ -1315,93 +1338,48 @@ __global__ __launch_bounds__(BLOCK) void k_dec_write_reg(const uint32_t *__restr
 
 // D2 (scan of the workgroup symbol counts) is k_scan_fused above.
 
-// D3: decode every subsequence from its synchronised start and write the symbols.
-// Symbols are staged in LDS so that the workgroup's contiguous output range leaves
-// as 16-byte stores; stage byte j maps to out byte (o0 & ~15) + j.
+// D3: decode every subsequence of the workgroup's ONE block from its synchronised start and write the symbols (OutWindow).
+// mode: which block (window_block); DEC_SPECIAL_ONLY: the interior ones belong to k_dec_write_reg.
 __global__ __launch_bounds__(BLOCK) void k_dec_write(const uint32_t *__restrict__ words, uint64_t n_bytes, uint64_t n_subs,
                                                      uint32_t n_blocks, DecodeTables tb, const uint32_t *__restrict__ sub_state,
                                                      const unsigned long long *__restrict__ blk_off, uint64_t n_symbols,
-                                                     uint8_t *__restrict__ out, uint32_t *__restrict__ ticket, uint32_t special_only,
-                                                     const uint32_t *__restrict__ void_flags) {
+                                                     uint8_t *__restrict__ out, uint32_t mode, const uint32_t *__restrict__ void_flags) {
     if (void_flags && !dec_state_final(void_flags[1], void_flags[2], n_blocks)) return;  // see k_dec_write_reg
+    const uint64_t b = window_block(mode, n_bytes, n_blocks);
+    if (b == NO_BLOCK) return;
+    const uint64_t o0 = blk_off[b];
+    if (o0 >= n_symbols) return;  // pad bits decoded past the declared length
     const DecodeSmem m = carve_decode_smem<false>(tb);
     const int tid = threadIdx.x;
+    const uint64_t sub_g = b * BLOCK + tid;
+    const bool live = sub_g < n_subs;
+    const SubResult st = unpack_state(live ? sub_state[sub_g] : 0u);
+    const uint32_t start = st.start_rel, count = st.count;
+
     stage_tables(m, tb);
-    Prefetch pf;
-    for (bool first_trip = true;; first_trip = false) {  // chunks: see k_dec_sync
-        uint64_t b0;
-        if (WRITE_TICKET && !special_only) {  // (a special-only launch must not eat tickets of k_dec_write_reg)
-            __syncthreads();  // tables staged (first trip); everybody is done with scratch[7] and the stage
-            if (tid == 0) m.scratch[7] = atomicAdd(ticket, WRITE_CHUNK);
-            __syncthreads();
-            b0 = m.scratch[7];
-        } else {
-            if (!first_trip) break;
-            b0 = static_cast<uint64_t>(blockIdx.x) * WRITE_CHUNK;
-            __syncthreads();
-        }
-        if (special_only) {  // one special block per workgroup (grid 3); the interior ones belong to k_dec_write_reg
-            if (!first_trip) break;
-            b0 = special_candidate(blockIdx.x, n_blocks);
-            if (b0 >= n_blocks || !special_block(b0, n_bytes)) break;
-        }
-        if (b0 >= n_blocks) break;
-        const uint64_t b1 = special_only ? b0 + 1 : (b0 + WRITE_CHUNK < n_blocks ? b0 + WRITE_CHUNK : n_blocks);
-        prefetch_block(pf, words, b0, n_bytes);
-    for (uint64_t b = b0; b < b1; ++b) {
-        const uint64_t o0 = blk_off[b];
-        if (o0 >= n_symbols) break;  // pad bits decoded past the declared length; offsets only grow from here
-        const uint64_t sub_g = b * BLOCK + tid;
-        const bool live = sub_g < n_subs;
-        const uint32_t st = live ? sub_state[sub_g] : 0u;
-        const uint32_t start = st & 0xffu, count = live ? (st >> 16) : 0u;
+    stage_block(m, words, b, n_bytes);
+    uint32_t block_total;
+    const uint32_t my_off = block_exclusive_scan(count, m.scratch, &block_total);  // its barrier also covers the staging
 
-        commit_block(m, pf);
-        if (b + 1 < b1) prefetch_block(pf, words, b + 1, n_bytes);
-        uint32_t block_total;
-        const uint32_t my_off = block_exclusive_scan(count, m.scratch, &block_total);  // its barrier also covers the staging
-
-        uint64_t o1 = o0 + block_total;
-        if (o1 > n_symbols) o1 = n_symbols;
-        const uint32_t n_out = static_cast<uint32_t>(o1 - o0);
-        const uint32_t phase = static_cast<uint32_t>(o0 & 15);  // stage offset of the first symbol
-        const uint32_t lim = block_limit(n_bytes, b);
-        uint8_t *out_base = out + (o0 - phase);
-
-        // stage positions are `phase + symbol index`; windows of DEC_STAGE_BYTES of them.
-        // Usual case: the block's symbols fit one window and none is clamped away.
-        const bool one_window = phase + block_total <= DEC_STAGE_BYTES && n_out == block_total;
-        for (uint32_t win = 0; win < phase + n_out; win += DEC_STAGE_BYTES) {
-            const uint32_t win_hi = min(win + DEC_STAGE_BYTES, phase + n_out);
-            const uint32_t my_lo = phase + my_off, my_hi = my_lo + count;
-            if (one_window && lim == 0xffffffffu) {
-                if (live && count) walk_subsequence<1, false, false>(m, tb, tid, start, lim, my_lo, 0, 0);
-            } else if (live && my_lo < win_hi && my_hi > win) {
-                walk_subsequence<2, true, false>(m, tb, tid, start, lim, my_lo, win, win_hi);
-            }
-            __syncthreads();
-            const uint32_t lo_valid = max(win, phase);  // first stage position holding a symbol in this window
-            for (uint32_t g = win + tid * 16; g < win_hi; g += BLOCK * 16) {
-                if (g >= lo_valid && g + 16 <= win_hi) {
-                    *reinterpret_cast<uint4 *>(out_base + g) = *reinterpret_cast<const uint4 *>(m.stage + (g - win));
-                } else {
-                    for (uint32_t k = max(g, lo_valid); k < min(g + 16, win_hi); ++k) out_base[k] = m.stage[k - win];
-                }
-            }
-            __syncthreads();
+    const OutWindow ow = out_window(out, o0, block_total, n_symbols);
+    const uint32_t lim = block_limit(n_bytes, b);
+    for (uint32_t win = 0; win < ow.end; win += DEC_STAGE_BYTES) {
+        const uint32_t win_hi = min(win + DEC_STAGE_BYTES, ow.end);
+        const uint32_t my_lo = ow.phase + my_off, my_hi = my_lo + count;
+        if (ow.one_window && lim == 0xffffffffu) {
+            if (live && count) walk_subsequence<1, false, false>(m, tb, tid, start, lim, my_lo, 0, 0);
+        } else if (live && my_lo < win_hi && my_hi > win) {
+            walk_subsequence<2, true, false>(m, tb, tid, start, lim, my_lo, win, win_hi);
         }
-    }
+        __syncthreads();
+        flush_stage_window(ow, m.stage, win, win_hi);
+        __syncthreads();
     }
 }
 
 // --------------------------------------------------------------------------------
 // launch wrappers
 // --------------------------------------------------------------------------------
-static inline size_t decode_smem_bytes(const DecodeTables &tb, bool with_stage, bool with_exits = true, bool with_stream = true) {
-    const uint32_t sub_w = (((tb.n_sub << tb.sub_bits) + 7u) & ~7u) / 2;
-    return ((with_stream ? DEC_SDATA_WORDS : 0) + (1u << tb.lut_bits) + sub_w + 64 + (with_exits ? BLOCK : 0) + 8) * sizeof(uint32_t) + (with_stage ? DEC_STAGE_BYTES + 16 : 0);
-}
-
 // Interior blocks take the register-window kernels; the LDS-window kernels keep the stream's first
 // and last blocks (and streams of nothing else).
 static bool use_reg_kernels(uint32_t n_blocks) { return n_blocks > 3; }
@@ -1563,44 +1541,52 @@ static void join_special(const SideLane *side, hipStream_t stream) {
 
 void launch_dec_sync(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint32_t iter, uint32_t max_trips, uint32_t flags, bool listed,
                      const SideLane *side, bool ticket_is_zero, KernelEvents ev) {
-    uint32_t *changed = s.flag + FLAG_CHANGED, *ticket = s.flag + FLAG_SYNC_TICKET, *worklist = listed ? s.worklist : nullptr, *n_work = listed ? s.flag + FLAG_WORK_COUNT : nullptr;
-    const uint32_t n_chunks = (s.n_blocks + SYNC_CHUNK - 1) / SYNC_CHUNK;
+    uint32_t *changed = s.flag + FLAG_CHANGED, *ticket = s.flag + FLAG_SYNC_TICKET;
+    // the LDS-window kernel on stream `on`: `grid` workgroups of one block each (mode: which blocks, window_block)
     const size_t smem = decode_smem_bytes(tb, false);
-    if (use_reg_kernels(s.n_blocks)) {
-        const size_t smem_reg = (step_table_words(tb) + BLOCK + 8) * sizeof(uint32_t);
-        constexpr uint32_t chunk = 4;  // blocks per ticket; measured 1 / 4 / 8 / 16
-        if (iter == 0 && s.n_blocks >= 16) {
-            if (!ticket_is_zero) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
-            constexpr uint32_t chunk2 = 4;  // superblocks per ticket; measured 1 / 2 / 4 / 8 / 16: 0.54 / 0.37 / 0.35 / 0.37 / 0.44 ms
-            fork_mark(side, stream);
-            ET_LAUNCH_TIMED(k_dec_sync_reg2, dim3(decode_grid(k_dec_sync_reg2, smem_reg, (s.n_blocks / 2 + chunk2 - 1) / chunk2, true)), dim3(BLOCK), smem_reg, stream, ev, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, chunk2);
-            const hipStream_t special = fork_special(side, stream);
-            hipLaunchKernelGGL(k_dec_sync<true>, dim3(8), dim3(BLOCK), smem, special, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY | DEC_SPECIAL_SUPER);
-            join_special(side, stream);
-        } else if (iter == 0) {
-            if (!ticket_is_zero) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
-            fork_mark(side, stream);
-            ET_LAUNCH_TIMED((k_dec_sync_reg<true, true>), dim3(decode_grid(k_dec_sync_reg<true, true>, smem_reg, (s.n_blocks + chunk - 1) / chunk, true)), dim3(BLOCK), smem_reg, stream, ev, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, chunk, static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr));
-            const hipStream_t special = fork_special(side, stream);
-            hipLaunchKernelGGL(k_dec_sync<true>, dim3(3), dim3(BLOCK), smem, special, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY);
-            join_special(side, stream);
-        } else {
-            if (worklist) {  // n_work zeroed by the caller
-                hipLaunchKernelGGL(k_dec_check, dim3((s.n_blocks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, s.sub_state, s.blk_exit, s.n_blocks, worklist, n_work);
-                hipLaunchKernelGGL((k_dec_sync_reg<false, false>), dim3(s.n_blocks < 512 ? s.n_blocks : 512), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, 1u, static_cast<const uint32_t *>(worklist), static_cast<const uint32_t *>(n_work));
-            } else {
-                hipLaunchKernelGGL((k_dec_sync_reg<false, false>), dim3(s.n_blocks), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, 1u, static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr));
-            }
-            // (not on the side lane: the fork/join events cost more than these ~5 us)
-            hipLaunchKernelGGL(k_dec_sync<false>, dim3(3), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags | DEC_SPECIAL_ONLY);
-        }
+    auto window = [&](auto kernel, uint32_t grid, hipStream_t on, uint32_t mode, KernelEvents e) {
+        ET_LAUNCH_TIMED(kernel, dim3(grid), dim3(BLOCK), smem, on, e, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit,
+                        s.blk_count, changed, max_trips, flags | mode);
+    };
+    if (!use_reg_kernels(s.n_blocks)) {
+        if (iter == 0) window(k_dec_sync<true>, s.n_blocks, stream, 0u, ev);
+        else window(k_dec_sync<false>, s.n_blocks, stream, 0u, KernelEvents{});
         return;
     }
-    if (SYNC_TICKET) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
-    if (iter == 0)
-        ET_LAUNCH_TIMED(k_dec_sync<true>, dim3(decode_grid(k_dec_sync<true>, smem, n_chunks, SYNC_TICKET)), dim3(BLOCK), smem, stream, ev, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags);
-    else
-        hipLaunchKernelGGL(k_dec_sync<false>, dim3(decode_grid(k_dec_sync<false>, smem, n_chunks, SYNC_TICKET)), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, s.n_blocks, tb, s.sub_state, s.blk_exit, s.blk_count, changed, ticket, max_trips, flags);
+    // k_dec_sync_reg on `stream`: by tickets of `chunk` blocks, over the worklist, or (both null) one block per workgroup
+    const size_t smem_reg = step_smem_bytes(step_table_words(tb), SS_SYNC);
+    const StepTableArgs ta = step_table_args(tb);
+    auto reg = [&](auto kernel, uint32_t grid, KernelEvents e, uint32_t chunk, const uint32_t *worklist, const uint32_t *n_work) {
+        ET_LAUNCH_TIMED(kernel, dim3(grid), dim3(BLOCK), smem_reg, stream, e, s.words, s.n_bytes, s.n_blocks, ta, s.sub_state, s.blk_exit, s.blk_count, changed,
+                        ticket, max_trips, chunk, worklist, n_work);
+    };
+    if (iter == 0) {
+        if (!ticket_is_zero) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
+        fork_mark(side, stream);
+        const bool super = s.n_blocks >= 16;  // 512-bit lanes over superblocks of two blocks
+        if (super) {
+            constexpr uint32_t chunk2 = 4;  // superblocks per ticket; measured 1 / 2 / 4 / 8 / 16: 0.54 / 0.37 / 0.35 / 0.37 / 0.44 ms
+            const uint32_t grid = decode_grid(k_dec_sync_reg2, smem_reg, (s.n_blocks / 2 + chunk2 - 1) / chunk2, true);
+            ET_LAUNCH_TIMED(k_dec_sync_reg2, dim3(grid), dim3(BLOCK), smem_reg, stream, ev, s.words, s.n_bytes, s.n_blocks, ta, s.sub_state, s.blk_exit,
+                            s.blk_count, changed, ticket, max_trips, chunk2);
+        } else {
+            constexpr uint32_t chunk = 4;  // blocks per ticket; measured 1 / 4 / 8 / 16
+            reg(k_dec_sync_reg<true, true>, decode_grid(k_dec_sync_reg<true, true>, smem_reg, (s.n_blocks + chunk - 1) / chunk, true), ev, chunk, nullptr, nullptr);
+        }
+        const hipStream_t special = fork_special(side, stream);
+        window(k_dec_sync<true>, super ? 8u : 3u, special, super ? DEC_SPECIAL_ONLY | DEC_SPECIAL_SUPER : DEC_SPECIAL_ONLY, KernelEvents{});
+        join_special(side, stream);
+        return;
+    }
+    if (listed) {  // FLAG_WORK_COUNT zeroed by the caller
+        uint32_t *n_work = s.flag + FLAG_WORK_COUNT;
+        hipLaunchKernelGGL(k_dec_check, dim3((s.n_blocks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, s.sub_state, s.blk_exit, s.n_blocks, s.worklist, n_work);
+        reg(k_dec_sync_reg<false, false>, s.n_blocks < 512 ? s.n_blocks : 512, KernelEvents{}, 1u, s.worklist, n_work);
+    } else {
+        reg(k_dec_sync_reg<false, false>, s.n_blocks, KernelEvents{}, 1u, nullptr, nullptr);
+    }
+    // (not on the side lane: the fork/join events cost more than these ~5 us)
+    window(k_dec_sync<false>, 3u, stream, DEC_SPECIAL_ONLY, KernelEvents{});
 }
 
 // Exhaustive synchronisation (see k_dec_maps).  Workspaces: lane_maps n_subs * stride,
@@ -1608,48 +1594,56 @@ void launch_dec_sync(hipStream_t stream, const DecSpan &s, const DecodeTables &t
 // one per 256 blocks (launch_dec_maps), and, once the input start is known, the way back down
 // and the counting walk (launch_dec_resolve).  A single GPU runs them back to back; ranges of
 // a stream split over GPUs exchange their composed maps in between.
+// (Every caller's tables come from prepare_decode_tables, which always sets tb.steps: the register-window kernels
+// need no test for it.)
 void launch_dec_maps(hipStream_t stream, const DecSpan &s, bool have_start, const DecodeTables &tb, uint32_t n_starts, uint32_t map_stride,
                      uint8_t *lane_maps, uint8_t *blk_maps, uint8_t *grp_maps) {
     const uint32_t n_groups = (s.n_blocks + 255) / 256;
-    const size_t smem = decode_smem_bytes(tb, true);
-    const bool reg = use_reg_kernels(s.n_blocks) && tb.steps != nullptr;
-    const size_t smem_reg = (step_table_words(tb) + BLOCK * 32 / 4 + BLOCK + 8) * sizeof(uint32_t);
-    if (reg) hipLaunchKernelGGL(k_dec_maps_reg, dim3(s.n_blocks), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), n_starts, map_stride, lane_maps, blk_maps);
-    hipLaunchKernelGGL(k_dec_maps, dim3(reg ? 3 : s.n_blocks), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, tb, n_starts, map_stride, lane_maps, blk_maps, reg ? 1u : 0u, have_start ? 1u : 0u);
+    const bool reg = use_reg_kernels(s.n_blocks);
+    if (reg)
+        hipLaunchKernelGGL(k_dec_maps_reg, dim3(s.n_blocks), dim3(BLOCK), step_smem_bytes(step_table_words(tb), SS_EXIT_MAPS), stream, s.words, s.n_bytes,
+                           s.n_blocks, step_table_args(tb), n_starts, map_stride, lane_maps, blk_maps);
+    hipLaunchKernelGGL(k_dec_maps, dim3(reg ? 3 : s.n_blocks), dim3(BLOCK), decode_smem_bytes(tb, true), stream, s.words, s.n_bytes, s.first_bit, s.n_subs, tb,
+                       n_starts, map_stride, lane_maps, blk_maps, reg ? DEC_SPECIAL_ONLY : 0u, have_start ? 1u : 0u);
     hipLaunchKernelGGL(k_dec_compose, dim3(n_groups), dim3(BLOCK), 0, stream, blk_maps, s.n_blocks, grp_maps);
 }
 
 void launch_dec_resolve(hipStream_t stream, const DecSpan &s, bool const_first, const DecodeTables &tb, uint32_t map_stride, const uint8_t *lane_maps,
                         const uint8_t *blk_maps, const uint8_t *grp_maps, uint8_t *blk_in, uint8_t *grp_in) {
     const uint32_t n_groups = (s.n_blocks + 255) / 256;
-    const size_t smem = decode_smem_bytes(tb, true);
-    const bool reg = use_reg_kernels(s.n_blocks) && tb.steps != nullptr;
-    const size_t smem_reg = (step_table_words(tb) + BLOCK * 32 / 4 + BLOCK + 8) * sizeof(uint32_t);
+    const bool reg = use_reg_kernels(s.n_blocks);
     // one workgroup walks all group maps (256 per LDS refill), then every group resolves its blocks
     hipLaunchKernelGGL(k_dec_chain, dim3(1), dim3(BLOCK), 0, stream, grp_maps, n_groups, static_cast<const uint8_t *>(nullptr), s.first_bit, grp_in);
     hipLaunchKernelGGL(k_dec_chain, dim3(n_groups), dim3(BLOCK), 0, stream, blk_maps, s.n_blocks, grp_in, 0u, blk_in);
-    if (reg) hipLaunchKernelGGL(k_dec_resolve_reg, dim3(s.n_blocks), dim3(BLOCK), smem_reg, stream, s.words, s.n_bytes, s.n_blocks, step_table_args(tb), map_stride, lane_maps, blk_in, s.sub_state, s.blk_exit, s.blk_count);
-    hipLaunchKernelGGL(k_dec_resolve, dim3(reg ? 3 : s.n_blocks), dim3(BLOCK), smem, stream, s.words, s.n_bytes, s.first_bit, s.n_subs, tb, map_stride, lane_maps, blk_in, s.sub_state, s.blk_exit, s.blk_count, reg ? 1u : 0u, const_first ? 1u : 0u);
+    if (reg)
+        hipLaunchKernelGGL(k_dec_resolve_reg, dim3(s.n_blocks), dim3(BLOCK), step_smem_bytes(step_table_words(tb), SS_EXIT_MAPS), stream, s.words, s.n_bytes,
+                           s.n_blocks, step_table_args(tb), map_stride, lane_maps, blk_in, s.sub_state, s.blk_exit, s.blk_count);
+    hipLaunchKernelGGL(k_dec_resolve, dim3(reg ? 3 : s.n_blocks), dim3(BLOCK), decode_smem_bytes(tb, true), stream, s.words, s.n_bytes, s.first_bit, s.n_subs, tb,
+                       map_stride, lane_maps, blk_in, s.sub_state, s.blk_exit, s.blk_count, reg ? DEC_SPECIAL_ONLY : 0u, const_first ? 1u : 0u);
 }
 
 void launch_dec_write_fallback(hipStream_t stream, const DecSpan &s, const DecodeTables &tb, uint64_t n_symbols, uint8_t *out, DecFlag ticket_word,
                                const SideLane *side, bool ticket_is_zero, bool speculative, KernelEvents ev) {
-    const uint32_t *words = s.words, *sub_state = s.sub_state, *void_flags = speculative ? s.flag : nullptr;
+    const uint32_t *void_flags = speculative ? s.flag : nullptr;
+    // k_dec_write on stream `on`: `grid` workgroups of one block each (mode: which blocks, window_block)
+    auto window = [&](uint32_t grid, hipStream_t on, uint32_t mode, KernelEvents e) {
+        ET_LAUNCH_TIMED(k_dec_write, dim3(grid), dim3(BLOCK), decode_smem_bytes(tb, true, false), on, e, s.words, s.n_bytes, s.n_subs, s.n_blocks, tb, s.sub_state,
+                        s.blk_off, n_symbols, out, mode, void_flags);
+    };
+    if (!use_reg_kernels(s.n_blocks)) {  // (no ticket: the word stays as it is)
+        window(s.n_blocks, stream, 0u, ev);
+        return;
+    }
     uint32_t *ticket = s.flag + ticket_word;
     if (!ticket_is_zero) (void)hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream);
     const uint32_t n_chunks = (s.n_blocks + WRITE_CHUNK - 1) / WRITE_CHUNK;
-    const size_t smem = decode_smem_bytes(tb, true, false);
-    if (use_reg_kernels(s.n_blocks)) {
-        const size_t smem_reg = (step_table_words(tb) + 64 + 8) * sizeof(uint32_t) + DEC_STAGE_BYTES + 16;
-        fork_mark(side, stream);
-        ET_LAUNCH_TIMED(k_dec_write_reg, dim3(decode_grid(k_dec_write_reg, smem_reg, n_chunks, true)), dim3(BLOCK), smem_reg, stream, ev, words, s.n_bytes, s.n_blocks, step_table_args(tb), tb.sym_len, sub_state, s.blk_off, n_symbols, out, ticket, void_flags);
-        const hipStream_t special = fork_special(side, stream);
-        hipLaunchKernelGGL(k_dec_write, dim3(3), dim3(BLOCK), smem, special, words, s.n_bytes, s.n_subs, s.n_blocks, tb, sub_state, s.blk_off, n_symbols, out, ticket, 1u, void_flags);
-        join_special(side, stream);
-        return;
-    }
-    ET_LAUNCH_TIMED(k_dec_write, dim3(decode_grid(k_dec_write, smem, n_chunks, WRITE_TICKET)), dim3(BLOCK), smem, stream, ev, words, s.n_bytes, s.n_subs, s.n_blocks, tb, sub_state, s.blk_off, n_symbols, out, ticket, 0u, void_flags);
+    const size_t smem_reg = step_smem_bytes(step_table_words(tb), SS_WRITE);
+    fork_mark(side, stream);
+    ET_LAUNCH_TIMED(k_dec_write_reg, dim3(decode_grid(k_dec_write_reg, smem_reg, n_chunks, true)), dim3(BLOCK), smem_reg, stream, ev, s.words, s.n_bytes, s.n_blocks,
+                    step_table_args(tb), tb.sym_len, s.sub_state, s.blk_off, n_symbols, out, ticket, void_flags);
+    const hipStream_t special = fork_special(side, stream);
+    window(3u, special, DEC_SPECIAL_ONLY, KernelEvents{});
+    join_special(side, stream);
 }
-
 
 }  // namespace et

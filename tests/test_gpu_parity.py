@@ -1124,6 +1124,80 @@ def test_fallback_sweeps_and_write_are_what_a_sparse_dictionary_runs(ctx, n):
     assert N.lib().et_decode_path(ctypes.byref(cb.raw), ctypes.byref(p)) == N.ET_OK and p.value == N.ET_PATH_WINDOWS  # (what ran)
 
 
+# Body sizes in bytes at which the round-1 kernels' block bookkeeping changes (a block is 8 KiB): one block and its edges;
+# the last streams of the LDS-window kernels alone and the first with interior blocks; streams that end inside and just
+# beyond the guard words of the block before (one or two special blocks at the end); either side of the 16 blocks from
+# which the first sweep takes superblocks, an odd block left over behind them, and the end cases again.
+_BLK = 8192
+_FALLBACK_EDGE_BYTES = [_BLK - 1, _BLK, _BLK + 1, 3 * _BLK - 1, 3 * _BLK, 3 * _BLK + 1, 3 * _BLK + 16, 3 * _BLK + 17, 3 * _BLK + 24, 3 * _BLK + 25,
+                        4 * _BLK, 15 * _BLK + 5, 16 * _BLK, 16 * _BLK + 1, 16 * _BLK + 17, 16 * _BLK + 25, 17 * _BLK + 1]
+
+
+def _decode_up_then_down(ctx, cb, cases, check_path):
+    """Every case (body bytes, text) decoded on ONE context, ascending and then descending with nothing in between: a
+    ticket or flag word that a larger stream leaves behind is met by a smaller one, and the other way round.  Asserts the
+    symbol count, the bytes, sentinels untouched behind them, and the path (check_path on timings("decode"))."""
+    import torch
+
+    staged = [(torch.from_numpy(np.frombuffer(body, dtype=np.uint8).copy()).cuda(), text) for body, text in cases]
+    out = torch.empty(max(t.size for _, t in cases) + 64, dtype=torch.uint8, device="cuda")
+    ctx.enable_timing(True)
+    try:
+        for d_body, text in staged + staged[::-1]:
+            n = text.size
+            out.fill_(0xA5)
+            assert ctx.decode_body_device(cb, d_body, n, out[: n + 64]) == n, d_body.numel()
+            check_path(ctx.timings("decode"))
+            got = out[: n + 64].cpu().numpy()
+            assert got[:n].tobytes() == text.tobytes(), d_body.numel()
+            assert (got[n:] == 0xA5).all(), d_body.numel()
+    finally:
+        ctx.enable_timing(False)
+
+
+def test_fallback_block_bookkeeping_sparse_dictionary(ctx):
+    """The windows path (sweeps and write of the round-1 kernels) at the body sizes of _FALLBACK_EDGE_BYTES: the first prefix of
+    one text whose packed body has at least that many bytes (the longest code is 16 bits: at most two more)."""
+    import entreepy_amd as E
+
+    O = _oracle()
+    data_t, len_t, syms = _sparse_dictionary()
+    cb = E.Codebook.from_tables(data_t, len_t)
+    rng = np.random.default_rng(17)
+    n_all = 400_000
+    text = syms[np.minimum(rng.integers(0, 300, size=n_all), syms.size - 1) % syms.size].astype(np.uint8)
+    text[rng.random(n_all) < 0.5] = 32  # (the recipe of test_fallback_sweeps_and_write_are_what_a_sparse_dictionary_runs)
+    end_bits = np.cumsum(len_t[text].astype(np.int64))
+    cases = []
+    for t in _FALLBACK_EDGE_BYTES:
+        n = int(np.searchsorted(end_bits, 8 * t - 7)) + 1  # the first prefix that ends in byte t - 1 or later
+        body, end = O.pack_body(data_t, len_t, text[:n])
+        assert end == end_bits[n - 1] and t <= len(body) <= t + 2, (t, len(body))
+        cases.append((body, text[:n]))
+
+    def windows(tm):
+        assert not tm["tree_walk_sync"] and not tm["chained_write"] and not tm["exhaustive_sync"]
+
+    _decode_up_then_down(ctx, cb, cases, windows)
+
+
+def test_fallback_block_bookkeeping_flat_table(ctx):
+    """The exit maps with the round-1 write behind them at the same sizes: the hand-made table of 200 codes of 8 bits (the flat
+    one of test_hand_made_tables_with_codes_nobody_has), where one symbol is one byte of body."""
+    import entreepy_amd as E
+
+    data_t, len_t = np.zeros(256, np.uint32), np.zeros(256, np.uint8)
+    data_t[:200], len_t[:200] = np.arange(200), 8
+    cb = E.Codebook.from_tables(data_t, len_t)
+    text = np.random.default_rng(17).integers(0, 200, size=max(_FALLBACK_EDGE_BYTES)).astype(np.uint8)
+    cases = [(text[:t].tobytes(), text[:t]) for t in _FALLBACK_EDGE_BYTES]  # (the code of symbol s is the byte s)
+
+    def exit_maps(tm):
+        assert tm["exhaustive_sync"] and not tm["chained_write"]
+
+    _decode_up_then_down(ctx, cb, cases, exit_maps)
+
+
 def test_fallback_range_sync_is_what_a_sparse_dictionary_runs(ctx):
     """et_decode_range_sync / _write with the same dictionary: ranges of a split stream take the round-1 sweeps (info says so),
     a wrong first guess is repaired, and the pieces concatenate to the text."""
