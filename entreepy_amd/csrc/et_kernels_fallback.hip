@@ -311,9 +311,13 @@ __device__ __forceinline__ SubResult walk_subsequence(const DecodeSmem &m, const
                 if (WRITE == 1) {                                                                         \
                     const uint32_t o_ = stage_pos + count;                                                \
                     /* second byte first, at o + (n == 2); then the first symbol at o: a one-symbol */   \
-                    /* step stores twice to the same byte and the later store (the symbol) wins     */   \
-                    m.stage[o_ + (n_ >> 1)] = static_cast<uint8_t>(syms_ >> 8);                           \
-                    m.stage[o_] = static_cast<uint8_t>(syms_);                                            \
+                    /* step stores twice to the same byte and the later store (the symbol) wins.    */   \
+                    /* A bit passed over (n == 0) stores nothing: with no codeword left in the      */   \
+                    /* subsequence, slot o is the NEXT lane's first, already written                */   \
+                    if (n_) {                                                                             \
+                        m.stage[o_ + (n_ >> 1)] = static_cast<uint8_t>(syms_ >> 8);                       \
+                        m.stage[o_] = static_cast<uint8_t>(syms_);                                        \
+                    }                                                                                     \
                     /* the write kernel's table holds at most two symbols per entry (DEC_WRITE_SYMS) */  \
                 } else if (WRITE == 2) {                                                                  \
                     for (uint32_t j_ = 0; j_ < n_; ++j_) {                                                \
@@ -1157,8 +1161,11 @@ __global__ __launch_bounds__(BLOCK) void k_dec_resolve_reg(const uint32_t *__res
 // The write walk over a lane's registers (et_kernels.h WSTEP_*): as walk_steps, with the
 // stage position riding in the state's upper bits.  A step stores two bytes: the second
 // symbol first, at (position after the step) - 1 -- for a one-symbol entry that is the
-// first symbol's own slot, which the first symbol then overwrites -- so no store is
-// conditional and none leaves the lane's own slots.
+// first symbol's own slot, which the first symbol then overwrites -- so the two stores of
+// a step that holds symbols need no condition between them and none leaves the lane's own
+// slots.  The escape pseudo-step holds none and stores nothing: it moves the position one
+// slot on (WSTEP_ESCAPE), and where no codeword follows in the lane -- bits passed over one
+// at a time up to the lane's end -- that slot is the NEXT lane's first, already written.
 //   MODE 1: X's upper bits are LDS addresses - 1 (the whole block fits the stage).
 //   MODE 2: they are positions in the block's output; bytes in [lo, hi) go to stage[pos - lo].
 template <int MODE>
@@ -1181,8 +1188,10 @@ __device__ __forceinline__ void walk_write(const StepWalk &sw, const uint8_t *sy
         const uint32_t p0_ = X >> 10;                                           \
         X += e & 0xffffu;                                                       \
         const uint32_t p1_ = X >> 10;                                           \
-        ET_PUT(p1_ - 1, e >> 24)                                                \
-        ET_PUT(p0_, e >> 16)                                                    \
+        if ((e & 0xffffu) != WSTEP_ESCAPE) { /* (the escape holds no symbol) */ \
+            ET_PUT(p1_ - 1, e >> 24)                                            \
+            ET_PUT(p0_, e >> 16)                                                \
+        }                                                                       \
     }
 #define ET_WW_SLOW(hi_, lo_)                                                                                           \
     {                                                                                                                  \

@@ -98,6 +98,38 @@ def _sparse_dictionary():
     return data_t, len_t, np.array([32, 101] + list(range(120, 220)))
 
 
+def _flat200_dictionary():
+    """200 symbols with the 8-bit codes 0 .. 199 (the code of symbol s is the byte s): the bytes 200 .. 255 are bit patterns
+    nobody has.  A tree the walk can hold, but nearly fixed-length: the exit maps, and -- the tree not being full -- the
+    window kernels' write behind them."""
+    data_t, len_t = np.zeros(256, np.uint32), np.zeros(256, np.uint8)
+    data_t[:200], len_t[:200] = np.arange(200), 8
+    return data_t, len_t
+
+
+def _small_holed_dictionary():
+    """0, 10, 110 and the sixteen 8-bit codewords 1110xxxx: a small tree with one hole, the pattern 1111.  The tree walk takes
+    it (the hole becomes a leaf that decodes as byte 0); if its sweep gives up, the exit maps pass the hole over bit by bit.
+    -> (data, length, the symbols)."""
+    data_t, len_t = np.zeros(256, np.uint32), np.zeros(256, np.uint8)
+    data_t[65], len_t[65] = 0b0, 1
+    data_t[66], len_t[66] = 0b10, 2
+    data_t[67], len_t[67] = 0b110, 3
+    for i in range(16):
+        data_t[100 + i], len_t[100 + i] = (0b1110 << 4) | i, 8
+    return data_t, len_t, np.array([65, 66, 67] + list(range(100, 116)))
+
+
+def sparse_text(n, seed):
+    """The text recipe of the sparse fixtures under _sparse_dictionary: half of it the 2-bit code of byte 32, so that the
+    stream re-synchronises."""
+    _, _, syms = _sparse_dictionary()
+    rng = np.random.default_rng(seed)
+    text = syms[np.minimum(rng.integers(0, 300, size=n), syms.size - 1) % syms.size].astype(np.uint8)
+    text[rng.random(n) < 0.5] = 32
+    return text
+
+
 def ones_longest(lengths):
     """{symbol: length} -> (data, length) of the canonical code of those lengths (tests/test_shared_host.py): the shortest
     codeword all zeros, the LONGEST all ones -- a run of 0xff bytes is that codeword over and over, from whatever bit."""
@@ -135,6 +167,44 @@ def _skewed_flat_dictionary():
     for i in range(100):
         data_t[120 + i], len_t[120 + i] = (0b100 << 13) | (i << 6), 16
     return data_t, len_t, np.arange(1, 7, dtype=np.uint8), np.arange(16, 32, dtype=np.uint8)
+
+
+def _skewed_run(rng, n, flat_follows):
+    """n skewed symbols of _skewed_flat_dictionary (the short ones the likelier); flat_follows: padded with one or two more so
+    that what follows begins 2, 4 or 6 bits behind a byte boundary, if the run itself begins at one."""
+    _, len_t, skewed, _ = _skewed_flat_dictionary()
+    run = skewed[np.minimum(rng.geometric(0.5, size=n) - 1, skewed.size - 1)]
+    if not flat_follows:
+        return run
+    bits = int(len_t[run].astype(np.int64).sum())
+    pad = []
+    if bits % 2:
+        pad.append(2)  # the 3-bit codeword
+    if (bits + 3 * len(pad)) % 8 == 0:
+        pad.append(1)  # the 2-bit codeword
+    run = np.concatenate([run, np.array(pad, np.uint8)])
+    assert int(len_t[run].astype(np.int64).sum()) % 8 in (2, 4, 6)
+    return run
+
+
+# island(where): (skewed symbols in front, flat symbols, skewed symbols behind) -- 144 blocks of 8 KiB each, the island in the
+# first, a middle and the last one
+ISLANDS = {"first": (3_000, 1_500, 3_200_000), "middle": (1_600_000, 1_500, 1_600_000), "last": (3_200_000, 1_500, 3_000)}
+
+
+def island(where, seed=7):
+    """-> (data, length, text): ONE stretch that does not settle in a long stream that does, under _skewed_flat_dictionary --
+    skewed symbols, 1 500 flat ones laid 2, 4 or 6 bits behind a byte boundary as in skewed_then_flat (12 000 bits: some 46
+    subsequences of 256 bits whose blind run-in stands in a phase that never meets the truth), skewed symbols again.  One
+    block gives up in the window family's first sweep and stays unsettled through the second; everything else is clean: few
+    enough blocks for the listed repair sweeps, not for the fallback (tests/test_syncwork_host.py checks all of that on the
+    input)."""
+    n_head, n_flat, n_tail = ISLANDS[where]
+    data_t, len_t, _, flat = _skewed_flat_dictionary()
+    rng = np.random.default_rng(seed)
+    head = _skewed_run(rng, n_head, True)
+    middle = flat[rng.integers(0, flat.size, size=n_flat)]
+    return data_t, len_t, np.concatenate([head, middle, _skewed_run(rng, n_tail, False)]).astype(np.uint8)
 
 
 def skewed_then_flat(n_head=40_000, n_flat=60_000, seed=5):

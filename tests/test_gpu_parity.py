@@ -4,7 +4,7 @@ import hashlib
 import numpy as np
 import pytest
 
-from tests import corpus
+from tests import bitwalk, corpus
 from tests.guards import _random_prefix_code, _sparse_dictionary, image_under, ones_longest, skewed_then_flat
 
 pytestmark = pytest.mark.gpu
@@ -1044,7 +1044,9 @@ def test_hand_made_tables_with_codes_nobody_has(ctx):
     """Dictionaries that leave bit patterns without a symbol (no encoder makes them): a valid stream decodes to its
     text on every path -- a skewed table (tree walk + chained tables, the patterns become leaves), a flat one (the
     exhaustive path, which keeps the older write kernel for such trees) -- and a stream that DOES contain the
-    patterns gives bounded output and no fault."""
+    patterns gives bounded output and no fault -- and exactly the bytes of the rule that ran (tests/bitwalk.py): under the
+    flat table the window kernels' "passed over one bit at a time"; under the skewed one the tree walk's "a leaf that decodes
+    as byte 0", unless its sweep gave up (the timing says so), and then bit by bit as well."""
     import torch
 
     import entreepy_amd as E
@@ -1081,9 +1083,19 @@ def test_hand_made_tables_with_codes_nobody_has(ctx):
         assert out[: text.size].cpu().numpy().tobytes() == text.tobytes()
         # junk: every byte value, so also the patterns no symbol has
         junk = torch.from_numpy(rng.integers(0, 256, size=body.size, dtype=np.uint8)).cuda()
-        m = ctx.decode_body_device(cb, junk, text.size, out)
+        ctx.enable_timing(True)
+        try:
+            m = ctx.decode_body_device(cb, junk, text.size, out)
+            tm = ctx.timings("decode")
+        finally:
+            ctx.enable_timing(False)
         torch.cuda.synchronize()
         assert 0 <= m <= text.size
+        by_leaves = tm["tree_walk_sync"] and tm["chained_write"] and not tm["exhaustive_sync"]
+        assert by_leaves or (tm["exhaustive_sync"] and not tm["chained_write"]), tm
+        want = bitwalk.decode_by_rule(junk.cpu().numpy(), data_t, len_t, "leaves" if by_leaves else "skip")[: text.size]
+        print(f"{int(len_t.max())}-bit table, junk: {m} symbols, {'holes as leaves' if by_leaves else 'bit by bit'}")
+        assert m == want.size and np.array_equal(out[:m].cpu().numpy(), want)
 
 
 @pytest.mark.parametrize("n", [4_000, 60_000, 2_000_000])

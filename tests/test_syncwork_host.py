@@ -14,7 +14,7 @@ from entreepy_amd import _native as N
 from oracle import oracle as O
 from tests import bitwalk as W
 from tests import corpus
-from tests.guards import _sparse_dictionary
+from tests.guards import _flat200_dictionary, _skewed_flat_dictionary, _small_holed_dictionary, _sparse_dictionary, image_under, island, skewed_then_flat, sparse_text
 from tests.test_gpu_rowsync import flat
 
 # name -> (the family a whole-stream decode starts on, as et_decode_path names it; declared clean for the tree walk)
@@ -28,6 +28,17 @@ FIXTURES = {
     "fixed": (N.ET_PATH_FIXED, False),              # 16 codewords of 4 bits
     "sparse": (N.ET_PATH_WINDOWS, False),           # tests/guards.py: no tree the walk can hold
 }
+# the fixtures of tests/test_gpu_windows.py, all under hand-made tables with bit patterns that are nobody's codeword (the reference
+# follows them by the window kernels' rule, Stream(skip=True)): name -> the family a whole-stream decode starts on
+WINDOW_FIXTURES = {
+    "sparse_big": N.ET_PATH_WINDOWS,    # the sparse recipe over 36 blocks and more: ranges of 16 blocks and beyond
+    "holes200": N.ET_PATH_EXIT_MAPS,    # 200 codes of 8 bits, 5 blocks + 17 bytes
+    "skewed_flat": N.ET_PATH_WINDOWS,   # tests/guards.py skewed_then_flat: the even phases of its flat half never merge
+    "island_first": N.ET_PATH_WINDOWS,  # tests/guards.py island: ONE block that does not settle among 144
+    "island_middle": N.ET_PATH_WINDOWS,
+    "island_last": N.ET_PATH_WINDOWS,
+}
+SPARSE_BIG_SYMBOLS = 265_000
 CLEAN_BELOW = W.LANE_BITS + W.RUN_IN_BITS  # a lane that is on the true chain before it leaves its own bits
 BODY_LAYOUTS = [(shift, start_bit) for shift in range(4) for start_bit in (0, 5)]  # decode_body_device: the pointer's low bits, the start bit
 BIG_SLOW_SYMBOLS = 2_460_000  # two_len_slow over more than 256 blocks: more than one group of exit maps
@@ -57,19 +68,22 @@ class Stream:
     """A stream as the range calls see it: `stream`, its bytes from the 4-byte aligned word the body starts in; first_bit, where
     the first codeword begins in it; the code table; the text.  And the reference's view of it, worked out once and read-only:
     L, S (bitwalk.next_table), `at` (the bit every whole codeword of the true chain begins at, those in the pad bits included),
-    on_chain (one flag per bit)."""
+    on_chain (one flag per bit).  skip: the reference follows the window kernels' rule for bit patterns without a codeword
+    (bitwalk: unmatched="skip") -- L is 1 there, C says where a codeword begins, and every walk over L is handed C; else C is
+    None."""
 
-    def __init__(self, name, data, length, text, stream, first_bit, comp=None, body_off=None):
+    def __init__(self, name, data, length, text, stream, first_bit, comp=None, body_off=None, skip=False):
         self.name, self.data, self.length, self.text = name, np.asarray(data, np.uint32), np.asarray(length, np.uint8), np.asarray(text, np.uint8)
         self.stream, self.first_bit, self.comp, self.body_off = np.frombuffer(bytes(stream), dtype=np.uint8), first_bit, comp, body_off
         self.n_bytes, self.n_bits = self.stream.size, self.stream.size * 8
         self.shift, self.start_bit = first_bit // 8, first_bit % 8  # the body lies `shift` bytes into the stream and begins at bit start_bit of that byte
         self.n_blocks = (self.n_bytes + W.BLOCK_BYTES - 1) // W.BLOCK_BYTES
-        self.L, self.S = W.next_table(self.stream, self.data, self.length)
-        _, self.at = W.walk_positions(self.L, first_bit, self.n_bits)
+        self.L, self.S, self.C = W.next_table(self.stream, self.data, self.length, "skip") if skip else (*W.next_table(self.stream, self.data, self.length), None)
+        _, self.at = W.walk_positions(self.L, first_bit, self.n_bits, self.C)
         self.on_chain = W.chain(self.L, first_bit, self.at)
-        for a in (self.L, self.S, self.at, self.on_chain):
+        for a in (self.L, self.S, self.at, self.on_chain) + ((self.C,) if skip else ()):
             a.setflags(write=False)
+        self._Lb, self._Cb, self._walks = self.L.tobytes(), self.C.tobytes() if skip else None, {}
 
     def codebook(self):
         return E.Codebook.from_tables(self.data, self.length)
@@ -84,6 +98,31 @@ class Stream:
         i, j = np.searchsorted(self.at, begin * 8), np.searchsorted(self.at, end * 8)
         exit_bit = int(self.at[j]) - end * 8 if j < self.at.size else 0  # (a codeword the stream's end cuts: nobody's, the walk ends there)
         return self.true_start(begin), exit_bit, int(j - i), self.S[self.at[i:j]]
+
+    def block_walk(self, b, off):
+        """The serial walk of block b from its bit `off` to its end (the stream's, for the last block) -> (exit, in bits behind
+        that end; the bits at which the counted codewords begin).  Kept: walks from different starts soon are the same walk."""
+        if (b, off) not in self._walks:
+            end = min((b + 1) * W.BLOCK_BYTES, self.n_bytes) * 8
+            exit_, at = W.walk_positions(self._Lb, b * W.BLOCK_BITS + off, end, self._Cb)
+            at.setflags(write=False)
+            self._walks[b, off] = (exit_ - end, at)
+        return self._walks[b, off]
+
+    def range_walk(self, begin, end, start):
+        """-> (exit_bit, at): the serial walk from bit `start` of the range [begin, end) bytes, a range of whole blocks or one
+        that ends with the stream, block by block."""
+        assert begin % W.BLOCK_BYTES == 0 and (end % W.BLOCK_BYTES == 0 or end == self.n_bytes) and begin < end
+        off, ats = start, []
+        for b in range(begin // W.BLOCK_BYTES, (end + W.BLOCK_BYTES - 1) // W.BLOCK_BYTES):
+            off, at = self.block_walk(b, off)
+            ats.append(at)
+        return off, np.concatenate(ats)
+
+    def range_count(self, begin, end, start):
+        """range_walk's (exit_bit, number of codewords)."""
+        exit_bit, at = self.range_walk(begin, end, start)
+        return exit_bit, at.size
 
     def cuts(self, widths=(1, 2, 5)):
         """Ranges of 1, 2 and 5 blocks at every block boundary, as (begin, end) in bytes; those that reach the stream's end
@@ -100,14 +139,26 @@ class Stream:
 @functools.lru_cache(maxsize=None)
 def fixture(name):
     """The fixture `name`, made once and shared; read-only."""
-    if name == "sparse":  # the dictionary and text of test_fallback_sweeps_and_write_are_what_a_sparse_dictionary_runs, n = 60 000
-        data_t, len_t, syms = _sparse_dictionary()
-        n = 60_000
-        rng = np.random.default_rng(n)
-        text = syms[np.minimum(rng.integers(0, 300, size=n), syms.size - 1) % syms.size].astype(np.uint8)
-        text[rng.random(n) < 0.5] = 32
+    if name in ("sparse", "sparse_big"):  # the dictionary and text of test_fallback_sweeps_and_write_are_what_a_sparse_dictionary_runs, n = 60 000
+        data_t, len_t, _ = _sparse_dictionary()
+        n = {"sparse": 60_000, "sparse_big": SPARSE_BIG_SYMBOLS}[name]
+        text = sparse_text(n, n)
         body, _ = O.pack_body(data_t, len_t, text)
-        return Stream(name, data_t, len_t, text, body, 0, comp=body, body_off=0)
+        return Stream(name, data_t, len_t, text, body, 0, comp=body, body_off=0, skip=True)
+    if name.startswith("junk/"):  # the first 6 blocks and 100 bytes of junk_stream: ranges whose INTERIOR blocks hold patterns that are nobody's
+        whole = junk_stream(name[len("junk/") :])
+        body = whole.stream[: 6 * W.BLOCK_BYTES + 100].tobytes()
+        return Stream(name, whole.data, whole.length, np.zeros(0, np.uint8), body, 0, comp=body, body_off=0, skip=True)
+    if name == "holes200":  # the flat table of test_fallback_block_bookkeeping_flat_table: the text is its own body
+        data_t, len_t = _flat200_dictionary()
+        text = np.random.default_rng(17).integers(0, 200, size=5 * W.BLOCK_BYTES + 17).astype(np.uint8)
+        return Stream(name, data_t, len_t, text, text.tobytes(), 0, comp=text.tobytes(), body_off=0, skip=True)
+    if name == "skewed_flat" or name.startswith("island_"):
+        data_t, len_t, text = skewed_then_flat() if name == "skewed_flat" else island(name[len("island_") :])
+        comp = image_under(data_t, len_t, text)
+        _, n_symbols, body_off = E.parse_header(comp)
+        assert n_symbols == text.size
+        return Stream(name, data_t, len_t, text, comp[body_off & ~3 :], (body_off & 3) * 8, comp=comp, body_off=body_off, skip=True)
     text = _text_of(name)
     comp = O.encode(text)[4:]
     cb, n_symbols, body_off = E.parse_header(comp)
@@ -135,16 +186,16 @@ def decode_path(cb):
 def test_the_walk_from_the_true_start_is_the_oracles_decode(name):
     fx = fixture(name)
     n = fx.text.size
-    exit_, syms = W.walk_symbols(fx.L, fx.S, fx.first_bit, fx.n_bits)
+    exit_, syms = W.walk_symbols(fx.L, fx.S, fx.first_bit, fx.n_bits, fx.C)
     assert fx.n_bits <= exit_ < fx.n_bits + 32 and n <= syms.size <= n + 7  # (whole codewords in the pad bits are decoded too)
     image = fx.comp if name != "sparse" else fx.codebook().header(n)[4:] + fx.comp
     assert syms[:n].tobytes() == O.decode(image) == fx.text.tobytes()
     bounds = W.boundaries(fx.first_bit, fx.length, fx.text)
     assert np.array_equal(fx.at[:n], bounds[:-1]) and (fx.at.size == n or fx.at[n] == bounds[-1])
     assert np.array_equal(fx.L[bounds[:-1]], fx.length[fx.text]) and np.array_equal(fx.S[bounds[:-1]], fx.text)
-    assert W.walk(fx.L, fx.first_bit, fx.n_bits) == (exit_, syms.size)
+    assert W.walk(fx.L, fx.first_bit, fx.n_bits, fx.C) == (exit_, syms.size)
     # the same through the pointer-doubling variant, for the whole stream and for every cut of it
-    jumps = W.Jumps(fx.L)
+    jumps = W.Jumps(fx.L, fx.C)
     assert [int(x[0]) for x in jumps.walk([fx.first_bit], [fx.n_bits])] == [exit_, syms.size]
     cuts = fx.cuts()
     assert len(cuts) >= 3 * fx.n_blocks - 5 and sum(1 for _, e in cuts if e == fx.n_bytes) >= 1
@@ -153,7 +204,8 @@ def test_the_walk_from_the_true_start_is_the_oracles_decode(name):
     exits, counts = jumps.walk(starts, ends)
     for (b, e), x, c in zip(cuts, exits, counts):
         s, exit_bit, n_sym, syms = fx.truth(b, e)
-        assert (int(x) - e * 8, int(c)) == (exit_bit, n_sym) == (W.walk(fx.L, b * 8 + s, e * 8)[0] - e * 8, syms.size), (b, e)
+        assert (int(x) - e * 8, int(c)) == (exit_bit, n_sym) == (W.walk(fx.L, b * 8 + s, e * 8, fx.C)[0] - e * 8, syms.size), (b, e)
+        assert (exit_bit, n_sym) == fx.range_count(b, e, s), (b, e)
         assert s < 32 and exit_bit < 32
 
 
@@ -240,7 +292,7 @@ def test_a_start_one_bit_off_is_visible_to_the_reference(name):
     and stands on the truth's boundary, or it reads on one bit behind the truth, codeword for codeword, until that happens
     -- the same count, the same exit.  So both directions are tried; what each shows is printed."""
     fx = fixture(name)
-    jumps = W.Jumps(fx.L)
+    jumps = W.Jumps(fx.L, fx.C)
     cuts = [(b, e) for b, e in fx.cuts((1,)) if e - b == W.BLOCK_BYTES]
     starts = np.array([b * 8 + fx.true_start(b) for b, _ in cuts])
     ends = np.array([e * 8 for _, e in cuts])
@@ -273,3 +325,216 @@ def test_the_skewed_then_flat_dictionary_is_the_window_sweeps_and_never_settles(
     k = ctypes.c_uint32(0)
     assert N.lib().et_treewalk_table(ctypes.byref(cb.raw), None, 0, ctypes.byref(k)) != N.ET_OK
     assert W.longest_unsettled_run(comp[off & ~3 :], (off & 3) * 8, cb.data, cb.length, 256, 128) == 256
+
+
+# ---- hand-made tables: bit patterns that are nobody's codeword (tests/test_gpu_windows.py, and the range tests of test_gpu_syncwork.py) ----
+
+JUNK_DICTIONARIES = {"sparse": lambda: _sparse_dictionary()[:2], "holes200": _flat200_dictionary, "skewed_flat": lambda: _skewed_flat_dictionary()[:2]}
+JUNK_BYTES = [8191, 8192, 3 * 8192 + 17, 4 * 8192, 16 * 8192 + 1, 17 * 8192 + 1]  # of test_gpu_parity's _FALLBACK_EDGE_BYTES
+JUNK_LANES_ENDING_IN_ONES = range(5, max(JUNK_BYTES) // 32, 41)  # six or seven subsequences of every block, the first one's too
+LONG_RANGES = [(0, 16), (1, 17), (3, 20), (16, None), (0, None)]  # of sparse_big, in blocks; None: the stream's end
+
+
+@functools.lru_cache(maxsize=None)
+def junk_stream(dictionary):
+    """Random bytes, every value, as a body under one of the hand-made tables: the longest of JUNK_BYTES, of which the others
+    are prefixes.  The last three bytes of every 41st subsequence of 256 bits are 0xff: under the sparse table and the 200
+    codes that is 24 bits passed over up to the subsequence's end, more than the kernels' tables index -- the lane's walk ends
+    in steps without a symbol, and the next symbol is the next lane's (JUNK_LANES_ENDING_IN_ONES, checked on the host)."""
+    data_t, len_t = JUNK_DICTIONARIES[dictionary]()
+    body = np.random.default_rng(20_241).integers(0, 256, size=max(JUNK_BYTES), dtype=np.uint8)
+    for lane in JUNK_LANES_ENDING_IN_ONES:
+        body[32 * lane + 29 : 32 * lane + 32] = 0xFF
+    return Stream(f"junk/{dictionary}/whole", data_t, len_t, np.zeros(0, np.uint8), body.tobytes(), 0, comp=body.tobytes(), body_off=0, skip=True)
+
+
+def junk_truth(dictionary, n_bytes, start_bit):
+    """What the first n_bytes of the junk decode to from bit start_bit, under the rule "a bit pattern without a codeword is
+    passed over one bit at a time" -> (the symbols, the bits passed over).  The blocks that end four bytes or more in front of
+    the prefix's end are the whole junk's (kept walks: no codeword that begins in them sees the end); the rest is walked over
+    a table of the prefix's own, whose end cuts what reaches beyond it."""
+    fx = junk_stream(dictionary)
+    whole = max(0, (n_bytes - 4) // W.BLOCK_BYTES)
+    off, ats = start_bit, []
+    for b in range(whole):
+        off, at = fx.block_walk(b, off)
+        ats.append(at)
+    rest = fx.stream[whole * W.BLOCK_BYTES : n_bytes]
+    L, _, C = W.next_table(rest, fx.data, fx.length, "skip")
+    _, at = W.walk_positions(L, off, rest.size * 8, C)
+    ats.append(at + whole * W.BLOCK_BITS)
+    at = np.concatenate(ats)
+    passed = n_bytes * 8 - start_bit - int(fx.L[at].astype(np.int64).sum())  # (less the bits of a codeword the end cuts: at most 31)
+    return fx.S[at], passed
+
+
+def _passed_over(fx, begin, end, start):
+    """The bits that the walk of the range [begin, end) bytes from its bit `start` steps over without a codeword."""
+    exit_bit, at = fx.range_walk(begin, end, start)
+    q = int(at[-1]) + int(fx.L[at[-1]]) if at.size else begin * 8 + start  # behind the last counted codeword ...
+    while q < end * 8 and not fx.C[q]:
+        q += 1  # ... single steps, up to the range's end or to a codeword that the stream's end cuts
+    return q - (begin * 8 + start) - int(fx.L[at].astype(np.int64).sum())
+
+
+@pytest.mark.parametrize("name", list(FIXTURES))
+def test_the_skip_walk_from_the_true_start_is_the_plain_walk(name):
+    """A stream of its table's own codewords holds no pattern for the rule to act on: under unmatched="skip" the true chain,
+    the symbols, every cut's (exit, count) -- by the serial walk and by pointer doubling -- are those of the default rule."""
+    fx = fixture(name)
+    L0, S0 = W.next_table(fx.stream, fx.data, fx.length)
+    L, S, C = W.next_table(fx.stream, fx.data, fx.length, "skip")
+    assert np.array_equal(C, L0 > 0) and np.array_equal(L[C], L0[C]) and (L[~C] == 1).all() and np.array_equal(S, S0)
+    exit_, at = W.walk_positions(L, fx.first_bit, fx.n_bits, C)
+    assert (exit_, at.tolist()) == (W.walk_positions(L0, fx.first_bit, fx.n_bits)[0], fx.at.tolist()) and C[at].all()
+    assert W.walk(L, fx.first_bit, fx.n_bits, C) == W.walk(L0, fx.first_bit, fx.n_bits) == (exit_, at.size)
+    assert np.array_equal(W.chain(L, fx.first_bit, C=C), fx.on_chain)
+    assert np.array_equal(W.walk_symbols(L, S, fx.first_bit, fx.n_bits, C)[1], S0[fx.at])
+    cuts = fx.cuts()
+    starts, ends = np.array([b * 8 + fx.true_start(b) for b, _ in cuts]), np.array([e * 8 for _, e in cuts])
+    for a, b in zip(W.Jumps(L, C).walk(starts, ends), W.Jumps(L0).walk(starts, ends)):
+        assert np.array_equal(a, b)
+    if FIXTURES[name][1]:  # (the fixtures NOT declared clean may hold lanes that the default rule cannot judge)
+        d = W.merge_distances(L, fx.on_chain, C=C)
+        assert np.array_equal(d, W.merge_distances(L0, fx.on_chain)) and int(d.max()) < W.NEVER
+
+
+def test_the_skip_rule_on_a_stream_small_enough_to_follow():
+    """Codewords 10 and 11 only, nobody has 0: in 10 0 0 11 0 1|, sixteen bits with the pad, the walk from bit 0 counts 10, 11
+    and -- bits 7 and 8 -- 10 (not the 10 at bits 5 and 6, where it never stands), steps over the zeros one at a time, and ends at the end; the one bit left at bit 15 is the
+    codeword 10 against the zeros behind the end: cut, uncounted, and the walk ends where the stream does."""
+    data, length = [0, 0b10, 0b11] + [0] * 253, [0, 2, 2] + [0] * 253
+    body = bytes([0b10001101, 0b00000001])
+    L, S, C = W.next_table(body, data, length, "skip")
+    assert L.tolist() == [2, 1, 1, 1, 2, 2, 1, 2, 1, 1, 1, 1, 1, 1, 1, 2] and C.tolist() == [l == 2 for l in L.tolist()]
+    assert W.walk(L, 0, 16, C) == (16, 3) and W.walk_positions(L, 0, 16, C)[1].tolist() == [0, 4, 7]
+    assert W.walk_symbols(L, S, 0, 16, C)[1].tolist() == [1, 2, 1]
+    assert W.walk(L, 0, 8, C) == (9, 3) and W.walk(L, 1, 8, C) == (9, 2) and W.walk(L, 5, 7, C) == (7, 1) and W.walk(L, 6, 7, C) == (7, 0)
+    jumps = W.Jumps(L, C)
+    exits, counts = jumps.walk([0, 0, 1, 6, 9, 15], [16, 8, 8, 7, 16, 16])
+    assert exits.tolist() == [16, 9, 9, 7, 16, 16] and counts.tolist() == [3, 3, 2, 0, 0, 0]
+    assert W.chain(L, 0, C=C).nonzero()[0].tolist() == [0, 4, 7, 16]
+    # lanes of 4 bits with a run-in of 1: from bits 3, 7, 11 -- a step over a zero onto bit 4, a boundary itself, a walk of steps to the end
+    assert W.merge_distances(L, W.chain(L, 0, C=C), lane_bits=4, run_in_bits=1, C=C).tolist() == [0, 1, 0, 5]
+    with pytest.raises(W.Unmatched):
+        W.walk(W.next_table(body + bytes(8), data, length)[0], 0, 16)
+
+
+def test_the_new_fixtures_are_what_their_gpu_tests_take_them_for():
+    """The planner agrees; the sizes; and every walk that a GPU test compares under the rule DOES meet patterns without a
+    codeword -- a fixture that stops reaching the rule fails here."""
+    for name, path in WINDOW_FIXTURES.items():
+        fx = fixture(name)
+        assert decode_path(fx.codebook()) == path and fx.C is not None and not fx.C.all(), name
+        n = fx.text.size
+        assert W.walk_symbols(fx.L, fx.S, fx.first_bit, fx.n_bits, fx.C)[1][:n].tobytes() == fx.text.tobytes()
+        assert fx.C[fx.at].all()  # the true chain itself holds codewords only
+    big, holes, sf = fixture("sparse_big"), fixture("holes200"), fixture("skewed_flat")
+    assert big.n_blocks >= 36 and big.n_bytes % W.BLOCK_BYTES and big.n_bytes <= 1_200_000
+    assert holes.n_bytes == 5 * W.BLOCK_BYTES + 17 and holes.stream.tobytes() == holes.text.tobytes()
+    assert [int(fixture(n).length.max()) for n in ("sparse", "holes200", "skewed_flat")] == [16, 8, 16]  # the maps' n_starts
+    # the exit maps: the walks from every start offset
+    for fx in (fixture("sparse"), holes, sf):
+        k = int(fx.length.max())
+        met = [sum(_passed_over(fx, b, e, p) for p in range(k)) for b, e in fx.cuts()]
+        print(f"{fx.name}: bits passed over by the {k} walks of each of {len(met)} ranges: {min(met)} .. {max(met)}")
+        assert min(met) > 0
+    # ... and under a stream of the table's own codewords those walks are on the true chain after a block: what the INTERIOR blocks
+    # of a range see of the rule comes from the junk ranges, where the walks from every start pass bits over in every block
+    for d in ("sparse", "holes200"):
+        fx = fixture("junk/" + d)
+        k = int(fx.length.max())
+        assert fx.n_blocks == 7 and fx.text.size == 0
+        for b in range(fx.n_blocks):
+            for p in range(k):
+                assert _passed_over(fx, b * W.BLOCK_BYTES, min((b + 1) * W.BLOCK_BYTES, fx.n_bytes), p) > (100 if b < 6 else 0), (d, b, p)
+    # the exits of the even start offsets never merge inside the flat half: a map there has truly different entries
+    b = sf.n_blocks // 2
+    exits = [sf.range_walk(b * W.BLOCK_BYTES, (b + 1) * W.BLOCK_BYTES, p)[0] for p in range(0, 8, 2)]
+    assert len(set(e % 8 for e in exits)) == 4 and sf.text[sf.truth(b * W.BLOCK_BYTES, (b + 1) * W.BLOCK_BYTES)[3].size * b] >= 16, exits
+    # the wrong known starts, true start + 1
+    for fx in (fixture("sparse"), sf):
+        met = [_passed_over(fx, b, e, fx.true_start(b) + 1) for b, e in fx.cuts()]
+        assert sum(m > 0 for m in met) >= len(met) // 2, (fx.name, met)
+    for b0, b1 in LONG_RANGES:
+        begin, end = b0 * W.BLOCK_BYTES, big.n_bytes if b1 is None else b1 * W.BLOCK_BYTES
+        assert _passed_over(big, begin, end, big.true_start(begin) + 1) > 0, (b0, b1)
+    # the junk
+    for d in JUNK_DICTIONARIES:
+        for n_bytes in JUNK_BYTES:
+            for start_bit in (0, 5):
+                syms, passed = junk_truth(d, n_bytes, start_bit)
+                assert passed > n_bytes // 4 and syms.size > n_bytes // 2, (d, n_bytes, start_bit, syms.size, passed)  # (a third of the steps or more)
+        print(f"junk under {d}: {syms.size} symbols, {passed} bits passed over in {n_bytes} bytes")
+    # subsequences whose last codeword ends 16 bits or more in front of their end, a codeword beginning within 32 bits behind it
+    for d in ("sparse", "holes200"):
+        fx = junk_stream(d)
+        ends = fx.at + fx.L[fx.at]
+        gap_over_a_lane_end = (fx.at[1:] // 256 > ends[:-1] // 256) & ((ends[:-1] // 256 + 1) * 256 - ends[:-1] >= 16) & (fx.at[1:] % 256 < 32)
+        blocks = set((fx.at[1:][gap_over_a_lane_end] // W.BLOCK_BITS).tolist())
+        assert {0, 1, 4, 16} <= blocks and len(blocks) >= 12, (d, sorted(blocks))  # the first block, interior ones, one behind the superblocks
+
+
+@pytest.mark.parametrize("where", ["first", "middle", "last"])
+def test_the_islands_reach_the_listed_repair_and_nothing_else(where):
+    """tests/guards.py island under the rule, every lane judged (no NEVER): k >= 1 blocks hold a run of unsettled 256-bit lanes
+    that outlasts the first sweep's trips AND the second's; k * 64 <= n_blocks, the rule of dec_state_final and body_first_sweep
+    for "repair sweeps, not the fallback"; every other block stays below the first sweep's trips, so that it does not give up.
+    From 16 blocks on the first sweep walks 512-bit lanes over superblocks: the same three conditions in that geometry.
+    Conditions on the input, not measurements.  And under the default rule most lanes of such a stream are nobody's to judge."""
+    from tests.test_gpu_syncwork import CERTAIN_FROM, FIRST_SWEEP_TRIPS
+
+    fx = fixture("island_" + where)
+    assert fx.n_blocks == 144
+    for lane_bits in (256, 512):
+        runs = W.unsettled_block_runs(fx.stream, fx.first_bit, fx.data, fx.length, lane_bits, 128, "skip")
+        certain = np.flatnonzero(runs >= CERTAIN_FROM["windows"])
+        print(f"island {where}, lanes of {lane_bits} bits: blocks {certain.tolist()} hold runs of {runs[certain].tolist()} unsettled lanes, the others at most {int(np.delete(runs, certain).max())}")
+        assert certain.tolist() == [{"first": 0, "middle": 71, "last": 143}[where]]
+        assert certain.size * 64 <= fx.n_blocks
+        assert int(np.delete(runs, certain).max()) < FIRST_SWEEP_TRIPS
+    L0, _ = W.next_table(fx.stream, fx.data, fx.length)
+    d0 = W.merge_distances(L0, fx.on_chain, 256, 128, enough=384)
+    assert int(np.count_nonzero(d0 == W.NEVER)) > d0.size // 2
+
+
+def test_holes_as_leaves_is_the_tree_walks_completed_tree():
+    """The second rule, the tree walk's (tw_build_tree(complete = true)): every child that a node of the codewords' tree lacks
+    becomes a leaf that decodes as byte 0.  bitwalk.leaves_for_holes gives those leaves as pseudo-codewords.  For the small
+    holed table of tests/guards.py: ONE leaf, 1111, four bits deep.  et_treewalk_table itself turns a holed table away (it
+    builds with complete = false), so the model is held against it through a FULL table: the codewords and, under symbols
+    behind every coded one (so that the nodes are numbered as they are without them), the pseudo-codewords -- accepted only
+    if prefix-free and full, with the holed tree's own nodes and not one more (every hole a child of a node that is there:
+    maximal), and its table is the brute-force table of tests/test_host_logic.py for those codes."""
+    from tests.test_host_logic import _brute_treewalk_table
+
+    data_t, len_t, syms = _small_holed_dictionary()
+    leaves = W.leaves_for_holes(data_t, len_t)
+    assert leaves == [(0b1111, 4, 0)]
+    n_int = ctypes.c_uint32(0)
+    holed = E.Codebook.from_tables(data_t, len_t)
+    assert N.lib().et_treewalk_table(ctypes.byref(holed.raw), None, 0, ctypes.byref(n_int)) == N.ET_ERR_UNSUPPORTED
+    assert decode_path(holed) == N.ET_PATH_TREE_WALK  # (the decode completes the tree)
+    for d, l in ((data_t, len_t), _flat200_dictionary()):  # the flat table too: 56 missing bytes in a handful of subtrees
+        leaves = W.leaves_for_holes(d, l)
+        nodes = {(int(d[s]) >> (int(l[s]) - k), k) for s in np.flatnonzero(l) for k in range(int(l[s]))}
+        full_d, full_l = d.copy(), l.copy()
+        free = [s for s in range(int(np.flatnonzero(l).max()) + 1, 256)]
+        assert len(leaves) <= len(free)
+        for s, (code, length, byte) in zip(free, leaves):
+            full_d[s], full_l[s] = code, length
+            assert byte == 0
+        full = E.Codebook.from_tables(full_d, full_l)
+        cap = (256 + 7) * 256
+        table = np.zeros(cap, dtype=np.uint16)
+        assert N.lib().et_treewalk_table(ctypes.byref(full.raw), table.ctypes.data, cap, ctypes.byref(n_int)) == N.ET_OK
+        assert n_int.value == len(nodes) == full.raw.n_coded - 1
+        want_n, want = _brute_treewalk_table(full_d, full_l)
+        assert want_n == n_int.value and np.array_equal(table[: want.size], want)
+    assert W.leaves_for_holes(*_flat200_dictionary()) == [(0b111, 3, 0), (0b1101, 4, 0), (0b11001, 5, 0)]  # the bytes 224 .., 208 .., 200 ..
+    # the model as a table: under it nothing is unmatched, and 0xff reads 1111 1111 -- two leaves, byte 0 twice
+    stream = bytes([0xFF, 0b11100101, 0b01101111]) + bytes(4)
+    L, S = W.next_table(stream, data_t, len_t, extra=W.leaves_for_holes(data_t, len_t))
+    assert (L[:24] > 0).all() and W.walk_symbols(L, S, 0, 24)[1].tolist() == [0, 0, 105, 65, 67, 0]
+    Lk, Sk, Ck = W.next_table(stream, data_t, len_t, "skip")
+    assert W.walk_symbols(Lk, Sk, 0, 24, Ck)[1].tolist() == [105, 65, 67, 100]  # bit by bit: eight ones passed over, 1110 0101, 0, 110, one more one passed over, 1110 0000 (begun in front of bit 24)
