@@ -17,6 +17,8 @@ from .codec import (  # noqa: F401
     MATCH_PREFIX,
     MatchResult,
     PackedResult,
+    SEARCH_CONTAINS,
+    SEARCH_SUFFIX,
     TakeResult,
     decode,
     default_context,

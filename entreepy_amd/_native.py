@@ -115,6 +115,7 @@ class MatchResult(ctypes.Structure):
 
 
 ET_MATCH_EQUAL, ET_MATCH_PREFIX, ET_MATCH_NOT = 0, 1, 0x100  # et_match_packed_device's mode
+ET_SEARCH_CONTAINS, ET_SEARCH_SUFFIX = 0, 1  # et_search_packed_device's mode; ET_MATCH_NOT may be or-ed in
 
 
 class JoinResult(ctypes.Structure):
@@ -197,6 +198,9 @@ SIGNATURES = {
     "et_match_pattern_max": (_sz, []),
     "et_match_result_size": (_sz, []),
     "et_match_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _sz, _vp, ctypes.POINTER(MatchResult)]),
+    "et_search_needle_max": (_sz, []),
+    "et_search_lane_bytes": (_sz, []),
+    "et_search_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _sz, _vp, _vp, ctypes.POINTER(MatchResult)]),
     "et_join_result_size": (_sz, []),
     "et_join_keys_max": (_sz, []),
     "et_join_hash": (_u64, [_vp, _sz, _u64]),

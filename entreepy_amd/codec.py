@@ -88,6 +88,7 @@ class TakeResult:  # struct et_take_result, and the call's own status in front
 
 
 MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT =N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_MATCH_NOT  # match_packed_device's mode
+SEARCH_CONTAINS, SEARCH_SUFFIX = N.ET_SEARCH_CONTAINS, N.ET_SEARCH_SUFFIX  # search_packed_device's mode; MATCH_NOT may be or-ed in
 
 
 def _check(status, ctx=None):
@@ -565,6 +566,25 @@ class Context:
                                             p, a.size, int(mode), rows_p, 0 if rows is None else rows.numel(), self._opt_ptr(status), ctypes.byref(res))
         return MatchResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
 
+    def search_packed_device(self, codebook, bodies, body_index, text_index, needle, mode, rows=None, pos=None, status=None):
+        """The records of the store (bodies, body_index, text_index: match_packed_device's) whose text contains `needle`
+        (SEARCH_CONTAINS) or ends with it (SEARCH_SUFFIX) -- with MATCH_NOT or-ed in, the valid records that do not -- found on the
+        compressed bytes by a walk over the codeword boundaries, nothing decoded.  needle: bytes on the host, at most 256.  rows:
+        int32/uint32 CUDA tensor that takes the selected record numbers, ascending; None: count only.  pos: optional tensor like rows
+        (not with MATCH_NOT): where in each selected record the needle lies -- the first occurrence, or length - len(needle).
+        status: optional uint8 CUDA tensor of one et_status byte per record; a failed record is never selected.  -> MatchResult;
+        .status is ET_OK or ET_ERR_CAP (no row written, .n_match = the room needed); any other failure of the call raises.
+        Stream-ordered like decode_packed_device."""
+        n = text_index.numel() - 1
+        a, p = _host_u8(bytes(needle))
+        rows_p, pos_p = (None if t is None else self._rows_ptr(t, "rows and pos are 1-D CUDA tensors of 32-bit integers") for t in (rows, pos))
+        assert pos is None or (rows is not None and pos.numel() >= rows.numel()), "pos is as large as rows"
+        res = N.MatchResult()
+        self._bind()
+        rc = N.lib().et_search_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                             p, a.size, int(mode), rows_p, 0 if rows is None else rows.numel(), pos_p, self._opt_ptr(status), ctypes.byref(res))
+        return MatchResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
+
     def join_packed_device(self, codebook, bodies, body_index, text_index, key_bodies, key_body_index, key_text_index, mode=0, rows=None, key_of_row=None, status=None,
                            key_status=None):
         """The records of the store (bodies, body_index, text_index: match_packed_device's) that equal SOME key of the key set
@@ -698,6 +718,28 @@ class Context:
         if res.n_failed:
             raise EntreepyError(res.first_status, f"match_packed: record {res.first_failed}")
         return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
+
+    def search_packed(self, codebook, blob, out_index, lengths, needle, mode):
+        """decode_packed's store, a needle and a mode -> ([the numbers of the records that contain the needle, or end with it],
+        ascending, [where in each]) through one search_packed_device call; with MATCH_NOT the records that do not, and no positions."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        assert out_index.size == lengths.size + 1
+        if not lengths.size:
+            return [], []
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
+        d_pos = None if mode & MATCH_NOT else torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
+        res = self.search_packed_device(codebook, d_blob, d_body_index, d_text_index, needle, mode, rows=d_rows, pos=d_pos)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"search_packed: record {res.first_failed}")
+        rows = d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copies run behind the call's kernels)
+        return rows, [] if d_pos is None else d_pos[: res.n_match].cpu().numpy().view(np.uint32).tolist()
 
     def join_packed(self, codebook, blob, out_index, lengths, key_blob, key_index, key_lengths, mode=0):
         """decode_packed's store and a key set of the same form (e.g. encode_packed's of the keys) -> [the numbers of the records that

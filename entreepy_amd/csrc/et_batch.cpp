@@ -23,6 +23,7 @@
 //   decode        table + counters -> k_packed_decode (poll)
 //   gather        table + counters -> k_gather_plan -> k_packed_scan -> k_packed_gather (poll: it alone knows the short rows); sizes only: the scan's (poll)
 //   match         counters + pattern (et_encode_pattern, on the host) -> k_match_flag -> k_packed_scan (poll) -> unless count only: k_rows_emit
+//   search        sorted codes + counters + pattern -> k_search_flag -> k_search_long -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   join          counters -> clear the table -> k_join_build -> k_join_flag (the keys' counters into the report) -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   take          counters -> k_take_plan -> k_take_scan (poll) -> unless sizes only: k_take_copy
 #include "et_ctx.h"
@@ -60,6 +61,7 @@ static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the p
 // The packed calls' device workspace (ctx->packed_ws) begins as the pinned region does, so an upload lands where it came from: the
 // table, the counters at PK_STATS for EVERY call, the match's pattern.  Behind the counters each call has its own layout:
 //   encode, gather   from PK_SIZES: a size word per record, or per row        take   from PK_SIZES: a TakeRow per row
+//   search  as the match, then a position and a list entry per record
 //   match   behind the pattern: the tile workspace (tile_ws)                   join   behind the counters: the tile workspace, the table's slots, a key number per record
 constexpr size_t PK_STATS = 2048, PK_PATTERN = PK_STATS + PK_COUNTER_BYTES, PK_SIZES = 4096, PK_MATCH_TILES = PK_PATTERN + et::MATCH_PATTERN_BYTES;
 static_assert(PK_PATTERN % 16 == 0 && PK_MATCH_TILES % 16 == 0 && PK_SIZES % 16 == 0 && sizeof(et::TakeRow) == 16,
@@ -433,6 +435,61 @@ extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     res->n_match = rep[et::PACKED_BYTES];
     read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
     if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records match than cap_rows");  // (k_rows_emit saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_search_needle_max(void) { return et::SEARCH_NEEDLE_MAX; }
+
+extern "C" size_t et_search_lane_bytes(void) { return et::SEARCH_LANE_BYTES; }
+
+extern "C" int et_search_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                       const uint64_t *d_text_index, size_t n_records, const uint8_t *needle, size_t needle_len, int mode, uint32_t *d_rows,
+                                       size_t cap_rows, uint32_t *d_pos, uint8_t *d_status, et_match_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || (!needle && needle_len)) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (misaligned(7, d_body_index, d_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_rows, d_pos)) return fail(ctx, ET_ERR_ARG, "the rows or the positions are not 4-byte aligned");
+    if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    if (needle_len > et::SEARCH_NEEDLE_MAX) return fail(ctx, ET_ERR_ARG, "the needle is longer than et_search_needle_max()");
+    const int what = mode & ~ET_MATCH_NOT;
+    if (what != ET_SEARCH_CONTAINS && what != ET_SEARCH_SUFFIX) return fail(ctx, ET_ERR_ARG, "unknown mode");
+    if (d_pos && (mode & ET_MATCH_NOT)) return fail(ctx, ET_ERR_ARG, "a record without an occurrence has no position");
+    if (d_pos && !d_rows) return fail(ctx, ET_ERR_ARG, "positions without rows");
+    *res = et_match_result{};
+    if (n_records == 0) return ET_OK;
+    ET_TRY(require_complete(ctx, cb));
+    DeviceGuard guard(ctx->device);
+    const et::PackedStore store{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    Bump layout{PK_MATCH_TILES};
+    const TileOffsets tiles = tile_ws(layout, (store.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const size_t at_pos = layout.take(static_cast<size_t>(store.n) * 4, 4), at_list = layout.take(static_cast<size_t>(store.n) * 4, 4);
+    ET_TRY(packed_ensure(ctx, layout.end));
+
+    // the sorted codes, the counters' first values and the needle's bits lie one behind the other: up in one copy
+    const uint32_t n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), false);
+    first_counters(ctx);
+    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
+    uint64_t bits = 0;
+    const int rc = et_encode_pattern(cb, needle, needle_len, pattern, et::SEARCH_PATTERN_BYTES, &bits);
+    if (rc != ET_OK && rc != ET_ERR_UNSUPPORTED) return fail(ctx, rc, "et_encode_pattern");
+    const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
+    std::memset(pattern + pat_bytes, 0, padded + 4 - pat_bytes);  // (and the word the head is read from, for a pattern of no bytes)
+    et::SearchJob job{};
+    job.pat_bits = static_cast<uint32_t>(bits);
+    job.needle_len = static_cast<uint32_t>(needle_len);
+    job.flags = (what == ET_SEARCH_SUFFIX ? et::SEARCH_F_SUFFIX : 0u) | ((mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u) | (rc == ET_ERR_UNSUPPORTED ? et::MATCH_F_NEVER : 0u);
+    job.head_mask = bits >= 32 ? 0xffffffffu : bits ? ~(0xffffffffu >> bits) : 0u;
+    job.head = (static_cast<uint32_t>(pattern[0]) << 24 | static_cast<uint32_t>(pattern[1]) << 16 | static_cast<uint32_t>(pattern[2]) << 8 | pattern[3]) & job.head_mask;
+    res->pattern_bits = job.pat_bits;
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_PATTERN + padded, hipMemcpyHostToDevice, ctx->stream));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_search(ctx->stream, store, ws<const uint2>(ctx, 0), n_codes, ws<const uint32_t>(ctx, PK_PATTERN), job, d_rows, cap_rows, d_pos, d_status, tile_ptrs(ctx, tiles),
+                      ws<uint32_t>(ctx, at_pos), ws<uint32_t>(ctx, at_list), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the search's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
+    res->n_match = rep[et::PACKED_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_rows_emit saw the same two figures)
     return ET_OK;
 }
 

@@ -148,6 +148,45 @@ struct TileWs {  // the tile workspace of the match and the join
 void launch_match(hipStream_t stream, const PackedStore &store, const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status,
                   const TileWs &tiles, const PackedReport &report);
 
+// The search (et_search_packed_device): which records of a packed store CONTAIN, or END WITH, a needle, and where -- judged on the
+// compressed bytes by a walk over the codeword boundaries with nothing written: the needle occurs at symbol i exactly when its bits
+// (et_encode_pattern) lie at the bit where codeword i begins, end inside the body, and i + needle_len <= length.
+//   k_search_flag  one record per lane, tiles of MATCH_TILE records, the sorted codes, the first-level table and the pattern in LDS:
+//                  judged, its status byte; a body of up to SEARCH_LANE_BYTES is walked by its lane alone, from global memory; a
+//                  longer one that can hold the needle goes onto a list in the workspace and counts as "no occurrence" for now; a
+//                  u32 position per record (SEARCH_NONE: none), ballot masks and tile counts as k_match_flag's
+//   k_search_long  one workgroup per listed record (k_packed_decode's shape, decode_stream's blocks without the write half): the
+//                  pattern's head compared at every boundary while the lanes' walks settle -- what a lane's last walk found is the
+//                  settled walk's --, the rest confirmed from global memory, the lowest hit reduced over the workgroup; a record with
+//                  an occurrence gets its position, and thread 0 corrects its bit of the tile's mask and the tile's count by one
+//                  atomic each
+//   k_packed_scan  the tile counts -> the tiles' first places in d_rows, n_match; its report is the call's
+//   k_rows_emit    (unless d_rows is null: count only) the match's, with the positions as the join's key numbers
+// SEARCH_LANE_BYTES is taken from the search_sweep leg of tools/batch_bench.py (profiles/search_bench.json): with
+// records of one size the lane path is the faster one up to bodies of 600 bytes and the slower one at 2 400; 512 leaves room for
+// stores of mixed sizes, where a wavefront waits for its longest body.
+constexpr uint32_t SEARCH_NEEDLE_MAX = 256;                        // bytes of text in a needle
+constexpr uint32_t SEARCH_PATTERN_BYTES = SEARCH_NEEDLE_MAX * 4;   // ... which take at most 32 bits each: 1 KiB, in LDS
+#ifndef ET_SEARCH_LANE_BYTES  // (a build for the sweep sets it: 0 sends every body to a workgroup, 8192 every body of the sweep to a lane)
+#define ET_SEARCH_LANE_BYTES 512
+#endif
+constexpr uint32_t SEARCH_LANE_BYTES = ET_SEARCH_LANE_BYTES;       // bodies up to this many bytes are walked by one lane
+constexpr uint32_t SEARCH_GRID = 2048;                             // workgroups of k_search_flag and k_rows_emit at most
+constexpr uint32_t SEARCH_NONE = 0xffffffffu;                      // the position of a record without an occurrence
+enum SearchFlag : uint32_t { SEARCH_F_SUFFIX = 1 };                // beside MATCH_F_NOT and MATCH_F_NEVER
+enum SearchWord { SEARCH_N_LONG = 4 };                             // the counters' word beside the records' two: records on the list
+struct SearchJob {
+    uint32_t head, head_mask;  // the pattern's first min(32, bits) bits at the top of a word, and which of its bits count
+    uint32_t pat_bits;         // bits of the encoded needle
+    uint32_t needle_len;       // its bytes of text
+    uint32_t flags;            // SearchFlag | MatchFlag
+    uint32_t pad;
+};
+// codes: the sorted codes on the device (launch_shared_decode's); pattern: the encoded needle on the device, zero-padded to a multiple
+// of 4 bytes; pos_of, long_list: a u32 per record each -- workspace.  The report leaves with the scan, in front of k_rows_emit.
+void launch_search(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const uint32_t *pattern, const SearchJob &job, uint32_t *d_rows,
+                   uint64_t cap_rows, uint32_t *d_pos, uint8_t *d_status, const TileWs &tiles, uint32_t *pos_of, uint32_t *long_list, const PackedReport &report);
+
 // The join (et_join_packed_device): which records of a packed store equal SOME key of a key set -- a packed store itself -- decided
 // on the compressed bytes through a hash table in the workspace (et_join.h: the hash, the slot format, the table's size).
 //   (clear)        the table's slots to ET_JOIN_EMPTY: one hipMemsetAsync

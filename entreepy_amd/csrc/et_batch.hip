@@ -23,6 +23,11 @@
 //   match    k_match_flag    one lane per record: judged, compared with the encoded needle on the compressed bytes; ballot masks, tile counts
 //            k_packed_scan   the tile counts -> each tile's first place among the rows, the report
 //            k_rows_emit     the selected record numbers, ascending, by popcount ranks
+//   search   k_search_flag   one lane per record: judged; a short body walked codeword by codeword with the needle's bits compared at every boundary;
+//                            a long one listed; positions, ballot masks, tile counts
+//            k_search_long   one workgroup per listed record: k_packed_decode's walk without its write half, compared on the settled boundaries
+//            k_packed_scan   as in the match
+//            k_rows_emit     as in the match, with the needle's position beside the record's number where asked for
 //   join     k_join_build    one lane per key of a key set: judged, hashed on the compressed bytes, inserted into a table in the workspace
 //            k_join_flag     one lane per record: judged, hashed, probed, every hit confirmed by bytes; ballot masks, tile counts, key numbers
 //            k_packed_scan   as in the match
@@ -290,14 +295,17 @@ struct BatchDecLds {
     uint32_t out[BATCH_STAGE_BYTES / 4 + 2];
 };
 
-__device__ __forceinline__ uint32_t find_code(const BatchDecLds &s, uint32_t n_codes, uint32_t win) {
+// (over bare arrays: k_search_flag keeps the tables without the decode's stages)
+__device__ __forceinline__ uint32_t find_code_in(const uint2 *codes, uint32_t n_codes, uint32_t win) {
     uint32_t lo = 0, hi = n_codes;  // codes[0] is the all-zero code of a full tree: codes[lo].x <= win throughout
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (s.codes[mid].x <= win) lo = mid; else hi = mid;
+        if (codes[mid].x <= win) lo = mid; else hi = mid;
     }
-    return s.codes[lo].y;
+    return codes[lo].y;
 }
+
+__device__ __forceinline__ uint32_t find_code(const BatchDecLds &s, uint32_t n_codes, uint32_t win) { return find_code_in(s.codes, n_codes, win); }
 
 // The lane's walk from `entry` (bits into its subsequence).  Returns its exit; *count = codewords that end at or before
 // the body's last bit (`room` = bits from the lane's first bit to there; <= 0 when the lane lies behind the body).
@@ -331,12 +339,14 @@ __device__ __forceinline__ uint32_t walk(BatchDecLds &s, uint32_t n_codes, uint3
 }
 
 // The first-level table from the sorted codes in s.codes (a barrier lies between their stores and this).
-__device__ __forceinline__ void fill_lut(BatchDecLds &s, uint32_t n_codes) {
+__device__ __forceinline__ void fill_lut_in(const uint2 *codes, uint16_t *lut, uint32_t n_codes) {
     for (uint32_t e = threadIdx.x; e < (1u << BATCH_LUT_BITS); e += BB) {
-        const uint32_t meta = find_code(s, n_codes, e << (32 - BATCH_LUT_BITS));
-        s.lut[e] = (meta >> 8) <= BATCH_LUT_BITS ? static_cast<uint16_t>(meta) : static_cast<uint16_t>(0);
+        const uint32_t meta = find_code_in(codes, n_codes, e << (32 - BATCH_LUT_BITS));
+        lut[e] = (meta >> 8) <= BATCH_LUT_BITS ? static_cast<uint16_t>(meta) : static_cast<uint16_t>(0);
     }
 }
+
+__device__ __forceinline__ void fill_lut(BatchDecLds &s, uint32_t n_codes) { fill_lut_in(s.codes, s.lut, n_codes); }
 
 // One stream under the tables in `s` (k_batch_decode, k_shared_decode): its blocks in order.  Returns the symbols it holds, at
 // most n_symbols; the first write_cap of them are stored.  Every block begins with a barrier: that is the one between
@@ -945,6 +955,288 @@ __global__ __launch_bounds__(BB) void k_rows_emit(const unsigned long long *__re
 }
 
 // --------------------------------------------------------------------------------
+// The search call: which records of a packed store contain (or end with) a needle, and at which symbol, decided on the compressed
+// bytes.  Under one complete prefix-free table the needle occurs at symbol i of a record's stored text exactly when the pattern's
+// bits (et_encode_pattern) lie at the bit where codeword i begins, they end inside the body, and i + needle_len <= length: the
+// parse from a boundary is unique, the same bits at a bit that is no boundary are no occurrence, and the length rejects what the
+// pad bits behind the last codeword read as.  So a search is the decode's walk over the boundaries with a bit comparison at each
+// and nothing written.  Four launches in stream order (et_batch.h), the host waiting for the scan alone.
+// Every loop is bounded: a lane's walk by the record's length (a trip per symbol), the workgroup's by the body's blocks, its fixed
+// point by 256 trips and a lane's walk inside it by its 256 bits -- a complete table (the host's require_complete) makes every step
+// advance.  No workgroup waits for another: k_search_long corrects a mask and a count by atomics nobody waits for.
+// --------------------------------------------------------------------------------
+struct SearchLds {  // k_search_flag's tables: 7 KiB
+    uint2 codes[256];
+    uint16_t lut[1u << BATCH_LUT_BITS];
+    uint32_t pat[SEARCH_PATTERN_BYTES / 4];  // the pattern, big-endian words: bit q of it is bit 31 - q % 32 of word q / 32
+};
+
+// A body as the walks see it: counted in bits from the 4-byte aligned word it begins in (decode_stream's geometry).
+struct BodyBits {
+    const uint32_t *words;
+    uint32_t first_bit, end_bit, n_words;  // the body's first bit, its last + 1, the aligned words that hold a byte of it
+};
+
+__device__ __forceinline__ BodyBits body_bits_of(const uint8_t *d_bodies, uint64_t body_off, uint32_t body_bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_bodies) + body_off;
+    BodyBits g;
+    g.words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
+    g.first_bit = static_cast<uint32_t>(a & 3) * 8;
+    g.end_bit = g.first_bit + body_bytes * 8;
+    g.n_words = (g.end_bit + 31) >> 5;
+    return g;
+}
+
+// Word k of the body, big-endian; zero behind the last word that holds a byte of it (which is never loaded).
+__device__ __forceinline__ uint64_t body_word_be(const BodyBits &g, uint32_t k) { return k < g.n_words ? __builtin_bswap32(g.words[k]) : 0u; }
+
+// The 32 bits from bit `bit` on, from global memory.
+__device__ __forceinline__ uint32_t body_window(const BodyBits &g, uint32_t bit) {
+    const uint32_t k = bit >> 5;
+    return static_cast<uint32_t>((((body_word_be(g, k) << 32) | body_word_be(g, k + 1)) << (bit & 31)) >> 32);
+}
+
+// Do the pattern's bits behind its first 32 lie behind bit `at` + 32 of the body?  The caller has compared the first 32 and knows
+// that at + pat_bits <= end_bit: every word compared under the mask holds a byte of the body.
+__device__ __forceinline__ bool confirm_rest(const uint32_t *pat, uint32_t pat_bits, const BodyBits &g, uint32_t at) {
+    for (uint32_t q = 32; q < pat_bits; q += 32) {
+        const uint32_t left = pat_bits - q, mask = left >= 32 ? 0xffffffffu : ~(0xffffffffu >> left);
+        if ((body_window(g, at + q) ^ pat[q >> 5]) & mask) return false;
+    }
+    return true;
+}
+
+// One lane, one body of a few words, from global memory: a trip per symbol.  At boundary idx (CONTAINS: every one up to `target` =
+// length - needle_len, the last at which an occurrence fits the length; SUFFIX: `target` alone) the pattern is compared -- its head
+// against the window the step needs anyway, the rest by confirm_rest --, then the codeword there is stepped over.  Returns the
+// lowest boundary with an occurrence, or SEARCH_NONE.  64 bits of body are kept in registers and move on a word at a time.
+__device__ __forceinline__ uint32_t search_lane(const SearchLds &t, uint32_t n_codes, const SearchJob &job, const BodyBits &g, uint32_t target) {
+    const bool suffix = job.flags & SEARCH_F_SUFFIX;
+    uint32_t pos = g.first_bit, k = 0;
+    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
+    for (uint32_t idx = 0; idx <= target; ++idx) {
+        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
+            k = pos >> 5;
+            two = (two << 32) | body_word_be(g, k + 1);
+        }
+        const uint32_t win = static_cast<uint32_t>((two << (pos & 31)) >> 32);
+        if (!suffix || idx == target) {
+            if (pos + job.pat_bits > g.end_bit) return SEARCH_NONE;  // (nor does it fit at a later boundary)
+            if (((win ^ job.head) & job.head_mask) == 0 && confirm_rest(t.pat, job.pat_bits, g, pos)) return idx;
+        }
+        uint32_t meta = t.lut[win >> (32 - BATCH_LUT_BITS)];
+        if (!meta) meta = find_code_in(t.codes, n_codes, win);
+        pos += meta >> 8;
+        if (pos > g.end_bit) return SEARCH_NONE;  // the bits ran out inside this codeword: no boundary behind it
+    }
+    return SEARCH_NONE;
+}
+
+// k_search_flag: k_match_flag's tiles, judgement, status bytes, tally, masks and counts, with the sorted codes, the first-level table
+// and the pattern in LDS once per workgroup.  A valid record whose length or body cannot hold the needle has no occurrence and is not
+// read; the empty needle is decided without a walk where the answer needs none; a body of up to SEARCH_LANE_BYTES is walked by its
+// lane (search_lane); a longer one goes onto long_list -- one atomic per wavefront that has any -- and counts as "no occurrence"
+// here: k_search_long corrects the records that have one.  pos_of[b] = the position, or SEARCH_NONE.  LDS 7 KiB + 24 words.
+__global__ __launch_bounds__(BB) void k_search_flag(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, const uint32_t *__restrict__ pattern, SearchJob job,
+                                                    TileWs tiles, uint32_t *__restrict__ pos_of, uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status,
+                                                    unsigned long long *__restrict__ stats) {
+    __shared__ SearchLds t;
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    __shared__ uint32_t s_count[2][BB / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    const uint32_t n_tiles = (store.n + MATCH_TILE - 1) / MATCH_TILE;
+    const bool suffix = job.flags & SEARCH_F_SUFFIX, negate = job.flags & MATCH_F_NOT, never = job.flags & MATCH_F_NEVER;
+    const uint32_t pat_bytes = (job.pat_bits + 7) >> 3;
+    if (tid < n_codes) t.codes[tid] = codes[tid];
+    if (tid < (job.pat_bits + 31) >> 5) t.pat[tid] = __builtin_bswap32(pattern[tid]);  // (at most 256 words)
+    __syncthreads();
+    fill_lut_in(t.codes, t.lut, n_codes);
+    __syncthreads();
+    PackedTally tally;
+    uint32_t set = 0;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, set ^= 1) {
+        const uint32_t b = tile * MATCH_TILE + tid;  // (n <= 0x7fffffff: no wrap)
+        bool valid = false, is_long = false;
+        uint32_t pos = SEARCH_NONE;
+        if (b < store.n) {
+            const Judged rec = judge_record(store, b);
+            if (d_status) d_status[b] = static_cast<uint8_t>(rec.status);
+            tally.note(b, rec.status);
+            if (!rec.status) {
+                valid = true;
+                if (!never && rec.len >= job.needle_len && rec.nb >= pat_bytes) {
+                    const uint32_t len = static_cast<uint32_t>(rec.len);
+                    if (!job.pat_bits && (!suffix || len == 0)) pos = 0;  // the empty needle: everywhere; at the end of an empty record
+                    else if (rec.nb == 0) pos = SEARCH_NONE;              // ... and not at the end of a text that is not there
+                    else if (rec.nb <= SEARCH_LANE_BYTES) pos = search_lane(t, n_codes, job, body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len))), len - job.needle_len);
+                    else is_long = true;
+                }
+                pos_of[b] = pos;
+            }
+        }
+        const unsigned long long longs = __ballot(is_long);
+        if (longs) {  // (the same for the whole wavefront)
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(stats + SEARCH_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
+            base = __shfl(base, 0, 64);
+            if (is_long) long_list[base + __popcll(longs & ((1ull << lane) - 1ull))] = b;
+        }
+        end_tile(valid && (pos != SEARCH_NONE) != negate, tile, set, tiles, s_count);
+    }
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
+// walk<false> with the pattern compared on the way (CONTAINS): at every codeword that ends inside the body the pattern's head is compared
+// with the window the step holds anyway, a pass is confirmed on the rest from global memory (an occurrence may run past the lane's
+// bits and past the staged block).  *hit = how many codewords of THIS walk lie in front of the first such occurrence (SEARCH_NONE:
+// none).  A lane walks again whenever its entry changes, so what its last walk leaves is the settled walk's; `at` = the bit of the
+// body's aligned base at which the lane's bits begin.
+__device__ __forceinline__ uint32_t walk_seek(const BatchDecLds &s, uint32_t n_codes, uint32_t lane_bit, uint32_t entry, int64_t room, uint32_t *count, uint32_t *hit,
+                                              const SearchJob &job, const uint32_t *pat, const BodyBits &g, uint32_t at) {
+    uint32_t pos = entry, cnt = 0, first_hit = SEARCH_NONE;
+    while (pos < 256) {
+        const uint32_t p = lane_bit + pos, k = p >> 5, sh = p & 31;
+        const uint64_t two = (static_cast<uint64_t>(s.bits[padded(k)]) << 32) | s.bits[padded(k + 1)];
+        const uint32_t win = static_cast<uint32_t>((two << sh) >> 32);
+        uint32_t meta = s.lut[win >> (32 - BATCH_LUT_BITS)];
+        if (!meta) meta = find_code(s, n_codes, win);
+        const uint32_t len = meta >> 8;
+        if (static_cast<int64_t>(pos + len) > room) {  // the bits ran out inside this codeword (walk<false>'s rule)
+            pos = 512;
+            break;
+        }
+        if (first_hit == SEARCH_NONE && ((win ^ job.head) & job.head_mask) == 0 && static_cast<int64_t>(pos + job.pat_bits) <= room &&
+            confirm_rest(pat, job.pat_bits, g, at + pos))
+            first_hit = cnt;
+        ++cnt;
+        pos += len;
+    }
+    *count = cnt;
+    *hit = first_hit;
+    return pos;
+}
+
+// SUFFIX: the lane whose codewords -- number `first` and on, from its settled entry -- hold number `target` walks to it and compares there.
+__device__ __forceinline__ bool walk_to(const BatchDecLds &s, uint32_t n_codes, uint32_t lane_bit, uint32_t entry, int64_t room, uint32_t first, uint32_t target,
+                                        const SearchJob &job, const uint32_t *pat, const BodyBits &g, uint32_t at) {
+    uint32_t pos = entry;
+    for (uint32_t idx = first; pos < 256; ++idx) {
+        const uint32_t p = lane_bit + pos, k = p >> 5, sh = p & 31;
+        const uint64_t two = (static_cast<uint64_t>(s.bits[padded(k)]) << 32) | s.bits[padded(k + 1)];
+        const uint32_t win = static_cast<uint32_t>((two << sh) >> 32);
+        if (idx == target)
+            return ((win ^ job.head) & job.head_mask) == 0 && static_cast<int64_t>(pos + job.pat_bits) <= room && confirm_rest(pat, job.pat_bits, g, at + pos);
+        uint32_t meta = s.lut[win >> (32 - BATCH_LUT_BITS)];
+        if (!meta) meta = find_code(s, n_codes, win);
+        pos += meta >> 8;
+    }
+    return false;
+}
+
+// One record by the whole workgroup under the tables in `s`: decode_stream's blocks -- the stage, the fixed point over the lanes'
+// entries, the scan of their counts -- without its write half.  CONTAINS compares inside the fixed point's walks (walk_seek) and
+// believes what each lane's LAST walk found, which is the settled walk's: a third pass over the bits, after the scan, cost as much as
+// the write pass it replaced.  A lane's hit becomes a symbol number once the scan has given its first codeword's, and counts when the
+// length allows it (a lane's later hits lie further on).  SUFFIX compares at one boundary, after the scan (walk_to); of the empty
+// needle it asks only whether boundary `target` = length exists.  The lowest hit is reduced over the workgroup through s_min (4
+// words); the blocks end with the first that has one, or once `target` boundaries lie behind.
+__device__ __forceinline__ uint32_t search_stream(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, uint32_t target, const SearchJob &job, const uint32_t *pat,
+                                                  uint32_t *s_min) {
+    const uint32_t tid = threadIdx.x;
+    const bool suffix = job.flags & SEARCH_F_SUFFIX;
+    const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
+    uint32_t start = g.first_bit, done = 0;  // the block's first codeword; boundaries so far
+    for (uint32_t blk = 0; blk < n_blocks && done <= target; ++blk) {
+        __syncthreads();  // (the block before is done with the stage, entry[BB] and s_min)
+        for (uint32_t k = tid; k < DEC_STAGED; k += BB) s.bits[padded(k)] = static_cast<uint32_t>(body_word_be(g, blk * DEC_WORDS + k));
+        s.entry[tid] = tid == 0 ? start : 0u;
+        __syncthreads();
+        const uint32_t lane_bit = tid * 256, at = blk * DEC_WORDS * 32 + lane_bit;
+        const int64_t room = static_cast<int64_t>(g.end_bit) - at;
+        uint32_t used = 0xffffffffu, exit = 256, count = 0, hit = SEARCH_NONE;
+        for (uint32_t trip = 0; trip < BB; ++trip) {
+            const uint32_t mine = s.entry[tid];
+            int changed = 0;
+            if (mine != used) {
+                const uint32_t was = exit;
+                if (room <= 0) exit = 256u;
+                else if (suffix) exit = walk<false>(s, n_codes, lane_bit, mine, room, &count);
+                else exit = walk_seek(s, n_codes, lane_bit, mine, room, &count, &hit, job, pat, g, at);
+                used = mine;
+                changed = exit != was || trip == 0;
+            }
+            __syncthreads();
+            if (changed) s.entry[tid + 1] = exit - 256;
+            if (!__syncthreads_or(changed)) break;
+        }
+        uint32_t total;
+        const uint32_t first = done + block_exclusive_scan(count, s.wsum, &total);  // (s.wsum: the next block's first barrier lies between two scans)
+        uint32_t found = SEARCH_NONE;
+        if (!suffix) {
+            if (hit != SEARCH_NONE && first + hit <= target) found = first + hit;
+        } else if (!job.pat_bits) {
+            if (done + total >= target) found = target;  // (the same for every lane)
+        } else if (first <= target && target < first + count && walk_to(s, n_codes, lane_bit, used, room, first, target, job, pat, g, at)) {
+            found = target;
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const uint32_t other = __shfl_xor(found, d, 64);
+            if (other < found) found = other;
+        }
+        if ((tid & 63) == 0) s_min[tid >> 6] = found;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < BB / 64; ++w)
+            if (s_min[w] < found) found = s_min[w];
+        if (found != SEARCH_NONE) return found;  // (the same for every lane; boundaries ascend with the blocks: the lowest)
+        start = s.entry[BB];
+        done += total;
+    }
+    return SEARCH_NONE;
+}
+
+// k_search_long: k_packed_decode's shape over long_list -- the sorted codes and the first-level table once per workgroup, the listed
+// records strided; the pattern (big-endian words) and the reduction's 4 words lie in the stage the decode keeps its symbols in.  A
+// workgroup beyond the list returns before it sets anything up: a store of short records pays a launch of empty workgroups.  A record
+// with an occurrence: pos_of[b] = its position, and thread 0 turns the record's bit of its tile's mask and moves the tile's count by
+// one (k_search_flag left "no occurrence" there; the scan runs behind this kernel).  LDS as k_batch_decode.
+__global__ __launch_bounds__(BB) void k_search_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, const uint32_t *__restrict__ pattern, SearchJob job,
+                                                    TileWs tiles, uint32_t *__restrict__ pos_of, const uint32_t *__restrict__ long_list,
+                                                    const unsigned long long *__restrict__ stats) {
+    __shared__ BatchDecLds s;
+    static_assert(SEARCH_PATTERN_BYTES / 4 + BB / 64 <= sizeof(s.out) / 4, "the pattern and s_min in the symbol stage");
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n_long = static_cast<uint32_t>(stats[SEARCH_N_LONG]);
+    if (blockIdx.x >= n_long) return;
+    uint32_t *pat = s.out, *s_min = s.out + SEARCH_PATTERN_BYTES / 4;
+    if (tid < n_codes) s.codes[tid] = codes[tid];
+    if (tid < (job.pat_bits + 31) >> 5) pat[tid] = __builtin_bswap32(pattern[tid]);
+    __syncthreads();
+    fill_lut(s, n_codes);
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
+        const uint32_t b = long_list[i];
+        const Judged rec = judge_record(store, b);
+        if (rec.status || rec.len < job.needle_len || rec.nb == 0) continue;  // (k_search_flag lists no such record; the same for every lane)
+        const uint32_t len = static_cast<uint32_t>(rec.len);
+        const uint32_t found = search_stream(s, n_codes, body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len))), len - job.needle_len, job, pat, s_min);
+        if (tid == 0 && found != SEARCH_NONE) {
+            pos_of[b] = found;
+            const unsigned long long bit = 1ull << (b & 63);
+            if (job.flags & MATCH_F_NOT) {
+                atomicAnd(tiles.masks + (b >> 6), ~bit);
+                atomicSub(tiles.counts + b / MATCH_TILE, 1u);
+            } else {
+                atomicOr(tiles.masks + (b >> 6), bit);
+                atomicAdd(tiles.counts + b / MATCH_TILE, 1u);
+            }
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------
 // The join call: which records of a packed store equal SOME key of a key set, itself a packed store under the same table, decided on
 // the compressed bytes.  Under one table the encoder is deterministic, so two records have the same text exactly when they have the
 // same length (symbols), the same body byte count and the same body bytes -- for bodies as the encoders write them; a body of no
@@ -1484,6 +1776,16 @@ void launch_match(hipStream_t stream, const PackedStore &store, const uint32_t *
     const uint32_t n_tiles = tiles_of(store.n), grid = capped(n_tiles, MATCH_GRID);
     hipLaunchKernelGGL(k_match_flag, dim3(grid), dim3(BB), 0, stream, store, pattern, job, tiles, d_status, r.stats);
     launch_scan_emit(stream, n_tiles, grid, tiles, d_rows, cap_rows, nullptr, nullptr, r);
+}
+
+void launch_search(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const uint32_t *pattern, const SearchJob &job, uint32_t *d_rows,
+                   uint64_t cap_rows, uint32_t *d_pos, uint8_t *d_status, const TileWs &tiles, uint32_t *pos_of, uint32_t *long_list, const PackedReport &r) {
+    const uint32_t n_tiles = tiles_of(store.n), grid = capped(n_tiles, SEARCH_GRID);
+    hipLaunchKernelGGL(k_search_flag, dim3(grid), dim3(BB), 0, stream, store, codes, n_codes, pattern, job, tiles, pos_of, long_list, d_status, r.stats);
+    if (!(job.flags & MATCH_F_NEVER))  // (nothing was listed)
+        hipLaunchKernelGGL(k_search_long, dim3(capped(store.n, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, codes, n_codes, pattern, job, tiles, pos_of,
+                           static_cast<const uint32_t *>(long_list), static_cast<const unsigned long long *>(r.stats));
+    launch_scan_emit(stream, n_tiles, grid, tiles, d_rows, cap_rows, pos_of, d_pos, r);
 }
 
 void launch_packed_encode(hipStream_t stream, const void *d_text, uint64_t text_bytes, const uint64_t *text_index, uint32_t n, void *d_out, uint64_t cap,

@@ -418,6 +418,48 @@ int et_match_packed_device(et_ctx *ctx, const et_codebook *cb,
                            const uint8_t *needle, size_t needle_len, int mode,   /* needle: HOST memory */
                            uint32_t *d_rows, size_t cap_rows, uint8_t *d_status, et_match_result *res);
 
+/* SEARCH: which records of a packed store CONTAIN a needle, or END with it, and at which symbol -- key LIKE '%x%' and key LIKE '%x' --
+ * found on the device WITHOUT decoding: the decode's walk over the codeword boundaries with a bit comparison at each and nothing
+ * written.  Under one complete prefix-free table the needle occurs at symbol i of a record's text exactly when its bits
+ * (et_encode_pattern) lie at the bit where codeword i begins, end inside the body, and i + needle_len <= length_b: the parse from a
+ * boundary is unique, the same bits at a bit that is no boundary are no occurrence, and the length bound rejects what the pad bits
+ * behind the last codeword read as.
+ *   The store, the judgement of a record from its own two pairs, d_status, d_rows, cap_rows, ET_MATCH_NOT and *res are the match
+ *     call's: a failed record is never read and never selected -- not under ET_MATCH_NOT either -- and fails alone.
+ *   text_b is what et_decode_packed_device would store for record b: the first n_b = min(length_b, codewords that end inside its
+ *     body) symbols.  ET_SEARCH_CONTAINS: the needle occurs in text_b; its position is the lowest symbol index, text_b.find(needle).
+ *     ET_SEARCH_SUFFIX: n_b == length_b and text_b ends with the needle; its position is length_b - needle_len -- so a record whose
+ *     body ends before its length never matches SUFFIX, as it never matches ET_MATCH_EQUAL, and can match CONTAINS on what is
+ *     there.  The empty needle: CONTAINS selects every valid record at position 0, SUFFIX every valid record with n_b == length_b
+ *     at position length_b.  A needle byte without a code matches nothing: the call is ET_OK, pattern_bits is 0, and under NOT
+ *     every valid record is selected.  needle is HOST memory.
+ *   d_rows[0 .. n_match): the selected record numbers, ascending -- the gather and take calls' d_rows; nothing at or beyond
+ *     d_rows + n_match is written.  d_rows == NULL: count only.  n_match > cap_rows: ET_ERR_CAP, no entry of d_rows or d_pos is
+ *     written, d_status is complete and res->n_match is the room needed.
+ *   d_pos (may be NULL; 32 bits each, 4-byte aligned, as large as d_rows and written only where d_rows is): d_pos[i] = the position
+ *     in record d_rows[i].
+ *   et_search_lane_bytes(): a body of up to this many bytes is walked by one lane, a longer one by a workgroup -- for tests that
+ *     want records on both sides; the answer does not depend on it.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_bodies, d_body_index or d_text_index; a null needle with
+ * needle_len > 0; an offset array that is not 8-byte aligned, d_rows or d_pos not 4-byte aligned; n_records above 0x7fffffff;
+ * needle_len above et_search_needle_max(); an unknown mode; d_pos with ET_MATCH_NOT, or with d_rows == NULL -- all checked before
+ * anything touches a device, *res untouched), ET_ERR_UNSUPPORTED (the table is not complete: nothing is enqueued), ET_ERR_CAP,
+ * ET_ERR_HIP, ET_ERR_NOMEM.  n_records == 0: ET_OK, nothing enqueued, *res zeroed.  One upload (the sorted codes, zeroed counters
+ * and the encoded needle, 3.2 KiB at most), four launches and one hand-over per call; stream-ordered like the other packed calls --
+ * *res is final on return, the device arrays once the ctx's stream has drained -- and it may follow or precede any of them on one
+ * ctx with nothing in between: d_rows may go straight into et_decode_packed_gather_device or et_take_packed_device.
+ * Out of scope: case folding and wildcards inside the needle, several needles per call, counting every occurrence, needles above
+ * et_search_needle_max() and records above et_batch_small_max(). */
+enum { ET_SEARCH_CONTAINS = 0, ET_SEARCH_SUFFIX = 1 };   /* ET_MATCH_NOT may be or-ed in */
+size_t et_search_needle_max(void);          /* longest needle in bytes of text: 256 */
+size_t et_search_lane_bytes(void);          /* bodies up to this many bytes are walked by one lane */
+int et_search_packed_device(et_ctx *ctx, const et_codebook *cb,
+                            const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                            const uint64_t *d_text_index, size_t n_records,
+                            const uint8_t *needle, size_t needle_len, int mode,   /* needle: HOST memory */
+                            uint32_t *d_rows, size_t cap_rows, uint32_t *d_pos,
+                            uint8_t *d_status, et_match_result *res);
+
 /* JOIN: which records of a packed store equal SOME key of a key set -- itself a packed store under the same table, in device
  * memory (e.g. what et_encode_packed_device made of a key column, or a run of another store) -- decided on the compressed bytes:
  * key IN (...), a semi-join against another table's key column, with ET_MATCH_NOT an anti-join.  One build pass over the keys (a

@@ -42,7 +42,16 @@ process of its own so that every leg loads exactly one build of the library:
                   the call's time over that copy's.  With it runs take_baseline, what the call replaces -- et_decode_packed_gather_device
                   of the rows, then et_encode_packed_device of that text -- on this tree's library or on the one named by --batch-lib (a
                   build of the commit before the call).  Both check their bodies against slices of the store's first.
---legs picks the legs (default: all).
+  search          the match leg's three stores with a 12-byte needle planted at a random position in 0.1 % and in 10 % of the records (and at
+                  the end of every second of those): et_search_packed_device under CONTAINS -- with positions, and count only -- and under
+                  SUFFIX, its rows and positions checked against the plain texts first.
+  search_baseline the first step of anything that searches by decoding, and the only part of it this library has:
+                  et_decode_packed_device of the same store -- on this tree's library or on the one named by --batch-lib (a build of the
+                  commit before the call).
+  search_sweep    (only when named) stores of 16 MiB of text in records of 32 .. 4096 bytes, CONTAINS: the times from which
+                  SEARCH_LANE_BYTES is chosen -- run it on builds with -DET_SEARCH_LANE_BYTES=0 and =8192 (ET_LIB_PATH names the library)
+                  for the two paths at every size.
+--legs picks the legs (default: all but search_sweep).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
 text once before timing.  One JSON line on stdout (and into --out).
@@ -54,6 +63,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs match --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/match_bench.json
     python tools/batch_bench.py --legs join --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/join_bench.json
     python tools/batch_bench.py --legs take --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/take_bench.json
+    python tools/batch_bench.py --legs search --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/search_bench.json
 """
 import argparse
 import ctypes
@@ -426,6 +436,137 @@ def _match_leg(leg, lib_path, shapes):
     print(json.dumps(results))
 
 
+SEARCH_NEEDLE_LEN = 12
+SEARCH_SELECTIVITIES = (("0.1%", 0.001), ("10%", 0.1))
+SWEEP_SIZES = (32, 64, 96, 128, 192, 256, 384, 512, 1024, 4096)  # bytes of text per record of the sweep's stores ...
+SWEEP_BYTES = 16 << 20                                            # ... of this much text each
+
+
+def _search_store(count, size, fraction):
+    """-> (text, text_index, needle, (rows that contain it, where, rows that end with it)): `count` text-like records, as long as
+    `size` says (a number, or a range); a 12-byte needle planted at a random position in `fraction` of them, and at the end of every
+    second of those as well.  The expected rows are Python's find and endswith over the plain texts."""
+    import numpy as np
+
+    from tests import corpus
+
+    rng = np.random.default_rng(0x5EA2C4 + count + int(fraction * 1000))
+    lengths = np.full(count, size) if isinstance(size, int) else rng.integers(size[0], size[1] + 1, size=count)
+    index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+    host = corpus.text_like(int(index[-1]), 0xB47C4 + count).copy()
+    needle = corpus.text_like(4096, 0x5EA2C4)[-SEARCH_NEEDLE_LEN:].copy()
+    for j, b in enumerate(rng.choice(count, size=max(int(count * fraction), 1), replace=False)):
+        at = int(index[b]) + int(rng.integers(0, int(lengths[b]) - SEARCH_NEEDLE_LEN + 1))
+        host[at : at + SEARCH_NEEDLE_LEN] = needle
+        if j % 2:
+            host[int(index[b + 1]) - SEARCH_NEEDLE_LEN : int(index[b + 1])] = needle
+    blob, nd = host.tobytes(), needle.tobytes()
+    rows, pos, ends = [], [], []
+    for b in range(count):
+        t = blob[int(index[b]) : int(index[b + 1])]
+        p = t.find(nd)
+        if p >= 0:
+            rows.append(b)
+            pos.append(p)
+            if t.endswith(nd):
+                ends.append(b)
+    return host, index, nd, (rows, pos, ends)
+
+
+def _search_leg(leg, lib_path, shapes):
+    """search / search_baseline / search_sweep: per shape and selectivity a packed store (et_encode_packed_device, untimed), then the
+    timed call: et_search_packed_device under CONTAINS (with positions, and count only) and SUFFIX, its rows and positions checked
+    against the plain texts first -- or the first step of anything that searches by decoding: et_decode_packed_device of the whole
+    store.  search_sweep: stores of SWEEP_BYTES of text in records of one size each, 10 % of them with the needle, under CONTAINS;
+    which path a size takes is the library's et_search_lane_bytes(), reported beside the times."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
+             "et_decode_packed_device"] + ([] if leg == "search_baseline" else ["et_search_packed_device", "et_search_lane_bytes"])
+    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
+    dev = torch.device("cuda", 0)
+    h = ctypes.c_void_p()
+    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
+    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+
+    def timed(fn):
+        ms = []
+        for rep in range(WARMUP + REPS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep >= WARMUP:
+                ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+    sweep = leg == "search_sweep"
+    results = {"lane_bytes": int(L.et_search_lane_bytes())} if sweep else {}
+    for count, size in [(SWEEP_BYTES // s, s) for s in SWEEP_SIZES] if sweep else SHAPES + [KEY_SHAPE]:
+        shape_name = f"{count}x{size}" if isinstance(size, int) else f"{count}x{size[0]}-{size[1]}"
+        if shapes and shape_name not in shapes:
+            continue
+        shape = {}
+        for sel_name, fraction in SEARCH_SELECTIVITIES[1:] if sweep else SEARCH_SELECTIVITIES:
+            host, index, needle, (rows, pos, ends) = _search_store(count, size, fraction)
+            text = torch.from_numpy(host).to(dev)
+            hist = np.bincount(host, minlength=256).astype(np.uint64)
+            cb = N.Codebook()
+            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+            total = int(index[-1])
+            cap = L.et_body_bound(ctypes.byref(cb), total) + count
+            bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+            text_index = torch.from_numpy(index.view(np.int64)).to(dev)
+            body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+            res = N.PackedResult()
+            assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
+                                             ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+            body_bytes = int(res.out_bytes)
+            torch.cuda.synchronize()
+            entry = {"records": count, "text_bytes": total, "body_bytes": body_bytes, "needle_bytes": len(needle), "contain": len(rows), "end_with": len(ends)}
+            if leg == "search_baseline":
+                dec = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
+
+                def decode():
+                    assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, dec.data_ptr(), total, None,
+                                                     None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.n_failed == 0 and res.n_short == 0
+
+                decode()
+                torch.cuda.synchronize()
+                assert torch.equal(dec[:total], text), "decoded bytes differ from the text"
+                entry["decode"] = timed(decode)
+                del dec
+            else:
+                d_rows, d_pos = torch.zeros(count, dtype=torch.int32, device=dev), torch.zeros(count, dtype=torch.int32, device=dev)
+                mres = N.MatchResult()
+
+                def call(mode, rows_t=d_rows, pos_t=d_pos):
+                    assert L.et_search_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, needle, len(needle), mode,
+                                                     None if rows_t is None else rows_t.data_ptr(), count, None if pos_t is None else pos_t.data_ptr(), None, ctypes.byref(mres)) == 0, L.et_last_error(h)
+                    assert mres.n_failed == 0
+
+                for name, mode, want in (("contains", N.ET_SEARCH_CONTAINS, rows), ("suffix", N.ET_SEARCH_SUFFIX, ends)):
+                    call(mode)
+                    torch.cuda.synchronize()
+                    assert mres.n_match == len(want) and d_rows[: mres.n_match].tolist() == want, "the rows differ from the plain texts'"
+                    if name == "contains":
+                        assert d_pos[: mres.n_match].tolist() == pos, "the positions differ from the plain texts'"
+                    if sweep and name == "suffix":
+                        continue
+                    entry[name] = {"rows": int(mres.n_match), **timed(lambda: call(mode))}
+                entry["contains"]["count_only"] = timed(lambda: call(N.ET_SEARCH_CONTAINS, None, None))
+            shape[sel_name] = entry
+            del text, bodies
+        results[shape_name] = shape
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 JOIN_KEYS = (16, 1024, 65536)
 JOIN_SELECTIVITIES = (("0.1%", 0.001), ("10%", 0.1))
 
@@ -664,7 +805,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take,search")
     ap.add_argument("--shapes", default="")  # (the match legs: a comma list of shape names, e.g. 262144x16-48; default: all)
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
@@ -672,6 +813,8 @@ def main():
     a = ap.parse_args()
     if a.leg and a.leg.startswith("match"):
         return _match_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
+    if a.leg and a.leg.startswith("search"):
+        return _search_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg and a.leg.startswith("join"):
         return _join_leg(a.leg, a.lib)
     if a.leg and a.leg.startswith("take"):
@@ -691,6 +834,10 @@ def main():
         legs += [("join_baseline", "join_baseline", a.batch_lib or here), ("join", "join", here)]
     if "take" in a.legs.split(","):
         legs += [("take_baseline", "take_baseline", a.batch_lib or here), ("take", "take", here)]
+    if "search" in a.legs.split(","):
+        legs += [("search_baseline", "search_baseline", a.batch_lib or here), ("search", "search", here)]
+    if "search_sweep" in a.legs.split(","):
+        legs += [("search_sweep", "search_sweep", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
     for name, leg, lib in legs:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--lib", lib, "--shapes", a.shapes], capture_output=True, text=True, timeout=600)
@@ -710,6 +857,9 @@ def main():
         out["gather_identity_extra_ms"] = {k: round(v["identity"]["ms"] - v["identity"]["packed_decode"]["ms"] - v["identity"]["sizes_only"]["ms"], 4) for k, v in out["gather"].items()}
     if "match" in out:  # > 1: the match call is the faster one
         out["match_vs_baseline"] = {k: {sel: {m: round(out["match_baseline"][k][sel][m]["ms"] / e[m]["ms"], 2) for m in ("prefix", "equal")} for sel, e in v.items()} for k, v in out["match"].items()}
+    if "search" in out:  # > 1: the search is faster than the decode of the whole store, the first step of a search by decoding
+        out["search_vs_decode"] = {k: {sel: {m: round(out["search_baseline"][k][sel]["decode"]["ms"] / e[m]["ms"], 2) for m in ("contains", "suffix")} for sel, e in v.items()}
+                                   for k, v in out["search"].items()}
     if "join" in out:  # > 1: the join call is the faster one
         out["join_vs_baseline"] = {k: {keys: {sel: round(out["join_baseline"][k][keys][sel]["ms"] / e["ms"], 2) for sel, e in v.items()} for keys, v in shape.items()}
                                    for k, shape in out["join"].items()}
