@@ -18,9 +18,14 @@
 #include <cstring>
 #include <string>
 
+// What a workspace holds BETWEEN calls (include/entreepy_hip.h, "STATE A CTX KEEPS BETWEEN CALLS"): a buffer that ensure() has to
+// replace takes what it held with it, and the link that named it is dropped there.
+enum Holds : uint32_t { HOLDS_NOTHING = 0, HOLDS_HISTOGRAM = 1, HOLDS_RANGE = 2 };
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    uint32_t holds = HOLDS_NOTHING;
 };
 
 constexpr size_t HEADER_STAGE = 8192;  // >= 4631-byte worst-case header, padded
@@ -71,13 +76,17 @@ struct et_ctx {
     std::string err;
 
     // encode workspaces
-    DevBuf tile_hist, block_hist, hist, tile_bits, tile_off, enc_table, group_sum;
+    DevBuf tile_hist{nullptr, 0, HOLDS_HISTOGRAM}, hist{nullptr, 0, HOLDS_HISTOGRAM};  // the link between et_histogram_device and the shard encode
+    DevBuf block_hist, tile_bits, tile_off, enc_table, group_sum;
     // decode workspaces
     // flag: the et::DEC_FLAG_WORDS words the decode's kernels and the host share (et_kernels.h DecFlag); lut: all decode tables, DEC_TABLES_BYTES
-    DevBuf sub_state, blk_exit, blk_count, blk_off, lut, flag, worklist;
-    DevBuf lane_maps, blk_maps, grp_maps, blk_in, grp_in;  // exhaustive synchronisation only
+    // (HOLDS_RANGE: what a held range -- `range` below -- reads again in et_decode_range_resolve and et_decode_range_write)
+    DevBuf sub_state{nullptr, 0, HOLDS_RANGE}, blk_exit{nullptr, 0, HOLDS_RANGE}, blk_count{nullptr, 0, HOLDS_RANGE}, blk_off{nullptr, 0, HOLDS_RANGE};
+    DevBuf lut{nullptr, 0, HOLDS_RANGE}, flag{nullptr, 0, HOLDS_RANGE}, worklist;
+    DevBuf lane_maps{nullptr, 0, HOLDS_RANGE}, blk_maps{nullptr, 0, HOLDS_RANGE}, grp_maps{nullptr, 0, HOLDS_RANGE}, blk_in, grp_in;  // exhaustive synchronisation only
     DevBuf row_scratch;                                    // the row walk's published words and ticket (et_rowsync.h)
-    DevBuf tw_table, tw_tree, blk_start, blk_pub, chain_table;  // tree-walk synchronisation, chained write tables (et_treewalk.h)
+    // tree-walk synchronisation, chained write tables (et_treewalk.h)
+    DevBuf tw_table{nullptr, 0, HOLDS_RANGE}, tw_tree{nullptr, 0, HOLDS_RANGE}, blk_start{nullptr, 0, HOLDS_RANGE}, blk_pub, chain_table{nullptr, 0, HOLDS_RANGE};
     et::TwUpload *h_tw_tree[2] = {};                       // pinned, used in turn like h_lut_buf
     int tw_turn = 0;
     // staging for the host-pointer / file-descriptor entry points
@@ -173,6 +182,10 @@ inline int ensure(et_ctx *ctx, DevBuf &b, size_t bytes) {
         ET_HIP(hipFree(b.p));
         b.p = nullptr;
         b.cap = 0;
+        // What the buffer held is gone: the calls that would read it again find no first call (hist_empty stays: an empty
+        // text's histogram is zeros, which et_histogram_host hands out without the device).
+        if (b.holds & HOLDS_HISTOGRAM) ctx->hist_text = nullptr;
+        if (b.holds & HOLDS_RANGE) ctx->range.valid = ctx->range.maps_valid = false;
     }
     const size_t want = (bytes + 4095) & ~static_cast<size_t>(4095);
     hipError_t e = hipMalloc(&b.p, want);

@@ -116,6 +116,7 @@ extern "C" int et_selftest_decode_tables(et_ctx *ctx, const et_codebook *cb, int
     *where = 0;
     if (cb->max_length > 32 || cb->n_coded == 0) return fail(ctx, ET_ERR_UNSUPPORTED, "no decode tables for this code table");
     DeviceGuard guard(ctx->device);
+    ctx->range.valid = ctx->range.maps_valid = false;  // shares the tables (ctx->lut)
     et::DecodeTables tb, tbw;
     ET_TRY(prepare_decode_tables(ctx, cb, &tb, &tbw));  // the device's (unless ET_DEC_TABLES_HOST=1: then this compares the host's with themselves)
     std::vector<uint8_t> dev(DEC_TABLES_BYTES);
@@ -147,6 +148,7 @@ extern "C" int et_selftest_treewalk_table(et_ctx *ctx, const et_codebook *cb, ui
     if (!ctx || !cb || !first_diff) return ET_ERR_ARG;
     *first_diff = 0;
     DeviceGuard guard(ctx->device);
+    ctx->range.valid = ctx->range.maps_valid = false;  // shares the tables (ctx->tw_table, ctx->chain_table)
     et::TwUpload *up = ctx->h_tw_tree[0];
     et::TwTree *tree = &up->tree;
     ET_HIP(hipStreamSynchronize(ctx->stream));

@@ -83,7 +83,21 @@ void et_ctx_destroy(et_ctx *ctx);
  * after all the work the ctx enqueued before it, so the ctx may move between streams
  * with its calls in flight.  The old stream must still be valid at the moment of the
  * switch.  A buffer the ctx wrote on stream A and a later ctx call reads on stream B is
- * therefore safe; ordering against work that is not the ctx's stays the caller's job. */
+ * therefore safe; ordering against work that is not the ctx's stays the caller's job.
+ * STATE A CTX KEEPS BETWEEN CALLS.  Two pairs of calls belong together through the ctx's workspaces:
+ *   et_histogram_device(d_text, n)  ->  et_encode_body_device / et_encode_head_shard_device of the same (d_text, n), and
+ *       et_histogram_host, et_histogram_device_ptr, et_histogram_on_host (the histogram link);
+ *   et_decode_range_sync, or et_decode_range_maps -> et_decode_range_resolve  ->  et_decode_range_write (the held range).
+ * Any other call of the ctx may come between the two halves, and then exactly one of two things holds: the second half gives what
+ * it gives without that call, or it returns ET_ERR_ARG, enqueues nothing and writes nothing, and et_last_error names the first
+ * half that is missing.  What drops the histogram link: a histogram of another text -- et_histogram_device, or a whole encode
+ * (et_encode_device, et_encode, et_encode_fd, a stream that et_encode_batch_device hands to et_encode_device), after which the link
+ * names THAT text --, et_ctx_set_tile_rounds, and any call that has to replace a workspace the histograms lie in (et_ctx_reserve
+ * for a larger text).  What drops the held range: a whole-stream decode (et_decode_device, et_decode, et_decode_fd,
+ * et_decode_body_device, a stream that et_decode_batch_device hands to et_decode_device), et_selftest_decode_tables and
+ * et_selftest_treewalk_table (they rebuild the tables), and any call that has to replace a workspace the range lies in
+ * (et_ctx_reserve again); another et_decode_range_sync / _maps puts its own range in place.  Everything else -- stream switches,
+ * timing, the batched, shared-table and packed calls, the other pair's calls -- leaves both alone (tests/retained.py is the table). */
 int et_ctx_set_stream(et_ctx *ctx, void *hip_stream);
 /* Back to the non-blocking stream the ctx created for itself (a switch, as above). */
 int et_ctx_use_own_stream(et_ctx *ctx);
