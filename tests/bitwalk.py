@@ -313,3 +313,132 @@ def merge_distances(L, is_boundary, lane_bits=LANE_BITS, run_in_bits=RUN_IN_BITS
         dist[live[cut]] = n - p0[live[cut]]
         live, pos = live[~stuck], (pos + step)[~stuck]
     return dist
+
+
+# ---- streams too long to hold bit by bit: the true chain from the text's code lengths, the walks in pieces ----------------------
+
+
+class TextBounds:
+    """The true codeword boundaries of a text packed from first_bit (boundaries()) without an entry per symbol: the sums of
+    every `every` code lengths are kept, a stretch of boundaries is worked out when asked for."""
+
+    def __init__(self, first_bit, length, text, every=4096):
+        self.lens = np.asarray(length, np.uint8)[np.asarray(text, np.uint8)]
+        self.every = every
+        whole = self.lens.size // every * every
+        sums = self.lens[:whole].reshape(-1, every).sum(axis=1, dtype=np.int64)
+        self.coarse = first_bit + np.concatenate([[0], np.cumsum(sums)])  # where symbol k * every begins
+        self.end = int(self.coarse[-1]) + int(self.lens[whole:].sum(dtype=np.int64))  # where the last codeword ends
+
+    def between(self, lo, hi):
+        """The boundaries p with lo <= p < hi, as int64: where the codewords begin, and where the last one ends."""
+        k0 = max(int(np.searchsorted(self.coarse, lo, side="right")) - 1, 0)
+        k1 = int(np.searchsorted(self.coarse, hi, side="left"))
+        lens = self.lens[k0 * self.every : k1 * self.every]
+        p = int(self.coarse[k0]) + np.concatenate([[0], np.cumsum(lens, dtype=np.int64)])
+        return p[(p >= lo) & (p < hi)]
+
+
+def _lengths16(piece, data, length):
+    """next_table's L for a table whose longest codeword has 16 bits or fewer, by ONE lookup of the 16 bits that begin at every
+    bit (the table is prefix-free: at most one codeword is a prefix of them); the last two bytes of `piece` are only read."""
+    lut = np.zeros(1 << 16, np.uint8)
+    for s in np.flatnonzero(length).tolist():
+        l, c = int(length[s]), int(data[s])
+        lut[c << (16 - l) : (c + 1) << (16 - l)] = l
+    b = piece.astype(np.uint32)
+    v = (b[:-2] << np.uint32(16)) | (b[1:-1] << np.uint32(8)) | b[2:]
+    w = (v[:, None] >> (8 - np.arange(8, dtype=np.uint32))[None, :]) & np.uint32(0xFFFF)
+    return lut[w.reshape(-1)]
+
+
+def _piece(stream, lo_bit, hi_bit, data, length, bounds, unmatched):
+    """next_table's L (and C) and the true chain's flags for the bits [lo_bit, hi_bit) of a stream (lo_bit a multiple of 8),
+    four more bytes read behind them for the codewords that reach over -> (L, C or None, on_chain with one more entry, for
+    hi_bit)."""
+    stream = np.frombuffer(bytes(stream), dtype=np.uint8) if not isinstance(stream, np.ndarray) else stream
+    data, length = np.asarray(data, np.uint32), np.asarray(length, np.uint8)
+    n = (hi_bit - lo_bit + 7) // 8
+    piece = np.zeros(n + 4, np.uint8)
+    got = stream[lo_bit // 8 : lo_bit // 8 + n + 4]
+    piece[: got.size] = got
+    if int(length.max()) <= 16:
+        L = _lengths16(piece, data, length)[: hi_bit - lo_bit]
+    else:
+        L = next_table(piece, data, length)[0][: hi_bit - lo_bit]
+    C = None
+    if unmatched == "skip":
+        C = L > 0
+        L[~C] = 1
+    on = np.zeros(hi_bit - lo_bit + 1, bool)
+    on[bounds.between(lo_bit, hi_bit + 1) - lo_bit] = True
+    return L, C, on
+
+
+def seam_walks(stream, first_bit, data, length, text, run_in_bits=RUN_IN_BITS, reach=1024, unmatched="skip", bounds=None):
+    """What the first lane of every block b >= 1 makes of its blind run-in, walked at the seams only: from run_in_bits in front
+    of the block's first bit, as if a codeword began there, to the first position at or behind that bit -> (blind, true,
+    merged), one entry per block from block 1 on, in bits behind the block's first bit: where the blind walk stands, where the
+    true chain's first codeword of the block begins, and where the blind walk first stands on the true chain (-1: not within
+    `reach` bits).  A sweep's first lane of a block that nobody hands a start begins at `blind`; the block before it ends on
+    `true`."""
+    n_bits = len(stream) * 8
+    bounds = bounds or TextBounds(first_bit, length, text)
+    seams = np.arange(1, (n_bits + BLOCK_BITS - 1) // BLOCK_BITS, dtype=np.int64) * BLOCK_BITS
+    blind, true, merged = (np.full(seams.size, -1, np.int64) for _ in range(3))
+    for i, seam in enumerate(seams.tolist()):
+        lo, hi = seam - run_in_bits, min(seam + reach, n_bits)
+        assert lo % 8 == 0
+        L, _, on = _piece(stream, lo, hi, data, length, bounds, unmatched)
+        ahead = np.flatnonzero(on[run_in_bits:])
+        true[i] = ahead[0] if ahead.size else -1
+        p = 0
+        while p < hi - lo:
+            if p >= run_in_bits:
+                if blind[i] < 0:
+                    blind[i] = p - run_in_bits
+                if on[p]:
+                    merged[i] = p - run_in_bits
+                    break
+            if not L[p]:
+                break  # (unmatched="stop": nothing says how to go on)
+            p += int(L[p])
+    return blind, true, merged
+
+
+def listed_after_first_sweep(stream, first_bit, data, length, text, **kw):
+    """-> (the blocks b >= 1 whose first lane's blind run-in leaves it another start than the true one -- what a check of
+    every block's start against the exit of the block before it lists, where nothing has settled the block's first lane --,
+    seam_walks' merged for them)."""
+    blind, true, merged = seam_walks(stream, first_bit, data, length, text, **kw)
+    wrong = np.flatnonzero(blind != true)
+    return wrong + 1, merged[wrong]
+
+
+def unsettled_block_runs_by_text(stream, first_bit, data, length, text, lanes=((LANE_BITS, RUN_IN_BITS),), unmatched="skip", piece_blocks=64, bounds=None):
+    """unsettled_block_runs for a stream of many megabytes whose text is at hand, for several lane geometries (lane_bits,
+    run_in_bits) at once -> one array per geometry: the true chain from the text's code lengths (TextBounds) instead of a walk,
+    the table and the lanes' blind walks in pieces of piece_blocks blocks -- a piece begins a lane early, so that its first lane
+    has its run-in, and ends a lane and a run-in late, so that no walk of its lanes leaves it.  The same figures as
+    unsettled_block_runs (tests/test_repairs_host.py holds the two against each other)."""
+    stream = np.frombuffer(bytes(stream), dtype=np.uint8) if not isinstance(stream, np.ndarray) else stream
+    n_bits = stream.size * 8
+    bounds = bounds or TextBounds(first_bit, length, text)
+    n_blocks = (n_bits + BLOCK_BITS - 1) // BLOCK_BITS
+    widest = max(l for l, _ in lanes)
+    dist = [np.zeros((n_bits + l - 1) // l, np.int64) for l, _ in lanes]
+    for b0 in range(0, n_blocks, piece_blocks):
+        b1 = min(b0 + piece_blocks, n_blocks)
+        lo = max(b0 * BLOCK_BITS - widest, 0)
+        hi = min(b1 * BLOCK_BITS + widest + max(r for _, r in lanes) + 64, n_bits)
+        L, C, on = _piece(stream, lo, hi, data, length, bounds, unmatched)
+        if hi == n_bits:
+            on[hi - lo] = True  # chain(): the stream's end
+        for (lane_bits, run_in_bits), out in zip(lanes, dist):
+            lead = (b0 * BLOCK_BITS - lo) // lane_bits  # whole lanes in front of the piece's own (lo is a multiple of every lane)
+            assert lo % lane_bits == 0
+            l0, l1 = b0 * BLOCK_BITS // lane_bits, min(b1 * BLOCK_BITS // lane_bits, out.size)
+            d = merge_distances(L, on, lane_bits, run_in_bits, enough=lane_bits + run_in_bits, C=C)
+            out[l0:l1] = d[lead : lead + l1 - l0]
+    assert C is None or max(int(d.max()) for d in dist) < NEVER
+    return [unsettled_runs(d, BLOCK_BITS // l, l + r) for d, (l, r) in zip(dist, lanes)]

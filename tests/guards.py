@@ -225,3 +225,99 @@ def skewed_then_flat(n_head=40_000, n_flat=60_000, seed=5):
     assert int(len_t[head].astype(np.int64).sum()) % 8 in (2, 4, 6)
     text = np.concatenate([head, flat[rng.integers(0, flat.size, size=n_flat)], head[:1000]]).astype(np.uint8)
     return data_t, len_t, text
+
+
+def _skewed_flat_tree_dictionary():
+    """_skewed_flat_dictionary's relative that the TREE WALK plans for: the same skewed and flat codewords, no filler, and every
+    bit pattern under prefix 1 that is no flat codeword's given to a short codeword of its own -- 1x0, 1x1x0, 1x1x1x0 (the bytes
+    40 .. 53: in no text, and a walk that stands at an even offset inside flat codewords, which reads flat codewords only,
+    never reads one).  The table is complete: 35 internal nodes, nothing unmatched, no hole for the walk to make a leaf of.
+    -> (data, length, the skewed symbols, the flat symbols)."""
+    data_t, len_t, skewed, flat = _skewed_flat_dictionary()
+    data_t, len_t = data_t.copy(), len_t.copy()
+    data_t[120:220], len_t[120:220] = 0, 0
+    s = 40
+    for k in (1, 2, 3):  # 1x 0, 1x1x 0, 1x1x1x 0
+        for j in range(1 << k):
+            x = [(j >> i) & 1 for i in range(k - 1, -1, -1)]
+            data_t[s], len_t[s] = int("".join("1%d" % b for b in x) + "0", 2), 2 * k + 1
+            s += 1
+    assert s == 54 and sum(2.0 ** -int(l) for l in len_t if l) == 1.0
+    return data_t, len_t, skewed, flat
+
+
+PERIOD_DICTIONARIES = {"windows": _skewed_flat_dictionary, "tree_walk": _skewed_flat_tree_dictionary}
+PERIOD_BLOCK_BITS = 65_536  # the decode's 8 KiB blocks
+ISLAND_FLAT, ISLAND_AT_BIT = 1_500, 20_000  # island()'s stretch; where in its block it begins (about: 2, 4 or 6 bits behind a byte boundary)
+
+
+def _skewed_up_to(rng, bits):
+    """Random skewed symbols of _skewed_flat_dictionary, as many of the draw as fit into `bits` bits -> (symbols, their bits)."""
+    _, len_t, skewed, _ = _skewed_flat_dictionary()
+    run = skewed[np.minimum(rng.geometric(0.5, size=bits // 2 + 1) - 1, skewed.size - 1)]
+    cum = np.cumsum(len_t[run].astype(np.int64))
+    n = int(np.searchsorted(cum, bits, side="right"))
+    return run[:n], int(cum[n - 1]) if n else 0
+
+
+def _skewed_fill(rng, bits, flat_follows=False, begins_at=0):
+    """Skewed symbols that fill EXACTLY `bits` bits: a random run, its tail the 2- and 3-bit codewords.  flat_follows: not
+    exactly -- up to 13 bits fewer, padded as _skewed_run pads so that a run which begins at bit begins_at ends 2, 4 or 6 bits
+    behind a byte boundary."""
+    run, used = _skewed_up_to(rng, bits - 8)
+    if flat_follows:
+        pad, end = [], begins_at + used
+        if end % 2:
+            pad.append(2)  # the 3-bit codeword
+        if (end + 3 * len(pad)) % 8 == 0:
+            pad.append(1)  # the 2-bit codeword
+        return np.concatenate([run, np.array(pad, np.uint8)])
+    left = bits - used
+    assert left >= 8
+    tail = [2] * (left % 2) + [1] * ((left - 3 * (left % 2)) // 2)
+    return np.concatenate([run, np.array(tail, np.uint8)])
+
+
+def periodic_islands(dictionary, period_blocks, island_block=None, seed=11):
+    """-> (data, length, period_text, period_body): ONE period of a stream that is tiled on the device -- skewed symbols, one
+    stretch that cannot settle (island()'s: ISLAND_FLAT flat symbols laid 2, 4 or 6 bits behind a byte boundary), skewed
+    symbols, EXACTLY period_blocks * 65 536 bits, the tail trimmed with the 2- and 3-bit codewords.  So the oracle's pack of the
+    period is whole 8 KiB blocks without a pad bit, N copies of those bytes are the body of N copies of the text, and every
+    copy lies on the block grid as the first does.  The stretch lies inside block island_block of the period (default: the
+    middle one), from about bit ISLAND_AT_BIT of it.  dictionary: "windows" (_skewed_flat_dictionary) or "tree_walk"
+    (_skewed_flat_tree_dictionary).  tests/test_repairs_host.py checks all of that, and which blocks give up, on the host."""
+    from oracle import oracle as O
+
+    data_t, len_t, _, flat = PERIOD_DICTIONARIES[dictionary]()
+    island_block = period_blocks // 2 if island_block is None else island_block
+    assert 0 <= island_block < period_blocks and ISLAND_AT_BIT + 8 * ISLAND_FLAT + 4_096 < PERIOD_BLOCK_BITS
+    rng = np.random.default_rng(seed)
+    head = _skewed_fill(rng, island_block * PERIOD_BLOCK_BITS + ISLAND_AT_BIT, True)
+    middle = flat[rng.integers(0, flat.size, size=ISLAND_FLAT)]
+    used = int(len_t[head].astype(np.int64).sum()) + 8 * ISLAND_FLAT
+    assert used % 8 in (2, 4, 6)
+    text = np.concatenate([head, middle, _skewed_fill(rng, period_blocks * PERIOD_BLOCK_BITS - used)]).astype(np.uint8)
+    body, end_bit = O.pack_body(data_t, len_t, text)
+    assert end_bit == period_blocks * PERIOD_BLOCK_BITS and len(body) * 8 == end_bit
+    return data_t, len_t, text, body
+
+
+def failed_run_ins(n_blocks, flat_symbols=40, lead_bits=200, seed=13):
+    """-> (data, length, text): a stream of n_blocks 8 KiB blocks (and a few bytes) under _skewed_flat_dictionary in which
+    EVERY block seam lies inside a SHORT flat stretch: skewed symbols up to some lead_bits in front of the seam, flat_symbols
+    flat ones 2, 4 or 6 bits behind a byte boundary (320 bits: the 128-bit blind run-in of the block's first lane begins inside
+    them, in a phase that never meets the truth, and is still inside them at the seam -- the lane begins where no codeword
+    does), skewed symbols again.  The stretch ends inside the lane it misleads, and the skewed symbols behind it bring that
+    lane's walk to the true chain within a few lanes (tests/test_repairs_host.py: within 1 024 bits): nobody gives up, no
+    block's exit moves, and every seam that no workgroup of the first sweep settles within itself goes on the worklist of the
+    second.  The same holds with the block grid 8 or 24 bits off (a body 1 or 3 bytes behind an aligned address)."""
+    data_t, len_t, _, flat = _skewed_flat_dictionary()
+    rng = np.random.default_rng(seed)
+    parts, used = [], 0
+    for b in range(1, n_blocks):
+        run = _skewed_fill(rng, b * PERIOD_BLOCK_BITS - lead_bits - used, True, used)
+        parts += [run, flat[rng.integers(0, flat.size, size=flat_symbols)]]
+        used += int(len_t[run].astype(np.int64).sum()) + 8 * flat_symbols
+        assert used % 8 in (2, 4, 6) and b * PERIOD_BLOCK_BITS + 64 < used < b * PERIOD_BLOCK_BITS + 8 * flat_symbols - 128
+    parts.append(_skewed_up_to(rng, n_blocks * PERIOD_BLOCK_BITS + 1_000 - used)[0])
+    return data_t, len_t, np.concatenate(parts).astype(np.uint8)

@@ -204,6 +204,13 @@ def check_repair_reach(ctx, comp, want, certain):
     assert (run >= CERTAIN_FROM[planned]) == certain, f"the longest run of unsettled lanes in a block is {run}"
     back, iters, bits = _timed(ctx, lambda: ctx.decode(comp))
     assert back == want
+    return check_what_ran(planned, run, certain, iters, bits)
+
+
+def check_what_ran(planned, run, certain, iters, bits):
+    """check_repair_reach's judgement of the timing, for a decode the caller has made (tests/test_gpu_repairs.py: a body on
+    the device): planned, the family the planner starts the stream on; run, the reference's longest run of unsettled lanes in a
+    block; certain, as there."""
     ran = (planned, iters, [b for b in BITS if bits[b]])
     print(f"longest unsettled run {run} lanes; planned family, sync_iters, bits: {ran}")
     if certain:
