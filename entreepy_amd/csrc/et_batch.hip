@@ -39,7 +39,9 @@
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
 //
-// The workgroup scans and the hand-over itself are et_device.h's.
+// What the kernels share is defined once: the text span and the pack rounds of the encodes (text_span, pack_rounds); the code tables,
+// the codeword step, the walk and the settling of a block of the decodes and the long search (CodeTables, code_at, walk, settle_block).
+// The workgroup scans, the 16-byte chunk load and the hand-over itself are et_device.h's.
 #include "et_batch.h"
 
 #include "et_device.h"
@@ -66,32 +68,16 @@ __device__ __forceinline__ void batch_done(uint32_t *counter, unsigned long long
     }
 }
 
-// 16 bytes of a stream that occupies [lo, hi) measured from a 16-byte aligned base: one load when the chunk lies
-// inside, byte loads of the valid bytes alone at the stream's two edges (its neighbours in the buffer are other
-// streams, or nothing).
-struct Chunk16 {
-    uint32_t w[4];
-    uint32_t valid;  // bit k: byte k belongs to the stream
+// A text of `len` bytes at ptr + off as load_chunk (et_device.h) takes it: bytes [lo, hi) from a 16-byte aligned base.  Its
+// neighbours in the buffer are other streams, or nothing: only its own bytes are loaded.
+struct TextSpan {
+    const uint8_t *base;
+    uint64_t lo, hi;
 };
 
-__device__ __forceinline__ Chunk16 load16(const uint8_t *__restrict__ base, uint64_t off, uint64_t lo, uint64_t hi) {
-    Chunk16 c;
-    c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0;
-    c.valid = 0;
-    if (off >= lo && off + 16 <= hi) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(base + off);
-        c.w[0] = v.x; c.w[1] = v.y; c.w[2] = v.z; c.w[3] = v.w;
-        c.valid = 0xffffu;
-    } else if (off + 16 > lo && off < hi) {
-        for (int k = 0; k < 16; ++k) {
-            const uint64_t p = off + k;
-            if (p >= lo && p < hi) {
-                c.w[k >> 2] |= static_cast<uint32_t>(base[p]) << (8 * (k & 3));
-                c.valid |= 1u << k;
-            }
-        }
-    }
-    return c;
+__device__ __forceinline__ TextSpan text_span(const uint8_t *ptr, uint64_t off, uint64_t len) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(ptr) + off;
+    return TextSpan{reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15)), a & 15, (a & 15) + len};
 }
 
 // block_exclusive_scan in u64 (k_packed_scan: a tile of body sizes can reach 2^32).  `scratch` is 4 LDS words of 8 bytes; ONE
@@ -129,11 +115,9 @@ __global__ __launch_bounds__(BB) void k_batch_hist(const uint8_t *__restrict__ d
     uint32_t *mine = sh + (tid & 31);
     for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
         const BatchSpan sp = spans[j];
-        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + sp.in_off;
-        const uint8_t *base = reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15));
-        const uint64_t lo = a & 15, hi = lo + sp.in_len;
-        for (uint64_t off = static_cast<uint64_t>(tid) * 16; off < hi; off += ROUND_BYTES) {
-            const Chunk16 c = load16(base, off, lo, hi);
+        const TextSpan t = text_span(d_in, sp.in_off, sp.in_len);
+        for (uint64_t off = static_cast<uint64_t>(tid) * 16; off < t.hi; off += ROUND_BYTES) {
+            const Chunk c = load_chunk(t.base, off, t.lo, t.hi);
             if (c.valid == 0xffffu) {
 #pragma unroll
                 for (int k = 0; k < 16; ++k) atomicAdd(mine + ((c.w[k >> 2] >> (8 * (k & 3))) & 0xffu) * 32, 1u);
@@ -169,10 +153,10 @@ __global__ __launch_bounds__(BB) void k_batch_hist(const uint8_t *__restrict__ d
 // --------------------------------------------------------------------------------
 constexpr uint32_t ENC_STAGE_WORDS = ROUND_BYTES * 32 / 32 + 8;  // 4096 symbols of at most 32 bits, + the shared first word
 
-// One round of the pack, shared by k_batch_encode and k_shared_encode: the lane's bit total over its 16 bytes, the workgroup
+// One round of the pack: the lane's bit total over its 16 bytes, the workgroup
 // scan, and the lane's codes ORed into the LDS image from stage bit (carry & 31) + what lies before the lane; `pending` (the
 // partial word the round before ended in) goes into stage word 0.  Returns the round's bits.  The caller's barrier follows.
-__device__ __forceinline__ uint32_t pack_round(const Chunk16 &c, const uint2 *s_tab, uint32_t *s_stage, uint32_t *s_wsum, uint32_t carry, uint32_t pending) {
+__device__ __forceinline__ uint32_t pack_round(const Chunk &c,const uint2 *s_tab, uint32_t *s_stage, uint32_t *s_wsum, uint32_t carry, uint32_t pending) {
     const int tid = threadIdx.x;
     uint32_t bits = 0;
 #pragma unroll
@@ -205,6 +189,46 @@ __device__ __forceinline__ uint32_t pack_round(const Chunk16 &c, const uint2 *s_
     return round_bits;
 }
 
+// Word g of the image at `line` (4-byte aligned): whole when it lies inside the image bytes [lo, hi), else its bytes that do.
+__device__ __forceinline__ void store_image_word(uint8_t *line, uint32_t g, uint32_t v, uint32_t lo, uint32_t hi) {
+    const uint32_t b0 = g * 4;
+    if (b0 >= lo && b0 + 4 <= hi) {
+        reinterpret_cast<uint32_t *>(line)[g] = v;
+    } else {
+        for (uint32_t k = 0; k < 4; ++k)
+            if (b0 + k >= lo && b0 + k < hi) line[b0 + k] = static_cast<uint8_t>(v >> (8 * k));
+    }
+}
+
+// The rounds of a text's pack, every encode's: its codes into the bit image at `line` (4-byte aligned) from image bit `carry` on,
+// `pending` = the bits of word carry / 32 in front of that (the header's last, partial word; 0 where the image begins with the body).
+// CLIP: image bytes [lo, hi) are the body, and all that is stored; else every word leaves whole, the last one with zero bits behind
+// the body.  s_stage is zero on entry and on return.
+template <bool CLIP>
+__device__ __forceinline__ void pack_rounds(const TextSpan &t, uint8_t *__restrict__ line, uint32_t carry, uint32_t pending, uint32_t lo, uint32_t hi, const uint2 *s_tab,
+                                            uint32_t *s_stage, uint32_t *s_wsum) {
+    const uint32_t tid = threadIdx.x;
+    auto store = [&](uint32_t g, uint32_t big_endian) {
+        if (CLIP) store_image_word(line, g, __builtin_bswap32(big_endian), lo, hi);
+        else reinterpret_cast<uint32_t *>(line)[g] = __builtin_bswap32(big_endian);
+    };
+    for (uint64_t r0 = 0; r0 < t.hi; r0 += ROUND_BYTES) {
+        const Chunk c = load_chunk(t.base, r0 + static_cast<uint64_t>(tid) * 16, t.lo, t.hi);
+        const uint32_t round_bits = pack_round(c, s_tab, s_stage, s_wsum, carry, pending);
+        __syncthreads();
+        const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
+        pending = (t_bits & 31) ? s_stage[full] : 0u;
+        __syncthreads();
+        for (uint32_t i = tid; i <= full; i += BB) {
+            if (i < full) store(w0 + i, s_stage[i]);
+            s_stage[i] = 0;
+        }
+        carry += round_bits;
+        __syncthreads();
+    }
+    if (tid == 0 && (carry & 31)) store(carry >> 5, pending);
+}
+
 __global__ __launch_bounds__(BB) void k_batch_encode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const BatchEncJob *__restrict__ jobs,
                                                      uint32_t n, const uint8_t *__restrict__ blob) {
     __shared__ uint2 s_tab[256];
@@ -221,27 +245,9 @@ __global__ __launch_bounds__(BB) void k_batch_encode(const uint8_t *__restrict__
         s_tab[tid] = tab[tid];
         const uint32_t hw = job.header_len >> 2;
         for (uint32_t i = tid; i < hw; i += BB) out32[i] = hdr[i];
-        uint32_t pending = (job.header_len & 3) ? __builtin_bswap32(hdr[hw]) : 0u;  // (the pad behind the header is zero)
-        uint32_t carry = job.header_len * 8;  // image bits written so far
-        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + job.in_off;
-        const uint8_t *base = reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15));
-        const uint64_t lo = a & 15, hi = lo + job.in_len;
+        const uint32_t pending = (job.header_len & 3) ? __builtin_bswap32(hdr[hw]) : 0u;  // (the pad behind the header is zero)
         __syncthreads();
-        for (uint64_t r0 = 0; r0 < hi; r0 += ROUND_BYTES) {
-            const Chunk16 c = load16(base, r0 + static_cast<uint64_t>(tid) * 16, lo, hi);
-            const uint32_t round_bits = pack_round(c, s_tab, s_stage, s_wsum, carry, pending);
-            __syncthreads();
-            const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
-            pending = (t_bits & 31) ? s_stage[full] : 0u;
-            __syncthreads();
-            for (uint32_t i = tid; i <= full; i += BB) {
-                if (i < full) out32[w0 + i] = __builtin_bswap32(s_stage[i]);
-                s_stage[i] = 0;
-            }
-            carry += round_bits;
-            __syncthreads();
-        }
-        if (tid == 0 && (carry & 31)) out32[carry >> 5] = __builtin_bswap32(pending);
+        pack_rounds<false>(text_span(d_in, job.in_off, job.in_len), d_out + job.out_off, job.header_len * 8, pending, 0, 0, s_tab, s_stage, s_wsum);
     }
 }
 
@@ -286,50 +292,89 @@ constexpr uint32_t DEC_WORDS = 2048;                                 // words pe
 constexpr uint32_t DEC_STAGED = DEC_WORDS + 2;                       // + what a window at the block's last bits reads
 __device__ __forceinline__ uint32_t padded(uint32_t k) { return k + (k >> 3); }  // lanes 8 words apart on different banks
 
+// The two tables every walk looks a codeword up in; the first member of the LDS of every kernel that walks.
+struct CodeTables {
+    uint2 codes[256];                    // the sorted codes: {left-aligned value, length << 8 | symbol}
+    uint16_t lut[1u << BATCH_LUT_BITS];  // by a window's first 11 bits: length << 8 | symbol, 0 = longer than 11 bits
+};
+
 struct BatchDecLds {
-    uint2 codes[256];
-    uint16_t lut[1u << BATCH_LUT_BITS];
+    CodeTables t;
     uint32_t bits[DEC_STAGED + (DEC_STAGED >> 3) + 2];
     uint32_t entry[BB + 1];
     uint32_t wsum[4];
     uint32_t out[BATCH_STAGE_BYTES / 4 + 2];
 };
 
-// (over bare arrays: k_search_flag keeps the tables without the decode's stages)
-__device__ __forceinline__ uint32_t find_code_in(const uint2 *codes, uint32_t n_codes, uint32_t win) {
+// The code the window begins with, by the binary search alone.
+__device__ __forceinline__ uint32_t search_codes(const CodeTables &t, uint32_t n_codes, uint32_t win) {
     uint32_t lo = 0, hi = n_codes;  // codes[0] is the all-zero code of a full tree: codes[lo].x <= win throughout
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (codes[mid].x <= win) lo = mid; else hi = mid;
+        if (t.codes[mid].x <= win) lo = mid; else hi = mid;
     }
-    return codes[lo].y;
+    return t.codes[lo].y;
 }
 
-__device__ __forceinline__ uint32_t find_code(const BatchDecLds &s, uint32_t n_codes, uint32_t win) { return find_code_in(s.codes, n_codes, win); }
+// THE codeword step: length << 8 | symbol of the code the window begins with -- the first-level table, then the search.
+__device__ __forceinline__ uint32_t code_at(const CodeTables &t, uint32_t n_codes, uint32_t win) {
+    uint32_t meta = t.lut[win >> (32 - BATCH_LUT_BITS)];
+    if (!meta) meta = search_codes(t, n_codes, win);
+    return meta;
+}
 
-// The lane's walk from `entry` (bits into its subsequence).  Returns its exit; *count = codewords that end at or before
-// the body's last bit (`room` = bits from the lane's first bit to there; <= 0 when the lane lies behind the body).
-// WRITE: symbol number first + k goes to stage byte first + k - s0 + align for numbers in [s0, s1).
-template <bool WRITE>
-__device__ __forceinline__ uint32_t walk(BatchDecLds &s, uint32_t n_codes, uint32_t lane_bit, uint32_t entry, int64_t room, uint32_t *count,
-                                         uint32_t first = 0, uint32_t s0 = 0, uint32_t s1 = 0, uint32_t align = 0) {
+// The prologue of every kernel that walks: the sorted codes into LDS, a barrier, the first-level table from them.  A barrier lies
+// between this and the first code_at: a block's first (settle_block), or the caller's own.
+__device__ __forceinline__ void load_tables(CodeTables &t, const uint2 *__restrict__ codes, uint32_t n_codes) {
+    if (threadIdx.x < n_codes) t.codes[threadIdx.x] = codes[threadIdx.x];
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < (1u << BATCH_LUT_BITS); e += BB) {
+        const uint32_t meta = search_codes(t, n_codes, e << (32 - BATCH_LUT_BITS));
+        t.lut[e] = (meta >> 8) <= BATCH_LUT_BITS ? static_cast<uint16_t>(meta) : static_cast<uint16_t>(0);
+    }
+}
+
+// A body as the walks see it: counted in bits from the 4-byte aligned word it begins in.
+struct BodyBits {
+    const uint32_t *words;
+    uint32_t first_bit, end_bit, n_words;  // the body's first bit, its last + 1, the aligned words that hold a byte of it
+};
+
+__device__ __forceinline__ BodyBits body_bits_of(const uint8_t *d_bodies, uint64_t body_off, uint32_t body_bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_bodies) + body_off;
+    BodyBits g;
+    g.words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
+    g.first_bit = static_cast<uint32_t>(a & 3) * 8;
+    g.end_bit = g.first_bit + body_bytes * 8;
+    g.n_words = (g.end_bit + 31) >> 5;
+    return g;
+}
+
+// Word k of the body, big-endian; zero behind the last word that holds a byte of it (which is never loaded).
+__device__ __forceinline__ uint64_t body_word_be(const BodyBits &g, uint32_t k) { return k < g.n_words ? __builtin_bswap32(g.words[k]) : 0u; }
+
+// The 32 bits from bit `bit` of the staged block on.
+__device__ __forceinline__ uint32_t lane_window(const BatchDecLds &s, uint32_t bit) {
+    const uint32_t k = bit >> 5;
+    const uint64_t two = (static_cast<uint64_t>(s.bits[padded(k)]) << 32) | s.bits[padded(k + 1)];
+    return static_cast<uint32_t>((two << (bit & 31)) >> 32);
+}
+
+// THE walk: the lane's codewords from `entry` (bits into its 256) until it leaves them.  Returns its exit; *count = the codewords
+// it stepped over, each of which ends at or before the body's last bit (`room` = bits from the lane's first bit to there; 0 when
+// the lane lies behind the body).  visit(cnt, pos, win, meta) sees every such codeword -- its number in this walk, its bit, the
+// window there, its length << 8 | symbol -- in front of the step over it, and ends the walk there by returning false (the exit of
+// a walk that was ended is nobody's entry: 512 like that of one whose bits ran out).
+template <class Visit>
+__device__ __forceinline__ uint32_t walk(const BatchDecLds &s, uint32_t n_codes, uint32_t entry, uint32_t room, uint32_t *count, Visit &&visit) {
+    const uint32_t lane_bit = threadIdx.x * 256;
     uint32_t pos = entry, cnt = 0;
-    uint8_t *stage = reinterpret_cast<uint8_t *>(s.out);
     while (pos < 256) {
-        const uint32_t p = lane_bit + pos, k = p >> 5, sh = p & 31;
-        const uint64_t two = (static_cast<uint64_t>(s.bits[padded(k)]) << 32) | s.bits[padded(k + 1)];
-        const uint32_t win = static_cast<uint32_t>((two << sh) >> 32);
-        uint32_t meta = s.lut[win >> (32 - BATCH_LUT_BITS)];
-        if (!meta) meta = find_code(s, n_codes, win);
-        const uint32_t len = meta >> 8;
-        if (static_cast<int64_t>(pos + len) > room) {  // the bits ran out inside this codeword: nothing behind it is one,
-            pos = 512;                                  // so the next lane's entry (256) lies behind ITS bits as well
+        const uint32_t win = lane_window(s, lane_bit + pos);
+        const uint32_t meta = code_at(s.t, n_codes, win), len = meta >> 8;
+        if (pos + len > room || !visit(cnt, pos, win, meta)) {  // THE rule: the bits ran out inside this codeword: nothing behind it
+            pos = 512;                                           // is one, so the next lane's entry (256) lies behind ITS bits as well
             break;
-        }
-        if (WRITE) {
-            const uint32_t idx = first + cnt;
-            if (idx >= s1) break;
-            if (idx >= s0) stage[idx - s0 + align] = static_cast<uint8_t>(meta);
         }
         ++cnt;
         pos += len;
@@ -338,81 +383,96 @@ __device__ __forceinline__ uint32_t walk(BatchDecLds &s, uint32_t n_codes, uint3
     return pos;
 }
 
-// The first-level table from the sorted codes in s.codes (a barrier lies between their stores and this).
-__device__ __forceinline__ void fill_lut_in(const uint2 *codes, uint16_t *lut, uint32_t n_codes) {
-    for (uint32_t e = threadIdx.x; e < (1u << BATCH_LUT_BITS); e += BB) {
-        const uint32_t meta = find_code_in(codes, n_codes, e << (32 - BATCH_LUT_BITS));
-        lut[e] = (meta >> 8) <= BATCH_LUT_BITS ? static_cast<uint16_t>(meta) : static_cast<uint16_t>(0);
+// The visitor of a walk that only counts.
+struct JustCount {
+    __device__ __forceinline__ bool operator()(uint32_t, uint32_t, uint32_t, uint32_t) const { return true; }
+};
+
+// One block of a body by the whole workgroup, up to where every lane knows its codewords: the block's DEC_STAGED big-endian words
+// into the stage, the fixed point over the lanes' entries (a lane walks again, with a fresh copy of `visit`, whenever its entry
+// changes: what `visit` holds on return is the settled walk's), the scan of the counts.  Begins with a barrier: the one between
+// load_tables, or the block before (its stages, entry[BB], what the caller keeps in LDS), and this block's first walk.
+struct Settled {
+    uint32_t used, count, first;  // the lane's settled entry, its codewords, how many of the block's lie in front of them
+    uint32_t room;                // bits from the lane's first to the body's last + 1; 0 when the lane lies behind the body
+    uint32_t total, start;        // the block's codewords; the bit of the next block at which its first codeword begins
+};
+
+template <class Visit>
+__device__ __forceinline__ Settled settle_block(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, uint32_t blk, uint32_t start, Visit &visit) {
+    const uint32_t tid = threadIdx.x;
+    const Visit fresh = visit;
+    __syncthreads();
+    for (uint32_t k = tid; k < DEC_STAGED; k += BB) s.bits[padded(k)] = static_cast<uint32_t>(body_word_be(g, blk * DEC_WORDS + k));
+    s.entry[tid] = tid == 0 ? start : 0u;
+    __syncthreads();
+    Settled b;
+    const uint32_t at = blk * DEC_WORDS * 32 + tid * 256;  // the lane's first bit, from the body's aligned base
+    b.room = g.end_bit > at ? g.end_bit - at : 0u;
+    b.used = 0xffffffffu;
+    b.count = 0;
+    uint32_t exit = 256;
+    for (uint32_t trip = 0; trip < BB; ++trip) {
+        const uint32_t mine = s.entry[tid];
+        int changed = 0;
+        if (mine != b.used) {
+            const uint32_t was = exit;
+            visit = fresh;
+            exit = b.room ? walk(s, n_codes, mine, b.room, &b.count, visit) : 256u;
+            b.used = mine;
+            changed = exit != was || trip == 0;
+        }
+        __syncthreads();
+        if (changed) s.entry[tid + 1] = exit - 256;
+        if (!__syncthreads_or(changed)) break;
     }
+    b.first = block_exclusive_scan(b.count, s.wsum, &b.total);  // (s.wsum: the next block's first barrier lies between two scans)
+    b.start = s.entry[BB];
+    return b;
 }
 
-__device__ __forceinline__ void fill_lut(BatchDecLds &s, uint32_t n_codes) { fill_lut_in(s.codes, s.lut, n_codes); }
-
-// One stream under the tables in `s` (k_batch_decode, k_shared_decode): its blocks in order.  Returns the symbols it holds, at
-// most n_symbols; the first write_cap of them are stored.  Every block begins with a barrier: that is the one between
-// fill_lut, or the stream before, and this stream's first walk.
-__device__ __forceinline__ uint32_t decode_stream(BatchDecLds &s, uint32_t n_codes, const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, uint64_t body_off,
-                                                  uint64_t out_off, uint32_t body_bytes, uint32_t n_symbols, uint32_t write_cap) {
+// One stream under the tables in `s`, its symbols to `out`: its blocks in order, each settled, then written.  Returns the symbols
+// it holds, at most n_symbols; the first write_cap of them are stored.
+__device__ __forceinline__ uint32_t decode_stream(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, uint8_t *__restrict__ out, uint32_t n_symbols, uint32_t write_cap) {
     const uint32_t tid = threadIdx.x;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + body_off;
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
-    const uint32_t first_bit = static_cast<uint32_t>(a & 3) * 8;
-    const uint32_t end_bit = first_bit + body_bytes * 8;  // the body's last bit + 1, from the aligned base
-    const uint32_t n_words = (end_bit + 31) >> 5, n_blocks = (n_words + DEC_WORDS - 1) / DEC_WORDS;
-    uint8_t *out = d_out + out_off;
-    uint32_t start = first_bit, done = 0;  // the block's first codeword; symbols so far
+    const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
+    uint32_t start = g.first_bit, done = 0;  // the block's first codeword; symbols so far
     for (uint32_t blk = 0; blk < n_blocks && done < n_symbols; ++blk) {
-        __syncthreads();  // (the block before is done with the stages and entry[BB])
-        for (uint32_t k = tid; k < DEC_STAGED; k += BB) {
-            const uint32_t g = blk * DEC_WORDS + k;
-            s.bits[padded(k)] = g < n_words ? __builtin_bswap32(words[g]) : 0u;  // (an aligned word that holds a body byte; zeros behind)
-        }
-        s.entry[tid] = tid == 0 ? start : 0u;
-        __syncthreads();
-        const uint32_t lane_bit = tid * 256;
-        const int64_t room = static_cast<int64_t>(end_bit) - (static_cast<int64_t>(blk) * DEC_WORDS * 32 + lane_bit);
-        uint32_t used = 0xffffffffu, exit = 256, count = 0;
-        for (uint32_t trip = 0; trip < BB; ++trip) {
-            const uint32_t mine = s.entry[tid];
-            int changed = 0;
-            if (mine != used) {
-                const uint32_t was = exit;
-                exit = room > 0 ? walk<false>(s, n_codes, lane_bit, mine, room, &count) : 256u;
-                used = mine;
-                changed = exit != was || trip == 0;
-            }
-            __syncthreads();
-            if (changed) s.entry[tid + 1] = exit - 256;
-            if (!__syncthreads_or(changed)) break;
-        }
+        JustCount counting;
+        const Settled b = settle_block(s, n_codes, g, blk, start, counting);
         // counts -> where the lane's symbols go
-        uint32_t total;
-        const uint32_t first = block_exclusive_scan(count, s.wsum, &total);  // (s.wsum: the next block's first barrier lies between two scans)
-        const uint32_t left = n_symbols - done, take = total < left ? total : left;
+        const uint32_t left = n_symbols - done, take = b.total < left ? b.total : left;
         const uint32_t cap_left = write_cap > done ? write_cap - done : 0u, n_write = take < cap_left ? take : cap_left;
         for (uint32_t s0 = 0; s0 < n_write; s0 += BATCH_STAGE_BYTES) {
             const uint32_t s1 = s0 + BATCH_STAGE_BYTES < n_write ? s0 + BATCH_STAGE_BYTES : n_write;
             uint8_t *dst = out + done + s0;
             const uint32_t align = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3);
-            if (count && first < s1 && first + count > s0) {
+            uint8_t *stage = reinterpret_cast<uint8_t *>(s.out);
+            if (b.count && b.first < s1 && b.first + b.count > s0) {
+                // the settled walk once more: symbol number first + cnt goes to stage byte first + cnt - s0 + align for numbers in [s0, s1),
+                // which are the walk's codewords [from, stop) (base: modulo 2^32 where s0 > first)
+                const uint32_t stop = s1 - b.first, from = s0 > b.first ? s0 - b.first : 0u, base = b.first - s0 + align;
                 uint32_t again;
-                (void)walk<true>(s, n_codes, lane_bit, used, room, &again, first, s0, s1, align);
+                (void)walk(s, n_codes, b.used, b.room, &again, [&](uint32_t cnt, uint32_t, uint32_t, uint32_t meta) {
+                    if (cnt >= stop) return false;
+                    if (cnt >= from) stage[cnt + base] = static_cast<uint8_t>(meta);
+                    return true;
+                });
             }
             __syncthreads();
             const uint32_t lo = align, hi = align + (s1 - s0);  // stage bytes [lo, hi) -> dst - align + [lo, hi)
             uint8_t *line = dst - align;
-            const uint8_t *stage = reinterpret_cast<const uint8_t *>(s.out);
             for (uint32_t w = tid; w * 4 < hi; w += BB) {
                 if (w * 4 >= lo && w * 4 + 4 <= hi) {
                     reinterpret_cast<uint32_t *>(line)[w] = s.out[w];
                 } else {
-                    for (uint32_t b = w * 4; b < w * 4 + 4; ++b)
-                        if (b >= lo && b < hi) line[b] = stage[b];
+                    for (uint32_t k = w * 4; k < w * 4 + 4; ++k)
+                        if (k >= lo && k < hi) line[k] = stage[k];
                 }
             }
             __syncthreads();
         }
-        start = s.entry[BB];
+        start = b.start;
         done += take;
     }
     return done;
@@ -426,10 +486,8 @@ __global__ __launch_bounds__(BB) void k_batch_decode(const uint8_t *__restrict__
     for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
         const BatchDecJob job = jobs[j];
         __syncthreads();  // (the stream before is done with the tables)
-        if (tid < job.n_codes) s.codes[tid] = reinterpret_cast<const uint2 *>(blob + job.blob_off)[tid];
-        __syncthreads();
-        fill_lut(s, job.n_codes);
-        const uint32_t done = decode_stream(s, job.n_codes, d_in, d_out, job.body_off, job.out_off, job.body_bytes, job.n_symbols, job.write_cap);
+        load_tables(s.t, reinterpret_cast<const uint2 *>(blob + job.blob_off), job.n_codes);
+        const uint32_t done = decode_stream(s, job.n_codes, body_bits_of(d_in, job.body_off, job.body_bytes), d_out + job.out_off, job.n_symbols, job.write_cap);
         if (tid == 0) host_totals[j] = done;
     }
     batch_done(counter, host_done, epoch);
@@ -443,25 +501,14 @@ __global__ __launch_bounds__(BB) void k_batch_decode(const uint8_t *__restrict__
 // word that belong to it as byte stores, so that [out_off, out_off + bytes) is all the stream writes and bodies may lie
 // back to back.  LDS as k_batch_encode.
 // --------------------------------------------------------------------------------
-// Word g of the image at `line` (4-byte aligned): whole when it lies inside the image bytes [lo, hi), else its bytes that do.
-__device__ __forceinline__ void store_image_word(uint8_t *line, uint32_t g, uint32_t v, uint32_t lo, uint32_t hi) {
-    const uint32_t b0 = g * 4;
-    if (b0 >= lo && b0 + 4 <= hi) {
-        reinterpret_cast<uint32_t *>(line)[g] = v;
-    } else {
-        for (uint32_t k = 0; k < 4; ++k)
-            if (b0 + k >= lo && b0 + k < hi) line[b0 + k] = static_cast<uint8_t>(v >> (8 * k));
-    }
-}
-
-// The count pass of a text that occupies [lo, hi) from its 16-byte aligned base (k_shared_encode, k_packed_count): the bytes
+// The count pass of a text (k_shared_encode, k_packed_count): the bytes
 // its body takes, and *uncoded = whether a byte of it has no code (the same for every lane).  Ends with a barrier: s_wsum is
 // free for the next scan.
-__device__ __forceinline__ uint32_t count_body(const uint8_t *__restrict__ base, uint64_t lo, uint64_t hi, const uint2 *s_tab, uint32_t *s_wsum, int *uncoded) {
+__device__ __forceinline__ uint32_t count_body(const TextSpan &t, const uint2 *s_tab, uint32_t *s_wsum, int *uncoded) {
     uint32_t bits = 0;
     int none = 0;
-    for (uint64_t off = static_cast<uint64_t>(threadIdx.x) * 16; off < hi; off += ROUND_BYTES) {
-        const Chunk16 c = load16(base, off, lo, hi);
+    for (uint64_t off = static_cast<uint64_t>(threadIdx.x) * 16; off < t.hi; off += ROUND_BYTES) {
+        const Chunk c = load_chunk(t.base, off, t.lo, t.hi);
 #pragma unroll
         for (int k = 0; k < 16; ++k)
             if (c.valid & (1u << k)) {
@@ -477,28 +524,10 @@ __device__ __forceinline__ uint32_t count_body(const uint8_t *__restrict__ base,
 }
 
 // The pack pass of that text (k_shared_encode, k_packed_pack): its body, `bytes` long, to dst at any alignment -- image bytes
-// [lead, end_byte) of the aligned line are the body, and all that is stored.  s_stage is zero on entry and on return.
-__device__ __forceinline__ void pack_body(const uint8_t *__restrict__ base, uint64_t lo, uint64_t hi, uint8_t *__restrict__ dst, uint32_t bytes, const uint2 *s_tab,
-                                          uint32_t *s_stage, uint32_t *s_wsum) {
-    const uint32_t tid = threadIdx.x;
-    const uint32_t lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3), end_byte = lead + bytes;
-    uint8_t *line = dst - lead;
-    uint32_t pending = 0, carry = lead * 8;  // image bits written so far
-    for (uint64_t r0 = 0; r0 < hi; r0 += ROUND_BYTES) {
-        const Chunk16 c = load16(base, r0 + static_cast<uint64_t>(tid) * 16, lo, hi);
-        const uint32_t round_bits = pack_round(c, s_tab, s_stage, s_wsum, carry, pending);
-        __syncthreads();
-        const uint32_t t_bits = (carry & 31) + round_bits, full = t_bits >> 5, w0 = carry >> 5;
-        pending = (t_bits & 31) ? s_stage[full] : 0u;
-        __syncthreads();
-        for (uint32_t i = tid; i <= full; i += BB) {
-            if (i < full) store_image_word(line, w0 + i, __builtin_bswap32(s_stage[i]), lead, end_byte);
-            s_stage[i] = 0;
-        }
-        carry += round_bits;
-        __syncthreads();
-    }
-    if (tid == 0 && (carry & 31)) store_image_word(line, carry >> 5, __builtin_bswap32(pending), lead, end_byte);
+// [lead, lead + bytes) of the aligned line are the body, and all that is stored.  s_stage is zero on entry and on return.
+__device__ __forceinline__ void pack_body(const TextSpan &t, uint8_t *__restrict__ dst, uint32_t bytes, const uint2 *s_tab, uint32_t *s_stage, uint32_t *s_wsum) {
+    const uint32_t lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 3);
+    pack_rounds<true>(t, dst - lead, lead * 8, 0u, lead, lead + bytes, s_tab, s_stage, s_wsum);
 }
 
 __global__ __launch_bounds__(BB) void k_shared_encode(const uint8_t *__restrict__ d_in, uint8_t *__restrict__ d_out, const SharedJob *__restrict__ jobs,
@@ -513,16 +542,14 @@ __global__ __launch_bounds__(BB) void k_shared_encode(const uint8_t *__restrict_
     __syncthreads();
     for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
         const SharedJob job = jobs[j];
-        const uintptr_t a = reinterpret_cast<uintptr_t>(d_in) + job.in_off;
-        const uint8_t *base = reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15));
-        const uint64_t lo = a & 15, hi = lo + job.in_len;
+        const TextSpan text = text_span(d_in, job.in_off, job.in_len);
         // the count pass
         int uncoded;
-        const uint32_t bytes = count_body(base, lo, hi, s_tab, s_wsum, &uncoded);
+        const uint32_t bytes = count_body(text, s_tab, s_wsum, &uncoded);
         const uint32_t status = uncoded ? SHARED_UNCODED : bytes > job.cap ? SHARED_CAP : SHARED_OK;
         if (tid == 0) host_results[j] = make_uint2(status == SHARED_OK ? bytes : 0u, status);
         if (status != SHARED_OK || !d_out || !bytes) continue;  // (the same for every lane)
-        pack_body(base, lo, hi, d_out + job.out_off, bytes, s_tab, s_stage, s_wsum);
+        pack_body(text, d_out + job.out_off, bytes, s_tab, s_stage, s_wsum);
     }
     batch_done(counter, host_done, epoch);
 }
@@ -537,12 +564,10 @@ __global__ __launch_bounds__(BB) void k_shared_decode(const uint8_t *__restrict_
                                                       uint32_t *__restrict__ counter, unsigned long long *__restrict__ host_done, unsigned long long epoch) {
     __shared__ BatchDecLds s;
     const uint32_t tid = threadIdx.x;
-    if (tid < n_codes) s.codes[tid] = codes[tid];
-    __syncthreads();
-    fill_lut(s, n_codes);
+    load_tables(s.t, codes, n_codes);
     for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
         const SharedJob job = jobs[j];
-        const uint32_t done = decode_stream(s, n_codes, d_in, d_out, job.in_off, job.out_off, job.in_len, job.cap, job.cap);
+        const uint32_t done = decode_stream(s, n_codes, body_bits_of(d_in, job.in_off, job.in_len), d_out + job.out_off, job.cap, job.cap);
         if (tid == 0) host_results[j] = make_uint2(done, 0u);
     }
     batch_done(counter, host_done, epoch);
@@ -652,10 +677,8 @@ __global__ __launch_bounds__(BB) void k_packed_count(const uint8_t *__restrict__
         } else if (t1 - t0 > BATCH_SMALL_MAX) {
             status = PACKED_UNSUPPORTED;
         } else if (t1 > t0) {  // (the same for every lane, like every branch above)
-            const uintptr_t a = reinterpret_cast<uintptr_t>(d_text) + t0;
-            const uint64_t lo = a & 15, hi = lo + (t1 - t0);
             int uncoded;
-            bytes = count_body(reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15)), lo, hi, s_tab, s_wsum, &uncoded);
+            bytes = count_body(text_span(d_text, t0, t1 - t0), s_tab, s_wsum, &uncoded);
             if (uncoded) {
                 status = PACKED_UNSUPPORTED;
                 bytes = 0;
@@ -738,9 +761,7 @@ __global__ __launch_bounds__(BB) void k_packed_pack(const uint8_t *__restrict__ 
         if (o1 <= o0) continue;
         const uint64_t t0 = text_index[j], t1 = text_index[j + 1];
         if (!(t0 < t1 && t1 <= text_bytes && t1 - t0 <= BATCH_SMALL_MAX)) continue;  // (k_packed_count gave such a record no bytes; asked again, for what is read below)
-        const uintptr_t a = reinterpret_cast<uintptr_t>(d_text) + t0;
-        const uint64_t lo = a & 15, hi = lo + (t1 - t0);
-        pack_body(reinterpret_cast<const uint8_t *>(a & ~static_cast<uintptr_t>(15)), lo, hi, d_out + o0, static_cast<uint32_t>(o1 - o0), s_tab, s_stage, s_wsum);
+        pack_body(text_span(d_text, t0, t1 - t0), d_out + o0, static_cast<uint32_t>(o1 - o0), s_tab, s_stage, s_wsum);
     }
 }
 
@@ -756,9 +777,7 @@ __global__ __launch_bounds__(BB) void k_packed_decode(PackedStore store, uint8_t
     const uint64_t out_bytes = store.text_index[store.n];
     PackedTally tally;
     if (out_bytes <= cap) {
-        if (tid < n_codes) s.codes[tid] = codes[tid];
-        __syncthreads();
-        fill_lut(s, n_codes);
+        load_tables(s.t, codes, n_codes);
         for (uint32_t j = blockIdx.x; j < store.n; j += gridDim.x) {
             const uint64_t b0 = store.body_index[j], b1 = store.body_index[j + 1], t0 = store.text_index[j], t1 = store.text_index[j + 1];
             uint32_t status = PACKED_OK, done = 0;
@@ -772,7 +791,7 @@ __global__ __launch_bounds__(BB) void k_packed_decode(PackedStore store, uint8_t
                 status = PACKED_UNSUPPORTED;
             } else {
                 const uint32_t count = static_cast<uint32_t>(t1 - t0);
-                done = decode_stream(s, n_codes, d_bodies, d_out, b0, t0, static_cast<uint32_t>(clip_body(b1 - b0, count)), count, count);
+                done = decode_stream(s, n_codes, body_bits_of(d_bodies, b0, static_cast<uint32_t>(clip_body(b1 - b0, count))), d_out + t0, count, count);
                 if (tid == 0 && done < count) ++tally.n_short;
             }
             if (tid == 0) {
@@ -818,16 +837,14 @@ __global__ __launch_bounds__(BB) void k_packed_gather(PackedStore store, const u
     const uint64_t out_bytes = out_index[n_rows];
     PackedTally tally;
     if (out_bytes <= cap) {
-        if (tid < n_codes) s.codes[tid] = codes[tid];
-        __syncthreads();
-        fill_lut(s, n_codes);
+        load_tables(s.t, codes, n_codes);
         for (uint32_t k = blockIdx.x; k < n_rows; k += gridDim.x) {
             const uint64_t o0 = out_index[k], o1 = out_index[k + 1];
             uint32_t done = 0;
             if (o1 > o0) {  // (the same for every lane)
                 const uint32_t r = rows[k], count = static_cast<uint32_t>(o1 - o0);
                 const uint64_t b0 = store.body_index[r], b1 = store.body_index[r + 1];
-                if (b1 > b0) done = decode_stream(s, n_codes, d_bodies, d_out, b0, o0, static_cast<uint32_t>(clip_body(b1 - b0, count)), count, count);
+                if (b1 > b0) done = decode_stream(s, n_codes, body_bits_of(d_bodies, b0, static_cast<uint32_t>(clip_body(b1 - b0, count))), d_out + o0, count, count);
                 if (tid == 0 && done < count) ++tally.n_short;  // (an empty body under a length above zero is a short one)
             }
             if (tid == 0 && d_written) d_written[k] = done;
@@ -966,29 +983,9 @@ __global__ __launch_bounds__(BB) void k_rows_emit(const unsigned long long *__re
 // advance.  No workgroup waits for another: k_search_long corrects a mask and a count by atomics nobody waits for.
 // --------------------------------------------------------------------------------
 struct SearchLds {  // k_search_flag's tables: 7 KiB
-    uint2 codes[256];
-    uint16_t lut[1u << BATCH_LUT_BITS];
+    CodeTables t;
     uint32_t pat[SEARCH_PATTERN_BYTES / 4];  // the pattern, big-endian words: bit q of it is bit 31 - q % 32 of word q / 32
 };
-
-// A body as the walks see it: counted in bits from the 4-byte aligned word it begins in (decode_stream's geometry).
-struct BodyBits {
-    const uint32_t *words;
-    uint32_t first_bit, end_bit, n_words;  // the body's first bit, its last + 1, the aligned words that hold a byte of it
-};
-
-__device__ __forceinline__ BodyBits body_bits_of(const uint8_t *d_bodies, uint64_t body_off, uint32_t body_bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_bodies) + body_off;
-    BodyBits g;
-    g.words = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
-    g.first_bit = static_cast<uint32_t>(a & 3) * 8;
-    g.end_bit = g.first_bit + body_bytes * 8;
-    g.n_words = (g.end_bit + 31) >> 5;
-    return g;
-}
-
-// Word k of the body, big-endian; zero behind the last word that holds a byte of it (which is never loaded).
-__device__ __forceinline__ uint64_t body_word_be(const BodyBits &g, uint32_t k) { return k < g.n_words ? __builtin_bswap32(g.words[k]) : 0u; }
 
 // The 32 bits from bit `bit` on, from global memory.
 __device__ __forceinline__ uint32_t body_window(const BodyBits &g, uint32_t bit) {
@@ -1010,7 +1007,7 @@ __device__ __forceinline__ bool confirm_rest(const uint32_t *pat, uint32_t pat_b
 // length - needle_len, the last at which an occurrence fits the length; SUFFIX: `target` alone) the pattern is compared -- its head
 // against the window the step needs anyway, the rest by confirm_rest --, then the codeword there is stepped over.  Returns the
 // lowest boundary with an occurrence, or SEARCH_NONE.  64 bits of body are kept in registers and move on a word at a time.
-__device__ __forceinline__ uint32_t search_lane(const SearchLds &t, uint32_t n_codes, const SearchJob &job, const BodyBits &g, uint32_t target) {
+__device__ __forceinline__ uint32_t search_lane(const SearchLds &s, uint32_t n_codes, const SearchJob &job, const BodyBits &g, uint32_t target) {
     const bool suffix = job.flags & SEARCH_F_SUFFIX;
     uint32_t pos = g.first_bit, k = 0;
     uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
@@ -1022,11 +1019,9 @@ __device__ __forceinline__ uint32_t search_lane(const SearchLds &t, uint32_t n_c
         const uint32_t win = static_cast<uint32_t>((two << (pos & 31)) >> 32);
         if (!suffix || idx == target) {
             if (pos + job.pat_bits > g.end_bit) return SEARCH_NONE;  // (nor does it fit at a later boundary)
-            if (((win ^ job.head) & job.head_mask) == 0 && confirm_rest(t.pat, job.pat_bits, g, pos)) return idx;
+            if (((win ^ job.head) & job.head_mask) == 0 && confirm_rest(s.pat, job.pat_bits, g, pos)) return idx;
         }
-        uint32_t meta = t.lut[win >> (32 - BATCH_LUT_BITS)];
-        if (!meta) meta = find_code_in(t.codes, n_codes, win);
-        pos += meta >> 8;
+        pos += code_at(s.t, n_codes, win) >> 8;
         if (pos > g.end_bit) return SEARCH_NONE;  // the bits ran out inside this codeword: no boundary behind it
     }
     return SEARCH_NONE;
@@ -1040,7 +1035,7 @@ __device__ __forceinline__ uint32_t search_lane(const SearchLds &t, uint32_t n_c
 __global__ __launch_bounds__(BB) void k_search_flag(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, const uint32_t *__restrict__ pattern, SearchJob job,
                                                     TileWs tiles, uint32_t *__restrict__ pos_of, uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status,
                                                     unsigned long long *__restrict__ stats) {
-    __shared__ SearchLds t;
+    __shared__ SearchLds s;
     __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
     __shared__ uint32_t s_count[2][BB / 64];
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -1048,10 +1043,8 @@ __global__ __launch_bounds__(BB) void k_search_flag(PackedStore store, const uin
     const uint32_t n_tiles = (store.n + MATCH_TILE - 1) / MATCH_TILE;
     const bool suffix = job.flags & SEARCH_F_SUFFIX, negate = job.flags & MATCH_F_NOT, never = job.flags & MATCH_F_NEVER;
     const uint32_t pat_bytes = (job.pat_bits + 7) >> 3;
-    if (tid < n_codes) t.codes[tid] = codes[tid];
-    if (tid < (job.pat_bits + 31) >> 5) t.pat[tid] = __builtin_bswap32(pattern[tid]);  // (at most 256 words)
-    __syncthreads();
-    fill_lut_in(t.codes, t.lut, n_codes);
+    if (tid < (job.pat_bits + 31) >> 5) s.pat[tid] = __builtin_bswap32(pattern[tid]);  // (at most 256 words)
+    load_tables(s.t, codes, n_codes);
     __syncthreads();
     PackedTally tally;
     uint32_t set = 0;
@@ -1069,7 +1062,7 @@ __global__ __launch_bounds__(BB) void k_search_flag(PackedStore store, const uin
                     const uint32_t len = static_cast<uint32_t>(rec.len);
                     if (!job.pat_bits && (!suffix || len == 0)) pos = 0;  // the empty needle: everywhere; at the end of an empty record
                     else if (rec.nb == 0) pos = SEARCH_NONE;              // ... and not at the end of a text that is not there
-                    else if (rec.nb <= SEARCH_LANE_BYTES) pos = search_lane(t, n_codes, job, body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len))), len - job.needle_len);
+                    else if (rec.nb <= SEARCH_LANE_BYTES) pos = search_lane(s, n_codes, job, body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len))), len - job.needle_len);
                     else is_long = true;
                 }
                 pos_of[b] = pos;
@@ -1087,60 +1080,34 @@ __global__ __launch_bounds__(BB) void k_search_flag(PackedStore store, const uin
     tally_lanes(tally, s_failed, s_first, stats);
 }
 
-// walk<false> with the pattern compared on the way (CONTAINS): at every codeword that ends inside the body the pattern's head is compared
-// with the window the step holds anyway, a pass is confirmed on the rest from global memory (an occurrence may run past the lane's
-// bits and past the staged block).  *hit = how many codewords of THIS walk lie in front of the first such occurrence (SEARCH_NONE:
-// none).  A lane walks again whenever its entry changes, so what its last walk leaves is the settled walk's; `at` = the bit of the
-// body's aligned base at which the lane's bits begin.
-__device__ __forceinline__ uint32_t walk_seek(const BatchDecLds &s, uint32_t n_codes, uint32_t lane_bit, uint32_t entry, int64_t room, uint32_t *count, uint32_t *hit,
-                                              const SearchJob &job, const uint32_t *pat, const BodyBits &g, uint32_t at) {
-    uint32_t pos = entry, cnt = 0, first_hit = SEARCH_NONE;
-    while (pos < 256) {
-        const uint32_t p = lane_bit + pos, k = p >> 5, sh = p & 31;
-        const uint64_t two = (static_cast<uint64_t>(s.bits[padded(k)]) << 32) | s.bits[padded(k + 1)];
-        const uint32_t win = static_cast<uint32_t>((two << sh) >> 32);
-        uint32_t meta = s.lut[win >> (32 - BATCH_LUT_BITS)];
-        if (!meta) meta = find_code(s, n_codes, win);
-        const uint32_t len = meta >> 8;
-        if (static_cast<int64_t>(pos + len) > room) {  // the bits ran out inside this codeword (walk<false>'s rule)
-            pos = 512;
-            break;
-        }
-        if (first_hit == SEARCH_NONE && ((win ^ job.head) & job.head_mask) == 0 && static_cast<int64_t>(pos + job.pat_bits) <= room &&
-            confirm_rest(pat, job.pat_bits, g, at + pos))
-            first_hit = cnt;
-        ++cnt;
-        pos += len;
-    }
-    *count = cnt;
-    *hit = first_hit;
-    return pos;
+// Do the pattern's bits lie at bit `at` of the body, where the 32-bit window is `win`?  The head against the window, a pass confirmed on
+// the rest from global memory (an occurrence may run past the lane's bits and past the staged block).
+__device__ __forceinline__ bool pattern_at(const SearchJob &job, const uint32_t *pat, const BodyBits &g, uint32_t at, uint32_t win) {
+    return ((win ^ job.head) & job.head_mask) == 0 && at + job.pat_bits <= g.end_bit && confirm_rest(pat, job.pat_bits, g, at);
 }
 
-// SUFFIX: the lane whose codewords -- number `first` and on, from its settled entry -- hold number `target` walks to it and compares there.
-__device__ __forceinline__ bool walk_to(const BatchDecLds &s, uint32_t n_codes, uint32_t lane_bit, uint32_t entry, int64_t room, uint32_t first, uint32_t target,
-                                        const SearchJob &job, const uint32_t *pat, const BodyBits &g, uint32_t at) {
-    uint32_t pos = entry;
-    for (uint32_t idx = first; pos < 256; ++idx) {
-        const uint32_t p = lane_bit + pos, k = p >> 5, sh = p & 31;
-        const uint64_t two = (static_cast<uint64_t>(s.bits[padded(k)]) << 32) | s.bits[padded(k + 1)];
-        const uint32_t win = static_cast<uint32_t>((two << sh) >> 32);
-        if (idx == target)
-            return ((win ^ job.head) & job.head_mask) == 0 && static_cast<int64_t>(pos + job.pat_bits) <= room && confirm_rest(pat, job.pat_bits, g, at + pos);
-        uint32_t meta = s.lut[win >> (32 - BATCH_LUT_BITS)];
-        if (!meta) meta = find_code(s, n_codes, win);
-        pos += meta >> 8;
+// CONTAINS, the visitor of the fixed point's walks: the pattern compared at every codeword on the way, with the window the step holds
+// anyway.  hit = how many codewords of THIS walk lie in front of the first occurrence (SEARCH_NONE: none); `at` = the bit of the body's
+// aligned base at which the lane's bits begin.
+struct SeekPattern {
+    const SearchJob *job;
+    const uint32_t *pat;
+    const BodyBits *g;
+    uint32_t at, hit;
+    __device__ __forceinline__ bool operator()(uint32_t cnt, uint32_t pos, uint32_t win, uint32_t) {
+        if (hit == SEARCH_NONE && pattern_at(*job, pat, *g, at + pos, win)) hit = cnt;
+        return true;
     }
-    return false;
-}
+};
 
-// One record by the whole workgroup under the tables in `s`: decode_stream's blocks -- the stage, the fixed point over the lanes'
-// entries, the scan of their counts -- without its write half.  CONTAINS compares inside the fixed point's walks (walk_seek) and
-// believes what each lane's LAST walk found, which is the settled walk's: a third pass over the bits, after the scan, cost as much as
-// the write pass it replaced.  A lane's hit becomes a symbol number once the scan has given its first codeword's, and counts when the
-// length allows it (a lane's later hits lie further on).  SUFFIX compares at one boundary, after the scan (walk_to); of the empty
-// needle it asks only whether boundary `target` = length exists.  The lowest hit is reduced over the workgroup through s_min (4
-// words); the blocks end with the first that has one, or once `target` boundaries lie behind.
+// One record by the whole workgroup under the tables in `s`: decode_stream's blocks without its write half.  CONTAINS compares inside
+// the fixed point's walks (SeekPattern) and believes what each lane's LAST walk found, which is the settled walk's: a third pass over
+// the bits, after the scan, cost as much as the write pass it replaced.  A lane's hit becomes a symbol number once the scan has given
+// its first codeword's, and counts when the length allows it (a lane's later hits lie further on).  SUFFIX settles by a counting walk
+// and compares at one boundary: the lane whose codewords hold number `target` walks to it again -- the settled walk counted it, so the
+// walk gets there -- and compares; of the empty needle it asks only whether boundary `target` = length exists.  The lowest hit is
+// reduced over the workgroup through s_min (4 words, free again at the next block's first barrier); the blocks end with the first that
+// has one, or once `target` boundaries lie behind.
 __device__ __forceinline__ uint32_t search_stream(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, uint32_t target, const SearchJob &job, const uint32_t *pat,
                                                   uint32_t *s_min) {
     const uint32_t tid = threadIdx.x;
@@ -1148,37 +1115,23 @@ __device__ __forceinline__ uint32_t search_stream(BatchDecLds &s, uint32_t n_cod
     const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
     uint32_t start = g.first_bit, done = 0;  // the block's first codeword; boundaries so far
     for (uint32_t blk = 0; blk < n_blocks && done <= target; ++blk) {
-        __syncthreads();  // (the block before is done with the stage, entry[BB] and s_min)
-        for (uint32_t k = tid; k < DEC_STAGED; k += BB) s.bits[padded(k)] = static_cast<uint32_t>(body_word_be(g, blk * DEC_WORDS + k));
-        s.entry[tid] = tid == 0 ? start : 0u;
-        __syncthreads();
-        const uint32_t lane_bit = tid * 256, at = blk * DEC_WORDS * 32 + lane_bit;
-        const int64_t room = static_cast<int64_t>(g.end_bit) - at;
-        uint32_t used = 0xffffffffu, exit = 256, count = 0, hit = SEARCH_NONE;
-        for (uint32_t trip = 0; trip < BB; ++trip) {
-            const uint32_t mine = s.entry[tid];
-            int changed = 0;
-            if (mine != used) {
-                const uint32_t was = exit;
-                if (room <= 0) exit = 256u;
-                else if (suffix) exit = walk<false>(s, n_codes, lane_bit, mine, room, &count);
-                else exit = walk_seek(s, n_codes, lane_bit, mine, room, &count, &hit, job, pat, g, at);
-                used = mine;
-                changed = exit != was || trip == 0;
-            }
-            __syncthreads();
-            if (changed) s.entry[tid + 1] = exit - 256;
-            if (!__syncthreads_or(changed)) break;
-        }
-        uint32_t total;
-        const uint32_t first = done + block_exclusive_scan(count, s.wsum, &total);  // (s.wsum: the next block's first barrier lies between two scans)
+        const uint32_t at = blk * DEC_WORDS * 32 + tid * 256;
+        JustCount counting;
+        SeekPattern seek{&job, pat, &g, at, SEARCH_NONE};
+        const Settled b = suffix ? settle_block(s, n_codes, g, blk, start, counting) : settle_block(s, n_codes, g, blk, start, seek);
+        const uint32_t first = done + b.first;
         uint32_t found = SEARCH_NONE;
         if (!suffix) {
-            if (hit != SEARCH_NONE && first + hit <= target) found = first + hit;
+            if (seek.hit != SEARCH_NONE && first + seek.hit <= target) found = first + seek.hit;
         } else if (!job.pat_bits) {
-            if (done + total >= target) found = target;  // (the same for every lane)
-        } else if (first <= target && target < first + count && walk_to(s, n_codes, lane_bit, used, room, first, target, job, pat, g, at)) {
-            found = target;
+            if (done + b.total >= target) found = target;  // (the same for every lane)
+        } else if (first <= target && target < first + b.count) {
+            uint32_t again;
+            (void)walk(s, n_codes, b.used, b.room, &again, [&](uint32_t cnt, uint32_t pos, uint32_t win, uint32_t) {
+                if (first + cnt != target) return true;
+                if (pattern_at(job, pat, g, at + pos, win)) found = target;
+                return false;
+            });
         }
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {
@@ -1191,11 +1144,12 @@ __device__ __forceinline__ uint32_t search_stream(BatchDecLds &s, uint32_t n_cod
         for (int w = 0; w < BB / 64; ++w)
             if (s_min[w] < found) found = s_min[w];
         if (found != SEARCH_NONE) return found;  // (the same for every lane; boundaries ascend with the blocks: the lowest)
-        start = s.entry[BB];
-        done += total;
+        start = b.start;
+        done += b.total;
     }
     return SEARCH_NONE;
 }
+
 
 // k_search_long: k_packed_decode's shape over long_list -- the sorted codes and the first-level table once per workgroup, the listed
 // records strided; the pattern (big-endian words) and the reduction's 4 words lie in the stage the decode keeps its symbols in.  A
@@ -1211,10 +1165,8 @@ __global__ __launch_bounds__(BB) void k_search_long(PackedStore store, const uin
     const uint32_t n_long = static_cast<uint32_t>(stats[SEARCH_N_LONG]);
     if (blockIdx.x >= n_long) return;
     uint32_t *pat = s.out, *s_min = s.out + SEARCH_PATTERN_BYTES / 4;
-    if (tid < n_codes) s.codes[tid] = codes[tid];
     if (tid < (job.pat_bits + 31) >> 5) pat[tid] = __builtin_bswap32(pattern[tid]);
-    __syncthreads();
-    fill_lut(s, n_codes);
+    load_tables(s.t, codes, n_codes);
     const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
     for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
         const uint32_t b = long_list[i];

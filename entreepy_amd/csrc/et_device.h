@@ -1,5 +1,5 @@
 // et_device.h -- what every kernel file (et_kernels.hip, et_kernels_fallback.hip, et_treewalk.hip, et_rowsync.hip, et_batch.hip)
-// needs, defined once: the wavefront / workgroup scans, the stream word that is zero beyond the stream's end, the hand-over of
+// needs, defined once: the wavefront / workgroup scans, the 16-byte chunk of a text that loads only the text's own bytes, the stream word that is zero beyond the stream's end, the hand-over of
 // pinned memory to the host that polls (the device half of wait_for_word, et_ctx.h), and on the host side the CU count, the
 // residency query and the launch that carries its own events.  No LDS is declared here.  Included by .hip files only.
 #pragma once
@@ -64,6 +64,40 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t *s
     if (wave > 2) before += w2;
     *total = w0 + w1 + w2 + w3;
     return before + (inc - x);
+}
+
+// --------------------------------------------------------------------------------
+// input addressing
+// --------------------------------------------------------------------------------
+// The text is addressed relative to a 16-byte aligned base: the stream occupies
+// bytes [lo, hi) of it (lo < 16).  A lane's 16-byte chunk is loaded with one
+// dwordx4 when it lies fully inside [lo, hi); the (at most two) partial chunks of a
+// stream are assembled from guarded byte loads so nothing outside it is touched.
+struct Chunk {
+    uint32_t w[4];
+    uint32_t valid;  // bit k set <=> byte k belongs to the stream
+};
+
+__device__ __forceinline__ Chunk load_chunk(const uint8_t *__restrict__ base, uint64_t off, uint64_t lo, uint64_t hi) {
+    Chunk c;
+    if (off >= lo && off + 16 <= hi) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(base + off);
+        c.w[0] = v.x; c.w[1] = v.y; c.w[2] = v.z; c.w[3] = v.w;
+        c.valid = 0xffffu;
+    } else {
+        c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0;
+        c.valid = 0;
+        if (off < hi && off + 16 > lo) {
+            for (int k = 0; k < 16; ++k) {
+                const uint64_t p = off + k;
+                if (p >= lo && p < hi) {
+                    c.w[k >> 2] |= static_cast<uint32_t>(base[p]) << (8 * (k & 3));
+                    c.valid |= 1u << k;
+                }
+            }
+        }
+    }
+    return c;
 }
 
 // --------------------------------------------------------------------------------

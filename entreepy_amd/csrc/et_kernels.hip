@@ -40,38 +40,7 @@ namespace et {
 // --------------------------------------------------------------------------------
 // input addressing
 // --------------------------------------------------------------------------------
-// The text is addressed relative to a 16-byte aligned base: the stream occupies
-// bytes [lo, hi) of it (lo < 16).  A lane's 16-byte chunk is loaded with one
-// dwordx4 when it lies fully inside [lo, hi); the (at most two) partial chunks of a
-// stream are assembled from guarded byte loads so nothing outside it is touched.
-struct Chunk {
-    uint32_t w[4];
-    uint32_t valid;  // bit k set <=> byte k belongs to the stream
-};
-
-__device__ __forceinline__ Chunk load_chunk(const uint8_t *__restrict__ base, uint64_t off, uint64_t lo, uint64_t hi) {
-    Chunk c;
-    if (off >= lo && off + 16 <= hi) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(base + off);
-        c.w[0] = v.x; c.w[1] = v.y; c.w[2] = v.z; c.w[3] = v.w;
-        c.valid = 0xffffu;
-    } else {
-        c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0;
-        c.valid = 0;
-        if (off < hi && off + 16 > lo) {
-            for (int k = 0; k < 16; ++k) {
-                const uint64_t p = off + k;
-                if (p >= lo && p < hi) {
-                    c.w[k >> 2] |= static_cast<uint32_t>(base[p]) << (8 * (k & 3));
-                    c.valid |= 1u << k;
-                }
-            }
-        }
-    }
-    return c;
-}
-
-// Tile-level version: `interior` (workgroup-uniform, so a scalar branch) says the whole
+// Tile-level version of load_chunk (et_device.h): `interior` (workgroup-uniform, so a scalar branch) says the whole
 // tile lies inside the stream and every chunk of it is a plain 16-byte load.
 // NT: a non-temporal load (the text is read once per pass: nothing of it is worth a cache line)
 template <bool NT = false>

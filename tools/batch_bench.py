@@ -78,6 +78,77 @@ sys.path.insert(0, ROOT)
 
 SHAPES = [(1024, 64 * 1024), (4096, 4 * 1024)]
 REPS, WARMUP = 20, 3
+TABLE = ["et_build_codebook", "et_body_bound", "et_codebook_is_complete"]
+STORE = TABLE + ["et_encode_packed_device"]
+
+
+def _open(lib_path, names):
+    """-> (L, h, the device): the library at lib_path with the named entry points (and the context's own) declared, and a context on
+    torch's current stream."""
+    import torch
+
+    from entreepy_amd import _native as N
+
+    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error"] + names
+    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)  # (torch is imported: the process-wide HIP runtime is loaded)
+    h = ctypes.c_void_p()
+    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
+    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+    return L, h, torch.device("cuda", 0)
+
+
+def _timed(fn):
+    """WARMUP untimed calls, then REPS between HIP events on the stream: the median, and the spread."""
+    import torch
+
+    ms = []
+    for rep in range(WARMUP + REPS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if rep >= WARMUP:
+            ms.append(e0.elapsed_time(e1))
+    return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def _codebook(L, text):
+    """-> the complete table built from the histogram of `text` (a tensor on the device, or numpy arrays on the host)"""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    if isinstance(text, torch.Tensor):
+        hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
+    else:
+        hist = sum(np.bincount(t, minlength=256) for t in text).astype(np.uint64)
+    cb = N.Codebook()
+    assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+    return cb
+
+
+def _packed_store(L, h, text, index, cb=None):
+    """-> (cb, bodies, body bytes, body_index, text_index), the tensors on the device: the records text[index[j] : index[j + 1]] (text a
+    tensor on the device, index numpy u64) as a packed store (et_encode_packed_device) under cb, or under a table from the text's histogram."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    if cb is None:
+        cb = _codebook(L, text)
+    n, total = index.size - 1, int(index[-1])
+    cap = L.et_body_bound(ctypes.byref(cb), total) + n
+    bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=text.device)
+    text_index = torch.from_numpy(index.view(np.int64)).to(text.device)
+    body_index = torch.zeros(n + 1, dtype=torch.int64, device=text.device)
+    res = N.PackedResult()
+    assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), n, bodies.data_ptr(), cap, body_index.data_ptr(), None,
+                                     ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+    torch.cuda.synchronize()
+    return cb, bodies, int(res.out_bytes), body_index, text_index
 
 
 def _leg(leg, lib_path):
@@ -87,26 +158,20 @@ def _leg(leg, lib_path):
     from entreepy_amd import _native as N
     from tests import corpus
 
-    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_encode_bound", "et_encode_device", "et_decode_device", "et_last_error"]
+    names = ["et_encode_bound", "et_encode_device", "et_decode_device"]
     if leg == "batch":
         names += ["et_encode_batch_device", "et_decode_batch_device"]
     if leg == "packed":
         names += ["et_encode_packed_device", "et_decode_packed_device"]
     if leg in ("shared", "packed", "dense"):
-        names += ["et_encode_shared_device", "et_decode_shared_device", "et_build_codebook", "et_write_header", "et_body_bound", "et_codebook_is_complete"]
-    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)  # (torch is imported: the process-wide HIP runtime is loaded)
-    dev = torch.device("cuda", 0)
-    h = ctypes.c_void_p()
-    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
-    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+        names += ["et_encode_shared_device", "et_decode_shared_device", "et_write_header"] + TABLE
+    L, h, dev = _open(lib_path, names)
     results = {}
     for count, size in SHAPES:
         text = corpus.text_like_torch(count * size, 0xB47C4 + size, dev)
         bound = L.et_encode_bound(size)
         if leg in ("shared", "packed", "dense"):  # one table for the whole shape, from the histogram of all of its text
-            hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
-            cb = N.Codebook()
-            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+            cb = _codebook(L, text)
             bound = (L.et_body_bound(ctypes.byref(cb), size) + 15) // 16 * 16
             head, head_len = np.zeros(8192, np.uint8), ctypes.c_size_t(0)
             assert L.et_write_header(ctypes.byref(cb), count * size, head.ctypes.data, head.size, ctypes.byref(head_len)) == 0
@@ -229,42 +294,13 @@ def _gather_leg(leg, lib_path):
     from entreepy_amd import _native as N
     from tests import corpus
 
-    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
-             "et_decode_packed_device", "et_decode_shared_device"] + (["et_decode_packed_gather_device"] if leg == "gather" else [])
-    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
-    dev = torch.device("cuda", 0)
-    h = ctypes.c_void_p()
-    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
-    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device", "et_decode_shared_device"] + (["et_decode_packed_gather_device"] if leg == "gather" else []))
     item = np.dtype([(name, {ctypes.c_uint64: "<u8", ctypes.c_int32: "<i4", ctypes.c_uint32: "<u4"}[t]) for name, t in N.BatchItem._fields_])
-
-    def timed(fn):
-        ms = []
-        for rep in range(WARMUP + REPS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if rep >= WARMUP:
-                ms.append(e0.elapsed_time(e1))
-        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
     results = {}
     for count, size in SHAPES:
         text = corpus.text_like_torch(count * size, 0xB47C4 + size, dev)
-        hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
-        cb = N.Codebook()
-        assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
-        cap = count * L.et_body_bound(ctypes.byref(cb), size)
-        bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
-        text_index = torch.arange(count + 1, dtype=torch.int64, device=dev) * size
-        body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, np.arange(count + 1, dtype=np.uint64) * np.uint64(size))
         res = N.PackedResult()
-        assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), count * size, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
-                                         ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
-        body_bytes = int(res.out_bytes)
-        torch.cuda.synchronize()
         shape = {"body_bytes": body_bytes}
         for name in SELECTIONS:
             rows = _selection(name, count)
@@ -297,11 +333,11 @@ def _gather_leg(leg, lib_path):
             run()
             torch.cuda.synchronize()
             assert torch.equal(dec[:need], want), "decoded rows differ from the text"
-            shape[name] = {"rows": int(rows.size), **timed(run)}
+            shape[name] = {"rows": int(rows.size), **_timed(run)}
             if leg == "gather":
-                shape[name]["sizes_only"] = timed(lambda: gather(None))
+                shape[name]["sizes_only"] = _timed(lambda: gather(None))
                 if name == "identity":
-                    shape[name]["packed_decode"] = timed(packed)
+                    shape[name]["packed_decode"] = _timed(packed)
             del dec, want
         results[f"{count}x{size}"] = shape
         del text, bodies
@@ -343,31 +379,11 @@ def _match_leg(leg, lib_path, shapes):
     """match / match_baseline: per shape and selectivity a packed store (et_encode_packed_device, untimed), then the timed filter: the
     call under PREFIX and EQUAL (and count only) -- or what it replaces: et_decode_packed_device of the whole store, then the first L
     bytes of every record gathered, compared, the lengths tested and nonzero, in torch on the device."""
-    import numpy as np
     import torch
 
     from entreepy_amd import _native as N
 
-    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
-             "et_decode_packed_device"] + (["et_match_packed_device"] if leg == "match" else [])
-    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
-    dev = torch.device("cuda", 0)
-    h = ctypes.c_void_p()
-    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
-    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
-
-    def timed(fn):
-        ms = []
-        for rep in range(WARMUP + REPS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if rep >= WARMUP:
-                ms.append(e0.elapsed_time(e1))
-        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device"] + (["et_match_packed_device"] if leg == "match" else []))
     results = {}
     for count, size in SHAPES + [KEY_SHAPE]:
         shape_name = f"{count}x{size}" if isinstance(size, int) else f"{count}x{size[0]}-{size[1]}"
@@ -376,19 +392,9 @@ def _match_leg(leg, lib_path, shapes):
         shape = {}
         for sel_name, fraction in SELECTIVITIES:
             text, index, chosen, key = _match_store(count, size, fraction, dev)
-            hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
-            cb = N.Codebook()
-            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+            cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, index)
             total = int(index[-1])
-            cap = L.et_body_bound(ctypes.byref(cb), total) + count
-            bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
-            text_index = torch.from_numpy(index.view(np.int64)).to(dev)
-            body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
             res = N.PackedResult()
-            assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
-                                             ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
-            body_bytes = int(res.out_bytes)
-            torch.cuda.synchronize()
             lengths = text_index[1:] - text_index[:-1]
 
             def torch_filter(buf, needle, equal):  # the first len(needle) bytes of every record gathered and compared, the lengths tested, nonzero
@@ -414,8 +420,8 @@ def _match_leg(leg, lib_path, shapes):
                     call(needle, mode)
                     torch.cuda.synchronize()
                     assert mres.n_match == want.numel() and torch.equal(d_rows[: mres.n_match].long(), want), "the rows differ from the records chosen"
-                    entry[name] = {"needle_bytes": len(needle), "rows": int(mres.n_match), **timed(lambda: call(needle, mode))}
-                    entry[name]["count_only"] = timed(lambda: call(needle, mode, None))
+                    entry[name] = {"needle_bytes": len(needle), "rows": int(mres.n_match), **_timed(lambda: call(needle, mode))}
+                    entry[name]["count_only"] = _timed(lambda: call(needle, mode, None))
             else:
                 dec = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
 
@@ -427,7 +433,7 @@ def _match_leg(leg, lib_path, shapes):
 
                 for name, (needle, mode, want) in needles.items():
                     assert torch.equal(baseline(needle, name == "equal"), want), "the rows differ from the records chosen"
-                    entry[name] = {"needle_bytes": len(needle), "rows": int(want.numel()), **timed(lambda: baseline(needle, name == "equal"))}
+                    entry[name] = {"needle_bytes": len(needle), "rows": int(want.numel()), **_timed(lambda: baseline(needle, name == "equal"))}
                 del dec
             shape[sel_name] = entry
             del text, bodies
@@ -479,31 +485,11 @@ def _search_leg(leg, lib_path, shapes):
     against the plain texts first -- or the first step of anything that searches by decoding: et_decode_packed_device of the whole
     store.  search_sweep: stores of SWEEP_BYTES of text in records of one size each, 10 % of them with the needle, under CONTAINS;
     which path a size takes is the library's et_search_lane_bytes(), reported beside the times."""
-    import numpy as np
     import torch
 
     from entreepy_amd import _native as N
 
-    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
-             "et_decode_packed_device"] + ([] if leg == "search_baseline" else ["et_search_packed_device", "et_search_lane_bytes"])
-    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
-    dev = torch.device("cuda", 0)
-    h = ctypes.c_void_p()
-    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
-    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
-
-    def timed(fn):
-        ms = []
-        for rep in range(WARMUP + REPS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if rep >= WARMUP:
-                ms.append(e0.elapsed_time(e1))
-        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device"] + ([] if leg == "search_baseline" else ["et_search_packed_device", "et_search_lane_bytes"]))
     sweep = leg == "search_sweep"
     results = {"lane_bytes": int(L.et_search_lane_bytes())} if sweep else {}
     for count, size in [(SWEEP_BYTES // s, s) for s in SWEEP_SIZES] if sweep else SHAPES + [KEY_SHAPE]:
@@ -514,19 +500,9 @@ def _search_leg(leg, lib_path, shapes):
         for sel_name, fraction in SEARCH_SELECTIVITIES[1:] if sweep else SEARCH_SELECTIVITIES:
             host, index, needle, (rows, pos, ends) = _search_store(count, size, fraction)
             text = torch.from_numpy(host).to(dev)
-            hist = np.bincount(host, minlength=256).astype(np.uint64)
-            cb = N.Codebook()
-            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+            cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, index, _codebook(L, [host]))
             total = int(index[-1])
-            cap = L.et_body_bound(ctypes.byref(cb), total) + count
-            bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
-            text_index = torch.from_numpy(index.view(np.int64)).to(dev)
-            body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
             res = N.PackedResult()
-            assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
-                                             ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
-            body_bytes = int(res.out_bytes)
-            torch.cuda.synchronize()
             entry = {"records": count, "text_bytes": total, "body_bytes": body_bytes, "needle_bytes": len(needle), "contain": len(rows), "end_with": len(ends)}
             if leg == "search_baseline":
                 dec = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
@@ -539,7 +515,7 @@ def _search_leg(leg, lib_path, shapes):
                 decode()
                 torch.cuda.synchronize()
                 assert torch.equal(dec[:total], text), "decoded bytes differ from the text"
-                entry["decode"] = timed(decode)
+                entry["decode"] = _timed(decode)
                 del dec
             else:
                 d_rows, d_pos = torch.zeros(count, dtype=torch.int32, device=dev), torch.zeros(count, dtype=torch.int32, device=dev)
@@ -558,8 +534,8 @@ def _search_leg(leg, lib_path, shapes):
                         assert d_pos[: mres.n_match].tolist() == pos, "the positions differ from the plain texts'"
                     if sweep and name == "suffix":
                         continue
-                    entry[name] = {"rows": int(mres.n_match), **timed(lambda: call(mode))}
-                entry["contains"]["count_only"] = timed(lambda: call(N.ET_SEARCH_CONTAINS, None, None))
+                    entry[name] = {"rows": int(mres.n_match), **_timed(lambda: call(mode))}
+                entry["contains"]["count_only"] = _timed(lambda: call(N.ET_SEARCH_CONTAINS, None, None))
             shape[sel_name] = entry
             del text, bodies
         results[shape_name] = shape
@@ -597,55 +573,18 @@ def _join_leg(leg, lib_path):
     """join / join_baseline: per key set and selectivity two packed stores (et_encode_packed_device, untimed), then the timed join: the
     call with d_rows and d_key_of_row (and count only) -- or what it replaces: one et_match_packed_device(ET_MATCH_EQUAL) per key, then
     the union of their rows sorted in torch."""
-    import numpy as np
     import torch
 
     from entreepy_amd import _native as N
 
-    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
-             "et_match_packed_device"] + (["et_join_packed_device"] if leg == "join" else [])
-    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
-    dev = torch.device("cuda", 0)
-    h = ctypes.c_void_p()
-    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
-    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
-
-    def timed(fn):
-        ms = []
-        for rep in range(WARMUP + REPS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if rep >= WARMUP:
-                ms.append(e0.elapsed_time(e1))
-        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
-    def pack(cb, host_text, index):
-        """-> (bodies, body bytes, body_index, text_index) on the device"""
-        n, total = index.size - 1, int(index[-1])
-        text = torch.from_numpy(host_text).to(dev)
-        cap = L.et_body_bound(ctypes.byref(cb), total) + n
-        bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
-        text_index = torch.from_numpy(index.view(np.int64)).to(dev)
-        body_index = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        res = N.PackedResult()
-        assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), n, bodies.data_ptr(), cap, body_index.data_ptr(), None,
-                                         ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
-        torch.cuda.synchronize()
-        return bodies, int(res.out_bytes), body_index, text_index
-
+    L, h, dev = _open(lib_path, STORE + ["et_match_packed_device"] + (["et_join_packed_device"] if leg == "join" else []))
     count, size = KEY_SHAPE
     shape = {}
     for n_keys in JOIN_KEYS:
         per_keys = {}
         for sel_name, fraction in JOIN_SELECTIVITIES:
             text, index, key_text, key_index = _join_store(count, size, n_keys, fraction)
-            hist = (np.bincount(text, minlength=256) + np.bincount(key_text, minlength=256)).astype(np.uint64)
-            cb = N.Codebook()
-            assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
-            bodies, body_bytes, body_index, text_index = pack(cb, text, index)
+            cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, torch.from_numpy(text).to(dev), index, _codebook(L, [text, key_text]))  # (one table for both stores)
             # the expected rows: set membership over the plain texts; the key of a row: the first index of its text among the keys
             blob, key_blob = text.tobytes(), key_text.tobytes()
             keys = [key_blob[int(a) : int(b)] for a, b in zip(key_index[:-1], key_index[1:])]
@@ -658,7 +597,7 @@ def _join_leg(leg, lib_path):
             entry = {"records": count, "keys": n_keys, "rows": len(want_rows), "body_bytes": body_bytes}
             d_rows = torch.zeros(count, dtype=torch.int32, device=dev)
             if leg == "join":
-                key_bodies, key_body_bytes, key_body_index, key_text_index = pack(cb, key_text, key_index)
+                _, key_bodies, key_body_bytes, key_body_index, key_text_index = _packed_store(L, h, torch.from_numpy(key_text).to(dev), key_index, cb)
                 d_key_of_row = torch.zeros(count, dtype=torch.int32, device=dev)
                 jres = N.JoinResult()
 
@@ -672,8 +611,8 @@ def _join_leg(leg, lib_path):
                 torch.cuda.synchronize()
                 assert jres.n_match == len(want_rows) and d_rows[: jres.n_match].tolist() == want_rows, "the rows differ from set membership over the texts"
                 assert d_key_of_row[: jres.n_match].tolist() == want_keys, "a key number is not the first index of the row's text"
-                entry.update(timed(call))
-                entry["count_only"] = timed(lambda: call(None))
+                entry.update(_timed(call))
+                entry["count_only"] = _timed(lambda: call(None))
             else:
                 mres = N.MatchResult()
 
@@ -688,7 +627,7 @@ def _join_leg(leg, lib_path):
                 got = baseline()
                 torch.cuda.synchronize()
                 assert got.tolist() == want_rows, "the rows differ from set membership over the texts"
-                entry.update(timed(baseline))
+                entry.update(_timed(baseline))
             per_keys[sel_name] = entry
             del bodies
         shape[f"{n_keys}_keys"] = per_keys
@@ -706,26 +645,7 @@ def _take_leg(leg, lib_path):
     from entreepy_amd import _native as N
     from tests import corpus
 
-    names = ["et_ctx_create", "et_ctx_destroy", "et_ctx_set_stream", "et_last_error", "et_build_codebook", "et_body_bound", "et_codebook_is_complete", "et_encode_packed_device",
-             "et_decode_packed_gather_device"] + (["et_take_packed_device"] if leg == "take" else [])
-    L = N.declare(ctypes.CDLL(lib_path, mode=ctypes.RTLD_GLOBAL), names)
-    dev = torch.device("cuda", 0)
-    h = ctypes.c_void_p()
-    assert L.et_ctx_create(0, ctypes.byref(h)) == 0
-    assert L.et_ctx_set_stream(h, ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
-
-    def timed(fn):
-        ms = []
-        for rep in range(WARMUP + REPS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if rep >= WARMUP:
-                ms.append(e0.elapsed_time(e1))
-        return {"ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_gather_device"] + (["et_take_packed_device"] if leg == "take" else []))
     rng = np.random.default_rng(0x7A4E5)
     count, size = KEY_SHAPE
     key_lengths = rng.integers(size[0], size[1] + 1, size=count)
@@ -735,18 +655,8 @@ def _take_leg(leg, lib_path):
     for shape_name, count, index, selections in stores:
         total = int(index[-1])
         text = corpus.text_like_torch(total, 0xB47C4 + count, dev)
-        hist = torch.bincount(text.to(torch.int32), minlength=256).cpu().numpy().astype(np.uint64)
-        cb = N.Codebook()
-        assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
-        cap = L.et_body_bound(ctypes.byref(cb), total) + count
-        bodies = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
-        text_index = torch.from_numpy(index.view(np.int64)).to(dev)
-        body_index = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, index)
         res = N.PackedResult()
-        assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, text_index.data_ptr(), count, bodies.data_ptr(), cap, body_index.data_ptr(), None,
-                                         ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
-        body_bytes = int(res.out_bytes)
-        torch.cuda.synchronize()
         host_bodies, bi = bodies[:body_bytes].cpu().numpy(), body_index.cpu().numpy().view(np.uint64)
         shape = {"body_bytes": body_bytes}
         for name in selections:
@@ -772,10 +682,10 @@ def _take_leg(leg, lib_path):
                 torch.cuda.synchronize()
                 assert np.array_equal(out[:need].cpu().numpy(), want), "the taken bodies differ from the store's"
                 assert np.array_equal(np.diff(out_body_index.cpu().numpy()), (bi[at + 1] - bi[at]).astype(np.int64)) and int(out_text_index[-1]) == text_need
-                entry.update(timed(take))
-                entry["sizes_only"] = timed(lambda: take(None))
+                entry.update(_timed(take))
+                entry["sizes_only"] = _timed(lambda: take(None))
                 src = bodies[:need] if need <= body_bytes else torch.zeros(need, dtype=torch.uint8, device=dev)
-                entry["copy_floor"] = timed(lambda: out[:need].copy_(src))
+                entry["copy_floor"] = _timed(lambda: out[:need].copy_(src))
                 entry["vs_copy_floor"] = round(entry["ms"] / entry["copy_floor"]["ms"], 2)
             else:
                 dec = torch.zeros(text_need + 64, dtype=torch.uint8, device=dev)
@@ -791,7 +701,7 @@ def _take_leg(leg, lib_path):
                 baseline()
                 torch.cuda.synchronize()
                 assert np.array_equal(out[:need].cpu().numpy(), want), "the re-encoded bodies differ from the store's"
-                entry.update(timed(baseline))
+                entry.update(_timed(baseline))
                 del dec
             shape[name] = entry
             del out, want
