@@ -13,6 +13,8 @@ from .codec import (  # noqa: F401
     EntreepyError,
     JoinResult,
     MATCH_EQUAL,
+    MATCH_LESS,
+    MATCH_LESS_EQUAL,
     MATCH_NOT,
     MATCH_PREFIX,
     MatchResult,

@@ -115,6 +115,7 @@ class MatchResult(ctypes.Structure):
 
 
 ET_MATCH_EQUAL, ET_MATCH_PREFIX, ET_MATCH_NOT = 0, 1, 0x100  # et_match_packed_device's mode
+ET_MATCH_LESS, ET_MATCH_LESS_EQUAL = 4, 5  # ... its order modes (2 and 3 are none)
 ET_SEARCH_CONTAINS, ET_SEARCH_SUFFIX = 0, 1  # et_search_packed_device's mode; ET_MATCH_NOT may be or-ed in
 
 

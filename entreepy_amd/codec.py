@@ -88,6 +88,7 @@ class TakeResult:  # struct et_take_result, and the call's own status in front
 
 
 MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT =N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_MATCH_NOT  # match_packed_device's mode
+MATCH_LESS, MATCH_LESS_EQUAL = N.ET_MATCH_LESS, N.ET_MATCH_LESS_EQUAL  # ... its order modes: text < needle, text <= needle (with MATCH_NOT: >=, >)
 SEARCH_CONTAINS, SEARCH_SUFFIX = N.ET_SEARCH_CONTAINS, N.ET_SEARCH_SUFFIX  # search_packed_device's mode; MATCH_NOT may be or-ed in
 
 
@@ -552,7 +553,8 @@ class Context:
 
     def match_packed_device(self, codebook, bodies, body_index, text_index, needle, mode, rows=None, status=None):
         """The records of the store (bodies, body_index, text_index: decode_packed_gather_device's) whose text equals `needle`
-        (MATCH_EQUAL) or begins with it (MATCH_PREFIX) -- with MATCH_NOT or-ed in, the valid records that do not -- found on the
+        (MATCH_EQUAL), begins with it (MATCH_PREFIX), or lies below it as bytes compare (MATCH_LESS: text < needle, MATCH_LESS_EQUAL:
+        text <= needle) -- with MATCH_NOT or-ed in, the valid records that do not: >= and > for the order modes -- found on the
         compressed bytes, nothing decoded.  needle: bytes on the host.  rows: int32/uint32 CUDA tensor that takes the selected record
         numbers, ascending (decode_packed_gather_device's rows); None: count only.  status: optional uint8 CUDA tensor of one et_status
         byte per record; a failed record is never selected.  -> MatchResult; .status is ET_OK or ET_ERR_CAP (no row written, .n_match =

@@ -11,7 +11,7 @@
 //            not made for -- texts above et_batch_small_max(), codes beyond 32 bits on encode, dictionaries that are not a full tree
 //            on decode -- runs through et_encode_device / et_decode_device for that stream alone, behind the batch launches (path = 1)
 //   shared   the table goes up once per call, the job records once per chunk of SHARED_CHUNK streams; every chunk ends with its poll
-//   packed   [table 2 KiB][the counters' first values][the match's pattern]: one upload per call of the part it needs, then the
+//   packed   [table 2 KiB][the counters' first values][the match's pattern][the order modes' boundaries]: one upload per call of the part it needs, then the
 //            launches, then one poll.  The records are u64 offset arrays ON THE DEVICE: no job records, no chunks, no host loop.  A
 //            report that leaves in front of the call's last kernel carries the figures that kernel decides by (do the bodies, or the
 //            rows, fit?), so the host returns ET_ERR_CAP or ET_OK from the same figures without waiting for it.
@@ -23,6 +23,7 @@
 //   decode        table + counters -> k_packed_decode (poll)
 //   gather        table + counters -> k_gather_plan -> k_packed_scan -> k_packed_gather (poll: it alone knows the short rows); sizes only: the scan's (poll)
 //   match         counters + pattern (et_encode_pattern, on the host) -> k_match_flag -> k_packed_scan (poll) -> unless count only: k_rows_emit
+//   order         (the match's LESS modes) sorted codes + counters + pattern + boundaries -> k_order_flag -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   search        sorted codes + counters + pattern -> k_search_flag -> k_search_long -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   join          counters -> clear the table -> k_join_build -> k_join_flag (the keys' counters into the report) -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   take          counters -> k_take_plan -> k_take_scan (poll) -> unless sizes only: k_take_copy
@@ -55,7 +56,8 @@ constexpr size_t PK_COUNTER_BYTES = et::PACKED_WORDS * 8;
 constexpr size_t PIN_PK_TABLE = PIN_SH_RESULTS + SCH * 8;  // 2 KiB, as PIN_SH_TABLE
 constexpr size_t PIN_PK_STATS = PIN_PK_TABLE + 2048;       // u64[PACKED_WORDS]
 constexpr size_t PIN_PK_PATTERN = PIN_PK_STATS + PK_COUNTER_BYTES;  // MATCH_PATTERN_BYTES
-constexpr size_t PIN_PK_REPORT = PIN_PK_PATTERN + et::MATCH_PATTERN_BYTES;  // u64[PACKED_WORDS]
+constexpr size_t PK_STARTS_BYTES = ((et::MATCH_NEEDLE_MAX + 1) * 4 + 15) & ~static_cast<size_t>(15);  // the order modes' boundary table, behind the pattern
+constexpr size_t PIN_PK_REPORT = PIN_PK_PATTERN + et::MATCH_PATTERN_BYTES + PK_STARTS_BYTES;  // u64[PACKED_WORDS]
 constexpr size_t PIN_BYTES = PIN_PK_REPORT + PK_COUNTER_BYTES;
 static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the pinned block");
 // The packed calls' device workspace (ctx->packed_ws) begins as the pinned region does, so an upload lands where it came from: the
@@ -63,6 +65,7 @@ static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the p
 //   encode, gather   from PK_SIZES: a size word per record, or per row        take   from PK_SIZES: a TakeRow per row
 //   search  as the match, then a position and a list entry per record
 //   match   behind the pattern: the tile workspace (tile_ws)                   join   behind the counters: the tile workspace, the table's slots, a key number per record
+//   order   (the match's LESS modes) the sorted codes, the counters, the pattern, the boundary table behind the pattern's last word, the tile workspace
 constexpr size_t PK_STATS = 2048, PK_PATTERN = PK_STATS + PK_COUNTER_BYTES, PK_SIZES = 4096, PK_MATCH_TILES = PK_PATTERN + et::MATCH_PATTERN_BYTES;
 static_assert(PK_PATTERN % 16 == 0 && PK_MATCH_TILES % 16 == 0 && PK_SIZES % 16 == 0 && sizeof(et::TakeRow) == 16,
               "k_match_flag loads pattern words, k_packed_scan 16 bytes of counts or sizes, k_take_plan stores a TakeRow as 16 bytes");
@@ -317,6 +320,53 @@ int packed_end(et_ctx *ctx, uint64_t epoch, et_packed_result *res, bool capped, 
     return ET_OK;
 }
 
+// The order modes of et_match_packed_device, behind its argument check.  A needle byte without a code ends the codable prefix
+// needle[:K]: no record holds that byte, so the prefix's bits and the byte itself (the table's last entry) decide.
+int order_call(et_ctx *ctx, const et_codebook *cb, const et::PackedStore &store, const uint8_t *needle, size_t needle_len, int mode, uint32_t *d_rows, size_t cap_rows,
+               uint8_t *d_status, et_match_result *res) {
+    size_t K = 0;
+    uint64_t bits = 0;
+    while (K < needle_len && cb->length[needle[K]] >= 1 && cb->length[needle[K]] <= 32) bits += cb->length[needle[K++]];
+    const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
+    Bump layout{PK_PATTERN + padded};
+    const size_t at_starts = layout.take((K + 1) * 4, 4);
+    const TileOffsets tiles = tile_ws(layout, (store.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    ET_TRY(packed_ensure(ctx, layout.end));
+
+    // the sorted codes, the counters' first values, the prefix's bits and the boundaries lie one behind the other: up in one copy
+    // (2 KiB + 64 bytes + at most 16 KiB of pattern + at most 4 097 words: 35 KiB at the most, where EQUAL and PREFIX send 16 KiB)
+    const uint32_t n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), false);
+    first_counters(ctx);
+    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
+    const int rc = et_encode_pattern(cb, needle, K, pattern, et::MATCH_PATTERN_BYTES, &bits);
+    if (rc != ET_OK) return fail(ctx, rc, "et_encode_pattern");
+    std::memset(pattern + pat_bytes, 0, padded - pat_bytes);
+    uint32_t *starts = pin<uint32_t>(ctx, PIN_PK_TABLE + at_starts);
+    uint32_t bit = 0;
+    for (size_t i = 0; i < K; ++i) {
+        starts[i] = bit << 8 | needle[i];
+        bit += cb->length[needle[i]];
+    }
+    starts[K] = bit << 8 | (K < needle_len ? needle[K] : 0u);
+    et::OrderJob job{};
+    job.pat_bits = static_cast<uint32_t>(bits);
+    job.n_coded = static_cast<uint32_t>(K);
+    job.needle_len = static_cast<uint32_t>(needle_len);
+    job.flags = ((mode & ~ET_MATCH_NOT) == ET_MATCH_LESS_EQUAL ? et::ORDER_F_EQUAL_TOO : 0u) | ((mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u) | (K < needle_len ? et::ORDER_F_TAIL : 0u);
+    for (uint32_t k = 0; k < std::min<size_t>(pat_bytes, 8); ++k) job.head |= static_cast<uint64_t>(pattern[k]) << (56 - 8 * k);
+    res->pattern_bits = job.pat_bits;
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), at_starts + (K + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_order(ctx->stream, store, ws<const uint2>(ctx, 0), n_codes, ws<const uint32_t>(ctx, PK_PATTERN), ws<const uint32_t>(ctx, at_starts), job, d_rows, cap_rows, d_status,
+                     tile_ptrs(ctx, tiles), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the match's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
+    res->n_match = rep[et::PACKED_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_rows_emit saw the same two figures)
+    return ET_OK;
+}
+
 // An item's own failure is the item's; a failure of the runtime under a delegated stream is the call's.
 bool call_level(int rc) { return rc == ET_ERR_HIP || rc == ET_ERR_NOMEM; }
 
@@ -398,12 +448,14 @@ extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
     if (needle_len > et::MATCH_NEEDLE_MAX) return fail(ctx, ET_ERR_ARG, "the needle is longer than et_match_pattern_max()");
     const int what = mode & ~ET_MATCH_NOT;
-    if (what != ET_MATCH_EQUAL && what != ET_MATCH_PREFIX) return fail(ctx, ET_ERR_ARG, "unknown mode");
+    const bool order = what == ET_MATCH_LESS || what == ET_MATCH_LESS_EQUAL;
+    if (what != ET_MATCH_EQUAL && what != ET_MATCH_PREFIX && !order) return fail(ctx, ET_ERR_ARG, "unknown mode");
     *res = et_match_result{};
     if (n_records == 0) return ET_OK;
     ET_TRY(require_complete(ctx, cb));
     DeviceGuard guard(ctx->device);
     const et::PackedStore store{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    if (order) return order_call(ctx, cb, store, needle, needle_len, mode, d_rows, cap_rows, d_status, res);
     Bump layout{PK_MATCH_TILES};
     const TileOffsets tiles = tile_ws(layout, (store.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
     ET_TRY(packed_ensure(ctx, layout.end));

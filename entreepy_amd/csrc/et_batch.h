@@ -148,6 +148,31 @@ struct TileWs {  // the tile workspace of the match and the join
 void launch_match(hipStream_t stream, const PackedStore &store, const uint32_t *pattern, const MatchJob &job, uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status,
                   const TileWs &tiles, const PackedReport &report);
 
+// The order modes of the match (ET_MATCH_LESS, ET_MATCH_LESS_EQUAL): which records' stored text lies below the needle, or at it, as
+// unsigned bytes -- judged on the compressed bytes.  A Huffman code does not keep the order of its symbols, but record and needle are
+// parsed by the same prefix-free code: the first BIT at which body and encoded needle differ lies inside the codeword of the first
+// SYMBOL at which the texts differ, and the host knows where the needle's codewords begin.  So a record costs its first differing
+// bit, one binary search among the needle's boundaries, ONE codeword decoded from the body there, and one byte comparison.
+//   k_order_flag   k_match_flag's frame (tiles, judgement, status bytes, tally, masks, counts) with the sorted codes in LDS: the
+//                  first MATCH_HEAD_BITS compared per lane, a longer common stretch by the whole wavefront for one lane at a time,
+//                  leaving at the first step with a difference; then per lane the boundary (`starts`, global memory), the codeword
+//                  (search_codes) and the comparison
+//   k_packed_scan, k_rows_emit   the match's, unchanged
+// `starts` (u32[n_coded + 1], strictly increasing): entry i = (the bit at which the needle's codeword i begins) << 8 | needle[i];
+// entry n_coded = pat_bits << 8 | the needle's first byte without a code (0 when every byte has one).  n_coded is the number of
+// leading needle bytes with a code; pattern and pat_bits are those bytes' alone.
+enum OrderFlag : uint32_t { ORDER_F_EQUAL_TOO = 1, ORDER_F_TAIL = 4 };  // LESS_EQUAL; a needle byte without a code follows (beside MATCH_F_NOT)
+struct OrderJob {
+    uint64_t head;        // the pattern's first 64 bits, the first at the top, zero behind pat_bits
+    uint32_t pat_bits;    // bits of the encoded codable prefix
+    uint32_t n_coded;     // its bytes of text (K)
+    uint32_t needle_len;  // the whole needle's (for the record: the kernel decides by n_coded and ORDER_F_TAIL and does not read it)
+    uint32_t flags;       // OrderFlag | MATCH_F_NOT
+};
+// codes: the sorted codes on the device (launch_shared_decode's); pattern: as launch_match's; starts: 4-byte aligned.
+void launch_order(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const uint32_t *pattern, const uint32_t *starts, const OrderJob &job,
+                  uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, const TileWs &tiles, const PackedReport &report);
+
 // The search (et_search_packed_device): which records of a packed store CONTAIN, or END WITH, a needle, and where -- judged on the
 // compressed bytes by a walk over the codeword boundaries with nothing written: the needle occurs at symbol i exactly when its bits
 // (et_encode_pattern) lie at the bit where codeword i begins, end inside the body, and i + needle_len <= length.

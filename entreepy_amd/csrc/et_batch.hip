@@ -307,14 +307,16 @@ struct BatchDecLds {
 };
 
 // The code the window begins with, by the binary search alone.
-__device__ __forceinline__ uint32_t search_codes(const CodeTables &t, uint32_t n_codes, uint32_t win) {
+__device__ __forceinline__ uint32_t search_codes(const uint2 *codes, uint32_t n_codes, uint32_t win) {
     uint32_t lo = 0, hi = n_codes;  // codes[0] is the all-zero code of a full tree: codes[lo].x <= win throughout
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (t.codes[mid].x <= win) lo = mid; else hi = mid;
+        if (codes[mid].x <= win) lo = mid; else hi = mid;
     }
-    return t.codes[lo].y;
+    return codes[lo].y;
 }
+
+__device__ __forceinline__ uint32_t search_codes(const CodeTables &t, uint32_t n_codes, uint32_t win) { return search_codes(t.codes, n_codes, win); }
 
 // THE codeword step: length << 8 | symbol of the code the window begins with -- the first-level table, then the search.
 __device__ __forceinline__ uint32_t code_at(const CodeTables &t, uint32_t n_codes, uint32_t win) {
@@ -352,6 +354,12 @@ __device__ __forceinline__ BodyBits body_bits_of(const uint8_t *d_bodies, uint64
 
 // Word k of the body, big-endian; zero behind the last word that holds a byte of it (which is never loaded).
 __device__ __forceinline__ uint64_t body_word_be(const BodyBits &g, uint32_t k) { return k < g.n_words ? __builtin_bswap32(g.words[k]) : 0u; }
+
+// The 32 bits from bit `bit` on, from global memory.
+__device__ __forceinline__ uint32_t body_window(const BodyBits &g, uint32_t bit) {
+    const uint32_t k = bit >> 5;
+    return static_cast<uint32_t>((((body_word_be(g, k) << 32) | body_word_be(g, k + 1)) << (bit & 31)) >> 32);
+}
 
 // The 32 bits from bit `bit` of the staged block on.
 __device__ __forceinline__ uint32_t lane_window(const BatchDecLds &s, uint32_t bit) {
@@ -950,6 +958,142 @@ __global__ __launch_bounds__(BB) void k_match_flag(PackedStore store, const uint
     tally_lanes(tally, s_failed, s_first, stats);
 }
 
+// k_order_flag: k_match_flag's tiles for the order modes (et_batch.h): is the record's stored text -- its first min(length,
+// codewords that end inside the body) symbols -- below the needle, equal to it, or above?  With B = the body's bits, P = pat_bits,
+// K = n_coded and d = the first bit below min(B, P) at which body and pattern differ (MSB-first: the lowest differing byte, its
+// highest differing bit):
+//   d found      i = the needle's codeword d lies in (starts[i] <= d < starts[i + 1], i < K).  i >= length: the text is needle[:length],
+//                a proper prefix: LESS.  Else the body's codeword at bit starts[i] -- it begins where the needle's does, the bits
+//                in front agree -- ends beyond B: the text is needle[:i], LESS; or inside: its symbol differs from needle[i] (a
+//                prefix-free code: different bits inside the needle's codeword are another codeword) and the bytes decide.
+//   none, B < P  the body is a prefix of the pattern, the text a proper prefix of the needle: LESS.
+//   none, P <= B length < K: LESS.  length == K: EQUAL, or LESS where a byte without a code follows in the needle (the tail byte t).
+//                length > K: the codeword at bit P ends beyond B: as length == K; inside: GREATER, or with a tail byte its symbol
+//                against t (no record holds t: they differ).
+// The pad bits behind a body's last codeword decide nothing: a difference there has i >= length or a codeword that ends beyond B.
+// The head: the aligned 8-byte words that hold the body's first min(8, bytes) bytes -- one, or two -- shifted into place; what lies
+// behind the body's bytes in them is garbage that d < min(B, P) keeps out.  Where the first MATCH_HEAD_BITS agree and more can be
+// compared, the lanes are taken one at a time from the ballot and all 64 compare 4 bytes each per step (k_match_flag's loads), the
+// wavefront leaving at the first step with a difference, whose lowest lane's bit goes back to the owner.  A lane then makes at
+// most one binary search in `starts` and decodes at most one codeword.  A failed record is never read and never selected.
+// LDS: the sorted codes (2 KiB) + 8 + 8 + 8 words.
+__global__ __launch_bounds__(BB) void k_order_flag(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, const uint32_t *__restrict__ pattern,
+                                                   const uint32_t *__restrict__ starts, OrderJob job, TileWs tiles, uint8_t *__restrict__ d_status,
+                                                   unsigned long long *__restrict__ stats) {
+    __shared__ uint2 s_codes[256];
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    __shared__ uint32_t s_count[2][BB / 64];
+    constexpr uint32_t HEAD_BYTES = MATCH_HEAD_BITS / 8, NONE = 0xffffffffu;
+    enum : uint32_t { LESS = 0, EQUAL = 1, GREATER = 2 };
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    const uint32_t P = job.pat_bits, K = job.n_coded;
+    const uint32_t n_tiles = (store.n + MATCH_TILE - 1) / MATCH_TILE;
+    const bool equal_too = job.flags & ORDER_F_EQUAL_TOO, negate = job.flags & MATCH_F_NOT, tail = job.flags & ORDER_F_TAIL;
+    if (tid < n_codes) s_codes[tid] = codes[tid];
+    __syncthreads();
+    PackedTally tally;
+    uint32_t set = 0;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, set ^= 1) {
+        const uint32_t b = tile * MATCH_TILE + tid;  // (n <= 0x7fffffff: no wrap)
+        bool valid = false, walk_on = false;
+        uint64_t b0 = 0, len = 0;
+        uint32_t B = 0, m = 0, d = NONE;  // the body's bits (clipped: below), min(B, P), the first differing bit below m
+        if (b < store.n) {
+            const Judged rec = judge_record(store, b);
+            if (d_status) d_status[b] = static_cast<uint8_t>(rec.status);
+            tally.note(b, rec.status);
+            if (!rec.status) {
+                valid = true;
+                b0 = rec.b0;
+                len = rec.len;
+                // (no bit beyond P + 32 is asked for: a longer body counts as one that holds them all)
+                B = static_cast<uint32_t>(rec.nb < MATCH_PATTERN_BYTES + 8 ? rec.nb : MATCH_PATTERN_BYTES + 8) * 8;
+                m = B < P ? B : P;
+                if (m) {
+                    const uint32_t head_bytes = (m + 7) >> 3 < HEAD_BYTES ? (m + 7) >> 3 : HEAD_BYTES;  // (of the body: m <= B)
+                    const uintptr_t a = reinterpret_cast<uintptr_t>(d_bodies) + b0;
+                    const uint64_t *q = reinterpret_cast<const uint64_t *>(a & ~static_cast<uintptr_t>(7));
+                    const uint32_t lead = static_cast<uint32_t>(a & 7);
+                    uint64_t v = q[0] >> (8 * lead);
+                    if (lead + head_bytes > 8) v |= q[1] << (64 - 8 * lead);  // (lead > 0 here; q[1] holds a byte of the head)
+                    const uint64_t x = __builtin_bswap64(v) ^ job.head;
+                    const uint32_t at = x ? static_cast<uint32_t>(__clzll(x)) : 64u;
+                    if (at < (m < MATCH_HEAD_BITS ? m : MATCH_HEAD_BITS)) d = at;
+                    else walk_on = m > MATCH_HEAD_BITS;
+                }
+            }
+        }
+        if (P > MATCH_HEAD_BITS) {  // (the same for every lane)
+            unsigned long long pending = __ballot(walk_on);
+            while (pending) {
+                const int src = __ffsll(pending) - 1;
+                pending &= pending - 1;
+                const uintptr_t body = reinterpret_cast<uintptr_t>(d_bodies) + __shfl(b0, src, 64);
+                const uint32_t m_src = __shfl(m, src, 64), cmp_bytes = (m_src + 7) >> 3;  // (of that body, and of the pattern)
+                uint32_t found = NONE;
+                for (uint32_t step = HEAD_BYTES; step < cmp_bytes; step += 64 * 4) {
+                    const uint32_t off = step + lane * 4;
+                    uint32_t x = 0;
+                    if (off < cmp_bytes) {
+                        const uint32_t nb = cmp_bytes - off < 4 ? cmp_bytes - off : 4;
+                        const uintptr_t a = body + off;
+                        const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~static_cast<uintptr_t>(3));
+                        const uint32_t lead = static_cast<uint32_t>(a & 3);
+                        uint32_t v = w[0] >> (8 * lead);
+                        if (lead + nb > 4) v |= w[1] << (32 - 8 * lead);  // (lead > 0 here; w[1] holds one of the nb bytes)
+                        x = (v ^ pattern[off >> 2]) & (nb == 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u);
+                    }
+                    const unsigned long long differ = __ballot(x != 0);
+                    if (differ) {  // the lowest lane holds the lowest bytes; its first differing bit in stream order
+                        const uint32_t at = off * 8 + static_cast<uint32_t>(__clz(static_cast<int>(__builtin_bswap32(x))));
+                        found = __shfl(at, __ffsll(differ) - 1, 64);
+                        break;
+                    }
+                }
+                if (static_cast<int>(lane) == src && found < m_src) d = found;  // (behind m: the pattern's last byte, beyond its bits)
+            }
+        }
+        bool selected = false;
+        if (valid) {
+            uint32_t cmp = LESS, at = NONE, against = 0, cut = LESS;  // decode at bit `at`: `cut` if the codeword ends beyond B, else its symbol against `against`
+            if (d != NONE) {
+                uint32_t lo = 0, hi = K;  // starts[lo] >> 8 <= d < starts[hi] >> 8 = P throughout
+                while (hi - lo > 1) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if ((starts[mid] >> 8) <= d) lo = mid; else hi = mid;
+                }
+                if (lo < len) {
+                    const uint32_t e = starts[lo];
+                    at = e >> 8;
+                    against = e & 0xffu;
+                }
+            } else if (B >= P && len >= K) {
+                cut = tail ? LESS : EQUAL;
+                if (len == K) cmp = cut;
+                else {
+                    at = P;
+                    against = starts[K] & 0xffu;  // the tail byte; 0 without one: no symbol is below it, GREATER
+                }
+            }
+            if (at != NONE) {
+                const uint32_t left = B - at;  // (at <= P <= B, or at <= d < B); the window is zero beyond B
+                cmp = cut;                     // no bit left: no byte of the body is there to read
+                if (left) {
+                    const BodyBits g = body_bits_of(d_bodies, b0, B >> 3);
+                    uint32_t win = body_window(g, g.first_bit + at);
+                    if (left < 32) win &= ~(0xffffffffu >> left);
+                    const uint32_t meta = search_codes(s_codes, n_codes, win);
+                    if ((meta >> 8) <= left) cmp = (meta & 0xffu) < against ? LESS : GREATER;
+                }
+            }
+            selected = (cmp == LESS || (equal_too && cmp == EQUAL)) != negate;
+        }
+        end_tile(selected, tile, set, tiles, s_count);
+    }
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
 // k_rows_emit (the match's and the join's last launch): a tile per trip, a record per lane: the tile's four masks (the same 32 bytes
 // for every lane), the record's rank among the tile's selected ones by popcounts, its number to rows[base[tile] + rank] -- ascending,
 // as tiles and ranks are -- and, KEYS, its key's (key_of[record]) to key_rows at the same place.  Every workgroup returns at once when
@@ -986,12 +1130,6 @@ struct SearchLds {  // k_search_flag's tables: 7 KiB
     CodeTables t;
     uint32_t pat[SEARCH_PATTERN_BYTES / 4];  // the pattern, big-endian words: bit q of it is bit 31 - q % 32 of word q / 32
 };
-
-// The 32 bits from bit `bit` on, from global memory.
-__device__ __forceinline__ uint32_t body_window(const BodyBits &g, uint32_t bit) {
-    const uint32_t k = bit >> 5;
-    return static_cast<uint32_t>((((body_word_be(g, k) << 32) | body_word_be(g, k + 1)) << (bit & 31)) >> 32);
-}
 
 // Do the pattern's bits behind its first 32 lie behind bit `at` + 32 of the body?  The caller has compared the first 32 and knows
 // that at + pat_bits <= end_bit: every word compared under the mask holds a byte of the body.
@@ -1727,6 +1865,13 @@ void launch_match(hipStream_t stream, const PackedStore &store, const uint32_t *
                   const TileWs &tiles, const PackedReport &r) {
     const uint32_t n_tiles = tiles_of(store.n), grid = capped(n_tiles, MATCH_GRID);
     hipLaunchKernelGGL(k_match_flag, dim3(grid), dim3(BB), 0, stream, store, pattern, job, tiles, d_status, r.stats);
+    launch_scan_emit(stream, n_tiles, grid, tiles, d_rows, cap_rows, nullptr, nullptr, r);
+}
+
+void launch_order(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const uint32_t *pattern, const uint32_t *starts, const OrderJob &job,
+                  uint32_t *d_rows, uint64_t cap_rows, uint8_t *d_status, const TileWs &tiles, const PackedReport &r) {
+    const uint32_t n_tiles = tiles_of(store.n), grid = capped(n_tiles, MATCH_GRID);
+    hipLaunchKernelGGL(k_order_flag, dim3(grid), dim3(BB), 0, stream, store, codes, n_codes, pattern, starts, job, tiles, d_status, r.stats);
     launch_scan_emit(stream, n_tiles, grid, tiles, d_rows, cap_rows, nullptr, nullptr, r);
 }
 

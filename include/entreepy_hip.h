@@ -404,6 +404,20 @@ int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb,
  *     there and never matches EQUAL.  ET_MATCH_NOT, or-ed in, selects the valid records that do NOT match.  The empty needle
  *     matches every valid record under PREFIX, every valid record of length 0 under EQUAL.  A needle byte without a code matches
  *     nothing: the call is ET_OK, pattern_bits is 0, and under NOT every valid record is selected.  needle is HOST memory.
+ *   Order: ET_MATCH_LESS selects the valid records with text_b < needle, ET_MATCH_LESS_EQUAL those with text_b <= needle; with
+ *     ET_MATCH_NOT or-ed in they are >= and > (a failed record is never selected).  The comparison is memcmp's, and Python's on
+ *     bytes: byte by byte as unsigned values, a proper prefix is less.  It is decided on the compressed bytes too: the first bit
+ *     at which body and encoded needle differ lies inside the codeword of the first symbol at which the texts differ, so a record
+ *     costs one codeword decoded at a boundary of the needle's -- `key < x`, `key >= x`, and the bucket counts of a range
+ *     partition from count-only calls.  text_b is the stored text above, hence: a record kept raw elsewhere (no body bytes, a
+ *     length above zero) reads as the empty text and lies below every needle that is not empty.  A body cut exactly behind the
+ *     needle's last codeword compares EQUAL here -- its stored text IS the needle: LESS_EQUAL selects it, LESS does not -- while
+ *     ET_MATCH_EQUAL, which asks for length_b == needle_len, rejects it: `<=` is not `<` or `==` on such a record.  Nothing is
+ *     less than the empty needle; LESS_EQUAL selects the records whose stored text is empty.  A needle byte without a code is
+ *     handled exactly here (EQUAL and PREFIX keep their rule): with j its first position, no record holds that byte, so the order
+ *     is decided against needle[:j], and for a record that starts with needle[:j] and goes on, by its symbol j against the byte
+ *     needle[j]; pattern_bits is the bit count of needle[:j] -- of the whole needle when every byte has a code.  The values 2
+ *     and 3 are no modes.
  *   d_rows[0 .. n_match) (32 bits each, 4-byte aligned, on the device) = the selected record numbers, ascending: the gather
  *     call's d_rows.  Nothing at or beyond d_rows + n_match is written.  d_rows == NULL: count only -- cap_rows is ignored,
  *     d_status and *res are the writing call's.  n_match > cap_rows: the call returns ET_ERR_CAP, no entry of d_rows is written,
@@ -417,13 +431,14 @@ int et_decode_packed_gather_device(et_ctx *ctx, const et_codebook *cb,
  * stream has drained -- and it may follow or precede packed, gather, shared-table and single-stream calls on one ctx with nothing
  * in between and with different tables: d_rows may go straight into et_decode_packed_gather_device on the same ctx. */
 int et_encode_pattern(const et_codebook *cb, const uint8_t *text, size_t n, uint8_t *out, size_t cap, uint64_t *n_bits);
-enum { ET_MATCH_EQUAL = 0, ET_MATCH_PREFIX = 1, ET_MATCH_NOT = 0x100 /* or-ed in: select the valid records that do NOT match */ };
+enum { ET_MATCH_EQUAL = 0, ET_MATCH_PREFIX = 1, ET_MATCH_LESS = 4, ET_MATCH_LESS_EQUAL = 5,
+       ET_MATCH_NOT = 0x100 /* or-ed in: select the valid records that do NOT match */ };
 size_t et_match_pattern_max(void);          /* longest needle in bytes of text: 4096 */
 typedef struct et_match_result {
     uint64_t n_match;       /* rows selected -- also when the call returns ET_ERR_CAP or d_rows is NULL */
     uint64_t n_failed, first_failed;   /* records whose status is not ET_OK, the lowest of them (valid when n_failed > 0) */
     int32_t first_status;   /* et_status of record first_failed */
-    uint32_t pattern_bits;  /* bits of the encoded needle (0 when a needle byte has no code) */
+    uint32_t pattern_bits;  /* bits of the encoded needle (0 when a needle byte has no code; LESS modes: of the bytes in front of it) */
 } et_match_result;
 size_t et_match_result_size(void);
 int et_match_packed_device(et_ctx *ctx, const et_codebook *cb,

@@ -48,6 +48,13 @@ process of its own so that every leg loads exactly one build of the library:
   search_baseline the first step of anything that searches by decoding, and the only part of it this library has:
                   et_decode_packed_device of the same store -- on this tree's library or on the one named by --batch-lib (a build of the
                   commit before the call).
+  order           the match leg's three stores, a tenth of the records copies of record 0: et_match_packed_device(ET_MATCH_LESS) with needles at
+                  the 0.1 %, 10 % and 50 % quantiles of the stored texts and, on the two page shapes, a needle that shares 1 KiB with that
+                  tenth (the wavefront path) -- with rows, and count only, the rows checked against Python's `<` over the plain texts first --
+                  and in the same process ET_MATCH_PREFIX with a 12-byte needle, the floor of a filter that reads one line per record.
+  order_baseline  what the call replaces, as far as this library has it: et_decode_packed_device of the whole store -- on this tree's
+                  library or on the one named by --batch-lib (a build of the commit before the modes); the comparison in torch that a
+                  caller would still have to run behind it is NOT in the figure.
   search_sweep    (only when named) stores of 16 MiB of text in records of 32 .. 4096 bytes, CONTAINS: the times from which
                   SEARCH_LANE_BYTES is chosen -- run it on builds with -DET_SEARCH_LANE_BYTES=0 and =8192 (ET_LIB_PATH names the library)
                   for the two paths at every size.
@@ -64,6 +71,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs join --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/join_bench.json
     python tools/batch_bench.py --legs take --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/take_bench.json
     python tools/batch_bench.py --legs search --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/search_bench.json
+    python tools/batch_bench.py --legs order --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/order_bench.json
 """
 import argparse
 import ctypes
@@ -442,6 +450,77 @@ def _match_leg(leg, lib_path, shapes):
     print(json.dumps(results))
 
 
+ORDER_QUANTILES = (("0.1%", 0.001), ("10%", 0.1), ("50%", 0.5))
+ORDER_SHARED_PREFIX = 1024  # bytes the wavefront-path needle shares with a tenth of the records
+
+
+def _order_leg(leg, lib_path, shapes):
+    """order / order_baseline: per shape a packed store with a tenth of its records copies of record 0 (et_encode_packed_device, untimed),
+    then the timed filter: ET_MATCH_LESS with needles at three quantiles of the stored texts and one that shares 1 KiB with that tenth,
+    with rows and count only, and ET_MATCH_PREFIX with a 12-byte needle beside it -- or what the call replaces: et_decode_packed_device
+    of the whole store (the comparison behind it is left out)."""
+    import torch
+
+    from entreepy_amd import _native as N
+
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device"] + (["et_match_packed_device"] if leg == "order" else []))
+    results = {}
+    for count, size in SHAPES + [KEY_SHAPE]:
+        shape_name = f"{count}x{size}" if isinstance(size, int) else f"{count}x{size[0]}-{size[1]}"
+        if shapes and shape_name not in shapes:
+            continue
+        text, index, chosen, key = _match_store(count, size, 0.1, dev)
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, index)
+        total = int(index[-1])
+        entry = {"records": count, "sharing": int(chosen.size), "text_bytes": total, "body_bytes": body_bytes}
+        if leg == "order":
+            host = text.cpu().numpy()
+            texts = [host[int(index[j]) : int(index[j + 1])].tobytes() for j in range(count)]
+            ranked = sorted(texts)
+            needles = {name: ranked[int(q * count)][:4096] for name, q in ORDER_QUANTILES}  # (et_match_pattern_max())
+            if len(key) > ORDER_SHARED_PREFIX:
+                needles["shares_1KiB"] = key[:ORDER_SHARED_PREFIX] + bytes([key[ORDER_SHARED_PREFIX] ^ 1])
+            d_rows = torch.zeros(count, dtype=torch.int32, device=dev)
+            mres = N.MatchResult()
+
+            def call(needle, mode, rows=d_rows):
+                assert L.et_match_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, needle, len(needle), mode,
+                                                None if rows is None else rows.data_ptr(), count, None, ctypes.byref(mres)) == 0, L.et_last_error(h)
+                assert mres.n_failed == 0
+
+            for name, needle in needles.items():
+                want = [j for j, t in enumerate(texts) if t < needle]
+                call(needle, N.ET_MATCH_LESS)
+                torch.cuda.synchronize()
+                assert mres.n_match == len(want) and d_rows[: mres.n_match].tolist() == want, "the rows differ from Python's `<` over the plain texts"
+                entry[name] = {"needle_bytes": len(needle), "rows": len(want), **_timed(lambda: call(needle, N.ET_MATCH_LESS))}
+                entry[name]["count_only"] = _timed(lambda: call(needle, N.ET_MATCH_LESS, None))
+            floor = key[:MATCH_PREFIX_LEN]
+            call(floor, N.ET_MATCH_PREFIX)
+            torch.cuda.synchronize()
+            assert mres.n_match == sum(t.startswith(floor) for t in texts)
+            entry["prefix_floor"] = {"needle_bytes": len(floor), "rows": int(mres.n_match), **_timed(lambda: call(floor, N.ET_MATCH_PREFIX))}
+            del host, texts, ranked
+        else:
+            dec = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
+            res = N.PackedResult()
+
+            def decode():
+                assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, dec.data_ptr(), total, None,
+                                                 None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                assert res.n_failed == 0 and res.n_short == 0
+
+            decode()
+            torch.cuda.synchronize()
+            assert torch.equal(dec[:total], text[:total]), "the decoded store differs from the text"
+            entry["decode"] = {"comparison_included": False, **_timed(decode)}
+            del dec
+        results[shape_name] = entry
+        del text, bodies
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 SEARCH_NEEDLE_LEN = 12
 SEARCH_SELECTIVITIES = (("0.1%", 0.001), ("10%", 0.1))
 SWEEP_SIZES = (32, 64, 96, 128, 192, 256, 384, 512, 1024, 4096)  # bytes of text per record of the sweep's stores ...
@@ -715,7 +794,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take,search")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take,search,order")
     ap.add_argument("--shapes", default="")  # (the match legs: a comma list of shape names, e.g. 262144x16-48; default: all)
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
@@ -723,6 +802,8 @@ def main():
     a = ap.parse_args()
     if a.leg and a.leg.startswith("match"):
         return _match_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
+    if a.leg and a.leg.startswith("order"):
+        return _order_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg and a.leg.startswith("search"):
         return _search_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg and a.leg.startswith("join"):
@@ -746,6 +827,8 @@ def main():
         legs += [("take_baseline", "take_baseline", a.batch_lib or here), ("take", "take", here)]
     if "search" in a.legs.split(","):
         legs += [("search_baseline", "search_baseline", a.batch_lib or here), ("search", "search", here)]
+    if "order" in a.legs.split(","):
+        legs += [("order_baseline", "order_baseline", a.batch_lib or here), ("order", "order", here)]
     if "search_sweep" in a.legs.split(","):
         legs += [("search_sweep", "search_sweep", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
@@ -770,6 +853,13 @@ def main():
     if "search" in out:  # > 1: the search is faster than the decode of the whole store, the first step of a search by decoding
         out["search_vs_decode"] = {k: {sel: {m: round(out["search_baseline"][k][sel]["decode"]["ms"] / e[m]["ms"], 2) for m in ("contains", "suffix")} for sel, e in v.items()}
                                    for k, v in out["search"].items()}
+    if "order" in out:  # per shape and needle: the decode's time over LESS's (> 1: LESS is faster), whether the medians lie further apart than the two spreads together, LESS over the PREFIX floor
+        out["order_vs_decode"] = {}
+        for k, v in out["order"].items():
+            dec, floor = out["order_baseline"][k]["decode"], v["prefix_floor"]
+            out["order_vs_decode"][k] = {name: {"decode_over_less": round(dec["ms"] / e["ms"], 2),
+                                                "beyond_both_spreads": dec["ms"] - e["ms"] > (dec["max_ms"] - dec["min_ms"]) + (e["max_ms"] - e["min_ms"]),
+                                                "less_over_prefix_floor": round(e["ms"] / floor["ms"], 2)} for name, e in v.items() if isinstance(e, dict) and name != "prefix_floor"}
     if "join" in out:  # > 1: the join call is the faster one
         out["join_vs_baseline"] = {k: {keys: {sel: round(out["join_baseline"][k][keys][sel]["ms"] / e["ms"], 2) for sel, e in v.items()} for keys, v in shape.items()}
                                    for k, shape in out["join"].items()}
