@@ -21,6 +21,8 @@ from .codec import (  # noqa: F401
     PackedResult,
     SEARCH_CONTAINS,
     SEARCH_SUFFIX,
+    SLICE_NO_STOP,
+    SLICE_TO_END,
     TakeResult,
     decode,
     default_context,

@@ -90,6 +90,7 @@ class TakeResult:  # struct et_take_result, and the call's own status in front
 MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT =N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_MATCH_NOT  # match_packed_device's mode
 MATCH_LESS, MATCH_LESS_EQUAL = N.ET_MATCH_LESS, N.ET_MATCH_LESS_EQUAL  # ... its order modes: text < needle, text <= needle (with MATCH_NOT: >=, >)
 SEARCH_CONTAINS, SEARCH_SUFFIX = N.ET_SEARCH_CONTAINS, N.ET_SEARCH_SUFFIX  # search_packed_device's mode; MATCH_NOT may be or-ed in
+SLICE_TO_END, SLICE_NO_STOP = N.ET_SLICE_TO_END, N.ET_SLICE_NO_STOP  # slice_packed_device: a count "to the end"; no stop byte
 
 
 def _check(status, ctx=None):
@@ -627,6 +628,34 @@ class Context:
                                            self._index_ptr(out_text_index, rows.numel()), self._opt_ptr(status), ctypes.byref(res))
         return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
 
+    def slice_packed_device(self, codebook, bodies, body_index, text_index, rows, first, count, out, out_body_index, out_text_index, stop=None, status=None):
+        """Row k of the NEW store is text[first : first + count] of record rows[k] of the store (bodies, body_index, text_index:
+        take_packed_device's; rows=None: row k is record k), cut in front of the first byte `stop` in it -- found and copied on the
+        compressed bytes, nothing decoded: its body, as encode_packed_device would write it under `codebook`, goes to
+        out[out_body_index[k] : out_body_index[k + 1]], and out_text_index[k + 1] - out_text_index[k] is its length.  first, count:
+        an int for every row, or an int32/uint32 CUDA tensor of one value per row (first may be search_packed_device's pos, or that
+        plus the needle's length); count=SLICE_TO_END: to the end.  stop: None, an int 0 .. 255, or one byte.  status: optional uint8
+        CUDA tensor of one et_status byte per ROW; a row that fails becomes an empty record.  out=None: sizes only.  out may not
+        overlap bodies.  -> TakeResult; .status is ET_OK or ET_ERR_CAP (nothing written, .out_bytes = the room needed); any other
+        failure of the call raises.  Stream-ordered like take_packed_device."""
+        n = text_index.numel() - 1
+        n_rows = n if rows is None else rows.numel()
+        what = "rows, first and count are ints or 1-D CUDA tensors of 32-bit integers"
+        first_p, first_v = (None, int(first)) if isinstance(first, (int, np.integer)) else (self._rows_ptr(first, what), 0)
+        count_p, count_v = (None, int(count)) if isinstance(count, (int, np.integer)) else (self._rows_ptr(count, what), 0)
+        assert all(p is None or t.numel() >= n_rows for p, t in ((first_p, first), (count_p, count))), "first and count hold a value per row"
+        if stop is None:
+            stop = SLICE_NO_STOP
+        elif not isinstance(stop, (int, np.integer)):
+            (stop,) = bytes(stop)
+        res = N.TakeResult()
+        self._bind()
+        rc = N.lib().et_slice_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                            None if rows is None else self._rows_ptr(rows, what), n_rows, first_p, first_v, count_p, count_v, int(stop),
+                                            self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows),
+                                            self._index_ptr(out_text_index, n_rows), self._opt_ptr(status), ctypes.byref(res))
+        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -792,6 +821,43 @@ class Context:
         _check(res.status, self._h)
         if res.n_failed:
             raise EntreepyError(res.first_status, f"take_packed: row {res.first_failed}")
+        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
+        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+
+    def slice_packed(self, codebook, blob, out_index, lengths, rows, first, count, stop=None):
+        """decode_packed's store, a list of record numbers (any order, repeats allowed) and where each row's slice begins and how long
+        it is at most (an int for every row, or a list of one per row) -> a store like take_packed's: (the bodies of
+        text[first : first + count], cut in front of `stop`, back to back as bytes, their offsets, their lengths), as encode_packed
+        of those pieces gives it, through one slice_packed_device call."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert out_index.size == lengths.size + 1
+        if not rows.size:
+            return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+
+        def per_row(v):
+            if isinstance(v, (int, np.integer)):
+                return int(v)
+            v = np.ascontiguousarray(v, dtype=np.uint32)
+            assert v.size == rows.size
+            return torch.from_numpy(v.view(np.int32)).to(d_blob.device)
+
+        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
+        good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none; a slice is no longer than its record's body)
+        room = int((out_index[good + 1] - out_index[good]).sum())
+        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=d_blob.device)
+        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        res = self.slice_packed_device(codebook, d_blob, d_body_index, d_text_index, d_rows, per_row(first), per_row(count), d_out, d_new_index, d_new_text, stop=stop)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"slice_packed: row {res.first_failed}")
         new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
         return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
 

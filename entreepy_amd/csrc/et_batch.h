@@ -263,4 +263,41 @@ enum TakeWord { TAKE_TEXT_BYTES = 3 };       // the report's word beside PACKED_
 void launch_take(hipStream_t stream, const PackedStore &store, const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index,
                  uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, const PackedReport &report);
 
+// The slice (et_slice_packed_device): symbols [first, first + count) of rows[]' stored texts, cut in front of a stop byte, as a NEW
+// packed store -- under one complete prefix-free table a substring is the run of bits between two codeword boundaries, so the body the
+// encoder would write for it is that run shifted to bit 7 of a byte, its last byte padded with zeros.  The search's walk finds the two
+// boundaries, the take's scan lays the rows out and the take's copy, reading bits for bytes, writes them.
+//   k_slice_plan  one row per lane, the sorted codes and the first-level table in LDS: judged as k_take_plan judges, its status byte;
+//                 a body of which the slice's end can reach up to SLICE_LANE_BYTES (clip_body: 4 bytes per symbol in front of the end)
+//                 is walked by its lane alone, from global memory, the walk ending where the slice does; a longer one goes onto a list
+//                 and is an empty row for now; a TakeRow per row: {bytes of the new body, symbols, where its first BIT lies}
+//   k_slice_long  one workgroup per listed row (k_search_long's shape): the blocks in front of the slice's end settled by a counting
+//                 walk, the lanes whose codewords meet [first, end) walk again; begin, end and the lowest stop reduced over the
+//                 workgroup; thread 0 stores the row's TakeRow
+//   k_take_scan   the take's, unchanged: its report is the call's
+//   k_take_copy   (unless d_out is null: sizes only) the take's tiles, rows and stores; a row's piece is a funnel shift of the source
+//                 bytes that hold its bits -- none behind the slice's last bit is loaded -- and a row's last byte is masked to its bits
+// A slice's TakeRow::src is the ADDRESS of its first bit (the byte's address * 8 + the bit, from the top) with the pad bits of its last
+// byte (0 .. 7) above it: bits = body_bytes * 8 - pad.
+// SLICE_LANE_BYTES is the search's threshold, kept: the lane's walk is search_lane's less the comparison and the workgroup's is
+// search_stream's with a counting visitor, so the search's sweep is about these two loops as well; no sweep of
+// the slice's own has been run.
+#ifndef ET_SLICE_LANE_BYTES  // (a build for the sweep sets it, as ET_SEARCH_LANE_BYTES)
+#define ET_SLICE_LANE_BYTES ET_SEARCH_LANE_BYTES
+#endif
+constexpr uint32_t SLICE_LANE_BYTES = ET_SLICE_LANE_BYTES;
+constexpr uint32_t SLICE_NO_STOP = 0x100;   // SliceJob::stop when nothing cuts: no symbol
+constexpr uint32_t SLICE_PAD_SHIFT = 61;    // TakeRow::src of a slice: the pad bits' place (an address of bits stays below 2^61)
+enum SliceWord { SLICE_N_LONG = 4 };        // the counters' word beside the rows' two: rows on the list
+struct SliceJob {
+    const uint32_t *rows;              // null: row k is record k
+    const uint32_t *d_first, *d_count; // null: the scalar beside it
+    uint32_t n_rows, first, count;
+    uint32_t stop;                     // the byte in front of which a slice ends, or SLICE_NO_STOP
+};
+// codes: the sorted codes on the device (launch_shared_decode's); plan: n_rows TakeRow of workspace (16-byte aligned); long_list: a
+// u32 per row.  The report leaves with the scan, in front of the copy.
+void launch_slice(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const SliceJob &job, void *d_out, uint64_t cap,
+                  uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
+
 }  // namespace et

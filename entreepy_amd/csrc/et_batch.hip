@@ -35,6 +35,10 @@
 //   take     k_take_plan     one lane per row of a selection: its record judged, {body bytes, length, where the body begins} into the workspace
 //            k_take_scan     ONE workgroup: the two sizes -> out_body_index and out_text_index, the report
 //            k_take_copy     the selected bodies back to back as they are: one lane per aligned 16-byte word of the OUTPUT
+//   slice    k_slice_plan    one lane per row: judged; a short body walked to the slice's two boundaries, cut in front of a stop byte; a long one listed
+//            k_slice_long    one workgroup per listed row: k_search_long's settled blocks, the boundaries reduced over the workgroup
+//            k_take_scan     as in the take
+//            k_take_copy     as in the take, a row's source a run of BITS: each byte a funnel shift of two, the last one masked to its bits
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -1731,6 +1735,22 @@ __device__ __forceinline__ void put_bytes(uint64_t &v0, uint64_t &v1, uint64_t x
     }
 }
 
+// The slice's piece: `c` bytes (1 .. 8) of a new body whose bits are the source's from bit address bit0 on (a byte's address * 8 + the
+// bit, from the top), of which `left` >= 1 belong to the slice.  Each byte is a funnel shift of two source bytes; only the source
+// bytes that hold one of the min(left, 8 c) bits are loaded (span_word: at most 9, all of them the record's), and where the slice
+// ends inside the piece's last byte the bits behind it are zero: the encoder's pad, whatever the source holds there.
+__device__ __forceinline__ uint64_t bit_span(uint64_t bit0, uint32_t c, uint32_t left) {
+    constexpr uint64_t ONES = 0x0101010101010101ull;
+    const uint32_t sh = static_cast<uint32_t>(bit0 & 7), v = left < 8 * c ? left : 8 * c, n = (sh + v + 7) >> 3;
+    const uintptr_t a = static_cast<uintptr_t>(bit0 >> 3);
+    const uint64_t lo = span_word(a, n < 8 ? n : 8u), hi = n > 8 ? span_word(a + 8, 1) : 0ull;
+    const uint64_t next = lo >> 8 | hi << 56;  // byte j: source byte j + 1
+    uint64_t x = ((lo & (ONES * (0xffu >> sh))) << sh) | ((next >> (8 - sh)) & (ONES * (0xffu >> (8 - sh))));
+    if (c < 8) x &= (1ull << (8 * c)) - 1ull;
+    if (v < 8 * c) x &= ~(((1ull << (8 * c - v)) - 1ull) << (8 * (c - 1)));  // (the row ends in this piece: 8 c - v pad bits, 1 .. 7)
+    return x;
+}
+
 // k_take_copy: the output's bytes [0, total) lie at d_out, any alignment; tile t is what of them lies in the t-th TAKE_TILE_BYTES
 // block counted from d_out's address rounded down, so every word below is an aligned 16 bytes of MEMORY.  A workgroup takes a run of
 // consecutive tiles.  Per tile it finds, together, the rows that own the tile's first and last byte (wg_upper_bound: a run of empty rows
@@ -1742,6 +1762,9 @@ __device__ __forceinline__ void put_bytes(uint64_t &v0, uint64_t &v1, uint64_t x
 // 8-byte source words.  A full word leaves as ONE 16-byte store; the first and the last word of the whole output, where d_out or its
 // end is not aligned, leave as byte stores of their own bytes.  Nothing is written when total > cap, no workgroup waits for another,
 // and a row that owns a byte was judged by k_take_plan, so its TakeRow is believed.  LDS 8 KiB + 16 bytes.
+// BITS (the slice call): a row's source is a run of BITS -- TakeRow::src as k_slice_plan leaves it -- and a piece is bit_span's; the
+// tiles, the rows and the stores are the same, and d_bodies is not looked at.
+template <bool BITS>
 __global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_bodies, const TakeRow *__restrict__ plan, const uint64_t *__restrict__ out_index,
                                                   uint32_t n_rows, uint8_t *__restrict__ d_out, uint64_t cap) {
     __shared__ uint64_t s_idx[TAKE_STAGE_ROWS];
@@ -1786,10 +1809,17 @@ __global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_
             for (int trip = 0; trip < 16; ++trip) {  // row k owns byte pos: out_index[k] <= pos < out_index[k + 1]
                 const uint64_t s = idx(k), e = idx(k + 1), piece_end = e < w1 ? e : w1;
                 const uint32_t c = static_cast<uint32_t>(piece_end - pos);  // 1 .. 16
-                const uintptr_t a = bodies + plan[k].src + (pos - s);
                 const uint32_t d = static_cast<uint32_t>(static_cast<int64_t>(pos) - rel);
-                put_bytes(v0, v1, span_word(a, c < 8 ? c : 8u), d);
-                if (c > 8) put_bytes(v0, v1, span_word(a + 8, c - 8), d + 8);
+                if constexpr (BITS) {
+                    const uint64_t src = plan[k].src, bit0 = (src & ((1ull << SLICE_PAD_SHIFT) - 1ull)) + 8 * (pos - s);
+                    const uint32_t left = static_cast<uint32_t>(e - pos) * 8 - static_cast<uint32_t>(src >> SLICE_PAD_SHIFT);  // the slice's bits from bit0 on
+                    put_bytes(v0, v1, bit_span(bit0, c < 8 ? c : 8u, left), d);
+                    if (c > 8) put_bytes(v0, v1, bit_span(bit0 + 64, c - 8, left - 64), d + 8);  // (9 bytes are left at least: left >= 65)
+                } else {
+                    const uintptr_t a = bodies + plan[k].src + (pos - s);
+                    put_bytes(v0, v1, span_word(a, c < 8 ? c : 8u), d);
+                    if (c > 8) put_bytes(v0, v1, span_word(a + 8, c - 8), d + 8);
+                }
                 pos = piece_end;
                 if (pos >= w1) break;
                 ++k;  // (a row behind owns byte pos < o1: k < row_end)
@@ -1810,6 +1840,195 @@ __global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_
             }
         }
         __syncthreads();  // (s_idx: between two tiles)
+    }
+}
+
+// --------------------------------------------------------------------------------
+// The slice call: symbols [first, first + count) of rows[]' stored texts, cut in front of the first `stop` byte among them, as a new
+// packed store.  Under one complete prefix-free table symbols [i, j) of a record are the bits from the boundary of codeword i to the
+// boundary of codeword j, so a slice is found by the search's walk over the boundaries -- nothing compared but the symbol the step
+// yields anyway, nothing written -- and written by the take's scan and copy, the copy reading a run of bits where the take reads a run
+// of bytes.  Four launches in stream order (et_batch.h), the host waiting for the scan alone.
+// Every loop is bounded as the search's are: a lane's walk by the slice's end (a trip per symbol, at most the record's length), the
+// workgroup's by the blocks of what the slice's end can reach of the body, its fixed point by 256 trips and a lane's walk inside it by
+// its 256 bits.  No workgroup waits for another: k_slice_long stores the TakeRow of its own row and nothing else.
+// --------------------------------------------------------------------------------
+// What row k asks of a stored text of at most `len` symbols: [first, end), end <= len; nothing when end <= first.  (first + count does
+// not wrap: 64 bits; ET_SLICE_TO_END lies beyond every length.)
+struct SliceAsk {
+    uint32_t first, end;
+};
+
+__device__ __forceinline__ SliceAsk slice_ask(const SliceJob &job, uint32_t k, uint32_t len) {
+    const uint32_t first = job.d_first ? job.d_first[k] : job.first, count = job.d_count ? job.d_count[k] : job.count;
+    const uint64_t end = static_cast<uint64_t>(first) + count;
+    return SliceAsk{first, end < len ? static_cast<uint32_t>(end) : len};
+}
+
+// What a walk found: the bit (from the body's aligned base) at which the slice's first codeword begins, the bit behind its last, its symbols.
+struct Sliced {
+    uint32_t begin, end, n;
+};
+
+// The TakeRow of a slice as it lies in memory: the new body's bytes, its symbols, the address of its first bit with the pad above it.
+__device__ __forceinline__ uint4 slice_row(const BodyBits &g, const Sliced &sl) {
+    if (!sl.n) return make_uint4(0u, 0u, 0u, 0u);  // (a codeword has a bit at least: symbols mean bits)
+    const uint32_t bits = sl.end - sl.begin, bytes = (bits + 7) >> 3;
+    const uint64_t src = (static_cast<uint64_t>(reinterpret_cast<uintptr_t>(g.words)) * 8 + sl.begin) | static_cast<uint64_t>(bytes * 8 - bits) << SLICE_PAD_SHIFT;
+    return make_uint4(bytes, sl.n, static_cast<uint32_t>(src), static_cast<uint32_t>(src >> 32));
+}
+
+// One lane, one body of a few words, from global memory (search_lane's shape): a trip per symbol in front of the slice's end.  The
+// stored text ends where the bits run out inside a codeword; the slice ends there, at ask.end, or in front of the first `stop` at or
+// behind ask.first.  64 bits of body are kept in registers and move on a word at a time.
+__device__ __forceinline__ Sliced slice_lane(const CodeTables &t, uint32_t n_codes, const BodyBits &g, const SliceAsk &ask, uint32_t stop) {
+    uint32_t pos = g.first_bit, k = 0, begin = 0, idx = 0;
+    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
+    for (; idx < ask.end; ++idx) {
+        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
+            k = pos >> 5;
+            two = (two << 32) | body_word_be(g, k + 1);
+        }
+        const uint32_t meta = code_at(t, n_codes, static_cast<uint32_t>((two << (pos & 31)) >> 32));
+        if (pos + (meta >> 8) > g.end_bit) break;  // the bits ran out inside this codeword: the stored text ends here
+        if (idx == ask.first) begin = pos;
+        if (idx >= ask.first && (meta & 0xffu) == stop) break;
+        pos += meta >> 8;
+    }
+    return Sliced{begin, pos, idx > ask.first ? idx - ask.first : 0u};
+}
+
+// k_slice_plan: k_take_plan's rows, judgement, status bytes and tally, with the sorted codes and the first-level table in LDS once per
+// workgroup.  A row that asks for nothing, or of a record without bytes or symbols, is the empty record and is not read; a body of
+// which the slice's end can reach up to SLICE_LANE_BYTES is walked by its lane (slice_lane); a longer one goes onto long_list -- one
+// atomic per wavefront that has any -- and is the empty record here: k_slice_long stores its TakeRow.  LDS 6 KiB + 8 words.
+__global__ __launch_bounds__(BB) void k_slice_plan(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, SliceJob job, TakeRow *__restrict__ plan,
+                                                   uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ CodeTables t;
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    load_tables(t, codes, n_codes);
+    __syncthreads();
+    PackedTally tally;
+    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
+        bool is_long = false;
+        if (k < job.n_rows) {
+            const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
+            const uint32_t status = !rec.status && rec.nb > TAKE_BODY_MAX ? PACKED_UNSUPPORTED : rec.status;
+            uint4 row = make_uint4(0u, 0u, 0u, 0u);
+            if (!status && rec.nb && rec.len) {
+                const SliceAsk ask = slice_ask(job, k, static_cast<uint32_t>(rec.len));
+                if (ask.end > ask.first) {
+                    const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, ask.end)));
+                    if (g.end_bit - g.first_bit <= SLICE_LANE_BYTES * 8) row = slice_row(g, slice_lane(t, n_codes, g, ask, job.stop));
+                    else is_long = true;
+                }
+            }
+            reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
+            if (d_status) d_status[k] = static_cast<uint8_t>(status);
+            tally.note(k, status);
+        }
+        const unsigned long long longs = __ballot(is_long);
+        if (longs) {  // (the same for the whole wavefront)
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
+            at = __shfl(at, 0, 64);
+            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
+        }
+    }
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
+// One row's body by the whole workgroup under the tables in `s`: search_stream's blocks with a counting walk to settle them.  Once the
+// scan has numbered a block's codewords, the lanes whose codewords meet [ask.first, ask.end) walk again and note, as symbol << 32 |
+// bit: where symbol ask.first begins, where the first `stop` among their symbols begins (the walk ends there), and where the last of
+// their symbols in the range ends.  The three are reduced over the workgroup through s_red (12 words, free again at the next block's
+// first barrier): the slice begins at the one begin, and ends at the lowest stop or else behind the highest symbol of the range that the
+// stored text holds.  The blocks end with the first that has a stop, or once ask.end codewords lie behind: none behind the slice's end
+// is visited.
+__device__ __forceinline__ Sliced slice_stream(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, const SliceAsk &ask, uint32_t stop, unsigned long long *s_red) {
+    constexpr unsigned long long NONE = ~0ull;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
+    uint32_t start = g.first_bit, done = 0;  // the block's first codeword; codewords so far
+    unsigned long long begin = NONE, end = 0;
+    for (uint32_t blk = 0; blk < n_blocks && done < ask.end; ++blk) {
+        const uint32_t at = blk * DEC_WORDS * 32 + tid * 256;
+        JustCount counting;
+        const Settled b = settle_block(s, n_codes, g, blk, start, counting);
+        const uint32_t lo = done + b.first;  // the number of the lane's first codeword
+        unsigned long long my_begin = NONE, my_stop = NONE, my_last = 0;
+        if (b.count && lo < ask.end && lo + b.count > ask.first) {
+            uint32_t again;
+            (void)walk(s, n_codes, b.used, b.room, &again, [&](uint32_t cnt, uint32_t pos, uint32_t, uint32_t meta) {
+                const uint32_t sym = lo + cnt;
+                if (sym >= ask.end) return false;
+                if (sym < ask.first) return true;
+                const unsigned long long here = static_cast<unsigned long long>(sym) << 32 | (at + pos);
+                if (sym == ask.first) my_begin = here;
+                if ((meta & 0xffu) == stop) {
+                    my_stop = here;
+                    return false;
+                }
+                my_last = static_cast<unsigned long long>(sym + 1) << 32 | (at + pos + (meta >> 8));
+                return true;
+            });
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const unsigned long long ob = __shfl_xor(my_begin, d, 64), os = __shfl_xor(my_stop, d, 64), ol = __shfl_xor(my_last, d, 64);
+            if (ob < my_begin) my_begin = ob;
+            if (os < my_stop) my_stop = os;
+            if (ol > my_last) my_last = ol;
+        }
+        if ((tid & 63) == 0) {
+            s_red[tid >> 6] = my_begin;
+            s_red[4 + (tid >> 6)] = my_stop;
+            s_red[8 + (tid >> 6)] = my_last;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < BB / 64; ++w) {
+            if (s_red[w] < my_begin) my_begin = s_red[w];
+            if (s_red[4 + w] < my_stop) my_stop = s_red[4 + w];
+            if (s_red[8 + w] > my_last) my_last = s_red[8 + w];
+        }
+        if (my_begin != NONE) begin = my_begin;  // (the same for every lane, like all below)
+        if (my_last > end) end = my_last;
+        if (my_stop != NONE) {  // the lowest stop: nothing at or behind it belongs to the slice
+            end = my_stop;
+            break;
+        }
+        start = b.start;
+        done += b.total;
+    }
+    if (begin == NONE) return Sliced{0u, 0u, 0u};  // the stored text ends in front of ask.first
+    return Sliced{static_cast<uint32_t>(begin), static_cast<uint32_t>(end), static_cast<uint32_t>(end >> 32) - ask.first};
+}
+
+// k_slice_long: k_search_long's shape over long_list -- the sorted codes and the first-level table once per workgroup, the listed rows
+// strided.  A workgroup beyond the list returns before it sets anything up.  Thread 0 stores the row's TakeRow (k_slice_plan left the empty record there; the scan runs behind this kernel).
+// LDS as k_batch_decode, and the reduction's 12 words.
+__global__ __launch_bounds__(BB) void k_slice_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, SliceJob job, TakeRow *__restrict__ plan,
+                                                   const uint32_t *__restrict__ long_list, const unsigned long long *__restrict__ stats) {
+    __shared__ BatchDecLds s;
+    __shared__ unsigned long long s_red[3 * (BB / 64)];
+    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
+    if (blockIdx.x >= n_long) return;
+    load_tables(s.t, codes, n_codes);
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
+        const uint32_t k = long_list[i];
+        if (k >= job.n_rows) continue;  // (k_slice_plan lists rows; the same for every lane, like all below)
+        const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
+        if (rec.status || rec.nb == 0 || rec.nb > TAKE_BODY_MAX || rec.len == 0) continue;  // (k_slice_plan lists no such row)
+        const SliceAsk ask = slice_ask(job, k, static_cast<uint32_t>(rec.len));
+        if (ask.end <= ask.first) continue;
+        const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, ask.end)));
+        const Sliced sl = slice_stream(s, n_codes, g, ask, job.stop, s_red);
+        if (threadIdx.x == 0) reinterpret_cast<uint4 *>(plan)[k] = slice_row(g, sl);
     }
 }
 
@@ -1844,7 +2063,20 @@ void launch_take(hipStream_t stream, const PackedStore &store, const uint32_t *r
                        static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
     if (!d_out) return;
     // (what fits into cap spans no more than cap / TAKE_TILE_BYTES + 2 tiles, at any alignment)
-    hipLaunchKernelGGL(k_take_copy, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(store.bodies),
+    hipLaunchKernelGGL(k_take_copy<false>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(store.bodies),
+                       static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+}
+
+void launch_slice(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const SliceJob &job, void *d_out, uint64_t cap,
+                  uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &r) {
+    const uint32_t n_rows = job.n_rows;
+    hipLaunchKernelGGL(k_slice_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
+    hipLaunchKernelGGL(k_slice_long, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list),
+                       static_cast<const unsigned long long *>(r.stats));
+    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
+                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
+    if (!d_out) return;
+    hipLaunchKernelGGL(k_take_copy<true>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(nullptr),
                        static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
 }
 

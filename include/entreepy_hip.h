@@ -602,6 +602,61 @@ int et_take_packed_device(et_ctx *ctx,
                           void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
                           uint8_t *d_status, et_take_result *res);
 
+/* SLICE: a PART of each selected record as a NEW packed store, on the device, nothing decoded and nothing encoded again --
+ * SUBSTR(key, a, n), LEFT(key, n), "the value behind user= up to the next ;" -- and what consumes the search call's d_pos: search ->
+ * slice -> join -> gather runs on one ctx with nothing in between.  Under one complete prefix-free table symbols [i, j) of a record
+ * are the bits from the boundary of codeword i to the boundary of codeword j, so the body the encoder would write for the substring
+ * is that run of bits shifted to bit 7 of a byte, the last byte padded with zeros: the search's walk finds the two boundaries, a
+ * bit-shifting version of the take's copy writes the result.
+ *   The store, d_rows (any order, repeats allowed), d_status (one et_status byte per ROW; may be NULL) and the judgement of a row are
+ *     the take call's: ET_ERR_ARG when d_rows[k] >= n_records and unless body_index[r] <= body_index[r+1] <= body_bytes and
+ *     text_index[r] <= text_index[r+1]; ET_ERR_UNSUPPORTED for a length above the small-stream limit and for a body above
+ *     4 * et_batch_small_max() bytes.  A failed row becomes an EMPTY record of the new store (no bytes, length 0), fails alone, and no
+ *     kernel reads where a bad pair points.  d_rows == NULL: row k is record k, and n_rows must equal n_records.
+ *   d_first[k], d_count[k] (32 bits each, 4-byte aligned, on the device; either may be NULL: then the scalar `first` or `count` holds
+ *     for every row; with the pointer the scalar is ignored): where row k's slice begins and how many symbols it has at most.
+ *     ET_SLICE_TO_END as a count: to the end.  d_first may be the search call's d_pos, or that plus the needle's length.
+ *   text_b is the stored text of record r = d_rows[k] as every packed call defines it: the first min(length_r, codewords that end
+ *     inside its body) symbols.  Row k of the result is s = text_b[first : first + count], clamped as Python clamps a slice
+ *     (first >= len(text_b): the empty record; first + count does not wrap).  0 <= stop <= 255: s is cut in front of the first
+ *     occurrence of byte `stop` in it (s[: s.find(stop)] when there is one); a stop byte without a code occurs in no record and cuts
+ *     nothing; ET_SLICE_NO_STOP: nothing cuts.
+ *   d_out[out_body_index[k], out_body_index[k+1]) holds exactly the bytes et_encode_packed_device writes for s under cb --
+ *     ceil(bits / 8) bytes, MSB-first from bit 7, the pad bits zero, also from a hand-made source body whose own pad bits are set: the
+ *     copied bits are codewords, the pad is masked and not copied -- and out_text_index[k+1] - out_text_index[k] == len(s).  Both
+ *     output arrays have n_rows + 1 entries (8-byte aligned, on the device) and begin with 0; the bodies lie back to back.  A body of
+ *     no bytes under a length above zero (a record kept raw elsewhere) has the empty stored text and slices to the empty record with
+ *     length 0 -- UNLIKE the take call, which keeps such a record's length: a slice's length is the symbols its body holds.
+ *   Nothing outside [d_out, d_out + out_body_index[n_rows]) is written, at any alignment of d_out and of d_bodies.
+ *   d_out == NULL: sizes only -- both output arrays, d_status and *res are the writing call's; cap is ignored.
+ *   out_body_index[n_rows] > cap: the call returns ET_ERR_CAP, not a byte of d_out is written; both output arrays and d_status are
+ *     complete and res->out_bytes is the room needed.  res->text_bytes is the sum of the slices' lengths.
+ *   et_slice_lane_bytes(): a body of which the slice's end can reach up to this many bytes (4 bytes per symbol in front of the end, and
+ *     8: a LEFT of a few symbols reaches little of a long body) is walked by one lane, a longer one by a workgroup -- for tests that
+ *     want rows on both sides; the answer does not depend on it.
+ * Out of scope: the k-th delimiter-separated field in one call; negative or from-the-end indices (the caller has text_index on the
+ * device for that); slicing in place -- [d_out, d_out + cap) may not overlap [d_bodies, d_bodies + body_bytes) --; several stores per
+ * call; records above the limits named above.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_bodies, d_body_index, d_text_index, d_out_body_index or
+ * d_out_text_index; an offset array that is not 8-byte aligned; d_rows, d_first or d_count not 4-byte aligned; n_records or n_rows
+ * above 0x7fffffff; d_rows == NULL with n_rows != n_records; d_out overlapping d_bodies; a stop outside [-1, 255] -- all checked
+ * before anything touches a device, *res untouched), ET_ERR_UNSUPPORTED (the table is not complete: nothing is enqueued), ET_ERR_CAP,
+ * ET_ERR_HIP, ET_ERR_NOMEM.  n_rows == 0: ET_OK, nothing enqueued, *res zeroed.  One upload (the sorted codes and zeroed counters,
+ * 2.1 KiB), four launches and one hand-over per call; stream-ordered like the other packed calls -- *res is final on return, the
+ * device arrays once the ctx's stream has drained -- and it may follow or precede any of them on one ctx with nothing in between. */
+#define ET_SLICE_TO_END 0xffffffffu
+#define ET_SLICE_NO_STOP (-1)
+size_t et_slice_lane_bytes(void);           /* a reach (min(body bytes, 4 * slice end + 8)) up to this is walked by one lane */
+int et_slice_packed_device(et_ctx *ctx, const et_codebook *cb,
+                           const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                           const uint64_t *d_text_index, size_t n_records,
+                           const uint32_t *d_rows, size_t n_rows,
+                           const uint32_t *d_first, uint32_t first,
+                           const uint32_t *d_count, uint32_t count,
+                           int stop,
+                           void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
+                           uint8_t *d_status, et_take_result *res);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

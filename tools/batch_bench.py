@@ -58,6 +58,9 @@ process of its own so that every leg loads exactly one build of the library:
   search_sweep    (only when named) stores of 16 MiB of text in records of 32 .. 4096 bytes, CONTAINS: the times from which
                   SEARCH_LANE_BYTES is chosen -- run it on builds with -DET_SEARCH_LANE_BYTES=0 and =8192 (ET_LIB_PATH names the library)
                   for the two paths at every size.
+  slice           et_slice_packed_device (LEFT 12, 64 symbols from the middle, behind a needle up to a stop byte) against what it replaces:
+                  a decode (or gather) of the rows' records and et_encode_packed_device of the cut text; the search's walk and the take's
+                  copy on the same rows as floors
 --legs picks the legs (default: all but search_sweep).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
@@ -72,6 +75,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs take --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/take_bench.json
     python tools/batch_bench.py --legs search --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/search_bench.json
     python tools/batch_bench.py --legs order --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/order_bench.json
+    python tools/batch_bench.py --legs slice --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/slice_bench.json
 """
 import argparse
 import ctypes
@@ -790,11 +794,136 @@ def _take_leg(leg, lib_path):
     print(json.dumps(results))
 
 
+SLICE_CASES = ("left12", "middle64", "after_needle")
+
+
+def _slice_leg(leg, lib_path, shapes):
+    """slice / slice_baseline: per shape a packed store with a 12-byte needle in 10 % of its records (_search_store; encoded untimed), then
+    per case -- LEFT 12 of every record; 64 symbols from the middle of every record; behind the needle up to the next space, of the records
+    that hold it (rows and positions from an untimed search) -- the timed call: et_slice_packed_device, its bytes and offsets checked
+    against et_encode_packed_device of Python's slices first, beside it the sizes-only call and the two floors on the same store and rows
+    (et_search_packed_device CONTAINS: the walk with nothing written; et_take_packed_device: the copy alone) -- or what it replaces:
+    et_decode_packed_device of the store (et_decode_packed_gather_device where the rows are a selection), then et_encode_packed_device
+    of the sliced text; the cutting in between is not timed."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    base = leg == "slice_baseline"
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device", "et_decode_packed_gather_device"]
+                      + ([] if base else ["et_slice_packed_device", "et_slice_lane_bytes", "et_search_packed_device", "et_take_packed_device"]))
+    results = {} if base else {"lane_bytes": int(L.et_slice_lane_bytes())}
+    for count, size in SHAPES + [KEY_SHAPE]:
+        shape_name = f"{count}x{size}" if isinstance(size, int) else f"{count}x{size[0]}-{size[1]}"
+        if shapes and shape_name not in shapes:
+            continue
+        host, index, needle, (found, pos, _) = _search_store(count, size, 0.1)
+        blob, lengths = host.tobytes(), np.diff(index).astype(np.int64)
+        text = torch.from_numpy(host).to(dev)
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, index, _codebook(L, [host]))
+        res, shape = N.PackedResult(), {"records": count, "body_bytes": body_bytes}
+        everyone = np.arange(count, dtype=np.uint32)
+        cases = {"left12": (None, np.zeros(count, np.int64), np.full(count, 12), None), "middle64": (None, lengths // 2, np.full(count, 64), None),
+                 "after_needle": (np.array(found, dtype=np.uint32), np.array(pos, dtype=np.int64) + len(needle), np.full(len(found), 0xFFFFFFFF), ord(" "))}
+        for name in SLICE_CASES:
+            rows, first, cnt, stop = cases[name]
+            at = everyone if rows is None else rows
+            pieces = []
+            for r, f, c in zip(at.tolist(), first.tolist(), cnt.tolist()):
+                piece = blob[int(index[r]) + f : min(int(index[r]) + f + c, int(index[r + 1]))] if f < lengths[r] else b""
+                pieces.append(piece if stop is None or bytes([stop]) not in piece else piece[: piece.index(bytes([stop]))])
+            cut_index = np.concatenate(([0], np.cumsum([len(x) for x in pieces]))).astype(np.uint64)
+            cut_total = int(cut_index[-1])
+            cut_text = torch.from_numpy(np.frombuffer(b"".join(pieces) + b"\0", np.uint8).copy()).to(dev)
+            _, want, need, want_index, cut_text_index = _packed_store(L, h, cut_text, cut_index, cb)  # what the slices must be: the encoder's bodies of Python's slices
+            n_rows = at.size
+            d_rows = torch.from_numpy(at.view(np.int32).copy()).to(dev)
+            out = torch.zeros(need + 64, dtype=torch.uint8, device=dev)
+            out_body_index, out_text_index = (torch.zeros(n_rows + 1, dtype=torch.int64, device=dev) for _ in range(2))
+            entry = {"rows": int(n_rows), "bytes": need, "text_bytes": cut_total}
+            if base:
+                room = int(index[-1]) if rows is None else int(lengths[at.astype(np.int64)].sum())
+                dec = torch.zeros(room + 64, dtype=torch.uint8, device=dev)
+
+                def baseline():
+                    if rows is None:
+                        assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, dec.data_ptr(), room, None,
+                                                         None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    else:
+                        assert L.et_decode_packed_gather_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, d_rows.data_ptr(),
+                                                                n_rows, dec.data_ptr(), room, out_text_index.data_ptr(), None, None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.out_bytes == room and res.n_failed == 0 and res.n_short == 0
+                    assert L.et_encode_packed_device(h, ctypes.byref(cb), cut_text.data_ptr(), cut_total, cut_text_index.data_ptr(), n_rows, out.data_ptr(), need, out_body_index.data_ptr(),
+                                                     None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.out_bytes == need and res.n_failed == 0
+
+                baseline()
+                torch.cuda.synchronize()
+                assert torch.equal(out[:need], want[:need]) and torch.equal(out_body_index, want_index)
+                entry.update(_timed(baseline))
+                del dec
+            else:
+                tres, mres = N.TakeResult(), N.MatchResult()
+                d_first, d_count = (torch.from_numpy(v.astype(np.uint32).view(np.int32).copy()).to(dev) for v in (first, cnt))
+                scalars = name == "left12"  # (the scalars where every row has the same; device arrays else)
+
+                def call(d_out=out):
+                    assert L.et_slice_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count,
+                                                    None if rows is None else d_rows.data_ptr(), n_rows, None if scalars else d_first.data_ptr(), 0, None if scalars else d_count.data_ptr(),
+                                                    12, -1 if stop is None else stop, None if d_out is None else d_out.data_ptr(), need, out_body_index.data_ptr(),
+                                                    out_text_index.data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+                    assert tres.out_bytes == need and tres.text_bytes == cut_total and tres.n_failed == 0
+
+                call()
+                torch.cuda.synchronize()
+                assert torch.equal(out[:need], want[:need]), "the slices differ from the encoder's bodies of Python's slices"
+                assert torch.equal(out_body_index, want_index) and torch.equal(out_text_index, cut_text_index)
+                entry.update(_timed(call))
+                entry["sizes_only"] = _timed(lambda: call(None))
+                d_hits, d_pos = (torch.zeros(count, dtype=torch.int32, device=dev) for _ in range(2))
+
+                def search():
+                    assert L.et_search_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, needle, len(needle),
+                                                     N.ET_SEARCH_CONTAINS, d_hits.data_ptr(), count, d_pos.data_ptr(), None, ctypes.byref(mres)) == 0, L.et_last_error(h)
+
+                taken = torch.zeros(body_bytes + 64, dtype=torch.uint8, device=dev)
+
+                def take():
+                    assert L.et_take_packed_device(h, bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, d_rows.data_ptr(), n_rows, taken.data_ptr(),
+                                                   body_bytes, out_body_index.data_ptr(), out_text_index.data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+
+                entry["search_floor"] = _timed(search)
+                entry["take_floor"] = _timed(take)
+                entry["vs_search_floor"] = round(entry["ms"] / entry["search_floor"]["ms"], 2)
+                entry["vs_take_floor"] = round(entry["ms"] / entry["take_floor"]["ms"], 2)
+                if name == "after_needle":  # the pair as it runs: the search's rows and positions straight into the slice, first = pos + 12 by a torch add
+
+                    def pair():
+                        search()
+                        d_after = d_pos[: mres.n_match] + len(needle)
+                        assert L.et_slice_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, d_hits.data_ptr(),
+                                                        mres.n_match, d_after.data_ptr(), 0, None, 0xFFFFFFFF, stop, out.data_ptr(), need, out_body_index.data_ptr(),
+                                                        out_text_index.data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+
+                    pair()
+                    torch.cuda.synchronize()
+                    assert torch.equal(out[:need], want[:need]) and mres.n_match == n_rows
+                    entry["search_then_slice"] = _timed(pair)
+                del taken
+            shape[name] = entry
+            del out, want, cut_text
+        results[shape_name] = shape
+        del text, bodies
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take,search,order")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take,search,order,slice")
     ap.add_argument("--shapes", default="")  # (the match legs: a comma list of shape names, e.g. 262144x16-48; default: all)
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
@@ -810,6 +939,8 @@ def main():
         return _join_leg(a.leg, a.lib)
     if a.leg and a.leg.startswith("take"):
         return _take_leg(a.leg, a.lib)
+    if a.leg and a.leg.startswith("slice"):
+        return _slice_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -829,6 +960,8 @@ def main():
         legs += [("search_baseline", "search_baseline", a.batch_lib or here), ("search", "search", here)]
     if "order" in a.legs.split(","):
         legs += [("order_baseline", "order_baseline", a.batch_lib or here), ("order", "order", here)]
+    if "slice" in a.legs.split(","):
+        legs += [("slice_baseline", "slice_baseline", a.batch_lib or here), ("slice", "slice", here)]
     if "search_sweep" in a.legs.split(","):
         legs += [("search_sweep", "search_sweep", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
@@ -865,6 +998,17 @@ def main():
                                    for k, shape in out["join"].items()}
     if "take" in out:  # > 1: the take call is the faster one; vs_copy_floor (in the take leg): its time over a plain copy of as many bytes
         out["take_vs_baseline"] = {k: {n: round(out["take_baseline"][k][n]["ms"] / e["ms"], 2) for n, e in v.items() if isinstance(e, dict)} for k, v in out["take"].items()}
+    if "slice" in out:  # per shape and case: the pair's time over the slice's (> 1: the slice is faster), and whether the medians lie further apart than the two spreads together
+        out["slice_vs_baseline"] = {}
+        for k, v in out["slice"].items():
+            if not isinstance(v, dict):
+                continue
+            out["slice_vs_baseline"][k] = {}
+            for name in SLICE_CASES:
+                old, new = out["slice_baseline"][k][name], v[name]
+                out["slice_vs_baseline"][k][name] = {"baseline_over_slice": round(old["ms"] / new["ms"], 2),
+                                                     "beyond_both_spreads": old["ms"] - new["ms"] > (old["max_ms"] - old["min_ms"]) + (new["max_ms"] - new["min_ms"])}
+        out["slice_condition_met"] = all(e["beyond_both_spreads"] for v in out["slice_vs_baseline"].values() for e in v.values())
     line = json.dumps(out)
     print(line)
     if a.out:
