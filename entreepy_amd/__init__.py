@@ -11,6 +11,8 @@ from .codec import (  # noqa: F401
     EmptyInputError,
     EncodeFlags,
     EntreepyError,
+    FIELD_ABSENT,
+    FIELD_TO_END,
     JoinResult,
     MATCH_EQUAL,
     MATCH_LESS,

@@ -91,6 +91,7 @@ MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT =N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_
 MATCH_LESS, MATCH_LESS_EQUAL = N.ET_MATCH_LESS, N.ET_MATCH_LESS_EQUAL  # ... its order modes: text < needle, text <= needle (with MATCH_NOT: >=, >)
 SEARCH_CONTAINS, SEARCH_SUFFIX = N.ET_SEARCH_CONTAINS, N.ET_SEARCH_SUFFIX  # search_packed_device's mode; MATCH_NOT may be or-ed in
 SLICE_TO_END, SLICE_NO_STOP = N.ET_SLICE_TO_END, N.ET_SLICE_NO_STOP  # slice_packed_device: a count "to the end"; no stop byte
+FIELD_TO_END, FIELD_ABSENT = N.ET_FIELD_TO_END, N.ET_FIELD_ABSENT  # field_packed_device: "every field from here on"; pos of a field that is not there
 
 
 def _check(status, ctx=None):
@@ -656,6 +657,36 @@ class Context:
                                             self._index_ptr(out_text_index, n_rows), self._opt_ptr(status), ctypes.byref(res))
         return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
 
+    def field_packed_device(self, codebook, bodies, body_index, text_index, rows, field, n_fields, delim, out, out_body_index, out_text_index, pos=None, status=None):
+        """Row k of the NEW store is delim.join(text.split(delim)[field : field + n_fields]) of record rows[k] of the store (bodies,
+        body_index, text_index: take_packed_device's; rows=None: row k is record k) -- SPLIT_PART, found and copied on the compressed
+        bytes, nothing decoded: its body, as encode_packed_device would write it under `codebook`, goes to
+        out[out_body_index[k] : out_body_index[k + 1]], and out_text_index[k + 1] - out_text_index[k] is its length.  field (from 0),
+        n_fields: an int for every row, or an int32/uint32 CUDA tensor of one value per row; n_fields=FIELD_TO_END: every field from
+        `field` on.  delim: an int 0 .. 255, or one byte.  pos: optional int32/uint32 CUDA tensor of one value per row: the symbol at
+        which the field begins, FIELD_ABSENT when the record has no such field (the row is then the empty record, its status ET_OK)
+        and for a failed row.  status: optional uint8 CUDA tensor of one et_status byte per ROW; a row that fails becomes an empty
+        record.  out=None: sizes only (pos is written).  out may not overlap bodies.  -> TakeResult; .status is ET_OK or ET_ERR_CAP
+        (nothing written, .out_bytes = the room needed); any other failure of the call raises.  Stream-ordered like
+        take_packed_device."""
+        n = text_index.numel() - 1
+        n_rows = n if rows is None else rows.numel()
+        what = "rows, field, n_fields and pos are ints or 1-D CUDA tensors of 32-bit integers"
+        field_p, field_v = (None, int(field)) if isinstance(field, (int, np.integer)) else (self._rows_ptr(field, what), 0)
+        count_p, count_v = (None, int(n_fields)) if isinstance(n_fields, (int, np.integer)) else (self._rows_ptr(n_fields, what), 0)
+        assert all(p is None or t.numel() >= n_rows for p, t in ((field_p, field), (count_p, n_fields))), "field and n_fields hold a value per row"
+        assert pos is None or pos.numel() >= n_rows, "pos holds a value per row"
+        if not isinstance(delim, (int, np.integer)):
+            (delim,) = bytes(delim)
+        res = N.TakeResult()
+        self._bind()
+        rc = N.lib().et_field_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                            None if rows is None else self._rows_ptr(rows, what), n_rows, field_p, field_v, count_p, count_v, int(delim),
+                                            self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows),
+                                            self._index_ptr(out_text_index, n_rows), None if pos is None else self._rows_ptr(pos, what), self._opt_ptr(status),
+                                            ctypes.byref(res))
+        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -860,6 +891,45 @@ class Context:
             raise EntreepyError(res.first_status, f"slice_packed: row {res.first_failed}")
         new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
         return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+
+    def field_packed(self, codebook, blob, out_index, lengths, rows, field, n_fields=1, delim=b","):
+        """decode_packed's store, a list of record numbers (any order, repeats allowed), each row's first field (from 0) and how many
+        fields it takes (an int for every row, or a list of one per row) -> a store like take_packed's and the fields' positions:
+        (the bodies of delim.join(text.split(delim)[field : field + n_fields]) back to back as bytes, their offsets, their lengths,
+        pos as a numpy u32 array: the symbol at which each field begins, FIELD_ABSENT where the record has no such field -- that row
+        is the empty record), through one field_packed_device call."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert out_index.size == lengths.size + 1
+        if not rows.size:
+            return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+
+        def per_row(v):
+            if isinstance(v, (int, np.integer)):
+                return int(v)
+            v = np.ascontiguousarray(v, dtype=np.uint32)
+            assert v.size == rows.size
+            return torch.from_numpy(v.view(np.int32)).to(d_blob.device)
+
+        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
+        good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none; a field is no longer than its record's body)
+        room = int((out_index[good + 1] - out_index[good]).sum())
+        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=d_blob.device)
+        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        d_pos = torch.empty(rows.size, dtype=torch.int32, device=d_blob.device)
+        res = self.field_packed_device(codebook, d_blob, d_body_index, d_text_index, d_rows, per_row(field), per_row(n_fields), delim, d_out, d_new_index, d_new_text, pos=d_pos)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"field_packed: row {res.first_failed}")
+        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
+        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text), d_pos.cpu().numpy().view(np.uint32)
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

@@ -28,6 +28,7 @@
 //   join          counters -> clear the table -> k_join_build -> k_join_flag (the keys' counters into the report) -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   take          counters -> k_take_plan -> k_take_scan (poll) -> unless sizes only: k_take_copy
 //   slice         sorted codes + counters -> k_slice_plan -> k_slice_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
+//   field         sorted codes + counters -> k_field_plan -> k_field_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -64,7 +65,7 @@ static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the p
 // The packed calls' device workspace (ctx->packed_ws) begins as the pinned region does, so an upload lands where it came from: the
 // table, the counters at PK_STATS for EVERY call, the match's pattern.  Behind the counters each call has its own layout:
 //   encode, gather   from PK_SIZES: a size word per record, or per row        take   from PK_SIZES: a TakeRow per row
-//   slice   from PK_SIZES: a TakeRow per row, then a list entry per row
+//   slice, field   from PK_SIZES: a TakeRow per row, then a list entry per row
 //   search  as the match, then a position and a list entry per record
 //   match   behind the pattern: the tile workspace (tile_ws)                   join   behind the counters: the tile workspace, the table's slots, a key number per record
 //   order   (the match's LESS modes) the sorted codes, the counters, the pattern, the boundary table behind the pattern's last word, the tile workspace
@@ -678,6 +679,50 @@ extern "C" int et_slice_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     res->text_bytes = rep[et::TAKE_TEXT_BYTES];
     read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
     if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the slices need more than cap bytes");  // (k_take_copy saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_field_lane_bytes(void) { return et::FIELD_LANE_BYTES; }
+
+extern "C" int et_field_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                      const uint64_t *d_text_index, size_t n_records, const uint32_t *d_rows, size_t n_rows, const uint32_t *d_field, uint32_t field,
+                                      const uint32_t *d_n_fields, uint32_t n_fields, int delim, void *d_out, size_t cap, uint64_t *d_out_body_index,
+                                      uint64_t *d_out_text_index, uint32_t *d_pos, uint8_t *d_status, et_take_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (misaligned(7, d_body_index, d_text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_rows, d_field, d_n_fields, d_pos)) return fail(ctx, ET_ERR_ARG, "the rows, the fields, the field counts or the positions are not 4-byte aligned");
+    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
+    if (!d_rows && n_rows != n_records) return fail(ctx, ET_ERR_ARG, "without d_rows, row k is record k: n_rows must be n_records");
+    if (d_out && cap && body_bytes) {  // (cutting in place is not this call's)
+        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
+        if (o < b + body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps d_bodies");
+    }
+    if (delim < 0 || delim > 255) return fail(ctx, ET_ERR_ARG, "delim is a byte");
+    *res = et_take_result{};
+    if (n_rows == 0) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    // the slice's upload and layout: the sorted codes and the counters' first values; behind them a TakeRow and a list entry per row
+    uint32_t n_codes = 0;
+    ET_TRY(packed_upload(ctx, cb, false, n_rows * (sizeof(et::TakeRow) / 4 + 1), &n_codes));
+    et::FieldJob job{};
+    job.rows = d_rows;
+    job.d_field = d_field;
+    job.d_n_fields = d_n_fields;
+    job.d_pos = d_pos;
+    job.n_rows = static_cast<uint32_t>(n_rows);
+    job.field = field;
+    job.n_fields = n_fields;
+    job.delim = static_cast<uint32_t>(delim);  // (a byte without a code is no symbol of the table: it occurs nowhere)
+    const et::PackedReport report = next_report(ctx);
+    et::launch_field(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, ws<const uint2>(ctx, 0), n_codes, job,
+                     d_out, cap, d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, PK_SIZES), ws<uint32_t>(ctx, PK_SIZES + n_rows * sizeof(et::TakeRow)), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the field call's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
+    res->out_bytes = rep[et::PACKED_BYTES];
+    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the fields need more than cap bytes");  // (k_take_copy saw the same two figures)
     return ET_OK;
 }
 

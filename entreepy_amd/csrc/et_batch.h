@@ -300,4 +300,33 @@ struct SliceJob {
 void launch_slice(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const SliceJob &job, void *d_out, uint64_t cap,
                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
 
+// The field (et_field_packed_device): fields [field, field + n_fields) of rows[]' stored texts, cut at a delimiter byte, as a NEW
+// packed store -- under one complete prefix-free table a delimiter is a codeword boundary whose codeword decodes to `delim`, so a run
+// of fields is the run of bits between two such boundaries and is written exactly as a slice is.  The walk counts the delimiters it
+// steps over; a codeword at or behind the record's length is no symbol of the stored text and is never counted.
+//   k_field_plan  k_slice_plan's frame: a body (clip_body of the whole length: nothing bounds where field k lies) up to
+//                 FIELD_LANE_BYTES is walked by its lane alone with a running delimiter count, the walk ending at the closing
+//                 delimiter; a longer one goes onto a list; a TakeRow per row in the slice's form, and d_pos
+//   k_field_long  one workgroup per listed row (k_slice_long's shape): per block the settling walk counts each lane's delimiters, a
+//                 second scan numbers them across the lanes, the count carried across the blocks beside the codewords'; the lanes
+//                 that hold one of the two target delimiters walk again; begin, closing delimiter and the text's end reduced over the
+//                 workgroup; thread 0 stores the row's TakeRow and d_pos
+//   k_take_scan, k_take_copy<BITS>   the slice's, unchanged
+// FIELD_LANE_BYTES is the search's threshold, kept: the lane's walk is slice_lane's with a counter.
+#ifndef ET_FIELD_LANE_BYTES  // (a build for the sweep sets it, as ET_SEARCH_LANE_BYTES)
+#define ET_FIELD_LANE_BYTES ET_SEARCH_LANE_BYTES
+#endif
+constexpr uint32_t FIELD_LANE_BYTES = ET_FIELD_LANE_BYTES;
+constexpr uint32_t FIELD_ABSENT = 0xffffffffu;  // d_pos of a row whose record has no such field, and of a failed row
+struct FieldJob {
+    const uint32_t *rows;                   // null: row k is record k
+    const uint32_t *d_field, *d_n_fields;   // null: the scalar beside it
+    uint32_t *d_pos;                        // null: not asked for
+    uint32_t n_rows, field, n_fields;
+    uint32_t delim;                         // the delimiter byte
+};
+// codes, plan, long_list: as launch_slice's (the counters' word for the list is the slice's, SLICE_N_LONG).
+void launch_field(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const FieldJob &job, void *d_out, uint64_t cap,
+                  uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
+
 }  // namespace et

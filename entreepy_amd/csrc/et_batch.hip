@@ -39,6 +39,10 @@
 //            k_slice_long    one workgroup per listed row: k_search_long's settled blocks, the boundaries reduced over the workgroup
 //            k_take_scan     as in the take
 //            k_take_copy     as in the take, a row's source a run of BITS: each byte a funnel shift of two, the last one masked to its bits
+//   field    k_field_plan    one lane per row: judged; a short body walked with a running delimiter count to the field's two boundaries; a long one listed
+//            k_field_long    one workgroup per listed row: settled blocks whose walks count delimiters, a second scan numbers them, the boundaries reduced
+//            k_take_scan     as in the take
+//            k_take_copy     as in the slice
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -2033,6 +2037,245 @@ __global__ __launch_bounds__(BB) void k_slice_long(PackedStore store, const uint
 }
 
 // --------------------------------------------------------------------------------
+// The field call: fields [field, field + n_fields) of rows[]' stored texts -- text_b.split(delim) --, the delimiters between them
+// kept, as a new packed store.  A delimiter is a codeword of the stored text that decodes to `delim`; the walks count them.  Numbered
+// from 1, the field begins behind delimiter `a` = field (a = 0: at the text's first symbol) and ends in front of delimiter `b` =
+// field + n_fields, or where the stored text ends when it has fewer; a text with fewer than `a` has no such field.  What lies between
+// is a run of bits between two codeword boundaries: a slice, written by the take's scan and the bit-reading copy.
+// THE rule of what counts: codeword number i of a body is a symbol of the stored text when it ends inside the body AND i < length.
+// Every loop is bounded as the slice's are: a lane's walk by the record's length, the workgroup's by the blocks of the body that the
+// length can reach, its fixed point by 256 trips and a lane's walk inside it by its 256 bits.  No workgroup waits for another.
+// --------------------------------------------------------------------------------
+struct FieldAsk {
+    uint32_t a, b;  // a <= b
+};
+
+__device__ __forceinline__ FieldAsk field_ask(const FieldJob &job, uint32_t k) {
+    const uint32_t field = job.d_field ? job.d_field[k] : job.field, n = job.d_n_fields ? job.d_n_fields[k] : job.n_fields;
+    const uint64_t b = static_cast<uint64_t>(field) + n;  // (64 bits: no wrap; a text has fewer than 2^32 - 1 delimiters)
+    return FieldAsk{field, b < 0xffffffffull ? static_cast<uint32_t>(b) : 0xffffffffu};
+}
+
+// What a walk found: the slice's three, and the symbol at which the field begins -- FIELD_ABSENT: no such field (n is 0 then).
+struct Fielded {
+    uint32_t begin, end, n, pos;
+};
+
+__device__ __forceinline__ uint4 field_row(const BodyBits &g, const Fielded &f) { return slice_row(g, Sliced{f.begin, f.end, f.n}); }
+
+// One lane, one body of a few words, from global memory: slice_lane's registers with a running delimiter count, a trip per symbol of
+// the stored text in front of the closing delimiter.  (a == b == 0 asks for nothing of the body: the caller does not come here.)
+__device__ __forceinline__ Fielded field_lane(const CodeTables &t, uint32_t n_codes, const BodyBits &g, uint32_t len, const FieldAsk &ask, uint32_t delim) {
+    uint32_t pos = g.first_bit, k = 0, idx = 0, seen = 0;
+    Fielded f{pos, pos, 0u, ask.a ? FIELD_ABSENT : 0u};
+    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
+    for (; idx < len; ++idx) {
+        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
+            k = pos >> 5;
+            two = (two << 32) | body_word_be(g, k + 1);
+        }
+        const uint32_t meta = code_at(t, n_codes, static_cast<uint32_t>((two << (pos & 31)) >> 32)), bits = meta >> 8;
+        if (pos + bits > g.end_bit) break;  // the bits ran out inside this codeword: the stored text ends here
+        if ((meta & 0xffu) == delim) {
+            ++seen;
+            if (seen == ask.a) {  // the field begins behind this one
+                f.begin = f.end = pos + bits;
+                f.pos = idx + 1;
+                if (ask.b == ask.a) return f;  // ... and no field was asked for: the empty record, present
+            } else if (seen == ask.b) {  // the closing one
+                f.end = pos;
+                f.n = idx - f.pos;
+                return f;
+            }
+        }
+        pos += bits;
+    }
+    if (f.pos == FIELD_ABSENT) return f;
+    f.end = pos;  // the stored text's end
+    f.n = idx - f.pos;
+    return f;
+}
+
+// k_field_plan: k_slice_plan's frame.  A record without bytes or symbols has the empty stored text: one empty field 0.  A row that asks
+// for no field of field 0 on is the empty record and is not read.  A body that the length can reach up to FIELD_LANE_BYTES is walked by
+// its lane (field_lane); a longer one goes onto long_list and is the empty record here: k_field_long stores its TakeRow and its
+// position.  d_pos[k] = the symbol at which the field begins, FIELD_ABSENT without one and for a failed row.  LDS 6 KiB + 8 words.
+__global__ __launch_bounds__(BB) void k_field_plan(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, FieldJob job, TakeRow *__restrict__ plan,
+                                                   uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ CodeTables t;
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    load_tables(t, codes, n_codes);
+    __syncthreads();
+    PackedTally tally;
+    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
+        bool is_long = false;
+        if (k < job.n_rows) {
+            const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
+            const uint32_t status = !rec.status && rec.nb > TAKE_BODY_MAX ? PACKED_UNSUPPORTED : rec.status;
+            uint4 row = make_uint4(0u, 0u, 0u, 0u);
+            uint32_t pos = FIELD_ABSENT;
+            if (!status) {
+                const FieldAsk ask = field_ask(job, k);
+                if (!rec.nb || !rec.len || !ask.b) {
+                    if (!ask.a) pos = 0;
+                } else {
+                    const uint32_t len = static_cast<uint32_t>(rec.len);
+                    const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len)));
+                    if (g.end_bit - g.first_bit <= FIELD_LANE_BYTES * 8) {
+                        const Fielded f = field_lane(t, n_codes, g, len, ask, job.delim);
+                        row = field_row(g, f);
+                        pos = f.pos;
+                    } else {
+                        is_long = true;
+                    }
+                }
+            }
+            reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
+            if (job.d_pos) job.d_pos[k] = pos;
+            if (d_status) d_status[k] = static_cast<uint8_t>(status);
+            tally.note(k, status);
+        }
+        const unsigned long long longs = __ballot(is_long);
+        if (longs) {  // (the same for the whole wavefront)
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
+            at = __shfl(at, 0, 64);
+            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
+        }
+    }
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
+// The visitor of the settling walks of the field call: the walk's delimiters, and the bit of the lane's 256 behind its last codeword.
+struct CountDelims {
+    uint32_t delim, n, last;
+    __device__ __forceinline__ bool operator()(uint32_t, uint32_t pos, uint32_t, uint32_t meta) {
+        n += (meta & 0xffu) == delim;
+        last = pos + (meta >> 8);
+        return true;
+    }
+};
+
+// One row's body by the whole workgroup under the tables in `s`: slice_stream's blocks, settled by a walk that counts its delimiters.
+// The visitor does not know its lane's symbol numbers; once the scan has given them, a lane whose codewords reach the length -- one
+// lane of the text's last block, the lanes behind it hold none -- counts again up to it, so no codeword at or behind `len` is ever a
+// delimiter.  A second scan (s_scan, 4 words, free again at the next block's first barrier) numbers the delimiters across the lanes,
+// `seen` carries them across the blocks beside `done`.  The lanes that hold delimiter a or b walk again and note, as symbol << 32 | bit,
+// where the field begins and where the closing delimiter does; every lane notes where its last symbol ends.  The three are reduced as
+// the slice's are (s_red, 12 words).  The begin found in one block is kept in a register until the end is found, blocks later.  The
+// blocks end with the one that holds the closing delimiter, or once `len` codewords lie behind: nothing behind is visited.
+__device__ __forceinline__ Fielded field_stream(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, uint32_t len, const FieldAsk &ask, uint32_t delim,
+                                                unsigned long long *s_red, uint32_t *s_scan) {
+    constexpr unsigned long long NONE = ~0ull;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
+    uint32_t start = g.first_bit, done = 0, seen = 0;  // the block's first codeword; codewords and delimiters so far
+    unsigned long long begin = ask.a ? NONE : g.first_bit, end = 0;
+    for (uint32_t blk = 0; blk < n_blocks && done < len; ++blk) {
+        const uint32_t at = blk * DEC_WORDS * 32 + tid * 256;
+        CountDelims counting{delim, 0u, 0u};
+        const Settled b = settle_block(s, n_codes, g, blk, start, counting);
+        const uint32_t lo = done + b.first;  // the number of the lane's first codeword
+        uint32_t held = b.count, mine = counting.n, last = counting.last;  // the lane's symbols of the stored text, the delimiters among them
+        if (lo >= len) {
+            held = mine = 0;
+        } else if (lo + b.count > len) {  // (lo + count <= 4 * len + 16: no wrap)
+            held = len - lo;
+            mine = 0;
+            uint32_t again;
+            (void)walk(s, n_codes, b.used, b.room, &again, [&](uint32_t cnt, uint32_t pos, uint32_t, uint32_t meta) {
+                if (cnt >= held) return false;
+                mine += (meta & 0xffu) == delim;
+                last = pos + (meta >> 8);
+                return true;
+            });
+        }
+        uint32_t block_delims;
+        const uint32_t before = seen + block_exclusive_scan(mine, s_scan, &block_delims);  // delimiters in front of the lane's first symbol
+        unsigned long long my_begin = NONE, my_close = NONE, my_last = held ? static_cast<unsigned long long>(lo + held) << 32 | (at + last) : 0ull;
+        const bool has_a = ask.a > before && ask.a - before <= mine, has_b = ask.b > before && ask.b - before <= mine;
+        if (has_a || has_b) {
+            uint32_t again, d = before;
+            (void)walk(s, n_codes, b.used, b.room, &again, [&](uint32_t cnt, uint32_t pos, uint32_t, uint32_t meta) {
+                if (cnt >= held) return false;
+                if ((meta & 0xffu) != delim) return true;
+                ++d;
+                if (d == ask.a) my_begin = static_cast<unsigned long long>(lo + cnt + 1) << 32 | (at + pos + (meta >> 8));
+                if (d == ask.b) {
+                    my_close = static_cast<unsigned long long>(lo + cnt) << 32 | (at + pos);
+                    return false;
+                }
+                return true;
+            });
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const unsigned long long ob = __shfl_xor(my_begin, d, 64), oc = __shfl_xor(my_close, d, 64), ol = __shfl_xor(my_last, d, 64);
+            if (ob < my_begin) my_begin = ob;
+            if (oc < my_close) my_close = oc;
+            if (ol > my_last) my_last = ol;
+        }
+        if ((tid & 63) == 0) {
+            s_red[tid >> 6] = my_begin;
+            s_red[4 + (tid >> 6)] = my_close;
+            s_red[8 + (tid >> 6)] = my_last;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < BB / 64; ++w) {
+            if (s_red[w] < my_begin) my_begin = s_red[w];
+            if (s_red[4 + w] < my_close) my_close = s_red[4 + w];
+            if (s_red[8 + w] > my_last) my_last = s_red[8 + w];
+        }
+        if (my_begin != NONE) begin = my_begin;  // (the same for every lane, like all below)
+        if (my_last > end) end = my_last;
+        if (my_close != NONE) {  // nothing at or behind the closing delimiter belongs to the field
+            end = my_close;
+            break;
+        }
+        start = b.start;
+        done += b.total;
+        seen += block_delims;
+    }
+    if (begin == NONE) return Fielded{0u, 0u, 0u, FIELD_ABSENT};  // the stored text has fewer than `a` delimiters
+    const uint32_t pos = static_cast<uint32_t>(begin >> 32);
+    if (ask.a == ask.b || end < begin) return Fielded{static_cast<uint32_t>(begin), static_cast<uint32_t>(begin), 0u, pos};  // (no field asked for; a text without a symbol)
+    return Fielded{static_cast<uint32_t>(begin), static_cast<uint32_t>(end), static_cast<uint32_t>(end >> 32) - pos, pos};
+}
+
+// k_field_long: k_slice_long's shape over long_list.  A workgroup beyond the list returns before it sets anything up.  Thread 0 stores
+// the row's TakeRow and position (k_field_plan left the empty record there; the scan runs behind this kernel).
+// LDS as k_batch_decode, the reduction's 12 words and the second scan's 4.
+__global__ __launch_bounds__(BB) void k_field_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, FieldJob job, TakeRow *__restrict__ plan,
+                                                   const uint32_t *__restrict__ long_list, const unsigned long long *__restrict__ stats) {
+    __shared__ BatchDecLds s;
+    __shared__ unsigned long long s_red[3 * (BB / 64)];
+    __shared__ uint32_t s_scan[BB / 64];
+    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
+    if (blockIdx.x >= n_long) return;
+    load_tables(s.t, codes, n_codes);
+    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
+    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
+        const uint32_t k = long_list[i];
+        if (k >= job.n_rows) continue;  // (k_field_plan lists rows; the same for every lane, like all below)
+        const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
+        if (rec.status || rec.nb == 0 || rec.nb > TAKE_BODY_MAX || rec.len == 0) continue;  // (k_field_plan lists no such row)
+        const FieldAsk ask = field_ask(job, k);
+        if (!ask.b) continue;
+        const uint32_t len = static_cast<uint32_t>(rec.len);
+        const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len)));
+        const Fielded f = field_stream(s, n_codes, g, len, ask, job.delim, s_red, s_scan);
+        if (threadIdx.x == 0) {
+            reinterpret_cast<uint4 *>(plan)[k] = field_row(g, f);
+            if (job.d_pos) job.d_pos[k] = f.pos;
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
 
 static uint32_t capped(uint64_t n, uint32_t most) { return n < most ? static_cast<uint32_t>(n) : most; }
@@ -2072,6 +2315,19 @@ void launch_slice(hipStream_t stream, const PackedStore &store, const uint2 *cod
     const uint32_t n_rows = job.n_rows;
     hipLaunchKernelGGL(k_slice_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
     hipLaunchKernelGGL(k_slice_long, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list),
+                       static_cast<const unsigned long long *>(r.stats));
+    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
+                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
+    if (!d_out) return;
+    hipLaunchKernelGGL(k_take_copy<true>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(nullptr),
+                       static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+}
+
+void launch_field(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const FieldJob &job, void *d_out, uint64_t cap,
+                  uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &r) {
+    const uint32_t n_rows = job.n_rows;
+    hipLaunchKernelGGL(k_field_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
+    hipLaunchKernelGGL(k_field_long, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list),
                        static_cast<const unsigned long long *>(r.stats));
     hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
                        static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);

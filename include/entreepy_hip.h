@@ -634,9 +634,8 @@ int et_take_packed_device(et_ctx *ctx,
  *   et_slice_lane_bytes(): a body of which the slice's end can reach up to this many bytes (4 bytes per symbol in front of the end, and
  *     8: a LEFT of a few symbols reaches little of a long body) is walked by one lane, a longer one by a workgroup -- for tests that
  *     want rows on both sides; the answer does not depend on it.
- * Out of scope: the k-th delimiter-separated field in one call; negative or from-the-end indices (the caller has text_index on the
- * device for that); slicing in place -- [d_out, d_out + cap) may not overlap [d_bodies, d_bodies + body_bytes) --; several stores per
- * call; records above the limits named above.
+ * Out of scope: negative or from-the-end indices (the caller has text_index on the device for that); slicing in place -- [d_out,
+ * d_out + cap) may not overlap [d_bodies, d_bodies + body_bytes) --; several stores per call; records above the limits named above.
  * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_bodies, d_body_index, d_text_index, d_out_body_index or
  * d_out_text_index; an offset array that is not 8-byte aligned; d_rows, d_first or d_count not 4-byte aligned; n_records or n_rows
  * above 0x7fffffff; d_rows == NULL with n_rows != n_records; d_out overlapping d_bodies; a stop outside [-1, 255] -- all checked
@@ -655,6 +654,52 @@ int et_slice_packed_device(et_ctx *ctx, const et_codebook *cb,
                            const uint32_t *d_count, uint32_t count,
                            int stop,
                            void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
+                           uint8_t *d_status, et_take_result *res);
+
+/* FIELD: the k-th DELIMITED FIELD of each selected record as a NEW packed store, on the device, nothing decoded and nothing encoded
+ * again -- SPLIT_PART(line, ',', k), column k of a CSV row, the third token of a log line.  Under one complete prefix-free table a
+ * delimiter is a codeword boundary whose codeword decodes to `delim`, so a run of fields is the run of bits between two such
+ * boundaries: the slice's walk counts the delimiters it steps over, the slice's scan and bit-shifting copy write the result.
+ *   The store, d_rows, d_status, the judgement of a row and what a failed row becomes are the slice call's.
+ *   d_field[k], d_n_fields[k] (32 bits each, 4-byte aligned, on the device; either may be NULL: then the scalar `field` or `n_fields`
+ *     holds for every row; with the pointer the scalar is ignored): row k's first field, counted from 0, and how many consecutive
+ *     fields it takes, the delimiters between them kept.  ET_FIELD_TO_END as n_fields: every field from `field` on.
+ *   text_b is the stored text of record r = d_rows[k] as every packed call defines it: the first min(length_r, codewords that end
+ *     inside its body) symbols -- a codeword at or behind length_r is no symbol and never a delimiter, nor is what the pad bits read
+ *     as.  With parts = text_b.split(delim) as Python splits: field >= len(parts): the field is ABSENT -- row k is the empty record,
+ *     d_pos[k] = ET_FIELD_ABSENT, the row's status stays ET_OK (SQL's SPLIT_PART).  Otherwise row k is
+ *     delim.join(parts[field : field + n_fields]), field + n_fields taken in 64 bits and clamped as Python clamps a slice;
+ *     n_fields == 0 is the empty record, present; d_pos[k] = the symbol of text_b at which parts[field] begins.  The empty stored
+ *     text -- also that of a body of no bytes under a length above zero -- has one empty field 0 at position 0.  A delim without a
+ *     code occurs in no record: every record is one field.
+ *   d_pos (n_rows entries of 32 bits, 4-byte aligned, on the device; may be NULL): as above; ET_FIELD_ABSENT for a failed row too.
+ *     It may be the slice call's d_first.
+ *   d_out, both output arrays (n_rows + 1 entries, the first 0), the bytes -- exactly what et_encode_packed_device writes for the
+ *     result, pad bits zero whatever the source's are --, d_out == NULL (sizes only; d_pos is written) and ET_ERR_CAP (no byte of d_out
+ *     written; both arrays, d_status and d_pos complete, res->out_bytes the room needed) are the slice call's.
+ *   et_field_lane_bytes(): a body (min(body bytes, 4 * length + 8)) up to this many bytes is walked by one lane, a longer one by a
+ *     workgroup -- for tests that want rows on both sides; the answer does not depend on it.
+ * Out of scope: several fields of a row into several output rows in one walk; multi-byte or regex delimiters; quoting and escapes;
+ * fields counted from the end; a count of absent rows in *res; cutting in place; several stores per call; records above the slice
+ * call's limits.
+ * The call's own status: ET_ERR_ARG (the slice call's argument errors; delim outside [0, 255]; d_field, d_n_fields or d_pos not
+ * 4-byte aligned -- all checked before anything touches a device, *res untouched), ET_ERR_UNSUPPORTED (the table is not complete:
+ * nothing is enqueued), ET_ERR_CAP, ET_ERR_HIP, ET_ERR_NOMEM.  n_rows == 0: ET_OK, nothing enqueued, *res zeroed.  One upload (the
+ * sorted codes and zeroed counters, 2.1 KiB), four launches and one hand-over per call; stream-ordered like the other packed calls --
+ * *res is final on return, the device arrays once the ctx's stream has drained -- and it may follow or precede any of them on one
+ * ctx with nothing in between. */
+#define ET_FIELD_TO_END 0xffffffffu
+#define ET_FIELD_ABSENT 0xffffffffu
+size_t et_field_lane_bytes(void);           /* a body (min(body bytes, 4 * length + 8)) up to this is walked by one lane */
+int et_field_packed_device(et_ctx *ctx, const et_codebook *cb,
+                           const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                           const uint64_t *d_text_index, size_t n_records,
+                           const uint32_t *d_rows, size_t n_rows,
+                           const uint32_t *d_field, uint32_t field,
+                           const uint32_t *d_n_fields, uint32_t n_fields,
+                           int delim,
+                           void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
+                           uint32_t *d_pos,
                            uint8_t *d_status, et_take_result *res);
 
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */

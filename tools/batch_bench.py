@@ -61,6 +61,9 @@ process of its own so that every leg loads exactly one build of the library:
   slice           et_slice_packed_device (LEFT 12, 64 symbols from the middle, behind a needle up to a stop byte) against what it replaces:
                   a decode (or gather) of the rows' records and et_encode_packed_device of the cut text; the search's walk and the take's
                   copy on the same rows as floors
+  field           et_field_packed_device (field k of the pages split at spaces, of 10 % of the rows; fields 0, 3 and 7 of 262 144 CSV lines, of
+                  all rows and of 10 %) against what it replaces: a decode (or gather) of the rows' records and et_encode_packed_device of
+                  the cut text; the slice up to the delimiter on the same rows and the search's walk over the store as floors
 --legs picks the legs (default: all but search_sweep).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
@@ -76,6 +79,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs search --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/search_bench.json
     python tools/batch_bench.py --legs order --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/order_bench.json
     python tools/batch_bench.py --legs slice --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/slice_bench.json
+    python tools/batch_bench.py --legs field --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/field_bench.json
 """
 import argparse
 import ctypes
@@ -919,11 +923,151 @@ def _slice_leg(leg, lib_path, shapes):
     print(json.dumps(results))
 
 
+CSV_SHAPE = (262144, "csv")  # the field legs' third shape: generated lines of 8 comma-separated fields of 4 .. 16 bytes
+FIELD_CASES = {"pages": [(3, "tenth"), (100, "tenth")], "csv": [(0, "all"), (3, "all"), (7, "all"), (0, "tenth"), (3, "tenth"), (7, "tenth")]}
+
+
+def _csv_store(count):
+    """-> (text, text_index): `count` lines of 8 comma-separated fields of 4 .. 16 text-like bytes each (a comma or a line end in
+    the source text becomes a space)."""
+    import numpy as np
+
+    from tests import corpus
+
+    rng = np.random.default_rng(0xF1E1DB + count)
+    widths = rng.integers(4, 17, size=(count, 8))
+    lengths = widths.sum(axis=1) + 7
+    index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+    host = corpus.text_like(int(index[-1]), 0xF1E1DC + count).copy()
+    host[(host == ord(",")) | (host == 10)] = ord(" ")
+    commas = (index[:-1, None].astype(np.int64) + np.cumsum(widths + 1, axis=1)[:, :7] - 1).ravel()  # behind each of a line's first seven fields
+    host[commas] = ord(",")
+    return host, index
+
+
+def _field_leg(leg, lib_path, shapes):
+    """field / field_baseline: per shape a packed store (encoded untimed) -- the two page shapes with the space as the delimiter, fields 3
+    and 100 of 10 % of the records; 262 144 CSV lines (_csv_store), fields 0, 3 and 7 of every record and of 10 % -- then the timed call:
+    et_field_packed_device, its bytes, offsets and positions checked against et_encode_packed_device of Python's split over the plain
+    texts first, beside it the sizes-only call and two floors on the same store (et_slice_packed_device(0, TO_END, stop=delim) on the
+    same rows: field 0 does the same work; et_search_packed_device CONTAINS over the whole store: the walk with nothing written) -- or
+    what it replaces: et_decode_packed_device of the store (et_decode_packed_gather_device where the rows are a selection), then
+    et_encode_packed_device of the cut text; the cutting in between is not timed."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    base = leg == "field_baseline"
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device", "et_decode_packed_gather_device"]
+                      + ([] if base else ["et_field_packed_device", "et_field_lane_bytes", "et_slice_packed_device", "et_search_packed_device"]))
+    results = {} if base else {"lane_bytes": int(L.et_field_lane_bytes())}
+    for count, size in SHAPES + [CSV_SHAPE]:
+        shape_name = f"{count}x{size}"
+        if shapes and shape_name not in shapes:
+            continue
+        csv = size == "csv"
+        if csv:
+            host, index = _csv_store(count)
+        else:
+            host, index, _, _ = _search_store(count, size, 0.1)
+        delim = ord(",") if csv else ord(" ")
+        needle = host[-SEARCH_NEEDLE_LEN:].tobytes()  # (the floor's walk: what it finds does not matter)
+        blob, d = host.tobytes(), bytes([delim])
+        text = torch.from_numpy(host).to(dev)
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, index, _codebook(L, [host]))
+        res, shape = N.PackedResult(), {"records": count, "body_bytes": body_bytes}
+        tenth = np.sort(np.random.default_rng(0xF1E1DD + count).choice(count, size=count // 10, replace=False)).astype(np.uint32)
+        parts_of = {}
+        for field, sel in FIELD_CASES["csv" if csv else "pages"]:
+            name = f"field{field}_{sel}"
+            rows = None if sel == "all" else tenth
+            at = np.arange(count, dtype=np.uint32) if rows is None else rows
+            pieces, where = [], []
+            for r in at.tolist():
+                if r not in parts_of:
+                    parts_of[r] = blob[int(index[r]) : int(index[r + 1])].split(d)
+                parts = parts_of[r]
+                pieces.append(parts[field] if field < len(parts) else b"")
+                where.append(sum(len(x) + 1 for x in parts[:field]) if field < len(parts) else 0xFFFFFFFF)
+            cut_index = np.concatenate(([0], np.cumsum([len(x) for x in pieces]))).astype(np.uint64)
+            cut_total = int(cut_index[-1])
+            cut_text = torch.from_numpy(np.frombuffer(b"".join(pieces) + b"\0", np.uint8).copy()).to(dev)
+            _, want, need, want_index, cut_text_index = _packed_store(L, h, cut_text, cut_index, cb)  # what the fields must be: the encoder's bodies of Python's split
+            n_rows = at.size
+            d_rows = torch.from_numpy(at.view(np.int32).copy()).to(dev)
+            out = torch.zeros(need + 64, dtype=torch.uint8, device=dev)
+            out_body_index, out_text_index = (torch.zeros(n_rows + 1, dtype=torch.int64, device=dev) for _ in range(2))
+            entry = {"rows": int(n_rows), "bytes": need, "text_bytes": cut_total, "absent": int(sum(w == 0xFFFFFFFF for w in where))}
+            if base:
+                room = int(index[-1]) if rows is None else int(np.diff(index).astype(np.int64)[at.astype(np.int64)].sum())
+                dec = torch.zeros(room + 64, dtype=torch.uint8, device=dev)
+
+                def baseline():
+                    if rows is None:
+                        assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, dec.data_ptr(), room, None,
+                                                         None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    else:
+                        assert L.et_decode_packed_gather_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, d_rows.data_ptr(),
+                                                                n_rows, dec.data_ptr(), room, out_text_index.data_ptr(), None, None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.out_bytes == room and res.n_failed == 0 and res.n_short == 0
+                    assert L.et_encode_packed_device(h, ctypes.byref(cb), cut_text.data_ptr(), cut_total, cut_text_index.data_ptr(), n_rows, out.data_ptr(), need, out_body_index.data_ptr(),
+                                                     None, ctypes.byref(res)) == 0, L.et_last_error(h)
+                    assert res.out_bytes == need and res.n_failed == 0
+
+                baseline()
+                torch.cuda.synchronize()
+                assert torch.equal(out[:need], want[:need]) and torch.equal(out_body_index, want_index)
+                entry.update(_timed(baseline))
+                del dec
+            else:
+                tres, mres = N.TakeResult(), N.MatchResult()
+                d_pos = torch.zeros(n_rows, dtype=torch.int32, device=dev)
+                rows_p = None if rows is None else d_rows.data_ptr()
+
+                def call(d_out=out):
+                    assert L.et_field_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, rows_p, n_rows, None, field,
+                                                    None, 1, delim, None if d_out is None else d_out.data_ptr(), need, out_body_index.data_ptr(), out_text_index.data_ptr(),
+                                                    d_pos.data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+                    assert tres.out_bytes == need and tres.text_bytes == cut_total and tres.n_failed == 0
+
+                call()
+                torch.cuda.synchronize()
+                assert torch.equal(out[:need], want[:need]), "the fields differ from the encoder's bodies of Python's split"
+                assert torch.equal(out_body_index, want_index) and torch.equal(out_text_index, cut_text_index)
+                assert d_pos.cpu().numpy().view(np.uint32).tolist() == where, "the positions differ from Python's"
+                entry.update(_timed(call))
+                entry["sizes_only"] = _timed(lambda: call(None))
+                sliced = torch.zeros(body_bytes + 64, dtype=torch.uint8, device=dev)
+                d_hits, d_found = (torch.zeros(count, dtype=torch.int32, device=dev) for _ in range(2))
+
+                def slice0():
+                    assert L.et_slice_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, rows_p, n_rows, None, 0,
+                                                    None, 0xFFFFFFFF, delim, sliced.data_ptr(), body_bytes, out_body_index.data_ptr(), out_text_index.data_ptr(), None,
+                                                    ctypes.byref(tres)) == 0, L.et_last_error(h)
+
+                def search():
+                    assert L.et_search_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), count, needle, len(needle),
+                                                     N.ET_SEARCH_CONTAINS, d_hits.data_ptr(), count, d_found.data_ptr(), None, ctypes.byref(mres)) == 0, L.et_last_error(h)
+
+                entry["slice0_floor"] = _timed(slice0)
+                entry["search_floor"] = _timed(search)
+                entry["vs_slice0_floor"] = round(entry["ms"] / entry["slice0_floor"]["ms"], 2)
+                entry["vs_search_floor"] = round(entry["ms"] / entry["search_floor"]["ms"], 2)
+                del sliced
+            shape[name] = entry
+            del out, want, cut_text
+        results[shape_name] = shape
+        del text, bodies
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
     ap.add_argument("--batch-lib", default=os.environ.get("ET_BATCH_LIB_PATH"))
-    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take,search,order,slice")
+    ap.add_argument("--legs", default="single_parent,single,batch,shared,packed,gather,match,join,take,search,order,slice,field")
     ap.add_argument("--shapes", default="")  # (the match legs: a comma list of shape names, e.g. 262144x16-48; default: all)
     ap.add_argument("--out")
     ap.add_argument("--leg")  # (internal: the child processes)
@@ -941,6 +1085,8 @@ def main():
         return _take_leg(a.leg, a.lib)
     if a.leg and a.leg.startswith("slice"):
         return _slice_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
+    if a.leg and a.leg.startswith("field"):
+        return _field_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -962,6 +1108,8 @@ def main():
         legs += [("order_baseline", "order_baseline", a.batch_lib or here), ("order", "order", here)]
     if "slice" in a.legs.split(","):
         legs += [("slice_baseline", "slice_baseline", a.batch_lib or here), ("slice", "slice", here)]
+    if "field" in a.legs.split(","):
+        legs += [("field_baseline", "field_baseline", a.batch_lib or here), ("field", "field", here)]
     if "search_sweep" in a.legs.split(","):
         legs += [("search_sweep", "search_sweep", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
@@ -1009,6 +1157,19 @@ def main():
                 out["slice_vs_baseline"][k][name] = {"baseline_over_slice": round(old["ms"] / new["ms"], 2),
                                                      "beyond_both_spreads": old["ms"] - new["ms"] > (old["max_ms"] - old["min_ms"]) + (new["max_ms"] - new["min_ms"])}
         out["slice_condition_met"] = all(e["beyond_both_spreads"] for v in out["slice_vs_baseline"].values() for e in v.values())
+    if "field" in out:  # per shape and case: the pair's time over the field call's (> 1: the field call is faster), and whether the medians lie further apart than the two spreads together
+        out["field_vs_baseline"] = {}
+        for k, v in out["field"].items():
+            if not isinstance(v, dict):
+                continue
+            out["field_vs_baseline"][k] = {}
+            for name, new in v.items():
+                if not isinstance(new, dict):
+                    continue
+                old = out["field_baseline"][k][name]
+                out["field_vs_baseline"][k][name] = {"baseline_over_field": round(old["ms"] / new["ms"], 2),
+                                                     "beyond_both_spreads": old["ms"] - new["ms"] > (old["max_ms"] - old["min_ms"]) + (new["max_ms"] - new["min_ms"])}
+        out["field_condition_met"] = all(e["beyond_both_spreads"] for v in out["field_vs_baseline"].values() for e in v.values())
     line = json.dumps(out)
     print(line)
     if a.out:
