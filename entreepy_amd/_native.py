@@ -218,6 +218,10 @@ SIGNATURES = {
     "et_field_lane_bytes": (_sz, []),
     "et_field_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, _vp,
                                               ctypes.POINTER(TakeResult)]),
+    "et_concat_sep_max": (_sz, []),
+    "et_concat_lane_bytes": (_sz, []),
+    "et_concat_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
+                                               ctypes.POINTER(TakeResult)]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),

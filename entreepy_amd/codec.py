@@ -687,6 +687,39 @@ class Context:
                                             ctypes.byref(res))
         return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
 
+    def concat_packed_device(self, codebook, a, sep, b, out, out_body_index, out_text_index, rows_a=None, rows_b=None, status=None):
+        """Row k of the NEW store is text(A[rows_a[k]]) + sep + text(B[rows_b[k]]), text() the record's stored text -- row-wise string
+        concatenation on the compressed bytes, nothing decoded: the left stored text's bits, sep's bits under `codebook` and the right
+        stored text's bits laid end to end.  Both sides are walked to the end of their stored text, as slice_packed_device walks: the
+        pad bits of either body are masked, not copied, a record kept raw (no bytes under a length) is the empty text on either side,
+        and out_text_index advances by the SYMBOLS of the three -- not by the right record's length where its body ends before it.
+        For every input the row is exactly what encode_packed_device writes for the concatenated stored texts.  a, b: (bodies, body_index, text_index) as
+        take_packed_device takes a store, or None for an absent side (prefix or suffix every record; not both); they may be the same
+        store.  sep: bytes, at most concat_sep_max() of them.  rows_a, rows_b: int32/uint32 CUDA tensors of one record number per row
+        (any order, repeats allowed), or None: row k is record k of that side.  A row fails -- the empty record -- with the left
+        record's status if that is not OK, else the right's, else ET_ERR_UNSUPPORTED for a new length above batch small_max.
+        out=None: sizes only.  out may not overlap either side's bodies.  -> TakeResult; .status is ET_OK or ET_ERR_CAP (nothing
+        written, .out_bytes = the room needed); any other failure of the call raises.  Stream-ordered like take_packed_device."""
+        sep_a, sep_p = _host_u8(bytes(sep))
+        what = "rows_a and rows_b are 1-D CUDA tensors of 32-bit integers"
+        sides, counts = [], []
+        for store, rows in ((a, rows_a), (b, rows_b)):
+            if store is None:
+                sides += [None, 0, None, None, 0, None]
+                continue
+            bodies, body_index, text_index = store
+            n = text_index.numel() - 1
+            sides += [bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n, None if rows is None else self._rows_ptr(rows, what)]
+            counts.append(n if rows is None else rows.numel())
+        assert counts and min(counts) == max(counts), "at least one side, and both sides give the same number of rows"
+        n_rows = counts[0]
+        res = N.TakeResult()
+        self._bind()
+        rc = N.lib().et_concat_packed_device(self._h, ctypes.byref(codebook.raw), *sides[:6], sep_p, sep_a.size, *sides[6:], n_rows, self._opt_ptr(out),
+                                             0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows), self._index_ptr(out_text_index, n_rows),
+                                             self._opt_ptr(status), ctypes.byref(res))
+        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -930,6 +963,47 @@ class Context:
             raise EntreepyError(res.first_status, f"field_packed: row {res.first_failed}")
         new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
         return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text), d_pos.cpu().numpy().view(np.uint32)
+
+    def concat_packed(self, codebook, a, sep, b, rows_a=None, rows_b=None):
+        """Two stores as decode_packed takes them -- a, b: (blob, out_index, lengths), or None for an absent side -- a literal and a
+        list of record numbers per side (None: row k is record k) -> a store like take_packed's: (the bodies of
+        text(a[rows_a[k]]) + sep + text(b[rows_b[k]]) back to back as bytes, their offsets, their lengths), as encode_packed of the
+        concatenated texts gives it, through one concat_packed_device call."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        stores, d_rows, counts, room = [], [], [], 0
+        for store, rows in ((a, rows_a), (b, rows_b)):
+            if store is None:
+                stores.append(None)
+                d_rows.append(None)
+                continue
+            blob, out_index, lengths = store
+            out_index = np.asarray(out_index, dtype=np.uint64)
+            lengths = np.asarray(lengths, dtype=np.uint64)
+            assert out_index.size == lengths.size + 1
+            text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+            d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+            stores.append((d_blob, d_body_index, torch.from_numpy(text_index.view(np.int64)).to(dev)))
+            rows = np.arange(lengths.size, dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+            d_rows.append(torch.from_numpy(rows.view(np.int32)).to(dev))
+            counts.append(rows.size)
+            good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none; a run is no longer than its record's body)
+            room += int((out_index[good + 1] - out_index[good]).sum())
+        assert counts and min(counts) == max(counts), "at least one side, and both sides give the same number of rows"
+        n_rows = counts[0]
+        if not n_rows:
+            return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        room += n_rows * (codebook.body_bound(len(bytes(sep))) + 1)  # (the literal's bits per row, and the byte a row rounds up to)
+        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
+        d_new_index = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        d_new_text = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        res = self.concat_packed_device(codebook, stores[0], sep, stores[1], d_out, d_new_index, d_new_text, rows_a=d_rows[0], rows_b=d_rows[1])
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"concat_packed: row {res.first_failed}")
+        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
+        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

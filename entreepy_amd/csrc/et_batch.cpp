@@ -29,6 +29,7 @@
 //   take          counters -> k_take_plan -> k_take_scan (poll) -> unless sizes only: k_take_copy
 //   slice         sorted codes + counters -> k_slice_plan -> k_slice_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
 //   field         sorted codes + counters -> k_field_plan -> k_field_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
+//   concat        sorted codes + counters + the encoded literal -> k_concat_plan -> k_concat_long -> k_take_scan (poll) -> unless sizes only: k_concat_copy
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -66,6 +67,7 @@ static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the p
 // table, the counters at PK_STATS for EVERY call, the match's pattern.  Behind the counters each call has its own layout:
 //   encode, gather   from PK_SIZES: a size word per record, or per row        take   from PK_SIZES: a TakeRow per row
 //   slice, field   from PK_SIZES: a TakeRow per row, then a list entry per row
+//   concat  the encoded literal at PK_PATTERN (it ends in front of PK_SIZES); from PK_SIZES: a TakeRow per row, a list entry per row, a ConcatPiece per row
 //   search  as the match, then a position and a list entry per record
 //   match   behind the pattern: the tile workspace (tile_ws)                   join   behind the counters: the tile workspace, the table's slots, a key number per record
 //   order   (the match's LESS modes) the sorted codes, the counters, the pattern, the boundary table behind the pattern's last word, the tile workspace
@@ -723,6 +725,80 @@ extern "C" int et_field_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     res->text_bytes = rep[et::TAKE_TEXT_BYTES];
     read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
     if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the fields need more than cap bytes");  // (k_take_copy saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_concat_sep_max(void) { return et::CONCAT_SEP_MAX; }
+
+extern "C" size_t et_concat_lane_bytes(void) { return et::CONCAT_LANE_BYTES; }
+
+static_assert(sizeof(et::ConcatPiece) == 32 && et::CONCAT_SEP_MAX * 4 <= et::SEARCH_PATTERN_BYTES && PK_PATTERN + et::SEARCH_PATTERN_BYTES <= PK_SIZES,
+              "k_concat_plan stores a ConcatPiece as 2 x 16 bytes; the encoded literal lies between the counters and the plan");
+
+extern "C" int et_concat_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_a_bodies, size_t a_body_bytes, const uint64_t *d_a_body_index,
+                                       const uint64_t *d_a_text_index, size_t n_a, const uint32_t *d_rows_a, const uint8_t *sep, size_t sep_len, const void *d_b_bodies,
+                                       size_t b_body_bytes, const uint64_t *d_b_body_index, const uint64_t *d_b_text_index, size_t n_b, const uint32_t *d_rows_b, size_t n_rows,
+                                       void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index, uint8_t *d_status, et_take_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_out_body_index || !d_out_text_index || (!sep && sep_len)) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (!d_a_bodies && !d_b_bodies) return fail(ctx, ET_ERR_ARG, "both sides are absent");
+    struct Side { const void *bodies; size_t body_bytes; const uint64_t *body_index, *text_index; size_t n; const uint32_t *rows; };
+    const Side sides[2] = {{d_a_bodies, a_body_bytes, d_a_body_index, d_a_text_index, n_a, d_rows_a}, {d_b_bodies, b_body_bytes, d_b_body_index, d_b_text_index, n_b, d_rows_b}};
+    if (misaligned(7, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many rows");
+    for (const Side &s : sides) {
+        if (!s.bodies) {  // an absent side: no records, no offsets (its rows are not looked at)
+            if (s.n || s.body_bytes || s.body_index || s.text_index) return fail(ctx, ET_ERR_ARG, "an absent side has no records, no bytes and no offset arrays");
+            continue;
+        }
+        if (!s.body_index || !s.text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+        if (misaligned(7, s.body_index, s.text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+        if (misaligned(3, s.rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+        if (s.n > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+        if (!s.rows && n_rows != s.n) return fail(ctx, ET_ERR_ARG, "without d_rows, row k is record k: n_rows must be that side's n");
+        if (d_out && cap && s.body_bytes) {  // (concatenating in place is not this call's)
+            const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(s.bodies);
+            if (o < b + s.body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps a side's bodies");
+        }
+    }
+    if (sep_len > et::CONCAT_SEP_MAX) return fail(ctx, ET_ERR_ARG, "the literal is longer than et_concat_sep_max()");
+    *res = et_take_result{};
+    if (n_rows == 0) return ET_OK;
+    ET_TRY(require_complete(ctx, cb));
+    uint8_t encoded[et::SEARCH_PATTERN_BYTES];
+    uint64_t bits = 0;
+    const int rc = et_encode_pattern(cb, sep, sep_len, encoded, sizeof(encoded), &bits);
+    if (rc != ET_OK) return fail(ctx, rc, "a byte of the literal has no code");
+    DeviceGuard guard(ctx->device);
+    // the slice's layout with the side array behind the list; the sorted codes, the counters' first values and the literal's bits lie
+    // one behind the other: up in one copy
+    Bump layout{PK_SIZES};
+    const size_t at_plan = layout.take(n_rows * sizeof(et::TakeRow), 16), at_list = layout.take(n_rows * 4, 4), at_pieces = layout.take(n_rows * sizeof(et::ConcatPiece), 16);
+    ET_TRY(packed_ensure(ctx, layout.end));
+    const uint32_t n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), false);
+    first_counters(ctx);
+    const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
+    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
+    std::memcpy(pattern, encoded, pat_bytes);
+    std::memset(pattern + pat_bytes, 0, padded - pat_bytes);
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_PATTERN + padded, hipMemcpyHostToDevice, ctx->stream));
+    et::ConcatJob job{};
+    job.rows_a = d_rows_a;
+    job.rows_b = d_rows_b;
+    job.sep = ws<const uint8_t>(ctx, PK_PATTERN);
+    job.n_rows = static_cast<uint32_t>(n_rows);
+    job.sep_bits = static_cast<uint32_t>(bits);
+    job.sep_len = static_cast<uint32_t>(sep_len);
+    const et::PackedReport report = next_report(ctx);
+    et::launch_concat(ctx->stream, et::PackedStore{d_a_bodies, a_body_bytes, d_a_body_index, d_a_text_index, static_cast<uint32_t>(n_a), 0},
+                      et::PackedStore{d_b_bodies, b_body_bytes, d_b_body_index, d_b_text_index, static_cast<uint32_t>(n_b), 0}, ws<const uint2>(ctx, 0), n_codes, job, d_out, cap,
+                      d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, at_plan), ws<uint32_t>(ctx, at_list), ws<et::ConcatPiece>(ctx, at_pieces), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the concat's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
+    res->out_bytes = rep[et::PACKED_BYTES];
+    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the rows need more than cap bytes");  // (k_concat_copy saw the same two figures)
     return ET_OK;
 }
 

@@ -329,4 +329,46 @@ struct FieldJob {
 void launch_field(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const FieldJob &job, void *d_out, uint64_t cap,
                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
 
+// The concat (et_concat_packed_device): row k = text(A[rows_a[k]]) + a literal + text(B[rows_b[k]]) as a NEW packed store -- under one
+// complete prefix-free table the body the encoder writes for x + y is the bits of x followed by the bits of y, so a row is three runs
+// of bits laid end to end: the left record's stored text (its pad dropped), the literal (et_encode_pattern, in the workspace), the
+// right record's stored text.  Both sides are walked to the end of their stored text, as the slice walks; the row's length is the
+// symbols of the three.  Either store may be absent (no bodies).
+//   k_concat_plan  k_slice_plan's frame over pairs of records: both judged as k_take_plan judges, the row's status byte (the left's
+//                  unless OK, else the right's, else PACKED_UNSUPPORTED for a new length above BATCH_SMALL_MAX); each side's body
+//                  (clip_body of its length) up to CONCAT_LANE_BYTES is walked by the row's lane to the end of its stored text; a row
+//                  with a longer one goes onto a list, that run absent for now; a TakeRow {new bytes, new length} and a ConcatPiece per row
+//   k_concat_long  one workgroup per listed row: the slice's counting walk to the end of each stored text the lane left, one after
+//                  the other; thread 0 completes the row's two records -- and fails the row where the length it found is above the limit
+//   k_take_scan    the take's, unchanged: its report is the call's
+//   k_concat_copy  (unless d_out is null: sizes only) k_take_copy's tiles, rows and stores; a row's bytes are the OR of its runs, each
+//                  a funnel shift of the source bytes that hold its bits to the destination BIT the run begins at
+// CONCAT_LANE_BYTES is the search's threshold, kept: the lane's walk is slice_lane itself; no sweep of its own.
+#ifndef ET_CONCAT_LANE_BYTES  // (a build for the sweep sets it, as ET_SEARCH_LANE_BYTES)
+#define ET_CONCAT_LANE_BYTES ET_SEARCH_LANE_BYTES
+#endif
+constexpr uint32_t CONCAT_LANE_BYTES = ET_CONCAT_LANE_BYTES;
+constexpr uint32_t CONCAT_SEP_MAX = SEARCH_NEEDLE_MAX;  // bytes of text in the literal: its bits take SEARCH_PATTERN_BYTES at most
+// Where a row's runs lie: 32 bytes, a 16-byte and an 8-byte load of k_concat_copy, four rows to a 128-byte line -- with the literal's
+// place known to the kernel, the row's bits are [0, a_bits) from a_bit, [a_bits, a_bits + sep_bits) the literal, then b_bits from b_bit.
+// Sources are ADDRESSES of bits (the byte's address * 8 + the bit, from the top): the two sides may be different stores.  The symbols
+// are what k_concat_long needs of a walk the lane has done.  A side not walked yet, or without a stored text, is all zeros.
+struct ConcatPiece {
+    uint64_t a_bit;          // the address of the left run's first bit
+    uint32_t a_bits, b_bits; // the two runs' bits
+    uint64_t b_bit;          // the address of the right run's first bit
+    uint32_t a_syms, b_syms; // the two stored texts' symbols
+};
+struct ConcatJob {
+    const uint32_t *rows_a, *rows_b;  // null: row k is record k of that side
+    const uint8_t *sep;               // the encoded literal on the device, zero-padded to a multiple of 4 bytes
+    uint32_t n_rows;
+    uint32_t sep_bits, sep_len;       // its bits; its bytes of text
+    uint32_t pad;
+};
+// codes, plan, long_list: as launch_slice's (the counters' word for the list is the slice's); pieces: n_rows ConcatPiece of workspace
+// (16-byte aligned).  a.bodies or b.bodies null: that side is absent.  The report leaves with the scan, in front of the copy.
+void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &b, const uint2 *codes, uint32_t n_codes, const ConcatJob &job, void *d_out, uint64_t cap,
+                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, ConcatPiece *pieces, const PackedReport &report);
+
 }  // namespace et

@@ -1768,6 +1768,7 @@ __device__ __forceinline__ uint64_t bit_span(uint64_t bit0, uint32_t c, uint32_t
 // and a row that owns a byte was judged by k_take_plan, so its TakeRow is believed.  LDS 8 KiB + 16 bytes.
 // BITS (the slice call): a row's source is a run of BITS -- TakeRow::src as k_slice_plan leaves it -- and a piece is bit_span's; the
 // tiles, the rows and the stores are the same, and d_bodies is not looked at.
+// (k_concat_copy below is a second copy of this frame with another piece: a fix to the frame belongs in both.)
 template <bool BITS>
 __global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_bodies, const TakeRow *__restrict__ plan, const uint64_t *__restrict__ out_index,
                                                   uint32_t n_rows, uint8_t *__restrict__ d_out, uint64_t cap) {
@@ -2276,6 +2277,251 @@ __global__ __launch_bounds__(BB) void k_field_long(PackedStore store, const uint
 }
 
 // --------------------------------------------------------------------------------
+// The concat call: row k of the new store is text(A[rows_a[k]]) + the literal + text(B[rows_b[k]]), text() the stored text.  Under one
+// complete prefix-free table the body the encoder writes for x + y is the bits of x followed by the bits of y, so a row is three runs
+// of BITS laid end to end: the left record's stored text (the slice's walk from symbol 0 to the end finds where its last codeword
+// ends; the pad is dropped), the literal (et_encode_pattern, in the workspace) and the right record's stored text, found the same
+// way.  The right run cannot be taken as the take takes a body, 8 * bytes bits and the length whole: behind a left run that ends
+// inside a byte its pad would spill into a byte the encoder does not write, and where its length does not end its text the row's own
+// pad would read as symbols.  k_take_scan lays the rows out; k_concat_copy writes them, each run shifted to the destination BIT it
+// begins at.
+// Every loop is bounded as the slice's are; k_concat_copy's as k_take_copy's.  No workgroup waits for another: k_concat_long stores
+// the two records of its own row (and, where the walked length fails the row, its status byte and two atomics) and nothing else.
+// --------------------------------------------------------------------------------
+// A side's record as the take judges it; an absent side (no bodies) contributes an OK record of nothing and is not looked at.
+__device__ __forceinline__ Judged judge_side(const PackedStore &store, const uint32_t *rows, uint32_t k) {
+    if (!store.bodies) return Judged{PACKED_OK, 0, 0, 0};
+    Judged rec = judge_record(store, rows ? rows[k] : k);
+    if (!rec.status && rec.nb > TAKE_BODY_MAX) rec.status = PACKED_UNSUPPORTED;
+    return rec;
+}
+
+// What the walks look at of a judged record with bytes and symbols, and who walks it.
+__device__ __forceinline__ BodyBits concat_body(const PackedStore &store, const Judged &rec) {
+    return body_bits_of(static_cast<const uint8_t *>(store.bodies), rec.b0, static_cast<uint32_t>(clip_body(rec.nb, rec.len)));
+}
+
+__device__ __forceinline__ bool concat_by_lane(const BodyBits &g) { return g.end_bit - g.first_bit <= CONCAT_LANE_BYTES * 8; }
+
+// A side's run: the ADDRESS of its stored text's first bit, its bits and its symbols; nothing until it is walked.
+struct ConcatRun {
+    uint64_t bit;
+    uint32_t bits, syms;
+};
+
+__device__ __forceinline__ ConcatRun concat_run(const BodyBits &g, const Sliced &sl) {
+    if (!sl.n) return ConcatRun{0, 0, 0};  // (no codeword ends inside the body: the empty stored text)
+    return ConcatRun{static_cast<uint64_t>(reinterpret_cast<uintptr_t>(g.words)) * 8 + sl.begin, sl.end - sl.begin, sl.n};
+}
+
+// The row's two records, from its status so far and its runs, and its status: a failed row, and one whose new length lies above the
+// limit (PACKED_UNSUPPORTED), is the empty record.
+__device__ __forceinline__ uint32_t concat_store(const ConcatJob &job, uint32_t k, uint32_t status, const ConcatRun &a, const ConcatRun &b, TakeRow *__restrict__ plan,
+                                                 ConcatPiece *__restrict__ pieces) {
+    const uint64_t len = static_cast<uint64_t>(a.syms) + job.sep_len + b.syms;
+    if (!status && len > BATCH_SMALL_MAX) status = PACKED_UNSUPPORTED;
+    uint4 row = make_uint4(0u, 0u, 0u, 0u), p0 = row, p1 = row;
+    if (!status) {
+        const uint64_t bits = static_cast<uint64_t>(a.bits) + job.sep_bits + b.bits;  // (three runs of at most 2^23 bits and a little)
+        row = make_uint4(static_cast<uint32_t>((bits + 7) >> 3), static_cast<uint32_t>(len), 0u, 0u);
+        p0 = make_uint4(static_cast<uint32_t>(a.bit), static_cast<uint32_t>(a.bit >> 32), a.bits, b.bits);
+        p1 = make_uint4(static_cast<uint32_t>(b.bit), static_cast<uint32_t>(b.bit >> 32), a.syms, b.syms);
+    }
+    reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow and ConcatPiece as they lie in memory)
+    reinterpret_cast<uint4 *>(pieces)[2 * k] = p0;
+    reinterpret_cast<uint4 *>(pieces)[2 * k + 1] = p1;
+    return status;
+}
+
+// k_concat_plan: k_slice_plan's frame over pairs of records.  The row's status is the left record's if that is not OK, else the
+// right's, else the new length's; a failed row is the empty record and neither of its bodies is read.  Each side's body (clip_body of
+// its whole length) up to CONCAT_LANE_BYTES is walked by the row's lane (slice_lane, from symbol 0 to the end, nothing cuts); a row
+// with a longer one goes onto long_list and that run counts as absent here: k_concat_long completes the row.  LDS 6 KiB + 8 words.
+__global__ __launch_bounds__(BB) void k_concat_plan(PackedStore a, PackedStore b, const uint2 *__restrict__ codes, uint32_t n_codes, ConcatJob job, TakeRow *__restrict__ plan,
+                                                    ConcatPiece *__restrict__ pieces, uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status,
+                                                    unsigned long long *__restrict__ stats) {
+    __shared__ CodeTables t;
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    const uint32_t lane = threadIdx.x & 63;
+    load_tables(t, codes, n_codes);
+    __syncthreads();
+    PackedTally tally;
+    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
+        bool is_long = false;
+        if (k < job.n_rows) {
+            const Judged ra = judge_side(a, job.rows_a, k), rb = judge_side(b, job.rows_b, k);
+            uint32_t status = ra.status ? ra.status : rb.status;
+            ConcatRun run_a{0, 0, 0}, run_b{0, 0, 0};
+#pragma unroll 1
+            for (int right = 0; right < 2 && !status; ++right) {
+                const Judged &rec = right ? rb : ra;
+                if (!rec.nb || !rec.len) continue;  // (a record kept raw, or empty, has the empty stored text)
+                const BodyBits g = concat_body(right ? b : a, rec);
+                if (!concat_by_lane(g)) {
+                    is_long = true;
+                    continue;
+                }
+                const ConcatRun run = concat_run(g, slice_lane(t, n_codes, g, SliceAsk{0u, static_cast<uint32_t>(rec.len)}, SLICE_NO_STOP));
+                if (right) run_b = run;
+                else run_a = run;
+            }
+            status = concat_store(job, k, status, run_a, run_b, plan, pieces);
+            if (status) is_long = false;  // (too long without its long runs already)
+            if (d_status) d_status[k] = static_cast<uint8_t>(status);
+            tally.note(k, status);
+        }
+        const unsigned long long longs = __ballot(is_long);
+        if (longs) {  // (the same for the whole wavefront)
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
+            at = __shfl(at, 0, 64);
+            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
+        }
+    }
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
+// k_concat_long: k_slice_long's shape over long_list: slice_stream from symbol 0 to the record's end, nothing cuts, for each side of
+// the row that k_concat_plan left to it -- one after the other, so a row has one writer.  Thread 0 completes the row's two records
+// from what k_concat_plan left of the other side; a row whose length the walks bring above the limit fails here -- the empty record,
+// its status byte, one tally -- for k_concat_plan held it for OK.  The scan runs behind this kernel.
+// LDS as k_batch_decode, and the reduction's 12 words.
+__global__ __launch_bounds__(BB) void k_concat_long(PackedStore a, PackedStore b, const uint2 *__restrict__ codes, uint32_t n_codes, ConcatJob job, TakeRow *__restrict__ plan,
+                                                    ConcatPiece *__restrict__ pieces, const uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status,
+                                                    unsigned long long *__restrict__ stats) {
+    __shared__ BatchDecLds s;
+    __shared__ unsigned long long s_red[3 * (BB / 64)];
+    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
+    if (blockIdx.x >= n_long) return;
+    load_tables(s.t, codes, n_codes);
+    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
+        const uint32_t k = long_list[i];
+        if (k >= job.n_rows) continue;  // (k_concat_plan lists rows; the same for every lane, like all below)
+        const Judged ra = judge_side(a, job.rows_a, k), rb = judge_side(b, job.rows_b, k);
+        if (ra.status || rb.status) continue;  // (k_concat_plan lists no such row)
+        const uint4 p0 = reinterpret_cast<const uint4 *>(pieces)[2 * k], p1 = reinterpret_cast<const uint4 *>(pieces)[2 * k + 1];  // what the lane has walked
+        ConcatRun run_a{static_cast<uint64_t>(p0.y) << 32 | p0.x, p0.z, p1.z}, run_b{static_cast<uint64_t>(p1.y) << 32 | p1.x, p0.w, p1.w};
+#pragma unroll 1
+        for (int right = 0; right < 2; ++right) {
+            const Judged &rec = right ? rb : ra;
+            if (!rec.nb || !rec.len) continue;
+            const BodyBits g = concat_body(right ? b : a, rec);
+            if (concat_by_lane(g)) continue;
+            const ConcatRun run = concat_run(g, slice_stream(s, n_codes, g, SliceAsk{0u, static_cast<uint32_t>(rec.len)}, SLICE_NO_STOP, s_red));
+            if (right) run_b = run;
+            else run_a = run;
+        }
+        if (threadIdx.x == 0) {
+            const uint32_t status = concat_store(job, k, PACKED_OK, run_a, run_b, plan, pieces);
+            if (status) {
+                if (d_status) d_status[k] = static_cast<uint8_t>(status);
+                PackedTally tally;
+                tally.note(k, status);
+                tally.add_to(stats);
+            }
+        }
+    }
+}
+
+// `n` bits (1 .. 64) from bit address `bit` on (a byte's address * 8 + the bit, from the top), the first at the top of the word and
+// zeros behind the last: from the 1 .. 9 bytes that hold one of them (span_word: no aligned word without such a byte is loaded).
+__device__ __forceinline__ uint64_t bits_at(uint64_t bit, uint32_t n) {
+    const uint32_t sh = static_cast<uint32_t>(bit & 7), nb = (sh + n + 7) >> 3;
+    const uintptr_t a = static_cast<uintptr_t>(bit >> 3);
+    uint64_t v = __builtin_bswap64(span_word(a, nb < 8 ? nb : 8u)) << sh;
+    if (nb > 8) v |= span_word(a + 8, 1) >> (8 - sh);  // (sh > 0 here: the ninth byte's first sh bits)
+    if (n < 64) v &= ~0ull << (64 - n);
+    return v;
+}
+
+// What a run -- the row's bits [r0, r1), which lie at bit address `src` on -- gives to the row's bits [q, qe), qe - q <= 64: its bits
+// among them at their places counted from the top, zeros elsewhere.  Nothing is loaded in front of the run's first bit or behind its last.
+__device__ __forceinline__ uint64_t run_bits(uint64_t src, uint32_t r0, uint32_t r1, uint32_t q, uint32_t qe) {
+    const uint32_t lo = q > r0 ? q : r0, hi = qe < r1 ? qe : r1;
+    if (lo >= hi) return 0ull;
+    return bits_at(src + (lo - r0), hi - lo) >> (lo - q);
+}
+
+// k_concat_copy: k_take_copy's frame -- its tiles, its rows (wg_upper_bound, the TAKE_STAGE_ROWS stretch in LDS), its words and its
+// stores, kept apart from it so that the take's two instantiations keep their code (a fix to the frame belongs in both).  What differs is the piece: `c` bytes (1 .. 8) of a
+// row from its bit q on are the OR of up to three runs -- the left bits, the literal's, the right bits -- each shifted to the bit it
+// begins at and masked to its own bits (run_bits); behind the last run the row's last byte keeps zeros, the encoder's pad.  A row's
+// runs come from its ConcatPiece (a 16-byte and an 8-byte load).  LDS 8 KiB + 16 bytes.
+__global__ __launch_bounds__(BB) void k_concat_copy(const ConcatPiece *__restrict__ pieces, const uint8_t *__restrict__ sep, uint32_t sep_bits,
+                                                    const uint64_t *__restrict__ out_index, uint32_t n_rows, uint8_t *__restrict__ d_out, uint64_t cap) {
+    __shared__ uint64_t s_idx[TAKE_STAGE_ROWS];
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t total = out_index[n_rows];
+    if (total > cap || total == 0) return;
+    const uintptr_t out = reinterpret_cast<uintptr_t>(d_out);
+    const uint64_t sep_bit = static_cast<uint64_t>(reinterpret_cast<uintptr_t>(sep)) * 8;
+    const uint64_t skew = out & (TAKE_TILE_BYTES - 1);  // bytes of tile 0 in front of d_out
+    const uint64_t n_tiles = (skew + total + TAKE_TILE_BYTES - 1) / TAKE_TILE_BYTES;
+    const uint64_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
+    const uint64_t t_begin = blockIdx.x * per, t_end = t_begin + per < n_tiles ? t_begin + per : n_tiles;
+    uint32_t hint = 0;  // every entry of out_index in front of it is at most the tile's first offset
+    for (uint64_t t = t_begin; t < t_end; ++t) {
+        const uint64_t o0 = t ? t * TAKE_TILE_BYTES - skew : 0, o1_full = (t + 1) * TAKE_TILE_BYTES - skew, o1 = o1_full < total ? o1_full : total;
+        const uint32_t row_lo = wg_upper_bound(out_index, hint, n_rows + 1, o0, s_cnt) - 1;
+        const uint32_t row_end = wg_upper_bound(out_index, row_lo + 1, n_rows + 1, o1 - 1, s_cnt);
+        hint = row_end;
+        const uint32_t entries = row_end - row_lo + 1;
+        const bool staged = entries <= TAKE_STAGE_ROWS;  // (the same for every thread)
+        if (staged)
+            for (uint32_t i = tid; i < entries; i += BB) s_idx[i] = out_index[row_lo + i];
+        __syncthreads();
+        auto idx = [&](uint32_t r) -> uint64_t { return staged ? s_idx[r - row_lo] : out_index[r]; };  // r in [row_lo, row_end]
+        const uintptr_t tile_addr = (out - skew) + t * TAKE_TILE_BYTES;
+#pragma unroll
+        for (uint32_t j = 0; j < TAKE_TILE_BYTES / (16 * BB); ++j) {
+            const uintptr_t aw = tile_addr + (j * BB + tid) * 16;
+            const int64_t rel = static_cast<int64_t>(aw) - static_cast<int64_t>(out);  // the word's first byte as an offset: negative in front of d_out
+            if (rel + 16 <= 0 || rel >= static_cast<int64_t>(total)) continue;
+            const uint64_t w0 = rel < 0 ? 0 : static_cast<uint64_t>(rel), w1 = static_cast<uint64_t>(rel + 16) < total ? static_cast<uint64_t>(rel + 16) : total;
+            uint32_t k = row_lo, hi = row_end;
+            while (hi - k > 1) {
+                const uint32_t mid = k + (hi - k) / 2;
+                if (idx(mid) <= w0) k = mid;
+                else hi = mid;
+            }
+            uint64_t v0 = 0, v1 = 0, pos = w0;
+            for (int trip = 0; trip < 16; ++trip) {  // row k owns byte pos: out_index[k] <= pos < out_index[k + 1]
+                const uint64_t s = idx(k), e = idx(k + 1), piece_end = e < w1 ? e : w1;
+                const uint32_t c = static_cast<uint32_t>(piece_end - pos);  // 1 .. 16
+                const uint32_t d = static_cast<uint32_t>(static_cast<int64_t>(pos) - rel);
+                const uint4 p0 = reinterpret_cast<const uint4 *>(pieces)[2 * k];
+                const uint2 p1 = reinterpret_cast<const uint2 *>(pieces)[4 * k + 2];
+                const uint64_t a_bit = static_cast<uint64_t>(p0.y) << 32 | p0.x, b_bit = static_cast<uint64_t>(p1.y) << 32 | p1.x;
+                const uint32_t r1 = p0.z, r2 = r1 + sep_bits, r3 = r2 + p0.w;  // where the runs end, in bits of the row
+                const uint32_t q = static_cast<uint32_t>(pos - s) * 8, qm = q + 8 * (c < 8 ? c : 8u), qe = q + 8 * c;
+                put_bytes(v0, v1, __builtin_bswap64(run_bits(a_bit, 0u, r1, q, qm) | run_bits(sep_bit, r1, r2, q, qm) | run_bits(b_bit, r2, r3, q, qm)), d);
+                if (c > 8) put_bytes(v0, v1, __builtin_bswap64(run_bits(a_bit, 0u, r1, qm, qe) | run_bits(sep_bit, r1, r2, qm, qe) | run_bits(b_bit, r2, r3, qm, qe)), d + 8);
+                pos = piece_end;
+                if (pos >= w1) break;
+                ++k;  // (a row behind owns byte pos < o1: k < row_end)
+                if (idx(k + 1) <= pos) {  // empty rows follow: the last r in [k, row_end) with out_index[r] <= pos
+                    hi = row_end;
+                    while (hi - k > 1) {
+                        const uint32_t mid = k + (hi - k) / 2;
+                        if (idx(mid) <= pos) k = mid;
+                        else hi = mid;
+                    }
+                }
+            }
+            if (w1 - w0 == 16) {
+                *reinterpret_cast<uint4 *>(aw) = make_uint4(static_cast<uint32_t>(v0), static_cast<uint32_t>(v0 >> 32), static_cast<uint32_t>(v1), static_cast<uint32_t>(v1 >> 32));
+            } else {  // the output's first or last word: its own bytes alone
+                for (uint32_t i = static_cast<uint32_t>(static_cast<int64_t>(w0) - rel); i < static_cast<uint32_t>(static_cast<int64_t>(w1) - rel); ++i)
+                    reinterpret_cast<uint8_t *>(aw)[i] = static_cast<uint8_t>((i < 8 ? v0 >> (8 * i) : v1 >> (8 * (i - 8))) & 0xffu);
+            }
+        }
+        __syncthreads();  // (s_idx: between two tiles)
+    }
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
 
 static uint32_t capped(uint64_t n, uint32_t most) { return n < most ? static_cast<uint32_t>(n) : most; }
@@ -2334,6 +2580,19 @@ void launch_field(hipStream_t stream, const PackedStore &store, const uint2 *cod
     if (!d_out) return;
     hipLaunchKernelGGL(k_take_copy<true>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(nullptr),
                        static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+}
+
+void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &b, const uint2 *codes, uint32_t n_codes, const ConcatJob &job, void *d_out, uint64_t cap,
+                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, ConcatPiece *pieces, const PackedReport &r) {
+    const uint32_t n_rows = job.n_rows;
+    hipLaunchKernelGGL(k_concat_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, a, b, codes, n_codes, job, plan, pieces, long_list, d_status, r.stats);
+    hipLaunchKernelGGL(k_concat_long, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, a, b, codes, n_codes, job, plan, pieces, static_cast<const uint32_t *>(long_list),
+                       d_status, r.stats);
+    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
+                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
+    if (!d_out) return;
+    hipLaunchKernelGGL(k_concat_copy, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const ConcatPiece *>(pieces), job.sep, job.sep_bits,
+                       static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
 }
 
 void launch_join(hipStream_t stream, const PackedStore &records, const PackedStore &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,

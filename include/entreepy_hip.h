@@ -702,6 +702,66 @@ int et_field_packed_device(et_ctx *ctx, const et_codebook *cb,
                            uint32_t *d_pos,
                            uint8_t *d_status, et_take_result *res);
 
+/* CONCAT: ROW-WISE STRING CONCATENATION as a NEW packed store, on the device, nothing decoded and nothing encoded again --
+ * last || ',' || first as a join key, id re-keyed as user=<id>, columns 0 and 3 of a CSV line put back together: the one call that
+ * builds a record from parts.  Under one complete prefix-free table the body the encoder writes for x + y is the bits of x followed
+ * by the bits of y, so a row is three runs of bits -- a stored text's, a literal's, a stored text's -- laid end to end: field -> concat -> join runs on
+ * one ctx with no text in between.  (Appending stores, UNION ALL, is a different thing and not this call's.)
+ *   Row k of the new store is text(A[rows_a[k]]) + sep + text(B[rows_b[k]]), text() the stored text as every packed call defines it:
+ *     the first min(length, codewords that end inside the body) symbols.  Both stores are the take call's, under the one table cb; A
+ *     and B may be the same store.  Either side may be ABSENT: d_x_bodies == NULL, with n_x == 0, x_body_bytes == 0 and null offset
+ *     arrays (its d_rows is not looked at); it contributes nothing to any row.  An absent left side with a literal prefixes every
+ *     record, an absent right side suffixes it.  At least one side is present.
+ *   d_rows_a[k], d_rows_b[k] (32 bits each, 4-byte aligned, on the device; any order, repeats allowed): the record of that side in
+ *     row k.  d_rows_x == NULL: row k is record k of that side, and n_rows must equal n_x.
+ *   sep (HOST memory, sep_len <= et_concat_sep_max() bytes; may be empty): the literal between the two, encoded once on the host by
+ *     et_encode_pattern.
+ *   How the pieces are laid: three runs of bits, end to end.  LEFT: its stored text's bits, found by the slice's walk from symbol 0
+ *     to the end, nothing cutting; the pad behind its last codeword is dropped, set or not.  LITERAL: et_encode_pattern's bits.
+ *     RIGHT: its stored text's bits, found the same way -- NOT its body as the take would take it: 8 * bytes bits behind a run that
+ *     ends inside a byte would push its pad into a byte the encoder does not write, and a length that does not end its text (a body
+ *     cut short, a record kept raw) would let the row's own pad read as symbols.  A record kept raw (no bytes, a length above 0) has
+ *     the empty stored text on either side, as in the slice.  Hence, for EVERY input: d_out[out_body_index[k], out_body_index[k+1])
+ *     holds exactly the bytes et_encode_packed_device writes for the concatenation of the three stored texts under cb --
+ *     ceil(bits / 8) bytes, MSB-first from bit 7, the pad bits zero whatever the sources' are -- and the new record's stored text is
+ *     that concatenation.
+ *   Sizes: out_text_index advances by symbols(A) + sep_len + symbols(B) per row, out_body_index by
+ *     ceil((bits(A) + sep_bits + bits(B)) / 8), symbols() and bits() the stored text's.  Both arrays have n_rows + 1 entries (8-byte
+ *     aligned, on the device) and begin with 0; the bodies lie back to back.
+ *   d_status[k] (one et_status byte per ROW; may be NULL): each side's record is judged as the take call judges a row (ET_ERR_ARG
+ *     for a number beyond that store or a bad pair of offsets, ET_ERR_UNSUPPORTED for a length above the small-stream limit or a body
+ *     above 4 * et_batch_small_max() bytes); the row's status is the left record's if that is not ET_OK, else the right's, else
+ *     ET_ERR_UNSUPPORTED when the new length exceeds et_batch_small_max() -- the output stays a store every packed call accepts.  A
+ *     failed row is the EMPTY record, fails alone and is tallied once; no byte is read where its pairs point.
+ *   *res is the take call's, as the slice reports it: out_bytes, text_bytes (the sum of the new lengths), n_failed, first_failed,
+ *     first_status.  Nothing outside [d_out, d_out + out_body_index[n_rows]) is written, at any alignment of d_out and of the bodies.
+ *     d_out == NULL: sizes only -- both output arrays, d_status and *res are the writing call's; cap is ignored.
+ *     out_body_index[n_rows] > cap: ET_ERR_CAP, not a byte of d_out is written; both output arrays and d_status are complete and
+ *     res->out_bytes is the room needed.
+ *   et_concat_lane_bytes(): a body of either side (min(body bytes, 4 * length + 8)) up to this many bytes is walked by one lane, a
+ *     longer one by a workgroup (the slice's threshold, kept) -- for tests that want rows on both sides; the answer does not depend on it.
+ * Out of scope: more than two store sides per call (chain the call); per-row literals; appending stores (UNION ALL); concatenating in
+ * place -- [d_out, d_out + cap) may overlap neither side's bodies --; records above the limits named above.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_out_body_index or d_out_text_index; both sides absent; an absent side with
+ * records, bytes or offset arrays; a present side with a null offset array, an offset array that is not 8-byte aligned, d_rows not
+ * 4-byte aligned, n above 0x7fffffff, or d_rows == NULL with n_rows != n; n_rows above 0x7fffffff; d_out overlapping either side's
+ * bodies; sep_len > et_concat_sep_max(); sep == NULL with sep_len > 0 -- all checked before anything touches a device, *res
+ * untouched), ET_ERR_UNSUPPORTED (the table is not complete, or a byte of the literal has no code: nothing is enqueued), ET_ERR_CAP,
+ * ET_ERR_HIP, ET_ERR_NOMEM.  n_rows == 0: ET_OK, nothing enqueued, *res zeroed.  One upload (the sorted codes, zeroed counters and the
+ * encoded literal, 3.1 KiB at most), four launches -- three without d_out -- and one hand-over per call; stream-ordered like the other packed calls -- *res is final on return, the device arrays once the ctx's stream
+ * has drained -- and it may follow or precede any of them on one ctx with nothing in between. */
+size_t et_concat_sep_max(void);             /* 256, the search's needle limit: the encoded literal is at most 1 KiB */
+size_t et_concat_lane_bytes(void);          /* a body (min(body bytes, 4 * length + 8)) up to this is walked by one lane */
+int et_concat_packed_device(et_ctx *ctx, const et_codebook *cb,
+                            const void *d_a_bodies, size_t a_body_bytes, const uint64_t *d_a_body_index,
+                            const uint64_t *d_a_text_index, size_t n_a, const uint32_t *d_rows_a,
+                            const uint8_t *sep, size_t sep_len,
+                            const void *d_b_bodies, size_t b_body_bytes, const uint64_t *d_b_body_index,
+                            const uint64_t *d_b_text_index, size_t n_b, const uint32_t *d_rows_b,
+                            size_t n_rows,
+                            void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
+                            uint8_t *d_status, et_take_result *res);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

@@ -64,7 +64,7 @@ process of its own so that every leg loads exactly one build of the library:
   field           et_field_packed_device (field k of the pages split at spaces, of 10 % of the rows; fields 0, 3 and 7 of 262 144 CSV lines, of
                   all rows and of 10 %) against what it replaces: a decode (or gather) of the rows' records and et_encode_packed_device of
                   the cut text; the slice up to the delimiter on the same rows and the search's walk over the store as floors
---legs picks the legs (default: all but search_sweep).
+--legs picks the legs (default: all but search_sweep and concat).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
 text once before timing.  One JSON line on stdout (and into --out).
@@ -80,6 +80,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs order --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/order_bench.json
     python tools/batch_bench.py --legs slice --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/slice_bench.json
     python tools/batch_bench.py --legs field --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/field_bench.json
+    python tools/batch_bench.py --legs concat --out profiles/concat_bench.json
 """
 import argparse
 import ctypes
@@ -1063,6 +1064,120 @@ def _field_leg(leg, lib_path, shapes):
     print(json.dumps(results))
 
 
+def _concat_leg(lib_path, shapes):
+    """concat: on the 262 144 CSV lines the stores of field 0 and of field 3 (et_field_packed_device, untimed), then field0 + "," +
+    field3 of every row and of 10 % of the rows, and "user=" + field0 of every row (no left side); on 4 096 x 4 KiB two selections of
+    10 % of the records with nothing between them (the workgroup's walk on both sides).  Per case et_concat_packed_device, its bytes
+    and offsets checked against the other route's, beside it the sizes-only call -- and, in the same process, the route it replaces:
+    et_decode_packed_device (et_decode_packed_gather_device where the rows are a selection) of both sides, the concatenated text and
+    its offsets built with torch on the device, et_encode_packed_device."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device", "et_decode_packed_gather_device", "et_field_packed_device", "et_concat_packed_device", "et_concat_lane_bytes"])
+    results = {"lane_bytes": int(L.et_concat_lane_bytes())}
+    res, tres = N.PackedResult(), N.TakeResult()
+
+    def store_of(text, index, cb=None):
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, text, index, cb)
+        return cb, (bodies, body_bytes, body_index, text_index, index.size - 1)
+
+    def field_of(cb, st, field):  # -> the store of one field of every record
+        bodies, body_bytes, body_index, text_index, n = st
+        out = torch.zeros(body_bytes + 64, dtype=torch.uint8, device=dev)
+        bi, ti = (torch.zeros(n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+        assert L.et_field_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, None, n, None, field, None, 1, ord(","),
+                                        out.data_ptr(), body_bytes, bi.data_ptr(), ti.data_ptr(), None, None, ctypes.byref(tres)) == 0 and tres.n_failed == 0, L.et_last_error(h)
+        torch.cuda.synchronize()
+        return out, int(tres.out_bytes), bi, ti, n
+
+    def lengths_of(st, d_rows):
+        text_index = st[3]
+        if d_rows is None:
+            return text_index[1:] - text_index[:-1]
+        rows = d_rows.to(torch.int64)
+        return text_index[rows + 1] - text_index[rows]
+
+    def decode(cb, st, d_rows, n_rows, room):  # -> the rows' texts back to back, on the device
+        bodies, body_bytes, body_index, text_index, n = st
+        dec = torch.empty(room + 64, dtype=torch.uint8, device=dev)
+        if d_rows is None:
+            assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, dec.data_ptr(), room, None, None,
+                                             ctypes.byref(res)) == 0, L.et_last_error(h)
+        else:
+            at = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+            assert L.et_decode_packed_gather_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, d_rows.data_ptr(), n_rows,
+                                                    dec.data_ptr(), room, at.data_ptr(), None, None, ctypes.byref(res)) == 0, L.et_last_error(h)
+        assert res.out_bytes == room and res.n_failed == 0 and res.n_short == 0
+        return dec
+
+    def case(cb, A, B, rows_a, rows_b, sep, n_rows):
+        d_rows = [None if r is None else torch.from_numpy(r.view(np.int32).copy()).to(dev) for r in (rows_a, rows_b)]
+        sep_t = torch.from_numpy(np.frombuffer(sep, np.uint8).copy()).to(dev)
+        room_out = sum(st[1] for st in (A, B) if st is not None) + n_rows * (len(sep) * 4 + 1)  # (a bound: whole stores, a literal of 32-bit codes)
+        outs = [torch.zeros(room_out + 64, dtype=torch.uint8, device=dev) for _ in range(2)]
+        idx = [[torch.zeros(n_rows + 1, dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(2)]
+        side = lambda st, r: ([None, 0, None, None, 0, None] if st is None else [st[0].data_ptr(), st[1], st[2].data_ptr(), st[3].data_ptr(), st[4], None if r is None else r.data_ptr()])  # noqa: E731
+
+        def call(d_out=outs[0]):
+            assert L.et_concat_packed_device(h, ctypes.byref(cb), *side(A, d_rows[0]), sep, len(sep), *side(B, d_rows[1]), n_rows, None if d_out is None else d_out.data_ptr(), room_out,
+                                             idx[0][0].data_ptr(), idx[0][1].data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+            assert tres.n_failed == 0
+
+        rooms = [0 if st is None else int(lengths_of(st, r).sum()) for st, r in ((A, d_rows[0]), (B, d_rows[1]))]  # (known to the caller: not part of the route)
+        total = sum(rooms) + n_rows * len(sep)
+
+        def baseline():
+            zero = torch.zeros(n_rows, dtype=torch.int64, device=dev)
+            len_a, len_b = (zero if st is None else lengths_of(st, r) for st, r in ((A, d_rows[0]), (B, d_rows[1])))
+            new_index = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(len_a + len(sep) + len_b, 0, out=new_index[1:])
+            text = torch.empty(total + 64, dtype=torch.uint8, device=dev)
+            for st, r, room, lengths, shift in ((A, d_rows[0], rooms[0], len_a, new_index[:-1]), (B, d_rows[1], rooms[1], len_b, new_index[:-1] + len_a + len(sep))):
+                if st is not None:  # byte i of the decoded side belongs to row[i]: it moves by where that row's part begins now less where it began
+                    dec = decode(cb, st, r, n_rows, room)
+                    row = torch.repeat_interleave(torch.arange(n_rows, device=dev), lengths, output_size=room)
+                    text[torch.arange(room, device=dev) + (shift - (torch.cumsum(lengths, 0) - lengths))[row]] = dec[:room]
+            if len(sep):
+                text[((new_index[:-1] + len_a)[:, None] + torch.arange(len(sep), device=dev)[None, :]).reshape(-1)] = sep_t.repeat(n_rows)
+            assert L.et_encode_packed_device(h, ctypes.byref(cb), text.data_ptr(), total, new_index.data_ptr(), n_rows, outs[1].data_ptr(), room_out, idx[1][0].data_ptr(), None,
+                                             ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+
+        call()
+        baseline()
+        torch.cuda.synchronize()
+        need = int(tres.out_bytes)
+        assert need == int(res.out_bytes) and torch.equal(outs[0][:need], outs[1][:need]) and torch.equal(idx[0][0], idx[1][0]), "the two routes differ"
+        entry = {"rows": int(n_rows), "bytes": need, "text_bytes": int(tres.text_bytes)}
+        entry.update(_timed(call))
+        entry["sizes_only"] = _timed(lambda: call(None))
+        entry["baseline"] = _timed(baseline)
+        gap, spreads = entry["baseline"]["ms"] - entry["ms"], (entry["baseline"]["max_ms"] - entry["baseline"]["min_ms"]) + (entry["max_ms"] - entry["min_ms"])
+        entry["baseline_over_concat"], entry["beyond_both_spreads"] = round(entry["baseline"]["ms"] / entry["ms"], 2), bool(gap > spreads)
+        return entry
+
+    count = CSV_SHAPE[0]
+    if not shapes or f"{count}xcsv" in shapes:
+        host, index = _csv_store(count)
+        cb, lines = store_of(torch.from_numpy(host).to(dev), index, _codebook(L, [host, np.frombuffer(b"user=", np.uint8)]))
+        f0, f3 = field_of(cb, lines, 0), field_of(cb, lines, 3)
+        tenth = np.sort(np.random.default_rng(0xC07CA7 + count).choice(count, size=count // 10, replace=False)).astype(np.uint32)
+        results[f"{count}xcsv"] = {"records": count, "field0_comma_field3_all": case(cb, f0, f3, None, None, b",", count),
+                                   "field0_comma_field3_tenth": case(cb, f0, f3, tenth, tenth, b",", tenth.size), "user_prefix_field0_all": case(cb, None, f0, None, None, b"user=", count)}
+        del lines, f0, f3
+    count, size = SHAPES[1]
+    if not shapes or f"{count}x{size}" in shapes:
+        host, index, _, _ = _search_store(count, size, 0.1)
+        cb, pages = store_of(torch.from_numpy(host).to(dev), index, _codebook(L, [host]))
+        rng = np.random.default_rng(0xC07CA8 + count)
+        rows_a, rows_b = (np.sort(rng.choice(count, size=count // 10, replace=False)).astype(np.uint32) for _ in range(2))
+        results[f"{count}x{size}"] = {"records": count, "two_selections_tenth": case(cb, pages, pages, rows_a, rows_b, b"", rows_a.size)}
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
@@ -1087,6 +1202,8 @@ def main():
         return _slice_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg and a.leg.startswith("field"):
         return _field_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
+    if a.leg == "concat":
+        return _concat_leg(a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -1110,6 +1227,8 @@ def main():
         legs += [("slice_baseline", "slice_baseline", a.batch_lib or here), ("slice", "slice", here)]
     if "field" in a.legs.split(","):
         legs += [("field_baseline", "field_baseline", a.batch_lib or here), ("field", "field", here)]
+    if "concat" in a.legs.split(","):  # (the baseline runs in the leg's own process, on this build)
+        legs += [("concat", "concat", here)]
     if "search_sweep" in a.legs.split(","):
         legs += [("search_sweep", "search_sweep", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
@@ -1170,6 +1289,8 @@ def main():
                 out["field_vs_baseline"][k][name] = {"baseline_over_field": round(old["ms"] / new["ms"], 2),
                                                      "beyond_both_spreads": old["ms"] - new["ms"] > (old["max_ms"] - old["min_ms"]) + (new["max_ms"] - new["min_ms"])}
         out["field_condition_met"] = all(e["beyond_both_spreads"] for v in out["field_vs_baseline"].values() for e in v.values())
+    if "concat" in out:
+        out["concat_condition_met"] = all(e["beyond_both_spreads"] for v in out["concat"].values() if isinstance(v, dict) for e in v.values() if isinstance(e, dict))
     line = json.dumps(out)
     print(line)
     if a.out:
