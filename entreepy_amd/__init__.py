@@ -5,6 +5,8 @@ The package is a thin host-side mirror of the reference's codec interface
 declared in include/entreepy_hip.h.  No CPU fallback exists.
 """
 from .codec import (  # noqa: F401
+    ASCII_LOWER,
+    ASCII_UPPER,
     Codebook,
     Context,
     DecodeFlags,
@@ -21,11 +23,13 @@ from .codec import (  # noqa: F401
     MATCH_PREFIX,
     MatchResult,
     PackedResult,
+    RECODE_DROP,
     SEARCH_CONTAINS,
     SEARCH_SUFFIX,
     SLICE_NO_STOP,
     SLICE_TO_END,
     TakeResult,
+    byte_map,
     decode,
     default_context,
     encode,

@@ -118,6 +118,7 @@ ET_MATCH_EQUAL, ET_MATCH_PREFIX, ET_MATCH_NOT = 0, 1, 0x100  # et_match_packed_d
 ET_MATCH_LESS, ET_MATCH_LESS_EQUAL = 4, 5  # ... its order modes (2 and 3 are none)
 ET_SEARCH_CONTAINS, ET_SEARCH_SUFFIX = 0, 1  # et_search_packed_device's mode; ET_MATCH_NOT may be or-ed in
 ET_SLICE_TO_END, ET_SLICE_NO_STOP = 0xFFFFFFFF, -1  # et_slice_packed_device: a count that means "to the end"; no stop byte
+ET_RECODE_DROP = -1  # et_recode_packed_device: the map entry of a byte that is deleted
 ET_FIELD_TO_END, ET_FIELD_ABSENT = 0xFFFFFFFF, 0xFFFFFFFF  # et_field_packed_device: "every field from here on"; the position of a field that is not there
 
 
@@ -222,6 +223,8 @@ SIGNATURES = {
     "et_concat_lane_bytes": (_sz, []),
     "et_concat_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
                                                ctypes.POINTER(TakeResult)]),
+    "et_recode_lane_bytes": (_sz, []),
+    "et_recode_packed_device": (ctypes.c_int, [_vp, _cbp, _cbp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(TakeResult)]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),

@@ -91,6 +91,21 @@ MATCH_EQUAL, MATCH_PREFIX, MATCH_NOT =N.ET_MATCH_EQUAL, N.ET_MATCH_PREFIX, N.ET_
 MATCH_LESS, MATCH_LESS_EQUAL = N.ET_MATCH_LESS, N.ET_MATCH_LESS_EQUAL  # ... its order modes: text < needle, text <= needle (with MATCH_NOT: >=, >)
 SEARCH_CONTAINS, SEARCH_SUFFIX = N.ET_SEARCH_CONTAINS, N.ET_SEARCH_SUFFIX  # search_packed_device's mode; MATCH_NOT may be or-ed in
 SLICE_TO_END, SLICE_NO_STOP = N.ET_SLICE_TO_END, N.ET_SLICE_NO_STOP  # slice_packed_device: a count "to the end"; no stop byte
+RECODE_DROP = N.ET_RECODE_DROP  # recode_packed_device: the map entry of a byte that is deleted
+
+
+def byte_map(frm=b"", to=b"", delete=b""):
+    """bytes.maketrans(frm, to) plus deletions, as recode_packed_device takes a map: 256 int16 values, entry c the byte that c becomes,
+    RECODE_DROP for the bytes of `delete` -- text.translate(bytes.maketrans(frm, to), delete), one byte to one byte or to none."""
+    m = np.frombuffer(bytes.maketrans(bytes(frm), bytes(to)), dtype=np.uint8).astype(np.int16)
+    m[np.frombuffer(bytes(delete), dtype=np.uint8)] = RECODE_DROP
+    return m
+
+
+ASCII_UPPER = byte_map(bytes(range(ord("a"), ord("z") + 1)), bytes(range(ord("A"), ord("Z") + 1)))  # bytes.upper(): a-z alone
+ASCII_LOWER = byte_map(bytes(range(ord("A"), ord("Z") + 1)), bytes(range(ord("a"), ord("z") + 1)))  # bytes.lower(): A-Z alone
+for _m in (ASCII_UPPER, ASCII_LOWER):
+    _m.setflags(write=False)
 FIELD_TO_END, FIELD_ABSENT = N.ET_FIELD_TO_END, N.ET_FIELD_ABSENT  # field_packed_device: "every field from here on"; pos of a field that is not there
 
 
@@ -720,6 +735,35 @@ class Context:
                                              self._opt_ptr(status), ctypes.byref(res))
         return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
 
+    def recode_packed_device(self, codebook_in, codebook_out, bodies, body_index, text_index, rows, out, out_body_index, out_text_index, byte_map=None, status=None):
+        """Row k of the NEW store is the stored text of record rows[k] of the store (bodies, body_index, text_index:
+        take_packed_device's, written under `codebook_in`; rows=None: row k is record k) sent through `byte_map` and written under
+        `codebook_out` -- text.translate(table, delete) and a change of table in one pass over the compressed bytes, no text in
+        between: its body, as encode_packed_device would write it under codebook_out, goes to
+        out[out_body_index[k] : out_body_index[k + 1]], and out_text_index[k + 1] - out_text_index[k] is its length.  byte_map: None
+        (the identity), or 256 integers (byte_map(), ASCII_UPPER, ASCII_LOWER): entry c is the byte c becomes, RECODE_DROP deletes it.
+        codebook_out may be codebook_in; the identity under one table normalises the store (pad bits cleared, lengths cut to what the
+        bodies hold).  A row fails -- the empty record -- as slice_packed_device's rows do, or with ET_ERR_UNSUPPORTED where a kept byte
+        of its stored text has no code under codebook_out.  status: optional uint8 CUDA tensor of one et_status byte per ROW.
+        out=None: sizes only.  out may not overlap bodies.  -> TakeResult; .status is ET_OK or ET_ERR_CAP (nothing written,
+        .out_bytes = the room needed); any other failure of the call raises.  Stream-ordered like take_packed_device."""
+        n = text_index.numel() - 1
+        n_rows = n if rows is None else rows.numel()
+        map_p = None
+        if byte_map is not None:
+            wide = np.asarray(byte_map)
+            assert wide.shape == (256,) and wide.dtype.kind in "iu", "byte_map holds 256 integers"
+            assert ((wide >= -32768) & (wide <= 32767)).all(), "a map entry is a byte, or RECODE_DROP"  # (what does not fit 16 bits is no byte either)
+            map_a = np.ascontiguousarray(wide, dtype=np.int16)
+            map_p = map_a.ctypes.data_as(ctypes.c_void_p)
+        res = N.TakeResult()
+        self._bind()
+        rc = N.lib().et_recode_packed_device(self._h, ctypes.byref(codebook_in.raw), ctypes.byref(codebook_out.raw), map_p, bodies.data_ptr(), bodies.numel(),
+                                             self._index_ptr(body_index, n), self._index_ptr(text_index), n, None if rows is None else self._rows_ptr(rows), n_rows,
+                                             self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows),
+                                             self._index_ptr(out_text_index, n_rows), self._opt_ptr(status), ctypes.byref(res))
+        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
         import torch
@@ -1002,6 +1046,35 @@ class Context:
         _check(res.status, self._h)
         if res.n_failed:
             raise EntreepyError(res.first_status, f"concat_packed: row {res.first_failed}")
+        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
+        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+
+    def recode_packed(self, codebook_in, codebook_out, blob, out_index, lengths, rows=None, byte_map=None):
+        """decode_packed's store under `codebook_in`, a list of record numbers (None: row k is record k) and a map -> a store like
+        take_packed's under `codebook_out`: (the bodies of the rows' texts sent through the map, back to back as bytes, their
+        offsets, their lengths), as encode_packed of the translated texts gives it, through two recode_packed_device calls: the
+        sizes, then the bytes."""
+        import torch
+
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        assert out_index.size == lengths.size + 1
+        rows = np.arange(lengths.size, dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        if not rows.size:
+            return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
+        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
+        args = (codebook_in, codebook_out, d_blob, d_body_index, d_text_index, d_rows)
+        sizes = self.recode_packed_device(*args, None, d_new_index, d_new_text, byte_map=byte_map)  # (a new body may be longer than the old: ask)
+        d_out = torch.empty(max(sizes.out_bytes, 1), dtype=torch.uint8, device=d_blob.device)
+        res = self.recode_packed_device(*args, d_out, d_new_index, d_new_text, byte_map=byte_map)
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"recode_packed: row {res.first_failed}")
         new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
         return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
 

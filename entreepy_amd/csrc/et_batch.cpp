@@ -30,6 +30,7 @@
 //   slice         sorted codes + counters -> k_slice_plan -> k_slice_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
 //   field         sorted codes + counters -> k_field_plan -> k_field_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
 //   concat        sorted codes + counters + the encoded literal -> k_concat_plan -> k_concat_long -> k_take_scan (poll) -> unless sizes only: k_concat_copy
+//   recode        sorted codes of table IN + counters + the output table -> k_recode_plan -> k_recode_long -> k_take_scan (poll) -> unless sizes only: k_recode_write, k_recode_write_long
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -68,6 +69,7 @@ static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the p
 //   encode, gather   from PK_SIZES: a size word per record, or per row        take   from PK_SIZES: a TakeRow per row
 //   slice, field   from PK_SIZES: a TakeRow per row, then a list entry per row
 //   concat  the encoded literal at PK_PATTERN (it ends in front of PK_SIZES); from PK_SIZES: a TakeRow per row, a list entry per row, a ConcatPiece per row
+//   recode  the output table (256 x {code of map[s] under table OUT, length}, 2 KiB) at PK_PATTERN; behind it a TakeRow per row, then a list entry per row
 //   search  as the match, then a position and a list entry per record
 //   match   behind the pattern: the tile workspace (tile_ws)                   join   behind the counters: the tile workspace, the table's slots, a key number per record
 //   order   (the match's LESS modes) the sorted codes, the counters, the pattern, the boundary table behind the pattern's last word, the tile workspace
@@ -799,6 +801,63 @@ extern "C" int et_concat_packed_device(et_ctx *ctx, const et_codebook *cb, const
     res->text_bytes = rep[et::TAKE_TEXT_BYTES];
     read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
     if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the rows need more than cap bytes");  // (k_concat_copy saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_recode_lane_bytes(void) { return et::RECODE_LANE_BYTES; }
+
+static_assert(PK_PATTERN % 16 == 0 && 2048 <= et::MATCH_PATTERN_BYTES, "the recode's output table lies where the match's pattern does, in both blocks");
+
+extern "C" int et_recode_packed_device(et_ctx *ctx, const et_codebook *cb_in, const et_codebook *cb_out, const int16_t *map, const void *d_bodies, size_t body_bytes,
+                                       const uint64_t *d_body_index, const uint64_t *d_text_index, size_t n_records, const uint32_t *d_rows, size_t n_rows, void *d_out,
+                                       size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index, uint8_t *d_status, et_take_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb_in || !cb_out || !res || !d_bodies || !d_body_index || !d_text_index || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (misaligned(7, d_body_index, d_text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
+    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
+    if (!d_rows && n_rows != n_records) return fail(ctx, ET_ERR_ARG, "without d_rows, row k is record k: n_rows must be n_records");
+    if (d_out && cap && body_bytes) {  // (recoding in place is not this call's)
+        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
+        if (o < b + body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps d_bodies");
+    }
+    if (map)
+        for (int s = 0; s < 256; ++s)
+            if (map[s] < ET_RECODE_DROP || map[s] > 255) return fail(ctx, ET_ERR_ARG, "a map entry is a byte, or ET_RECODE_DROP");
+    *res = et_take_result{};
+    if (n_rows == 0) return ET_OK;
+    ET_TRY(require_complete(ctx, cb_in));
+    ET_TRY(require_complete(ctx, cb_out));
+    DeviceGuard guard(ctx->device);
+    // the slice's layout behind the output table; the sorted codes of cb_in, the counters' first values and the output table lie one
+    // behind the other: up in one copy
+    Bump layout{PK_PATTERN + 2048};
+    const size_t at_plan = layout.take(n_rows * sizeof(et::TakeRow), 16), at_list = layout.take(n_rows * 4, 4);
+    ET_TRY(packed_ensure(ctx, layout.end));
+    const uint32_t n_codes = fill_shared_table(cb_in, pin<uint32_t>(ctx, PIN_PK_TABLE), false);
+    first_counters(ctx);
+    // the map composed with cb_out, by the INPUT symbol: the device looks one entry up per symbol and knows neither
+    uint32_t *out_tab = pin<uint32_t>(ctx, PIN_PK_PATTERN);
+    for (int s = 0; s < 256; ++s) {
+        const int to = map ? map[s] : s;
+        const uint32_t len = to < 0 ? 0u : cb_out->length[to];
+        out_tab[2 * s] = len ? et_left_aligned(cb_out->data[to], len) : 0u;
+        out_tab[2 * s + 1] = to < 0 ? 0u : len ? len : et::RECODE_UNCODED;
+    }
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_PATTERN + 2048, hipMemcpyHostToDevice, ctx->stream));
+    et::RecodeJob job{};
+    job.rows = d_rows;
+    job.out_tab = ws<const uint2>(ctx, PK_PATTERN);
+    job.n_rows = static_cast<uint32_t>(n_rows);
+    const et::PackedReport report = next_report(ctx);
+    et::launch_recode(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, ws<const uint2>(ctx, 0), n_codes, job,
+                      d_out, cap, d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, at_plan), ws<uint32_t>(ctx, at_list), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the recode's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
+    res->out_bytes = rep[et::PACKED_BYTES];
+    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the recoded rows need more than cap bytes");  // (both writes saw the same two figures)
     return ET_OK;
 }
 

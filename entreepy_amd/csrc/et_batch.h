@@ -371,4 +371,48 @@ struct ConcatJob {
 void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &b, const uint2 *codes, uint32_t n_codes, const ConcatJob &job, void *d_out, uint64_t cap,
                    uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, ConcatPiece *pieces, const PackedReport &report);
 
+
+// The recode (et_recode_packed_device): rows[]' stored texts under table IN, each byte sent through a 256-entry map (or dropped), as
+// a NEW packed store under table OUT -- the walk of the decodes feeding the pack loop of the encodes with nothing in between: for
+// every symbol s of the stored text the codeword of map[s] under OUT is laid behind the one before.  The first packed call whose
+// output bits are no copy of input bits, and the first with two tables; the map costs the device nothing: the host composes it with
+// OUT into ONE table indexed by the INPUT symbol (RecodeEntry below).  Five launches, three for a sizes-only call:
+//   k_recode_plan   k_slice_plan's frame: judged as k_take_plan judges, its status byte; a body (clip_body of the whole length) up to
+//                   RECODE_LANE_BYTES is walked by its lane to the end of its stored text, summing output bits, kept symbols and the
+//                   "uncoded" flag; a longer one goes onto a list; a TakeRow per row: {new bytes, new length, new BITS}
+//   k_recode_long   one workgroup per listed row: the blocks settled by a walk whose visitor sums the same three per lane, the lane
+//                   in which symbol `length` falls walks again, cut there; the totals carried across the blocks; thread 0 stores the
+//                   row's TakeRow, or fails the row where a kept symbol has no code
+//   k_take_scan     the take's, unchanged: its report is the call's
+//   k_recode_write  (unless d_out is null: sizes only) one lane per row the lane has planned: the walk again, the codes into a 64-bit
+//                   accumulator that begins at the destination's aligned word; whole words leave as dword stores, the row's first and
+//                   last word clipped to its bytes
+//   k_recode_write_long   (likewise) one workgroup per listed row, block by block: settled, the lanes' output bits scanned to each
+//                   lane's destination bit, the lanes walk again and OR their codes into an LDS bit image (pack_round's inner loop),
+//                   flushed in rounds of RECODE_ROUND_BITS destination bits -- a block of 1-bit codes becomes 256 KiB of 32-bit ones
+//                   --, the partial word carried as `pending` (pack_rounds' hand-over)
+// A row owns whole bytes, so no two rows share an output byte and no workgroup waits for another.  The short and the long write are
+// two kernels: one lane's registers and 8 KiB of LDS against a workgroup's 35 KiB; neither pays for the other's occupancy.
+// RECODE_LANE_BYTES is the search's threshold, kept: the recode_sweep leg of tools/batch_bench.py (profiles/recode_sweep.json)
+// has the lane path the faster one up to source bodies of 600 bytes and the slower one at 1 200 with records of one size; 512 leaves room for
+// stores of mixed sizes, where a wavefront waits for its longest body.
+#ifndef ET_RECODE_LANE_BYTES  // (a build for the sweep sets it, as ET_SEARCH_LANE_BYTES)
+#define ET_RECODE_LANE_BYTES ET_SEARCH_LANE_BYTES
+#endif
+constexpr uint32_t RECODE_LANE_BYTES = ET_RECODE_LANE_BYTES;
+constexpr uint32_t RECODE_ROUND_BITS = BATCH_STAGE_BYTES * 8;  // destination bits per flush of the long write: BatchDecLds::out is the image
+// The output table's entry for INPUT symbol s: {the left-aligned code of map[s] under OUT, its length}; length 0: s is dropped;
+// RECODE_UNCODED: s is kept but map[s] has no code under OUT -- a row whose stored text holds such a symbol fails.
+constexpr uint32_t RECODE_UNCODED = 0x80000000u;
+constexpr uint32_t RECODE_LEN_MASK = 0x3fu;
+struct RecodeJob {
+    const uint32_t *rows;  // null: row k is record k
+    const uint2 *out_tab;  // 256 RecodeEntry-shaped pairs on the device (16-byte aligned)
+    uint32_t n_rows, pad;
+};
+// codes: the sorted codes of table IN on the device (launch_shared_decode's); plan, long_list: as launch_slice's (the counters' word
+// for the list is the slice's, SLICE_N_LONG).  The report leaves with the scan, in front of the two writes.
+void launch_recode(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const RecodeJob &job, void *d_out, uint64_t cap,
+                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
+
 }  // namespace et

@@ -43,6 +43,15 @@
 //            k_field_long    one workgroup per listed row: settled blocks whose walks count delimiters, a second scan numbers them, the boundaries reduced
 //            k_take_scan     as in the take
 //            k_take_copy     as in the slice
+//   concat   k_concat_plan   one lane per row of two stores: both judged; short bodies walked to the end of their stored text; a long one listed
+//            k_concat_long   one workgroup per listed row: the slice's counting walk for each long side
+//            k_take_scan     as in the take
+//            k_concat_copy   k_take_copy's frame: a row's bytes are the OR of its three runs of bits
+//   recode   k_recode_plan   one lane per row: judged; a short body walked under table IN, the output table's bits, symbols and flag summed; a long one listed
+//            k_recode_long   one workgroup per listed row: settled blocks whose walks sum the same three, cut at the length
+//            k_take_scan     as in the take
+//            k_recode_write  one lane per short row: the walk again, the codes under table OUT into a 64-bit accumulator, dword stores
+//            k_recode_write_long   one workgroup per listed row: settled blocks, the walk again into an LDS bit image, flushed in rounds
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -2522,6 +2531,371 @@ __global__ __launch_bounds__(BB) void k_concat_copy(const ConcatPiece *__restric
 }
 
 // --------------------------------------------------------------------------------
+// The recode call: row k of the new store is bytes(map[c] for c in text(rows[k]) if map[c] is kept), text() the stored text under
+// table IN, written as the encoder writes it under table OUT.  The walk of the decodes feeds the pack loop of the encodes with
+// nothing in between: for every symbol s of the stored text the entry s of ONE table -- map composed with OUT by the host, 256 x
+// {left-aligned code, length} indexed by the INPUT symbol -- is laid behind the one before.  Length 0: the byte is dropped;
+// RECODE_UNCODED: it is kept but has no code under OUT, and the row fails (PACKED_UNSUPPORTED, the empty record).
+// THE rule of what counts is the field's: codeword number i of a body is a symbol of the stored text when it ends inside the body
+// AND i < length; nothing else is looked up in the output table, so a codeword behind the length or in the pad fails no row.
+// The body is read twice (sizes, then bits) and the new body written once.  A row owns whole bytes: no two rows share an output
+// byte, pad bits are zero because the accumulators begin as zeros, and every store is clipped to the row's own bytes.
+// Every loop is bounded as the slice's are: a lane's walk by the record's length, the workgroup's by the blocks of the body that the
+// length can reach, its fixed point by 256 trips, a lane's walk inside it by its 256 bits, and the flush rounds of a block by the
+// block's output bits (at most 65 536 codewords of 32 bits: 16 rounds).  No workgroup waits for another.
+// --------------------------------------------------------------------------------
+// What a walk over a stored text sums: the new body's bits, its symbols, and whether a kept symbol has no code under OUT.
+struct Recoded {
+    uint32_t bits, kept, uncoded;
+    __device__ __forceinline__ void add(const uint2 e) {
+        bits += e.y & RECODE_LEN_MASK;
+        kept += e.y != 0;
+        uncoded |= e.y >> 31;
+    }
+};
+
+// A row's record as the slice judges it, and what of its body the walks look at.
+__device__ __forceinline__ Judged recode_judge(const PackedStore &store, const RecodeJob &job, uint32_t k) {
+    Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
+    if (!rec.status && rec.nb > TAKE_BODY_MAX) rec.status = PACKED_UNSUPPORTED;
+    return rec;
+}
+
+__device__ __forceinline__ BodyBits recode_body(const PackedStore &store, const Judged &rec) {
+    return body_bits_of(static_cast<const uint8_t *>(store.bodies), rec.b0, static_cast<uint32_t>(clip_body(rec.nb, rec.len)));
+}
+
+__device__ __forceinline__ bool recode_by_lane(const BodyBits &g) { return g.end_bit - g.first_bit <= RECODE_LANE_BYTES * 8; }
+
+// One lane, one body of a few words, from global memory (slice_lane's walk from symbol 0 to the end of the stored text): visit(s) sees
+// every symbol of the stored text, in order.
+template <class Visit>
+__device__ __forceinline__ void recode_lane(const CodeTables &t, uint32_t n_codes, const BodyBits &g, uint32_t len, Visit &&visit) {
+    uint32_t pos = g.first_bit, k = 0;
+    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
+    for (uint32_t idx = 0; idx < len; ++idx) {
+        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
+            k = pos >> 5;
+            two = (two << 32) | body_word_be(g, k + 1);
+        }
+        const uint32_t meta = code_at(t, n_codes, static_cast<uint32_t>((two << (pos & 31)) >> 32));
+        if (pos + (meta >> 8) > g.end_bit) break;  // the bits ran out inside this codeword: the stored text ends here
+        visit(meta & 0xffu);
+        pos += meta >> 8;
+    }
+}
+
+// The TakeRow of a recoded row as it lies in memory: the new body's bytes, its symbols, its BITS (the long write bounds its rounds by them).
+__device__ __forceinline__ uint4 recode_row(const Recoded &r) {
+    if (r.uncoded || !r.bits) return make_uint4(0u, 0u, 0u, 0u);
+    return make_uint4((r.bits + 7) >> 3, r.kept, r.bits, 0u);
+}
+
+// k_recode_plan: k_slice_plan's frame -- rows, judgement, status bytes, tally, the list's ballot -- with the output table beside the
+// code tables in LDS.  A record without bytes or symbols has the empty stored text and is not read; a body up to RECODE_LANE_BYTES is
+// walked by its lane, and a kept symbol without a code fails the row here; a longer one goes onto long_list and is the empty record
+// for now: k_recode_long stores its TakeRow.  LDS 8 KiB + 8 words.
+__global__ __launch_bounds__(BB) void k_recode_plan(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, RecodeJob job, TakeRow *__restrict__ plan,
+                                                    uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ CodeTables t;
+    __shared__ uint2 s_otab[256];
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    const uint32_t lane = threadIdx.x & 63;
+    s_otab[threadIdx.x] = job.out_tab[threadIdx.x];
+    load_tables(t, codes, n_codes);
+    __syncthreads();
+    PackedTally tally;
+    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
+        bool is_long = false;
+        if (k < job.n_rows) {
+            const Judged rec = recode_judge(store, job, k);
+            uint32_t status = rec.status;
+            uint4 row = make_uint4(0u, 0u, 0u, 0u);
+            if (!status && rec.nb && rec.len) {
+                const BodyBits g = recode_body(store, rec);
+                if (recode_by_lane(g)) {
+                    Recoded sum{0u, 0u, 0u};
+                    recode_lane(t, n_codes, g, static_cast<uint32_t>(rec.len), [&](uint32_t sym) { sum.add(s_otab[sym]); });
+                    if (sum.uncoded) status = PACKED_UNSUPPORTED;
+                    row = recode_row(sum);
+                } else {
+                    is_long = true;
+                }
+            }
+            reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
+            if (d_status) d_status[k] = static_cast<uint8_t>(status);
+            tally.note(k, status);
+        }
+        const unsigned long long longs = __ballot(is_long);
+        if (longs) {  // (the same for the whole wavefront)
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
+            at = __shfl(at, 0, 64);
+            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
+        }
+    }
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
+// The visitor of the settling walks of the recode: what the walk's codewords give under the output table.
+struct SumRecoded {
+    const uint2 *otab;
+    Recoded r;
+    __device__ __forceinline__ bool operator()(uint32_t, uint32_t, uint32_t, uint32_t meta) {
+        r.add(otab[meta & 0xffu]);
+        return true;
+    }
+};
+
+// One block of a long row, settled, and what each lane's symbols OF THE STORED TEXT give: the visitor does not know its lane's symbol
+// numbers; once the scan has given them, the lanes behind the length hold nothing and the one lane whose codewords reach it sums
+// again up to it (field_stream's cut), so nothing at or behind `len` is ever looked up.  `done`: the codewords of the blocks before.
+struct RecodedBlock {
+    Settled b;
+    uint32_t held;  // the lane's symbols of the stored text
+    Recoded mine;   // ... and what they give
+};
+
+__device__ __forceinline__ RecodedBlock recode_block(BatchDecLds &s, const uint2 *otab, uint32_t n_codes, const BodyBits &g, uint32_t blk, uint32_t start, uint32_t done,
+                                                     uint32_t len) {
+    SumRecoded summing{otab, Recoded{0u, 0u, 0u}};
+    RecodedBlock rb;
+    rb.b = settle_block(s, n_codes, g, blk, start, summing);
+    const uint32_t lo = done + rb.b.first;  // the number of the lane's first codeword
+    rb.held = rb.b.count;
+    rb.mine = summing.r;
+    if (lo >= len || !rb.b.count) {
+        rb.held = 0;
+        rb.mine = Recoded{0u, 0u, 0u};
+    } else if (lo + rb.b.count > len) {  // (lo + count <= 4 * len + 16: no wrap)
+        const uint32_t held = len - lo;
+        Recoded cut{0u, 0u, 0u};
+        uint32_t again;
+        (void)walk(s, n_codes, rb.b.used, rb.b.room, &again, [&](uint32_t cnt, uint32_t, uint32_t, uint32_t meta) {
+            if (cnt >= held) return false;
+            cut.add(otab[meta & 0xffu]);
+            return true;
+        });
+        rb.held = held;
+        rb.mine = cut;
+    }
+    return rb;
+}
+
+// k_recode_long: k_slice_long's shape over long_list.  A workgroup beyond the list returns before it sets anything up.  Per block the
+// lanes' three sums are added up over the workgroup (two scans: the bits; the symbols with the flag's count above them) and carried
+// in registers across the blocks.  Thread 0 stores the row's TakeRow (k_recode_plan left the empty record there; the scan runs behind
+// this kernel), or fails the row -- its status byte, one tally -- where a kept symbol has no code: k_recode_plan held it for OK.
+// LDS as k_batch_decode, the output table's 2 KiB and the scans' 4 words: 35.2 KiB.
+__global__ __launch_bounds__(BB) void k_recode_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, RecodeJob job, TakeRow *__restrict__ plan,
+                                                    const uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ BatchDecLds s;
+    __shared__ uint2 s_otab[256];
+    __shared__ uint32_t s_scan[BB / 64];
+    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
+    if (blockIdx.x >= n_long) return;
+    s_otab[threadIdx.x] = job.out_tab[threadIdx.x];
+    load_tables(s.t, codes, n_codes);
+    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
+        const uint32_t k = long_list[i];
+        if (k >= job.n_rows) continue;  // (k_recode_plan lists rows; the same for every lane, like all below)
+        const Judged rec = recode_judge(store, job, k);
+        if (rec.status || rec.nb == 0 || rec.len == 0) continue;  // (k_recode_plan lists no such row)
+        const uint32_t len = static_cast<uint32_t>(rec.len);
+        const BodyBits g = recode_body(store, rec);
+        const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
+        uint32_t start = g.first_bit, done = 0;  // the block's first codeword; codewords so far
+        Recoded sum{0u, 0u, 0u};
+        for (uint32_t blk = 0; blk < n_blocks && done < len; ++blk) {
+            const RecodedBlock rb = recode_block(s, s_otab, n_codes, g, blk, start, done, len);
+            uint32_t bits, rest;  // (a block's codewords: at most 65 536 + 8, its flags at most 256: the two share a word)
+            (void)block_exclusive_scan(rb.mine.bits, s_scan, &bits);
+            __syncthreads();
+            (void)block_exclusive_scan(rb.mine.kept | rb.mine.uncoded << 20, s_scan, &rest);
+            sum.bits += bits;
+            sum.kept += rest & 0xfffffu;
+            sum.uncoded |= rest >> 20;
+            start = rb.b.start;
+            done += rb.b.total;
+        }
+        if (threadIdx.x == 0) {
+            reinterpret_cast<uint4 *>(plan)[k] = recode_row(sum);
+            if (sum.uncoded) {
+                if (d_status) d_status[k] = static_cast<uint8_t>(PACKED_UNSUPPORTED);
+                PackedTally tally;
+                tally.note(k, PACKED_UNSUPPORTED);
+                tally.add_to(stats);
+            }
+        }
+    }
+}
+
+// store_image_word for the recode's writes (a copy: shared, it changed the comparison sequence of k_shared_encode's and k_packed_pack's clipped stores).
+__device__ __forceinline__ void recode_store_word(uint8_t *line, uint32_t g, uint32_t v, uint32_t lo, uint32_t hi) {
+    const uint32_t b0 = g * 4;
+    if (b0 >= lo && b0 + 4 <= hi) {
+        reinterpret_cast<uint32_t *>(line)[g] = v;
+    } else {
+        for (uint32_t k = 0; k < 4; ++k)
+            if (b0 + k >= lo && b0 + k < hi) line[b0 + k] = static_cast<uint8_t>(v >> (8 * k));
+    }
+}
+
+// Where a row's bits go: the image begins at the aligned word that holds the row's first byte; the row's bytes are image bytes [lo, hi).
+struct RecodeDst {
+    uint8_t *line;
+    uint32_t lo, hi;
+};
+
+__device__ __forceinline__ RecodeDst recode_dst(uint8_t *d_out, uint64_t at, uint32_t bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_out) + at;
+    const uint32_t lo = static_cast<uint32_t>(a & 3);
+    return RecodeDst{reinterpret_cast<uint8_t *>(a & ~static_cast<uintptr_t>(3)), lo, lo + bytes};
+}
+
+// k_recode_write: the rows a lane has planned, a row per lane, k_recode_plan's walk once more: every kept symbol's code goes into a
+// 64-bit accumulator that begins at the destination's aligned word (the bytes in front of the row are zeros in it and are clipped
+// from the store); a word that has filled leaves as one dword store, the row's first and last word as their own bytes
+// (recode_store_word), the last one with zero bits behind the body.  Failed and empty rows have no bytes; a listed row is
+// k_recode_write_long's.  Nothing is written when the rows need more than cap.  LDS 8 KiB.
+__global__ __launch_bounds__(BB) void k_recode_write(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, RecodeJob job, const TakeRow *__restrict__ plan,
+                                                     const uint64_t *__restrict__ out_index, uint8_t *__restrict__ d_out, uint64_t cap) {
+    __shared__ CodeTables t;
+    __shared__ uint2 s_otab[256];
+    if (out_index[job.n_rows] > cap) return;  // (the same for every thread)
+    s_otab[threadIdx.x] = job.out_tab[threadIdx.x];
+    load_tables(t, codes, n_codes);
+    __syncthreads();
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * BB + threadIdx.x; k < job.n_rows; k += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t bytes = plan[k].body_bytes;
+        if (!bytes) continue;
+        const Judged rec = recode_judge(store, job, static_cast<uint32_t>(k));
+        if (rec.status || rec.nb == 0 || rec.len == 0) continue;  // (such a row has no bytes)
+        const BodyBits g = recode_body(store, rec);
+        if (!recode_by_lane(g)) continue;
+        const RecodeDst dst = recode_dst(d_out, out_index[k], bytes);
+        uint32_t word = 0, fill = dst.lo * 8;
+        uint64_t acc = 0;
+        recode_lane(t, n_codes, g, static_cast<uint32_t>(rec.len), [&](uint32_t sym) {
+            const uint2 e = s_otab[sym];
+            const uint32_t n = e.y & RECODE_LEN_MASK;
+            if (!n) return;
+            acc |= (static_cast<uint64_t>(e.x) << 32) >> fill;  // (fill < 32 here: the code's 32 bits stay inside the 64)
+            fill += n;
+            if (fill >= 32) {
+                recode_store_word(dst.line, word, __builtin_bswap32(static_cast<uint32_t>(acc >> 32)), dst.lo, dst.hi);
+                acc <<= 32;
+                ++word;
+                fill -= 32;
+            }
+        });
+        if (fill) recode_store_word(dst.line, word, __builtin_bswap32(static_cast<uint32_t>(acc >> 32)), dst.lo, dst.hi);
+    }
+}
+
+// k_recode_write_long: one workgroup per listed row that has bytes, block by block: the block settled and cut as k_recode_long does
+// it, the lanes' output bits scanned to each lane's destination bit within the block, then rounds of RECODE_ROUND_BITS destination
+// bits -- one 8 KiB block of 1-bit codes becomes 256 KiB of 32-bit ones, sixteen rounds; a block of 32-bit codes that become 1-bit ones
+// is one round of 256 bytes: a round never spans two input blocks, the partial word is what crosses.  In a round the lanes whose bits
+// meet it walk again and OR their codes into the LDS image (BatchDecLds::out: pack_round's inner loop -- an accumulator, atomicOr
+// where a word fills); a code that straddles a round's edge leaves its bits on either side in their own rounds.  Whole words leave as
+// byte-swapped dword stores, the row's first and last word clipped to its bytes, the word a round ends in is carried as `pending`
+// (pack_rounds' hand-over).  The image is zero between rounds.  Nothing is written when the rows need more than cap.
+// LDS as k_recode_long: 35.2 KiB, three workgroups per CU.
+__global__ __launch_bounds__(BB) void k_recode_write_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, RecodeJob job,
+                                                          const TakeRow *__restrict__ plan, const uint32_t *__restrict__ long_list,
+                                                          const unsigned long long *__restrict__ stats, const uint64_t *__restrict__ out_index,
+                                                          uint8_t *__restrict__ d_out, uint64_t cap) {
+    static_assert(RECODE_ROUND_BITS / 32 + 2 <= sizeof(BatchDecLds::out) / 4, "a round's words, the word it begins in and the one it ends in");
+    __shared__ BatchDecLds s;
+    __shared__ uint2 s_otab[256];
+    __shared__ uint32_t s_scan[BB / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
+    if (blockIdx.x >= n_long || out_index[job.n_rows] > cap) return;  // (the same for every thread)
+    s_otab[tid] = job.out_tab[tid];
+    load_tables(s.t, codes, n_codes);
+    for (uint32_t i = tid; i < sizeof(s.out) / 4; i += BB) s.out[i] = 0u;
+    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
+        const uint32_t k = long_list[i];
+        if (k >= job.n_rows) continue;  // (k_recode_plan lists rows; the same for every lane, like all below)
+        const uint32_t bytes = plan[k].body_bytes;
+        if (!bytes) continue;  // a failed row, or one whose every symbol is dropped
+        const Judged rec = recode_judge(store, job, k);
+        if (rec.status || rec.nb == 0 || rec.len == 0) continue;  // (k_recode_plan lists no such row)
+        const uint32_t len = static_cast<uint32_t>(rec.len);
+        const BodyBits g = recode_body(store, rec);
+        const RecodeDst dst = recode_dst(d_out, out_index[k], bytes);
+        const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
+        uint32_t start = g.first_bit, done = 0;     // the block's first codeword; codewords so far
+        uint32_t carry = dst.lo * 8, pending = 0;   // the image bit the next round begins at; the bits of word carry / 32 in front of it
+        for (uint32_t blk = 0; blk < n_blocks && done < len; ++blk) {
+            const RecodedBlock rb = recode_block(s, s_otab, n_codes, g, blk, start, done, len);
+            uint32_t block_bits;
+            const uint32_t before = block_exclusive_scan(rb.mine.bits, s_scan, &block_bits);  // the lane's first output bit within the block
+            for (uint32_t w0 = 0; w0 < block_bits; w0 += RECODE_ROUND_BITS) {
+                const uint32_t round_bits = block_bits - w0 < RECODE_ROUND_BITS ? block_bits - w0 : RECODE_ROUND_BITS, w1 = w0 + round_bits;
+                const uint32_t base = carry & 31;  // the round's first bit in the image
+                if (tid == 0 && pending) atomicOr(&s.out[0], pending);
+                if (rb.mine.bits && before < w1 && before + rb.mine.bits > w0) {
+                    uint32_t p = before, wi = 0, fill = 0, again;
+                    uint64_t acc = 0;
+                    bool open = false;
+                    (void)walk(s, n_codes, rb.b.used, rb.b.room, &again, [&](uint32_t cnt, uint32_t, uint32_t, uint32_t meta) {
+                        if (cnt >= rb.held) return false;
+                        const uint2 e = s_otab[meta & 0xffu];
+                        uint32_t n = e.y & RECODE_LEN_MASK, v = e.x, at = p;
+                        if (!n) return true;
+                        if (at >= w1) return false;
+                        p += n;
+                        if (p <= w0) return true;
+                        if (at < w0) {  // the code's first bits went out with the round before
+                            v <<= w0 - at;
+                            n -= w0 - at;
+                            at = w0;
+                        }
+                        if (at + n > w1) {  // ... and its last ones go out with the next
+                            n = w1 - at;
+                            v &= ~0u << (32 - n);
+                        }
+                        if (!open) {
+                            const uint32_t q = base + (at - w0);
+                            wi = q >> 5;
+                            fill = q & 31;
+                            open = true;
+                        }
+                        acc |= (static_cast<uint64_t>(v) << 32) >> fill;
+                        fill += n;
+                        if (fill >= 32) {
+                            atomicOr(&s.out[wi], static_cast<uint32_t>(acc >> 32));
+                            acc <<= 32;
+                            ++wi;
+                            fill -= 32;
+                        }
+                        return true;
+                    });
+                    if (fill) atomicOr(&s.out[wi], static_cast<uint32_t>(acc >> 32));
+                }
+                __syncthreads();
+                const uint32_t t_bits = base + round_bits, full = t_bits >> 5, first_word = carry >> 5;
+                pending = (t_bits & 31) ? s.out[full] : 0u;
+                __syncthreads();
+                for (uint32_t w = tid; w <= full; w += BB) {
+                    if (w < full) recode_store_word(dst.line, first_word + w, __builtin_bswap32(s.out[w]), dst.lo, dst.hi);
+                    s.out[w] = 0u;
+                }
+                carry += round_bits;
+                __syncthreads();
+            }
+            start = rb.b.start;
+            done += rb.b.total;
+        }
+        if (tid == 0 && (carry & 31)) recode_store_word(dst.line, carry >> 5, __builtin_bswap32(pending), dst.lo, dst.hi);
+    }
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
 
 static uint32_t capped(uint64_t n, uint32_t most) { return n < most ? static_cast<uint32_t>(n) : most; }
@@ -2593,6 +2967,21 @@ void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &
     if (!d_out) return;
     hipLaunchKernelGGL(k_concat_copy, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const ConcatPiece *>(pieces), job.sep, job.sep_bits,
                        static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+}
+
+void launch_recode(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const RecodeJob &job, void *d_out, uint64_t cap,
+                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &r) {
+    const uint32_t n_rows = job.n_rows, lanes = capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID), groups = capped(n_rows, SHARED_DEC_GRID);
+    hipLaunchKernelGGL(k_recode_plan, dim3(lanes), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
+    hipLaunchKernelGGL(k_recode_long, dim3(groups), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list), d_status, r.stats);
+    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
+                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
+    if (!d_out) return;
+    hipLaunchKernelGGL(k_recode_write, dim3(lanes), dim3(BB), 0, stream, store, codes, n_codes, job, static_cast<const TakeRow *>(plan),
+                       static_cast<const uint64_t *>(out_body_index), static_cast<uint8_t *>(d_out), cap);
+    hipLaunchKernelGGL(k_recode_write_long, dim3(groups), dim3(BB), 0, stream, store, codes, n_codes, job, static_cast<const TakeRow *>(plan),
+                       static_cast<const uint32_t *>(long_list), static_cast<const unsigned long long *>(r.stats), static_cast<const uint64_t *>(out_body_index),
+                       static_cast<uint8_t *>(d_out), cap);
 }
 
 void launch_join(hipStream_t stream, const PackedStore &records, const PackedStore &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,

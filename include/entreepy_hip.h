@@ -762,6 +762,63 @@ int et_concat_packed_device(et_ctx *ctx, const et_codebook *cb,
                             void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
                             uint8_t *d_status, et_take_result *res);
 
+/* RECODE: A STORE UNDER A SECOND TABLE, THROUGH A BYTE MAP (re-tabling, UPPER, LOWER, TRANSLATE, stripping characters) as a NEW packed
+ * store, on the device, no text in between: the codewords of a record are walked under cb_in and for each symbol s the codeword of
+ * map[s] under cb_out is emitted, or nothing where the byte is dropped.  The call that lifts "one table" from the others: a key set
+ * written under yesterday's table is recoded and joined against today's store, two stores are brought under one table and
+ * concatenated, and case-insensitive =, LIKE and IN are match / search / join on the store recoded through an ASCII upper-casing map
+ * against the upper-cased needle -- all on one ctx with nothing in between.
+ *   The store, d_rows (any order, repeats allowed; NULL: row k is record k, and n_rows must equal n_records) and d_status are the
+ *     slice call's, and a row is judged as the slice call judges it: ET_ERR_ARG for a number beyond the store or a bad pair of
+ *     offsets, ET_ERR_UNSUPPORTED for a length above the small-stream limit or a body above 4 * et_batch_small_max() bytes.  A failed
+ *     row is the EMPTY record of the new store (no bytes, length 0), fails alone and is tallied once; nothing is read where its
+ *     offsets point.
+ *   text_r is the stored text of record r under cb_in as every packed call defines it: the first min(length_r, codewords that end
+ *     inside its body) symbols.  A codeword at or behind length_r is no symbol, and neither is whatever the pad bits read as.
+ *   map (HOST memory, 256 entries; NULL: the identity): map[c] is a byte value in [0, 255], or ET_RECODE_DROP to delete that byte.
+ *   Row k is t = bytes(map[c] for c in text_r if map[c] != DROP), r = rows[k], and d_out[out_body_index[k], out_body_index[k+1])
+ *     holds exactly the bytes et_encode_packed_device writes for t under cb_out -- ceil(bits / 8) bytes, MSB-first from bit 7, the pad
+ *     bits zero whatever the source's are -- with out_text_index[k+1] - out_text_index[k] == len(t).  A body of no bytes under a
+ *     length above zero (a record kept raw elsewhere) has the empty stored text and recodes to the empty record, length 0: the
+ *     slice's rule, not the take's.
+ *   A kept byte map[c] without a code in cb_out fails the row with ET_ERR_UNSUPPORTED (the encoder's status for a byte without a
+ *     code); the row is the empty record.  Only symbols of the stored text can fail a row: the same byte behind the length, or in the
+ *     pad bits, or dropped by the map, does not.
+ *   Both tables must be complete (et_codebook_is_complete).  cb_out may be cb_in: a pure TRANSLATE.  The identity map with cb_out ==
+ *     cb_in is NOT short-cut to the take: it runs, and NORMALISES the store -- pad bits cleared, lengths cut to what the bodies hold.
+ *     A new record has at most as many symbols as the old and at most 4 bytes per symbol: the output is a store every packed call
+ *     accepts.
+ *   Both output arrays have n_rows + 1 entries (8-byte aligned, on the device) and begin with 0; the bodies lie back to back.
+ *   *res is the take call's: out_bytes, text_bytes (the sum of the new lengths), n_failed, first_failed, first_status.  Nothing
+ *     outside [d_out, d_out + out_body_index[n_rows]) is written, at any alignment of d_out and of the bodies.
+ *     d_out == NULL: sizes only -- both output arrays, d_status and *res are the writing call's; cap is ignored.
+ *     out_body_index[n_rows] > cap: ET_ERR_CAP, not a byte of d_out is written; both output arrays and d_status are complete and
+ *     res->out_bytes is the room needed.
+ *   et_recode_lane_bytes(): a body (min(body bytes, 4 * length + 8)) up to this many bytes is walked by one lane, a longer one by a
+ *     workgroup (the search's threshold, kept) -- for tests that want rows on both sides; the answer does not depend on it.
+ * Out of scope: per-row maps; one byte to several, or several to one (REPLACE of substrings); UTF-8 case folding; recoding in place
+ * -- [d_out, d_out + cap) may not overlap the bodies --; several stores per call; the symbol histogram of a store taken on its
+ * compressed bytes, which a caller would want in order to build the best cb_out: until then the caller decodes and uses
+ * et_histogram_device.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb_in, cb_out, res, d_bodies or offset array; an offset array that is not 8-byte
+ * aligned; d_rows not 4-byte aligned; n_records or n_rows above 0x7fffffff; d_rows == NULL with n_rows != n_records; d_out
+ * overlapping the bodies; a map entry that is neither a byte nor ET_RECODE_DROP -- all checked before anything touches a device,
+ * *res untouched), ET_ERR_UNSUPPORTED (a table is not complete: nothing is enqueued), ET_ERR_CAP, ET_ERR_HIP, ET_ERR_NOMEM.
+ * n_rows == 0: ET_OK, nothing enqueued, *res zeroed.  One upload (the sorted codes of cb_in, zeroed counters and the output table --
+ * map composed with cb_out on the host, indexed by the input symbol: 4.1 KiB), five launches -- plan, long rows, scan, the lanes'
+ * write, the workgroups' write; three without d_out -- and one hand-over per call; stream-ordered like the other packed calls --
+ * *res is final on return, the device arrays once the ctx's stream has drained -- and it may follow or precede any of them on one
+ * ctx with nothing in between. */
+#define ET_RECODE_DROP (-1)
+size_t et_recode_lane_bytes(void);          /* a body (min(body bytes, 4 * length + 8)) up to this is walked by one lane */
+int et_recode_packed_device(et_ctx *ctx, const et_codebook *cb_in, const et_codebook *cb_out,
+                            const int16_t *map,                     /* HOST, 256 entries, or NULL = identity */
+                            const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                            const uint64_t *d_text_index, size_t n_records,
+                            const uint32_t *d_rows, size_t n_rows,
+                            void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
+                            uint8_t *d_status, et_take_result *res);
+
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).
  * Also leaves per-tile histograms in the ctx for a following et_encode_body_device

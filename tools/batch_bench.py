@@ -64,7 +64,12 @@ process of its own so that every leg loads exactly one build of the library:
   field           et_field_packed_device (field k of the pages split at spaces, of 10 % of the rows; fields 0, 3 and 7 of 262 144 CSV lines, of
                   all rows and of 10 %) against what it replaces: a decode (or gather) of the rows' records and et_encode_packed_device of
                   the cut text; the slice up to the delimiter on the same rows and the search's walk over the store as floors
---legs picks the legs (default: all but search_sweep and concat).
+  recode          (only when named) et_recode_packed_device (every row re-tabled, ASCII UPPER of every row under one table, 10 % of the
+                  rows re-tabled; the two shapes and the 262 144 CSV lines) against what it replaces, in the same process: a decode (or
+                  gather), a torch gather through the map's table, et_encode_packed_device under the other table; the sizes-only call
+                  and the slice [0, TO_END) of the same rows as floors
+  recode_sweep    (only when named) the search sweep's stores, every row re-tabled: run it on builds with -DET_RECODE_LANE_BYTES=0 and =8192
+--legs picks the legs (default: all but the sweeps, concat and recode).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
 text once before timing.  One JSON line on stdout (and into --out).
@@ -81,6 +86,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs slice --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/slice_bench.json
     python tools/batch_bench.py --legs field --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/field_bench.json
     python tools/batch_bench.py --legs concat --out profiles/concat_bench.json
+    python tools/batch_bench.py --legs recode --out profiles/recode_bench.json
 """
 import argparse
 import ctypes
@@ -1178,6 +1184,113 @@ def _concat_leg(lib_path, shapes):
     print(json.dumps(results))
 
 
+RECODE_SWEEP_SIZES = (128, 512, 1024, 2048, 4096, 8192, 12288)  # bytes of text per record of the recode sweep's stores (bodies of about 0.6 of that)
+
+
+def _recode_leg(lib_path, shapes, sweep=False):
+    """recode_sweep (only when named): stores of SWEEP_BYTES of text in records of one size each, every row re-tabled: the times from
+    which RECODE_LANE_BYTES would be chosen -- run it on builds with -DET_RECODE_LANE_BYTES=0 and =8192 (ET_LIB_PATH names the library).
+    recode: on 1 024 x 64 KiB, 4 096 x 4 KiB and the 262 144 CSV lines three cells -- every row re-tabled (table OUT from the
+    histogram turned upside down over the same symbols), ASCII UPPER of every row under one table (of the text and its upper-cased
+    self), a random 10 % of the rows re-tabled.  Per cell et_recode_packed_device, its bytes and offsets checked against the other
+    route's, beside it the sizes-only call (what the plan costs without the write) and the slice [0, TO_END) of the same rows (a walk
+    and a copy: the floor) -- and, in the same process, the route it replaces: et_decode_packed_device (et_decode_packed_gather_device
+    for a selection), a torch gather through the 256-entry table where there is a map, et_encode_packed_device under table OUT."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device", "et_decode_packed_gather_device", "et_slice_packed_device", "et_recode_packed_device", "et_recode_lane_bytes"])
+    results = {"lane_bytes": int(L.et_recode_lane_bytes())}
+    res, tres = N.PackedResult(), N.TakeResult()
+    upper = np.arange(256, dtype=np.int16)
+    upper[97:123] -= 32
+
+    def table_of(hist):
+        cb = N.Codebook()
+        hist = np.ascontiguousarray(hist, dtype=np.uint64)
+        assert L.et_build_codebook(hist.ctypes.data, ctypes.byref(cb)) == 0 and L.et_codebook_is_complete(ctypes.byref(cb)) == 0
+        return cb
+
+    def case(cb_in, cb_out, st, rows, bmap):
+        bodies, body_bytes, body_index, text_index, n = st
+        n_rows = n if rows is None else rows.size
+        d_rows = None if rows is None else torch.from_numpy(rows.view(np.int32).copy()).to(dev)
+        rows_p = None if d_rows is None else d_rows.data_ptr()
+        map_p = None if bmap is None else bmap.ctypes.data
+        lut = None if bmap is None else torch.from_numpy(bmap.astype(np.uint8)).to(dev)
+        idx = [[torch.zeros(n_rows + 1, dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(3)]
+
+        def call(d_out, cap):
+            assert L.et_recode_packed_device(h, ctypes.byref(cb_in), ctypes.byref(cb_out), map_p, bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n,
+                                             rows_p, n_rows, None if d_out is None else d_out.data_ptr(), cap, idx[0][0].data_ptr(), idx[0][1].data_ptr(), None,
+                                             ctypes.byref(tres)) == 0, L.et_last_error(h)
+            assert tres.n_failed == 0
+
+        call(None, 0)
+        need, room = int(tres.out_bytes), int(tres.text_bytes)  # (no drops: the rows' text bytes are the old ones)
+        outs = [torch.zeros(need + 64, dtype=torch.uint8, device=dev) for _ in range(2)]
+        sliced = torch.zeros(body_bytes + 64, dtype=torch.uint8, device=dev)
+        at = text_index if d_rows is None else torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+
+        def baseline():
+            dec = torch.empty(room + 64, dtype=torch.uint8, device=dev)
+            if d_rows is None:
+                assert L.et_decode_packed_device(h, ctypes.byref(cb_in), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, dec.data_ptr(), room, None,
+                                                 None, ctypes.byref(res)) == 0, L.et_last_error(h)
+            else:
+                assert L.et_decode_packed_gather_device(h, ctypes.byref(cb_in), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, rows_p, n_rows,
+                                                        dec.data_ptr(), room, at.data_ptr(), None, None, ctypes.byref(res)) == 0, L.et_last_error(h)
+            assert res.out_bytes == room and res.n_failed == 0 and res.n_short == 0
+            text = dec if lut is None else lut[dec[:room].to(torch.int64)]
+            assert L.et_encode_packed_device(h, ctypes.byref(cb_out), text.data_ptr(), room, at.data_ptr(), n_rows, outs[1].data_ptr(), need, idx[1][0].data_ptr(), None,
+                                             ctypes.byref(res)) == 0 and res.n_failed == 0, L.et_last_error(h)
+
+        def slice0():
+            assert L.et_slice_packed_device(h, ctypes.byref(cb_in), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, rows_p, n_rows, None, 0, None,
+                                            0xFFFFFFFF, -1, sliced.data_ptr(), body_bytes, idx[2][0].data_ptr(), idx[2][1].data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+
+        call(outs[0], need)
+        baseline()
+        torch.cuda.synchronize()
+        assert need == int(res.out_bytes) and torch.equal(outs[0][:need], outs[1][:need]) and torch.equal(idx[0][0], idx[1][0]), "the two routes differ"
+        entry = {"rows": int(n_rows), "bytes": need, "text_bytes": room}
+        entry.update(_timed(lambda: call(outs[0], need)))
+        entry["sizes_only"] = _timed(lambda: call(None, 0))
+        entry["slice0_floor"] = _timed(slice0)
+        entry["baseline"] = _timed(baseline)
+        gap, spreads = entry["baseline"]["ms"] - entry["ms"], (entry["baseline"]["max_ms"] - entry["baseline"]["min_ms"]) + (entry["max_ms"] - entry["min_ms"])
+        entry["baseline_over_recode"], entry["beyond_both_spreads"] = round(entry["baseline"]["ms"] / entry["ms"], 2), bool(gap > spreads)
+        entry["vs_slice0_floor"] = round(entry["ms"] / entry["slice0_floor"]["ms"], 2)
+        return entry
+
+    todo = [(f"{count}x{size}", lambda count=count, size=size: _search_store(count, size, 0.1)[:2]) for count, size in SHAPES] + [(f"{CSV_SHAPE[0]}xcsv", lambda: _csv_store(CSV_SHAPE[0]))]
+    if sweep:
+        todo = [(f"{SWEEP_BYTES // size}x{size}", lambda size=size: _search_store(SWEEP_BYTES // size, size, 0.1)[:2]) for size in RECODE_SWEEP_SIZES]
+    for name, make in todo:
+        if shapes and name not in shapes:
+            continue
+        host, index = make()
+        n = index.size - 1
+        hist = np.bincount(host, minlength=256).astype(np.uint64)
+        turned = np.where(hist > 0, hist.max() + 1 - hist, 0)  # the same symbols, what was frequent is rare
+        hist_up = hist + np.bincount(np.frombuffer(host.tobytes().upper(), np.uint8), minlength=256).astype(np.uint64)
+        text = torch.from_numpy(host).to(dev)
+        cb1, cb2, cbu = table_of(hist), table_of(turned), table_of(hist_up)
+        _, *plain = _packed_store(L, h, text, index, cb1)
+        cased = None if sweep else _packed_store(L, h, text, index, cbu)[1:]
+        if sweep:
+            results[name] = {"records": n, "retable_all": case(cb1, cb2, (*plain, n), None, None)}
+            continue
+        tenth = np.sort(np.random.default_rng(0x4EC0DE + n).choice(n, size=n // 10, replace=False)).astype(np.uint32)
+        results[name] = {"records": n, "retable_all": case(cb1, cb2, (*plain, n), None, None), "upper_all": case(cbu, cbu, (*cased, n), None, upper),
+                         "retable_tenth": case(cb1, cb2, (*plain, n), tenth, None)}
+        del text, plain, cased
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
@@ -1204,6 +1317,8 @@ def main():
         return _field_leg(a.leg, a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg == "concat":
         return _concat_leg(a.lib, [s for s in a.shapes.split(",") if s])
+    if a.leg in ("recode", "recode_sweep"):
+        return _recode_leg(a.lib, [s for s in a.shapes.split(",") if s], sweep=a.leg == "recode_sweep")
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -1229,6 +1344,10 @@ def main():
         legs += [("field_baseline", "field_baseline", a.batch_lib or here), ("field", "field", here)]
     if "concat" in a.legs.split(","):  # (the baseline runs in the leg's own process, on this build)
         legs += [("concat", "concat", here)]
+    if "recode" in a.legs.split(","):  # (likewise)
+        legs += [("recode", "recode", here)]
+    if "recode_sweep" in a.legs.split(","):
+        legs += [("recode_sweep", "recode_sweep", here)]
     if "search_sweep" in a.legs.split(","):
         legs += [("search_sweep", "search_sweep", here)]
     out = {"tool": "batch_bench", "reps": REPS, "warmup": WARMUP, "batch_on_another_build": bool(a.batch_lib)}
@@ -1291,6 +1410,8 @@ def main():
         out["field_condition_met"] = all(e["beyond_both_spreads"] for v in out["field_vs_baseline"].values() for e in v.values())
     if "concat" in out:
         out["concat_condition_met"] = all(e["beyond_both_spreads"] for v in out["concat"].values() if isinstance(v, dict) for e in v.values() if isinstance(e, dict))
+    if "recode" in out:
+        out["recode_condition_met"] = all(e["beyond_both_spreads"] for v in out["recode"].values() if isinstance(v, dict) for e in v.values() if isinstance(e, dict))
     line = json.dumps(out)
     print(line)
     if a.out:
