@@ -525,6 +525,9 @@ class Context:
     def _packed_result(self, status, res):
         return PackedResult(self._cap_or_raise(status), res.out_bytes, res.n_failed, res.first_failed, res.n_short, res.first_status)
 
+    def _take_result(self, status, res):
+        return TakeResult(self._cap_or_raise(status), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+
     def encode_packed_device(self, codebook, text, text_index, out, out_index, status=None):
         """Record b: text[text_index[b] : text_index[b + 1]] -> its body under `codebook` at out[out_index[b] : out_index[b + 1]],
         the bodies back to back from out_index[0] = 0; the scan that lays them out runs on the GPU.  text, out: uint8 CUDA tensors;
@@ -642,7 +645,7 @@ class Context:
         rc = N.lib().et_take_packed_device(self._h, bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n, rows_p, rows.numel(),
                                            self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, rows.numel()),
                                            self._index_ptr(out_text_index, rows.numel()), self._opt_ptr(status), ctypes.byref(res))
-        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+        return self._take_result(rc, res)
 
     def slice_packed_device(self, codebook, bodies, body_index, text_index, rows, first, count, out, out_body_index, out_text_index, stop=None, status=None):
         """Row k of the NEW store is text[first : first + count] of record rows[k] of the store (bodies, body_index, text_index:
@@ -670,7 +673,7 @@ class Context:
                                             None if rows is None else self._rows_ptr(rows, what), n_rows, first_p, first_v, count_p, count_v, int(stop),
                                             self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows),
                                             self._index_ptr(out_text_index, n_rows), self._opt_ptr(status), ctypes.byref(res))
-        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+        return self._take_result(rc, res)
 
     def field_packed_device(self, codebook, bodies, body_index, text_index, rows, field, n_fields, delim, out, out_body_index, out_text_index, pos=None, status=None):
         """Row k of the NEW store is delim.join(text.split(delim)[field : field + n_fields]) of record rows[k] of the store (bodies,
@@ -700,7 +703,7 @@ class Context:
                                             self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows),
                                             self._index_ptr(out_text_index, n_rows), None if pos is None else self._rows_ptr(pos, what), self._opt_ptr(status),
                                             ctypes.byref(res))
-        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+        return self._take_result(rc, res)
 
     def concat_packed_device(self, codebook, a, sep, b, out, out_body_index, out_text_index, rows_a=None, rows_b=None, status=None):
         """Row k of the NEW store is text(A[rows_a[k]]) + sep + text(B[rows_b[k]]), text() the record's stored text -- row-wise string
@@ -733,7 +736,7 @@ class Context:
         rc = N.lib().et_concat_packed_device(self._h, ctypes.byref(codebook.raw), *sides[:6], sep_p, sep_a.size, *sides[6:], n_rows, self._opt_ptr(out),
                                              0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows), self._index_ptr(out_text_index, n_rows),
                                              self._opt_ptr(status), ctypes.byref(res))
-        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+        return self._take_result(rc, res)
 
     def recode_packed_device(self, codebook_in, codebook_out, bodies, body_index, text_index, rows, out, out_body_index, out_text_index, byte_map=None, status=None):
         """Row k of the NEW store is the stored text of record rows[k] of the store (bodies, body_index, text_index:
@@ -762,7 +765,7 @@ class Context:
                                              self._index_ptr(body_index, n), self._index_ptr(text_index), n, None if rows is None else self._rows_ptr(rows), n_rows,
                                              self._opt_ptr(out), 0 if out is None else out.numel(), self._index_ptr(out_body_index, n_rows),
                                              self._index_ptr(out_text_index, n_rows), self._opt_ptr(status), ctypes.byref(res))
-        return TakeResult(self._cap_or_raise(rc), res.out_bytes, res.text_bytes, res.n_failed, res.first_failed, res.first_status)
+        return self._take_result(rc, res)
 
     def _packed_upload(self, blob, index):
         """-> (the bytes on the device, in a tensor that is never empty: one spare byte behind an empty blob; the offsets)."""
@@ -904,70 +907,86 @@ class Context:
             raise EntreepyError(res.first_key_status, f"join_packed: key {res.first_key_failed}")
         return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
 
+    # What the list helpers of the store-deriving calls (take, slice, field, concat, recode) share.
+    @staticmethod
+    def _store_arrays(out_index, lengths):
+        """decode_packed's offsets and lengths as numpy u64 arrays."""
+        out_index = np.asarray(out_index, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        assert out_index.size == lengths.size + 1
+        return out_index, lengths
+
+    def _store_upload(self, blob, out_index, lengths):
+        """-> (bodies, body_index, text_index) on the device, as take_packed_device takes a store; text_index from the lengths."""
+        import torch
+
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        return d_blob, d_body_index, torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
+
+    @staticmethod
+    def _per_row(v, n_rows, dev):
+        """A per-row argument: an int for every row as it is, a list of one value per row as a device tensor."""
+        import torch
+
+        if isinstance(v, (int, np.integer)):
+            return int(v)
+        v = np.ascontiguousarray(v, dtype=np.uint32)
+        assert v.size == n_rows
+        return torch.from_numpy(v.view(np.int32)).to(dev)
+
+    @staticmethod
+    def _bodies_room(out_index, lengths, rows):
+        """The bytes of the rows' bodies: room for a result that is no longer than they are.  (A row beyond the store fails in the
+        call, and takes none.)"""
+        good = rows[rows < lengths.size]
+        return int((out_index[good + 1] - out_index[good]).sum())
+
+    @staticmethod
+    def _new_store(room, n_rows, dev):
+        """-> (out, out_body_index, out_text_index) for a call: `room` bytes, or None for sizes only, and the new index pair."""
+        import torch
+
+        d_out = None if room is None else torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
+        return d_out, torch.empty(n_rows + 1, dtype=torch.int64, device=dev), torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+
+    def _store_download(self, what, res, d_out, d_new_index, d_new_text):
+        """The end of a list helper: raises for the call or its first failed row, then -> (bodies, offsets, lengths) on the host."""
+        _check(res.status, self._h)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"{what}: row {res.first_failed}")
+        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
+        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+
     def take_packed(self, blob, out_index, lengths, rows):
         """decode_packed's store and a list of record numbers (any order, repeats allowed) -> (the bodies of those records back to back
         as bytes, their offsets as a numpy u64 array of len(rows) + 1, their lengths as a numpy u64 array): a store of the same form,
         as encode_packed of those records' texts gives it, through one take_packed_device call."""
-        import torch
-
-        out_index = np.asarray(out_index, dtype=np.uint64)
-        lengths = np.asarray(lengths, dtype=np.uint64)
+        out_index, lengths = self._store_arrays(out_index, lengths)
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        assert out_index.size == lengths.size + 1
         if not rows.size:
             return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
-        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
-        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
-        good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none)
-        room = int((out_index[good + 1] - out_index[good]).sum())
-        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=d_blob.device)
-        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        res = self.take_packed_device(d_blob, d_body_index, d_text_index, d_rows, d_out, d_new_index, d_new_text)
-        _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"take_packed: row {res.first_failed}")
-        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
-        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+        store = self._store_upload(blob, out_index, lengths)
+        dev = store[0].device
+        new = self._new_store(self._bodies_room(out_index, lengths, rows), rows.size, dev)
+        res = self.take_packed_device(*store, self._per_row(rows, rows.size, dev), *new)
+        return self._store_download("take_packed", res, *new)
 
     def slice_packed(self, codebook, blob, out_index, lengths, rows, first, count, stop=None):
         """decode_packed's store, a list of record numbers (any order, repeats allowed) and where each row's slice begins and how long
         it is at most (an int for every row, or a list of one per row) -> a store like take_packed's: (the bodies of
         text[first : first + count], cut in front of `stop`, back to back as bytes, their offsets, their lengths), as encode_packed
         of those pieces gives it, through one slice_packed_device call."""
-        import torch
-
-        out_index = np.asarray(out_index, dtype=np.uint64)
-        lengths = np.asarray(lengths, dtype=np.uint64)
+        out_index, lengths = self._store_arrays(out_index, lengths)
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        assert out_index.size == lengths.size + 1
         if not rows.size:
             return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
-        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
-
-        def per_row(v):
-            if isinstance(v, (int, np.integer)):
-                return int(v)
-            v = np.ascontiguousarray(v, dtype=np.uint32)
-            assert v.size == rows.size
-            return torch.from_numpy(v.view(np.int32)).to(d_blob.device)
-
-        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
-        good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none; a slice is no longer than its record's body)
-        room = int((out_index[good + 1] - out_index[good]).sum())
-        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=d_blob.device)
-        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        res = self.slice_packed_device(codebook, d_blob, d_body_index, d_text_index, d_rows, per_row(first), per_row(count), d_out, d_new_index, d_new_text, stop=stop)
-        _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"slice_packed: row {res.first_failed}")
-        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
-        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+        store = self._store_upload(blob, out_index, lengths)
+        dev = store[0].device
+        first, count, d_rows = (self._per_row(v, rows.size, dev) for v in (first, count, rows))
+        new = self._new_store(self._bodies_room(out_index, lengths, rows), rows.size, dev)  # (a slice is no longer than its record's body)
+        res = self.slice_packed_device(codebook, *store, d_rows, first, count, *new, stop=stop)
+        return self._store_download("slice_packed", res, *new)
 
     def field_packed(self, codebook, blob, out_index, lengths, rows, field, n_fields=1, delim=b","):
         """decode_packed's store, a list of record numbers (any order, repeats allowed), each row's first field (from 0) and how many
@@ -977,36 +996,17 @@ class Context:
         is the empty record), through one field_packed_device call."""
         import torch
 
-        out_index = np.asarray(out_index, dtype=np.uint64)
-        lengths = np.asarray(lengths, dtype=np.uint64)
+        out_index, lengths = self._store_arrays(out_index, lengths)
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        assert out_index.size == lengths.size + 1
         if not rows.size:
             return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
-        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
-
-        def per_row(v):
-            if isinstance(v, (int, np.integer)):
-                return int(v)
-            v = np.ascontiguousarray(v, dtype=np.uint32)
-            assert v.size == rows.size
-            return torch.from_numpy(v.view(np.int32)).to(d_blob.device)
-
-        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
-        good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none; a field is no longer than its record's body)
-        room = int((out_index[good + 1] - out_index[good]).sum())
-        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=d_blob.device)
-        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        d_pos = torch.empty(rows.size, dtype=torch.int32, device=d_blob.device)
-        res = self.field_packed_device(codebook, d_blob, d_body_index, d_text_index, d_rows, per_row(field), per_row(n_fields), delim, d_out, d_new_index, d_new_text, pos=d_pos)
-        _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"field_packed: row {res.first_failed}")
-        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
-        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text), d_pos.cpu().numpy().view(np.uint32)
+        store = self._store_upload(blob, out_index, lengths)
+        dev = store[0].device
+        field, n_fields, d_rows = (self._per_row(v, rows.size, dev) for v in (field, n_fields, rows))
+        new = self._new_store(self._bodies_room(out_index, lengths, rows), rows.size, dev)  # (a field is no longer than its record's body)
+        d_pos = torch.empty(rows.size, dtype=torch.int32, device=dev)
+        res = self.field_packed_device(codebook, *store, d_rows, field, n_fields, delim, *new, pos=d_pos)
+        return (*self._store_download("field_packed", res, *new), d_pos.cpu().numpy().view(np.uint32))
 
     def concat_packed(self, codebook, a, sep, b, rows_a=None, rows_b=None):
         """Two stores as decode_packed takes them -- a, b: (blob, out_index, lengths), or None for an absent side -- a literal and a
@@ -1023,31 +1023,20 @@ class Context:
                 d_rows.append(None)
                 continue
             blob, out_index, lengths = store
-            out_index = np.asarray(out_index, dtype=np.uint64)
-            lengths = np.asarray(lengths, dtype=np.uint64)
-            assert out_index.size == lengths.size + 1
-            text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-            d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-            stores.append((d_blob, d_body_index, torch.from_numpy(text_index.view(np.int64)).to(dev)))
+            out_index, lengths = self._store_arrays(out_index, lengths)
+            stores.append(self._store_upload(blob, out_index, lengths))
             rows = np.arange(lengths.size, dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
-            d_rows.append(torch.from_numpy(rows.view(np.int32)).to(dev))
+            d_rows.append(self._per_row(rows, rows.size, dev))
             counts.append(rows.size)
-            good = rows[rows < lengths.size]  # (a row beyond the store fails below, and takes none; a run is no longer than its record's body)
-            room += int((out_index[good + 1] - out_index[good]).sum())
+            room += self._bodies_room(out_index, lengths, rows)  # (a run is no longer than its record's body)
         assert counts and min(counts) == max(counts), "at least one side, and both sides give the same number of rows"
         n_rows = counts[0]
         if not n_rows:
             return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
         room += n_rows * (codebook.body_bound(len(bytes(sep))) + 1)  # (the literal's bits per row, and the byte a row rounds up to)
-        d_out = torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
-        d_new_index = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-        d_new_text = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-        res = self.concat_packed_device(codebook, stores[0], sep, stores[1], d_out, d_new_index, d_new_text, rows_a=d_rows[0], rows_b=d_rows[1])
-        _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"concat_packed: row {res.first_failed}")
-        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
-        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+        new = self._new_store(room, n_rows, dev)
+        res = self.concat_packed_device(codebook, stores[0], sep, stores[1], *new, rows_a=d_rows[0], rows_b=d_rows[1])
+        return self._store_download("concat_packed", res, *new)
 
     def recode_packed(self, codebook_in, codebook_out, blob, out_index, lengths, rows=None, byte_map=None):
         """decode_packed's store under `codebook_in`, a list of record numbers (None: row k is record k) and a map -> a store like
@@ -1056,27 +1045,19 @@ class Context:
         sizes, then the bytes."""
         import torch
 
-        out_index = np.asarray(out_index, dtype=np.uint64)
-        lengths = np.asarray(lengths, dtype=np.uint64)
-        assert out_index.size == lengths.size + 1
+        out_index, lengths = self._store_arrays(out_index, lengths)
         rows = np.arange(lengths.size, dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
         if not rows.size:
             return b"", np.zeros(1, np.uint64), np.zeros(0, np.uint64)
-        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
-        d_rows = torch.from_numpy(rows.view(np.int32)).to(d_blob.device)
-        d_new_index = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        d_new_text = torch.empty(rows.size + 1, dtype=torch.int64, device=d_blob.device)
-        args = (codebook_in, codebook_out, d_blob, d_body_index, d_text_index, d_rows)
-        sizes = self.recode_packed_device(*args, None, d_new_index, d_new_text, byte_map=byte_map)  # (a new body may be longer than the old: ask)
-        d_out = torch.empty(max(sizes.out_bytes, 1), dtype=torch.uint8, device=d_blob.device)
-        res = self.recode_packed_device(*args, d_out, d_new_index, d_new_text, byte_map=byte_map)
-        _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"recode_packed: row {res.first_failed}")
-        new_text = d_new_text.cpu().numpy().view(np.uint64)  # (the copies run behind the call's kernels)
-        return d_out[: res.out_bytes].cpu().numpy().tobytes(), d_new_index.cpu().numpy().view(np.uint64), np.diff(new_text)
+        store = self._store_upload(blob, out_index, lengths)
+        dev = store[0].device
+        args = (codebook_in, codebook_out, *store, self._per_row(rows, rows.size, dev))
+        new = self._new_store(None, rows.size, dev)
+        sizes = self.recode_packed_device(*args, *new, byte_map=byte_map)  # (a new body may be longer than the old: ask)
+        new = (torch.empty(max(sizes.out_bytes, 1), dtype=torch.uint8, device=dev), *new[1:])
+        res = self.recode_packed_device(*args, *new, byte_map=byte_map)
+        return self._store_download("recode_packed", res, *new)
+
 
     # -- staged calls (sharded encode) ----------------------------------------------
     def histogram_device(self, text, hist):

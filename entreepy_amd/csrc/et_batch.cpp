@@ -612,35 +612,70 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
     return ET_OK;
 }
 
+// ---- the calls that derive a new packed store from an old one (take, slice, field, concat, recode) ---------------------------
+// A source store as such a call is given it, and what the kernels take it for.
+struct Source {
+    const void *bodies;
+    size_t body_bytes;
+    const uint64_t *body_index, *text_index;
+    size_t n;
+    const uint32_t *rows;  // null: row k is record k
+};
+
+et::PackedStore packed_store(const Source &s) { return et::PackedStore{s.bodies, s.body_bytes, s.body_index, s.text_index, static_cast<uint32_t>(s.n), 0}; }
+
+// The head of such a call, behind the null check of what is the call's own: one source against the rows and the output, the checks
+// in THIS order.  unaligned4: one of the call's own per-row arrays is not 4-byte aligned.  The texts that differ between the calls:
+struct SourceTexts {
+    const char *unaligned4, *too_many, *without_rows, *overlap;
+};
+constexpr const char *ROWS_ARE_RECORDS = "without d_rows, row k is record k: n_rows must be n_records";
+
+int source_args(et_ctx *ctx, const Source &s, size_t n_rows, bool unaligned4, const void *d_out, size_t cap, const uint64_t *d_out_body_index, const uint64_t *d_out_text_index,
+                const SourceTexts &t) {
+    if (!s.bodies || !s.body_index || !s.text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (misaligned(7, s.body_index, s.text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (unaligned4 || misaligned(3, s.rows)) return fail(ctx, ET_ERR_ARG, t.unaligned4);
+    if (s.n > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, t.too_many);
+    if (!s.rows && n_rows != s.n) return fail(ctx, ET_ERR_ARG, t.without_rows);
+    if (d_out && cap && s.body_bytes) {  // (deriving in place is not these calls')
+        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(s.bodies);
+        if (o < b + s.body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, t.overlap);
+    }
+    return ET_OK;
+}
+
+// ... and its tail, behind the launches: the poll (`never`: the call's message), the report into *res; ET_ERR_CAP (`too_much`)
+// when d_out was given and the report exceeds cap -- the call's last kernels saw the same two figures.
+int derived_end(et_ctx *ctx, uint64_t epoch, et_take_result *res, const void *d_out, uint64_t cap, const char *never, const char *too_much) {
+    ET_TRY(packed_poll(ctx, epoch, never));
+    const uint64_t *rep = report_words(ctx);
+    res->out_bytes = rep[et::PACKED_BYTES];
+    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, too_much);
+    return ET_OK;
+}
+
 extern "C" size_t et_take_result_size(void) { return sizeof(et_take_result); }
 
 extern "C" int et_take_packed_device(et_ctx *ctx, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index, const uint64_t *d_text_index, size_t n_records,
                                      const uint32_t *d_rows, size_t n_rows, void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index, uint8_t *d_status,
                                      et_take_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!res || !d_bodies || !d_body_index || !d_text_index || !d_rows || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
-    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
-    if (d_out && cap && body_bytes) {  // (in-place compaction is not this call's)
-        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
-        if (o < b + body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps d_bodies");
-    }
+    if (!res || !d_rows || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, d_rows};
+    ET_TRY(source_args(ctx, src, n_rows, false, d_out, cap, d_out_body_index, d_out_text_index,
+                       {"the rows are not 4-byte aligned", "too many records or rows", ROWS_ARE_RECORDS, "d_out overlaps d_bodies"}));
     *res = et_take_result{};
     if (n_rows == 0) return ET_OK;
     DeviceGuard guard(ctx->device);
     ET_TRY(packed_ensure(ctx, PK_SIZES + n_rows * sizeof(et::TakeRow)));
     ET_HIP(hipMemcpyAsync(ws<uint8_t>(ctx, PK_STATS), first_counters(ctx), PK_COUNTER_BYTES, hipMemcpyHostToDevice, ctx->stream));
     const et::PackedReport report = next_report(ctx);
-    et::launch_take(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, d_rows, static_cast<uint32_t>(n_rows),
-                    d_out, cap, d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, PK_SIZES), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the take's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->out_bytes = rep[et::PACKED_BYTES];
-    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the taken bodies need more than cap bytes");  // (k_take_copy saw the same two figures)
-    return ET_OK;
+    et::launch_take(ctx->stream, packed_store(src), d_rows, static_cast<uint32_t>(n_rows), d_out, cap, d_out_body_index, d_out_text_index, d_status,
+                    ws<et::TakeRow>(ctx, PK_SIZES), report);
+    return derived_end(ctx, report.epoch, res, d_out, cap, "the take's report never reached the host", "the taken bodies need more than cap bytes");
 }
 
 extern "C" size_t et_slice_lane_bytes(void) { return et::SLICE_LANE_BYTES; }
@@ -650,15 +685,10 @@ extern "C" int et_slice_packed_device(et_ctx *ctx, const et_codebook *cb, const 
                                       const uint32_t *d_count, uint32_t count, int stop, void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
                                       uint8_t *d_status, et_take_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_rows, d_first, d_count)) return fail(ctx, ET_ERR_ARG, "the rows, the firsts or the counts are not 4-byte aligned");
-    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
-    if (!d_rows && n_rows != n_records) return fail(ctx, ET_ERR_ARG, "without d_rows, row k is record k: n_rows must be n_records");
-    if (d_out && cap && body_bytes) {  // (slicing in place is not this call's)
-        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
-        if (o < b + body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps d_bodies");
-    }
+    if (!cb || !res || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, d_rows};
+    ET_TRY(source_args(ctx, src, n_rows, misaligned(3, d_first, d_count), d_out, cap, d_out_body_index, d_out_text_index,
+                       {"the rows, the firsts or the counts are not 4-byte aligned", "too many records or rows", ROWS_ARE_RECORDS, "d_out overlaps d_bodies"}));
     if (stop < ET_SLICE_NO_STOP || stop > 255) return fail(ctx, ET_ERR_ARG, "stop is a byte, or ET_SLICE_NO_STOP");
     *res = et_take_result{};
     if (n_rows == 0) return ET_OK;
@@ -675,15 +705,9 @@ extern "C" int et_slice_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     job.count = count;
     job.stop = stop < 0 ? et::SLICE_NO_STOP : static_cast<uint32_t>(stop);  // (a byte without a code is no symbol of the table: it cuts nothing)
     const et::PackedReport report = next_report(ctx);
-    et::launch_slice(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, ws<const uint2>(ctx, 0), n_codes, job,
-                     d_out, cap, d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, PK_SIZES), ws<uint32_t>(ctx, PK_SIZES + n_rows * sizeof(et::TakeRow)), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the slice's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->out_bytes = rep[et::PACKED_BYTES];
-    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the slices need more than cap bytes");  // (k_take_copy saw the same two figures)
-    return ET_OK;
+    et::launch_slice(ctx->stream, packed_store(src), ws<const uint2>(ctx, 0), n_codes, job, d_out, cap, d_out_body_index, d_out_text_index, d_status,
+                     ws<et::TakeRow>(ctx, PK_SIZES), ws<uint32_t>(ctx, PK_SIZES + n_rows * sizeof(et::TakeRow)), report);
+    return derived_end(ctx, report.epoch, res, d_out, cap, "the slice's report never reached the host", "the slices need more than cap bytes");
 }
 
 extern "C" size_t et_field_lane_bytes(void) { return et::FIELD_LANE_BYTES; }
@@ -693,15 +717,10 @@ extern "C" int et_field_packed_device(et_ctx *ctx, const et_codebook *cb, const 
                                       const uint32_t *d_n_fields, uint32_t n_fields, int delim, void *d_out, size_t cap, uint64_t *d_out_body_index,
                                       uint64_t *d_out_text_index, uint32_t *d_pos, uint8_t *d_status, et_take_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_rows, d_field, d_n_fields, d_pos)) return fail(ctx, ET_ERR_ARG, "the rows, the fields, the field counts or the positions are not 4-byte aligned");
-    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
-    if (!d_rows && n_rows != n_records) return fail(ctx, ET_ERR_ARG, "without d_rows, row k is record k: n_rows must be n_records");
-    if (d_out && cap && body_bytes) {  // (cutting in place is not this call's)
-        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
-        if (o < b + body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps d_bodies");
-    }
+    if (!cb || !res || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, d_rows};
+    ET_TRY(source_args(ctx, src, n_rows, misaligned(3, d_field, d_n_fields, d_pos), d_out, cap, d_out_body_index, d_out_text_index,
+                       {"the rows, the fields, the field counts or the positions are not 4-byte aligned", "too many records or rows", ROWS_ARE_RECORDS, "d_out overlaps d_bodies"}));
     if (delim < 0 || delim > 255) return fail(ctx, ET_ERR_ARG, "delim is a byte");
     *res = et_take_result{};
     if (n_rows == 0) return ET_OK;
@@ -719,15 +738,9 @@ extern "C" int et_field_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     job.n_fields = n_fields;
     job.delim = static_cast<uint32_t>(delim);  // (a byte without a code is no symbol of the table: it occurs nowhere)
     const et::PackedReport report = next_report(ctx);
-    et::launch_field(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, ws<const uint2>(ctx, 0), n_codes, job,
-                     d_out, cap, d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, PK_SIZES), ws<uint32_t>(ctx, PK_SIZES + n_rows * sizeof(et::TakeRow)), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the field call's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->out_bytes = rep[et::PACKED_BYTES];
-    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the fields need more than cap bytes");  // (k_take_copy saw the same two figures)
-    return ET_OK;
+    et::launch_field(ctx->stream, packed_store(src), ws<const uint2>(ctx, 0), n_codes, job, d_out, cap, d_out_body_index, d_out_text_index, d_status,
+                     ws<et::TakeRow>(ctx, PK_SIZES), ws<uint32_t>(ctx, PK_SIZES + n_rows * sizeof(et::TakeRow)), report);
+    return derived_end(ctx, report.epoch, res, d_out, cap, "the field call's report never reached the host", "the fields need more than cap bytes");
 }
 
 extern "C" size_t et_concat_sep_max(void) { return et::CONCAT_SEP_MAX; }
@@ -744,24 +757,16 @@ extern "C" int et_concat_packed_device(et_ctx *ctx, const et_codebook *cb, const
     if (!ctx) return ET_ERR_ARG;
     if (!cb || !res || !d_out_body_index || !d_out_text_index || (!sep && sep_len)) return fail(ctx, ET_ERR_ARG, "null pointer");
     if (!d_a_bodies && !d_b_bodies) return fail(ctx, ET_ERR_ARG, "both sides are absent");
-    struct Side { const void *bodies; size_t body_bytes; const uint64_t *body_index, *text_index; size_t n; const uint32_t *rows; };
-    const Side sides[2] = {{d_a_bodies, a_body_bytes, d_a_body_index, d_a_text_index, n_a, d_rows_a}, {d_b_bodies, b_body_bytes, d_b_body_index, d_b_text_index, n_b, d_rows_b}};
+    const Source sides[2] = {{d_a_bodies, a_body_bytes, d_a_body_index, d_a_text_index, n_a, d_rows_a}, {d_b_bodies, b_body_bytes, d_b_body_index, d_b_text_index, n_b, d_rows_b}};
     if (misaligned(7, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
     if (n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many rows");
-    for (const Side &s : sides) {
+    for (const Source &s : sides) {
         if (!s.bodies) {  // an absent side: no records, no offsets (its rows are not looked at)
             if (s.n || s.body_bytes || s.body_index || s.text_index) return fail(ctx, ET_ERR_ARG, "an absent side has no records, no bytes and no offset arrays");
             continue;
         }
-        if (!s.body_index || !s.text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-        if (misaligned(7, s.body_index, s.text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-        if (misaligned(3, s.rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
-        if (s.n > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
-        if (!s.rows && n_rows != s.n) return fail(ctx, ET_ERR_ARG, "without d_rows, row k is record k: n_rows must be that side's n");
-        if (d_out && cap && s.body_bytes) {  // (concatenating in place is not this call's)
-            const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(s.bodies);
-            if (o < b + s.body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps a side's bodies");
-        }
+        ET_TRY(source_args(ctx, s, n_rows, false, d_out, cap, d_out_body_index, d_out_text_index,
+                           {"the rows are not 4-byte aligned", "too many records", "without d_rows, row k is record k: n_rows must be that side's n", "d_out overlaps a side's bodies"}));
     }
     if (sep_len > et::CONCAT_SEP_MAX) return fail(ctx, ET_ERR_ARG, "the literal is longer than et_concat_sep_max()");
     *res = et_take_result{};
@@ -792,16 +797,9 @@ extern "C" int et_concat_packed_device(et_ctx *ctx, const et_codebook *cb, const
     job.sep_bits = static_cast<uint32_t>(bits);
     job.sep_len = static_cast<uint32_t>(sep_len);
     const et::PackedReport report = next_report(ctx);
-    et::launch_concat(ctx->stream, et::PackedStore{d_a_bodies, a_body_bytes, d_a_body_index, d_a_text_index, static_cast<uint32_t>(n_a), 0},
-                      et::PackedStore{d_b_bodies, b_body_bytes, d_b_body_index, d_b_text_index, static_cast<uint32_t>(n_b), 0}, ws<const uint2>(ctx, 0), n_codes, job, d_out, cap,
-                      d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, at_plan), ws<uint32_t>(ctx, at_list), ws<et::ConcatPiece>(ctx, at_pieces), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the concat's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->out_bytes = rep[et::PACKED_BYTES];
-    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the rows need more than cap bytes");  // (k_concat_copy saw the same two figures)
-    return ET_OK;
+    et::launch_concat(ctx->stream, packed_store(sides[0]), packed_store(sides[1]), ws<const uint2>(ctx, 0), n_codes, job, d_out, cap, d_out_body_index, d_out_text_index, d_status,
+                      ws<et::TakeRow>(ctx, at_plan), ws<uint32_t>(ctx, at_list), ws<et::ConcatPiece>(ctx, at_pieces), report);
+    return derived_end(ctx, report.epoch, res, d_out, cap, "the concat's report never reached the host", "the rows need more than cap bytes");
 }
 
 extern "C" size_t et_recode_lane_bytes(void) { return et::RECODE_LANE_BYTES; }
@@ -812,15 +810,10 @@ extern "C" int et_recode_packed_device(et_ctx *ctx, const et_codebook *cb_in, co
                                        const uint64_t *d_body_index, const uint64_t *d_text_index, size_t n_records, const uint32_t *d_rows, size_t n_rows, void *d_out,
                                        size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index, uint8_t *d_status, et_take_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!cb_in || !cb_out || !res || !d_bodies || !d_body_index || !d_text_index || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index, d_out_body_index, d_out_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
-    if (n_records > 0x7fffffffu || n_rows > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records or rows");
-    if (!d_rows && n_rows != n_records) return fail(ctx, ET_ERR_ARG, "without d_rows, row k is record k: n_rows must be n_records");
-    if (d_out && cap && body_bytes) {  // (recoding in place is not this call's)
-        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_bodies);
-        if (o < b + body_bytes && b < o + cap) return fail(ctx, ET_ERR_ARG, "d_out overlaps d_bodies");
-    }
+    if (!cb_in || !cb_out || !res || !d_out_body_index || !d_out_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, d_rows};
+    ET_TRY(source_args(ctx, src, n_rows, false, d_out, cap, d_out_body_index, d_out_text_index,
+                       {"the rows are not 4-byte aligned", "too many records or rows", ROWS_ARE_RECORDS, "d_out overlaps d_bodies"}));
     if (map)
         for (int s = 0; s < 256; ++s)
             if (map[s] < ET_RECODE_DROP || map[s] > 255) return fail(ctx, ET_ERR_ARG, "a map entry is a byte, or ET_RECODE_DROP");
@@ -850,16 +843,11 @@ extern "C" int et_recode_packed_device(et_ctx *ctx, const et_codebook *cb_in, co
     job.out_tab = ws<const uint2>(ctx, PK_PATTERN);
     job.n_rows = static_cast<uint32_t>(n_rows);
     const et::PackedReport report = next_report(ctx);
-    et::launch_recode(ctx->stream, et::PackedStore{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0}, ws<const uint2>(ctx, 0), n_codes, job,
-                      d_out, cap, d_out_body_index, d_out_text_index, d_status, ws<et::TakeRow>(ctx, at_plan), ws<uint32_t>(ctx, at_list), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the recode's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->out_bytes = rep[et::PACKED_BYTES];
-    res->text_bytes = rep[et::TAKE_TEXT_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_out && res->out_bytes > cap) return fail(ctx, ET_ERR_CAP, "the recoded rows need more than cap bytes");  // (both writes saw the same two figures)
-    return ET_OK;
+    et::launch_recode(ctx->stream, packed_store(src), ws<const uint2>(ctx, 0), n_codes, job, d_out, cap, d_out_body_index, d_out_text_index, d_status,
+                      ws<et::TakeRow>(ctx, at_plan), ws<uint32_t>(ctx, at_list), report);
+    return derived_end(ctx, report.epoch, res, d_out, cap, "the recode's report never reached the host", "the recoded rows need more than cap bytes");
 }
+
 
 extern "C" int et_selftest_join_hash(et_ctx *ctx, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index, const uint64_t *d_text_index, size_t n,
                                      uint64_t *d_hash) {

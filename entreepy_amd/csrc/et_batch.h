@@ -263,15 +263,21 @@ enum TakeWord { TAKE_TEXT_BYTES = 3 };       // the report's word beside PACKED_
 void launch_take(hipStream_t stream, const PackedStore &store, const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index,
                  uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, const PackedReport &report);
 
+// The derived stores -- the slice, the field, the concat and the recode below -- share one frame, stated once in et_batch.hip: a plan
+// kernel is plan_rows (a row per lane: judge_row, reach_body, lane_walks; the lane's walk is lane_walk; the status byte, the tally, the
+// wavefront's rows onto long_list with one atomic), a long kernel is long_rows (a listed row per workgroup, the list strided, nothing set
+// up beyond the list; settle_block per 8 KiB block, reduce_min_min_max, cut_at_length, fail_row_late).  What is said of a kernel below
+// is its family's middle.  The counters' word for the list is SLICE_N_LONG for all four.
+//
 // The slice (et_slice_packed_device): symbols [first, first + count) of rows[]' stored texts, cut in front of a stop byte, as a NEW
 // packed store -- under one complete prefix-free table a substring is the run of bits between two codeword boundaries, so the body the
 // encoder would write for it is that run shifted to bit 7 of a byte, its last byte padded with zeros.  The search's walk finds the two
 // boundaries, the take's scan lays the rows out and the take's copy, reading bits for bytes, writes them.
-//   k_slice_plan  one row per lane, the sorted codes and the first-level table in LDS: judged as k_take_plan judges, its status byte;
+//   k_slice_plan  plan_rows, the sorted codes and the first-level table in LDS: judged as k_take_plan judges (judge_row);
 //                 a body of which the slice's end can reach up to SLICE_LANE_BYTES (clip_body: 4 bytes per symbol in front of the end)
 //                 is walked by its lane alone, from global memory, the walk ending where the slice does; a longer one goes onto a list
 //                 and is an empty row for now; a TakeRow per row: {bytes of the new body, symbols, where its first BIT lies}
-//   k_slice_long  one workgroup per listed row (k_search_long's shape): the blocks in front of the slice's end settled by a counting
+//   k_slice_long  long_rows: the blocks in front of the slice's end settled by a counting
 //                 walk, the lanes whose codewords meet [first, end) walk again; begin, end and the lowest stop reduced over the
 //                 workgroup; thread 0 stores the row's TakeRow
 //   k_take_scan   the take's, unchanged: its report is the call's
@@ -304,15 +310,15 @@ void launch_slice(hipStream_t stream, const PackedStore &store, const uint2 *cod
 // packed store -- under one complete prefix-free table a delimiter is a codeword boundary whose codeword decodes to `delim`, so a run
 // of fields is the run of bits between two such boundaries and is written exactly as a slice is.  The walk counts the delimiters it
 // steps over; a codeword at or behind the record's length is no symbol of the stored text and is never counted.
-//   k_field_plan  k_slice_plan's frame: a body (clip_body of the whole length: nothing bounds where field k lies) up to
+//   k_field_plan  plan_rows: a body (clip_body of the whole length: nothing bounds where field k lies) up to
 //                 FIELD_LANE_BYTES is walked by its lane alone with a running delimiter count, the walk ending at the closing
 //                 delimiter; a longer one goes onto a list; a TakeRow per row in the slice's form, and d_pos
-//   k_field_long  one workgroup per listed row (k_slice_long's shape): per block the settling walk counts each lane's delimiters, a
+//   k_field_long  long_rows: per block the settling walk counts each lane's delimiters, a
 //                 second scan numbers them across the lanes, the count carried across the blocks beside the codewords'; the lanes
 //                 that hold one of the two target delimiters walk again; begin, closing delimiter and the text's end reduced over the
 //                 workgroup; thread 0 stores the row's TakeRow and d_pos
 //   k_take_scan, k_take_copy<BITS>   the slice's, unchanged
-// FIELD_LANE_BYTES is the search's threshold, kept: the lane's walk is slice_lane's with a counter.
+// FIELD_LANE_BYTES is the search's threshold, kept: the lane's walk is the slice's (lane_walk) with a counter.
 #ifndef ET_FIELD_LANE_BYTES  // (a build for the sweep sets it, as ET_SEARCH_LANE_BYTES)
 #define ET_FIELD_LANE_BYTES ET_SEARCH_LANE_BYTES
 #endif
@@ -325,7 +331,7 @@ struct FieldJob {
     uint32_t n_rows, field, n_fields;
     uint32_t delim;                         // the delimiter byte
 };
-// codes, plan, long_list: as launch_slice's (the counters' word for the list is the slice's, SLICE_N_LONG).
+// codes, plan, long_list: as launch_slice's.
 void launch_field(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const FieldJob &job, void *d_out, uint64_t cap,
                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
 
@@ -334,16 +340,16 @@ void launch_field(hipStream_t stream, const PackedStore &store, const uint2 *cod
 // of bits laid end to end: the left record's stored text (its pad dropped), the literal (et_encode_pattern, in the workspace), the
 // right record's stored text.  Both sides are walked to the end of their stored text, as the slice walks; the row's length is the
 // symbols of the three.  Either store may be absent (no bodies).
-//   k_concat_plan  k_slice_plan's frame over pairs of records: both judged as k_take_plan judges, the row's status byte (the left's
+//   k_concat_plan  plan_rows over pairs of records: both judged as k_take_plan judges (judge_row), the row's status byte (the left's
 //                  unless OK, else the right's, else PACKED_UNSUPPORTED for a new length above BATCH_SMALL_MAX); each side's body
 //                  (clip_body of its length) up to CONCAT_LANE_BYTES is walked by the row's lane to the end of its stored text; a row
 //                  with a longer one goes onto a list, that run absent for now; a TakeRow {new bytes, new length} and a ConcatPiece per row
-//   k_concat_long  one workgroup per listed row: the slice's counting walk to the end of each stored text the lane left, one after
+//   k_concat_long  long_rows: the slice's counting walk (slice_stream) to the end of each stored text the lane left, one after
 //                  the other; thread 0 completes the row's two records -- and fails the row where the length it found is above the limit
 //   k_take_scan    the take's, unchanged: its report is the call's
 //   k_concat_copy  (unless d_out is null: sizes only) k_take_copy's tiles, rows and stores; a row's bytes are the OR of its runs, each
 //                  a funnel shift of the source bytes that hold its bits to the destination BIT the run begins at
-// CONCAT_LANE_BYTES is the search's threshold, kept: the lane's walk is slice_lane itself; no sweep of its own.
+// CONCAT_LANE_BYTES is the search's threshold, kept: the lane's walk is the slice's own (slice_lane); no sweep of its own.
 #ifndef ET_CONCAT_LANE_BYTES  // (a build for the sweep sets it, as ET_SEARCH_LANE_BYTES)
 #define ET_CONCAT_LANE_BYTES ET_SEARCH_LANE_BYTES
 #endif
@@ -366,7 +372,7 @@ struct ConcatJob {
     uint32_t sep_bits, sep_len;       // its bits; its bytes of text
     uint32_t pad;
 };
-// codes, plan, long_list: as launch_slice's (the counters' word for the list is the slice's); pieces: n_rows ConcatPiece of workspace
+// codes, plan, long_list: as launch_slice's; pieces: n_rows ConcatPiece of workspace
 // (16-byte aligned).  a.bodies or b.bodies null: that side is absent.  The report leaves with the scan, in front of the copy.
 void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &b, const uint2 *codes, uint32_t n_codes, const ConcatJob &job, void *d_out, uint64_t cap,
                    uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, ConcatPiece *pieces, const PackedReport &report);
@@ -377,17 +383,17 @@ void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &
 // every symbol s of the stored text the codeword of map[s] under OUT is laid behind the one before.  The first packed call whose
 // output bits are no copy of input bits, and the first with two tables; the map costs the device nothing: the host composes it with
 // OUT into ONE table indexed by the INPUT symbol (RecodeEntry below).  Five launches, three for a sizes-only call:
-//   k_recode_plan   k_slice_plan's frame: judged as k_take_plan judges, its status byte; a body (clip_body of the whole length) up to
+//   k_recode_plan   plan_rows: judged as k_take_plan judges (judge_row); a body (clip_body of the whole length) up to
 //                   RECODE_LANE_BYTES is walked by its lane to the end of its stored text, summing output bits, kept symbols and the
 //                   "uncoded" flag; a longer one goes onto a list; a TakeRow per row: {new bytes, new length, new BITS}
-//   k_recode_long   one workgroup per listed row: the blocks settled by a walk whose visitor sums the same three per lane, the lane
-//                   in which symbol `length` falls walks again, cut there; the totals carried across the blocks; thread 0 stores the
+//   k_recode_long   long_rows: the blocks settled by a walk whose visitor sums the same three per lane, the lane in which symbol
+//                   `length` falls walks again, cut there (cut_at_length); the totals carried across the blocks; thread 0 stores the
 //                   row's TakeRow, or fails the row where a kept symbol has no code
 //   k_take_scan     the take's, unchanged: its report is the call's
 //   k_recode_write  (unless d_out is null: sizes only) one lane per row the lane has planned: the walk again, the codes into a 64-bit
 //                   accumulator that begins at the destination's aligned word; whole words leave as dword stores, the row's first and
 //                   last word clipped to its bytes
-//   k_recode_write_long   (likewise) one workgroup per listed row, block by block: settled, the lanes' output bits scanned to each
+//   k_recode_write_long   (likewise) long_rows, block by block: settled and cut, the lanes' output bits scanned to each
 //                   lane's destination bit, the lanes walk again and OR their codes into an LDS bit image (pack_round's inner loop),
 //                   flushed in rounds of RECODE_ROUND_BITS destination bits -- a block of 1-bit codes becomes 256 KiB of 32-bit ones
 //                   --, the partial word carried as `pending` (pack_rounds' hand-over)
@@ -410,8 +416,8 @@ struct RecodeJob {
     const uint2 *out_tab;  // 256 RecodeEntry-shaped pairs on the device (16-byte aligned)
     uint32_t n_rows, pad;
 };
-// codes: the sorted codes of table IN on the device (launch_shared_decode's); plan, long_list: as launch_slice's (the counters' word
-// for the list is the slice's, SLICE_N_LONG).  The report leaves with the scan, in front of the two writes.
+// codes: the sorted codes of table IN on the device (launch_shared_decode's); plan, long_list: as launch_slice's.
+// The report leaves with the scan, in front of the two writes.
 void launch_recode(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const RecodeJob &job, void *d_out, uint64_t cap,
                    uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
 

@@ -1858,14 +1858,169 @@ __global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_
 }
 
 // --------------------------------------------------------------------------------
+// The derived stores: the slice, the field, the concat and the recode each make a NEW packed store out of rows[] of an old one on the
+// compressed bytes, and share the frame that is stated here once.
+//   plan_rows   a row per lane: the row is judged (judge_row), what the ask can reach of its body is taken (reach_body), and a body
+//               up to the family's threshold (lane_walks) is walked by that lane from global memory (lane_walk); a longer one goes
+//               onto long_list -- one atomic per wavefront that has any -- and is the empty record for now
+//   long_rows   a listed row per workgroup, the list strided: the body settled block by block (settle_block), what the lanes found
+//               reduced (reduce_min_min_max) or scanned, a lane that reaches the record's length cut there (cut_at_length); thread 0
+//               stores the row's TakeRow, or fails the row (fail_row_late): the plan kernel left the empty record there and held the
+//               row for OK, and k_take_scan runs behind both kernels
+// A family below is its middle: what it asks of a row, and what its walks note.
+// Every loop is bounded as the search's are: a lane's walk by the symbols its caller allows (a trip per symbol, at most the record's
+// length), the workgroup's by the blocks of what the reach leaves of the body, its fixed point by 256 trips and a lane's walk inside
+// it by its 256 bits.  No workgroup waits for another: a long kernel stores what belongs to its own row and nothing else.
+// --------------------------------------------------------------------------------
+// Row k's record as the take judges it: judge_record, and a body above TAKE_BODY_MAX is unsupported too.  rows null: row k is record
+// k.  A store without bodies (the concat's absent side) contributes an OK record of nothing and is not looked at.
+__device__ __forceinline__ Judged judge_row(const PackedStore &store, const uint32_t *rows, uint32_t k) {
+    if (!store.bodies) return Judged{PACKED_OK, 0, 0, 0};
+    Judged rec = judge_record(store, rows ? rows[k] : k);
+    if (!rec.status && rec.nb > TAKE_BODY_MAX) rec.status = PACKED_UNSUPPORTED;
+    return rec;
+}
+
+// A judged record whose body is read: one kept raw, or empty, has the empty stored text.
+__device__ __forceinline__ bool stored_text(const Judged &rec) { return !rec.status && rec.nb && rec.len; }
+
+// What the walks look at of such a record when nothing behind symbol `reach` is asked for (clip_body: 4 bytes per symbol in front
+// of it), and whether its lane walks that alone.
+__device__ __forceinline__ BodyBits reach_body(const PackedStore &store, const Judged &rec, uint64_t reach) {
+    return body_bits_of(static_cast<const uint8_t *>(store.bodies), rec.b0, static_cast<uint32_t>(clip_body(rec.nb, reach)));
+}
+
+__device__ __forceinline__ bool lane_walks(const BodyBits &g, uint32_t lane_bytes) { return g.end_bit - g.first_bit <= lane_bytes * 8; }
+
+__device__ __forceinline__ void store_row(TakeRow *__restrict__ plan, uint32_t k, uint4 row) { reinterpret_cast<uint4 *>(plan)[k] = row; }  // (TakeRow as it lies in memory)
+
+// The plan frame: row(k) does a row's work -- its TakeRow included -- and returns its status and whether it goes onto long_list; the
+// frame stores the status byte, tallies, and appends the wavefront's long rows with one atomic.  The caller has its tables in LDS
+// and a barrier behind them.  LDS: 8 words.
+struct RowPlan {
+    uint32_t status;
+    bool is_long;
+};
+
+template <class Row>
+__device__ __forceinline__ void plan_rows(uint32_t n_rows, uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats, Row &&row) {
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    const uint32_t lane = threadIdx.x & 63;
+    PackedTally tally;
+    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
+        bool is_long = false;
+        if (k < n_rows) {
+            const RowPlan p = row(k);
+            is_long = p.is_long;
+            if (d_status) d_status[k] = static_cast<uint8_t>(p.status);
+            tally.note(k, p.status);
+        }
+        const unsigned long long longs = __ballot(is_long);
+        if (longs) {  // (the same for the whole wavefront)
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
+            at = __shfl(at, 0, 64);
+            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
+        }
+    }
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
+// The long-row frame (k_search_long's shape): a workgroup beyond the list returns before it sets anything up; set_up() then loads
+// the tables once per workgroup -- false: nothing to do in this call, the same for every thread --; row(k) sees the listed rows,
+// strided.  row re-judges its record and skips what the plan kernel never lists; everything in it is the same for every lane.
+template <class SetUp, class Row>
+__device__ __forceinline__ void long_rows(uint32_t n_rows, const uint32_t *__restrict__ long_list, const unsigned long long *__restrict__ stats, SetUp &&set_up, Row &&row) {
+    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
+    if (blockIdx.x >= n_long || !set_up()) return;
+    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
+        const uint32_t k = long_list[i];
+        if (k < n_rows) row(k);  // (the plan kernel lists rows)
+    }
+}
+
+// A row that fails behind its plan kernel, which held it for OK: its status byte and two atomics, by thread 0.
+__device__ __forceinline__ void fail_row_late(uint32_t k, uint32_t status, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    if (d_status) d_status[k] = static_cast<uint8_t>(status);
+    PackedTally tally;
+    tally.note(k, status);
+    tally.add_to(stats);
+}
+
+// One lane, one body of a few words, from global memory (search_lane's shape): a trip per symbol of the stored text, `most` at most.
+// 64 bits of body are kept in registers and move on a word at a time.  visit(idx, pos, meta) sees symbol idx -- its bit, its length
+// << 8 | symbol -- in front of the step over it and ends the walk there by returning false; the stored text ends where the bits run
+// out inside a codeword.  Returns the symbol and the bit at which the walk ended: those of the codeword it did not step over.
+struct LaneEnd {
+    uint32_t idx, pos;
+};
+
+template <class Visit>
+__device__ __forceinline__ LaneEnd lane_walk(const CodeTables &t, uint32_t n_codes, const BodyBits &g, uint32_t most, Visit &&visit) {
+    uint32_t pos = g.first_bit, k = 0, idx = 0;
+    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
+    for (; idx < most; ++idx) {
+        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
+            k = pos >> 5;
+            two = (two << 32) | body_word_be(g, k + 1);
+        }
+        const uint32_t meta = code_at(t, n_codes, static_cast<uint32_t>((two << (pos & 31)) >> 32));
+        if (pos + (meta >> 8) > g.end_bit) break;  // the bits ran out inside this codeword: the stored text ends here
+        if (!visit(idx, pos, meta)) break;
+        pos += meta >> 8;
+    }
+    return LaneEnd{idx, pos};
+}
+
+// Three words of symbol << 32 | bit, one per lane, reduced over the workgroup -- the lowest `a`, the lowest `b`, the highest `c` --
+// by shuffles and through s_red (12 words, free again at the next block's first barrier).  Every lane has the three on return.
+__device__ __forceinline__ void reduce_min_min_max(unsigned long long &a, unsigned long long &b, unsigned long long &c, unsigned long long *s_red) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long oa = __shfl_xor(a, d, 64), ob = __shfl_xor(b, d, 64), oc = __shfl_xor(c, d, 64);
+        if (oa < a) a = oa;
+        if (ob < b) b = ob;
+        if (oc > c) c = oc;
+    }
+    if ((tid & 63) == 0) {
+        s_red[tid >> 6] = a;
+        s_red[4 + (tid >> 6)] = b;
+        s_red[8 + (tid >> 6)] = c;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < BB / 64; ++w) {
+        if (s_red[w] < a) a = s_red[w];
+        if (s_red[4 + w] < b) b = s_red[4 + w];
+        if (s_red[8 + w] > c) c = s_red[8 + w];
+    }
+}
+
+// The cut at the length, behind settle_block: what this lane holds of the STORED TEXT.  THE rule of what counts: codeword number i
+// of a body is a symbol of the stored text when it ends inside the body AND i < length.  The settling visitor does not know its
+// lane's symbol numbers; once the scan has given them (`lo`: the number of the lane's first codeword), the lanes behind `len` hold
+// nothing and `visit` is `fresh` again; the one lane whose codewords reach `len` -- a lane of the text's last block -- walks again
+// with a fresh visitor up to it, so nothing at or behind `len` is ever seen.  Returns the lane's symbols; `visit` holds what they give.
+template <class Visit>
+__device__ __forceinline__ uint32_t cut_at_length(const BatchDecLds &s, uint32_t n_codes, const Settled &b, uint32_t lo, uint32_t len, Visit &visit, const Visit &fresh) {
+    if (lo + b.count <= len) return b.count;  // (lo + count <= 4 * len + 16: no wrap)
+    visit = fresh;
+    if (lo >= len) return 0u;
+    const uint32_t held = len - lo;
+    uint32_t again;
+    (void)walk(s, n_codes, b.used, b.room, &again, [&](uint32_t cnt, uint32_t pos, uint32_t win, uint32_t meta) { return cnt < held && visit(cnt, pos, win, meta); });
+    return held;
+}
+
+// --------------------------------------------------------------------------------
 // The slice call: symbols [first, first + count) of rows[]' stored texts, cut in front of the first `stop` byte among them, as a new
 // packed store.  Under one complete prefix-free table symbols [i, j) of a record are the bits from the boundary of codeword i to the
-// boundary of codeword j, so a slice is found by the search's walk over the boundaries -- nothing compared but the symbol the step
-// yields anyway, nothing written -- and written by the take's scan and copy, the copy reading a run of bits where the take reads a run
-// of bytes.  Four launches in stream order (et_batch.h), the host waiting for the scan alone.
-// Every loop is bounded as the search's are: a lane's walk by the slice's end (a trip per symbol, at most the record's length), the
-// workgroup's by the blocks of what the slice's end can reach of the body, its fixed point by 256 trips and a lane's walk inside it by
-// its 256 bits.  No workgroup waits for another: k_slice_long stores the TakeRow of its own row and nothing else.
+// boundary of codeword j, so a slice is found by a walk over the boundaries -- nothing compared but the symbol the step yields
+// anyway, nothing written -- and written by the take's scan and copy, the copy reading a run of bits where the take reads a run of
+// bytes.  Four launches in stream order (et_batch.h), the host waiting for the scan alone.  The reach of a slice is its end: no
+// block behind it is visited.
 // --------------------------------------------------------------------------------
 // What row k asks of a stored text of at most `len` symbols: [first, end), end <= len; nothing when end <= first.  (first + count does
 // not wrap: 64 bits; ET_SLICE_TO_END lies beyond every length.)
@@ -1892,76 +2047,48 @@ __device__ __forceinline__ uint4 slice_row(const BodyBits &g, const Sliced &sl) 
     return make_uint4(bytes, sl.n, static_cast<uint32_t>(src), static_cast<uint32_t>(src >> 32));
 }
 
-// One lane, one body of a few words, from global memory (search_lane's shape): a trip per symbol in front of the slice's end.  The
-// stored text ends where the bits run out inside a codeword; the slice ends there, at ask.end, or in front of the first `stop` at or
-// behind ask.first.  64 bits of body are kept in registers and move on a word at a time.
+// lane_walk in front of the slice's end: the slice ends where the stored text does, at ask.end, or in front of the first `stop` at
+// or behind ask.first.
 __device__ __forceinline__ Sliced slice_lane(const CodeTables &t, uint32_t n_codes, const BodyBits &g, const SliceAsk &ask, uint32_t stop) {
-    uint32_t pos = g.first_bit, k = 0, begin = 0, idx = 0;
-    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
-    for (; idx < ask.end; ++idx) {
-        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
-            k = pos >> 5;
-            two = (two << 32) | body_word_be(g, k + 1);
-        }
-        const uint32_t meta = code_at(t, n_codes, static_cast<uint32_t>((two << (pos & 31)) >> 32));
-        if (pos + (meta >> 8) > g.end_bit) break;  // the bits ran out inside this codeword: the stored text ends here
+    uint32_t begin = 0;
+    const LaneEnd e = lane_walk(t, n_codes, g, ask.end, [&](uint32_t idx, uint32_t pos, uint32_t meta) {
         if (idx == ask.first) begin = pos;
-        if (idx >= ask.first && (meta & 0xffu) == stop) break;
-        pos += meta >> 8;
-    }
-    return Sliced{begin, pos, idx > ask.first ? idx - ask.first : 0u};
+        return idx < ask.first || (meta & 0xffu) != stop;
+    });
+    return Sliced{begin, e.pos, e.idx > ask.first ? e.idx - ask.first : 0u};
 }
 
-// k_slice_plan: k_take_plan's rows, judgement, status bytes and tally, with the sorted codes and the first-level table in LDS once per
-// workgroup.  A row that asks for nothing, or of a record without bytes or symbols, is the empty record and is not read; a body of
-// which the slice's end can reach up to SLICE_LANE_BYTES is walked by its lane (slice_lane); a longer one goes onto long_list -- one
-// atomic per wavefront that has any -- and is the empty record here: k_slice_long stores its TakeRow.  LDS 6 KiB + 8 words.
+// k_slice_plan: plan_rows with the sorted codes and the first-level table in LDS once per workgroup.  A row that asks for nothing,
+// or of a record without bytes or symbols, is the empty record and is not read; a body of which the slice's end can reach up to
+// SLICE_LANE_BYTES is walked by its lane (slice_lane).  LDS 6 KiB + 8 words.
 __global__ __launch_bounds__(BB) void k_slice_plan(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, SliceJob job, TakeRow *__restrict__ plan,
                                                    uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
     __shared__ CodeTables t;
-    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
     load_tables(t, codes, n_codes);
     __syncthreads();
-    PackedTally tally;
-    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
-        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
-        bool is_long = false;
-        if (k < job.n_rows) {
-            const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
-            const uint32_t status = !rec.status && rec.nb > TAKE_BODY_MAX ? PACKED_UNSUPPORTED : rec.status;
-            uint4 row = make_uint4(0u, 0u, 0u, 0u);
-            if (!status && rec.nb && rec.len) {
-                const SliceAsk ask = slice_ask(job, k, static_cast<uint32_t>(rec.len));
-                if (ask.end > ask.first) {
-                    const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, ask.end)));
-                    if (g.end_bit - g.first_bit <= SLICE_LANE_BYTES * 8) row = slice_row(g, slice_lane(t, n_codes, g, ask, job.stop));
-                    else is_long = true;
-                }
+    plan_rows(job.n_rows, long_list, d_status, stats, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.rows, k);
+        RowPlan p{rec.status, false};
+        uint4 row = make_uint4(0u, 0u, 0u, 0u);
+        if (stored_text(rec)) {
+            const SliceAsk ask = slice_ask(job, k, static_cast<uint32_t>(rec.len));
+            if (ask.end > ask.first) {
+                const BodyBits g = reach_body(store, rec, ask.end);
+                if (lane_walks(g, SLICE_LANE_BYTES)) row = slice_row(g, slice_lane(t, n_codes, g, ask, job.stop));
+                else p.is_long = true;
             }
-            reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
-            if (d_status) d_status[k] = static_cast<uint8_t>(status);
-            tally.note(k, status);
         }
-        const unsigned long long longs = __ballot(is_long);
-        if (longs) {  // (the same for the whole wavefront)
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
-            at = __shfl(at, 0, 64);
-            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
-        }
-    }
-    tally_lanes(tally, s_failed, s_first, stats);
+        store_row(plan, k, row);
+        return p;
+    });
 }
 
 // One row's body by the whole workgroup under the tables in `s`: search_stream's blocks with a counting walk to settle them.  Once the
 // scan has numbered a block's codewords, the lanes whose codewords meet [ask.first, ask.end) walk again and note, as symbol << 32 |
 // bit: where symbol ask.first begins, where the first `stop` among their symbols begins (the walk ends there), and where the last of
-// their symbols in the range ends.  The three are reduced over the workgroup through s_red (12 words, free again at the next block's
-// first barrier): the slice begins at the one begin, and ends at the lowest stop or else behind the highest symbol of the range that the
-// stored text holds.  The blocks end with the first that has a stop, or once ask.end codewords lie behind: none behind the slice's end
-// is visited.
+// their symbols in the range ends.  The three are reduced over the workgroup (reduce_min_min_max): the slice begins at the one
+// begin, and ends at the lowest stop or else behind the highest symbol of the range that the stored text holds.  The blocks end with
+// the first that has a stop, or once ask.end codewords lie behind: none behind the slice's end is visited.
 __device__ __forceinline__ Sliced slice_stream(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, const SliceAsk &ask, uint32_t stop, unsigned long long *s_red) {
     constexpr unsigned long long NONE = ~0ull;
     const uint32_t tid = threadIdx.x;
@@ -1990,25 +2117,7 @@ __device__ __forceinline__ Sliced slice_stream(BatchDecLds &s, uint32_t n_codes,
                 return true;
             });
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const unsigned long long ob = __shfl_xor(my_begin, d, 64), os = __shfl_xor(my_stop, d, 64), ol = __shfl_xor(my_last, d, 64);
-            if (ob < my_begin) my_begin = ob;
-            if (os < my_stop) my_stop = os;
-            if (ol > my_last) my_last = ol;
-        }
-        if ((tid & 63) == 0) {
-            s_red[tid >> 6] = my_begin;
-            s_red[4 + (tid >> 6)] = my_stop;
-            s_red[8 + (tid >> 6)] = my_last;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < BB / 64; ++w) {
-            if (s_red[w] < my_begin) my_begin = s_red[w];
-            if (s_red[4 + w] < my_stop) my_stop = s_red[4 + w];
-            if (s_red[8 + w] > my_last) my_last = s_red[8 + w];
-        }
+        reduce_min_min_max(my_begin, my_stop, my_last, s_red);
         if (my_begin != NONE) begin = my_begin;  // (the same for every lane, like all below)
         if (my_last > end) end = my_last;
         if (my_stop != NONE) {  // the lowest stop: nothing at or behind it belongs to the slice
@@ -2022,28 +2131,20 @@ __device__ __forceinline__ Sliced slice_stream(BatchDecLds &s, uint32_t n_codes,
     return Sliced{static_cast<uint32_t>(begin), static_cast<uint32_t>(end), static_cast<uint32_t>(end >> 32) - ask.first};
 }
 
-// k_slice_long: k_search_long's shape over long_list -- the sorted codes and the first-level table once per workgroup, the listed rows
-// strided.  A workgroup beyond the list returns before it sets anything up.  Thread 0 stores the row's TakeRow (k_slice_plan left the empty record there; the scan runs behind this kernel).
-// LDS as k_batch_decode, and the reduction's 12 words.
+// k_slice_long: long_rows with slice_stream.  LDS as k_batch_decode, and the reduction's 12 words.
 __global__ __launch_bounds__(BB) void k_slice_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, SliceJob job, TakeRow *__restrict__ plan,
                                                    const uint32_t *__restrict__ long_list, const unsigned long long *__restrict__ stats) {
     __shared__ BatchDecLds s;
     __shared__ unsigned long long s_red[3 * (BB / 64)];
-    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
-    if (blockIdx.x >= n_long) return;
-    load_tables(s.t, codes, n_codes);
-    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
-    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
-        const uint32_t k = long_list[i];
-        if (k >= job.n_rows) continue;  // (k_slice_plan lists rows; the same for every lane, like all below)
-        const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
-        if (rec.status || rec.nb == 0 || rec.nb > TAKE_BODY_MAX || rec.len == 0) continue;  // (k_slice_plan lists no such row)
+    long_rows(job.n_rows, long_list, stats, [&] { return load_tables(s.t, codes, n_codes), true; }, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.rows, k);
+        if (!stored_text(rec)) return;
         const SliceAsk ask = slice_ask(job, k, static_cast<uint32_t>(rec.len));
-        if (ask.end <= ask.first) continue;
-        const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, ask.end)));
+        if (ask.end <= ask.first) return;
+        const BodyBits g = reach_body(store, rec, ask.end);
         const Sliced sl = slice_stream(s, n_codes, g, ask, job.stop, s_red);
-        if (threadIdx.x == 0) reinterpret_cast<uint4 *>(plan)[k] = slice_row(g, sl);
-    }
+        if (threadIdx.x == 0) store_row(plan, k, slice_row(g, sl));
+    });
 }
 
 // --------------------------------------------------------------------------------
@@ -2051,10 +2152,8 @@ __global__ __launch_bounds__(BB) void k_slice_long(PackedStore store, const uint
 // kept, as a new packed store.  A delimiter is a codeword of the stored text that decodes to `delim`; the walks count them.  Numbered
 // from 1, the field begins behind delimiter `a` = field (a = 0: at the text's first symbol) and ends in front of delimiter `b` =
 // field + n_fields, or where the stored text ends when it has fewer; a text with fewer than `a` has no such field.  What lies between
-// is a run of bits between two codeword boundaries: a slice, written by the take's scan and the bit-reading copy.
-// THE rule of what counts: codeword number i of a body is a symbol of the stored text when it ends inside the body AND i < length.
-// Every loop is bounded as the slice's are: a lane's walk by the record's length, the workgroup's by the blocks of the body that the
-// length can reach, its fixed point by 256 trips and a lane's walk inside it by its 256 bits.  No workgroup waits for another.
+// is a run of bits between two codeword boundaries: a slice, written by the take's scan and the bit-reading copy.  The reach of a
+// field is the record's whole length: nothing bounds where field k lies.
 // --------------------------------------------------------------------------------
 struct FieldAsk {
     uint32_t a, b;  // a <= b
@@ -2073,90 +2172,66 @@ struct Fielded {
 
 __device__ __forceinline__ uint4 field_row(const BodyBits &g, const Fielded &f) { return slice_row(g, Sliced{f.begin, f.end, f.n}); }
 
-// One lane, one body of a few words, from global memory: slice_lane's registers with a running delimiter count, a trip per symbol of
-// the stored text in front of the closing delimiter.  (a == b == 0 asks for nothing of the body: the caller does not come here.)
+// lane_walk with a running delimiter count, ended at the closing delimiter -- or behind the opening one when no field was asked for
+// (a == b).  (a == b == 0 asks for nothing of the body: the caller does not come here.)
 __device__ __forceinline__ Fielded field_lane(const CodeTables &t, uint32_t n_codes, const BodyBits &g, uint32_t len, const FieldAsk &ask, uint32_t delim) {
-    uint32_t pos = g.first_bit, k = 0, idx = 0, seen = 0;
-    Fielded f{pos, pos, 0u, ask.a ? FIELD_ABSENT : 0u};
-    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
-    for (; idx < len; ++idx) {
-        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
-            k = pos >> 5;
-            two = (two << 32) | body_word_be(g, k + 1);
+    uint32_t seen = 0;
+    bool closed = false;
+    Fielded f{g.first_bit, g.first_bit, 0u, ask.a ? FIELD_ABSENT : 0u};
+    const LaneEnd e = lane_walk(t, n_codes, g, len, [&](uint32_t idx, uint32_t pos, uint32_t meta) {
+        if ((meta & 0xffu) != delim) return true;
+        ++seen;
+        if (seen == ask.a) {  // the field begins behind this one
+            f.begin = f.end = pos + (meta >> 8);
+            f.pos = idx + 1;
+            closed = ask.b == ask.a;  // ... and no field was asked for: the empty record, present
+        } else if (seen == ask.b) {  // the closing one
+            f.end = pos;
+            f.n = idx - f.pos;
+            closed = true;
         }
-        const uint32_t meta = code_at(t, n_codes, static_cast<uint32_t>((two << (pos & 31)) >> 32)), bits = meta >> 8;
-        if (pos + bits > g.end_bit) break;  // the bits ran out inside this codeword: the stored text ends here
-        if ((meta & 0xffu) == delim) {
-            ++seen;
-            if (seen == ask.a) {  // the field begins behind this one
-                f.begin = f.end = pos + bits;
-                f.pos = idx + 1;
-                if (ask.b == ask.a) return f;  // ... and no field was asked for: the empty record, present
-            } else if (seen == ask.b) {  // the closing one
-                f.end = pos;
-                f.n = idx - f.pos;
-                return f;
-            }
-        }
-        pos += bits;
-    }
-    if (f.pos == FIELD_ABSENT) return f;
-    f.end = pos;  // the stored text's end
-    f.n = idx - f.pos;
+        return !closed;
+    });
+    if (closed || f.pos == FIELD_ABSENT) return f;
+    f.end = e.pos;  // the stored text's end
+    f.n = e.idx - f.pos;
     return f;
 }
 
-// k_field_plan: k_slice_plan's frame.  A record without bytes or symbols has the empty stored text: one empty field 0.  A row that asks
-// for no field of field 0 on is the empty record and is not read.  A body that the length can reach up to FIELD_LANE_BYTES is walked by
-// its lane (field_lane); a longer one goes onto long_list and is the empty record here: k_field_long stores its TakeRow and its
-// position.  d_pos[k] = the symbol at which the field begins, FIELD_ABSENT without one and for a failed row.  LDS 6 KiB + 8 words.
+// k_field_plan: plan_rows.  A record without bytes or symbols has the empty stored text: one empty field 0.  A row that asks for no
+// field of field 0 on is the empty record and is not read.  A body that the length can reach up to FIELD_LANE_BYTES is walked by its
+// lane (field_lane).  d_pos[k] = the symbol at which the field begins, FIELD_ABSENT without one and for a failed row; k_field_long
+// stores a listed row's.  LDS 6 KiB + 8 words.
 __global__ __launch_bounds__(BB) void k_field_plan(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, FieldJob job, TakeRow *__restrict__ plan,
                                                    uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
     __shared__ CodeTables t;
-    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
     load_tables(t, codes, n_codes);
     __syncthreads();
-    PackedTally tally;
-    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
-        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
-        bool is_long = false;
-        if (k < job.n_rows) {
-            const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
-            const uint32_t status = !rec.status && rec.nb > TAKE_BODY_MAX ? PACKED_UNSUPPORTED : rec.status;
-            uint4 row = make_uint4(0u, 0u, 0u, 0u);
-            uint32_t pos = FIELD_ABSENT;
-            if (!status) {
-                const FieldAsk ask = field_ask(job, k);
-                if (!rec.nb || !rec.len || !ask.b) {
-                    if (!ask.a) pos = 0;
+    plan_rows(job.n_rows, long_list, d_status, stats, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.rows, k);
+        RowPlan p{rec.status, false};
+        uint4 row = make_uint4(0u, 0u, 0u, 0u);
+        uint32_t pos = FIELD_ABSENT;
+        if (!rec.status) {
+            const FieldAsk ask = field_ask(job, k);
+            if (!stored_text(rec) || !ask.b) {
+                if (!ask.a) pos = 0;
+            } else {
+                const uint32_t len = static_cast<uint32_t>(rec.len);
+                const BodyBits g = reach_body(store, rec, len);
+                if (lane_walks(g, FIELD_LANE_BYTES)) {
+                    const Fielded f = field_lane(t, n_codes, g, len, ask, job.delim);
+                    row = field_row(g, f);
+                    pos = f.pos;
                 } else {
-                    const uint32_t len = static_cast<uint32_t>(rec.len);
-                    const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len)));
-                    if (g.end_bit - g.first_bit <= FIELD_LANE_BYTES * 8) {
-                        const Fielded f = field_lane(t, n_codes, g, len, ask, job.delim);
-                        row = field_row(g, f);
-                        pos = f.pos;
-                    } else {
-                        is_long = true;
-                    }
+                    p.is_long = true;
                 }
             }
-            reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
-            if (job.d_pos) job.d_pos[k] = pos;
-            if (d_status) d_status[k] = static_cast<uint8_t>(status);
-            tally.note(k, status);
         }
-        const unsigned long long longs = __ballot(is_long);
-        if (longs) {  // (the same for the whole wavefront)
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
-            at = __shfl(at, 0, 64);
-            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
-        }
-    }
-    tally_lanes(tally, s_failed, s_first, stats);
+        store_row(plan, k, row);
+        if (job.d_pos) job.d_pos[k] = pos;
+        return p;
+    });
 }
 
 // The visitor of the settling walks of the field call: the walk's delimiters, and the bit of the lane's 256 behind its last codeword.
@@ -2169,14 +2244,13 @@ struct CountDelims {
     }
 };
 
-// One row's body by the whole workgroup under the tables in `s`: slice_stream's blocks, settled by a walk that counts its delimiters.
-// The visitor does not know its lane's symbol numbers; once the scan has given them, a lane whose codewords reach the length -- one
-// lane of the text's last block, the lanes behind it hold none -- counts again up to it, so no codeword at or behind `len` is ever a
-// delimiter.  A second scan (s_scan, 4 words, free again at the next block's first barrier) numbers the delimiters across the lanes,
-// `seen` carries them across the blocks beside `done`.  The lanes that hold delimiter a or b walk again and note, as symbol << 32 | bit,
-// where the field begins and where the closing delimiter does; every lane notes where its last symbol ends.  The three are reduced as
-// the slice's are (s_red, 12 words).  The begin found in one block is kept in a register until the end is found, blocks later.  The
-// blocks end with the one that holds the closing delimiter, or once `len` codewords lie behind: nothing behind is visited.
+// One row's body by the whole workgroup under the tables in `s`: slice_stream's blocks, settled by a walk that counts its delimiters
+// and cut at the length (cut_at_length), so no codeword at or behind `len` is ever a delimiter.  A second scan (s_scan, 4 words, free
+// again at the next block's first barrier) numbers the delimiters across the lanes, `seen` carries them across the blocks beside
+// `done`.  The lanes that hold delimiter a or b walk again and note, as symbol << 32 | bit, where the field begins and where the
+// closing delimiter does; every lane notes where its last symbol ends.  The three are reduced over the workgroup
+// (reduce_min_min_max).  The begin found in one block is kept in a register until the end is found, blocks later.  The blocks end
+// with the one that holds the closing delimiter, or once `len` codewords lie behind: nothing behind is visited.
 __device__ __forceinline__ Fielded field_stream(BatchDecLds &s, uint32_t n_codes, const BodyBits &g, uint32_t len, const FieldAsk &ask, uint32_t delim,
                                                 unsigned long long *s_red, uint32_t *s_scan) {
     constexpr unsigned long long NONE = ~0ull;
@@ -2184,28 +2258,16 @@ __device__ __forceinline__ Fielded field_stream(BatchDecLds &s, uint32_t n_codes
     const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
     uint32_t start = g.first_bit, done = 0, seen = 0;  // the block's first codeword; codewords and delimiters so far
     unsigned long long begin = ask.a ? NONE : g.first_bit, end = 0;
+    const CountDelims fresh{delim, 0u, 0u};
     for (uint32_t blk = 0; blk < n_blocks && done < len; ++blk) {
         const uint32_t at = blk * DEC_WORDS * 32 + tid * 256;
-        CountDelims counting{delim, 0u, 0u};
+        CountDelims counting = fresh;
         const Settled b = settle_block(s, n_codes, g, blk, start, counting);
         const uint32_t lo = done + b.first;  // the number of the lane's first codeword
-        uint32_t held = b.count, mine = counting.n, last = counting.last;  // the lane's symbols of the stored text, the delimiters among them
-        if (lo >= len) {
-            held = mine = 0;
-        } else if (lo + b.count > len) {  // (lo + count <= 4 * len + 16: no wrap)
-            held = len - lo;
-            mine = 0;
-            uint32_t again;
-            (void)walk(s, n_codes, b.used, b.room, &again, [&](uint32_t cnt, uint32_t pos, uint32_t, uint32_t meta) {
-                if (cnt >= held) return false;
-                mine += (meta & 0xffu) == delim;
-                last = pos + (meta >> 8);
-                return true;
-            });
-        }
+        const uint32_t held = cut_at_length(s, n_codes, b, lo, len, counting, fresh), mine = counting.n;  // the lane's symbols of the stored text, the delimiters among them
         uint32_t block_delims;
         const uint32_t before = seen + block_exclusive_scan(mine, s_scan, &block_delims);  // delimiters in front of the lane's first symbol
-        unsigned long long my_begin = NONE, my_close = NONE, my_last = held ? static_cast<unsigned long long>(lo + held) << 32 | (at + last) : 0ull;
+        unsigned long long my_begin = NONE, my_close = NONE, my_last = held ? static_cast<unsigned long long>(lo + held) << 32 | (at + counting.last) : 0ull;
         const bool has_a = ask.a > before && ask.a - before <= mine, has_b = ask.b > before && ask.b - before <= mine;
         if (has_a || has_b) {
             uint32_t again, d = before;
@@ -2221,25 +2283,7 @@ __device__ __forceinline__ Fielded field_stream(BatchDecLds &s, uint32_t n_codes
                 return true;
             });
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const unsigned long long ob = __shfl_xor(my_begin, d, 64), oc = __shfl_xor(my_close, d, 64), ol = __shfl_xor(my_last, d, 64);
-            if (ob < my_begin) my_begin = ob;
-            if (oc < my_close) my_close = oc;
-            if (ol > my_last) my_last = ol;
-        }
-        if ((tid & 63) == 0) {
-            s_red[tid >> 6] = my_begin;
-            s_red[4 + (tid >> 6)] = my_close;
-            s_red[8 + (tid >> 6)] = my_last;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < BB / 64; ++w) {
-            if (s_red[w] < my_begin) my_begin = s_red[w];
-            if (s_red[4 + w] < my_close) my_close = s_red[4 + w];
-            if (s_red[8 + w] > my_last) my_last = s_red[8 + w];
-        }
+        reduce_min_min_max(my_begin, my_close, my_last, s_red);
         if (my_begin != NONE) begin = my_begin;  // (the same for every lane, like all below)
         if (my_last > end) end = my_last;
         if (my_close != NONE) {  // nothing at or behind the closing delimiter belongs to the field
@@ -2256,33 +2300,26 @@ __device__ __forceinline__ Fielded field_stream(BatchDecLds &s, uint32_t n_codes
     return Fielded{static_cast<uint32_t>(begin), static_cast<uint32_t>(end), static_cast<uint32_t>(end >> 32) - pos, pos};
 }
 
-// k_field_long: k_slice_long's shape over long_list.  A workgroup beyond the list returns before it sets anything up.  Thread 0 stores
-// the row's TakeRow and position (k_field_plan left the empty record there; the scan runs behind this kernel).
+// k_field_long: long_rows with field_stream; thread 0 stores the row's position beside its TakeRow.
 // LDS as k_batch_decode, the reduction's 12 words and the second scan's 4.
 __global__ __launch_bounds__(BB) void k_field_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, FieldJob job, TakeRow *__restrict__ plan,
                                                    const uint32_t *__restrict__ long_list, const unsigned long long *__restrict__ stats) {
     __shared__ BatchDecLds s;
     __shared__ unsigned long long s_red[3 * (BB / 64)];
     __shared__ uint32_t s_scan[BB / 64];
-    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
-    if (blockIdx.x >= n_long) return;
-    load_tables(s.t, codes, n_codes);
-    const uint8_t *d_bodies = static_cast<const uint8_t *>(store.bodies);
-    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
-        const uint32_t k = long_list[i];
-        if (k >= job.n_rows) continue;  // (k_field_plan lists rows; the same for every lane, like all below)
-        const Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
-        if (rec.status || rec.nb == 0 || rec.nb > TAKE_BODY_MAX || rec.len == 0) continue;  // (k_field_plan lists no such row)
+    long_rows(job.n_rows, long_list, stats, [&] { return load_tables(s.t, codes, n_codes), true; }, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.rows, k);
+        if (!stored_text(rec)) return;
         const FieldAsk ask = field_ask(job, k);
-        if (!ask.b) continue;
+        if (!ask.b) return;
         const uint32_t len = static_cast<uint32_t>(rec.len);
-        const BodyBits g = body_bits_of(d_bodies, rec.b0, static_cast<uint32_t>(clip_body(rec.nb, len)));
+        const BodyBits g = reach_body(store, rec, len);
         const Fielded f = field_stream(s, n_codes, g, len, ask, job.delim, s_red, s_scan);
         if (threadIdx.x == 0) {
-            reinterpret_cast<uint4 *>(plan)[k] = field_row(g, f);
+            store_row(plan, k, field_row(g, f));
             if (job.d_pos) job.d_pos[k] = f.pos;
         }
-    }
+    });
 }
 
 // --------------------------------------------------------------------------------
@@ -2293,25 +2330,9 @@ __global__ __launch_bounds__(BB) void k_field_long(PackedStore store, const uint
 // way.  The right run cannot be taken as the take takes a body, 8 * bytes bits and the length whole: behind a left run that ends
 // inside a byte its pad would spill into a byte the encoder does not write, and where its length does not end its text the row's own
 // pad would read as symbols.  k_take_scan lays the rows out; k_concat_copy writes them, each run shifted to the destination BIT it
-// begins at.
-// Every loop is bounded as the slice's are; k_concat_copy's as k_take_copy's.  No workgroup waits for another: k_concat_long stores
-// the two records of its own row (and, where the walked length fails the row, its status byte and two atomics) and nothing else.
+// begins at.  The reach of a side is its record's whole length; k_concat_copy's loops are bounded as k_take_copy's.  k_concat_long
+// stores the two records of its own row (and, where the walked length fails the row, its status byte and two atomics) and nothing else.
 // --------------------------------------------------------------------------------
-// A side's record as the take judges it; an absent side (no bodies) contributes an OK record of nothing and is not looked at.
-__device__ __forceinline__ Judged judge_side(const PackedStore &store, const uint32_t *rows, uint32_t k) {
-    if (!store.bodies) return Judged{PACKED_OK, 0, 0, 0};
-    Judged rec = judge_record(store, rows ? rows[k] : k);
-    if (!rec.status && rec.nb > TAKE_BODY_MAX) rec.status = PACKED_UNSUPPORTED;
-    return rec;
-}
-
-// What the walks look at of a judged record with bytes and symbols, and who walks it.
-__device__ __forceinline__ BodyBits concat_body(const PackedStore &store, const Judged &rec) {
-    return body_bits_of(static_cast<const uint8_t *>(store.bodies), rec.b0, static_cast<uint32_t>(clip_body(rec.nb, rec.len)));
-}
-
-__device__ __forceinline__ bool concat_by_lane(const BodyBits &g) { return g.end_bit - g.first_bit <= CONCAT_LANE_BYTES * 8; }
-
 // A side's run: the ADDRESS of its stored text's first bit, its bits and its symbols; nothing until it is walked.
 struct ConcatRun {
     uint64_t bit;
@@ -2336,101 +2357,74 @@ __device__ __forceinline__ uint32_t concat_store(const ConcatJob &job, uint32_t 
         p0 = make_uint4(static_cast<uint32_t>(a.bit), static_cast<uint32_t>(a.bit >> 32), a.bits, b.bits);
         p1 = make_uint4(static_cast<uint32_t>(b.bit), static_cast<uint32_t>(b.bit >> 32), a.syms, b.syms);
     }
-    reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow and ConcatPiece as they lie in memory)
-    reinterpret_cast<uint4 *>(pieces)[2 * k] = p0;
+    store_row(plan, k, row);
+    reinterpret_cast<uint4 *>(pieces)[2 * k] = p0;  // (ConcatPiece as it lies in memory)
     reinterpret_cast<uint4 *>(pieces)[2 * k + 1] = p1;
     return status;
 }
 
-// k_concat_plan: k_slice_plan's frame over pairs of records.  The row's status is the left record's if that is not OK, else the
-// right's, else the new length's; a failed row is the empty record and neither of its bodies is read.  Each side's body (clip_body of
-// its whole length) up to CONCAT_LANE_BYTES is walked by the row's lane (slice_lane, from symbol 0 to the end, nothing cuts); a row
-// with a longer one goes onto long_list and that run counts as absent here: k_concat_long completes the row.  LDS 6 KiB + 8 words.
+// k_concat_plan: plan_rows over pairs of records.  The row's status is the left record's if that is not OK, else the right's, else
+// the new length's; a failed row is the empty record and neither of its bodies is read.  Each side's body up to CONCAT_LANE_BYTES is
+// walked by the row's lane (slice_lane, from symbol 0 to the end, nothing cuts); a row with a longer one goes onto long_list and that
+// run counts as absent here: k_concat_long completes the row.  LDS 6 KiB + 8 words.
 __global__ __launch_bounds__(BB) void k_concat_plan(PackedStore a, PackedStore b, const uint2 *__restrict__ codes, uint32_t n_codes, ConcatJob job, TakeRow *__restrict__ plan,
                                                     ConcatPiece *__restrict__ pieces, uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status,
                                                     unsigned long long *__restrict__ stats) {
     __shared__ CodeTables t;
-    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    const uint32_t lane = threadIdx.x & 63;
     load_tables(t, codes, n_codes);
     __syncthreads();
-    PackedTally tally;
-    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
-        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
-        bool is_long = false;
-        if (k < job.n_rows) {
-            const Judged ra = judge_side(a, job.rows_a, k), rb = judge_side(b, job.rows_b, k);
-            uint32_t status = ra.status ? ra.status : rb.status;
-            ConcatRun run_a{0, 0, 0}, run_b{0, 0, 0};
+    plan_rows(job.n_rows, long_list, d_status, stats, [&](uint32_t k) {
+        const Judged ra = judge_row(a, job.rows_a, k), rb = judge_row(b, job.rows_b, k);
+        RowPlan p{ra.status ? ra.status : rb.status, false};
+        ConcatRun run_a{0, 0, 0}, run_b{0, 0, 0};
 #pragma unroll 1
-            for (int right = 0; right < 2 && !status; ++right) {
-                const Judged &rec = right ? rb : ra;
-                if (!rec.nb || !rec.len) continue;  // (a record kept raw, or empty, has the empty stored text)
-                const BodyBits g = concat_body(right ? b : a, rec);
-                if (!concat_by_lane(g)) {
-                    is_long = true;
-                    continue;
-                }
-                const ConcatRun run = concat_run(g, slice_lane(t, n_codes, g, SliceAsk{0u, static_cast<uint32_t>(rec.len)}, SLICE_NO_STOP));
-                if (right) run_b = run;
-                else run_a = run;
+        for (int right = 0; right < 2 && !p.status; ++right) {
+            const Judged &rec = right ? rb : ra;
+            if (!stored_text(rec)) continue;
+            const BodyBits g = reach_body(right ? b : a, rec, rec.len);
+            if (!lane_walks(g, CONCAT_LANE_BYTES)) {
+                p.is_long = true;
+                continue;
             }
-            status = concat_store(job, k, status, run_a, run_b, plan, pieces);
-            if (status) is_long = false;  // (too long without its long runs already)
-            if (d_status) d_status[k] = static_cast<uint8_t>(status);
-            tally.note(k, status);
+            const ConcatRun run = concat_run(g, slice_lane(t, n_codes, g, SliceAsk{0u, static_cast<uint32_t>(rec.len)}, SLICE_NO_STOP));
+            if (right) run_b = run;
+            else run_a = run;
         }
-        const unsigned long long longs = __ballot(is_long);
-        if (longs) {  // (the same for the whole wavefront)
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
-            at = __shfl(at, 0, 64);
-            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
-        }
-    }
-    tally_lanes(tally, s_failed, s_first, stats);
+        p.status = concat_store(job, k, p.status, run_a, run_b, plan, pieces);
+        if (p.status) p.is_long = false;  // (too long without its long runs already)
+        return p;
+    });
 }
 
-// k_concat_long: k_slice_long's shape over long_list: slice_stream from symbol 0 to the record's end, nothing cuts, for each side of
-// the row that k_concat_plan left to it -- one after the other, so a row has one writer.  Thread 0 completes the row's two records
-// from what k_concat_plan left of the other side; a row whose length the walks bring above the limit fails here -- the empty record,
-// its status byte, one tally -- for k_concat_plan held it for OK.  The scan runs behind this kernel.
-// LDS as k_batch_decode, and the reduction's 12 words.
+// k_concat_long: long_rows with slice_stream from symbol 0 to the record's end, nothing cuts, for each side of the row that
+// k_concat_plan left to it -- one after the other, so a row has one writer.  Thread 0 completes the row's two records from what
+// k_concat_plan left of the other side; a row whose length the walks bring above the limit fails here (fail_row_late), the empty
+// record.  LDS as k_batch_decode, and the reduction's 12 words.
 __global__ __launch_bounds__(BB) void k_concat_long(PackedStore a, PackedStore b, const uint2 *__restrict__ codes, uint32_t n_codes, ConcatJob job, TakeRow *__restrict__ plan,
                                                     ConcatPiece *__restrict__ pieces, const uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status,
                                                     unsigned long long *__restrict__ stats) {
     __shared__ BatchDecLds s;
     __shared__ unsigned long long s_red[3 * (BB / 64)];
-    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
-    if (blockIdx.x >= n_long) return;
-    load_tables(s.t, codes, n_codes);
-    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
-        const uint32_t k = long_list[i];
-        if (k >= job.n_rows) continue;  // (k_concat_plan lists rows; the same for every lane, like all below)
-        const Judged ra = judge_side(a, job.rows_a, k), rb = judge_side(b, job.rows_b, k);
-        if (ra.status || rb.status) continue;  // (k_concat_plan lists no such row)
+    long_rows(job.n_rows, long_list, stats, [&] { return load_tables(s.t, codes, n_codes), true; }, [&](uint32_t k) {
+        const Judged ra = judge_row(a, job.rows_a, k), rb = judge_row(b, job.rows_b, k);
+        if (ra.status || rb.status) return;
         const uint4 p0 = reinterpret_cast<const uint4 *>(pieces)[2 * k], p1 = reinterpret_cast<const uint4 *>(pieces)[2 * k + 1];  // what the lane has walked
         ConcatRun run_a{static_cast<uint64_t>(p0.y) << 32 | p0.x, p0.z, p1.z}, run_b{static_cast<uint64_t>(p1.y) << 32 | p1.x, p0.w, p1.w};
 #pragma unroll 1
         for (int right = 0; right < 2; ++right) {
             const Judged &rec = right ? rb : ra;
-            if (!rec.nb || !rec.len) continue;
-            const BodyBits g = concat_body(right ? b : a, rec);
-            if (concat_by_lane(g)) continue;
+            if (!stored_text(rec)) continue;
+            const BodyBits g = reach_body(right ? b : a, rec, rec.len);
+            if (lane_walks(g, CONCAT_LANE_BYTES)) continue;
             const ConcatRun run = concat_run(g, slice_stream(s, n_codes, g, SliceAsk{0u, static_cast<uint32_t>(rec.len)}, SLICE_NO_STOP, s_red));
             if (right) run_b = run;
             else run_a = run;
         }
         if (threadIdx.x == 0) {
             const uint32_t status = concat_store(job, k, PACKED_OK, run_a, run_b, plan, pieces);
-            if (status) {
-                if (d_status) d_status[k] = static_cast<uint8_t>(status);
-                PackedTally tally;
-                tally.note(k, status);
-                tally.add_to(stats);
-            }
+            if (status) fail_row_late(k, status, d_status, stats);
         }
-    }
+    });
 }
 
 // `n` bits (1 .. 64) from bit address `bit` on (a byte's address * 8 + the bit, from the top), the first at the top of the word and
@@ -2536,13 +2530,12 @@ __global__ __launch_bounds__(BB) void k_concat_copy(const ConcatPiece *__restric
 // nothing in between: for every symbol s of the stored text the entry s of ONE table -- map composed with OUT by the host, 256 x
 // {left-aligned code, length} indexed by the INPUT symbol -- is laid behind the one before.  Length 0: the byte is dropped;
 // RECODE_UNCODED: it is kept but has no code under OUT, and the row fails (PACKED_UNSUPPORTED, the empty record).
-// THE rule of what counts is the field's: codeword number i of a body is a symbol of the stored text when it ends inside the body
-// AND i < length; nothing else is looked up in the output table, so a codeword behind the length or in the pad fails no row.
+// Nothing but a symbol of the stored text (cut_at_length's rule) is looked up in the output table, so a codeword behind the length
+// or in the pad fails no row.  The reach of a row is its record's whole length.
 // The body is read twice (sizes, then bits) and the new body written once.  A row owns whole bytes: no two rows share an output
 // byte, pad bits are zero because the accumulators begin as zeros, and every store is clipped to the row's own bytes.
-// Every loop is bounded as the slice's are: a lane's walk by the record's length, the workgroup's by the blocks of the body that the
-// length can reach, its fixed point by 256 trips, a lane's walk inside it by its 256 bits, and the flush rounds of a block by the
-// block's output bits (at most 65 536 codewords of 32 bits: 16 rounds).  No workgroup waits for another.
+// Beside the derived stores' bounds: the flush rounds of a block are bounded by the block's output bits (at most 65 536 codewords of
+// 32 bits: 16 rounds).
 // --------------------------------------------------------------------------------
 // What a walk over a stored text sums: the new body's bits, its symbols, and whether a kept symbol has no code under OUT.
 struct Recoded {
@@ -2554,88 +2547,43 @@ struct Recoded {
     }
 };
 
-// A row's record as the slice judges it, and what of its body the walks look at.
-__device__ __forceinline__ Judged recode_judge(const PackedStore &store, const RecodeJob &job, uint32_t k) {
-    Judged rec = judge_record(store, job.rows ? job.rows[k] : k);
-    if (!rec.status && rec.nb > TAKE_BODY_MAX) rec.status = PACKED_UNSUPPORTED;
-    return rec;
-}
-
-__device__ __forceinline__ BodyBits recode_body(const PackedStore &store, const Judged &rec) {
-    return body_bits_of(static_cast<const uint8_t *>(store.bodies), rec.b0, static_cast<uint32_t>(clip_body(rec.nb, rec.len)));
-}
-
-__device__ __forceinline__ bool recode_by_lane(const BodyBits &g) { return g.end_bit - g.first_bit <= RECODE_LANE_BYTES * 8; }
-
-// One lane, one body of a few words, from global memory (slice_lane's walk from symbol 0 to the end of the stored text): visit(s) sees
-// every symbol of the stored text, in order.
-template <class Visit>
-__device__ __forceinline__ void recode_lane(const CodeTables &t, uint32_t n_codes, const BodyBits &g, uint32_t len, Visit &&visit) {
-    uint32_t pos = g.first_bit, k = 0;
-    uint64_t two = (body_word_be(g, 0) << 32) | body_word_be(g, 1);
-    for (uint32_t idx = 0; idx < len; ++idx) {
-        if ((pos >> 5) != k) {  // (a codeword has at most 32 bits: one word on)
-            k = pos >> 5;
-            two = (two << 32) | body_word_be(g, k + 1);
-        }
-        const uint32_t meta = code_at(t, n_codes, static_cast<uint32_t>((two << (pos & 31)) >> 32));
-        if (pos + (meta >> 8) > g.end_bit) break;  // the bits ran out inside this codeword: the stored text ends here
-        visit(meta & 0xffu);
-        pos += meta >> 8;
-    }
-}
-
 // The TakeRow of a recoded row as it lies in memory: the new body's bytes, its symbols, its BITS (the long write bounds its rounds by them).
 __device__ __forceinline__ uint4 recode_row(const Recoded &r) {
     if (r.uncoded || !r.bits) return make_uint4(0u, 0u, 0u, 0u);
     return make_uint4((r.bits + 7) >> 3, r.kept, r.bits, 0u);
 }
 
-// k_recode_plan: k_slice_plan's frame -- rows, judgement, status bytes, tally, the list's ballot -- with the output table beside the
-// code tables in LDS.  A record without bytes or symbols has the empty stored text and is not read; a body up to RECODE_LANE_BYTES is
-// walked by its lane, and a kept symbol without a code fails the row here; a longer one goes onto long_list and is the empty record
-// for now: k_recode_long stores its TakeRow.  LDS 8 KiB + 8 words.
+// k_recode_plan: plan_rows with the output table beside the code tables in LDS.  A record without bytes or symbols has the empty
+// stored text and is not read; a body up to RECODE_LANE_BYTES is walked by its lane (lane_walk to the end of the stored text), and
+// a kept symbol without a code fails the row here.  LDS 8 KiB + 8 words.
 __global__ __launch_bounds__(BB) void k_recode_plan(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, RecodeJob job, TakeRow *__restrict__ plan,
                                                     uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
     __shared__ CodeTables t;
     __shared__ uint2 s_otab[256];
-    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
-    const uint32_t lane = threadIdx.x & 63;
     s_otab[threadIdx.x] = job.out_tab[threadIdx.x];
     load_tables(t, codes, n_codes);
     __syncthreads();
-    PackedTally tally;
-    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < job.n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
-        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;  // (n_rows <= 0x7fffffff: no wrap)
-        bool is_long = false;
-        if (k < job.n_rows) {
-            const Judged rec = recode_judge(store, job, k);
-            uint32_t status = rec.status;
-            uint4 row = make_uint4(0u, 0u, 0u, 0u);
-            if (!status && rec.nb && rec.len) {
-                const BodyBits g = recode_body(store, rec);
-                if (recode_by_lane(g)) {
-                    Recoded sum{0u, 0u, 0u};
-                    recode_lane(t, n_codes, g, static_cast<uint32_t>(rec.len), [&](uint32_t sym) { sum.add(s_otab[sym]); });
-                    if (sum.uncoded) status = PACKED_UNSUPPORTED;
-                    row = recode_row(sum);
-                } else {
-                    is_long = true;
-                }
+    plan_rows(job.n_rows, long_list, d_status, stats, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.rows, k);
+        RowPlan p{rec.status, false};
+        uint4 row = make_uint4(0u, 0u, 0u, 0u);
+        if (stored_text(rec)) {
+            const BodyBits g = reach_body(store, rec, rec.len);
+            if (lane_walks(g, RECODE_LANE_BYTES)) {
+                Recoded sum{0u, 0u, 0u};
+                (void)lane_walk(t, n_codes, g, static_cast<uint32_t>(rec.len), [&](uint32_t, uint32_t, uint32_t meta) {
+                    sum.add(s_otab[meta & 0xffu]);
+                    return true;
+                });
+                if (sum.uncoded) p.status = PACKED_UNSUPPORTED;
+                row = recode_row(sum);
+            } else {
+                p.is_long = true;
             }
-            reinterpret_cast<uint4 *>(plan)[k] = row;  // (TakeRow as it lies in memory)
-            if (d_status) d_status[k] = static_cast<uint8_t>(status);
-            tally.note(k, status);
         }
-        const unsigned long long longs = __ballot(is_long);
-        if (longs) {  // (the same for the whole wavefront)
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(stats + SLICE_N_LONG, static_cast<unsigned long long>(__popcll(longs)));
-            at = __shfl(at, 0, 64);
-            if (is_long) long_list[at + __popcll(longs & ((1ull << lane) - 1ull))] = k;
-        }
-    }
-    tally_lanes(tally, s_failed, s_first, stats);
+        store_row(plan, k, row);
+        return p;
+    });
 }
 
 // The visitor of the settling walks of the recode: what the walk's codewords give under the output table.
@@ -2648,9 +2596,8 @@ struct SumRecoded {
     }
 };
 
-// One block of a long row, settled, and what each lane's symbols OF THE STORED TEXT give: the visitor does not know its lane's symbol
-// numbers; once the scan has given them, the lanes behind the length hold nothing and the one lane whose codewords reach it sums
-// again up to it (field_stream's cut), so nothing at or behind `len` is ever looked up.  `done`: the codewords of the blocks before.
+// One block of a long row, settled and cut at the length (cut_at_length): what each lane's symbols OF THE STORED TEXT give.  `done`:
+// the codewords of the blocks before.
 struct RecodedBlock {
     Settled b;
     uint32_t held;  // the lane's symbols of the stored text
@@ -2659,51 +2606,34 @@ struct RecodedBlock {
 
 __device__ __forceinline__ RecodedBlock recode_block(BatchDecLds &s, const uint2 *otab, uint32_t n_codes, const BodyBits &g, uint32_t blk, uint32_t start, uint32_t done,
                                                      uint32_t len) {
-    SumRecoded summing{otab, Recoded{0u, 0u, 0u}};
+    const SumRecoded fresh{otab, Recoded{0u, 0u, 0u}};
+    SumRecoded summing = fresh;
     RecodedBlock rb;
     rb.b = settle_block(s, n_codes, g, blk, start, summing);
-    const uint32_t lo = done + rb.b.first;  // the number of the lane's first codeword
-    rb.held = rb.b.count;
+    rb.held = cut_at_length(s, n_codes, rb.b, done + rb.b.first, len, summing, fresh);
     rb.mine = summing.r;
-    if (lo >= len || !rb.b.count) {
-        rb.held = 0;
-        rb.mine = Recoded{0u, 0u, 0u};
-    } else if (lo + rb.b.count > len) {  // (lo + count <= 4 * len + 16: no wrap)
-        const uint32_t held = len - lo;
-        Recoded cut{0u, 0u, 0u};
-        uint32_t again;
-        (void)walk(s, n_codes, rb.b.used, rb.b.room, &again, [&](uint32_t cnt, uint32_t, uint32_t, uint32_t meta) {
-            if (cnt >= held) return false;
-            cut.add(otab[meta & 0xffu]);
-            return true;
-        });
-        rb.held = held;
-        rb.mine = cut;
-    }
     return rb;
 }
 
-// k_recode_long: k_slice_long's shape over long_list.  A workgroup beyond the list returns before it sets anything up.  Per block the
-// lanes' three sums are added up over the workgroup (two scans: the bits; the symbols with the flag's count above them) and carried
-// in registers across the blocks.  Thread 0 stores the row's TakeRow (k_recode_plan left the empty record there; the scan runs behind
-// this kernel), or fails the row -- its status byte, one tally -- where a kept symbol has no code: k_recode_plan held it for OK.
+// k_recode_long: long_rows.  Per block the lanes' three sums are added up over the workgroup (two scans: the bits; the symbols with
+// the flag's count above them) and carried in registers across the blocks.  Thread 0 stores the row's TakeRow, or fails the row
+// (fail_row_late) where a kept symbol has no code.
 // LDS as k_batch_decode, the output table's 2 KiB and the scans' 4 words: 35.2 KiB.
 __global__ __launch_bounds__(BB) void k_recode_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, RecodeJob job, TakeRow *__restrict__ plan,
                                                     const uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
     __shared__ BatchDecLds s;
     __shared__ uint2 s_otab[256];
     __shared__ uint32_t s_scan[BB / 64];
-    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
-    if (blockIdx.x >= n_long) return;
-    s_otab[threadIdx.x] = job.out_tab[threadIdx.x];
-    load_tables(s.t, codes, n_codes);
-    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
-        const uint32_t k = long_list[i];
-        if (k >= job.n_rows) continue;  // (k_recode_plan lists rows; the same for every lane, like all below)
-        const Judged rec = recode_judge(store, job, k);
-        if (rec.status || rec.nb == 0 || rec.len == 0) continue;  // (k_recode_plan lists no such row)
+    const auto set_up = [&] {
+        s_otab[threadIdx.x] = job.out_tab[threadIdx.x];
+        load_tables(s.t, codes, n_codes);
+        return true;
+    };
+    long_rows(job.n_rows, long_list, stats, set_up, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.rows, k);
+        if (!stored_text(rec)) return;
         const uint32_t len = static_cast<uint32_t>(rec.len);
-        const BodyBits g = recode_body(store, rec);
+        const BodyBits g = reach_body(store, rec, len);
         const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
         uint32_t start = g.first_bit, done = 0;  // the block's first codeword; codewords so far
         Recoded sum{0u, 0u, 0u};
@@ -2720,15 +2650,10 @@ __global__ __launch_bounds__(BB) void k_recode_long(PackedStore store, const uin
             done += rb.b.total;
         }
         if (threadIdx.x == 0) {
-            reinterpret_cast<uint4 *>(plan)[k] = recode_row(sum);
-            if (sum.uncoded) {
-                if (d_status) d_status[k] = static_cast<uint8_t>(PACKED_UNSUPPORTED);
-                PackedTally tally;
-                tally.note(k, PACKED_UNSUPPORTED);
-                tally.add_to(stats);
-            }
+            store_row(plan, k, recode_row(sum));
+            if (sum.uncoded) fail_row_late(k, PACKED_UNSUPPORTED, d_status, stats);
         }
-    }
+    });
 }
 
 // store_image_word for the recode's writes (a copy: shared, it changed the comparison sequence of k_shared_encode's and k_packed_pack's clipped stores).
@@ -2770,17 +2695,17 @@ __global__ __launch_bounds__(BB) void k_recode_write(PackedStore store, const ui
     for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * BB + threadIdx.x; k < job.n_rows; k += static_cast<uint64_t>(gridDim.x) * BB) {
         const uint32_t bytes = plan[k].body_bytes;
         if (!bytes) continue;
-        const Judged rec = recode_judge(store, job, static_cast<uint32_t>(k));
-        if (rec.status || rec.nb == 0 || rec.len == 0) continue;  // (such a row has no bytes)
-        const BodyBits g = recode_body(store, rec);
-        if (!recode_by_lane(g)) continue;
+        const Judged rec = judge_row(store, job.rows, static_cast<uint32_t>(k));
+        if (!stored_text(rec)) continue;  // (such a row has no bytes)
+        const BodyBits g = reach_body(store, rec, rec.len);
+        if (!lane_walks(g, RECODE_LANE_BYTES)) continue;
         const RecodeDst dst = recode_dst(d_out, out_index[k], bytes);
         uint32_t word = 0, fill = dst.lo * 8;
         uint64_t acc = 0;
-        recode_lane(t, n_codes, g, static_cast<uint32_t>(rec.len), [&](uint32_t sym) {
-            const uint2 e = s_otab[sym];
+        (void)lane_walk(t, n_codes, g, static_cast<uint32_t>(rec.len), [&](uint32_t, uint32_t, uint32_t meta) {
+            const uint2 e = s_otab[meta & 0xffu];
             const uint32_t n = e.y & RECODE_LEN_MASK;
-            if (!n) return;
+            if (!n) return true;
             acc |= (static_cast<uint64_t>(e.x) << 32) >> fill;  // (fill < 32 here: the code's 32 bits stay inside the 64)
             fill += n;
             if (fill >= 32) {
@@ -2789,19 +2714,21 @@ __global__ __launch_bounds__(BB) void k_recode_write(PackedStore store, const ui
                 ++word;
                 fill -= 32;
             }
+            return true;
         });
         if (fill) recode_store_word(dst.line, word, __builtin_bswap32(static_cast<uint32_t>(acc >> 32)), dst.lo, dst.hi);
     }
 }
 
-// k_recode_write_long: one workgroup per listed row that has bytes, block by block: the block settled and cut as k_recode_long does
-// it, the lanes' output bits scanned to each lane's destination bit within the block, then rounds of RECODE_ROUND_BITS destination
-// bits -- one 8 KiB block of 1-bit codes becomes 256 KiB of 32-bit ones, sixteen rounds; a block of 32-bit codes that become 1-bit ones
-// is one round of 256 bytes: a round never spans two input blocks, the partial word is what crosses.  In a round the lanes whose bits
-// meet it walk again and OR their codes into the LDS image (BatchDecLds::out: pack_round's inner loop -- an accumulator, atomicOr
-// where a word fills); a code that straddles a round's edge leaves its bits on either side in their own rounds.  Whole words leave as
-// byte-swapped dword stores, the row's first and last word clipped to its bytes, the word a round ends in is carried as `pending`
-// (pack_rounds' hand-over).  The image is zero between rounds.  Nothing is written when the rows need more than cap.
+// k_recode_write_long: long_rows over the listed rows that have bytes, block by block: the block settled and cut as k_recode_long
+// does it (recode_block), the lanes' output bits scanned to each lane's destination bit within the block, then rounds of
+// RECODE_ROUND_BITS destination bits -- one 8 KiB block of 1-bit codes becomes 256 KiB of 32-bit ones, sixteen rounds; a block of
+// 32-bit codes that become 1-bit ones is one round of 256 bytes: a round never spans two input blocks, the partial word is what
+// crosses.  In a round the lanes whose bits meet it walk again and OR their codes into the LDS image (BatchDecLds::out: pack_round's
+// inner loop -- an accumulator, atomicOr where a word fills); a code that straddles a round's edge leaves its bits on either side in
+// their own rounds.  Whole words leave as byte-swapped dword stores, the row's first and last word clipped to its bytes, the word a
+// round ends in is carried as `pending` (pack_rounds' hand-over).  The image is zero between rounds: the set-up zeroes it, behind the
+// two returns.  Nothing is written when the rows need more than cap.
 // LDS as k_recode_long: 35.2 KiB, three workgroups per CU.
 __global__ __launch_bounds__(BB) void k_recode_write_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, RecodeJob job,
                                                           const TakeRow *__restrict__ plan, const uint32_t *__restrict__ long_list,
@@ -2812,20 +2739,20 @@ __global__ __launch_bounds__(BB) void k_recode_write_long(PackedStore store, con
     __shared__ uint2 s_otab[256];
     __shared__ uint32_t s_scan[BB / 64];
     const uint32_t tid = threadIdx.x;
-    const uint32_t n_long = static_cast<uint32_t>(stats[SLICE_N_LONG]);
-    if (blockIdx.x >= n_long || out_index[job.n_rows] > cap) return;  // (the same for every thread)
-    s_otab[tid] = job.out_tab[tid];
-    load_tables(s.t, codes, n_codes);
-    for (uint32_t i = tid; i < sizeof(s.out) / 4; i += BB) s.out[i] = 0u;
-    for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
-        const uint32_t k = long_list[i];
-        if (k >= job.n_rows) continue;  // (k_recode_plan lists rows; the same for every lane, like all below)
+    const auto set_up = [&] {
+        if (out_index[job.n_rows] > cap) return false;  // (the same for every thread)
+        s_otab[tid] = job.out_tab[tid];
+        load_tables(s.t, codes, n_codes);
+        for (uint32_t i = tid; i < sizeof(s.out) / 4; i += BB) s.out[i] = 0u;
+        return true;
+    };
+    long_rows(job.n_rows, long_list, stats, set_up, [&](uint32_t k) {
         const uint32_t bytes = plan[k].body_bytes;
-        if (!bytes) continue;  // a failed row, or one whose every symbol is dropped
-        const Judged rec = recode_judge(store, job, k);
-        if (rec.status || rec.nb == 0 || rec.len == 0) continue;  // (k_recode_plan lists no such row)
+        if (!bytes) return;  // a failed row, or one whose every symbol is dropped
+        const Judged rec = judge_row(store, job.rows, k);
+        if (!stored_text(rec)) return;
         const uint32_t len = static_cast<uint32_t>(rec.len);
-        const BodyBits g = recode_body(store, rec);
+        const BodyBits g = reach_body(store, rec, len);
         const RecodeDst dst = recode_dst(d_out, out_index[k], bytes);
         const uint32_t n_blocks = (g.n_words + DEC_WORDS - 1) / DEC_WORDS;
         uint32_t start = g.first_bit, done = 0;     // the block's first codeword; codewords so far
@@ -2892,7 +2819,7 @@ __global__ __launch_bounds__(BB) void k_recode_write_long(PackedStore store, con
             done += rb.b.total;
         }
         if (tid == 0 && (carry & 31)) recode_store_word(dst.line, carry >> 5, __builtin_bswap32(pending), dst.lo, dst.hi);
-    }
+    });
 }
 
 // --------------------------------------------------------------------------------
@@ -2919,51 +2846,61 @@ static void launch_scan_emit(hipStream_t stream, uint32_t n_tiles, uint32_t grid
     else hipLaunchKernelGGL(k_rows_emit<false>, dim3(grid), dim3(BB), 0, stream, masks, base, n_tiles, d_rows, cap_rows, key_of, d_key_of_row);
 }
 
+// The grids of the take and the derived stores: a plan kernel's (a row per lane), a long kernel's (a listed row per workgroup).
+static uint32_t plan_grid(uint32_t n_rows) { return capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID); }
+
+static uint32_t long_grid(uint32_t n_rows) { return capped(n_rows, SHARED_DEC_GRID); }
+
+// k_take_scan behind the plan: the call's report leaves with it.
+static void launch_take_scan(hipStream_t stream, const TakeRow *plan, uint32_t n_rows, uint64_t *out_body_index, uint64_t *out_text_index, const PackedReport &r) {
+    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, plan, n_rows, out_body_index, out_text_index, static_cast<const unsigned long long *>(r.stats), r.host_result,
+                       r.host_done, r.epoch);
+}
+
+// k_take_copy behind the scan; BITS: the rows' sources are addresses of bits, and d_bodies is not looked at.
+template <bool BITS>
+static void launch_take_copy(hipStream_t stream, const void *d_bodies, const TakeRow *plan, const uint64_t *out_body_index, uint32_t n_rows, void *d_out, uint64_t cap) {
+    // (what fits into cap spans no more than cap / TAKE_TILE_BYTES + 2 tiles, at any alignment)
+    hipLaunchKernelGGL(k_take_copy<BITS>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(d_bodies), plan, out_body_index,
+                       n_rows, static_cast<uint8_t *>(d_out), cap);
+}
+
 void launch_take(hipStream_t stream, const PackedStore &store, const uint32_t *rows, uint32_t n_rows, void *d_out, uint64_t cap, uint64_t *out_body_index,
                  uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, const PackedReport &r) {
-    hipLaunchKernelGGL(k_take_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, rows, n_rows, plan, d_status, r.stats);
-    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
-                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
-    if (!d_out) return;
-    // (what fits into cap spans no more than cap / TAKE_TILE_BYTES + 2 tiles, at any alignment)
-    hipLaunchKernelGGL(k_take_copy<false>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(store.bodies),
-                       static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+    hipLaunchKernelGGL(k_take_plan, dim3(plan_grid(n_rows)), dim3(BB), 0, stream, store, rows, n_rows, plan, d_status, r.stats);
+    launch_take_scan(stream, plan, n_rows, out_body_index, out_text_index, r);
+    if (d_out) launch_take_copy<false>(stream, store.bodies, plan, out_body_index, n_rows, d_out, cap);
+}
+
+// The slice's and the field's four launches: the two differ in their kernels and their job alone.
+template <class Job, class PlanKernel, class LongKernel>
+static void launch_cut(hipStream_t stream, PlanKernel plan_kernel, LongKernel long_kernel, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const Job &job,
+                       void *d_out, uint64_t cap, uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list,
+                       const PackedReport &r) {
+    hipLaunchKernelGGL(plan_kernel, dim3(plan_grid(job.n_rows)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
+    hipLaunchKernelGGL(long_kernel, dim3(long_grid(job.n_rows)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list),
+                       static_cast<const unsigned long long *>(r.stats));
+    launch_take_scan(stream, plan, job.n_rows, out_body_index, out_text_index, r);
+    if (d_out) launch_take_copy<true>(stream, nullptr, plan, out_body_index, job.n_rows, d_out, cap);
 }
 
 void launch_slice(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const SliceJob &job, void *d_out, uint64_t cap,
                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &r) {
-    const uint32_t n_rows = job.n_rows;
-    hipLaunchKernelGGL(k_slice_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
-    hipLaunchKernelGGL(k_slice_long, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list),
-                       static_cast<const unsigned long long *>(r.stats));
-    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
-                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
-    if (!d_out) return;
-    hipLaunchKernelGGL(k_take_copy<true>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(nullptr),
-                       static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+    launch_cut(stream, k_slice_plan, k_slice_long, store, codes, n_codes, job, d_out, cap, out_body_index, out_text_index, d_status, plan, long_list, r);
 }
 
 void launch_field(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const FieldJob &job, void *d_out, uint64_t cap,
                   uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &r) {
-    const uint32_t n_rows = job.n_rows;
-    hipLaunchKernelGGL(k_field_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
-    hipLaunchKernelGGL(k_field_long, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list),
-                       static_cast<const unsigned long long *>(r.stats));
-    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
-                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
-    if (!d_out) return;
-    hipLaunchKernelGGL(k_take_copy<true>, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const uint8_t *>(nullptr),
-                       static_cast<const TakeRow *>(plan), static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
+    launch_cut(stream, k_field_plan, k_field_long, store, codes, n_codes, job, d_out, cap, out_body_index, out_text_index, d_status, plan, long_list, r);
 }
 
 void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &b, const uint2 *codes, uint32_t n_codes, const ConcatJob &job, void *d_out, uint64_t cap,
                    uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, ConcatPiece *pieces, const PackedReport &r) {
     const uint32_t n_rows = job.n_rows;
-    hipLaunchKernelGGL(k_concat_plan, dim3(capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID)), dim3(BB), 0, stream, a, b, codes, n_codes, job, plan, pieces, long_list, d_status, r.stats);
-    hipLaunchKernelGGL(k_concat_long, dim3(capped(n_rows, SHARED_DEC_GRID)), dim3(BB), 0, stream, a, b, codes, n_codes, job, plan, pieces, static_cast<const uint32_t *>(long_list),
-                       d_status, r.stats);
-    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
-                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
+    hipLaunchKernelGGL(k_concat_plan, dim3(plan_grid(n_rows)), dim3(BB), 0, stream, a, b, codes, n_codes, job, plan, pieces, long_list, d_status, r.stats);
+    hipLaunchKernelGGL(k_concat_long, dim3(long_grid(n_rows)), dim3(BB), 0, stream, a, b, codes, n_codes, job, plan, pieces, static_cast<const uint32_t *>(long_list), d_status,
+                       r.stats);
+    launch_take_scan(stream, plan, n_rows, out_body_index, out_text_index, r);
     if (!d_out) return;
     hipLaunchKernelGGL(k_concat_copy, dim3(capped(cap / TAKE_TILE_BYTES + 2, TAKE_GRID)), dim3(BB), 0, stream, static_cast<const ConcatPiece *>(pieces), job.sep, job.sep_bits,
                        static_cast<const uint64_t *>(out_body_index), n_rows, static_cast<uint8_t *>(d_out), cap);
@@ -2971,11 +2908,10 @@ void launch_concat(hipStream_t stream, const PackedStore &a, const PackedStore &
 
 void launch_recode(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const RecodeJob &job, void *d_out, uint64_t cap,
                    uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &r) {
-    const uint32_t n_rows = job.n_rows, lanes = capped((n_rows + BB - 1) / BB, GATHER_PLAN_GRID), groups = capped(n_rows, SHARED_DEC_GRID);
+    const uint32_t n_rows = job.n_rows, lanes = plan_grid(n_rows), groups = long_grid(n_rows);
     hipLaunchKernelGGL(k_recode_plan, dim3(lanes), dim3(BB), 0, stream, store, codes, n_codes, job, plan, long_list, d_status, r.stats);
     hipLaunchKernelGGL(k_recode_long, dim3(groups), dim3(BB), 0, stream, store, codes, n_codes, job, plan, static_cast<const uint32_t *>(long_list), d_status, r.stats);
-    hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(BB), 0, stream, static_cast<const TakeRow *>(plan), n_rows, out_body_index, out_text_index,
-                       static_cast<const unsigned long long *>(r.stats), r.host_result, r.host_done, r.epoch);
+    launch_take_scan(stream, plan, n_rows, out_body_index, out_text_index, r);
     if (!d_out) return;
     hipLaunchKernelGGL(k_recode_write, dim3(lanes), dim3(BB), 0, stream, store, codes, n_codes, job, static_cast<const TakeRow *>(plan),
                        static_cast<const uint64_t *>(out_body_index), static_cast<uint8_t *>(d_out), cap);
