@@ -15,6 +15,8 @@ from .codec import (  # noqa: F401
     EntreepyError,
     FIELD_ABSENT,
     FIELD_TO_END,
+    GROUP_NONE,
+    GroupResult,
     JoinResult,
     MATCH_EQUAL,
     MATCH_LESS,

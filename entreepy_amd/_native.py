@@ -136,6 +136,21 @@ class JoinResult(ctypes.Structure):
     ]
 
 
+class GroupResult(ctypes.Structure):
+    """struct et_group_result: what et_group_packed_device reports about the store and its groups."""
+
+    _fields_ = [
+        ("n_groups", ctypes.c_uint64),
+        ("n_failed", ctypes.c_uint64),
+        ("first_failed", ctypes.c_uint64),
+        ("first_status", ctypes.c_int32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
+ET_GROUP_NONE = 0xFFFFFFFF  # et_group_packed_device: d_group_of of a failed record
+
+
 class TakeResult(ctypes.Structure):
     """struct et_take_result: what et_take_packed_device reports about the rows and the store it made of them."""
 
@@ -211,6 +226,9 @@ SIGNATURES = {
     "et_join_table_slots": (_sz, [_sz]),
     "et_join_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(JoinResult)]),
     "et_selftest_join_hash": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "et_group_result_size": (_sz, []),
+    "et_group_records_max": (_sz, []),
+    "et_group_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(GroupResult)]),
     "et_take_result_size": (_sz, []),
     "et_take_packed_device": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(TakeResult)]),
     "et_slice_lane_bytes": (_sz, []),
@@ -312,6 +330,8 @@ def lib():
             raise ImportError(f"{LIB_PATH}: et_match_result is {L.et_match_result_size()} bytes there, {ctypes.sizeof(MatchResult)} in this binding")
         if L.et_join_result_size() != ctypes.sizeof(JoinResult):
             raise ImportError(f"{LIB_PATH}: et_join_result is {L.et_join_result_size()} bytes there, {ctypes.sizeof(JoinResult)} in this binding")
+        if L.et_group_result_size() != ctypes.sizeof(GroupResult):
+            raise ImportError(f"{LIB_PATH}: et_group_result is {L.et_group_result_size()} bytes there, {ctypes.sizeof(GroupResult)} in this binding")
         if L.et_take_result_size() != ctypes.sizeof(TakeResult):
             raise ImportError(f"{LIB_PATH}: et_take_result is {L.et_take_result_size()} bytes there, {ctypes.sizeof(TakeResult)} in this binding")
         _lib = L

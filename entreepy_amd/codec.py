@@ -78,6 +78,18 @@ class JoinResult:  # struct et_join_result, and the call's own status in front
 
 
 @dataclass
+class GroupResult:  # struct et_group_result, and the call's own status in front
+    status: int
+    n_groups: int
+    n_failed: int
+    first_failed: int
+    first_status: int
+
+
+GROUP_NONE = N.ET_GROUP_NONE  # group_packed_device: group_of of a failed record
+
+
+@dataclass
 class TakeResult:  # struct et_take_result, and the call's own status in front
     status: int
     out_bytes: int
@@ -628,6 +640,26 @@ class Context:
                                            rows_p, 0 if rows is None else rows.numel(), key_of_p, self._opt_ptr(status), self._opt_ptr(key_status), ctypes.byref(res))
         return JoinResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.n_keys_failed, res.first_key_failed, res.first_status, res.first_key_status)
 
+    def group_packed_device(self, codebook, bodies, body_index, text_index, first_rows=None, count=None, group_of=None, status=None):
+        """The groups of equal records of the store (bodies, body_index, text_index: join_packed_device's) -- DISTINCT, GROUP BY and
+        COUNT(*) -- decided on the compressed bytes by a join of the store with itself, nothing decoded.  Groups are numbered in order
+        of first appearance.  first_rows: int32/uint32 CUDA tensor that takes each group's lowest record number, ascending
+        (take_packed_device's rows: the store of the distinct texts); None: count only.  count: optional tensor like first_rows: the
+        members of each group.  group_of: optional tensor of one 32-bit entry per record: its group, GROUP_NONE for a failed record.
+        count and group_of need first_rows.  status: optional uint8 CUDA tensor of one et_status byte per record; a failed record
+        belongs to no group.  -> GroupResult; .status is ET_OK or ET_ERR_CAP (nothing written, .n_groups = the room needed); any
+        other failure of the call raises.  Stream-ordered like decode_packed_device."""
+        n = text_index.numel() - 1
+        what = "first_rows, count and group_of are 1-D CUDA tensors of 32-bit integers"
+        first_p, count_p, group_p = (None if t is None else self._rows_ptr(t, what) for t in (first_rows, count, group_of))
+        assert count is None or (first_rows is not None and count.numel() >= first_rows.numel()), "count is as large as first_rows"
+        assert group_of is None or group_of.numel() >= n, "group_of holds an entry per record"
+        res = N.GroupResult()
+        self._bind()
+        rc = N.lib().et_group_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
+                                            first_p, 0 if first_rows is None else first_rows.numel(), count_p, group_p, self._opt_ptr(status), ctypes.byref(res))
+        return GroupResult(self._cap_or_raise(rc), res.n_groups, res.n_failed, res.first_failed, res.first_status)
+
     def take_packed_device(self, bodies, body_index, text_index, rows, out, out_body_index, out_text_index, status=None):
         """Row k of the NEW store is record rows[k] of the store (bodies, body_index, text_index: decode_packed_gather_device's), in any
         order, with repeats: its body goes as it is to out[out_body_index[k] : out_body_index[k + 1]], the bodies back to back from 0,
@@ -906,6 +938,28 @@ class Context:
         if res.n_keys_failed:
             raise EntreepyError(res.first_key_status, f"join_packed: key {res.first_key_failed}")
         return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
+
+    def group_packed(self, codebook, blob, out_index, lengths):
+        """decode_packed's store -> (first_rows, counts, group_of) as numpy u32 arrays: each distinct text's first record, ascending,
+        how many records hold it, and every record's group -- through a count-only group_packed_device call, then the writing one."""
+        import torch
+
+        out_index, lengths = np.asarray(out_index, dtype=np.uint64), np.asarray(lengths, dtype=np.uint64)
+        assert out_index.size == lengths.size + 1
+        if not lengths.size:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
+        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
+        store = (d_blob, d_body_index, torch.from_numpy(text_index.view(np.int64)).to(d_blob.device))
+        res = self.group_packed_device(codebook, *store)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"group_packed: record {res.first_failed}")
+        d_first, d_count = (torch.empty(max(res.n_groups, 1), dtype=torch.int32, device=d_blob.device) for _ in range(2))
+        d_group_of = torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
+        res = self.group_packed_device(codebook, *store, first_rows=d_first, count=d_count, group_of=d_group_of)
+        _check(res.status, self._h)
+        host = lambda t, k: t[:k].cpu().numpy().view(np.uint32)  # (the copies run behind the call's kernels)
+        return host(d_first, res.n_groups), host(d_count, res.n_groups), host(d_group_of, lengths.size)
 
     # What the list helpers of the store-deriving calls (take, slice, field, concat, recode) share.
     @staticmethod

@@ -26,6 +26,7 @@
 //   order         (the match's LESS modes) sorted codes + counters + pattern + boundaries -> k_order_flag -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   search        sorted codes + counters + pattern -> k_search_flag -> k_search_long -> k_packed_scan (poll) -> unless count only: k_rows_emit
 //   join          counters -> clear the table -> k_join_build -> k_join_flag (the keys' counters into the report) -> k_packed_scan (poll) -> unless count only: k_rows_emit
+//   group         counters -> clear the table -> k_group_build (the store as its own key set) -> k_group_flag -> k_packed_scan (poll) -> unless count only: k_group_emit, k_group_number
 //   take          counters -> k_take_plan -> k_take_scan (poll) -> unless sizes only: k_take_copy
 //   slice         sorted codes + counters -> k_slice_plan -> k_slice_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
 //   field         sorted codes + counters -> k_field_plan -> k_field_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
@@ -72,6 +73,7 @@ static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the p
 //   recode  the output table (256 x {code of map[s] under table OUT, length}, 2 KiB) at PK_PATTERN; behind it a TakeRow per row, then a list entry per row
 //   search  as the match, then a position and a list entry per record
 //   match   behind the pattern: the tile workspace (tile_ws)                   join   behind the counters: the tile workspace, the table's slots, a key number per record
+//   group   as the join, the table sized for the records themselves, then a hash, a representative and a group number per record
 //   order   (the match's LESS modes) the sorted codes, the counters, the pattern, the boundary table behind the pattern's last word, the tile workspace
 constexpr size_t PK_STATS = 2048, PK_PATTERN = PK_STATS + PK_COUNTER_BYTES, PK_SIZES = 4096, PK_MATCH_TILES = PK_PATTERN + et::MATCH_PATTERN_BYTES;
 static_assert(PK_PATTERN % 16 == 0 && PK_MATCH_TILES % 16 == 0 && PK_SIZES % 16 == 0 && sizeof(et::TakeRow) == 16,
@@ -609,6 +611,48 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
     read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
     read_failures(rep, et::JOIN_KEYS_FAILED, &res->n_keys_failed, &res->first_key_failed, &res->first_key_status);
     if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_rows_emit saw the same two figures)
+    return ET_OK;
+}
+
+extern "C" size_t et_group_result_size(void) { return sizeof(et_group_result); }
+
+extern "C" size_t et_group_records_max(void) { return et::ET_JOIN_KEYS_MAX; }
+
+static_assert(ET_GROUP_NONE == et::GROUP_NONE, "d_group_of of a failed record");
+
+extern "C" int et_group_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                      const uint64_t *d_text_index, size_t n_records, uint32_t *d_first_rows, size_t cap_groups, uint32_t *d_count, uint32_t *d_group_of,
+                                      uint8_t *d_status, et_group_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (misaligned(7, d_body_index, d_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    if (misaligned(3, d_first_rows, d_count, d_group_of)) return fail(ctx, ET_ERR_ARG, "the first rows, the counts or the group numbers are not 4-byte aligned");
+    if (n_records > et::ET_JOIN_KEYS_MAX) return fail(ctx, ET_ERR_ARG, "more records than et_group_records_max()");
+    if ((d_count || d_group_of) && !d_first_rows) return fail(ctx, ET_ERR_ARG, "counts or group numbers without first rows");
+    *res = et_group_result{};
+    if (n_records == 0) return ET_OK;
+    ET_TRY(require_complete(ctx, cb));
+    DeviceGuard guard(ctx->device);
+    const et::PackedStore records{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    // the join's layout, the store as its own key set, plus three words per record: its hash, its representative, and a representative's group
+    const size_t slots = et::et_join_slots_for(n_records);
+    Bump layout{PK_STATS + PK_COUNTER_BYTES};
+    const TileOffsets tiles = tile_ws(layout, (records.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const size_t at_table = layout.take(slots * 8, 8), at_hash_of = layout.take(n_records * 8, 8), at_rep_of = layout.take(n_records * 4, 4), at_dense = layout.take(n_records * 4, 4);
+    ET_TRY(packed_ensure(ctx, layout.end));
+
+    const uint64_t *first = first_counters(ctx);
+    ET_HIP(hipMemcpyAsync(ws<uint8_t>(ctx, PK_STATS), first, PK_COUNTER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    ET_HIP(hipMemsetAsync(ws<uint8_t>(ctx, at_table), 0xff, slots * 8, ctx->stream));
+    const et::PackedReport report = next_report(ctx);
+    et::launch_group(ctx->stream, records, ws<unsigned long long>(ctx, at_table), slots, d_first_rows, cap_groups, d_count, d_group_of, d_status, tile_ptrs(ctx, tiles),
+                     ws<uint64_t>(ctx, at_hash_of), ws<uint32_t>(ctx, at_rep_of), ws<uint32_t>(ctx, at_dense), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the group call's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
+    if (rep[et::PACKED_N_FAILED] & et::JOIN_FAULT_BIT) return fail(ctx, ET_ERR_HIP, "a probe sequence of the group call's table met no slot of its text");
+    res->n_groups = rep[et::PACKED_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_first_rows && res->n_groups > cap_groups) return fail(ctx, ET_ERR_CAP, "more groups than cap_groups");  // (k_group_emit and k_group_number saw the same two figures)
     return ET_OK;
 }
 

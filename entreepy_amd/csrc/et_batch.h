@@ -239,6 +239,30 @@ void launch_join(hipStream_t stream, const PackedStore &records, const PackedSto
 // et_selftest_join_hash: d_hash[b] = the hash of record b as k_join_build and k_join_flag compute it (a failed record's entry is left).
 void launch_join_hash(hipStream_t stream, const PackedStore &records, uint64_t *d_hash);
 
+// The group (et_group_packed_device): which records of a packed store hold the same text -- the distinct texts in order of first
+// appearance, how many records hold each, and every record's group -- decided on the compressed bytes as a join of the store with
+// itself.  With the store as its own key set, the slot a record ends in names the lowest-numbered record of its text: the group's
+// representative, whose rank among the representatives is the group's number.
+//   (clear)         the table's slots to ET_JOIN_EMPTY: one hipMemsetAsync
+//   k_group_build   k_join_build's tiles over the store itself: judged, hashed (the hash kept: a u64 per record), inserted -- the slot LOADED before
+//                   any atomic, so that a record behind the first of its text, which finds a lower number there, issues none; the
+//                   table is final behind it
+//   k_group_flag    one record per lane, tiles of MATCH_TILE records: judged, its status byte, probed with the kept hash for the slot of its
+//                   text; a slot that holds the record's own number ends the probe with no look at bytes, any other is confirmed by length,
+//                   byte count and bytes; a u32 representative per record, ballot masks and tile counts of "is its own representative"
+//   k_packed_scan   the tile counts -> the tiles' first group numbers, n_groups; its report is the call's
+//   k_group_emit    (unless count only) per representative: d_first_rows[g], d_count[g] = 0, and g into a second word per record
+//   k_group_number  (unless neither is asked for) per record: d_group_of[b] = its representative's g, and d_count[g] += 1 -- combined in
+//                   the wavefront by rounds of "the lowest lane left takes its group, one atomic adds the popcount of the lanes that
+//                   share it" until GROUP_COMBINE_MISSES rounds served their leader alone, the remainder adding singly
+// Bodies above JOIN_LANE_BYTES are handled by the whole wavefront in the build and in the flag kernel, as in the join.
+constexpr uint32_t GROUP_NONE = 0xffffffffu;      // d_group_of[b], and the representative, of a failed record
+constexpr uint32_t GROUP_COMBINE_MISSES = 4;      // k_group_number stops combining after this many rounds that found their leader alone
+// table: `slots` u64 (et_join_slots_for(records.n)), cleared; hash_of: a u64 per record, rep_of, dense: a u32 per record each --
+// workspace.  The report ({n_groups, failed, first << 8 | status}, then `epoch`) leaves with the scan, in front of k_group_emit.
+void launch_group(hipStream_t stream, const PackedStore &records, unsigned long long *table, uint64_t slots, uint32_t *d_first_rows, uint64_t cap_groups, uint32_t *d_count,
+                  uint32_t *d_group_of, uint8_t *d_status, const TileWs &tiles, uint64_t *hash_of, uint32_t *rep_of, uint32_t *dense, const PackedReport &report);
+
 // The take (et_take_packed_device): a selection of a packed store's records as a NEW packed store -- the bodies of rows[] copied
 // back to back as they are, both offset arrays made by a scan -- without a table: no bit is interpreted.
 //   k_take_plan   one row per lane (k_gather_plan's shape, plus: a body above TAKE_BODY_MAX is unsupported): a TakeRow per row into

@@ -32,6 +32,11 @@
 //            k_join_flag     one lane per record: judged, hashed, probed, every hit confirmed by bytes; ballot masks, tile counts, key numbers
 //            k_packed_scan   as in the match
 //            k_rows_emit     as in the match, with the lowest equal key's number beside the record's where asked for
+//   group    k_group_build   the join's build with the store as its own key set: equal records meet in one slot, which keeps the lowest number; the slot is loaded before any atomic
+//            k_group_flag    one lane per record: judged, probed with the build's hash for its representative; ballot masks and tile counts of the representatives
+//            k_packed_scan   as in the match
+//            k_group_emit    the representatives, ascending, by popcount ranks: first rows, counts zeroed, each one's dense number
+//            k_group_number  one lane per record: its group's number; the counts by adds combined in the wavefront
 //   take     k_take_plan     one lane per row of a selection: its record judged, {body bytes, length, where the body begins} into the workspace
 //            k_take_scan     ONE workgroup: the two sizes -> out_body_index and out_text_index, the report
 //            k_take_copy     the selected bodies back to back as they are: one lane per aligned 16-byte word of the OUTPUT
@@ -1607,6 +1612,204 @@ __global__ __launch_bounds__(BB) void k_join_hash(PackedStore recs, uint64_t *__
 }
 
 // --------------------------------------------------------------------------------
+// The group call: which records of a packed store hold the same text, decided on the compressed bytes -- a join of the store with
+// itself.  k_group_build is k_join_build with the store as its own key set; when it is over, the slot a valid record's probe sequence ends
+// in holds the LOWEST number among the records of its text (the insert's atomicMin), whatever the order of the workgroups: that record
+// is the group's representative, and its rank among the representatives -- the flag kernels' masks, counts and scan -- is the group's
+// number.  A body of no bytes under a length above zero equals nothing: it was never inserted and is its own representative.
+// Every probe loop ends after `slots` trips at the latest and sets the join's fault bit when it runs out; a valid record that was
+// inserted always finds its text in front of the first empty slot, so an empty slot met here is the same fault.  No workgroup waits
+// for another: the counts are added by atomics nobody waits for, behind the launch that zeroed them.
+// --------------------------------------------------------------------------------
+// The representative of `me`, record b of the store the table was built over: the probe sequence to the slot with the hash's tag that
+// holds b itself -- no byte is looked at: b is the lowest of its text -- or a record that is confirmed by length, byte count and bytes.
+template <bool WAVE>
+__device__ __forceinline__ uint32_t group_probe(const PackedStore &recs, const unsigned long long *table, uint64_t slot_mask, uint64_t h, const JoinItem &me, uint32_t b,
+                                                uint32_t lane, bool *fault) {
+    uint64_t pos = h & slot_mask;
+    for (uint64_t trip = 0; trip <= slot_mask; ++trip, pos = (pos + 1) & slot_mask) {
+        const unsigned long long slot = table[pos];
+        if (slot == ET_JOIN_EMPTY) break;
+        if ((slot ^ h) >> 32) continue;
+        if (static_cast<uint32_t>(slot) == b) return b;
+        const JoinItem other = key_item(recs, static_cast<uint32_t>(slot));
+        if (other.len != me.len || other.nb != me.nb) continue;
+        if (WAVE ? wave_same(me.body, other.body, me.nb, lane) : lane_same(me.body, other.body, me.nb)) return static_cast<uint32_t>(slot);
+    }
+    *fault = true;
+    return b;
+}
+
+// Record k into the table: join_insert for a store in which MOST records may hold one text.  There join_insert sends a failed
+// compare-and-swap and an atomicMin per record to one slot (262 144 records, 90 % of them one text: 5.4 ms of a 5.4 ms call, DESIGN
+// section 6).  Here the slot is LOADED first.  What a load returns may be old, but a slot only ever goes from empty to a text's word and
+// from there to lower numbers of the same text, so an old value is never wrong, only late: "empty" is settled by the compare-and-swap;
+// a word of another tag or text is passed; a word of this text BELOW k's means the slot holds a number no higher now and k has
+// nothing to add -- no atomic at all, which is the case for nearly every record behind the first of its text --; a higher one gets
+// the atomicMin.  false: `slots` trips without an end.  WAVE: as join_insert's.
+template <bool WAVE>
+__device__ __forceinline__ bool group_insert(const PackedStore &recs, unsigned long long *table, uint64_t slot_mask, uint32_t k, uint64_t h, const JoinItem &me, uint32_t lane) {
+    const unsigned long long word = (h & 0xffffffff00000000ull) | k;
+    uint64_t pos = h & slot_mask;
+    for (uint64_t trip = 0; trip <= slot_mask; ++trip, pos = (pos + 1) & slot_mask) {
+        unsigned long long old = 0;
+        if (!WAVE || lane == 0) {
+            old = __atomic_load_n(table + pos, __ATOMIC_RELAXED);
+            if (old == ET_JOIN_EMPTY) old = atomicCAS(table + pos, ET_JOIN_EMPTY, word);
+        }
+        if (WAVE) old = __shfl(old, 0, 64);
+        if (old == ET_JOIN_EMPTY) return true;
+        if ((old ^ word) >> 32) continue;
+        const JoinItem other = key_item(recs, static_cast<uint32_t>(old));
+        if (other.len != me.len || other.nb != me.nb) continue;
+        if (!(WAVE ? wave_same(me.body, other.body, me.nb, lane) : lane_same(me.body, other.body, me.nb))) continue;
+        if (old > word && (!WAVE || lane == 0)) atomicMin(table + pos, word);
+        return true;
+    }
+    return false;
+}
+
+// k_group_build: k_join_build's tiles over the store itself, less what the group call has no use for (status bytes and tally are
+// k_group_flag's; no [min, max]): a valid record -- unless it is a body of no bytes under a length above zero -- is hashed, its hash
+// kept for k_group_flag (hash_of[k]: the body is hashed once per call), and inserted by group_insert, alone up to JOIN_LANE_BYTES of
+// body, by its wavefront above.  No LDS.
+__global__ __launch_bounds__(BB) void k_group_build(PackedStore recs, unsigned long long *__restrict__ table, uint64_t slot_mask, uint64_t *__restrict__ hash_of,
+                                                    unsigned long long *__restrict__ stats) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t n_tiles = (recs.n + MATCH_TILE - 1) / MATCH_TILE;
+    bool fault = false;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t k = tile * MATCH_TILE + tid;  // (n <= 2^24: no wrap)
+        bool enter = false;
+        JoinItem me{0, 0, 0};
+        if (k < recs.n) {
+            const Judged rec = judge_record(recs, k);
+            if (!rec.status) {
+                me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + rec.b0, rec.nb, rec.len};
+                enter = me.nb > 0 || me.len == 0;
+            }
+        }
+        const uint64_t h = join_hash_lanes(enter, me.body, me.nb, me.len, lane);
+        if (enter) hash_of[k] = h;
+        if (enter && me.nb <= JOIN_LANE_BYTES && !group_insert<false>(recs, table, slot_mask, k, h, me, lane)) fault = true;
+        unsigned long long longs = __ballot(enter && me.nb > JOIN_LANE_BYTES);
+        while (longs) {
+            const int src = __ffsll(longs) - 1;
+            longs &= longs - 1;
+            const JoinItem it{static_cast<uintptr_t>(__shfl(static_cast<uint64_t>(me.body), src, 64)), __shfl(me.nb, src, 64), __shfl(me.len, src, 64)};
+            if (!group_insert<true>(recs, table, slot_mask, __shfl(k, src, 64), __shfl(h, src, 64), it, lane)) fault = true;
+        }
+    }
+    if (fault) atomicOr(stats + PACKED_N_FAILED, JOIN_FAULT_BIT);
+}
+
+// k_group_flag: k_join_flag's tiles, judgement, status bytes, tally, masks and counts over the store the table was built from (final:
+// k_group_build is over).  A valid record is probed with the hash the build kept -- alone up to JOIN_LANE_BYTES of body, by its
+// wavefront above -- for its representative; the body of no bytes under a length above zero is its own without a probe.  rep_of[b] =
+// the representative, or GROUP_NONE for a failed record; the flag of the tile's masks is "valid and its own representative".
+// LDS: 8 + 8 + 8 words.
+__global__ __launch_bounds__(BB) void k_group_flag(PackedStore recs, const unsigned long long *__restrict__ table, uint64_t slot_mask, const uint64_t *__restrict__ hash_of,
+                                                   TileWs tiles, uint32_t *__restrict__ rep_of, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ unsigned long long s_failed[BB / 64], s_first[BB / 64];
+    __shared__ uint32_t s_count[2][BB / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t n_tiles = (recs.n + MATCH_TILE - 1) / MATCH_TILE;
+    PackedTally tally;
+    bool fault = false;
+    uint32_t set = 0;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, set ^= 1) {
+        const uint32_t b = tile * MATCH_TILE + tid;  // (n <= 2^24: no wrap)
+        bool valid = false, probe = false;
+        JoinItem me{0, 0, 0};
+        if (b < recs.n) {
+            const Judged rec = judge_record(recs, b);
+            if (d_status) d_status[b] = static_cast<uint8_t>(rec.status);
+            tally.note(b, rec.status);
+            if (!rec.status) {
+                valid = true;
+                me = JoinItem{reinterpret_cast<uintptr_t>(recs.bodies) + rec.b0, rec.nb, rec.len};
+                probe = me.nb > 0 || me.len == 0;
+            }
+        }
+        const uint64_t h = probe ? hash_of[b] : 0;  // (the build judged b as this kernel does: a record that is probed was hashed)
+        uint32_t rep = valid ? b : GROUP_NONE;
+        if (probe && me.nb <= JOIN_LANE_BYTES) rep = group_probe<false>(recs, table, slot_mask, h, me, b, lane, &fault);
+        unsigned long long longs = __ballot(probe && me.nb > JOIN_LANE_BYTES);
+        while (longs) {
+            const int src = __ffsll(longs) - 1;
+            longs &= longs - 1;
+            const JoinItem it{static_cast<uintptr_t>(__shfl(static_cast<uint64_t>(me.body), src, 64)), __shfl(me.nb, src, 64), __shfl(me.len, src, 64)};
+            const uint32_t found = group_probe<true>(recs, table, slot_mask, __shfl(h, src, 64), it, __shfl(b, src, 64), lane, &fault);
+            if (static_cast<int>(lane) == src) rep = found;
+        }
+        if (b < recs.n) rep_of[b] = rep;
+        end_tile(valid && rep == b, tile, set, tiles, s_count);
+    }
+    if (fault) atomicOr(stats + PACKED_N_FAILED, JOIN_FAULT_BIT);
+    tally_lanes(tally, s_failed, s_first, stats);
+}
+
+// k_group_emit: k_rows_emit's tiles and ranks over the representatives: group g = base[tile] + rank of a representative gets its
+// first row, its count zeroed (COUNT) and its number stored where k_group_number finds it: dense[representative] = g.  Every
+// workgroup returns at once when the groups do not fit: ET_ERR_CAP writes nothing.  No LDS.
+template <bool COUNT>
+__global__ __launch_bounds__(BB) void k_group_emit(const unsigned long long *__restrict__ masks, const uint64_t *__restrict__ base, uint32_t n_tiles,
+                                                   uint32_t *__restrict__ first_rows, uint64_t cap_groups, uint32_t *__restrict__ count, uint32_t *__restrict__ dense) {
+    if (base[n_tiles] > cap_groups) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const unsigned long long *m = masks + static_cast<uint64_t>(tile) * (MATCH_TILE / 64);
+        const unsigned long long mine = m[wave];
+        if (!((mine >> lane) & 1)) continue;
+        uint32_t rank = __popcll(mine & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wave; ++w) rank += __popcll(m[w]);
+        const uint32_t record = tile * MATCH_TILE + tid;
+        const uint64_t g = base[tile] + rank;
+        first_rows[g] = record;
+        if (COUNT) count[g] = 0u;
+        dense[record] = static_cast<uint32_t>(g);
+    }
+}
+
+// k_group_number: a record per lane.  g = dense[rep_of[b]] is the record's group; a failed record's is GROUP_NONE.  group_of[b] = g
+// (may be null), and -- COUNT -- the record is added into count[g], which k_group_emit zeroed.  The adds are combined in the
+// wavefront first: per round the lowest lane still holding a record takes its group, the ballot of the lanes with the same group is
+// that group's share of the wavefront, and the leader adds its popcount with ONE atomic.  The rounds go on while they pay: after
+// GROUP_COMBINE_MISSES rounds that served their leader alone the rest adds singly, so a round that shares removes two lanes at least
+// and there are 32 + GROUP_COMBINE_MISSES at the most.  A column in which one value holds most records sends one add per wavefront to
+// that value's count, not 64; 64 records in 16 groups cost 16; a column of all different values pays GROUP_COMBINE_MISSES rounds -- a
+// readlane, a compare and a ballot each, and the leader's add is one it owed anyway -- and adds as it would have.
+// Integer adds commute: the counts are exact, whatever the order.  Returns at once when the groups do not fit.  No LDS.
+template <bool COUNT>
+__global__ __launch_bounds__(BB) void k_group_number(const uint32_t *__restrict__ rep_of, const uint32_t *__restrict__ dense, const uint64_t *__restrict__ base,
+                                                     uint32_t n_tiles, uint32_t n, uint64_t cap_groups, uint32_t *__restrict__ group_of, uint32_t *__restrict__ count) {
+    const uint64_t n_groups = base[n_tiles];
+    if (n_groups > cap_groups) return;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t b = tile * MATCH_TILE + threadIdx.x;
+        uint32_t g = GROUP_NONE;
+        if (b < n) {
+            const uint32_t rep = rep_of[b];
+            if (rep < n) g = dense[rep];
+            if (g >= n_groups) g = GROUP_NONE;  // (only behind a fault, which the host reports: a word k_group_emit never stored indexes nothing)
+            if (group_of) group_of[b] = g;
+        }
+        if (COUNT) {
+            unsigned long long left = __ballot(g != GROUP_NONE);
+            for (uint32_t alone = 0; left && alone < GROUP_COMBINE_MISSES;) {
+                const int leader = __ffsll(left) - 1;
+                const uint32_t lead_g = __shfl(g, leader, 64);
+                const unsigned long long same = __ballot(g == lead_g);  // (lead_g is a group: no failed lane is in it; a lane served before has another group)
+                if (static_cast<int>(threadIdx.x & 63) == leader) atomicAdd(count + lead_g, static_cast<uint32_t>(__popcll(same)));
+                left &= ~same;
+                alone += (same & (same - 1)) == 0;  // (a round that served its leader alone cost what a single add costs, and bought nothing)
+            }
+            if ((left >> (threadIdx.x & 63)) & 1) atomicAdd(count + g, 1u);
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------
 // The take call: rows[] of a packed store as a new packed store.  Under one table a body is a self-contained byte string, so row k of
 // the result is the bytes d_bodies[body_index[r], body_index[r + 1]) of its record r = rows[k] as they are, and its length is r's; no
 // bit is interpreted and no table comes to the device.  Three launches in stream order (et_batch.h), the host waiting for the second
@@ -2927,6 +3130,24 @@ void launch_join(hipStream_t stream, const PackedStore &records, const PackedSto
     hipLaunchKernelGGL(k_join_flag, dim3(grid), dim3(BB), 0, stream, records, keys, static_cast<const unsigned long long *>(table), slots - 1, flags, tiles, key_of, d_status,
                        r.stats, r.host_result);
     launch_scan_emit(stream, n_tiles, grid, tiles, d_rows, cap_rows, key_of, d_key_of_row, r);
+}
+
+void launch_group(hipStream_t stream, const PackedStore &records, unsigned long long *table, uint64_t slots, uint32_t *d_first_rows, uint64_t cap_groups, uint32_t *d_count,
+                  uint32_t *d_group_of, uint8_t *d_status, const TileWs &tiles, uint64_t *hash_of, uint32_t *rep_of, uint32_t *dense, const PackedReport &r) {
+    const uint32_t n_tiles = tiles_of(records.n), grid = capped(n_tiles, JOIN_GRID);
+    hipLaunchKernelGGL(k_group_build, dim3(grid), dim3(BB), 0, stream, records, table, slots - 1, hash_of, r.stats);
+    hipLaunchKernelGGL(k_group_flag, dim3(grid), dim3(BB), 0, stream, records, static_cast<const unsigned long long *>(table), slots - 1, static_cast<const uint64_t *>(hash_of), tiles,
+                       rep_of, d_status, r.stats);
+    launch_scan<true>(stream, tiles.counts, n_tiles, tiles.base, r);
+    if (!d_first_rows) return;
+    const unsigned long long *masks = tiles.masks;
+    const uint64_t *base = tiles.base;
+    if (d_count) hipLaunchKernelGGL(k_group_emit<true>, dim3(grid), dim3(BB), 0, stream, masks, base, n_tiles, d_first_rows, cap_groups, d_count, dense);
+    else hipLaunchKernelGGL(k_group_emit<false>, dim3(grid), dim3(BB), 0, stream, masks, base, n_tiles, d_first_rows, cap_groups, d_count, dense);
+    if (!d_count && !d_group_of) return;
+    const uint32_t *reps = rep_of, *numbers = dense;
+    if (d_count) hipLaunchKernelGGL(k_group_number<true>, dim3(grid), dim3(BB), 0, stream, reps, numbers, base, n_tiles, records.n, cap_groups, d_group_of, d_count);
+    else hipLaunchKernelGGL(k_group_number<false>, dim3(grid), dim3(BB), 0, stream, reps, numbers, base, n_tiles, records.n, cap_groups, d_group_of, d_count);
 }
 
 void launch_join_hash(hipStream_t stream, const PackedStore &records, uint64_t *d_hash) {

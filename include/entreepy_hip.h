@@ -553,6 +553,63 @@ int et_join_packed_device(et_ctx *ctx, const et_codebook *cb,
 int et_selftest_join_hash(et_ctx *ctx, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
                           const uint64_t *d_text_index, size_t n, uint64_t *d_hash);
 
+/* GROUP: which records of a packed store hold the SAME text -- SELECT DISTINCT key, GROUP BY key and COUNT(*) -- decided on the
+ * compressed bytes, nothing decoded: the distinct texts in order of first appearance, how many records hold each, and the group of
+ * every record.  A join of the store with itself: one build pass puts the store's own records into the join's hash table, where equal
+ * records meet in one slot that keeps the lowest record number; one probe pass finds every record's slot.  (Unrelated to et_group,
+ * the multi-GPU membership further down.)
+ *   The store is the join call's, and a record is judged as the join judges it, from its own two pairs of offsets: ET_ERR_ARG
+ *     unless body_index[b] <= body_index[b+1] <= body_bytes and text_index[b] <= text_index[b+1]; ET_ERR_UNSUPPORTED for a length
+ *     above the small-stream limit.  d_status[b] (one et_status byte per record; may be NULL) holds the status.  A failed record
+ *     belongs to no group, is never a first row and is counted nowhere; its d_group_of entry is ET_GROUP_NONE.  It fails alone, and
+ *     no kernel reads where its pair points.
+ *   Records a and b are EQUAL by the join's rule, word for word: both valid, their lengths (text_index differences) equal, their body
+ *     byte counts equal and those bytes identical -- except that a body of no bytes under a length above zero, which is how a record
+ *     looks whose encode failed and which is kept raw elsewhere, equals nothing, not even its like: each such record is a group of its
+ *     own, with count 1.  A length of 0 with an empty body equals its like.  Under one table the encoder is deterministic, so for
+ *     bodies exactly as this library's encoders write them (ceil(bits / 8) bytes, the pad bits zero) two records are in one group
+ *     exactly when their stored texts are the same.  A hand-made body with bytes behind its last codeword, or with pad bits that are
+ *     not zero, can equal a needle under ET_MATCH_EQUAL and is put in a group apart from the encoder-made body of the same text here;
+ *     records whose stored texts differ are never in one group.
+ *   The group of a valid record is the set of valid records equal to it; its REPRESENTATIVE is the lowest record number in it.
+ *     Groups are numbered 0 .. n_groups - 1 by ascending representative: the order of first appearance, the same on every call.
+ *   d_first_rows[0 .. n_groups) (32 bits each, 4-byte aligned, on the device) = the representatives, ascending: the d_rows that the
+ *     take and gather calls consume -- take(d_first_rows) is the store of the distinct texts.  d_count[g] (may be NULL) = the members
+ *     of group g; their sum is the number of valid records, and the counts are exact and the same on every call.  d_group_of[b]
+ *     (may be NULL; n_records entries) = the group of record b, or ET_GROUP_NONE.  Nothing at or beyond d_first_rows + n_groups or
+ *     d_count + n_groups is written.
+ *   d_first_rows == NULL: count only -- cap_groups is ignored, d_status and *res are the writing call's; d_count or d_group_of given
+ *     without d_first_rows is ET_ERR_ARG.  n_groups > cap_groups: the call returns ET_ERR_CAP, no entry of d_first_rows, d_count or
+ *     d_group_of is written, d_status is complete and res->n_groups is the room needed.
+ * The call's own status: ET_ERR_ARG (a null ctx, cb, res, d_bodies, d_body_index or d_text_index; an offset array that is not
+ * 8-byte aligned; d_first_rows, d_count or d_group_of not 4-byte aligned; n_records above et_group_records_max(); d_count or
+ * d_group_of with d_first_rows == NULL -- all checked before anything touches a device, *res untouched), ET_ERR_UNSUPPORTED (the table
+ * is not complete: nothing is enqueued), ET_ERR_CAP, ET_ERR_HIP, ET_ERR_NOMEM.  n_records == 0: ET_OK, nothing enqueued, *res zeroed.
+ * One upload (64 bytes of counters), a clear of the table (et_join_table_slots(n_records) slots), three launches and one hand-over
+ * for a count-only call, behind the scan; up to two more launches behind the hand-over for a writing one.  Stream-ordered like the
+ * other packed calls -- *res is final on return, the device arrays once the ctx's stream has drained -- and it may follow or precede
+ * any other packed, gather, match, search, join, take, slice, field, concat, recode, shared-table or single-stream call on one ctx
+ * with nothing in between: the store may come straight from et_field_packed_device, d_first_rows may go straight into
+ * et_take_packed_device.  It keeps the state a ctx holds between calls (the histogram link, the held range) as it is.
+ * Out of scope: groups in SORTED order (ORDER BY: groups come in order of first appearance); grouping a selection given by d_rows
+ * (take first); grouping over several columns in one call (concat first); more than et_group_records_max() records per call; sums
+ * or other aggregates over a value column (d_group_of is on the device for that); case-insensitive grouping (recode first). */
+#define ET_GROUP_NONE 0xffffffffu
+typedef struct et_group_result {
+    uint64_t n_groups;                      /* groups found -- also when the call returns ET_ERR_CAP or d_first_rows is NULL */
+    uint64_t n_failed, first_failed;        /* records whose status is not ET_OK, the lowest of them (valid when n_failed > 0) */
+    int32_t first_status;                   /* et_status of record first_failed */
+    uint32_t pad;
+} et_group_result;
+size_t et_group_result_size(void);
+size_t et_group_records_max(void);          /* most records per call: et_join_keys_max(), 1 << 24 */
+int et_group_packed_device(et_ctx *ctx, const et_codebook *cb,
+                           const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                           const uint64_t *d_text_index, size_t n_records,
+                           uint32_t *d_first_rows, size_t cap_groups,
+                           uint32_t *d_count, uint32_t *d_group_of,
+                           uint8_t *d_status, et_group_result *res);
+
 /* TAKE: a SELECTION of a packed store's records as a NEW packed store, on the device, nothing decoded and nothing encoded again: what
  * keeps the result of a match or a join compressed -- as the key set of the next join, as the store that is left when rows are
  * deleted or reordered, or as the bytes that go to another rank or a file.  Under one table a record's body is a self-contained byte

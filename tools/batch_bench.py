@@ -69,7 +69,11 @@ process of its own so that every leg loads exactly one build of the library:
                   gather), a torch gather through the map's table, et_encode_packed_device under the other table; the sizes-only call
                   and the slice [0, TO_END) of the same rows as floors
   recode_sweep    (only when named) the search sweep's stores, every row re-tabled: run it on builds with -DET_RECODE_LANE_BYTES=0 and =8192
---legs picks the legs (default: all but the sweeps, concat and recode).
+  group           (only when named) et_group_packed_device (262 144 key-like records drawn from pools of 16, 1 024 and 65 536 values, all
+                  different, and 1 024 values with one on 90 % of the records; 4 096 x 4 KiB pages from a pool of 512) with all three
+                  outputs and count only, against what it replaces, in the same process: et_decode_packed_device, the texts padded into
+                  a matrix with their lengths, torch.unique(dim=0) with inverse and counts; the two partitions and counts compared first
+--legs picks the legs (default: all but the sweeps, concat, recode and group).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
 text once before timing.  One JSON line on stdout (and into --out).
@@ -87,6 +91,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs field --batch-lib /path/to/parent/libentreepy_hip.so --out profiles/field_bench.json
     python tools/batch_bench.py --legs concat --out profiles/concat_bench.json
     python tools/batch_bench.py --legs recode --out profiles/recode_bench.json
+    python tools/batch_bench.py --legs group --out profiles/group_bench.json
 """
 import argparse
 import ctypes
@@ -1291,6 +1296,100 @@ def _recode_leg(lib_path, shapes, sweep=False):
     print(json.dumps(results))
 
 
+GROUP_POOLS = [("pool_16", 16, 0.0), ("pool_1024", 1024, 0.0), ("pool_65536", 65536, 0.0), ("all_distinct", None, 0.0), ("pool_1024_one_value_90pct", 1024, 0.9)]
+
+
+def _group_store(count, size, pool, hot):
+    """-> (text, text_index) as numpy arrays: `count` records drawn from `pool` different text-like values (None: every record its own),
+    as long as `size` says (a number, or a range); `hot` of the records hold value 0.  A value's first four bytes spell its number, so
+    that no two values are the same text."""
+    import numpy as np
+
+    from tests import corpus
+
+    n_values = count if pool is None else pool
+    rng = np.random.default_rng(0x6E0A9 + count + n_values + int(hot * 1000))
+    value_lengths = np.full(n_values, size) if isinstance(size, int) else rng.integers(size[0], size[1] + 1, size=n_values)
+    value_index = np.concatenate(([0], np.cumsum(value_lengths))).astype(np.int64)
+    values = corpus.text_like(int(value_index[-1]), 0x6E0A9 + n_values).copy()
+    for k in range(4):
+        values[value_index[:-1] + k] = 48 + ((np.arange(n_values) >> (6 * k)) & 63)
+    pick = np.arange(count) if pool is None else rng.integers(0, n_values, size=count)
+    if hot:
+        pick[rng.random(count) < hot] = 0
+    lengths = value_lengths[pick]
+    index = np.concatenate(([0], np.cumsum(lengths))).astype(np.int64)
+    src = np.repeat(value_index[pick] - index[:-1], lengths) + np.arange(int(index[-1]))
+    return values[src], index.astype(np.uint64)
+
+
+def _group_leg(lib_path, shapes):
+    """group: on the 262 144 key-like records texts drawn from pools of 16, 1 024 and 65 536 values, all different, and 1 024 values with
+    one of them on 90 % of the records; on 4 096 x 4 KiB pages drawn from a pool of 512 (the wavefront's path).  Per case
+    et_group_packed_device with all three outputs, beside it the count-only call -- and, in the same process, the route it replaces:
+    et_decode_packed_device, the texts padded into an [n, longest + 4] matrix on the device with the length in the last four columns (no
+    padding makes two texts equal), torch.unique(dim=0, return_inverse=True, return_counts=True).  The two routes' answers are compared
+    first: the partition d_group_of induces is the one `inverse` induces, and the counts agree class by class."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device", "et_group_packed_device"])
+    results = {}
+    res, gres = N.PackedResult(), N.GroupResult()
+
+    def case(host, index):
+        n, total = index.size - 1, int(index[-1])
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, torch.from_numpy(host).to(dev), index)
+        first, count, group_of = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))
+        lengths = text_index[1:] - text_index[:-1]
+        longest = int(lengths.max())
+        found = {}
+
+        def call(write=True):
+            assert L.et_group_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, first.data_ptr() if write else None, n,
+                                            count.data_ptr() if write else None, group_of.data_ptr() if write else None, None, ctypes.byref(gres)) == 0, L.et_last_error(h)
+            assert gres.n_failed == 0
+
+        def baseline():
+            dec = torch.empty(total + 64, dtype=torch.uint8, device=dev)
+            assert L.et_decode_packed_device(h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n, dec.data_ptr(), total, None, None,
+                                             ctypes.byref(res)) == 0 and res.n_failed == 0 and res.n_short == 0, L.et_last_error(h)
+            padded = torch.zeros((n, longest + 4), dtype=torch.uint8, device=dev)
+            row = torch.repeat_interleave(torch.arange(n, device=dev), lengths, output_size=total)
+            padded[row, torch.arange(total, device=dev) - text_index[:-1][row]] = dec[:total]
+            padded[:, longest:] = lengths.to(torch.int32).view(torch.uint8).reshape(n, 4)
+            found["values"], found["inverse"], found["counts"] = torch.unique(padded, dim=0, return_inverse=True, return_counts=True)
+
+        call()
+        baseline()
+        torch.cuda.synchronize()
+        g = int(gres.n_groups)
+        of, inverse = group_of.to(torch.int64), found["inverse"].reshape(-1).to(torch.int64)
+        assert g == found["counts"].numel() and torch.unique(of * g + inverse).numel() == g, "the two routes' partitions differ"
+        assert torch.equal(count[:g].to(torch.int64), found["counts"][inverse[first[:g].to(torch.int64)]].to(torch.int64)), "the two routes' counts differ"
+        assert int(count[:g].sum()) == n and bool((first[1:g] > first[: g - 1]).all())
+        entry = {"records": int(n), "groups": g, "largest_group": int(count[:g].max()), "text_bytes": total, "body_bytes": body_bytes}
+        entry.update(_timed(call))
+        entry["count_only"] = _timed(lambda: call(False))
+        entry["baseline"] = _timed(baseline)
+        gap, spreads = entry["baseline"]["ms"] - entry["ms"], (entry["baseline"]["max_ms"] - entry["baseline"]["min_ms"]) + (entry["max_ms"] - entry["min_ms"])
+        entry["baseline_over_group"], entry["beyond_both_spreads"] = round(entry["baseline"]["ms"] / entry["ms"], 2), bool(gap > spreads)
+        found.clear()
+        return entry
+
+    count, size = KEY_SHAPE
+    name = f"{count}x{size[0]}-{size[1]}"
+    if not shapes or name in shapes:
+        results[name] = {case_name: case(*_group_store(count, size, pool, hot)) for case_name, pool, hot in GROUP_POOLS}
+    count, size = SHAPES[1]
+    if not shapes or f"{count}x{size}" in shapes:
+        results[f"{count}x{size}"] = {"pool_512": case(*_group_store(count, size, 512, 0.0))}
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
@@ -1319,6 +1418,8 @@ def main():
         return _concat_leg(a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg in ("recode", "recode_sweep"):
         return _recode_leg(a.lib, [s for s in a.shapes.split(",") if s], sweep=a.leg == "recode_sweep")
+    if a.leg == "group":
+        return _group_leg(a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -1346,6 +1447,8 @@ def main():
         legs += [("concat", "concat", here)]
     if "recode" in a.legs.split(","):  # (likewise)
         legs += [("recode", "recode", here)]
+    if "group" in a.legs.split(","):  # (likewise)
+        legs += [("group", "group", here)]
     if "recode_sweep" in a.legs.split(","):
         legs += [("recode_sweep", "recode_sweep", here)]
     if "search_sweep" in a.legs.split(","):
@@ -1412,6 +1515,8 @@ def main():
         out["concat_condition_met"] = all(e["beyond_both_spreads"] for v in out["concat"].values() if isinstance(v, dict) for e in v.values() if isinstance(e, dict))
     if "recode" in out:
         out["recode_condition_met"] = all(e["beyond_both_spreads"] for v in out["recode"].values() if isinstance(v, dict) for e in v.values() if isinstance(e, dict))
+    if "group" in out:
+        out["group_condition_met"] = {k: {name: e["beyond_both_spreads"] for name, e in v.items()} for k, v in out["group"].items()}
     line = json.dumps(out)
     print(line)
     if a.out:
