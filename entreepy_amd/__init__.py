@@ -24,6 +24,11 @@ from .codec import (  # noqa: F401
     MATCH_NOT,
     MATCH_PREFIX,
     MatchResult,
+    NUMBER_BAD,
+    NUMBER_EMPTY,
+    NUMBER_OK,
+    NUMBER_RANGE,
+    NumberResult,
     PackedResult,
     RECODE_DROP,
     SEARCH_CONTAINS,

@@ -151,6 +151,24 @@ class GroupResult(ctypes.Structure):
 ET_GROUP_NONE = 0xFFFFFFFF  # et_group_packed_device: d_group_of of a failed record
 
 
+class NumberResult(ctypes.Structure):
+    """struct et_number_result: what et_number_packed_device reports about the rows: how many are of each kind, how many failed."""
+
+    _fields_ = [
+        ("n_ok", ctypes.c_uint64),
+        ("n_empty", ctypes.c_uint64),
+        ("n_bad", ctypes.c_uint64),
+        ("n_range", ctypes.c_uint64),
+        ("n_failed", ctypes.c_uint64),
+        ("first_failed", ctypes.c_uint64),
+        ("first_status", ctypes.c_int32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
+ET_NUMBER_OK, ET_NUMBER_EMPTY, ET_NUMBER_BAD, ET_NUMBER_RANGE = 0, 1, 2, 3  # et_number_packed_device: a row's kind byte
+
+
 class TakeResult(ctypes.Structure):
     """struct et_take_result: what et_take_packed_device reports about the rows and the store it made of them."""
 
@@ -243,6 +261,11 @@ SIGNATURES = {
                                                ctypes.POINTER(TakeResult)]),
     "et_recode_lane_bytes": (_sz, []),
     "et_recode_packed_device": (ctypes.c_int, [_vp, _cbp, _cbp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(TakeResult)]),
+    "et_number_result_size": (_sz, []),
+    "et_number_symbols_max": (_sz, []),
+    "et_number_lane_bytes": (_sz, []),
+    "et_number_packed_device": (ctypes.c_int, [_vp, _cbp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
+                                               _vp, _vp, ctypes.POINTER(NumberResult)]),
     "et_codebook_is_complete": (ctypes.c_int, [_cbp]),
     "et_body_bound": (_sz, [_cbp, _sz]),
     "et_histogram_device": (ctypes.c_int, [_vp, _vp, _sz, _vp]),
@@ -332,6 +355,8 @@ def lib():
             raise ImportError(f"{LIB_PATH}: et_join_result is {L.et_join_result_size()} bytes there, {ctypes.sizeof(JoinResult)} in this binding")
         if L.et_group_result_size() != ctypes.sizeof(GroupResult):
             raise ImportError(f"{LIB_PATH}: et_group_result is {L.et_group_result_size()} bytes there, {ctypes.sizeof(GroupResult)} in this binding")
+        if L.et_number_result_size() != ctypes.sizeof(NumberResult):
+            raise ImportError(f"{LIB_PATH}: et_number_result is {L.et_number_result_size()} bytes there, {ctypes.sizeof(NumberResult)} in this binding")
         if L.et_take_result_size() != ctypes.sizeof(TakeResult):
             raise ImportError(f"{LIB_PATH}: et_take_result is {L.et_take_result_size()} bytes there, {ctypes.sizeof(TakeResult)} in this binding")
         _lib = L

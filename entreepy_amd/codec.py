@@ -90,6 +90,21 @@ GROUP_NONE = N.ET_GROUP_NONE  # group_packed_device: group_of of a failed record
 
 
 @dataclass
+class NumberResult:  # struct et_number_result, and the call's own status in front
+    status: int
+    n_ok: int
+    n_empty: int
+    n_bad: int
+    n_range: int
+    n_failed: int
+    first_failed: int
+    first_status: int
+
+
+NUMBER_OK, NUMBER_EMPTY, NUMBER_BAD, NUMBER_RANGE = N.ET_NUMBER_OK, N.ET_NUMBER_EMPTY, N.ET_NUMBER_BAD, N.ET_NUMBER_RANGE  # number_packed_device: a row's kind
+
+
+@dataclass
 class TakeResult:  # struct et_take_result, and the call's own status in front
     status: int
     out_bytes: int
@@ -707,6 +722,46 @@ class Context:
                                             self._index_ptr(out_text_index, n_rows), self._opt_ptr(status), ctypes.byref(res))
         return self._take_result(rc, res)
 
+    def number_packed_device(self, codebook, bodies, body_index, text_index, rows, first, count, stop=None, values=None, kind=None, group_of=None, n_groups=None, sum=None,
+                             n=None, min=None, max=None, status=None):
+        """text[first : first + count] of record rows[k] of the store (slice_packed_device's store, rows, first, count and stop, word
+        for word), cut in front of the first byte `stop`, READ as an integer of the grammar [+-]?[0-9]+ on the compressed bytes, nothing
+        decoded.  values: optional int64 CUDA tensor of one entry per row: the value, 0 unless the row is NUMBER_OK.  kind: optional
+        uint8 CUDA tensor of one entry per row: NUMBER_OK, NUMBER_EMPTY (the empty text: SQL's NULL; also a failed row), NUMBER_BAD (not
+        of the grammar, or more than 32 symbols), NUMBER_RANGE (outside int64).  sum, n, min, max: optional int64 CUDA tensors of
+        n_groups entries each (n holds u64 counts): the aggregates over the NUMBER_OK rows of each group, initialised by the call --
+        0, 0, INT64_MAX, INT64_MIN --, the sum modulo 2^64.  group_of: int32/uint32 CUDA tensor of one group number per ROW
+        (group_packed_device's group_of when rows is None; GROUP_NONE skips the row, any other number >= n_groups fails it); None:
+        every row is in group 0 and n_groups is 1.  status: optional uint8 CUDA tensor of one et_status byte per ROW.  With no output
+        the call only counts.  -> NumberResult; any failure of the call raises.  Stream-ordered like slice_packed_device."""
+        n_records = text_index.numel() - 1
+        n_rows = n_records if rows is None else rows.numel()
+        what = "rows, first, count and group_of are ints or 1-D CUDA tensors of 32-bit integers"
+        first_p, first_v = (None, int(first)) if isinstance(first, (int, np.integer)) else (self._rows_ptr(first, what), 0)
+        count_p, count_v = (None, int(count)) if isinstance(count, (int, np.integer)) else (self._rows_ptr(count, what), 0)
+        assert all(p is None or t.numel() >= n_rows for p, t in ((first_p, first), (count_p, count))), "first and count hold a value per row"
+        if stop is None:
+            stop = SLICE_NO_STOP
+        elif not isinstance(stop, (int, np.integer)):
+            (stop,) = bytes(stop)
+        aggregates = [t for t in (sum, n, min, max) if t is not None]
+        if n_groups is None:
+            n_groups = 1 if aggregates and group_of is None else aggregates[0].numel() if aggregates else 0
+        for t in aggregates + ([] if values is None else [values]):
+            assert t.is_cuda and t.dim() == 1 and t.element_size() == 8 and t.is_contiguous() and not t.is_floating_point(), "values and the aggregates are 1-D CUDA tensors of 64-bit integers"
+        assert all(t.numel() >= n_groups for t in aggregates), "an aggregate holds an entry per group"
+        assert values is None or values.numel() >= n_rows, "values holds an entry per row"
+        assert kind is None or (kind.is_cuda and kind.element_size() == 1 and kind.is_contiguous() and kind.numel() >= n_rows), "kind is a CUDA tensor of one byte per row"
+        assert group_of is None or group_of.numel() >= n_rows, "group_of holds an entry per row"
+        res = N.NumberResult()
+        self._bind()
+        rc = N.lib().et_number_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n_records),
+                                             self._index_ptr(text_index), n_records, None if rows is None else self._rows_ptr(rows, what), n_rows, first_p, first_v, count_p,
+                                             count_v, int(stop), self._opt_ptr(values), self._opt_ptr(kind), None if group_of is None else self._rows_ptr(group_of, what),
+                                             int(n_groups), self._opt_ptr(sum), self._opt_ptr(n), self._opt_ptr(min), self._opt_ptr(max), self._opt_ptr(status), ctypes.byref(res))
+        _check(rc, self._h)
+        return NumberResult(rc, res.n_ok, res.n_empty, res.n_bad, res.n_range, res.n_failed, res.first_failed, res.first_status)
+
     def field_packed_device(self, codebook, bodies, body_index, text_index, rows, field, n_fields, delim, out, out_body_index, out_text_index, pos=None, status=None):
         """Row k of the NEW store is delim.join(text.split(delim)[field : field + n_fields]) of record rows[k] of the store (bodies,
         body_index, text_index: take_packed_device's; rows=None: row k is record k) -- SPLIT_PART, found and copied on the compressed
@@ -1041,6 +1096,38 @@ class Context:
         new = self._new_store(self._bodies_room(out_index, lengths, rows), rows.size, dev)  # (a slice is no longer than its record's body)
         res = self.slice_packed_device(codebook, *store, d_rows, first, count, *new, stop=stop)
         return self._store_download("slice_packed", res, *new)
+
+    def number_packed(self, codebook, blob, out_index, lengths, rows, first, count, stop=None, group_of=None, n_groups=None):
+        """decode_packed's store, a list of record numbers (any order, repeats allowed) and slice_packed's first, count and stop ->
+        (values as a numpy int64 array, kinds as a numpy u8 array) of text[first : first + count] read as integers, through one
+        number_packed_device call.  With n_groups (and group_of: a list of one group number per row; None: one group) also the four
+        aggregates: -> (values, kinds, sums, counts, minima, maxima), int64 arrays but the u64 counts.  Raises for a failed row."""
+        import torch
+
+        out_index, lengths = self._store_arrays(out_index, lengths)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if n_groups is None and group_of is not None:
+            raise ValueError("group_of needs n_groups")
+        if not rows.size:
+            empty = (np.zeros(0, np.int64), np.zeros(0, np.uint8))
+            if n_groups is None:
+                return empty
+            g = int(n_groups)
+            return empty + (np.zeros(g, np.int64), np.zeros(g, np.uint64), np.full(g, np.iinfo(np.int64).max), np.full(g, np.iinfo(np.int64).min))
+        store = self._store_upload(blob, out_index, lengths)
+        dev = store[0].device
+        first, count, d_rows = (self._per_row(v, rows.size, dev) for v in (first, count, rows))
+        d_values, d_kind = torch.empty(rows.size, dtype=torch.int64, device=dev), torch.empty(rows.size, dtype=torch.uint8, device=dev)
+        agg = {} if n_groups is None else {k: torch.empty(int(n_groups), dtype=torch.int64, device=dev) for k in ("sum", "n", "min", "max")}
+        d_group_of = None if group_of is None else self._per_row(list(group_of), rows.size, dev)
+        res = self.number_packed_device(codebook, *store, d_rows, first, count, stop=stop, values=d_values, kind=d_kind, group_of=d_group_of,
+                                        n_groups=None if n_groups is None else int(n_groups), **agg)
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"number_packed: row {res.first_failed}")
+        out = (d_values.cpu().numpy(), d_kind.cpu().numpy())  # (the copies run behind the call's kernels)
+        if n_groups is None:
+            return out
+        return out + (agg["sum"].cpu().numpy(), agg["n"].cpu().numpy().view(np.uint64), agg["min"].cpu().numpy(), agg["max"].cpu().numpy())
 
     def field_packed(self, codebook, blob, out_index, lengths, rows, field, n_fields=1, delim=b","):
         """decode_packed's store, a list of record numbers (any order, repeats allowed), each row's first field (from 0) and how many

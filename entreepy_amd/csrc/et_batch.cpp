@@ -32,6 +32,7 @@
 //   field         sorted codes + counters -> k_field_plan -> k_field_long -> k_take_scan (poll) -> unless sizes only: k_take_copy (reading bits)
 //   concat        sorted codes + counters + the encoded literal -> k_concat_plan -> k_concat_long -> k_take_scan (poll) -> unless sizes only: k_concat_copy
 //   recode        sorted codes of table IN + counters + the output table -> k_recode_plan -> k_recode_long -> k_take_scan (poll) -> unless sizes only: k_recode_write, k_recode_write_long
+//   number        sorted codes + counters -> the aggregates' first values (hipMemsetAsync, k_number_fill) -> k_number_plan -> k_number_long -> k_number_fold (poll)
 #include "et_ctx.h"
 
 #include "et_batch.h"
@@ -69,6 +70,7 @@ static_assert(PIN_PK_TABLE % 16 == 0 && PIN_PK_REPORT % 8 == 0, "layout of the p
 // table, the counters at PK_STATS for EVERY call, the match's pattern.  Behind the counters each call has its own layout:
 //   encode, gather   from PK_SIZES: a size word per record, or per row        take   from PK_SIZES: a TakeRow per row
 //   slice, field   from PK_SIZES: a TakeRow per row, then a list entry per row
+//   number  from PK_SIZES: a NumberRow per row, then a list entry per row
 //   concat  the encoded literal at PK_PATTERN (it ends in front of PK_SIZES); from PK_SIZES: a TakeRow per row, a list entry per row, a ConcatPiece per row
 //   recode  the output table (256 x {code of map[s] under table OUT, length}, 2 KiB) at PK_PATTERN; behind it a TakeRow per row, then a list entry per row
 //   search  as the match, then a position and a list entry per record
@@ -890,6 +892,73 @@ extern "C" int et_recode_packed_device(et_ctx *ctx, const et_codebook *cb_in, co
     et::launch_recode(ctx->stream, packed_store(src), ws<const uint2>(ctx, 0), n_codes, job, d_out, cap, d_out_body_index, d_out_text_index, d_status,
                       ws<et::TakeRow>(ctx, at_plan), ws<uint32_t>(ctx, at_list), report);
     return derived_end(ctx, report.epoch, res, d_out, cap, "the recode's report never reached the host", "the recoded rows need more than cap bytes");
+}
+
+extern "C" size_t et_number_result_size(void) { return sizeof(et_number_result); }
+
+extern "C" size_t et_number_symbols_max(void) { return et::NUMBER_SYMBOLS_MAX; }
+
+extern "C" size_t et_number_lane_bytes(void) { return et::NUMBER_LANE_BYTES; }
+
+static_assert(int(et::NUMBER_OK) == ET_NUMBER_OK && int(et::NUMBER_EMPTY) == ET_NUMBER_EMPTY && int(et::NUMBER_BAD) == ET_NUMBER_BAD && int(et::NUMBER_RANGE) == ET_NUMBER_RANGE,
+              "a row's kind byte is its ET_NUMBER_*");
+static_assert(sizeof(et::NumberRow) == 16 && sizeof(et_number_result) == 56 && int(et::NUMBER_N_RANGE) < int(et::PACKED_WORDS) && int(et::NUMBER_N_EMPTY) > int(et::SLICE_N_LONG),
+              "k_number_plan stores a NumberRow as 16 bytes; the kinds' counters lie in the free words behind the list's");
+
+extern "C" int et_number_packed_device(et_ctx *ctx, const et_codebook *cb, const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                                       const uint64_t *d_text_index, size_t n_records, const uint32_t *d_rows, size_t n_rows, const uint32_t *d_first, uint32_t first,
+                                       const uint32_t *d_count, uint32_t count, int stop, int64_t *d_values, uint8_t *d_kind, const uint32_t *d_group_of, size_t n_groups,
+                                       int64_t *d_sum, uint64_t *d_n, int64_t *d_min, int64_t *d_max, uint8_t *d_status, et_number_result *res) {
+    if (!ctx) return ET_ERR_ARG;
+    if (!cb || !res) return fail(ctx, ET_ERR_ARG, "null pointer");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, d_rows};
+    ET_TRY(source_args(ctx, src, n_rows, misaligned(3, d_first, d_count), nullptr, 0, nullptr, nullptr,
+                       {"the rows, the firsts or the counts are not 4-byte aligned", "too many records or rows", ROWS_ARE_RECORDS, ""}));
+    if (stop < ET_SLICE_NO_STOP || stop > 255) return fail(ctx, ET_ERR_ARG, "stop is a byte, or ET_SLICE_NO_STOP");
+    const bool aggregates = d_sum || d_n || d_min || d_max;
+    if (misaligned(7, d_values, d_sum, d_n, d_min, d_max)) return fail(ctx, ET_ERR_ARG, "the values or an aggregate array are not 8-byte aligned");
+    if (misaligned(3, d_group_of)) return fail(ctx, ET_ERR_ARG, "the group numbers are not 4-byte aligned");
+    if (d_group_of && !aggregates) return fail(ctx, ET_ERR_ARG, "group numbers without an aggregate output");
+    if (aggregates && n_groups == 0) return fail(ctx, ET_ERR_ARG, "an aggregate output without a group");
+    if (n_groups > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many groups");
+    if (aggregates && !d_group_of && n_groups != 1) return fail(ctx, ET_ERR_ARG, "without d_group_of every row is in group 0: n_groups must be 1");
+    *res = et_number_result{};
+    if (n_rows == 0) return ET_OK;
+    DeviceGuard guard(ctx->device);
+    // the slice's upload -- the sorted codes and the counters' first values in one copy -- and its layout: behind them a NumberRow
+    // and a list entry per row
+    uint32_t n_codes = 0;
+    ET_TRY(packed_upload(ctx, cb, false, n_rows * (sizeof(et::NumberRow) / 4 + 1), &n_codes));
+    // the aggregates' first values where a byte pattern gives them; launch_number fills min and max
+    if (d_sum) ET_HIP(hipMemsetAsync(d_sum, 0, n_groups * 8, ctx->stream));
+    if (d_n) ET_HIP(hipMemsetAsync(d_n, 0, n_groups * 8, ctx->stream));
+    et::NumberJob job{};
+    job.ask.rows = d_rows;
+    job.ask.d_first = d_first;
+    job.ask.d_count = d_count;
+    job.ask.n_rows = static_cast<uint32_t>(n_rows);
+    job.ask.first = first;
+    job.ask.count = count;
+    job.ask.stop = stop < 0 ? et::SLICE_NO_STOP : static_cast<uint32_t>(stop);  // (a byte without a code is no symbol of the table: it cuts nothing)
+    job.d_values = d_values;
+    job.d_kind = d_kind;
+    job.group_of = d_group_of;
+    job.n_groups = aggregates ? static_cast<uint32_t>(n_groups) : 0u;
+    job.d_sum = d_sum;
+    job.d_n = reinterpret_cast<unsigned long long *>(d_n);
+    job.d_min = d_min;
+    job.d_max = d_max;
+    const et::PackedReport report = next_report(ctx);
+    et::launch_number(ctx->stream, packed_store(src), ws<const uint2>(ctx, 0), n_codes, job, d_status, ws<et::NumberRow>(ctx, PK_SIZES),
+                      ws<uint32_t>(ctx, PK_SIZES + n_rows * sizeof(et::NumberRow)), report);
+    ET_TRY(packed_poll(ctx, report.epoch, "the number call's report never reached the host"));
+    const uint64_t *rep = report_words(ctx);
+    res->n_empty = rep[et::NUMBER_N_EMPTY];
+    res->n_bad = rep[et::NUMBER_N_BAD];
+    res->n_range = rep[et::NUMBER_N_RANGE];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    res->n_ok = n_rows - res->n_empty - res->n_bad - res->n_range - res->n_failed;
+    return ET_OK;
 }
 
 

@@ -291,7 +291,7 @@ void launch_take(hipStream_t stream, const PackedStore &store, const uint32_t *r
 // kernel is plan_rows (a row per lane: judge_row, reach_body, lane_walks; the lane's walk is lane_walk; the status byte, the tally, the
 // wavefront's rows onto long_list with one atomic), a long kernel is long_rows (a listed row per workgroup, the list strided, nothing set
 // up beyond the list; settle_block per 8 KiB block, reduce_min_min_max, cut_at_length, fail_row_late).  What is said of a kernel below
-// is its family's middle.  The counters' word for the list is SLICE_N_LONG for all four.
+// is its family's middle.  The counters' word for the list is SLICE_N_LONG for all four, and for the number call, the frame's fifth member.
 //
 // The slice (et_slice_packed_device): symbols [first, first + count) of rows[]' stored texts, cut in front of a stop byte, as a NEW
 // packed store -- under one complete prefix-free table a substring is the run of bits between two codeword boundaries, so the body the
@@ -444,5 +444,57 @@ struct RecodeJob {
 // The report leaves with the scan, in front of the two writes.
 void launch_recode(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const RecodeJob &job, void *d_out, uint64_t cap,
                    uint64_t *out_body_index, uint64_t *out_text_index, uint8_t *d_status, TakeRow *plan, uint32_t *long_list, const PackedReport &report);
+
+// The number (et_number_packed_device): rows[]' slices READ as integers -- CAST(SUBSTR(..) AS BIGINT), SUM / COUNT / MIN / MAX per group
+// -- on the compressed bytes.  The fifth member of the derived-store frame, and the first that makes no store: the ask, the judgement,
+// the reach and both walks are the slice's, but what a walk notes is not two bit positions: it is the digits, accumulated by ONE state
+// machine (NumberParse, et_batch.hip) that both paths use -- sign seen, digits seen, the magnitude in a u64 that saturates, symbols
+// seen, bad.  A row's output is a word, so there is no scan and no copy.
+//   (fill)          the aggregates' first values: hipMemsetAsync for sum and n (0), k_number_fill for min and max (INT64_MAX, INT64_MIN)
+//   k_number_plan   plan_rows: judged (judge_row), and a row whose group number is neither ET_GROUP_NONE nor below n_groups fails with
+//                   PACKED_ARG; the ask is slice_ask, the reach reach_body(.., ask.end); a reach up to NUMBER_LANE_BYTES is walked by
+//                   its lane (lane_walk), the visitor parsing from ask.first on, ending the walk at `stop` or at the first symbol that
+//                   makes the row BAD; a longer one goes onto long_list and is EMPTY for now; the lane stores d_values[k], d_kind[k] and
+//                   the row's NumberRow in the workspace
+//   k_number_long   long_rows with slice_stream unchanged: its Sliced{begin, end, n} is the number's run of bits; n above
+//                   NUMBER_SYMBOLS_MAX is BAD without another look, otherwise thread 0 walks the n codewords from `begin` (lane_walk over
+//                   that run alone: nothing behind the slice's end is visited) and stores the row's three outputs
+//   k_number_fold   always launched, a row per lane over the NumberRows: the three kinds tallied into the counters' words 5 .. 7, the
+//                   aggregates that were asked for folded in -- combined in the wavefront as k_group_number combines its counts:
+//                   the lowest lane left broadcasts its group, the ballot of the lanes with that group is its share, sum, min and max
+//                   are reduced over them (the others hold the identity), the leader issues one atomic per aggregate, and after
+//                   GROUP_COMBINE_MISSES rounds that served their leader alone the rest adds singly --; the last workgroup to arrive
+//                   at the counters' word 0 sends the report {failed, first << 8 | status, empty, bad, range}, then `epoch`
+// NUMBER_LANE_BYTES is the search's threshold, kept, as the slice and the field keep it: the lane's walk is the slice's with four more
+// registers, the workgroup's IS the slice's; no sweep of its own has been run.
+// Every loop is bounded as the frame states; the parse lane of k_number_long takes at most NUMBER_SYMBOLS_MAX trips.
+#ifndef ET_NUMBER_LANE_BYTES  // (a build for the sweep sets it, as ET_SEARCH_LANE_BYTES)
+#define ET_NUMBER_LANE_BYTES ET_SEARCH_LANE_BYTES
+#endif
+constexpr uint32_t NUMBER_LANE_BYTES = ET_NUMBER_LANE_BYTES;
+constexpr uint32_t NUMBER_SYMBOLS_MAX = 32;  // 19 digits and a sign are what int64 needs; the rest is room for leading zeros
+// A row's kind: et_number_packed_device's four (et_batch.cpp asserts the values), and in the workspace one more: the row failed.
+enum NumberKind : uint32_t { NUMBER_OK = 0, NUMBER_EMPTY = 1, NUMBER_BAD = 2, NUMBER_RANGE = 3, NUMBER_FAILED = 4 };
+// The counters' words beside PACKED_N_FAILED, PACKED_FIRST and SLICE_N_LONG: workgroups of k_number_fold that have arrived; rows of
+// each kind but OK, which is the remainder.  The report's words are the same.
+enum NumberWord { NUMBER_ARRIVED = 0, NUMBER_N_EMPTY = 5, NUMBER_N_BAD = 6, NUMBER_N_RANGE = 7 };
+struct NumberRow {  // what the plan and the long kernel leave per row for the fold: 16 bytes, one load
+    int64_t value;  // 0 unless NUMBER_OK
+    uint32_t kind;  // NumberKind
+    uint32_t pad;
+};
+struct NumberJob {
+    SliceJob ask;               // the rows and the ask: the slice's, word for word
+    int64_t *d_values;          // null: not asked for
+    uint8_t *d_kind;            // likewise
+    const uint32_t *group_of;   // the group of ROW k; null: every row in group 0
+    uint32_t n_groups, pad;
+    int64_t *d_sum;             // the aggregates, n_groups entries each; null: not asked for
+    unsigned long long *d_n;
+    int64_t *d_min, *d_max;
+};
+// codes, long_list: as launch_slice's; rows: n_rows NumberRow of workspace (16-byte aligned).  The report leaves with the fold.
+void launch_number(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const NumberJob &job, uint8_t *d_status, NumberRow *rows,
+                   uint32_t *long_list, const PackedReport &report);
 
 }  // namespace et

@@ -57,6 +57,9 @@
 //            k_take_scan     as in the take
 //            k_recode_write  one lane per short row: the walk again, the codes under table OUT into a 64-bit accumulator, dword stores
 //            k_recode_write_long   one workgroup per listed row: settled blocks, the walk again into an LDS bit image, flushed in rounds
+//   number   k_number_plan   one lane per row: judged; a short reach walked to the slice's end, its symbols from `first` on parsed as an integer; a long one listed
+//            k_number_long   one workgroup per listed row: the slice's settled blocks, then ONE lane parses the at most 32 codewords of the run they found
+//            k_number_fold   one lane per row: the kinds counted, the aggregates folded in by adds combined in the wavefront, the report
 //
 // The kernels the host waits for end the same way: the last workgroup to finish (a device counter tells which)
 // stores the launch's epoch into a pinned word the host polls.
@@ -2062,7 +2065,7 @@ __global__ __launch_bounds__(BB) void k_take_copy(const uint8_t *__restrict__ d_
 
 // --------------------------------------------------------------------------------
 // The derived stores: the slice, the field, the concat and the recode each make a NEW packed store out of rows[] of an old one on the
-// compressed bytes, and share the frame that is stated here once.
+// compressed bytes, and share the frame that is stated here once.  The number call, behind them, reads a word per row where they make a store, in the same frame.
 //   plan_rows   a row per lane: the row is judged (judge_row), what the ask can reach of its body is taken (reach_body), and a body
 //               up to the family's threshold (lane_walks) is walked by that lane from global memory (lane_walk); a longer one goes
 //               onto long_list -- one atomic per wavefront that has any -- and is the empty record for now
@@ -3026,6 +3029,230 @@ __global__ __launch_bounds__(BB) void k_recode_write_long(PackedStore store, con
 }
 
 // --------------------------------------------------------------------------------
+// The number call: rows[]' slices s = text_b[first : first + count], cut in front of the first `stop`, READ as integers of the
+// grammar [+-]?[0-9]+ -- a word per row, and sums, counts, minima and maxima per group -- with nothing decoded and no store made.  The
+// ask, the judgement, the reach and both walks are the slice's; the family's middle is what a walk notes: not two bit positions
+// but the digits themselves, accumulated by NumberParse, which the lane's walk and the workgroup's parse lane both use.  Three
+// launches in stream order behind the fill of the aggregates (et_batch.h), the host waiting for the last: the fold.
+// --------------------------------------------------------------------------------
+// THE state machine: take(sym) per symbol of s, in order; false: the row is BAD and nothing behind changes that.  The magnitude
+// SATURATES at 2^64 - 1 (`over`), so a run of digits of any length is judged right: never wrapped into range.
+struct NumberParse {
+    enum : uint32_t { NEG = 1, DIGITS = 2, OVER = 4, BAD = 8 };
+    uint64_t mag = 0;
+    uint32_t n = 0, flags = 0;  // symbols seen; what they were (one word of bits: the state is a lane's own, in registers)
+
+    __device__ __forceinline__ bool take(uint32_t sym) {
+        constexpr uint64_t TENTH = ~0ull / 10;  // (2^64 - 1 = 10 * TENTH + 5)
+        const uint32_t d = sym - '0';
+        const bool digit = d <= 9u, sign = n == 0 && (sym == '+' || sym == '-');
+        uint32_t f = flags;
+        f |= ++n > NUMBER_SYMBOLS_MAX || !(digit || sign) ? BAD : 0u;
+        f |= digit ? DIGITS : 0u;
+        f |= sign && sym == '-' ? NEG : 0u;
+        if (digit) {
+            const bool over = (f & OVER) || mag > TENTH || (mag == TENTH && d > 5u);
+            mag = over ? ~0ull : mag * 10 + d;
+            f |= over ? OVER : 0u;
+        }
+        flags = f;
+        return !(f & BAD);
+    }
+
+    __device__ __forceinline__ NumberRow row() const {
+        const uint64_t most = flags & NEG ? 1ull << 63 : (1ull << 63) - 1;
+        const uint32_t kind = !n ? NUMBER_EMPTY : (flags & BAD) || !(flags & DIGITS) ? NUMBER_BAD : (flags & OVER) || mag > most ? NUMBER_RANGE : NUMBER_OK;
+        return NumberRow{kind ? 0 : static_cast<int64_t>(flags & NEG ? 0 - mag : mag), kind, 0u};  // (-2^63 is 0 - 2^63 in 64 bits)
+    }
+};
+
+// A row's outputs: the two the caller may have asked for, and the NumberRow the fold reads.  A failed row is EMPTY with value 0 to
+// the caller and NUMBER_FAILED to the fold, which counts it nowhere.
+__device__ __forceinline__ void store_number(const NumberJob &job, NumberRow *__restrict__ rows, uint32_t k, const NumberRow &r) {
+    reinterpret_cast<uint4 *>(rows)[k] = make_uint4(static_cast<uint32_t>(r.value), static_cast<uint32_t>(static_cast<uint64_t>(r.value) >> 32), r.kind, 0u);  // (NumberRow as it lies in memory)
+    if (job.d_values) job.d_values[k] = r.value;
+    if (job.d_kind) job.d_kind[k] = static_cast<uint8_t>(r.kind == NUMBER_FAILED ? NUMBER_EMPTY : r.kind);
+}
+
+// k_number_fill: min and max have first values that no byte pattern gives.  A group per lane; either may be null.
+__global__ __launch_bounds__(BB) void k_number_fill(int64_t *__restrict__ d_min, int64_t *__restrict__ d_max, uint32_t n_groups) {
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * BB + threadIdx.x; g < n_groups; g += static_cast<uint64_t>(gridDim.x) * BB) {
+        if (d_min) d_min[g] = INT64_MAX;
+        if (d_max) d_max[g] = INT64_MIN;
+    }
+}
+
+// k_number_plan: plan_rows, k_slice_plan's tables and ask.  A row whose group number names no group fails here, alone, like a row
+// whose record does.  A row that asks for nothing, or of a record without bytes or symbols, is EMPTY and is not read.  The lane's
+// visitor steps over the symbols in front of ask.first, ends the walk at `stop`, and hands every other symbol to the state machine,
+// which ends it at the first that makes the row BAD -- the 33rd at the latest.  LDS 6 KiB + 8 words.
+__global__ __launch_bounds__(BB) void k_number_plan(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, NumberJob job, NumberRow *__restrict__ rows,
+                                                    uint32_t *__restrict__ long_list, uint8_t *__restrict__ d_status, unsigned long long *__restrict__ stats) {
+    __shared__ CodeTables t;
+    load_tables(t, codes, n_codes);
+    __syncthreads();
+    plan_rows(job.ask.n_rows, long_list, d_status, stats, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.ask.rows, k);
+        RowPlan p{rec.status, false};
+        if (!p.status && job.group_of) {
+            const uint32_t group = job.group_of[k];
+            if (group != GROUP_NONE && group >= job.n_groups) p.status = PACKED_ARG;
+        }
+        NumberRow r{0, p.status ? NUMBER_FAILED : NUMBER_EMPTY, 0u};
+        if (!p.status && stored_text(rec)) {
+            const SliceAsk ask = slice_ask(job.ask, k, static_cast<uint32_t>(rec.len));
+            if (ask.end > ask.first) {
+                const BodyBits g = reach_body(store, rec, ask.end);
+                if (lane_walks(g, NUMBER_LANE_BYTES)) {
+                    NumberParse parse;
+                    (void)lane_walk(t, n_codes, g, ask.end, [&](uint32_t idx, uint32_t, uint32_t meta) {
+                        if (idx < ask.first) return true;
+                        return (meta & 0xffu) != job.ask.stop && parse.take(meta & 0xffu);
+                    });
+                    r = parse.row();
+                } else {
+                    p.is_long = true;
+                }
+            }
+        }
+        store_number(job, rows, k, r);
+        return p;
+    });
+}
+
+// The run of bits [begin, end) of a body as a body of its own: counted from the aligned word `begin` lies in, as lane_walk takes it.
+__device__ __forceinline__ BodyBits bits_between(const BodyBits &g, uint32_t begin, uint32_t end) {
+    BodyBits h;
+    h.words = g.words + (begin >> 5);
+    h.first_bit = begin & 31;
+    h.end_bit = end - (begin & ~31u);
+    h.n_words = (h.end_bit + 31) >> 5;  // (end <= g.end_bit: no word behind the body's last)
+    return h;
+}
+
+// k_number_long: long_rows with slice_stream, unchanged: what it returns is the number's run of bits and its symbols.  More than
+// NUMBER_SYMBOLS_MAX symbols are BAD without another look; otherwise thread 0 alone walks the run -- at most 32 trips, nothing behind
+// the slice's end visited, no stop among its symbols -- with the lane's state machine, and stores the row's outputs.  The plan kernel
+// lists OK rows only: nothing fails here.  LDS as k_slice_long.
+__global__ __launch_bounds__(BB) void k_number_long(PackedStore store, const uint2 *__restrict__ codes, uint32_t n_codes, NumberJob job, NumberRow *__restrict__ rows,
+                                                    const uint32_t *__restrict__ long_list, const unsigned long long *__restrict__ stats) {
+    __shared__ BatchDecLds s;
+    __shared__ unsigned long long s_red[3 * (BB / 64)];
+    long_rows(job.ask.n_rows, long_list, stats, [&] { return load_tables(s.t, codes, n_codes), true; }, [&](uint32_t k) {
+        const Judged rec = judge_row(store, job.ask.rows, k);
+        if (!stored_text(rec)) return;
+        const SliceAsk ask = slice_ask(job.ask, k, static_cast<uint32_t>(rec.len));
+        if (ask.end <= ask.first) return;
+        const BodyBits g = reach_body(store, rec, ask.end);
+        const Sliced sl = slice_stream(s, n_codes, g, ask, job.ask.stop, s_red);
+        if (threadIdx.x != 0 || !sl.n) return;  // (no symbols: the plan kernel's EMPTY stands)
+        NumberRow r{0, NUMBER_BAD, 0u};
+        if (sl.n <= NUMBER_SYMBOLS_MAX && sl.end > sl.begin && sl.end <= g.end_bit) {
+            NumberParse parse;
+            (void)lane_walk(s.t, n_codes, bits_between(g, sl.begin, sl.end), sl.n, [&](uint32_t, uint32_t, uint32_t meta) { return parse.take(meta & 0xffu); });
+            r = parse.row();
+        }
+        store_number(job, rows, k, r);
+    });
+}
+
+// Sum, minimum and maximum of the lanes of a wavefront; a lane outside holds the identity.  Every lane has the three on return.
+__device__ __forceinline__ void reduce_sum_min_max(uint64_t &sum, int64_t &lo, int64_t &hi) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        sum += __shfl_xor(sum, d, 64);
+        const int64_t ol = __shfl_xor(lo, d, 64), oh = __shfl_xor(hi, d, 64);
+        if (ol < lo) lo = ol;
+        if (oh > hi) hi = oh;
+    }
+}
+
+// One atomic per aggregate that was asked for.  The sum wraps modulo 2^64: an unsigned add.
+__device__ __forceinline__ void fold_into(const NumberJob &job, uint32_t group, uint64_t sum, unsigned long long n, int64_t lo, int64_t hi) {
+    if (job.d_sum) atomicAdd(reinterpret_cast<unsigned long long *>(job.d_sum) + group, static_cast<unsigned long long>(sum));
+    if (job.d_n) atomicAdd(job.d_n + group, n);
+    if (job.d_min) atomicMin(reinterpret_cast<long long *>(job.d_min) + group, static_cast<long long>(lo));
+    if (job.d_max) atomicMax(reinterpret_cast<long long *>(job.d_max) + group, static_cast<long long>(hi));
+}
+
+// k_number_fold: a row per lane over the NumberRows that the two kernels in front left, whatever the caller asked to see.  The
+// kinds but OK are counted per lane, reduced over the wavefront and the workgroup (4 x 3 words of LDS) and added to the counters by
+// thread 0.  AGG: every OK row whose group is one (a row of ET_GROUP_NONE is skipped; a number beyond n_groups failed its row in the
+// plan kernel, and is asked again for what is written below) is folded into its group's aggregates, the adds combined in the
+// wavefront first, by k_group_number's rounds: the lowest lane left takes its group, the ballot of the lanes with that group is its
+// share, the three values are reduced over the share -- a round that found its leader alone skips that --, the leader issues the
+// atomics; after GROUP_COMBINE_MISSES rounds without company the rest adds singly.  A whole-column SUM sends one add per wavefront to
+// its one address, not 64.  Integer adds, min and max commute: every aggregate is exact and the same on every call.
+// The report: thread 0's counts are in `stats` before its tick of NUMBER_ARRIVED (packed_report's fences); the last workgroup to tick
+// reads the counters back, stores them and hands over.  No workgroup waits for another.
+template <bool AGG>
+__global__ __launch_bounds__(BB) void k_number_fold(const NumberRow *__restrict__ rows, NumberJob job, PackedReport report) {
+    __shared__ unsigned long long s_kinds[3][BB / 64];
+    const uint32_t n_rows = job.ask.n_rows, lane = threadIdx.x & 63;
+    unsigned long long kinds[3] = {0, 0, 0};
+    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * BB; base < n_rows; base += static_cast<uint64_t>(gridDim.x) * BB) {
+        const uint32_t k = static_cast<uint32_t>(base) + threadIdx.x;
+        uint32_t group = GROUP_NONE;
+        int64_t value = 0;
+        if (k < n_rows) {
+            const uint4 r = reinterpret_cast<const uint4 *>(rows)[k];  // (NumberRow as it lies in memory)
+            kinds[0] += r.z == NUMBER_EMPTY;
+            kinds[1] += r.z == NUMBER_BAD;
+            kinds[2] += r.z == NUMBER_RANGE;
+            if (AGG && r.z == NUMBER_OK) {
+                group = job.group_of ? job.group_of[k] : 0u;
+                if (group >= job.n_groups) group = GROUP_NONE;
+                value = static_cast<int64_t>(static_cast<uint64_t>(r.y) << 32 | r.x);
+            }
+        }
+        if (AGG) {
+            unsigned long long left = __ballot(group != GROUP_NONE);
+            for (uint32_t alone = 0; left && alone < GROUP_COMBINE_MISSES;) {
+                const int leader = __ffsll(left) - 1;
+                const uint32_t lead_group = __shfl(group, leader, 64);
+                const bool in = group == lead_group;  // (lead_group is a group: no lane without one is in it; a lane served before has another)
+                const unsigned long long same = __ballot(in);
+                const bool single = (same & (same - 1)) == 0;
+                uint64_t sum = in ? static_cast<uint64_t>(value) : 0ull;
+                int64_t lo = in ? value : INT64_MAX, hi = in ? value : INT64_MIN;
+                if (!single) reduce_sum_min_max(sum, lo, hi);  // (the same for the whole wavefront)
+                if (static_cast<int>(lane) == leader) fold_into(job, lead_group, sum, static_cast<unsigned long long>(__popcll(same)), lo, hi);
+                left &= ~same;
+                alone += single;
+            }
+            if ((left >> lane) & 1) fold_into(job, group, static_cast<uint64_t>(value), 1ull, value, value);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) kinds[i] += __shfl_xor(kinds[i], d, 64);
+        if (lane == 0) s_kinds[i][threadIdx.x >> 6] = kinds[i];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    unsigned long long *stats = report.stats, *host_result = report.host_result;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        unsigned long long total = 0;
+        for (int w = 0; w < BB / 64; ++w) total += s_kinds[i][w];
+        if (total) atomicAdd(stats + NUMBER_N_EMPTY + i, total);
+    }
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the counts have landed before the tick leaves
+    const unsigned long long before = atomicAdd(stats + NUMBER_ARRIVED, 1ull);
+    if (before != gridDim.x - 1) return;
+    __threadfence();
+    host_result[NUMBER_ARRIVED] = 0;
+    host_result[PACKED_N_FAILED] = atomicAdd(stats + PACKED_N_FAILED, 0ull);
+    host_result[PACKED_FIRST] = atomicMin(stats + PACKED_FIRST, ~0ull);
+    host_result[NUMBER_N_EMPTY] = atomicAdd(stats + NUMBER_N_EMPTY, 0ull);
+    host_result[NUMBER_N_BAD] = atomicAdd(stats + NUMBER_N_BAD, 0ull);
+    host_result[NUMBER_N_RANGE] = atomicAdd(stats + NUMBER_N_RANGE, 0ull);
+    hand_over(report.host_done, report.epoch);
+}
+
+// --------------------------------------------------------------------------------
 static uint32_t batch_grid(uint32_t n) { return n < MAX_GRID ? n : MAX_GRID; }
 
 static uint32_t capped(uint64_t n, uint32_t most) { return n < most ? static_cast<uint32_t>(n) : most; }
@@ -3121,6 +3348,18 @@ void launch_recode(hipStream_t stream, const PackedStore &store, const uint2 *co
     hipLaunchKernelGGL(k_recode_write_long, dim3(groups), dim3(BB), 0, stream, store, codes, n_codes, job, static_cast<const TakeRow *>(plan),
                        static_cast<const uint32_t *>(long_list), static_cast<const unsigned long long *>(r.stats), static_cast<const uint64_t *>(out_body_index),
                        static_cast<uint8_t *>(d_out), cap);
+}
+
+void launch_number(hipStream_t stream, const PackedStore &store, const uint2 *codes, uint32_t n_codes, const NumberJob &job, uint8_t *d_status, NumberRow *rows,
+                   uint32_t *long_list, const PackedReport &r) {
+    const uint32_t n_rows = job.ask.n_rows, lanes = plan_grid(n_rows);
+    if (job.d_min || job.d_max) hipLaunchKernelGGL(k_number_fill, dim3(plan_grid(job.n_groups)), dim3(BB), 0, stream, job.d_min, job.d_max, job.n_groups);
+    hipLaunchKernelGGL(k_number_plan, dim3(lanes), dim3(BB), 0, stream, store, codes, n_codes, job, rows, long_list, d_status, r.stats);
+    hipLaunchKernelGGL(k_number_long, dim3(long_grid(n_rows)), dim3(BB), 0, stream, store, codes, n_codes, job, rows, static_cast<const uint32_t *>(long_list),
+                       static_cast<const unsigned long long *>(r.stats));
+    const NumberRow *left = rows;
+    if (job.d_sum || job.d_n || job.d_min || job.d_max) hipLaunchKernelGGL(k_number_fold<true>, dim3(lanes), dim3(BB), 0, stream, left, job, r);
+    else hipLaunchKernelGGL(k_number_fold<false>, dim3(lanes), dim3(BB), 0, stream, left, job, r);
 }
 
 void launch_join(hipStream_t stream, const PackedStore &records, const PackedStore &keys, uint32_t flags, unsigned long long *table, uint64_t slots, uint32_t *d_rows,

@@ -588,12 +588,14 @@ int et_selftest_join_hash(et_ctx *ctx, const void *d_bodies, size_t body_bytes, 
  * One upload (64 bytes of counters), a clear of the table (et_join_table_slots(n_records) slots), three launches and one hand-over
  * for a count-only call, behind the scan; up to two more launches behind the hand-over for a writing one.  Stream-ordered like the
  * other packed calls -- *res is final on return, the device arrays once the ctx's stream has drained -- and it may follow or precede
- * any other packed, gather, match, search, join, take, slice, field, concat, recode, shared-table or single-stream call on one ctx
+ * any other packed, gather, match, search, join, take, slice, field, concat, recode, number, shared-table or single-stream call on one ctx
  * with nothing in between: the store may come straight from et_field_packed_device, d_first_rows may go straight into
- * et_take_packed_device.  It keeps the state a ctx holds between calls (the histogram link, the held range) as it is.
+ * et_take_packed_device, d_group_of straight into et_number_packed_device.  It keeps the state a ctx holds between calls (the histogram
+ * link, the held range) as it is.
  * Out of scope: groups in SORTED order (ORDER BY: groups come in order of first appearance); grouping a selection given by d_rows
  * (take first); grouping over several columns in one call (concat first); more than et_group_records_max() records per call; sums
- * or other aggregates over a value column (d_group_of is on the device for that); case-insensitive grouping (recode first). */
+ * or other aggregates over a value column (et_number_packed_device takes d_group_of for that); case-insensitive grouping (recode
+ * first). */
 #define ET_GROUP_NONE 0xffffffffu
 typedef struct et_group_result {
     uint64_t n_groups;                      /* groups found -- also when the call returns ET_ERR_CAP or d_first_rows is NULL */
@@ -672,7 +674,8 @@ int et_take_packed_device(et_ctx *ctx,
  *     kernel reads where a bad pair points.  d_rows == NULL: row k is record k, and n_rows must equal n_records.
  *   d_first[k], d_count[k] (32 bits each, 4-byte aligned, on the device; either may be NULL: then the scalar `first` or `count` holds
  *     for every row; with the pointer the scalar is ignored): where row k's slice begins and how many symbols it has at most.
- *     ET_SLICE_TO_END as a count: to the end.  d_first may be the search call's d_pos, or that plus the needle's length.
+ *     ET_SLICE_TO_END as a count: to the end.  d_first may be the search call's d_pos, or that plus the needle's length.  (et_number_packed_device
+ *     takes the same ask and reads the slice as an integer instead of storing it.)
  *   text_b is the stored text of record r = d_rows[k] as every packed call defines it: the first min(length_r, codewords that end
  *     inside its body) symbols.  Row k of the result is s = text_b[first : first + count], clamped as Python clamps a slice
  *     (first >= len(text_b): the empty record; first + count does not wrap).  0 <= stop <= 255: s is cut in front of the first
@@ -730,7 +733,7 @@ int et_slice_packed_device(et_ctx *ctx, const et_codebook *cb,
  *     text -- also that of a body of no bytes under a length above zero -- has one empty field 0 at position 0.  A delim without a
  *     code occurs in no record: every record is one field.
  *   d_pos (n_rows entries of 32 bits, 4-byte aligned, on the device; may be NULL): as above; ET_FIELD_ABSENT for a failed row too.
- *     It may be the slice call's d_first.
+ *     It may be the slice call's d_first, or the number call's.
  *   d_out, both output arrays (n_rows + 1 entries, the first 0), the bytes -- exactly what et_encode_packed_device writes for the
  *     result, pad bits zero whatever the source's are --, d_out == NULL (sizes only; d_pos is written) and ET_ERR_CAP (no byte of d_out
  *     written; both arrays, d_status and d_pos complete, res->out_bytes the room needed) are the slice call's.
@@ -875,6 +878,77 @@ int et_recode_packed_device(et_ctx *ctx, const et_codebook *cb_in, const et_code
                             const uint32_t *d_rows, size_t n_rows,
                             void *d_out, size_t cap, uint64_t *d_out_body_index, uint64_t *d_out_text_index,
                             uint8_t *d_status, et_take_result *res);
+
+/* NUMBER: a part of each selected record READ AS AN INTEGER, on the device, nothing decoded -- CAST(SPLIT_PART(line, ',', 3) AS
+ * BIGINT), "the number behind user= up to the next ;" -- and SUM, COUNT, MIN and MAX of those values per group: SELECT key,
+ * SUM(amount) ... GROUP BY key runs as field -> group -> number on one ctx with nothing in between, and what consumes the field
+ * call's and the search call's d_pos as a number.  The slice's walk finds the value; what it notes is not two bit positions but the
+ * digits themselves, and the output is one word per row, not a new store.
+ *   The store, d_rows (NULL: row k is record k, and n_rows must equal n_records), d_first / first, d_count / count, stop, d_status
+ *     (one et_status byte per ROW; may be NULL) and the judgement of a row are the slice call's, word for word.  Row k's text is
+ *     s = text_b[first : first + count], clamped as Python clamps a slice, first + count not wrapping, cut in front of the first
+ *     `stop` byte in it; text_b is the stored text of record r = d_rows[k] as every packed call defines it: a codeword at or behind
+ *     the record's length is no symbol, what the pad bits read as is no symbol, and a body of no bytes under a length above zero (a
+ *     record kept raw elsewhere) has the empty stored text.
+ *   The grammar is [+-]?[0-9]+ over the WHOLE of s, ASCII, nothing else.  d_kind[k] (one byte per row; may be NULL):
+ *     ET_NUMBER_OK     s is of the grammar and lies in [-2^63, 2^63 - 1]
+ *     ET_NUMBER_EMPTY  s is empty: SQL's NULL -- and the kind of a failed row
+ *     ET_NUMBER_BAD    s is not of the grammar, or has more than et_number_symbols_max() = 32 symbols: 19 digits and a sign are what
+ *                      int64 needs, the rest is room for leading zeros
+ *     ET_NUMBER_RANGE  s is of the grammar, within 32 symbols, and lies outside [-2^63, 2^63 - 1]; the magnitude saturates and never
+ *                      wraps: "1" followed by 31 zeros is RANGE, "-9223372036854775808" is OK
+ *     d_values[k] (int64, 8-byte aligned, n_rows entries; may be NULL) = the value for ET_NUMBER_OK, 0 otherwise.
+ *   The aggregates are asked for by passing any of d_sum (int64), d_n (uint64), d_min, d_max (int64): n_groups entries each, 8-byte
+ *     aligned, on the device, each may be NULL.  d_group_of[k] (32 bits, 4-byte aligned, n_rows entries) is the group of ROW k -- with
+ *     d_rows == NULL the group call's d_group_of as it is; NULL: every row is in group 0, and n_groups must be 1.  ET_GROUP_NONE
+ *     skips the row; any other value >= n_groups fails the row alone with ET_ERR_ARG.  The call initialises the entries itself -- sum
+ *     0, n 0, min INT64_MAX, max INT64_MIN: what a group without an OK row keeps -- and folds in every ET_NUMBER_OK row.  d_sum wraps
+ *     modulo 2^64.  Integer adds, min and max commute: every output is exact and the same on every call.
+ *   A failed row is ET_NUMBER_EMPTY with value 0, is folded nowhere and is counted in res->n_failed ONLY; it fails alone, and no
+ *     kernel reads where a bad pair points.  res->n_ok + n_empty + n_bad + n_range + n_failed == n_rows.
+ *   Every output pointer NULL: the call only counts -- d_status and *res are the writing call's.
+ *   There is no ET_ERR_CAP: every output has a size the caller knows.  Nothing outside the n_rows entries of d_values, d_kind and
+ *     d_status and the n_groups entries of the aggregates is written.
+ *   et_number_lane_bytes(): a reach (min(body bytes, 4 * slice end + 8)) up to this many bytes is walked by one lane, a longer one by
+ *     a workgroup -- the slice's threshold, kept -- for tests that want rows on both sides; the answer does not depend on it.
+ * Out of scope: whitespace, hex, floats, exponents and thousands separators; several numbers per row; values wider than 64 bits; AVG
+ * (it is sum / n); per-row stop bytes.
+ * The call's own status: ET_ERR_ARG (the slice call's argument errors, in its order: a null ctx, cb, res, d_bodies, d_body_index or
+ * d_text_index; an offset array that is not 8-byte aligned; d_rows, d_first or d_count not 4-byte aligned; n_records or n_rows above
+ * 0x7fffffff; d_rows == NULL with n_rows != n_records; a stop outside [-1, 255]; then d_values or an aggregate array not 8-byte
+ * aligned; d_group_of not 4-byte aligned; d_group_of without an aggregate output; an aggregate output with n_groups == 0; n_groups
+ * above 0x7fffffff; an aggregate output without d_group_of and n_groups != 1 -- all checked before anything touches a device, *res
+ * untouched), ET_ERR_UNSUPPORTED (the table is not complete: nothing is enqueued), ET_ERR_HIP, ET_ERR_NOMEM.  n_rows == 0: ET_OK,
+ * nothing enqueued, *res zeroed -- and the aggregates are NOT initialised either.  One upload (the slice's: the sorted codes and
+ * zeroed counters, 2.1 KiB), the fill of the aggregates that were asked for, three launches -- plan, long rows, fold -- and one
+ * hand-over per call, behind the fold; stream-ordered like the other packed calls -- *res is final on return, the device arrays once
+ * the ctx's stream has drained -- and it may follow or precede any of them on one ctx with nothing in between: d_first may come
+ * straight from et_field_packed_device or et_search_packed_device, d_group_of from et_group_packed_device.  It keeps the state a ctx
+ * holds between calls (the histogram link, the held range) as it is. */
+#define ET_NUMBER_OK 0
+#define ET_NUMBER_EMPTY 1
+#define ET_NUMBER_BAD 2
+#define ET_NUMBER_RANGE 3
+typedef struct et_number_result {
+    uint64_t n_ok, n_empty, n_bad, n_range; /* rows of each kind; a failed row is in none of them */
+    uint64_t n_failed, first_failed;        /* rows whose status is not ET_OK, the lowest of them (valid when n_failed > 0) */
+    int32_t first_status;                   /* et_status of row first_failed */
+    uint32_t pad;
+} et_number_result;
+size_t et_number_result_size(void);
+size_t et_number_symbols_max(void);         /* most symbols of a number: 32 */
+size_t et_number_lane_bytes(void);          /* a reach (min(body bytes, 4 * slice end + 8)) up to this is walked by one lane */
+int et_number_packed_device(et_ctx *ctx, const et_codebook *cb,
+                            const void *d_bodies, size_t body_bytes, const uint64_t *d_body_index,
+                            const uint64_t *d_text_index, size_t n_records,
+                            const uint32_t *d_rows, size_t n_rows,
+                            const uint32_t *d_first, uint32_t first,
+                            const uint32_t *d_count, uint32_t count,
+                            int stop,
+                            int64_t *d_values, uint8_t *d_kind,
+                            const uint32_t *d_group_of, size_t n_groups,
+                            int64_t *d_sum, uint64_t *d_n, int64_t *d_min, int64_t *d_max,
+                            uint8_t *d_status, et_number_result *res);
 
 /* ---- staged entry points (sharded multi-GPU encode, tests) ------------------------ */
 /* encode.zig:43-47 on the GPU: 256 x u64 counts of d_text[0..n) into d_hist (device).

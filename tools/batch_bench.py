@@ -73,7 +73,12 @@ process of its own so that every leg loads exactly one build of the library:
                   different, and 1 024 values with one on 90 % of the records; 4 096 x 4 KiB pages from a pool of 512) with all three
                   outputs and count only, against what it replaces, in the same process: et_decode_packed_device, the texts padded into
                   a matrix with their lengths, torch.unique(dim=0) with inverse and counts; the two partitions and counts compared first
---legs picks the legs (default: all but the sweeps, concat, recode and group).
+  number          (only when named) et_number_packed_device (field 3 of 262 144 CSV lines read as integers: every line, 10 % of them, the
+                  whole column's SUM / COUNT / MIN / MAX, SUM per key for pools of 16 and 65 536 keys; 4 096 x 4 KiB pages with a number
+                  behind a 12-byte needle) against what it replaces, in the same process: the field call (or search and slice) of the
+                  column as a store, et_decode_packed_device, a torch parse of the padded matrix, scatter_add_; values and aggregates
+                  checked against Python's first; the slice call on the same ask and the field call as floors
+--legs picks the legs (default: all but the sweeps, concat, recode, group and number).
 Timing: HIP events on the stream round the whole sequence of calls (all encodes; all decodes), WARMUP untimed repetitions, then
 REPS timed ones; the median is the figure, min and max the run-to-run spread.  Every leg checks its decoded bytes against the
 text once before timing.  One JSON line on stdout (and into --out).
@@ -92,6 +97,7 @@ text once before timing.  One JSON line on stdout (and into --out).
     python tools/batch_bench.py --legs concat --out profiles/concat_bench.json
     python tools/batch_bench.py --legs recode --out profiles/recode_bench.json
     python tools/batch_bench.py --legs group --out profiles/group_bench.json
+    python tools/batch_bench.py --legs number --out profiles/number_bench.json
 """
 import argparse
 import ctypes
@@ -100,6 +106,7 @@ import os
 import statistics
 import subprocess
 import sys
+from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -1390,6 +1397,248 @@ def _group_leg(lib_path, shapes):
     print(json.dumps(results))
 
 
+NUMBER_POOLS = (16, 65536)          # the number leg's key pools: field 0 of its CSV lines
+NUMBER_NEEDLE = b"page-amount="     # ... and what stands in front of the number in its pages: 12 bytes
+NUMBER_WIDTH = 20                   # columns of the baseline's padded matrix: a sign and 19 digits
+
+
+def _number_lines(count, pool):
+    """-> (text, text_index, keys, amounts): `count` CSV lines of 8 fields -- field 0 a key out of `pool`, field 3 an integer of either
+    sign with 1 .. 12 digits, the others 4 .. 16 text-like bytes (a comma or a line end in the source text becomes a space)."""
+    import numpy as np
+
+    from tests import corpus
+
+    rng = np.random.default_rng(0x4E0B + count + pool)
+    widths = rng.integers(4, 17, size=(count, 6))
+    offs = np.concatenate(([0], np.cumsum(widths.ravel()))).astype(np.int64)
+    filler = corpus.text_like(int(offs[-1]), 0x4E0C + count).copy()
+    filler[(filler == ord(",")) | (filler == 10)] = ord(" ")
+    blob = filler.tobytes()
+    keys = rng.integers(0, pool, size=count)
+    amounts = (rng.random(count) * 10.0 ** rng.integers(1, 13, size=count)).astype(np.int64) * rng.choice([-1, 1], size=count)
+    lines = []
+    for i in range(count):
+        f = [blob[offs[6 * i + j] : offs[6 * i + j + 1]] for j in range(6)]
+        lines.append(b"k%07d,%s,%s,%d,%s,%s,%s,%s" % (keys[i], f[0], f[1], amounts[i], f[2], f[3], f[4], f[5]))
+    index = np.concatenate(([0], np.cumsum([len(x) for x in lines]))).astype(np.uint64)
+    return np.frombuffer(b"".join(lines), np.uint8).copy(), index, keys, amounts
+
+
+def _number_pages(count, size):
+    """-> (text, text_index, amounts): `count` text-like pages of `size` bytes, in each NUMBER_NEEDLE, an integer and ";" at a random place."""
+    import numpy as np
+
+    from tests import corpus
+
+    rng = np.random.default_rng(0x4E0D + count)
+    host = corpus.text_like(count * size, 0x4E0E + count).copy()
+    host[host == ord(";")] = ord(",")
+    amounts = (rng.random(count) * 10.0 ** rng.integers(1, 13, size=count)).astype(np.int64) * rng.choice([-1, 1], size=count)
+    for b in range(count):
+        piece = NUMBER_NEEDLE + b"%d;" % amounts[b]
+        at = b * size + int(rng.integers(0, size - len(piece)))
+        host[at : at + len(piece)] = np.frombuffer(piece, np.uint8)
+    assert all(host[b * size : (b + 1) * size].tobytes().count(NUMBER_NEEDLE) == 1 for b in range(0, count, 97))
+    return host, (np.arange(count + 1) * size).astype(np.uint64), amounts
+
+
+def _number_leg(lib_path, shapes):
+    """number: on 262 144 CSV lines of 8 fields (field 0 a key out of a pool of 16 or 65 536, field 3 an integer) -- (a) the values of
+    field 3 of every line through the field call's positions and stop=",", (b) of a random 10 %, (c) the whole column's SUM, COUNT, MIN
+    and MAX, (d) SUM per key with et_group_packed_device's group numbers over field 0 -- and on 4 096 x 4 KiB pages (e) the number behind
+    a 12-byte needle (search -> number).  Per case et_number_packed_device alone on positions that are already there (`ms`), the whole
+    new route (`route`: the sizes-only field call, or the search, that finds the positions, then the number call) and, in the same
+    process, the route it replaces (`baseline`): et_field_packed_device (or search and slice) of the column as a store,
+    et_decode_packed_device of it, the text padded into an [n, 20] matrix and parsed in torch, scatter_add_ / scatter_reduce_ for the
+    aggregates.  Values and aggregates are checked against Python's first.  The verdict compares `route` with `baseline`: HIT when the
+    gap exceeds both spreads, MISS when it does not or the call is slower.  Floors: the slice call on the same ask, the field call."""
+    import numpy as np
+    import torch
+
+    from entreepy_amd import _native as N
+
+    L, h, dev = _open(lib_path, STORE + ["et_decode_packed_device", "et_field_packed_device", "et_slice_packed_device", "et_search_packed_device", "et_group_packed_device",
+                                         "et_number_packed_device", "et_number_lane_bytes"])
+    results = {"lane_bytes": int(L.et_number_lane_bytes())}
+    res, tres, mres, gres, nres = N.PackedResult(), N.TakeResult(), N.MatchResult(), N.GroupResult(), N.NumberResult()
+    pow10 = torch.tensor([10**k for k in range(19)], dtype=torch.int64, device=dev)
+    cols = torch.arange(NUMBER_WIDTH, device=dev)[None, :]
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+
+    def parse(dec, text_index, n, total):
+        """The torch parse of the baseline: the column's text padded into a matrix, sign and digits to int64."""
+        lengths = text_index[1:] - text_index[:-1]
+        row = torch.repeat_interleave(torch.arange(n, device=dev), lengths, output_size=total)
+        padded = torch.zeros((n, NUMBER_WIDTH), dtype=torch.uint8, device=dev)
+        padded[row, torch.arange(total, device=dev) - text_index[:-1][row]] = dec[:total]
+        digit = padded.to(torch.int64) - 48
+        mine = (digit >= 0) & (digit <= 9) & (cols < lengths[:, None])
+        values = (torch.where(mine, digit, 0) * pow10[(lengths[:, None] - 1 - cols).clamp(0, 18)]).sum(dim=1)
+        return torch.where(padded[:, 0] == 45, -values, values)
+
+    def verdict(entry):
+        new, old = entry["route"], entry["baseline"]
+        gap, spreads = old["ms"] - new["ms"], (old["max_ms"] - old["min_ms"]) + (new["max_ms"] - new["min_ms"])
+        entry["baseline_over_route"], entry["beyond_both_spreads"] = round(old["ms"] / new["ms"], 2), bool(gap > spreads)
+        entry["verdict"] = "HIT" if gap > spreads else "MISS"
+        return entry
+
+    def store_of(host, index):
+        n = index.size - 1
+        cb, bodies, body_bytes, body_index, text_index = _packed_store(L, h, torch.from_numpy(host).to(dev), index, _codebook(L, [host]))
+        return SimpleNamespace(cb=cb, bodies=bodies, body_bytes=body_bytes, body_index=body_index, text_index=text_index, n=n,
+                               args=lambda: (h, ctypes.byref(cb), bodies.data_ptr(), body_bytes, body_index.data_ptr(), text_index.data_ptr(), n))
+
+    def decode(st_args, n, total, dec):
+        assert L.et_decode_packed_device(*st_args, dec.data_ptr(), total, None, None, ctypes.byref(res)) == 0 and res.n_failed == 0 and res.n_short == 0, L.et_last_error(h)
+
+    def number(st, rows, n_rows, d_first, stop, values=None, group_of=None, n_groups=0, agg=None):
+        agg = agg or {}
+        assert L.et_number_packed_device(*st.args(), ptr(rows), n_rows, d_first.data_ptr(), 0, None, 0xFFFFFFFF, stop, ptr(values), None, ptr(group_of), n_groups, ptr(agg.get("sum")),
+                                         ptr(agg.get("n")), ptr(agg.get("min")), ptr(agg.get("max")), None, ctypes.byref(nres)) == 0, L.et_last_error(h)
+        assert nres.n_ok == n_rows and nres.n_failed == 0
+
+    count, _ = CSV_SHAPE
+    for pool in NUMBER_POOLS:
+        name = f"{count}xcsv_pool_{pool}"
+        if shapes and name not in shapes:
+            continue
+        host, index, keys, amounts = _number_lines(count, pool)
+        st = store_of(host, index)
+        shape = {"records": count, "body_bytes": st.body_bytes}
+        tenth = np.sort(np.random.default_rng(0x4E0F + count).choice(count, size=count // 10, replace=False)).astype(np.uint32)
+        d_tenth = torch.from_numpy(tenth.view(np.int32).copy()).to(dev)
+        out = torch.zeros(st.body_bytes + 64, dtype=torch.uint8, device=dev)
+        obi, oti = (torch.zeros(count + 1, dtype=torch.int64, device=dev) for _ in range(2))
+        d_pos, values = torch.zeros(count, dtype=torch.int32, device=dev), torch.zeros(count, dtype=torch.int64, device=dev)
+        dec = torch.zeros(count * NUMBER_WIDTH + 64, dtype=torch.uint8, device=dev)
+
+        def field(k, rows, n_rows, write):
+            assert L.et_field_packed_device(*st.args(), ptr(rows), n_rows, None, k, None, 1, ord(","), out.data_ptr() if write else None, st.body_bytes, obi.data_ptr(), oti.data_ptr(),
+                                            d_pos.data_ptr(), None, ctypes.byref(tres)) == 0 and tres.n_failed == 0, L.et_last_error(h)
+
+        # the group numbers of (d), untimed: both routes are given them
+        field(0, None, count, True)
+        g_first, g_of = (torch.zeros(count, dtype=torch.int32, device=dev) for _ in range(2))
+        assert L.et_group_packed_device(h, ctypes.byref(st.cb), out.data_ptr(), int(tres.out_bytes), obi.data_ptr(), oti.data_ptr(), count, g_first.data_ptr(), count, None, g_of.data_ptr(),
+                                        None, ctypes.byref(gres)) == 0 and gres.n_failed == 0, L.et_last_error(h)
+        torch.cuda.synchronize()
+        n_groups = int(gres.n_groups)
+        assert n_groups == len(set(keys.tolist()))
+        g_of64 = g_of.to(torch.int64)
+        first_rows = g_first[:n_groups].cpu().numpy()
+        want_sums = np.zeros(pool, np.int64)
+        np.add.at(want_sums, keys, amounts)
+        found = {}
+
+        def case(rows, n_rows, want_values, groups):
+            """groups: None (values alone), 1 (the whole column), or n_groups (per key)."""
+            entry = {"rows": int(n_rows)}
+            agg = None
+            if groups:
+                agg = {k: torch.zeros(groups, dtype=torch.int64, device=dev) for k in (("sum", "n", "min", "max") if groups == 1 else ("sum",))}
+            of = g_of if groups and groups > 1 else None
+
+            def call():
+                number(st, rows, n_rows, d_pos, ord(","), None if groups else values, of, groups or 0, agg)
+
+            def route():
+                field(3, rows, n_rows, False)
+                call()
+
+            def baseline():
+                field(3, rows, n_rows, True)
+                total = int(tres.text_bytes)
+                decode((h, ctypes.byref(st.cb), out.data_ptr(), int(tres.out_bytes), obi.data_ptr(), oti.data_ptr(), n_rows), n_rows, total, dec)
+                v = parse(dec, oti[: n_rows + 1], n_rows, total)
+                found["values"] = v
+                if groups == 1:
+                    found["agg"] = (v.sum(), v.min(), v.max())
+                elif groups:
+                    found["agg"] = (torch.zeros(groups, dtype=torch.int64, device=dev).scatter_add_(0, g_of64, v),)
+
+            route()
+            baseline()
+            torch.cuda.synchronize()
+            assert found["values"].cpu().numpy().tolist() == want_values.tolist(), "the baseline's values differ from Python's"
+            if not groups:
+                assert values[:n_rows].cpu().numpy().tolist() == want_values.tolist(), "the values differ from Python's"
+            elif groups == 1:
+                got = [int(agg[k][0]) for k in ("sum", "n", "min", "max")]
+                assert got == [int(want_values.sum()), n_rows, int(want_values.min()), int(want_values.max())] and [int(x) for x in found["agg"]] == [got[0], got[2], got[3]]
+            else:
+                assert torch.equal(agg["sum"], found["agg"][0]) and agg["sum"].cpu().numpy().tolist() == want_sums[keys[first_rows]].tolist(), "the sums per key differ from Python's"
+            entry.update(_timed(call))
+            entry["route"], entry["baseline"] = _timed(route), _timed(baseline)
+            field(3, rows, n_rows, False)  # (the floors' positions)
+
+            def slice_floor():
+                assert L.et_slice_packed_device(*st.args(), ptr(rows), n_rows, d_pos.data_ptr(), 0, None, 0xFFFFFFFF, ord(","), out.data_ptr(), st.body_bytes, obi.data_ptr(),
+                                                oti.data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+
+            entry["slice_floor"], entry["field_floor"] = _timed(slice_floor), _timed(lambda: field(3, rows, n_rows, False))
+            found.clear()
+            return verdict(entry)
+
+        shape["a_values_all"] = case(None, count, amounts, None)
+        shape["b_values_tenth"] = case(d_tenth, tenth.size, amounts[tenth.astype(np.int64)], None)
+        shape["c_column_sum_n_min_max"] = case(None, count, amounts, 1)
+        shape["d_sum_per_key"] = dict(case(None, count, amounts, n_groups), groups=n_groups)
+        results[name] = shape
+        del st, out, dec
+
+    count, size = SHAPES[1]
+    name = f"{count}x{size}"
+    if not shapes or name in shapes:
+        host, index, amounts = _number_pages(count, size)
+        st = store_of(host, index)
+        d_rows, d_pos = (torch.zeros(count, dtype=torch.int32, device=dev) for _ in range(2))
+        values = torch.zeros(count, dtype=torch.int64, device=dev)
+        out = torch.zeros(st.body_bytes + 64, dtype=torch.uint8, device=dev)
+        obi, oti = (torch.zeros(count + 1, dtype=torch.int64, device=dev) for _ in range(2))
+        dec = torch.zeros(count * NUMBER_WIDTH + 64, dtype=torch.uint8, device=dev)
+        found = {}
+
+        def search():
+            assert L.et_search_packed_device(*st.args(), NUMBER_NEEDLE, len(NUMBER_NEEDLE), N.ET_SEARCH_CONTAINS, d_rows.data_ptr(), count, d_pos.data_ptr(), None,
+                                             ctypes.byref(mres)) == 0 and mres.n_match == count, L.et_last_error(h)
+            return d_pos + len(NUMBER_NEEDLE)
+
+        d_first = search()
+
+        def call():
+            number(st, d_rows, count, d_first, ord(";"), values)
+
+        def route():
+            number(st, d_rows, count, search(), ord(";"), values)
+
+        def baseline():
+            first = search()
+            assert L.et_slice_packed_device(*st.args(), d_rows.data_ptr(), count, first.data_ptr(), 0, None, 0xFFFFFFFF, ord(";"), out.data_ptr(), st.body_bytes, obi.data_ptr(),
+                                            oti.data_ptr(), None, ctypes.byref(tres)) == 0 and tres.n_failed == 0, L.et_last_error(h)
+            total = int(tres.text_bytes)
+            decode((h, ctypes.byref(st.cb), out.data_ptr(), int(tres.out_bytes), obi.data_ptr(), oti.data_ptr(), count), count, total, dec)
+            found["values"] = parse(dec, oti, count, total)
+
+        route()
+        baseline()
+        torch.cuda.synchronize()
+        assert values.cpu().numpy().tolist() == amounts.tolist() == found["values"].cpu().numpy().tolist(), "the values differ from Python's"
+        entry = {"rows": count, "body_bytes": st.body_bytes}
+        entry.update(_timed(call))
+        entry["route"], entry["baseline"] = _timed(route), _timed(baseline)
+
+        def slice_floor():
+            assert L.et_slice_packed_device(*st.args(), d_rows.data_ptr(), count, d_first.data_ptr(), 0, None, 0xFFFFFFFF, ord(";"), out.data_ptr(), st.body_bytes, obi.data_ptr(),
+                                            oti.data_ptr(), None, ctypes.byref(tres)) == 0, L.et_last_error(h)
+
+        entry["slice_floor"], entry["search_floor"] = _timed(slice_floor), _timed(search)
+        results[name] = {"e_number_behind_a_needle": verdict(entry)}
+    L.et_ctx_destroy(h)
+    print(json.dumps(results))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=os.environ.get("ET_PARENT_LIB_PATH"))
@@ -1420,6 +1669,8 @@ def main():
         return _recode_leg(a.lib, [s for s in a.shapes.split(",") if s], sweep=a.leg == "recode_sweep")
     if a.leg == "group":
         return _group_leg(a.lib, [s for s in a.shapes.split(",") if s])
+    if a.leg == "number":
+        return _number_leg(a.lib, [s for s in a.shapes.split(",") if s])
     if a.leg:
         return (_gather_leg if a.leg.startswith("gather") else _leg)(a.leg, a.lib)
     here = os.environ.get("ET_LIB_PATH") or os.path.join(ROOT, "entreepy_amd", "libentreepy_hip.so")
@@ -1449,6 +1700,8 @@ def main():
         legs += [("recode", "recode", here)]
     if "group" in a.legs.split(","):  # (likewise)
         legs += [("group", "group", here)]
+    if "number" in a.legs.split(","):  # (likewise)
+        legs += [("number", "number", here)]
     if "recode_sweep" in a.legs.split(","):
         legs += [("recode_sweep", "recode_sweep", here)]
     if "search_sweep" in a.legs.split(","):
@@ -1517,6 +1770,8 @@ def main():
         out["recode_condition_met"] = all(e["beyond_both_spreads"] for v in out["recode"].values() if isinstance(v, dict) for e in v.values() if isinstance(e, dict))
     if "group" in out:
         out["group_condition_met"] = {k: {name: e["beyond_both_spreads"] for name, e in v.items()} for k, v in out["group"].items()}
+    if "number" in out:
+        out["number_verdicts"] = {k: {name: e["verdict"] for name, e in v.items() if isinstance(e, dict)} for k, v in out["number"].items() if isinstance(v, dict)}
     line = json.dumps(out)
     print(line)
     if a.out:
