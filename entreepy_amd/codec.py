@@ -544,6 +544,15 @@ class Context:
     def _opt_ptr(t):
         return None if t is None else t.data_ptr()
 
+    def _store_args(self, bodies, body_index, text_index):
+        """A store as the selecting calls' C functions take it: its five arguments, the record count last."""
+        n = text_index.numel() - 1
+        return bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n
+
+    def _out32(self, t, what="rows is a 1-D CUDA tensor of 32-bit integers"):
+        """An optional output of 32-bit entries: (its pointer, how many it holds), (None, 0) without one."""
+        return (None, 0) if t is None else (self._rows_ptr(t, what), t.numel())
+
     def _cap_or_raise(self, rc):
         if rc != N.ET_ERR_CAP:  # (a capacity error still carries the room needed: the caller reads it and comes back)
             _check(rc, self._h)
@@ -606,13 +615,11 @@ class Context:
         numbers, ascending (decode_packed_gather_device's rows); None: count only.  status: optional uint8 CUDA tensor of one et_status
         byte per record; a failed record is never selected.  -> MatchResult; .status is ET_OK or ET_ERR_CAP (no row written, .n_match =
         the room needed); any other failure of the call raises.  Stream-ordered like decode_packed_device."""
-        n = text_index.numel() - 1
         a, p = _host_u8(bytes(needle))
-        rows_p = None if rows is None else self._rows_ptr(rows)
         res = N.MatchResult()
         self._bind()
-        rc = N.lib().et_match_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
-                                            p, a.size, int(mode), rows_p, 0 if rows is None else rows.numel(), self._opt_ptr(status), ctypes.byref(res))
+        rc = N.lib().et_match_packed_device(self._h, ctypes.byref(codebook.raw), *self._store_args(bodies, body_index, text_index), p, a.size, int(mode), *self._out32(rows),
+                                            self._opt_ptr(status), ctypes.byref(res))
         return MatchResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
 
     def search_packed_device(self, codebook, bodies, body_index, text_index, needle, mode, rows=None, pos=None, status=None):
@@ -624,14 +631,13 @@ class Context:
         status: optional uint8 CUDA tensor of one et_status byte per record; a failed record is never selected.  -> MatchResult;
         .status is ET_OK or ET_ERR_CAP (no row written, .n_match = the room needed); any other failure of the call raises.
         Stream-ordered like decode_packed_device."""
-        n = text_index.numel() - 1
         a, p = _host_u8(bytes(needle))
-        rows_p, pos_p = (None if t is None else self._rows_ptr(t, "rows and pos are 1-D CUDA tensors of 32-bit integers") for t in (rows, pos))
+        what = "rows and pos are 1-D CUDA tensors of 32-bit integers"
         assert pos is None or (rows is not None and pos.numel() >= rows.numel()), "pos is as large as rows"
         res = N.MatchResult()
         self._bind()
-        rc = N.lib().et_search_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
-                                             p, a.size, int(mode), rows_p, 0 if rows is None else rows.numel(), pos_p, self._opt_ptr(status), ctypes.byref(res))
+        rc = N.lib().et_search_packed_device(self._h, ctypes.byref(codebook.raw), *self._store_args(bodies, body_index, text_index), p, a.size, int(mode), *self._out32(rows, what),
+                                             self._out32(pos, what)[0], self._opt_ptr(status), ctypes.byref(res))
         return MatchResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.first_status, res.pattern_bits)
 
     def join_packed_device(self, codebook, bodies, body_index, text_index, key_bodies, key_body_index, key_text_index, mode=0, rows=None, key_of_row=None, status=None,
@@ -645,14 +651,13 @@ class Context:
         equals nothing.  An empty key set (key_body_index of one entry) selects nothing.  -> JoinResult; .status is ET_OK or
         ET_ERR_CAP (no row written, .n_match = the room needed); any other failure of the call raises.  Stream-ordered like
         decode_packed_device."""
-        n, n_keys = text_index.numel() - 1, key_text_index.numel() - 1
-        rows_p, key_of_p = (None if t is None else self._rows_ptr(t, "rows and key_of_row are 1-D CUDA tensors of 32-bit integers") for t in (rows, key_of_row))
+        what = "rows and key_of_row are 1-D CUDA tensors of 32-bit integers"
         assert key_of_row is None or (rows is not None and key_of_row.numel() >= rows.numel()), "key_of_row is as large as rows"
         res = N.JoinResult()
         self._bind()
-        rc = N.lib().et_join_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
-                                           key_bodies.data_ptr(), key_bodies.numel(), self._index_ptr(key_body_index, n_keys), self._index_ptr(key_text_index), n_keys, int(mode),
-                                           rows_p, 0 if rows is None else rows.numel(), key_of_p, self._opt_ptr(status), self._opt_ptr(key_status), ctypes.byref(res))
+        rc = N.lib().et_join_packed_device(self._h, ctypes.byref(codebook.raw), *self._store_args(bodies, body_index, text_index),
+                                           *self._store_args(key_bodies, key_body_index, key_text_index), int(mode), *self._out32(rows, what), self._out32(key_of_row, what)[0],
+                                           self._opt_ptr(status), self._opt_ptr(key_status), ctypes.byref(res))
         return JoinResult(self._cap_or_raise(rc), res.n_match, res.n_failed, res.first_failed, res.n_keys_failed, res.first_key_failed, res.first_status, res.first_key_status)
 
     def group_packed_device(self, codebook, bodies, body_index, text_index, first_rows=None, count=None, group_of=None, status=None):
@@ -664,15 +669,13 @@ class Context:
         count and group_of need first_rows.  status: optional uint8 CUDA tensor of one et_status byte per record; a failed record
         belongs to no group.  -> GroupResult; .status is ET_OK or ET_ERR_CAP (nothing written, .n_groups = the room needed); any
         other failure of the call raises.  Stream-ordered like decode_packed_device."""
-        n = text_index.numel() - 1
         what = "first_rows, count and group_of are 1-D CUDA tensors of 32-bit integers"
-        first_p, count_p, group_p = (None if t is None else self._rows_ptr(t, what) for t in (first_rows, count, group_of))
         assert count is None or (first_rows is not None and count.numel() >= first_rows.numel()), "count is as large as first_rows"
-        assert group_of is None or group_of.numel() >= n, "group_of holds an entry per record"
+        assert group_of is None or group_of.numel() >= text_index.numel() - 1, "group_of holds an entry per record"
         res = N.GroupResult()
         self._bind()
-        rc = N.lib().et_group_packed_device(self._h, ctypes.byref(codebook.raw), bodies.data_ptr(), bodies.numel(), self._index_ptr(body_index, n), self._index_ptr(text_index), n,
-                                            first_p, 0 if first_rows is None else first_rows.numel(), count_p, group_p, self._opt_ptr(status), ctypes.byref(res))
+        rc = N.lib().et_group_packed_device(self._h, ctypes.byref(codebook.raw), *self._store_args(bodies, body_index, text_index), *self._out32(first_rows, what),
+                                            self._out32(count, what)[0], self._out32(group_of, what)[0], self._opt_ptr(status), ctypes.byref(res))
         return GroupResult(self._cap_or_raise(rc), res.n_groups, res.n_failed, res.first_failed, res.first_status)
 
     def take_packed_device(self, bodies, body_index, text_index, rows, out, out_body_index, out_text_index, status=None):
@@ -933,19 +936,14 @@ class Context:
         match_packed_device call: what decode_packed_rows takes."""
         import torch
 
-        out_index = np.asarray(out_index, dtype=np.uint64)
-        lengths = np.asarray(lengths, dtype=np.uint64)
-        assert out_index.size == lengths.size + 1
+        out_index, lengths = self._store_arrays(out_index, lengths)
         if not lengths.size:
             return []
-        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
-        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
-        res = self.match_packed_device(codebook, d_blob, d_body_index, d_text_index, needle, mode, rows=d_rows)
+        store = self._store_upload(blob, out_index, lengths)
+        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=store[0].device)
+        res = self.match_packed_device(codebook, *store, needle, mode, rows=d_rows)
         _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"match_packed: record {res.first_failed}")
+        self._raise_failed(res, "match_packed")
         return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
 
     def search_packed(self, codebook, blob, out_index, lengths, needle, mode):
@@ -953,20 +951,15 @@ class Context:
         ascending, [where in each]) through one search_packed_device call; with MATCH_NOT the records that do not, and no positions."""
         import torch
 
-        out_index = np.asarray(out_index, dtype=np.uint64)
-        lengths = np.asarray(lengths, dtype=np.uint64)
-        assert out_index.size == lengths.size + 1
+        out_index, lengths = self._store_arrays(out_index, lengths)
         if not lengths.size:
             return [], []
-        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-        d_text_index = torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)
-        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
-        d_pos = None if mode & MATCH_NOT else torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
-        res = self.search_packed_device(codebook, d_blob, d_body_index, d_text_index, needle, mode, rows=d_rows, pos=d_pos)
+        store = self._store_upload(blob, out_index, lengths)
+        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=store[0].device)
+        d_pos = None if mode & MATCH_NOT else torch.empty_like(d_rows)
+        res = self.search_packed_device(codebook, *store, needle, mode, rows=d_rows, pos=d_pos)
         _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"search_packed: record {res.first_failed}")
+        self._raise_failed(res, "search_packed")
         rows = d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copies run behind the call's kernels)
         return rows, [] if d_pos is None else d_pos[: res.n_match].cpu().numpy().view(np.uint32).tolist()
 
@@ -975,21 +968,14 @@ class Context:
         equal some key] -- with MATCH_NOT those that equal none --, ascending, through one join_packed_device call."""
         import torch
 
-        out_index, key_index = np.asarray(out_index, dtype=np.uint64), np.asarray(key_index, dtype=np.uint64)
-        lengths, key_lengths = np.asarray(lengths, dtype=np.uint64), np.asarray(key_lengths, dtype=np.uint64)
-        assert out_index.size == lengths.size + 1 and key_index.size == key_lengths.size + 1
+        (out_index, lengths), (key_index, key_lengths) = self._store_arrays(out_index, lengths), self._store_arrays(key_index, key_lengths)
         if not lengths.size:
             return []
-        sides = []
-        for b, index, lens in ((blob, out_index, lengths), (key_blob, key_index, key_lengths)):
-            d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(b), dtype=np.uint8)), index)
-            text_index = np.concatenate(([0], np.cumsum(lens))).astype(np.uint64)
-            sides += [d_blob, d_body_index, torch.from_numpy(text_index.view(np.int64)).to(d_blob.device)]
-        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=sides[0].device)
-        res = self.join_packed_device(codebook, *sides, mode=mode, rows=d_rows)
+        store, keys = self._store_upload(blob, out_index, lengths), self._store_upload(key_blob, key_index, key_lengths)
+        d_rows = torch.empty(lengths.size, dtype=torch.int32, device=store[0].device)
+        res = self.join_packed_device(codebook, *store, *keys, mode=mode, rows=d_rows)
         _check(res.status, self._h)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"join_packed: record {res.first_failed}")
+        self._raise_failed(res, "join_packed")
         if res.n_keys_failed:
             raise EntreepyError(res.first_key_status, f"join_packed: key {res.first_key_failed}")
         return d_rows[: res.n_match].cpu().numpy().view(np.uint32).tolist()  # (the copy runs behind the call's kernels)
@@ -999,24 +985,27 @@ class Context:
         how many records hold it, and every record's group -- through a count-only group_packed_device call, then the writing one."""
         import torch
 
-        out_index, lengths = np.asarray(out_index, dtype=np.uint64), np.asarray(lengths, dtype=np.uint64)
-        assert out_index.size == lengths.size + 1
+        out_index, lengths = self._store_arrays(out_index, lengths)
         if not lengths.size:
             return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
-        text_index = np.concatenate(([0], np.cumsum(lengths))).astype(np.uint64)
-        d_blob, d_body_index = self._packed_upload(np.array(np.frombuffer(bytes(blob), dtype=np.uint8)), out_index)
-        store = (d_blob, d_body_index, torch.from_numpy(text_index.view(np.int64)).to(d_blob.device))
+        store = self._store_upload(blob, out_index, lengths)
+        dev = store[0].device
         res = self.group_packed_device(codebook, *store)
-        if res.n_failed:
-            raise EntreepyError(res.first_status, f"group_packed: record {res.first_failed}")
-        d_first, d_count = (torch.empty(max(res.n_groups, 1), dtype=torch.int32, device=d_blob.device) for _ in range(2))
-        d_group_of = torch.empty(lengths.size, dtype=torch.int32, device=d_blob.device)
+        self._raise_failed(res, "group_packed")
+        d_first, d_count = (torch.empty(max(res.n_groups, 1), dtype=torch.int32, device=dev) for _ in range(2))
+        d_group_of = torch.empty(lengths.size, dtype=torch.int32, device=dev)
         res = self.group_packed_device(codebook, *store, first_rows=d_first, count=d_count, group_of=d_group_of)
         _check(res.status, self._h)
         host = lambda t, k: t[:k].cpu().numpy().view(np.uint32)  # (the copies run behind the call's kernels)
         return host(d_first, res.n_groups), host(d_count, res.n_groups), host(d_group_of, lengths.size)
 
-    # What the list helpers of the store-deriving calls (take, slice, field, concat, recode) share.
+    # What the list helpers of the selecting and the store-deriving calls share.
+    @staticmethod
+    def _raise_failed(res, what):
+        """The first failed record of a call, as an EntreepyError."""
+        if res.n_failed:
+            raise EntreepyError(res.first_status, f"{what}: record {res.first_failed}")
+
     @staticmethod
     def _store_arrays(out_index, lengths):
         """decode_packed's offsets and lengths as numpy u64 arrays."""

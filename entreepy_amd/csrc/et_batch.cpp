@@ -253,7 +253,8 @@ T *ws(et_ctx *ctx, size_t off) { return reinterpret_cast<T *>(static_cast<uint8_
 // The tile workspace of the match and the join: a count per tile (padded to 16 bytes), the tiles' first places (tiles + 1), four masks per tile.
 struct TileOffsets { size_t counts, base, masks; };
 
-TileOffsets tile_ws(Bump &b, size_t n_tiles) {
+TileOffsets tile_ws(Bump &b, size_t n_records) {
+    const size_t n_tiles = (n_records + et::MATCH_TILE - 1) / et::MATCH_TILE;
     TileOffsets t;
     t.counts = b.take((n_tiles * 4 + 15) & ~static_cast<size_t>(15), 16);
     t.base = b.take((n_tiles + 1) * 8, 16);
@@ -331,27 +332,87 @@ int packed_end(et_ctx *ctx, uint64_t epoch, et_packed_result *res, bool capped, 
     return ET_OK;
 }
 
+// ---- the calls that select records of a packed store (match with its order modes, search, join, group) ------------------------
+// A store as a selecting or a deriving call is given it, and what the kernels take it for.
+struct Source {
+    const void *bodies;
+    size_t body_bytes;
+    const uint64_t *body_index, *text_index;
+    size_t n;
+    const uint32_t *rows;  // null: row k is record k
+};
+
+et::PackedStore packed_store(const Source &s) { return et::PackedStore{s.bodies, s.body_bytes, s.body_index, s.text_index, static_cast<uint32_t>(s.n), 0}; }
+
+// The head of a selecting call, the checks in THIS order: the store (and the join's key set, unless empty) is there and `missing`, one of
+// the call's own pointers, is not true; the offset arrays are 8-byte, the 32-bit outputs `out32` 4-byte aligned; `most` records at most.
+struct SelectTexts { const char *unaligned4, *too_many; };  // the two texts that differ between the calls
+
+int select_args(et_ctx *ctx, const et_codebook *cb, const void *res, const Source &s, const Source *keys, bool missing, std::initializer_list<const void *> out32, size_t most,
+                const SelectTexts &t) {
+    const bool no_keys = keys && keys->n && (!keys->bodies || !keys->body_index || !keys->text_index);
+    if (!cb || !res || !s.bodies || !s.body_index || !s.text_index || missing || no_keys) return fail(ctx, ET_ERR_ARG, "null pointer");
+    if (misaligned(7, s.body_index, s.text_index) || (keys && misaligned(7, keys->body_index, keys->text_index))) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
+    for (const void *out : out32)
+        if (misaligned(3, out)) return fail(ctx, ET_ERR_ARG, t.unaligned4);
+    if (s.n > most) return fail(ctx, ET_ERR_ARG, t.too_many);
+    return ET_OK;
+}
+
+// ... and its tail, behind the launches: the poll (`never`), the fault bit of a call with a hash table (`fault`: ET_ERR_HIP), how many
+// were selected (res->*count), the records' failures; ET_ERR_CAP (`too_much`) when rows were asked for and more are selected than `cap`.
+template <typename Res>
+int selected_end(et_ctx *ctx, uint64_t epoch, Res *res, uint64_t Res::*count, const void *d_rows, uint64_t cap, const char *never, const char *too_much, const char *fault = nullptr) {
+    ET_TRY(packed_poll(ctx, epoch, never));
+    const uint64_t *rep = report_words(ctx);
+    if (fault && (rep[et::PACKED_N_FAILED] & et::JOIN_FAULT_BIT)) return fail(ctx, ET_ERR_HIP, fault);
+    res->*count = rep[et::PACKED_BYTES];
+    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
+    if (d_rows && res->*count > cap) return fail(ctx, ET_ERR_CAP, too_much);
+    return ET_OK;
+}
+
+// The needle of the match, its order modes and the search: the pattern of its first n_coded bytes (et_encode_pattern) in the pinned
+// block (behind packed_ensure), zero-padded to a word and `spare` bytes on; the bits, the length and the flags the three jobs share (a byte
+// without a code: MATCH_F_NEVER; the order modes' codable prefix has none); pattern_bits.  The head words are each family's own.
+struct Needle { const uint8_t *pattern; size_t pat_bytes, padded; };
+
+template <typename Job>
+int needle_job(et_ctx *ctx, const et_codebook *cb, const uint8_t *needle, size_t n_coded, size_t needle_len, size_t pattern_cap, int mode, size_t spare, Job *job,
+               et_match_result *res, Needle *nd) {
+    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
+    uint64_t bits = 0;
+    const int rc = et_encode_pattern(cb, needle, n_coded, pattern, pattern_cap, &bits);
+    if (rc != ET_OK && rc != ET_ERR_UNSUPPORTED) return fail(ctx, rc, "et_encode_pattern");
+    const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
+    std::memset(pattern + pat_bytes, 0, padded + spare - pat_bytes);
+    job->pat_bits = static_cast<uint32_t>(bits);
+    job->needle_len = static_cast<uint32_t>(needle_len);
+    job->flags = ((mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u) | (rc == ET_ERR_UNSUPPORTED ? et::MATCH_F_NEVER : 0u);
+    res->pattern_bits = job->pat_bits;
+    *nd = Needle{pattern, pat_bytes, padded};
+    return ET_OK;
+}
+
 // The order modes of et_match_packed_device, behind its argument check.  A needle byte without a code ends the codable prefix
 // needle[:K]: no record holds that byte, so the prefix's bits and the byte itself (the table's last entry) decide.
 int order_call(et_ctx *ctx, const et_codebook *cb, const et::PackedStore &store, const uint8_t *needle, size_t needle_len, int mode, uint32_t *d_rows, size_t cap_rows,
                uint8_t *d_status, et_match_result *res) {
-    size_t K = 0;
-    uint64_t bits = 0;
+    size_t K = 0, bits = 0;
     while (K < needle_len && cb->length[needle[K]] >= 1 && cb->length[needle[K]] <= 32) bits += cb->length[needle[K++]];
     const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
     Bump layout{PK_PATTERN + padded};
     const size_t at_starts = layout.take((K + 1) * 4, 4);
-    const TileOffsets tiles = tile_ws(layout, (store.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const TileOffsets tiles = tile_ws(layout, store.n);
     ET_TRY(packed_ensure(ctx, layout.end));
 
     // the sorted codes, the counters' first values, the prefix's bits and the boundaries lie one behind the other: up in one copy
     // (2 KiB + 64 bytes + at most 16 KiB of pattern + at most 4 097 words: 35 KiB at the most, where EQUAL and PREFIX send 16 KiB)
     const uint32_t n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), false);
     first_counters(ctx);
-    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
-    const int rc = et_encode_pattern(cb, needle, K, pattern, et::MATCH_PATTERN_BYTES, &bits);
-    if (rc != ET_OK) return fail(ctx, rc, "et_encode_pattern");
-    std::memset(pattern + pat_bytes, 0, padded - pat_bytes);
+    et::OrderJob job{};
+    Needle nd;
+    ET_TRY(needle_job(ctx, cb, needle, K, needle_len, et::MATCH_PATTERN_BYTES, mode, 0, &job, res, &nd));
     uint32_t *starts = pin<uint32_t>(ctx, PIN_PK_TABLE + at_starts);
     uint32_t bit = 0;
     for (size_t i = 0; i < K; ++i) {
@@ -359,23 +420,14 @@ int order_call(et_ctx *ctx, const et_codebook *cb, const et::PackedStore &store,
         bit += cb->length[needle[i]];
     }
     starts[K] = bit << 8 | (K < needle_len ? needle[K] : 0u);
-    et::OrderJob job{};
-    job.pat_bits = static_cast<uint32_t>(bits);
     job.n_coded = static_cast<uint32_t>(K);
-    job.needle_len = static_cast<uint32_t>(needle_len);
-    job.flags = ((mode & ~ET_MATCH_NOT) == ET_MATCH_LESS_EQUAL ? et::ORDER_F_EQUAL_TOO : 0u) | ((mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u) | (K < needle_len ? et::ORDER_F_TAIL : 0u);
-    for (uint32_t k = 0; k < std::min<size_t>(pat_bytes, 8); ++k) job.head |= static_cast<uint64_t>(pattern[k]) << (56 - 8 * k);
-    res->pattern_bits = job.pat_bits;
+    job.flags |= ((mode & ~ET_MATCH_NOT) == ET_MATCH_LESS_EQUAL ? et::ORDER_F_EQUAL_TOO : 0u) | (K < needle_len ? et::ORDER_F_TAIL : 0u);
+    for (uint32_t k = 0; k < std::min<size_t>(nd.pat_bytes, 8); ++k) job.head |= static_cast<uint64_t>(nd.pattern[k]) << (56 - 8 * k);  // (big-endian: bit 0 of the body is bit 63)
     ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), at_starts + (K + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     const et::PackedReport report = next_report(ctx);
     et::launch_order(ctx->stream, store, ws<const uint2>(ctx, 0), n_codes, ws<const uint32_t>(ctx, PK_PATTERN), ws<const uint32_t>(ctx, at_starts), job, d_rows, cap_rows, d_status,
                      tile_ptrs(ctx, tiles), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the match's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->n_match = rep[et::PACKED_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_rows_emit saw the same two figures)
-    return ET_OK;
+    return selected_end(ctx, report.epoch, res, &et_match_result::n_match, d_rows, cap_rows, "the match's report never reached the host", "more records are selected than cap_rows");
 }
 
 // An item's own failure is the item's; a failure of the runtime under a delegated stream is the call's.
@@ -453,10 +505,8 @@ extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const 
                                       const uint64_t *d_text_index, size_t n_records, const uint8_t *needle, size_t needle_len, int mode, uint32_t *d_rows,
                                       size_t cap_rows, uint8_t *d_status, et_match_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || (!needle && needle_len)) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_rows)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
-    if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, nullptr};
+    ET_TRY(select_args(ctx, cb, res, src, nullptr, !needle && needle_len, {d_rows}, 0x7fffffffu, {"the rows are not 4-byte aligned", "too many records"}));
     if (needle_len > et::MATCH_NEEDLE_MAX) return fail(ctx, ET_ERR_ARG, "the needle is longer than et_match_pattern_max()");
     const int what = mode & ~ET_MATCH_NOT;
     const bool order = what == ET_MATCH_LESS || what == ET_MATCH_LESS_EQUAL;
@@ -465,40 +515,28 @@ extern "C" int et_match_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     if (n_records == 0) return ET_OK;
     ET_TRY(require_complete(ctx, cb));
     DeviceGuard guard(ctx->device);
-    const et::PackedStore store{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    const et::PackedStore store = packed_store(src);
     if (order) return order_call(ctx, cb, store, needle, needle_len, mode, d_rows, cap_rows, d_status, res);
     Bump layout{PK_MATCH_TILES};
-    const TileOffsets tiles = tile_ws(layout, (store.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const TileOffsets tiles = tile_ws(layout, store.n);
     ET_TRY(packed_ensure(ctx, layout.end));
 
     // the counters' first values and the needle's bits, up in one copy
     const uint64_t *first = first_counters(ctx);
-    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
-    uint64_t bits = 0;
-    const int rc = et_encode_pattern(cb, needle, needle_len, pattern, et::MATCH_PATTERN_BYTES, &bits);
-    if (rc != ET_OK && rc != ET_ERR_UNSUPPORTED) return fail(ctx, rc, "et_encode_pattern");
-    const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
-    std::memset(pattern + pat_bytes, 0, padded - pat_bytes);
     et::MatchJob job{};
-    job.pat_bits = static_cast<uint32_t>(bits);
-    job.needle_len = static_cast<uint32_t>(needle_len);
-    job.flags = (what == ET_MATCH_EQUAL ? et::MATCH_F_EQUAL : 0u) | ((mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u) | (rc == ET_ERR_UNSUPPORTED ? et::MATCH_F_NEVER : 0u);
-    const uint64_t head_bits = std::min<uint64_t>(bits, et::MATCH_HEAD_BITS);
+    Needle nd;
+    ET_TRY(needle_job(ctx, cb, needle, needle_len, needle_len, et::MATCH_PATTERN_BYTES, mode, 0, &job, res, &nd));
+    job.flags |= what == ET_MATCH_EQUAL ? et::MATCH_F_EQUAL : 0u;
+    const uint64_t head_bits = std::min<uint64_t>(job.pat_bits, et::MATCH_HEAD_BITS);
     for (uint32_t k = 0; k < (head_bits + 7) / 8; ++k) {  // (memory order: byte k of the body is bits 8k .. 8k + 7 of the word)
         const uint64_t left = head_bits - 8 * k;
-        job.head |= static_cast<uint64_t>(pattern[k]) << (8 * k);
+        job.head |= static_cast<uint64_t>(nd.pattern[k]) << (8 * k);
         job.head_mask |= static_cast<uint64_t>(left >= 8 ? 0xffu : (0xffu << (8 - left)) & 0xffu) << (8 * k);
     }
-    res->pattern_bits = job.pat_bits;
-    ET_HIP(hipMemcpyAsync(ws<uint8_t>(ctx, PK_STATS), first, PK_COUNTER_BYTES + padded, hipMemcpyHostToDevice, ctx->stream));
+    ET_HIP(hipMemcpyAsync(ws<uint8_t>(ctx, PK_STATS), first, PK_COUNTER_BYTES + nd.padded, hipMemcpyHostToDevice, ctx->stream));
     const et::PackedReport report = next_report(ctx);
     et::launch_match(ctx->stream, store, ws<const uint32_t>(ctx, PK_PATTERN), job, d_rows, cap_rows, d_status, tile_ptrs(ctx, tiles), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the match's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->n_match = rep[et::PACKED_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records match than cap_rows");  // (k_rows_emit saw the same two figures)
-    return ET_OK;
+    return selected_end(ctx, report.epoch, res, &et_match_result::n_match, d_rows, cap_rows, "the match's report never reached the host", "more records match than cap_rows");
 }
 
 extern "C" size_t et_search_needle_max(void) { return et::SEARCH_NEEDLE_MAX; }
@@ -509,10 +547,8 @@ extern "C" int et_search_packed_device(et_ctx *ctx, const et_codebook *cb, const
                                        const uint64_t *d_text_index, size_t n_records, const uint8_t *needle, size_t needle_len, int mode, uint32_t *d_rows,
                                        size_t cap_rows, uint32_t *d_pos, uint8_t *d_status, et_match_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index || (!needle && needle_len)) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_rows, d_pos)) return fail(ctx, ET_ERR_ARG, "the rows or the positions are not 4-byte aligned");
-    if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, nullptr};
+    ET_TRY(select_args(ctx, cb, res, src, nullptr, !needle && needle_len, {d_rows, d_pos}, 0x7fffffffu, {"the rows or the positions are not 4-byte aligned", "too many records"}));
     if (needle_len > et::SEARCH_NEEDLE_MAX) return fail(ctx, ET_ERR_ARG, "the needle is longer than et_search_needle_max()");
     const int what = mode & ~ET_MATCH_NOT;
     if (what != ET_SEARCH_CONTAINS && what != ET_SEARCH_SUFFIX) return fail(ctx, ET_ERR_ARG, "unknown mode");
@@ -522,38 +558,26 @@ extern "C" int et_search_packed_device(et_ctx *ctx, const et_codebook *cb, const
     if (n_records == 0) return ET_OK;
     ET_TRY(require_complete(ctx, cb));
     DeviceGuard guard(ctx->device);
-    const et::PackedStore store{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    const et::PackedStore store = packed_store(src);
     Bump layout{PK_MATCH_TILES};
-    const TileOffsets tiles = tile_ws(layout, (store.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const TileOffsets tiles = tile_ws(layout, store.n);
     const size_t at_pos = layout.take(static_cast<size_t>(store.n) * 4, 4), at_list = layout.take(static_cast<size_t>(store.n) * 4, 4);
     ET_TRY(packed_ensure(ctx, layout.end));
 
     // the sorted codes, the counters' first values and the needle's bits lie one behind the other: up in one copy
     const uint32_t n_codes = fill_shared_table(cb, pin<uint32_t>(ctx, PIN_PK_TABLE), false);
     first_counters(ctx);
-    uint8_t *pattern = pin<uint8_t>(ctx, PIN_PK_PATTERN);
-    uint64_t bits = 0;
-    const int rc = et_encode_pattern(cb, needle, needle_len, pattern, et::SEARCH_PATTERN_BYTES, &bits);
-    if (rc != ET_OK && rc != ET_ERR_UNSUPPORTED) return fail(ctx, rc, "et_encode_pattern");
-    const size_t pat_bytes = static_cast<size_t>((bits + 7) / 8), padded = (pat_bytes + 3) & ~static_cast<size_t>(3);
-    std::memset(pattern + pat_bytes, 0, padded + 4 - pat_bytes);  // (and the word the head is read from, for a pattern of no bytes)
     et::SearchJob job{};
-    job.pat_bits = static_cast<uint32_t>(bits);
-    job.needle_len = static_cast<uint32_t>(needle_len);
-    job.flags = (what == ET_SEARCH_SUFFIX ? et::SEARCH_F_SUFFIX : 0u) | ((mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u) | (rc == ET_ERR_UNSUPPORTED ? et::MATCH_F_NEVER : 0u);
-    job.head_mask = bits >= 32 ? 0xffffffffu : bits ? ~(0xffffffffu >> bits) : 0u;
-    job.head = (static_cast<uint32_t>(pattern[0]) << 24 | static_cast<uint32_t>(pattern[1]) << 16 | static_cast<uint32_t>(pattern[2]) << 8 | pattern[3]) & job.head_mask;
-    res->pattern_bits = job.pat_bits;
-    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_PATTERN + padded, hipMemcpyHostToDevice, ctx->stream));
+    Needle nd;  // (4 spare bytes: the word the head is read from, for a pattern of no bytes)
+    ET_TRY(needle_job(ctx, cb, needle, needle_len, needle_len, et::SEARCH_PATTERN_BYTES, mode, 4, &job, res, &nd));
+    job.flags |= what == ET_SEARCH_SUFFIX ? et::SEARCH_F_SUFFIX : 0u;
+    job.head_mask = job.pat_bits >= 32 ? 0xffffffffu : job.pat_bits ? ~(0xffffffffu >> job.pat_bits) : 0u;
+    job.head = (static_cast<uint32_t>(nd.pattern[0]) << 24 | static_cast<uint32_t>(nd.pattern[1]) << 16 | static_cast<uint32_t>(nd.pattern[2]) << 8 | nd.pattern[3]) & job.head_mask;
+    ET_HIP(hipMemcpyAsync(ctx->packed_ws.p, pin<uint8_t>(ctx, PIN_PK_TABLE), PK_PATTERN + nd.padded, hipMemcpyHostToDevice, ctx->stream));
     const et::PackedReport report = next_report(ctx);
     et::launch_search(ctx->stream, store, ws<const uint2>(ctx, 0), n_codes, ws<const uint32_t>(ctx, PK_PATTERN), job, d_rows, cap_rows, d_pos, d_status, tile_ptrs(ctx, tiles),
                       ws<uint32_t>(ctx, at_pos), ws<uint32_t>(ctx, at_list), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the search's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    res->n_match = rep[et::PACKED_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_rows_emit saw the same two figures)
-    return ET_OK;
+    return selected_end(ctx, report.epoch, res, &et_match_result::n_match, d_rows, cap_rows, "the search's report never reached the host", "more records are selected than cap_rows");
 }
 
 extern "C" size_t et_join_keys_max(void) { return et::ET_JOIN_KEYS_MAX; }
@@ -577,11 +601,8 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
                                      const uint64_t *d_key_text_index, size_t n_keys, int mode, uint32_t *d_rows, size_t cap_rows, uint32_t *d_key_of_row, uint8_t *d_status,
                                      uint8_t *d_key_status, et_join_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (n_keys && (!d_key_bodies || !d_key_body_index || !d_key_text_index)) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index, d_key_body_index, d_key_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_rows, d_key_of_row)) return fail(ctx, ET_ERR_ARG, "the rows are not 4-byte aligned");
-    if (n_records > 0x7fffffffu) return fail(ctx, ET_ERR_ARG, "too many records");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, nullptr}, key_src{d_key_bodies, key_body_bytes, d_key_body_index, d_key_text_index, n_keys, nullptr};
+    ET_TRY(select_args(ctx, cb, res, src, &key_src, false, {d_rows, d_key_of_row}, 0x7fffffffu, {"the rows are not 4-byte aligned", "too many records"}));
     if (n_keys > et::ET_JOIN_KEYS_MAX) return fail(ctx, ET_ERR_ARG, "more keys than et_join_keys_max()");
     if (mode != 0 && mode != ET_MATCH_NOT) return fail(ctx, ET_ERR_ARG, "unknown mode");
     if (d_key_of_row && (mode & ET_MATCH_NOT)) return fail(ctx, ET_ERR_ARG, "a record no key equals has no key number");
@@ -590,11 +611,10 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
     if (n_records == 0) return ET_OK;
     ET_TRY(require_complete(ctx, cb));
     DeviceGuard guard(ctx->device);
-    const et::PackedStore records{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
-    const et::PackedStore keys{d_key_bodies, key_body_bytes, d_key_body_index, d_key_text_index, static_cast<uint32_t>(n_keys), 0};
+    const et::PackedStore records = packed_store(src), keys = packed_store(key_src);
     const size_t slots = et::et_join_slots_for(n_keys);
     Bump layout{PK_STATS + PK_COUNTER_BYTES};
-    const TileOffsets tiles = tile_ws(layout, (records.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const TileOffsets tiles = tile_ws(layout, records.n);
     const size_t at_table = layout.take(slots * 8, 8), at_key_of = layout.take(static_cast<size_t>(records.n) * 4, 4);
     ET_TRY(packed_ensure(ctx, layout.end));
 
@@ -606,14 +626,10 @@ extern "C" int et_join_packed_device(et_ctx *ctx, const et_codebook *cb, const v
     const et::PackedReport report = next_report(ctx);
     et::launch_join(ctx->stream, records, keys, (mode & ET_MATCH_NOT) ? et::MATCH_F_NOT : 0u, ws<unsigned long long>(ctx, at_table), slots, d_rows, cap_rows, d_key_of_row,
                     d_status, d_key_status, tile_ptrs(ctx, tiles), ws<uint32_t>(ctx, at_key_of), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the join's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    if (rep[et::PACKED_N_FAILED] & et::JOIN_FAULT_BIT) return fail(ctx, ET_ERR_HIP, "a probe sequence of the join's table met no empty slot");
-    res->n_match = rep[et::PACKED_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    read_failures(rep, et::JOIN_KEYS_FAILED, &res->n_keys_failed, &res->first_key_failed, &res->first_key_status);
-    if (d_rows && res->n_match > cap_rows) return fail(ctx, ET_ERR_CAP, "more records are selected than cap_rows");  // (k_rows_emit saw the same two figures)
-    return ET_OK;
+    const int rc = selected_end(ctx, report.epoch, res, &et_join_result::n_match, d_rows, cap_rows, "the join's report never reached the host",
+                                "more records are selected than cap_rows", "a probe sequence of the join's table met no empty slot");
+    if (rc == ET_OK || rc == ET_ERR_CAP) read_failures(report_words(ctx), et::JOIN_KEYS_FAILED, &res->n_keys_failed, &res->first_key_failed, &res->first_key_status);
+    return rc;  // (the keys' failures are reported with ET_ERR_CAP too, as the records' are)
 }
 
 extern "C" size_t et_group_result_size(void) { return sizeof(et_group_result); }
@@ -626,20 +642,19 @@ extern "C" int et_group_packed_device(et_ctx *ctx, const et_codebook *cb, const 
                                       const uint64_t *d_text_index, size_t n_records, uint32_t *d_first_rows, size_t cap_groups, uint32_t *d_count, uint32_t *d_group_of,
                                       uint8_t *d_status, et_group_result *res) {
     if (!ctx) return ET_ERR_ARG;
-    if (!cb || !res || !d_bodies || !d_body_index || !d_text_index) return fail(ctx, ET_ERR_ARG, "null pointer");
-    if (misaligned(7, d_body_index, d_text_index)) return fail(ctx, ET_ERR_ARG, "an offset array is not 8-byte aligned");
-    if (misaligned(3, d_first_rows, d_count, d_group_of)) return fail(ctx, ET_ERR_ARG, "the first rows, the counts or the group numbers are not 4-byte aligned");
-    if (n_records > et::ET_JOIN_KEYS_MAX) return fail(ctx, ET_ERR_ARG, "more records than et_group_records_max()");
+    const Source src{d_bodies, body_bytes, d_body_index, d_text_index, n_records, nullptr};
+    ET_TRY(select_args(ctx, cb, res, src, nullptr, false, {d_first_rows, d_count, d_group_of}, et::ET_JOIN_KEYS_MAX,
+                       {"the first rows, the counts or the group numbers are not 4-byte aligned", "more records than et_group_records_max()"}));
     if ((d_count || d_group_of) && !d_first_rows) return fail(ctx, ET_ERR_ARG, "counts or group numbers without first rows");
     *res = et_group_result{};
     if (n_records == 0) return ET_OK;
     ET_TRY(require_complete(ctx, cb));
     DeviceGuard guard(ctx->device);
-    const et::PackedStore records{d_bodies, body_bytes, d_body_index, d_text_index, static_cast<uint32_t>(n_records), 0};
+    const et::PackedStore records = packed_store(src);
     // the join's layout, the store as its own key set, plus three words per record: its hash, its representative, and a representative's group
     const size_t slots = et::et_join_slots_for(n_records);
     Bump layout{PK_STATS + PK_COUNTER_BYTES};
-    const TileOffsets tiles = tile_ws(layout, (records.n + et::MATCH_TILE - 1) / et::MATCH_TILE);
+    const TileOffsets tiles = tile_ws(layout, records.n);
     const size_t at_table = layout.take(slots * 8, 8), at_hash_of = layout.take(n_records * 8, 8), at_rep_of = layout.take(n_records * 4, 4), at_dense = layout.take(n_records * 4, 4);
     ET_TRY(packed_ensure(ctx, layout.end));
 
@@ -649,27 +664,11 @@ extern "C" int et_group_packed_device(et_ctx *ctx, const et_codebook *cb, const 
     const et::PackedReport report = next_report(ctx);
     et::launch_group(ctx->stream, records, ws<unsigned long long>(ctx, at_table), slots, d_first_rows, cap_groups, d_count, d_group_of, d_status, tile_ptrs(ctx, tiles),
                      ws<uint64_t>(ctx, at_hash_of), ws<uint32_t>(ctx, at_rep_of), ws<uint32_t>(ctx, at_dense), report);
-    ET_TRY(packed_poll(ctx, report.epoch, "the group call's report never reached the host"));
-    const uint64_t *rep = report_words(ctx);
-    if (rep[et::PACKED_N_FAILED] & et::JOIN_FAULT_BIT) return fail(ctx, ET_ERR_HIP, "a probe sequence of the group call's table met no slot of its text");
-    res->n_groups = rep[et::PACKED_BYTES];
-    read_failures(rep, et::PACKED_N_FAILED, &res->n_failed, &res->first_failed, &res->first_status);
-    if (d_first_rows && res->n_groups > cap_groups) return fail(ctx, ET_ERR_CAP, "more groups than cap_groups");  // (k_group_emit and k_group_number saw the same two figures)
-    return ET_OK;
+    return selected_end(ctx, report.epoch, res, &et_group_result::n_groups, d_first_rows, cap_groups, "the group call's report never reached the host",
+                        "more groups than cap_groups", "a probe sequence of the group call's table met no slot of its text");
 }
 
 // ---- the calls that derive a new packed store from an old one (take, slice, field, concat, recode) ---------------------------
-// A source store as such a call is given it, and what the kernels take it for.
-struct Source {
-    const void *bodies;
-    size_t body_bytes;
-    const uint64_t *body_index, *text_index;
-    size_t n;
-    const uint32_t *rows;  // null: row k is record k
-};
-
-et::PackedStore packed_store(const Source &s) { return et::PackedStore{s.bodies, s.body_bytes, s.body_index, s.text_index, static_cast<uint32_t>(s.n), 0}; }
-
 // The head of such a call, behind the null check of what is the call's own: one source against the rows and the output, the checks
 // in THIS order.  unaligned4: one of the call's own per-row arrays is not 4-byte aligned.  The texts that differ between the calls:
 struct SourceTexts {
