@@ -9,6 +9,10 @@
 //   hash     = mix(sum + mix(length * ET_JOIN_STEP + n_bytes))
 // with mix the finaliser of splitmix64.  A body of no bytes has no words: its hash is that of (length, 0) alone.  The hash picks a
 // slot and its upper half is the slot's tag; it never decides alone -- every hit is confirmed by length, byte count and bytes.
+// That sentence is held by the collide_* fixtures of tests/test_gpu_join.py and tests/test_gpu_group.py: mix is a bijection and the
+// sum is plain, so tests/hashcraft.py solves a body's last word for any wanted hash, and the fixtures hold DIFFERENT texts with one
+// tag and one home slot, with one whole 64-bit hash, with one hash under other lengths and byte counts, and with one hash and equal
+// first 512 bytes -- a confirmation that looks at less merges them (tests/test_join_host.py shows which fixture catches what).
 #pragma once
 
 #include <stddef.h>

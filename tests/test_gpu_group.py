@@ -6,7 +6,10 @@ implement.  The one exception is the hand-made-body fixture, where the documente
 with sentinels first; everything at or behind n_groups must still hold them.
 
 The stores are made by the *_fixture functions below, without a GPU: tests/test_group_host.py checks on the same fixtures that the
-byte rule gives the partition that dict membership gives, and that they reach the cases named here."""
+byte rule gives the partition that dict membership gives, and that they reach the cases named here.  The stores: edges, counting, trap,
+chain (one home slot, tags that differ), near, long, failures, mixed, csv -- and collide_one_tag, collide_one_hash, collide_sizes,
+collide_wave: the join's texts with hash tags, or whole hashes, equal by construction (tests/hashcraft.py), the only ones in which a tag
+hit is confirmed between two DIFFERENT texts."""
 import ctypes
 import functools
 from types import SimpleNamespace
@@ -18,11 +21,12 @@ from tests import corpus
 from tests import retained_group  # noqa: F401  (the call's row joins the table of tests/retained.py)
 from tests.test_gpu_batch import SENTINEL, _small_max
 from tests.test_gpu_gather import _mixed_store, dev_rows, make_store, upload, want_rows  # noqa: F401  (through judged)
-from tests.test_gpu_join import LANE_BYTES, TILE, _rand_texts, _raw, handmade_fixture, host_hash, long_fixture, near_fixture, run_join, table_slots, trap_fixture
+from tests.test_gpu_join import CRAFT_RECORDS, CRAFTED, CRAFTS, LANE_BYTES, TILE, _rand_texts, _raw, acgt_texts, check_crafted_hashes, handmade_fixture, host_hash, long_fixture, \
+    near_fixture, run_join, spread, table_slots, trap_fixture
 from tests.test_gpu_match import EQUAL, ROW_SENTINEL, _pack, _store, judged, run_match
 from tests.test_gpu_packed import TAIL, _dev_bytes, _dev_index, _index_of
 from tests.test_gpu_shared import _cb, want_decode  # noqa: F401
-from tests.test_shared_host import oracle_table, table_255, table_ladder
+from tests.test_shared_host import oracle_table, table_2bit, table_255, table_ladder
 
 pytestmark = pytest.mark.gpu
 
@@ -244,7 +248,31 @@ def csv_fixture():
     return _store(oracle_table(np.frombuffer(b"".join(lines), np.uint8)), lines), lines
 
 
+@functools.lru_cache(maxsize=None)
+def collide_store(name):
+    """-> (store, info).  The join's crafted texts (tests/test_gpu_join.py's *_craft: one tag and one home slot; one whole hash; one hash
+    under other sizes; one hash on the wavefront path) as ONE store of 632 records -- three tiles, a table of 2 048 slots, under whose
+    mask the crafted homes are still equal --: every crafted text two or three times, its copies in different tiles, among fillers that
+    are all different.  In the second tile a record fails (a decreasing body pair; the filler behind it begins 2 bytes early), in
+    the third one is kept raw (no body under its length)."""
+    c = CRAFTS[name]()
+    tab = table_2bit()
+    rng = np.random.default_rng(0x6E0A9800 + CRAFTED.index(name))
+    crafted = list(c.keys) + list(c.strangers)
+    placed = [((i + j) % 3, t) for i, t in enumerate(crafted) for j in range(2 + i % 2)]
+    texts = spread(rng, CRAFT_RECORDS, placed, acgt_texts(rng, CRAFT_RECORDS - len(placed), avoid=c.hashes))
+    filler = lambda b: texts[b] not in c.hashes  # noqa: E731
+    failed = next(b for b in range(TILE + 1, 2 * TILE - 1) if filler(b - 1) and filler(b) and filler(b + 1))
+    raw = next(b for b in range(2 * TILE, CRAFT_RECORDS) if filler(b))
+    bodies = [_pack(tab, t) for t in texts]
+    bodies[raw] = b""
+    st = _store(tab, texts, bodies)
+    st.body_index[failed + 1] = st.body_index[failed] - np.uint64(2)
+    return st, SimpleNamespace(craft=c, crafted=crafted, copies={t: 2 + i % 2 for i, t in enumerate(crafted)}, failed=failed, raw=raw, others=CRAFT_RECORDS - len(placed) - 1)
+
+
 STORES = {"trap": trap_store, "chain": lambda: chain_fixture()[0], "long": long_store, "failures": failures_fixture, "mixed": mixed_fixture,
+          **{f"collide_{name}": (lambda name=name: collide_store(name)[0]) for name in CRAFTED},
           **{f"near_{i}": (lambda i=i: near_stores()[i]) for i in range(3)},
           **{f"counting_{kind}": (lambda kind=kind: counting_fixture(kind)) for kind in ("one", "distinct", "skewed")},
           **{f"edges_{n}": (lambda n=n: edges_fixture(n)) for n in EDGE_SIZES}}
@@ -296,6 +324,53 @@ def test_a_chain_of_32_records_with_one_home_slot_that_wraps(ctx):
     st, info = chain_fixture()
     r = group(ctx, st)
     assert r.res.n_groups == COLLIDERS + 20 and r.count[: r.res.n_groups].tolist() == [2] * (COLLIDERS + 20)
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_the_device_gives_every_crafted_record_the_crafted_hash(ctx, name):
+    st, info = collide_store(name)
+    assert check_crafted_hashes(ctx, st, info.craft.hashes) == sum(info.copies.values())
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_texts_whose_tags_collide_by_construction_are_groups_apart(ctx, name):
+    """Three times with identical arrays (the order of the inserts races), and count-only: as many groups as there are different crafted
+    texts and fillers, each crafted text's with its two or three members."""
+    st, info = collide_store(name)
+    dev = upload(st)
+    runs = [group(ctx, st, dev=dev) for _ in range(3)]
+    r = runs[0]
+    for again in runs[1:]:
+        assert np.array_equal(again.first, r.first) and np.array_equal(again.count, r.count) and np.array_equal(again.group_of, r.group_of) and again.res == r.res
+    assert len(set(info.crafted)) == len(info.crafted)
+    assert r.res.n_groups == len(info.crafted) + info.others, "two different texts with one tag were merged, or one text was split"
+    texts = [t for _, _, t in judged(st)]
+    by_text = {texts[b]: c for b, c in zip(r.first[: r.res.n_groups].tolist(), r.count.tolist()) if not _raw(st, b)}
+    assert {t: by_text.get(t) for t in info.crafted} == info.copies
+    check_group(run_group(ctx, st.cb, dev, st.n, r.res.n_groups, count_only=True), st)
+
+
+def test_take_of_the_first_rows_of_one_hash_is_the_key_set_the_join_numbers_the_groups_by(ctx):
+    """test_take_of_the_first_rows_is_the_key_set_the_join_numbers_the_groups_by on the store of 32 texts with ONE 64-bit hash: the taken
+    key set holds every one of them, and the join gives each record its group although every probe passes slots of its own tag.  The
+    failed record has no row; the record kept raw is taken as it is and, as a key and as a record, equals nothing."""
+    import torch
+
+    st, info = collide_store("one_hash")
+    first, counts, group_of = want_group(st)
+    dev = upload(st)
+    r = group(ctx, st, dev=dev)
+    g = r.res.n_groups
+    d_keys = torch.full((st.bodies.size + TAIL,), SENTINEL, dtype=torch.uint8, device="cuda")
+    d_key_body_index, d_key_text_index = (torch.full((g + 1,), -1, dtype=torch.int64, device="cuda") for _ in range(2))
+    t = ctx.take_packed_device(*dev, r.d_first[:g], d_keys[: st.bodies.size], d_key_body_index, d_key_text_index)
+    assert (t.status, t.n_failed) == (OK, 0)
+    kdev = (d_keys[: max(t.out_bytes, 1)], d_key_body_index, d_key_text_index)
+    j = run_join(ctx, st.cb, dev, st.n, kdev, g, 0, st.n)
+    rows = [b for b in range(st.n) if group_of[b] != NONE and not _raw(st, b)]
+    assert rows == [b for b in range(st.n) if b not in (info.failed, info.raw)]
+    assert (j.res.status, j.res.n_match, j.res.n_failed, j.res.first_failed, j.res.n_keys_failed) == (OK, len(rows), 1, info.failed, 0)
+    assert j.rows[: len(rows)].tolist() == rows and j.keys[: len(rows)].tolist() == [group_of[b] for b in rows] == [int(r.group_of[b]) for b in rows]
 
 
 # --- 3. long bodies -------------------------------------------------------------------------------------------------------------------

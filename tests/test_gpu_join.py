@@ -7,7 +7,10 @@ exception is the hand-made-body fixture, where the documented byte rule IS the e
 first; everything behind n_match must still hold them.
 
 The stores and key sets are made by the *_fixture functions below, without a GPU: tests/test_join_host.py checks on the same fixtures
-that the byte rule selects what membership selects, and that they reach the cases named here."""
+that the byte rule selects what membership selects, and that they reach the cases named here.  The fixtures: hash (hand-made bodies for
+the device's hash), edges, trap, near, collisions (one home slot, tags that differ), duplicates, minmax, long, failures, handmade, mixed,
+family -- and collide_one_tag, collide_one_hash, collide_sizes, collide_wave: texts made with tests/hashcraft.py whose hash tags, or
+whole hashes, are equal by construction, the only ones in which a tag hit is confirmed between two DIFFERENT texts."""
 import ctypes
 import functools
 from types import SimpleNamespace
@@ -15,7 +18,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from tests import corpus
+from tests import corpus, hashcraft
 from tests.test_gpu_batch import SENTINEL, _small_max, _u8
 from tests.test_gpu_gather import _mixed_store, dev_rows, make_store, upload, want_rows  # noqa: F401  (want_rows, want_decode: through judged)
 from tests.test_gpu_match import EQUAL, HEAD_BITS, PREFIX, ROW_SENTINEL, _pack, _store, judged, pattern_bits, run_match, want_match
@@ -341,8 +344,148 @@ def mixed_fixture():
     return st, _store(st.tab, texts)
 
 
+# --- hash tags that collide by construction (tests/hashcraft.py): the only fixtures in which the confirmation of a tag hit says "different" ----
+# All under table_2bit, where every string of 8 k bytes is the encoder's own body of 32 k symbols.  A *_craft function makes the texts --
+# .keys: those the key set holds, .strangers: those the store holds beside them and that equal no key, .hashes: text -> the hash it was
+# made for --, collide_fixture puts them among fillers.  The expectations stay want_join's: a dict over (length, text).
+
+LOW_BITS = 12  # the crafted hashes agree in their low 12 bits: one home slot under every table of up to 4 096 slots
+CRAFT_RECORDS = 2 * TILE + 120  # three tiles, the last one partial
+CRAFT_KEYS = 56  # a table of 256 slots
+CRAFTED = ("one_tag", "one_hash", "sizes", "wave")
+
+
+def _word(rng):
+    return int(rng.integers(0, 1 << 64, dtype=np.uint64))
+
+
+def _crafted(length, words):
+    """The text of `length` symbols whose body is these full words; the encoder packs it back into exactly them."""
+    body = hashcraft.body_of(words)
+    text = hashcraft.text_2bit(body, length)
+    assert bytes(_pack(table_2bit(), text)) == body
+    return text
+
+
+@functools.lru_cache(maxsize=None)
+def one_tag_craft():
+    """16 one-word texts (8 bytes, 32 symbols) whose hashes share the upper 32 bits -- the tag -- and the low 12 bits -- the home slot --
+    and differ between them: a slot that holds one of them is passed by no tag test, only by the comparison of the bytes.  8 are keys."""
+    rng = np.random.default_rng(0x10A5EB00)
+    tag, low = int(rng.integers(1, 1 << 32)), int(rng.integers(0, 1 << LOW_BITS))
+    mids = rng.choice(1 << (32 - LOW_BITS), size=16, replace=False)
+    hashes = [tag << 32 | int(m) << LOW_BITS | low for m in mids]
+    texts = [_crafted(32, [hashcraft.solve_word([], [], h, 8, 32)]) for h in hashes]
+    return SimpleNamespace(tag=tag, low=low, hashes=dict(zip(texts, hashes)), keys=texts[:8], strangers=texts[8:], twice=None)
+
+
+@functools.lru_cache(maxsize=None)
+def one_hash_craft():
+    """32 different two-word texts (16 bytes, 64 symbols) with ONE 64-bit hash, whose low 12 bits are 4 096 - 5: the home slot lies 5
+    below the end of every table of up to 4 096 slots, so the chain wraps.  16 are keys, and key 5's text is a key twice."""
+    rng = np.random.default_rng(0x10A5EB10)
+    h = (_word(rng) & ~((1 << LOW_BITS) - 1)) | ((1 << LOW_BITS) - 5)
+    firsts = []
+    while len(firsts) < 32:
+        w = _word(rng)
+        if w not in firsts:
+            firsts.append(w)
+    texts = [_crafted(64, [w, hashcraft.solve_word([w], [], h, 16, 64)]) for w in firsts]
+    return SimpleNamespace(h=h, hashes={t: h for t in texts}, keys=texts[:16], strangers=texts[16:], twice=texts[5])
+
+
+@functools.lru_cache(maxsize=None)
+def sizes_craft():
+    """One 64-bit hash under other sizes: 8 bytes under 32 symbols, 8 bytes under 31 (the solved word's last symbol must be an A, which
+    it is for a quarter of the hashes tried) and 16 bytes under 64 -- the three keys.  The strangers: a second 16-byte text and an 8-byte
+    text under 30 symbols with that same hash; and, because a one-word body is determined by its hash, length and byte count -- no second
+    one exists --, for 8 bytes under 32 and under 31 symbols a text each whose hash has the keys' tag and low 12 bits."""
+    rng = np.random.default_rng(0x10A5EB20)
+    while True:
+        h = _word(rng)
+        w31, w30 = hashcraft.solve_word([], [], h, 8, 31), hashcraft.solve_word([], [], h, 8, 30)
+        if (w31 >> 56) & 3 == 0 and (w30 >> 56) & 15 == 0:  # (the symbols behind the length lie in the low bits of byte 7)
+            break
+    a, b, d = _crafted(32, [hashcraft.solve_word([], [], h, 8, 32)]), _crafted(31, [w31]), _crafted(30, [w30])
+    c = [_crafted(64, [w, hashcraft.solve_word([w], [], h, 16, 64)]) for w in (_word(rng), _word(rng))]
+    mid = (1 << 32) - (1 << LOW_BITS)
+    while True:
+        h2 = h ^ (int(rng.integers(1, 1 << (32 - LOW_BITS))) << LOW_BITS)
+        w31 = hashcraft.solve_word([], [], h2, 8, 31)
+        if (w31 >> 56) & 3 == 0:
+            break
+    assert h2 != h and (h2 ^ h) & ~mid == 0
+    a2, b2 = _crafted(32, [hashcraft.solve_word([], [], h2, 8, 32)]), _crafted(31, [w31])
+    return SimpleNamespace(h=h, h2=h2, hashes={a: h, b: h, d: h, c[0]: h, c[1]: h, a2: h2, b2: h2}, keys=[a, b, c[0]], strangers=[c[1], d, a2, b2], twice=None)
+
+
+@functools.lru_cache(maxsize=None)
+def wave_craft():
+    """Bodies above LANE_BYTES, all with ONE 64-bit hash.  17 words (136 bytes: one step of the wavefront): a pair that differs in word
+    0 and the solved last word.  66 words (528 bytes: past one WAVE_STEP): such a pair, and three texts whose first 512 bytes are equal
+    and that differ only in words 64 and 65, so that the second trip decides.  Of each pair one is a key and one a stranger; of the three,
+    two are keys.  Two lane-sized texts (16 bytes) with that hash as well: a key beside the wave-sized strangers, a stranger beside the
+    wave-sized keys."""
+    rng = np.random.default_rng(0x10A5EB30)
+    h = _word(rng)
+
+    def solved(words, n):
+        return _crafted(32 * n, words + [hashcraft.solve_word(words, [], h, 8 * n, 32 * n)])
+
+    short, long_, stem = [_word(rng) for _ in range(16)], [_word(rng) for _ in range(65)], [_word(rng) for _ in range(64)]
+    a = [solved(short, 17), solved([short[0] ^ 1] + short[1:], 17)]
+    b = [solved(long_, 66), solved([long_[0] ^ (1 << 63)] + long_[1:], 66)]
+    c = [solved(stem + [w], 66) for w in (5, 6, 1 << 40)]
+    lanes = [solved([_word(rng)], 2) for _ in range(2)]
+    texts = a + b + c + lanes
+    return SimpleNamespace(h=h, hashes={t: h for t in texts}, keys=[a[0], b[0], c[0], c[2], lanes[0]], strangers=[a[1], b[1], c[1], lanes[1]], twice=None, a=a, b=b, c=c, lanes=lanes)
+
+
+CRAFTS = {"one_tag": one_tag_craft, "one_hash": one_hash_craft, "sizes": sizes_craft, "wave": wave_craft}
+
+
+def acgt_texts(rng, n, avoid=()):
+    """n different random texts of 9 .. 40 symbols over ACGT, none of them in `avoid`: the fillers."""
+    letters, out, seen = np.frombuffer(b"ACGT", np.uint8), [], set(avoid)
+    while len(out) < n:
+        t = letters[rng.integers(0, 4, size=int(rng.integers(9, 41)))].tobytes()
+        if t not in seen:
+            seen.add(t)
+            out.append(t)
+    return out
+
+
+def spread(rng, n, placed, fillers):
+    """n texts: every (tile, text) of `placed` at a random place of that tile of 256, the fillers in order at the other places."""
+    free = [[int(i) for i in rng.permutation(np.arange(t * TILE, min((t + 1) * TILE, n)))] for t in range((n + TILE - 1) // TILE)]
+    texts = [None] * n
+    for tile, t in placed:
+        texts[free[tile].pop()] = t
+    rest = iter(fillers)
+    return [t if t is not None else next(rest) for t in texts]
+
+
+@functools.lru_cache(maxsize=None)
+def collide_fixture(name):
+    """-> (store, key set, the craft).  56 keys -- a table of 256 slots --: the craft's keys (and the one that occurs twice) at scattered
+    numbers among fillers.  632 records: every crafted key and stranger, dealt over the three tiles in turn so that colliders lie in
+    different wavefronts and workgroups, 20 of the filler keys' texts, and fillers that are no key."""
+    c = CRAFTS[name]()
+    tab = table_2bit()
+    rng = np.random.default_rng(0x10A5EC00 + CRAFTED.index(name))
+    key_texts = list(c.keys) + ([c.twice] if c.twice else [])
+    fill = acgt_texts(rng, CRAFT_KEYS - len(key_texts) + CRAFT_RECORDS, avoid=c.hashes)
+    key_fill, fill = fill[: CRAFT_KEYS - len(key_texts)], fill[CRAFT_KEYS - len(key_texts) :]
+    keys = [None] * CRAFT_KEYS
+    for t, k in zip(key_texts + key_fill, rng.permutation(CRAFT_KEYS)):
+        keys[int(k)] = t
+    placed = [(i % 3, t) for i, t in enumerate(list(c.keys) + list(c.strangers))]
+    records = spread(rng, CRAFT_RECORDS, placed, key_fill[:20] + fill[: CRAFT_RECORDS - len(placed) - 20])
+    return _store(tab, records), _store(tab, keys), c
+
+
 FIXTURES = {"trap": trap_fixture, "near": near_fixture, "collisions": lambda: collisions_fixture()[:2], "duplicates": lambda: duplicates_fixture()[:2], "minmax": minmax_fixture,
-            "long": long_fixture, "failures": failures_fixture, "mixed": mixed_fixture,
+            "long": long_fixture, "failures": failures_fixture, "mixed": mixed_fixture, **{f"collide_{name}": (lambda name=name: collide_fixture(name)[:2]) for name in CRAFTED},
             **{f"edges_{n}_{nk}": (lambda n=n, nk=nk: (edges_fixture(n)[0], edges_fixture(n)[1][nk])) for n in (1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 2 * TILE + 1) for nk in (1, 2, 255, 257)}}
 
 
@@ -406,6 +549,62 @@ def test_a_chain_of_32_keys_with_one_home_slot_that_wraps(ctx):
     texts = [t for _, _, t in judged(st)]
     selected = {texts[b] for b in r.rows[: r.res.n_match].tolist()}
     assert set(info.colliders) <= selected and info.inside not in selected and info.inside in texts
+
+
+def device_hashes(ctx, st):
+    """et_selftest_join_hash over a store -> one uint64 per record; all ones where the call left the sentinel."""
+    import torch
+
+    from entreepy_amd import _native as N
+
+    d_bodies, d_body_index, d_text_index = upload(st)
+    d_hash = torch.full((st.n + 8,), -1, dtype=torch.int64, device="cuda")
+    assert N.lib().et_selftest_join_hash(ctx._h, d_bodies.data_ptr(), d_bodies.numel(), d_body_index.data_ptr(), d_text_index.data_ptr(), st.n, d_hash.data_ptr()) == OK
+    got = d_hash.cpu().numpy().view(np.uint64)
+    assert bool((got[st.n :] == np.uint64(0xFFFFFFFFFFFFFFFF)).all())
+    return got[: st.n].tolist()
+
+
+def check_crafted_hashes(ctx, st, hashes):
+    """The device gives every valid record the hash of its definition, and every crafted text the hash it was made for -> how many
+    crafted records that were.  Without this a fixture could fail to collide on the device and its tests pass for the wrong reason."""
+    got, blob, crafted = device_hashes(ctx, st), st.bodies.tobytes(), 0
+    for b, (status, length, text) in enumerate(judged(st)):
+        if status:
+            assert got[b] == 0xFFFFFFFFFFFFFFFF, b
+            continue
+        assert got[b] == hashcraft.hash_of(blob[int(st.body_index[b]) : int(st.body_index[b + 1])], length), b
+        if text in hashes and not _raw(st, b):
+            assert got[b] == hashes[text], b
+            crafted += 1
+    return crafted
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_the_device_gives_every_crafted_record_and_key_the_crafted_hash(ctx, name):
+    st, ks, c = collide_fixture(name)
+    assert check_crafted_hashes(ctx, st, c.hashes) == len(c.keys) + len(c.strangers)
+    assert check_crafted_hashes(ctx, ks, c.hashes) == len(c.keys) + (c.twice is not None)
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_texts_whose_tags_collide_by_construction_are_told_apart_by_their_bytes(ctx, name):
+    """Both modes, three times with identical arrays (the order of the inserts races), and count-only: every crafted key's text is found
+    under the first number of that text, every stranger -- same tag, same home slot or same whole hash -- is unmatched."""
+    st, ks, c = collide_fixture(name)
+    dev, kdev = upload(st), upload(ks)
+    texts, key_texts = [t for _, _, t in judged(st)], [t for _, _, t in judged(ks)]
+    runs = [both_modes(ctx, st, ks, dev=dev, kdev=kdev) for _ in range(3)]
+    (r, rn) = runs[0]
+    for again, again_not in runs[1:]:
+        assert np.array_equal(again.rows, r.rows) and np.array_equal(again.keys, r.keys) and again.res == r.res
+        assert np.array_equal(again_not.rows, rn.rows) and again_not.res == rn.res
+    got = dict(zip((texts[b] for b in r.rows[: r.res.n_match].tolist()), r.keys.tolist()))
+    unmatched = {texts[b] for b in rn.rows[: rn.res.n_match].tolist()}
+    assert [got.get(t) for t in c.keys] == [key_texts.index(t) for t in c.keys], "a crafted key's text is not found under its first number"
+    assert all(t not in got and t in unmatched for t in c.strangers), "a text that is no key was matched by one with its tag"
+    for mode in (0, NOT):
+        check_join(run_join(ctx, st.cb, dev, st.n, kdev, ks.n, mode, len(want_join(st, ks, mode)[0]), count_only=True), st, ks, mode)
 
 
 # --- 5. duplicates -------------------------------------------------------------------------------------------------------------------

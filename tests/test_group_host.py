@@ -1,6 +1,8 @@
 """et_group_packed_device as far as it can be checked without a GPU: declared, bound, exported, the result struct's size; and, in pure
 Python with the oracle, that on the stores of tests/test_gpu_group.py the byte rule the kernels implement gives the partition that dict
-membership over the oracle's texts gives, and that those fixtures reach the cases the GPU tests name."""
+membership over the oracle's texts gives, and that those fixtures reach the cases the GPU tests name.  For the stores whose hash tags
+collide by construction (tests/hashcraft.py): that they collide under the group's own table, and that a model of the table which confirms
+a tag hit by less than length, byte count and all bytes gives another partition -- tests/test_join_host.py's model, over the store itself."""
 import ctypes
 import os
 import re
@@ -12,8 +14,10 @@ import pytest
 import entreepy_amd as E
 from entreepy_amd import _native as N
 from tests.test_gpu_gather import make_store, upload, want_rows  # noqa: F401  (the helpers the fixtures are made with)
-from tests.test_gpu_group import COLLIDERS, EDGE_SIZES, NONE, STORES, chain_fixture, counting_fixture, csv_fixture, edges_fixture, failures_fixture, long_store, near_stores, want_group
-from tests.test_gpu_join import LANE_BYTES, TILE, _raw, handmade_fixture, host_hash, table_slots
+from tests import hashcraft
+from tests.test_gpu_group import COLLIDERS, EDGE_SIZES, NONE, STORES, chain_fixture, collide_store, counting_fixture, csv_fixture, edges_fixture, failures_fixture, long_store, near_stores, want_group
+from tests.test_gpu_join import CRAFT_RECORDS, CRAFTED, LANE_BYTES, LOW_BITS, TILE, _raw, handmade_fixture, host_hash, table_slots
+from tests.test_join_host import CATCHES, CONFIRM, TableModel, items_of, orders
 from tests.test_gpu_match import judged
 from tests.test_gpu_shared import want_decode  # noqa: F401
 
@@ -154,3 +158,58 @@ def test_the_group_call_has_a_row_that_keeps_both_states():
     assert NAME in row.calls and NAME in N.SIGNATURES and (row.hist, row.held, row.names, row.encodes) == (R.KEEPS, R.KEEPS, None, None)
     assert "group" not in R.DROPS_HISTOGRAM | R.DROPS_RANGE
     assert len(set(R.RECORDS)) == len(R.RECORDS) == 5  # (the row's store is RECORDS twice: five groups of two)
+
+
+# --- hash tags that collide by construction (tests/hashcraft.py) ----------------------------------------------------------------------
+
+
+def model_group(st, order, confirm):
+    """want_group(st) as the hash table gives it (tests/test_join_host.py's TableModel over the store itself): a record's representative
+    is the number in the first confirmed slot of its probe sequence, a group's number the rank of its representative."""
+    items = items_of(st)
+    table = TableModel(items, order, CONFIRM[confirm])
+    reps = []
+    for b, (status, _, _) in enumerate(judged(st)):
+        reps.append(NONE if status else b if items[b] is None else table.find(items[b], own=b))
+    first = [b for b, r in enumerate(reps) if r == b]
+    rank = {b: g for g, b in enumerate(first)}
+    return first, [reps.count(b) for b in first], [NONE if r == NONE else rank.get(r, NONE) for r in reps]
+
+
+def test_the_crafted_stores_collide_under_the_groups_own_table():
+    low = (1 << LOW_BITS) - 1
+    for name in CRAFTED:
+        st, info = collide_store(name)
+        slots = table_slots(st.n)
+        assert st.n == CRAFT_RECORDS and 256 < slots <= 1 << LOW_BITS, "the crafted homes are equal under the group's mask too"
+        texts, statuses = [t for _, _, t in judged(st)], [s for s, _, _ in judged(st)]
+        assert info.crafted == list(info.craft.keys) + list(info.craft.strangers) and len(set(info.crafted)) == len(info.crafted)
+        for t in info.crafted:
+            places = [b for b, u in enumerate(texts) if u == t]
+            assert len(places) == info.copies[t] in (2, 3) and len({b // TILE for b in places}) == len(places), "every copy in another tile"
+            assert all(host_hash(st.bodies[int(st.body_index[b]) : int(st.body_index[b + 1])], len(t)) == info.craft.hashes[t] for b in places)
+        assert {2, 3} == set(info.copies.values())
+        assert [b for b, s in enumerate(statuses) if s] == [info.failed] and statuses[info.failed] == ARG and TILE < info.failed < 2 * TILE
+        assert [b for b in range(st.n) if _raw(st, b)] == [info.raw] and info.raw >= 2 * TILE
+        first, counts, group_of = want_group(st)
+        assert len(first) == len(info.crafted) + info.others and sorted(counts) == [1] * info.others + sorted(info.copies.values())
+        for b, item in enumerate(items_of(st)):
+            if item is not None:
+                assert hashcraft.hash_of(item[1], item[0]) == host_hash(item[1], item[0])
+    hashes = list(collide_store("one_tag")[1].craft.hashes.values())
+    mask = table_slots(CRAFT_RECORDS) - 1
+    assert len({h >> 32 for h in hashes}) == 1 and len({h & mask for h in hashes}) == 1 and len({h & 0xFFFFFFFF & ~low for h in hashes}) == len(hashes)
+    h = collide_store("one_hash")[1].craft.h
+    assert (h & mask) + 5 == mask + 1  # the chain of 32 wraps here as well
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_a_table_that_confirms_a_tag_hit_by_less_groups_wrongly(name):
+    """tests/test_join_host.py's test of that name for the group call: the full confirmation gives the dict's partition in every
+    insertion order, each weakening a different one on the fixtures CATCHES names."""
+    st, _ = collide_store(name)
+    want = want_group(st)
+    for order in orders(st.n):
+        assert model_group(st, order, "full") == want
+        for weak, caught in CATCHES.items():
+            assert (model_group(st, order, weak) != want) == (name in caught), (weak, name)

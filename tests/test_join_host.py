@@ -2,7 +2,9 @@
 against the definition in csrc/et_join.h written out in Python -- for every division of a body's words into two groups and every
 alignment of the buffer --; et_join_table_slots; and, in pure Python with the oracle, that on the stores and key sets of
 tests/test_gpu_join.py the byte rule the kernels implement selects the rows dict membership over the texts selects, and that those
-fixtures reach the cases the GPU tests name."""
+fixtures reach the cases the GPU tests name.  For the fixtures whose hash tags collide by construction (tests/hashcraft.py): that
+hashcraft's hash is the library's, that every crafted pair collides as its docstring claims, and that a model of the hash table which
+confirms a tag hit by less than length, byte count and ALL bytes answers wrongly on a named fixture -- so the fixtures can fail."""
 import ctypes
 import os
 import re
@@ -14,9 +16,10 @@ import pytest
 import entreepy_amd as E
 from entreepy_amd import _native as N
 from tests.test_gpu_gather import make_store, upload, want_rows  # noqa: F401  (the helpers the fixtures are made with)
-from tests.test_gpu_join import COLLIDERS, FIXTURES, LANE_BYTES, NOT, WAVE_STEP, _raw, collisions_fixture, duplicates_fixture, handmade_fixture, hash_fixture, host_hash, \
-    table_slots, trap_fixture, want_join
-from tests.test_gpu_match import judged
+from tests import hashcraft
+from tests.test_gpu_join import COLLIDERS, CRAFT_KEYS, CRAFT_RECORDS, CRAFTED, FIXTURES, LANE_BYTES, LOW_BITS, NOT, TILE, WAVE_STEP, _raw, collide_fixture, collisions_fixture, \
+    duplicates_fixture, handmade_fixture, hash_fixture, host_hash, table_slots, trap_fixture, want_join
+from tests.test_gpu_match import _pack, judged
 from tests.test_gpu_shared import _length_batch, want_decode  # noqa: F401
 from tests.test_shared_host import table_2bit
 
@@ -172,3 +175,183 @@ def test_the_fixtures_reach_the_cases_the_gpu_tests_name():
     # failures: a body of no bytes under a length above zero on both sides, with the same length
     st, ks = FIXTURES["failures"]()
     assert _raw(st, 5) and _raw(ks, 2) and 5 in want_join(st, ks, NOT)[0]
+
+
+# --- hash tags that collide by construction (tests/hashcraft.py) --------------------------------------------------------------------
+
+
+def body_of(text):
+    return bytes(_pack(table_2bit(), text)) if len(text) else b""
+
+
+def items_of(s):
+    """Per record (length, body bytes) -- what the kernels hash and compare --, or None where the record fails or is kept raw."""
+    blob = s.bodies.tobytes()
+    return [None if status or _raw(s, b) else (int(s.text_index[b + 1]) - int(s.text_index[b]), blob[int(s.body_index[b]) : int(s.body_index[b + 1])])
+            for b, (status, _, _) in enumerate(judged(s))]
+
+
+def _sizes(a, b):
+    return a[0] == b[0] and len(a[1]) == len(b[1])
+
+
+# How a tag hit is confirmed: in full, as csrc/et_join.h demands, and the three weakenings a build could have.
+CONFIRM = {"full": lambda a, b: a == b, "tag": lambda a, b: True, "sizes": _sizes, "first512": lambda a, b: _sizes(a, b) and a[1][:WAVE_STEP] == b[1][:WAVE_STEP]}
+
+
+class TableModel:
+    """The kernels' hash table, one step at a time: linear probing from hash & mask, a slot holds tag << 32 | number, an insert that
+    meets a confirmed slot of its tag leaves the lower number there, a probe ends at the first empty slot."""
+
+    def __init__(self, items, order, confirm):
+        self.items, self.confirm, self.slots = items, confirm, table_slots(len(items))
+        self.table = [None] * self.slots
+        for k in order:
+            if items[k] is not None:
+                self.insert(k)
+
+    def chain(self, item):
+        h = hashcraft.hash_of(item[1], item[0])
+        return h >> 32, ((h + i) & (self.slots - 1) for i in range(self.slots))
+
+    def insert(self, k):
+        tag, places = self.chain(self.items[k])
+        for pos in places:
+            old = self.table[pos]
+            if old is None:
+                self.table[pos] = tag << 32 | k
+                return
+            if old >> 32 == tag and self.confirm(self.items[k], self.items[old & 0xFFFFFFFF]):
+                self.table[pos] = min(old, tag << 32 | k)
+                return
+        raise AssertionError("the table is full")
+
+    def find(self, item, own=None):
+        """The number in the first confirmed slot, or None at an empty one.  own: the group's probe, which takes a slot that holds the
+        record's own number without a look at the bytes."""
+        tag, places = self.chain(item)
+        for pos in places:
+            slot = self.table[pos]
+            if slot is None:
+                return None
+            if slot >> 32 == tag and (slot & 0xFFFFFFFF == own or self.confirm(item, self.items[slot & 0xFFFFFFFF])):
+                return slot & 0xFFFFFFFF
+        raise AssertionError("no empty slot")
+
+
+def orders(n):
+    """Insertion orders to try: the identity, the reverse and three shuffles."""
+    rng = np.random.default_rng(0x10A5ED00 + n)
+    return [list(range(n)), list(reversed(range(n)))] + [[int(i) for i in rng.permutation(n)] for _ in range(3)]
+
+
+def model_join(st, ks, order, confirm):
+    """want_join(st, ks, 0) as the table gives it, the [min, max] filter of the keys' body sizes included."""
+    table = TableModel(items_of(ks), order, CONFIRM[confirm])
+    sizes = [len(item[1]) for item in table.items if item is not None]
+    rows, keys = [], []
+    for b, item in enumerate(items_of(st)):
+        k = table.find(item) if item is not None and min(sizes) <= len(item[1]) <= max(sizes) else None
+        if k is not None:
+            rows.append(b)
+            keys.append(k)
+    return rows, keys
+
+
+# Which fixture a weakened confirmation answers wrongly on, in every insertion order; on the others it answers as the dict does.
+CATCHES = {"tag": {"one_tag", "one_hash", "sizes", "wave"}, "sizes": {"one_tag", "one_hash", "sizes", "wave"}, "first512": {"wave"}}
+
+
+def test_hashcraft_restates_the_librarys_hash_and_inverts_it():
+    rng = np.random.default_rng(0x10A5ED10)
+    for x in [0, 1, hashcraft.M64, hashcraft.STEP] + [int(v) for v in rng.integers(0, 1 << 64, size=200, dtype=np.uint64)]:
+        assert hashcraft.unmix(hashcraft.mix(x)) == x == hashcraft.mix(hashcraft.unmix(x)) and hashcraft.mix(x) == _mix(x)
+    stores = [hash_fixture()[0]] + [s for name in CRAFTED for s in collide_fixture(name)[:2]]
+    for st in stores:
+        blob = st.bodies.tobytes()
+        for a, b, n in zip(st.body_index[:-1], st.body_index[1:], np.diff(st.text_index)):
+            assert hashcraft.hash_of(blob[int(a) : int(b)], int(n)) == host_hash(blob[int(a) : int(b)], int(n))
+    for name in CRAFTED:
+        for text, h in collide_fixture(name)[2].hashes.items():
+            assert host_hash(body_of(text), len(text)) == h, name
+    # the solved word at every place of a body, its last word partial or not
+    for n_bytes in (8, 16, 21, 24, 136, 529):
+        words = hashcraft.words_of(rng.integers(0, 256, size=n_bytes).astype(np.uint8).tobytes())
+        for i in range(n_bytes // 8):
+            h, length = int(rng.integers(0, 1 << 64, dtype=np.uint64)), int(rng.integers(0, 1 << 18))
+            w = hashcraft.solve_word(words[:i], words[i + 1 :], h, n_bytes, length)
+            body = hashcraft.body_of(words[:i] + [w] + words[i + 1 :])[:n_bytes]
+            assert host_hash(body, length) == h
+
+
+def _differing_words(a, b):
+    wa, wb = hashcraft.words_of(body_of(a)), hashcraft.words_of(body_of(b))
+    assert len(wa) == len(wb)
+    return {i for i, (x, y) in enumerate(zip(wa, wb)) if x != y}
+
+
+def _size(text):
+    return len(body_of(text)), len(text)
+
+
+def test_the_crafted_fixtures_collide_as_they_claim():
+    low = (1 << LOW_BITS) - 1
+    for name in CRAFTED:
+        st, ks, c = collide_fixture(name)
+        crafted = list(c.keys) + list(c.strangers)
+        texts, key_texts = [t for _, _, t in judged(st)], [t for _, _, t in judged(ks)]
+        assert (st.n, ks.n, table_slots(ks.n)) == (CRAFT_RECORDS, CRAFT_KEYS, 256) and len(set(crafted)) == len(crafted) == len(c.hashes)
+        assert all(texts.count(t) == 1 for t in crafted) and all(t in key_texts for t in c.keys) and not set(c.strangers) & set(key_texts)
+        for part in (c.keys, c.strangers):
+            assert len({texts.index(t) // TILE for t in part}) == 3 and len({texts.index(t) // 64 for t in part}) >= 3, "colliders in different tiles and wavefronts"
+        assert all(host_hash(body_of(t), len(t)) == c.hashes[t] for t in crafted)
+        rows, keys = want_join(st, ks, 0)
+        assert {texts.index(t) for t in c.keys} <= set(rows) and not {texts.index(t) for t in c.strangers} & set(rows)
+        sizes = [len(item[1]) for item in items_of(ks)]
+        assert all(min(sizes) <= len(item[1]) <= max(sizes) for item in items_of(st)), "the [min, max] filter decides no record"
+    # one tag, one home: equal upper halves, equal low 12 bits -- the home under the key set's 256 slots and the group's 2 048 --, and
+    # a difference between the mask and bit 31; one word each
+    c = collide_fixture("one_tag")[2]
+    hashes = list(c.hashes.values())
+    assert {h >> 32 for h in hashes} == {c.tag} and {h & low for h in hashes} == {c.low} and len({(h >> LOW_BITS) & 0xFFFFF for h in hashes}) == 16
+    assert {_size(t) for t in c.hashes} == {(8, 32)} and len(c.keys) == len(c.strangers) == 8
+    # one full hash: 32 texts of two words, both different in every pair; the home 5 below the table's end, 17 keys from there; one text
+    # a key twice, at numbers apart
+    st, ks, c = collide_fixture("one_hash")
+    key_texts = [t for _, _, t in judged(ks)]
+    assert set(c.hashes.values()) == {c.h} and len(c.hashes) == 32 and {_size(t) for t in c.hashes} == {(16, 64)}
+    assert all(_differing_words(a, b) == {0, 1} for a in c.hashes for b in c.hashes if a != b)
+    assert c.h & 255 == 256 - 5 and sum(t in c.hashes for t in key_texts) == 17 and len(c.keys) == 16
+    twice = [k for k, t in enumerate(key_texts) if t == c.twice]
+    assert len(twice) == 2 and twice[1] - twice[0] > 1 and c.twice in c.keys
+    rows, keys = want_join(st, ks, 0)
+    assert keys[rows.index([t for _, _, t in judged(st)].index(c.twice))] == twice[0]
+    # one hash, other sizes
+    c = collide_fixture("sizes")[2]
+    a, b, c0 = c.keys
+    c1, d, a2, b2 = c.strangers
+    assert [_size(t) for t in (a, b, c0, c1, d, a2, b2)] == [(8, 32), (8, 31), (16, 64), (16, 64), (8, 30), (8, 32), (8, 31)]
+    assert {c.hashes[t] for t in (a, b, c0, c1, d)} == {c.h} and c.hashes[a2] == c.hashes[b2] == c.h2 != c.h
+    assert c.h2 >> 32 == c.h >> 32 and c.h2 & low == c.h & low
+    assert len({body_of(t) for t in (a, b, d, a2, b2)}) == 5 and _differing_words(c0, c1) == {0, 1}
+    # the wavefront path: one step and two; which words differ; lane-sized texts with the same hash on both sides
+    c = collide_fixture("wave")[2]
+    assert set(c.hashes.values()) == {c.h}
+    assert [_size(t) for t in c.a + c.b + c.c + c.lanes] == [(136, 544)] * 2 + [(528, 2112)] * 5 + [(16, 64)] * 2
+    assert 16 <= LANE_BYTES < 136 <= WAVE_STEP < 528 <= 2 * WAVE_STEP
+    assert _differing_words(*c.a) == {0, 16} and _differing_words(*c.b) == {0, 65}
+    assert all(_differing_words(x, y) == {64, 65} and body_of(x)[:WAVE_STEP] == body_of(y)[:WAVE_STEP] for x in c.c for y in c.c if x != y)
+    assert c.keys == [c.a[0], c.b[0], c.c[0], c.c[2], c.lanes[0]] and c.strangers == [c.a[1], c.b[1], c.c[1], c.lanes[1]]
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_a_table_that_confirms_a_tag_hit_by_less_answers_wrongly(name):
+    """The fixture can fail: the table model with the full confirmation gives the dict's answer in every insertion order; confirming by
+    the tag alone, by tag and sizes, by tag, sizes and the first 512 bytes, it answers wrongly on the fixtures CATCHES names."""
+    st, ks, _ = collide_fixture(name)
+    want = want_join(st, ks, 0)
+    for order in orders(ks.n):
+        assert model_join(st, ks, order, "full") == want
+        for weak, caught in CATCHES.items():
+            assert (model_join(st, ks, order, weak) != want) == (name in caught), (weak, name)
+    assert set().union(*CATCHES.values()) == set(CRAFTED) and all(CATCHES.values())
