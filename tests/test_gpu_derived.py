@@ -23,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 PLAN_GRID, LANES, LONG_GRID = 1024, 256, 1024  # csrc/et_batch.h GATHER_PLAN_GRID, csrc/et_batch.hip BB, csrc/et_batch.h SHARED_DEC_GRID
 N_ROWS = PLAN_GRID * LANES + 65  # a second trip of 65 rows: one whole wavefront and one row of the next
+TAKE_GRID, TAKE_TILE_BYTES = 2048, 8192  # csrc/et_batch.h: workgroups of k_take_copy<BITS> and k_concat_copy at most, bytes of output per tile
 SPACE = ord(" ")
 
 
@@ -77,6 +78,10 @@ def test_rows_past_one_plan_grid_and_listed_rows_past_one_long_grid(ctx, family)
     cycle_want = one()
     assert cycle_want.status.tolist() == [0, 0, 0, 0, 6] and int(np.diff(cycle_want.text_index)[1]) > 0  # (the long row gives something; ET_ERR_ARG beyond the store)
     want = tiled(cycle_want, N_ROWS)
+    # What the copy behind the plan reaches here: more tiles of output than it has workgroups, so that a workgroup copies a run of them
+    # (`per` >= 2, `hint` and the staged index carried from tile to tile) -- but for the field, whose rows are a few bytes each and
+    # whose output stays within one tile per workgroup (k_take_copy<true> past its grid is the slice's case; tests/test_gpu_strides.py has <false>).
+    assert (want.total > TAKE_GRID * TAKE_TILE_BYTES) == (family != "field")
     for sizes_only in (False, True):
         r = check(run(ctx, want.total, sizes_only), want)
         assert (r.res.n_failed, r.res.first_failed, r.res.first_status) == (int((rows == cycle[-1]).sum()), 4, 6)
